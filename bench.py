@@ -12,17 +12,21 @@ rows, which is resident in HBM when the timed region starts (generated on the de
   global read range (`dist.shard_range`), no data-path collective, ONE int64[11] all-reduce of the
   call histogram per step through the C ABI's RCCL communicator (`wdx_reduce_counts`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR] [--full]
 
 With `--gpus N` (N>1) and no torchrun environment this process starts the N ranks itself
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py`) BEFORE anything touches the GPU
 and forwards the ranks' output; under torchrun it is one rank.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed on the launch stream), `cpu_baseline` (the CPU oracle -- a port of the reference's
-CPU path -- timed on this host on a bounded sample of the same reads, which doubles as the parity
-gate) and, at N=1, `secondary` (the shipped-model DTW regime, host-buffer minibatches, live ticks
-and DTW_SVM.predict, each with its own parity check).
+Rank 0 prints ONE JSON line: `metric`, `value` (reads/s over the K timed steps), `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` and the workload's configuration.  A plain run does nothing else: set-up, W warm-up
+steps, K timed steps, the outputs of the last step if `--dump-outputs DIR` asks for them, the line.
+
+`--full` adds to the line what takes work of its own: `roofline` (dominant kernel, HIP-event timed on the
+launch stream) and the per-kernel times, the calls' accuracy against the generator's barcodes,
+`cpu_baseline` (the CPU oracle -- a port of the reference's CPU path -- timed on this host on a bounded
+sample of the same reads, which doubles as the parity gate) and, at N=1, `secondary` (the shipped-model
+DTW regime, host-buffer minibatches, live ticks and DTW_SVM.predict, each with its own parity check).
 """
 from __future__ import annotations
 
@@ -53,13 +57,20 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (default: C3 = 10 M at N=1, C4 = 5 M at N>1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy (float32 / float64): "
+                         "the call histogram whole, status / call / distances of a fixed, seeded sample of rank 0's reads "
+                         "and their read indices")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel times and roofline, call accuracy, the CPU baseline + parity gate and (N=1) the "
+                         "secondary regimes")
     ap.add_argument("--cpu-seconds", type=float, default=33.0,
-                    help="time budget of the CPU baseline / parity gate (oracle on all host cores)")
+                    help="--full: time budget of the CPU baseline / parity gate (oracle on all host cores)")
     ap.add_argument("--parity-reads", type=int, default=1_000_000,
-                    help="upper bound of reads verified against the oracle inside the time budget; a run with "
+                    help="--full: upper bound of reads verified against the oracle inside the time budget; a run with "
                          "--cpu-seconds 0 verifies exactly this many")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline / parity gate")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary regimes")
     ap.add_argument("--leg", default="", help="run ONE secondary leg alone and print its JSON (shipped_model_e2e)")
     ap.add_argument("--ctx-opt", action="append", default=[], metavar="ID=VALUE",
                     help="diagnostic: wdx_ctx_set_option(ID, VALUE) on the bench context (experiments only; the line "
@@ -616,7 +627,9 @@ def secondary_regimes(device):
     # packed staging, only the windows cross the bus; feeder: ONE GPU-facing process, P producer processes fill a shared
     # page-locked ring -- always with the producers' own 40 MB fill per minibatch, like "pipe refill")
     # (most telling first: the leg stops launching once 20 s are spent and says which configurations it skipped)
-    for mode, refill, P, jit in (("feeder", False, 16, 0), ("sync", False, 16, 0), ("sync", False, 4, 0), ("pipe", False, 1, 2900),
+    # (sync: every worker opens a context of its own, and this process holds one too -- 15 workers keep the processes
+    # with the GPU open at 16)
+    for mode, refill, P, jit in (("feeder", False, 16, 0), ("sync", False, 15, 0), ("sync", False, 4, 0), ("pipe", False, 1, 2900),
                                  ("feeder", True, 16, 2900), ("feeder_full", False, 16, 0), ("feeder", False, 4, 0)):
         key = "%s%s%s_P%d" % (mode, "_refill" if refill else "", "_jitter" if jit else "", P)
         cmd = [sys.executable, os.path.join(ROOT, "tools", "host_workers.py"), "--workers", str(P), "--mode", mode,
@@ -863,6 +876,168 @@ def make_refs(spec_clean, synth, sig_proc, device=None, n_barcodes=None):
     return fb.fpt
 
 
+DUMP_READS = 1 << 20   # per-read outputs dumped: 2^20 reads x (10 distances + status + call) float32 + index float64 = 58.7 MB
+
+
+def dump_outputs(path, res, first_read):
+    """What the last timed step handed its caller, as .npy files under `path`: the all-reduced call histogram whole;
+    status, call and the distance rows of a fixed, seeded sample of DUMP_READS reads of this shard (every read of a
+    smaller shard), with their global read indices.  The distance rows of failed reads are not defined by the ABI
+    (wdx_demux_dev) and are written as NaN."""
+    import numpy as np
+    import torch
+
+    n = int(res.status.shape[0])
+    idx = np.arange(n) if n <= DUMP_READS else np.sort(np.random.default_rng(0).choice(n, DUMP_READS, replace=False))
+    ti = torch.from_numpy(idx).to(res.status.device)
+    status = res.status[ti].cpu().numpy()
+    dist = res.dist[ti].cpu().numpy()
+    dist[status != 0] = np.nan
+    arrays = {"read_index": (idx + first_read).astype(np.float64), "status": status.astype(np.float32),
+              "call": res.call[ti].cpu().numpy().astype(np.float32), "dist": dist,
+              "counts": res.counts.cpu().numpy().astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def kernel_figures(eng, params, off, a_s, a_e, max_len, n_reads, total_samples, steps, value, world):
+    """--full: the HIP-event times the library recorded around its launches during the timed steps, the roofline of
+    the dominant kernel and the fused path's figures."""
+    import torch
+
+    from warpdemux_amd import _lib
+
+    fp_ms, fp_n = eng.kernel_time(_lib.K_FINGERPRINT)            # the whole fingerprint chain
+    fpm_ms, fpm_n = eng.kernel_time(_lib.K_FINGERPRINT_MAIN)     # its main kernel's launches alone
+    fpc_ms, fpc_n = eng.kernel_time(_lib.K_FINGERPRINT_CLIP)     # clip_bounds_kernel (median / MAD ahead of the main kernel)
+    fpt_ms, fpt_n = eng.kernel_time(_lib.K_FINGERPRINT_TAIL)     # split main kernel: its tail-kernel launches alone (part of MAIN)
+    dtw_ms, dtw_n = eng.kernel_time(_lib.K_DTW)
+    tr_ms, tr_n = eng.kernel_time(_lib.K_TRANSPOSE)
+    cnt_ms, cnt_n = eng.kernel_time(_lib.K_COUNT)
+    red_ms, red_n = eng.kernel_time(_lib.K_REDUCE)
+
+    # ---- roofline of the dominant kernel (algorithmic bytes, DESIGN.md "Measurement") ------------
+    steps = max(steps, 1)
+    fp_bytes = 4.0 * total_samples + 8.0 * K_FPT * n_reads + 4.0 * n_reads
+    dtw_bytes = (8.0 * K_FPT + 4.0 * N_BARCODES + 4.0) * n_reads
+    if fp_ms >= dtw_ms:
+        # The fingerprint stage is a chain of launches (DESIGN.md 4.1): the main kernel takes every read whose adapter
+        # window fits its instantiation and the list kernels the rest.  `achieved` prices the main kernel alone: the
+        # algorithmic bytes of the reads IT completes (window within its capacity; the engine reports the capacity)
+        # over ITS launches' HIP-event time -- the figure rocprofv3's average for that kernel must reproduce.
+        main_cap = 5120 if max_len > 4096 and n_reads >= 2048 else (4096 if max_len <= 4096 else 6144)
+        w_start = torch.clamp(a_s.to(torch.int64) - params.padding, min=0)
+        w_stop = torch.minimum(a_e.to(torch.int64) + params.padding, off[1:] - off[:-1])
+        lens = w_stop - w_start
+        fits = lens <= main_cap
+        main_reads = int(fits.sum().item())
+        main_samples = int(lens[fits].sum().item())
+        main_bytes = 4.0 * main_samples + (8.0 * K_FPT + 4.0) * main_reads
+        dom, dom_ms, dom_n, dom_bytes = "fingerprint_fast_kernel", fpm_ms, fpm_n, main_bytes
+        # Round 6: the main kernel is a PAIR per launch slice -- the workgroup-per-read tile kernel (fingerprint_fast_kernel<...,
+        # SPLIT>: load, clip, t-score tiles, peak list, export of <= 256 peaks with prefix sums) and the wave-per-read tail
+        # kernel (fingerprint_split_tail_kernel: suppression, top-E, boundaries, event means, normalisation, output).  The
+        # MAIN events bracket the pairs, the TAIL events the tail kernel alone; the dominant kernel is the tile kernel, priced
+        # on ITS algorithmic bytes (the samples it reads: 4 N per read -- the fingerprints are the tail kernel's output) over
+        # ITS time (MAIN - TAIL), the figure rocprofv3's average for that kernel must reproduce.
+        split_pair = None
+        if fpt_n > 0 and fpt_ms > 0:
+            split_pair = {"tile_kernel": "fingerprint_fast_kernel<20, false, 12, 1, true, true>", "tail_kernel": "fingerprint_split_tail_kernel<12>",
+                          "launch_pairs": fpm_n, "pair_ms_per_step": fpm_ms / steps, "tail_ms_per_step": fpt_ms / steps,
+                          "tile_ms_per_step": (fpm_ms - fpt_ms) / steps, "avg_tail_launch_ms": fpt_ms / fpt_n,
+                          "pair_algorithmic_bytes_per_step": main_bytes,
+                          "pair_achieved_gbs": main_bytes / (fpm_ms / steps * 1e-3) / 1e9,
+                          "pair_frac": main_bytes / (fpm_ms / steps * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            dom_ms, dom_bytes = fpm_ms - fpt_ms, 4.0 * main_samples
+    else:
+        dom, dom_ms, dom_n, dom_bytes = "dtw_band_kernel<15>", dtw_ms, dtw_n, dtw_bytes
+    launches_per_step = max(dom_n // steps, 1)
+    avg_ms = dom_ms / max(dom_n, 1)
+    dom_bytes = dom_bytes / launches_per_step  # per kernel launch (a step may be sliced)
+    achieved = dom_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    # HBM traffic of that kernel from the PMC passes (profiles/traffic.json, written by
+    # tools/collect_traffic.py on the same workload); null when not collected for this size
+    # NOT measured by this run: PMC counters need rocprofv3 around the process, so these two figures are read from the
+    # committed passes of the same workload and carry their source (file, round) in the line
+    traffic = traffic_src = traffic_parts = None
+    try:
+        with open(os.path.join(ROOT, "profiles", "traffic.json")) as fh:
+            tj = json.load(fh)
+        if tj.get("kernel") == dom and tj.get("reads_per_step") == n_reads:
+            traffic = tj.get("hbm_bytes_per_step") / launches_per_step
+            traffic_parts = {"fetched_per_launch": tj.get("fetch_bytes_per_launch_corrected"), "written_per_launch": tj.get("write_bytes_per_launch"),
+                             "note": "the tile kernel reads each sample once (fetched = 1.02 x its algorithmic bytes); what it writes are the "
+                                     "exported peak lists (<= 4.6 KB per read) that the tail kernel reads back"}
+            traffic_src = {"file": "profiles/traffic.json", "round": tj.get("round"), "collected_by": "tools/collect_traffic.py "
+                           "(separate rocprofv3 --pmc passes of this command; not measured by this run)"}
+    except (OSError, ValueError, TypeError):
+        pass
+    valu_busy = valu_src = None
+    try:
+        with open(os.path.join(ROOT, "profiles", "sq_counters_latest.json")) as fh:
+            sj = json.load(fh)
+        pl = sj["kernels"][dom.split("<")[0]]["per_launch"]
+        valu_busy = pl["SQ_ACTIVE_INST_VALU"] * 4.0 / (1024.0 * pl["GRBM_GUI_ACTIVE"] / 8.0)
+        valu_src = {"file": "profiles/sq_counters_latest.json", "round": sj.get("round"),
+                    "collected_by": "tools/collect_sq.py (rocprofv3 --pmc pass of this command; not measured by this run)"}
+    except (OSError, ValueError, KeyError):
+        pass
+
+    fused_bytes_per_read = 4.0 * total_samples / n_reads + 4.0 * N_BARCODES + 4.0
+    return {
+        "roofline": {
+            "bound": "hbm",
+            "kernel": dom,
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "traffic_parts": traffic_parts,
+            "algorithmic_bytes_per_launch": dom_bytes,
+            "avg_launch_ms": avg_ms,
+            "launches": dom_n,
+            **({"kernel_instantiation": ("fingerprint_fast_kernel<%d, false, 12, 1, true, true> (%d-sample windows; the tile kernel of the split "
+                                         "main pair: algorithmic bytes = the samples it reads)" % (main_cap // 256, main_cap)) if split_pair else
+                                        "fingerprint_fast_kernel<%d, false> (%d-sample windows)" % (main_cap // 256, main_cap),
+                "split_main_pair": split_pair,
+                "reads_per_launch": main_reads / launches_per_step,
+                "share_of_reads": main_reads / n_reads,
+                "stage": {"what": "whole fingerprint chain (clip_bounds_kernel ahead of the main kernel + main kernel + "
+                                  "list kernels for longer windows, peak-list overflows, exact-score retries, the "
+                                  "exact general kernel)",
+                          "ms_per_step": fp_ms / steps,
+                          "algorithmic_gb_per_step": fp_bytes / 1e9,
+                          "achieved_gbs": fp_bytes / (fp_ms / steps * 1e-3) / 1e9 if fp_ms else None},
+                # the launch ahead of the main kernel: one wave per read, the samples of the main kernel's reads once
+                # more from HBM (4 N bytes in, 16 bytes out per read) -- priced like the main kernel, on its own
+                # algorithmic bytes and its own HIP events
+                "clip_bounds_kernel": ({"ms_per_step": fpc_ms / steps, "launches": fpc_n,
+                                        "algorithmic_bytes_per_step": 4.0 * main_samples + 16.0 * n_reads,
+                                        "achieved": (4.0 * main_samples + 16.0 * n_reads) / (fpc_ms / steps * 1e-3) / 1e9,
+                                        "frac": (4.0 * main_samples + 16.0 * n_reads) / (fpc_ms / steps * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                                       if fpc_ms else None)}
+               if dom == "fingerprint_fast_kernel" else {}),
+            # what actually bounds the kernel (float64 VALU issue), from the committed PMC pass
+            "valu_busy_frac": valu_busy,
+            "valu_busy_source": valu_src,
+        },
+        "kernels_ms_per_step": {   # HIP-event sums over all launches of a step (a step may be sliced)
+            "fingerprint": fp_ms / steps, "fingerprint_main_kernel": fpm_ms / steps,
+            "fingerprint_tail_kernel": fpt_ms / steps, "fingerprint_clip_kernel": fpc_ms / steps, "dtw": dtw_ms / steps,
+            "transpose": tr_ms / steps,
+            "count": cnt_ms / steps, "count_allreduce": red_ms / steps,
+        },
+        "fused_path": {
+            "algorithmic_bytes_per_read": fused_bytes_per_read,
+            "hbm_frac_whole_job_per_gpu": value / world * fused_bytes_per_read / 1e9 / HBM_PEAK_GBS,
+            "dtw_gcups_per_gpu": (n_reads * float(N_BARCODES * CELLS_110)) / (dtw_ms / max(dtw_n, 1) * 1e-3) / 1e9 if dtw_ms else None,
+        },
+    }
+
+
 def run_rank(args):
     import numpy as np
     import torch
@@ -948,8 +1123,9 @@ def run_rank(args):
         torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
-    eng.kernel_time_reset()
-    eng.kernel_timing(True)
+    if args.full:   # HIP events around the library's launches, for the per-kernel figures
+        eng.kernel_time_reset()
+        eng.kernel_timing(True)
     dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -958,19 +1134,11 @@ def run_rank(args):
     torch.cuda.synchronize()
     dist.barrier()
     t1 = time.perf_counter()
-    eng.kernel_timing(False)
+    if args.full:
+        eng.kernel_timing(False)
     coll_dev = tdev if (world > 1 and not host_collectives) else None
     elapsed = dist.max_over_ranks(t1 - t0, device=coll_dev)
     per_rank_ms = [v / args.steps * 1e3 for v in dist.gather_over_ranks(t1 - t0, device=coll_dev)]
-
-    fp_ms, fp_n = eng.kernel_time(_lib.K_FINGERPRINT)            # the whole fingerprint chain
-    fpm_ms, fpm_n = eng.kernel_time(_lib.K_FINGERPRINT_MAIN)     # its main kernel's launches alone
-    fpc_ms, fpc_n = eng.kernel_time(_lib.K_FINGERPRINT_CLIP)     # clip_bounds_kernel (median / MAD ahead of the main kernel)
-    fpt_ms, fpt_n = eng.kernel_time(_lib.K_FINGERPRINT_TAIL)     # split main kernel: its tail-kernel launches alone (part of MAIN)
-    dtw_ms, dtw_n = eng.kernel_time(_lib.K_DTW)
-    tr_ms, tr_n = eng.kernel_time(_lib.K_TRANSPOSE)
-    cnt_ms, cnt_n = eng.kernel_time(_lib.K_COUNT)
-    red_ms, red_n = eng.kernel_time(_lib.K_REDUCE)
 
     counts = res.counts.cpu().numpy()
     n_fail = int(counts[N_BARCODES])
@@ -978,89 +1146,24 @@ def run_rank(args):
         raise RuntimeError(f"rank {rank}: all-reduced call histogram does not add up: {counts.sum()} != {total}")
     if rank == 0 and n_fail > 0.01 * total:
         raise RuntimeError(f"{n_fail} of {total} reads failed: the synthetic workload should fingerprint cleanly")
-    # every read of the shard, on the device: the calls against the generator's true barcodes, per tenth of the shard
-    # (a launch slice that wrote nothing, or wrote another slice's reads, cannot pass this; the bitwise gate below
-    # samples the same range)
-    okd = res.status == 0
-    hit = ((res.call == bc) & okd).to(torch.float64)
-    edges = [n_reads * i // 10 for i in range(11)]
-    acc_tenths = [float(hit[a:b].sum().item() / max(int(okd[a:b].sum().item()), 1)) for a, b in zip(edges[:-1], edges[1:])]
-    accuracy = float(hit.sum().item() / max(int(okd.sum().item()), 1))
-    if min(acc_tenths) <= 0.75:
-        raise RuntimeError(f"rank {rank}: calls disagree with the generator's barcodes: accuracy per tenth of the shard {acc_tenths}")
-    del okd, hit
-
-    # ---- roofline of the dominant kernel (algorithmic bytes, DESIGN.md "Measurement") ------------
-    steps = max(args.steps, 1)
-    fp_bytes = 4.0 * total_samples + 8.0 * K_FPT * n_reads + 4.0 * n_reads
-    dtw_bytes = (8.0 * K_FPT + 4.0 * N_BARCODES + 4.0) * n_reads
-    if fp_ms >= dtw_ms:
-        # The fingerprint stage is a chain of launches: the main kernel takes every read whose adapter
-        # window fits its instantiation and the list kernels the rest.  `achieved` prices the main kernel alone: the
-        # algorithmic bytes of the reads IT completes (window within its capacity; the engine reports the capacity)
-        # over ITS launches' HIP-event time -- the figure rocprofv3's average for that kernel must reproduce.
-        main_cap = 5120 if max_len > 4096 and n_reads >= 2048 else (4096 if max_len <= 4096 else 6144)
-        w_start = torch.clamp(a_s.to(torch.int64) - params.padding, min=0)
-        w_stop = torch.minimum(a_e.to(torch.int64) + params.padding, off[1:] - off[:-1])
-        lens = w_stop - w_start
-        fits = lens <= main_cap
-        main_reads = int(fits.sum().item())
-        main_samples = int(lens[fits].sum().item())
-        main_bytes = 4.0 * main_samples + (8.0 * K_FPT + 4.0) * main_reads
-        dom, dom_ms, dom_n, dom_bytes = "fingerprint_fast_kernel", fpm_ms, fpm_n, main_bytes
-        # Round 6: the main kernel is a PAIR per launch slice -- the workgroup-per-read tile kernel (fingerprint_fast_kernel<...,
-        # SPLIT>: load, clip, t-score tiles, peak list, export of <= 256 peaks with prefix sums) and the wave-per-read tail
-        # kernel (fingerprint_split_tail_kernel: suppression, top-E, boundaries, event means, normalisation, output).  The
-        # MAIN events bracket the pairs, the TAIL events the tail kernel alone; the dominant kernel is the tile kernel, priced
-        # on ITS algorithmic bytes (the samples it reads: 4 N per read -- the fingerprints are the tail kernel's output) over
-        # ITS time (MAIN - TAIL), the figure rocprofv3's average for that kernel must reproduce.
-        split_pair = None
-        if fpt_n > 0 and fpt_ms > 0:
-            split_pair = {"tile_kernel": "fingerprint_fast_kernel<20, false, 12, 1, true, true>", "tail_kernel": "fingerprint_split_tail_kernel<12>",
-                          "launch_pairs": fpm_n, "pair_ms_per_step": fpm_ms / steps, "tail_ms_per_step": fpt_ms / steps,
-                          "tile_ms_per_step": (fpm_ms - fpt_ms) / steps, "avg_tail_launch_ms": fpt_ms / fpt_n,
-                          "pair_algorithmic_bytes_per_step": main_bytes,
-                          "pair_achieved_gbs": main_bytes / (fpm_ms / steps * 1e-3) / 1e9,
-                          "pair_frac": main_bytes / (fpm_ms / steps * 1e-3) / 1e9 / HBM_PEAK_GBS}
-            dom_ms, dom_bytes = fpm_ms - fpt_ms, 4.0 * main_samples
-    else:
-        dom, dom_ms, dom_n, dom_bytes = "dtw_band_kernel<15>", dtw_ms, dtw_n, dtw_bytes
-    launches_per_step = max(dom_n // steps, 1)
-    avg_ms = dom_ms / max(dom_n, 1)
-    dom_bytes = dom_bytes / launches_per_step  # per kernel launch (a step may be sliced)
-    achieved = dom_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    # HBM traffic of that kernel from the PMC passes (profiles/traffic.json, written by
-    # tools/collect_traffic.py on the same workload); null when not collected for this size
-    # NOT measured by this run: PMC counters need rocprofv3 around the process, so these two figures are read from the
-    # committed passes of the same workload and carry their source (file, round) in the line
-    traffic = traffic_src = traffic_parts = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "traffic.json")) as fh:
-            tj = json.load(fh)
-        if tj.get("kernel") == dom and tj.get("reads_per_step") == n_reads:
-            traffic = tj.get("hbm_bytes_per_step") / launches_per_step
-            traffic_parts = {"fetched_per_launch": tj.get("fetch_bytes_per_launch_corrected"), "written_per_launch": tj.get("write_bytes_per_launch"),
-                             "note": "the tile kernel reads each sample once (fetched = 1.02 x its algorithmic bytes); what it writes are the "
-                                     "exported peak lists (<= 4.6 KB per read) that the tail kernel reads back"}
-            traffic_src = {"file": "profiles/traffic.json", "round": tj.get("round"), "collected_by": "tools/collect_traffic.py "
-                           "(separate rocprofv3 --pmc passes of this command; not measured by this run)"}
-    except (OSError, ValueError, TypeError):
-        pass
-    valu_busy = valu_src = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "sq_counters_latest.json")) as fh:
-            sj = json.load(fh)
-        pl = sj["kernels"][dom.split("<")[0]]["per_launch"]
-        valu_busy = pl["SQ_ACTIVE_INST_VALU"] * 4.0 / (1024.0 * pl["GRBM_GUI_ACTIVE"] / 8.0)
-        valu_src = {"file": "profiles/sq_counters_latest.json", "round": sj.get("round"),
-                    "collected_by": "tools/collect_sq.py (rocprofv3 --pmc pass of this command; not measured by this run)"}
-    except (OSError, ValueError, KeyError):
-        pass
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, lo)
+    if args.full:
+        # every read of the shard, on the device: the calls against the generator's true barcodes, per tenth of the shard
+        # (a launch slice that wrote nothing, or wrote another slice's reads, cannot pass this; the bitwise gate below
+        # samples the same range)
+        okd = res.status == 0
+        hit = ((res.call == bc) & okd).to(torch.float64)
+        edges = [n_reads * i // 10 for i in range(11)]
+        acc_tenths = [float(hit[a:b].sum().item() / max(int(okd[a:b].sum().item()), 1)) for a, b in zip(edges[:-1], edges[1:])]
+        accuracy = float(hit.sum().item() / max(int(okd.sum().item()), 1))
+        if min(acc_tenths) <= 0.75:
+            raise RuntimeError(f"rank {rank}: calls disagree with the generator's barcodes: accuracy per tenth of the shard {acc_tenths}")
+        del okd, hit
 
     out = None
     if rank == 0:
         value = total * args.steps / elapsed
-        fused_bytes_per_read = 4.0 * total_samples / n_reads + 4.0 * N_BARCODES + 4.0
         out = {
             "metric": "reads/sec demuxed (110-pt DTW x 10 barcodes)",
             "value": value,
@@ -1082,8 +1185,9 @@ def run_rank(args):
                 "reads_per_gpu": per_gpu,
                 "reads_total": total,
                 "failed_reads": n_fail,
-                "call_accuracy_vs_true_barcode": {"whole_shard": accuracy, "min_over_tenths": min(acc_tenths),
-                                                  "asserted": "> 0.75 in every tenth of rank 0's shard (all reads, on the device)"},
+                **({"call_accuracy_vs_true_barcode": {"whole_shard": accuracy, "min_over_tenths": min(acc_tenths),
+                                                      "asserted": "> 0.75 in every tenth of rank 0's shard (all reads, on the device)"}}
+                   if args.full else {}),
                 **({"ctx_options": list(args.ctx_opt)} if args.ctx_opt else {}),
                 "sharding": "contiguous shards of one global read range (dist.shard_range), one process per GPU, "
                             "one int64[11] count all-reduce per step",
@@ -1092,60 +1196,13 @@ def run_rank(args):
                                    + (("; " + reducer.note) if reducer.note else ""),
                 "rccl_ranks": reducer.rccl_ranks,     # ncclCommCount of the C ABI's communicator (null: no communicator)
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dom,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "traffic_parts": traffic_parts,
-                "algorithmic_bytes_per_launch": dom_bytes,
-                "avg_launch_ms": avg_ms,
-                "launches": dom_n,
-                **({"kernel_instantiation": ("fingerprint_fast_kernel<%d, false, 12, 1, true, true> (%d-sample windows; the tile kernel of the split "
-                                             "main pair: algorithmic bytes = the samples it reads)" % (main_cap // 256, main_cap)) if split_pair else
-                                            "fingerprint_fast_kernel<%d, false> (%d-sample windows)" % (main_cap // 256, main_cap),
-                    "split_main_pair": split_pair,
-                    "reads_per_launch": main_reads / launches_per_step,
-                    "share_of_reads": main_reads / n_reads,
-                    "stage": {"what": "whole fingerprint chain (clip_bounds_kernel ahead of the main kernel + main kernel + "
-                                      "list kernels for longer windows, peak-list overflows, exact-score retries, the "
-                                      "exact general kernel)",
-                              "ms_per_step": fp_ms / steps,
-                              "algorithmic_gb_per_step": fp_bytes / 1e9,
-                              "achieved_gbs": fp_bytes / (fp_ms / steps * 1e-3) / 1e9 if fp_ms else None},
-                    # the launch ahead of the main kernel: one wave per read, the samples of the main kernel's reads once
-                    # more from HBM (4 N bytes in, 16 bytes out per read) -- priced like the main kernel, on its own
-                    # algorithmic bytes and its own HIP events
-                    "clip_bounds_kernel": ({"ms_per_step": fpc_ms / steps, "launches": fpc_n,
-                                            "algorithmic_bytes_per_step": 4.0 * main_samples + 16.0 * n_reads,
-                                            "achieved": (4.0 * main_samples + 16.0 * n_reads) / (fpc_ms / steps * 1e-3) / 1e9,
-                                            "frac": (4.0 * main_samples + 16.0 * n_reads) / (fpc_ms / steps * 1e-3) / 1e9 / HBM_PEAK_GBS}
-                                           if fpc_ms else None)}
-                   if dom == "fingerprint_fast_kernel" else {}),
-                # what actually bounds the kernel (float64 VALU issue), from the committed PMC pass
-                "valu_busy_frac": valu_busy,
-                "valu_busy_source": valu_src,
-            },
-            "kernels_ms_per_step": {   # HIP-event sums over all launches of a step (a step may be sliced)
-                "fingerprint": fp_ms / steps, "fingerprint_main_kernel": fpm_ms / steps,
-                "fingerprint_tail_kernel": fpt_ms / steps, "fingerprint_clip_kernel": fpc_ms / steps, "dtw": dtw_ms / steps,
-                "transpose": tr_ms / steps,
-                "count": cnt_ms / steps, "count_allreduce": red_ms / steps,
-            },
-            "fused_path": {
-                "algorithmic_bytes_per_read": fused_bytes_per_read,
-                "hbm_frac_whole_job_per_gpu": value / world * fused_bytes_per_read / 1e9 / HBM_PEAK_GBS,
-                "dtw_gcups_per_gpu": (n_reads * float(N_BARCODES * CELLS_110)) / (dtw_ms / max(dtw_n, 1) * 1e-3) / 1e9 if dtw_ms else None,
-            },
         }
+        if args.full:
+            out.update(kernel_figures(eng, params, off, a_s, a_e, max_len, n_reads, total_samples, args.steps, value, world))
 
     # ---- CPU baseline + parity gate on a bounded sample (rank 0, N=1 only) ------------------------------
     parity_failed = False
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu, parity = cpu_baseline_and_parity(eng, sig, off, a_s, a_e, res, refs, n_reads,
                                               args.cpu_seconds, args.parity_reads)
         out["cpu_baseline"] = cpu
@@ -1158,11 +1215,11 @@ def run_rank(args):
         g_fpt = eng.fingerprint(sig[: int(off[ns].item())], a_s[:ns], a_e[:ns], offsets=off[: ns + 1], max_len=max_len)[0]
         fs = g_fpt.cpu().numpy()
         out["dtaidistance"] = try_dtaidistance(eng, refs, fs[~np.isnan(fs).any(axis=1)])
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["cpu_baseline"] = None
 
     # ---- secondary regimes, after the big buffers are gone ----------------------------------------------
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         sig = off = a_s = a_e = bc = res = None
         eng._work = None
         torch.cuda.synchronize()

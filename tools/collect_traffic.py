@@ -26,7 +26,7 @@ def run_pass(counter, outdir, reads, parse_only=False):
     env = dict(os.environ, TMPDIR="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "--",
            sys.executable, os.path.join(ROOT, "bench.py"), "--reads", str(reads), "--steps", "1", "--warmup", "0",
-           "--no-cpu", "--no-secondary", "--calib"]
+           "--full", "--no-cpu", "--no-secondary", "--calib"]
     if not parse_only:
         with open(os.path.join(d, "bench.log"), "w") as fh:
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=fh, stderr=subprocess.STDOUT, check=True)

@@ -3,7 +3,7 @@
 # the LDS request (capP 2048 -> 48 KB -> three workgroups per CU instead of four); the work per read is unchanged.
 cd "$(dirname "$0")/../.."
 for opt in "" "--ctx-opt 6=2048" "" "--ctx-opt 6=2048"; do
-    python3 bench.py --steps 4 --warmup 1 --no-cpu --no-secondary --ctx-opt 5=1 $opt 2>&1 | grep -E "workgroups/CU|^\{" |
+    python3 bench.py --full --steps 4 --warmup 1 --no-cpu --no-secondary --ctx-opt 5=1 $opt 2>&1 | grep -E "workgroups/CU|^\{" |
         python3 -c "
 import sys, json
 for l in sys.stdin:
