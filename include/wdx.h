@@ -62,7 +62,17 @@ extern "C" {
 #define WDX_NORM_MEAN 1
 #define WDX_NORM_MEDIAN 2
 
-/* The hot-path knobs of SigProcConfig (config/sig_proc.py:16-70 + ADAPTed core.*), by value. */
+/* The hot-path knobs of SigProcConfig (config/sig_proc.py:16-70 + ADAPTed core.*), by value.
+ * Limits, checked once per call before any launch (wdx_fingerprint.hip, launch_fingerprint):
+ *   num_events          1 .. 253   0 or less -> WDX_ERR_INVALID, 254 or more -> WDX_ERR_UNSUPPORTED
+ *   barcode_num_events  1 .. 254   outside   -> WDX_ERR_INVALID (beyond num_events + 1 every read fails, as in
+ *                                               the reference)
+ *   running_stat_width  0 .. 64    outside   -> WDX_ERR_UNSUPPORTED (0 is accepted: no t-scores, so every read
+ *                                               fails, WDX_READ_FAIL_SEGMENT or with accept_less_cpts
+ *                                               WDX_READ_FAIL_UNKNOWN, as in the reference)
+ *   padding             >= 0       negative  -> WDX_ERR_INVALID
+ *   min_obs_per_base    any        below 1 every read fails with WDX_READ_FAIL_UNKNOWN (scipy refuses distance 0)
+ * Adapter windows (padding included) longer than WDX_MAX_ADAPTER_SAMPLES come back WDX_READ_FAIL_UNKNOWN. */
 typedef struct wdx_seg_params {
     int32_t padding;            /* sig_extract.padding                                          */
     int32_t sig_norm;           /* sig_extract.normalization   (WDX_NORM_*)                     */

@@ -129,6 +129,34 @@ def test_g4b_long_adapter_windows_bit_exact(golden_dir):
     assert {"rna004_15200", "rna002_15200", "trna_15200", "rna002_11201", "rna002_15200_nan_middle"} <= tags
 
 
+def test_g11_parameter_domain_bit_exact(golden_dir):
+    """g11: the reference's detect_results_to_fpt over the parameter domain beyond the shipped triples
+    (tests/golden/make_golden_domain.py) -- num_events 1 .. 253 with up to 254 barcode events, reach 17 / 18 .. 1000,
+    widths 0 .. 64, settings the reference fails on, short windows on the shrink's .5 ties, 11 200 / 11 201 / 16 384
+    samples."""
+    g = _load(golden_dir, "g11_param_domain.npz")
+    tags, seen, reach = set(), set(), 0
+    for k in range(int(g["n"])):
+        tag = str(g[f"tag_{k}"])
+        a_start, a_end, ok = (int(v) for v in g[f"args_{k}"])
+        p = _params_from(g, k)
+        res = orc.fingerprint_one(g[f"row_{k}"], a_start, a_end, p, ok=bool(ok))
+        st_ref = int(g[f"status_{k}"])
+        assert res["status"] == st_ref, f"case {k} ({tag}): status {res['status']} != {st_ref}"
+        if st_ref == 0:
+            assert _same(res["fpt"], g[f"fpt_{k}"]), f"case {k} ({tag}) fpt"
+            assert _same(res["dwell"], g[f"dwell_{k}"]), f"case {k} ({tag}) dwell"
+            assert _same(res["stats"], g[f"stats_{k}"]), f"case {k} ({tag}) stats"
+            n = a_end - a_start + 2 * p.padding
+            reach += min(p.min_obs_per_base, round(n / p.num_events / 2)) > 17
+        tags.add(tag)
+        seen.add(st_ref)
+    assert {0, 3, 5} <= seen
+    assert reach >= 10, "too few successful reads with a suppression reach beyond 17"
+    assert {"E126_K127", "E1_K2", "E253_K254_segnorm_median", "d9_w64", "d0", "w0", "K_E_plus_2",
+            "E200_K201_signorm_median", "E200_d20_w40_K200_11201", "E253_d25_w30_K254_16384"} <= tags
+
+
 def test_g4_signorm_median(golden_dir):
     g = _load(golden_dir, "g4_fingerprint.npz")
     hit = 0

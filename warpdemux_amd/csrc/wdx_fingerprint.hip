@@ -266,13 +266,20 @@ __device__ __forceinline__ double np_pairwise_leaf(const double *p, int n) {  //
     }
     return res;
 }
-// n <= 256 (kSegCap = 254): at most one level of the recursion
-__device__ double np_pairwise_sum_dev(const double *a, int n) {
-    if (n <= 128) return np_pairwise_leaf(a, n);
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_leaf(a, n2) + np_pairwise_leaf(a + n2, n - n2);
+template <int kDepth>
+__device__ double np_pairwise_tree(const double *a, int n) {
+    if constexpr (kDepth == 0) {
+        return np_pairwise_leaf(a, n);
+    } else {
+        if (n <= 128) return np_pairwise_leaf(a, n);
+        int n2 = n / 2;
+        n2 -= n2 % 8;
+        return np_pairwise_tree<kDepth - 1>(a, n2) + np_pairwise_tree<kDepth - 1>(a + n2, n - n2);
+    }
 }
+// n <= kSegCap + 1 = 255: two levels of the recursion.  The split point is rounded DOWN to a multiple of 8, so the right
+// half of n = 249 .. 255 still holds 129 .. 135 values and is split once more (120 + 134 -> 120 + (64 + 70) for 254)
+__device__ double np_pairwise_sum_dev(const double *a, int n) { return np_pairwise_tree<2>(a, n); }
 
 // np.add.reduce over the float32 values val(0..n): NumPy's exact association -- the ufunc hands the inner loop at
 // most 8192 elements (np.getbufsize()) at a time, each chunk is summed by the pairwise routine (leaves of <= 128
