@@ -410,7 +410,8 @@ int wdx_feeder_alive(void *ring);   /* 1 while a feeder process serves the ring,
  * model trained on those references is resident] on the context's own stream, and the requested outputs
  * come back in one copy; one synchronisation per call.  Outputs are HOST pointers: status int32[n] is
  * required; call int32[n], dist (n, n_refs) float32, fpt (n, K) float64, prob (n, k) float64,
- * pred int32[n] (barcode label or -1 = outlier, worker.py:125), conf float64[n] are nullable. */
+ * pred int32[n] (barcode label or -1 = outlier, worker.py:125), conf float64[n] are nullable.  A read whose
+ * fingerprint failed has pred -1 and NaN prob / conf, like wdx_demux_svm_dev. */
 int wdx_live_tick(wdx_ctx *ctx, const float *const *rows, const int32_t *row_len, int64_t n_reads,
                   const int32_t *a_start, const int32_t *a_end, const uint8_t *ok, const wdx_seg_params *p,
                   int64_t n_refs, int32_t use_svm, double *fpt, float *dist, int32_t *call, int32_t *status,

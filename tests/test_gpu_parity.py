@@ -872,24 +872,24 @@ def test_device_synth_matches_numpy_and_fused_pipeline():
 # ----------------------------------------------------------------------------------------------
 # N1: DTW_SVM.predict -- DTW -> exp kernel -> libsvm predict_probability -> process_probs
 # ----------------------------------------------------------------------------------------------
-def _svm_case(n_classes, n_train, n_query, seed, thresholds=False):
+def _svm_case(n_classes, n_train, n_query, seed, thresholds=False, gamma=1.0, pwr_dist=1):
     from test_oracle_svm import make_model
     from warpdemux_amd.models import DTW_SVM
 
-    svc, Xtr, centers, rng = make_model(n_classes, n_train, seed=seed)
+    svc, Xtr, centers, rng = make_model(n_classes, n_train, seed=seed, gamma=gamma, pwr_dist=pwr_dist)
     yq = rng.integers(0, n_classes, n_query)
     Xq = centers[yq] + 0.9 * rng.normal(size=(n_query, Xtr.shape[1]))
     label_mapper = {i: 3 * i + 1 for i in range(n_classes)}
     thr = rng.uniform(0.05, 0.6, n_classes) if thresholds else None
     n_support, support, dual_coef, rho, probA, probB, k = orc.svm_params(svc)
     m = DTW_SVM(Xtr, n_support, support, dual_coef, rho, probA, probB, label_mapper, thr, window=15, penalty=0.1,
-                gamma=1.0, pwr_dist=1, block_size=2000)
+                gamma=gamma, pwr_dist=pwr_dist, block_size=2000)
     return svc, Xtr, Xq, label_mapper, thr, m
 
 
-def _reference_tail(svc, Xtr, Xq, label_mapper, thr):
+def _reference_tail(svc, Xtr, Xq, label_mapper, thr, gamma=1.0, pwr_dist=1):
     """models/dtw_svm.py:85-98 with the oracle's DTW and scikit-learn's own predict_proba."""
-    Kq = np.exp(-1.0 * np.power(orc.dtw_matrix(Xq, Xtr, 15, 0.1), 1))
+    Kq = np.exp(-gamma * np.power(orc.dtw_matrix(Xq, Xtr, 15, 0.1), pwr_dist))
     prob = svc.predict_proba(Kq)
     idx = np.argmax(prob, axis=1)
     pred = np.array([label_mapper[i] for i in idx])
@@ -900,14 +900,21 @@ def _reference_tail(svc, Xtr, Xq, label_mapper, thr):
     return pred, prob, conf
 
 
+# pwr_dist 2 / 3: gamma 0.3 and 1.2 scaled by 5.7^(1 - p) (5.7 = the median DTW distance of make_model's sets), so the
+# kernel values are spread like those of the pwr_dist = 1 models and not almost all 0
+_SKL_CASES = [(2, 80, False, {}), (3, 150, True, {}), (5, 300, True, {}), (11, 500, False, {}), (12, 700, True, {}),
+              (16, 800, True, {}),    # largest supported model
+              (3, 150, True, dict(gamma=0.3 / 5.7, pwr_dist=2)), (5, 300, True, dict(gamma=1.2 / 5.7, pwr_dist=2)),
+              (4, 200, False, dict(gamma=0.3 / 5.7 ** 2, pwr_dist=3)), (11, 500, True, dict(gamma=1.2 / 5.7 ** 2, pwr_dist=3))]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_classes,n_train,thresholds", [(2, 80, False), (3, 150, True), (5, 300, True),
-                                                          (11, 500, False), (12, 700, True),
-                                                          (16, 800, True)])    # largest supported model
-def test_dtw_svm_predict_matches_sklearn(n_classes, n_train, thresholds):
+@pytest.mark.parametrize("n_classes,n_train,thresholds,kern", [
+    pytest.param(*c, id="-".join(map(str, c[:3])) + "".join(f"-{key}{v:.4g}" for key, v in c[3].items())) for c in _SKL_CASES])
+def test_dtw_svm_predict_matches_sklearn(n_classes, n_train, thresholds, kern):
     sklearn = pytest.importorskip("sklearn")
-    svc, Xtr, Xq, label_mapper, thr, m = _svm_case(n_classes, n_train, 333, seed=n_classes, thresholds=thresholds)
-    pred_ref, prob_ref, conf_ref = _reference_tail(svc, Xtr, Xq, label_mapper, thr)
+    svc, Xtr, Xq, label_mapper, thr, m = _svm_case(n_classes, n_train, 333, seed=n_classes, thresholds=thresholds, **kern)
+    pred_ref, prob_ref, conf_ref = _reference_tail(svc, Xtr, Xq, label_mapper, thr, **kern)
     pred, prob = m.predict(Xq)
     assert prob.shape == prob_ref.shape and pred.shape == pred_ref.shape
     # float32 exp on the device may differ from NumPy's by one ulp in the kernel value: 1e-5 on probabilities
@@ -931,8 +938,9 @@ def test_dtw_svm_predict_matches_sklearn(n_classes, n_train, thresholds):
 
 @pytest.mark.gpu
 def test_dtw_svm_predict_matches_oracle_on_device_kernel_values():
-    """With the kernel matrix the device itself produced the oracle's libsvm restatement must agree to
-    double rounding: isolates the classifier tail from the float32 exp."""
+    """On the device's own DTW distances (bit-equal to the oracle's) the tail agrees with scikit-learn's predict_proba to
+    1e-5: the device's float32 exp may differ from NumPy's by one ulp in a kernel value.  The exact comparison of the tail
+    (1e-12, kernel values exactly 0 / 1) is tests/test_gpu_svm.py."""
     pytest.importorskip("sklearn")
     svc, Xtr, Xq, label_mapper, thr, m = _svm_case(5, 300, 200, seed=9)
     D = pdist.distance_matrix_to(Xq, Xtr, window=15, penalty=0.1, n_jobs=1)

@@ -9,7 +9,7 @@ from oracle import wdx_oracle as orc
 sklearn = pytest.importorskip("sklearn")
 
 
-def make_model(n_classes, n_train, seed, L=25):
+def make_model(n_classes, n_train, seed, L=25, gamma=1.0, pwr_dist=1):
     from sklearn.svm import SVC
 
     rng = np.random.default_rng(seed)
@@ -17,7 +17,7 @@ def make_model(n_classes, n_train, seed, L=25):
     y = rng.integers(0, n_classes, n_train)
     Xtr = centers[y] + 0.9 * rng.normal(size=(n_train, L))
     D = orc.dtw_matrix(Xtr, Xtr, 15, 0.1)
-    K = np.exp(-1.0 * np.power(D, 1))            # pdist_kernel, models/dtw_svm.py:21-22 (float32)
+    K = np.exp(-gamma * np.power(D, pwr_dist))   # pdist_kernel, models/dtw_svm.py:21-22 (float32)
     svc = SVC(kernel="precomputed", probability=True, C=1.0, random_state=seed).fit(K, y)
     return svc, Xtr, centers, rng
 
@@ -70,3 +70,34 @@ def test_oracle_matches_reference_model_golden(which):
     pred[conf < g["thresholds"][idx]] = -1
     assert np.array_equal(pred, g["y_pred"])
     assert (g["y_pred"] == -1).sum() > 10 and len(np.unique(g["y_pred"])) == len(label_mapper)
+
+
+@pytest.mark.parametrize("k", range(2, 17))
+def test_numpy_tail_helper_matches_the_oracle(k):
+    """tests/helpers/svm_ref.py (the float64 NumPy restatement with the coupling's stopping margin, the reference side of
+    tests/test_gpu_svm.py) against the oracle's libsvm restatement on the synthetic models: 0/1 kernel rows as the exact
+    tier uses them and continuous ones."""
+    from helpers import svm_ref
+
+    p, gamma, far = svm_ref.EXACT_KERNELS[k % len(svm_ref.EXACT_KERNELS)]
+    m = svm_ref.synth_model(k, seed=k, thresholds=k % 2 == 0, gamma=gamma, pwr_dist=p)
+    D = svm_ref.exact_distances(200, m.n_train, far, seed=100 + k)
+    rng = np.random.default_rng(k)
+    for K in ((D == 0).astype(np.float64), rng.uniform(0, 1, size=(100, m.n_train)) ** 4):
+        ref = m.predict(K)
+        prob, dec = orc.svm_predict_proba(K, *m.arrays(), want_dec=True)
+        np.testing.assert_array_equal(ref.dec, dec)          # same operations in the same order
+        np.testing.assert_allclose(ref.prob, prob, rtol=0, atol=1e-13)
+        assert np.all(ref.iters >= 1) and np.all(np.isfinite(ref.margin))
+        # process_probs on the oracle's probabilities
+        best = np.argmax(prob, axis=1)
+        srt = np.sort(prob, axis=1)
+        conf = srt[:, -1] - srt[:, -2]
+        pred = m.label_map[best].astype(np.int64)
+        if m.thresholds is not None:
+            pred[conf < m.thresholds[best]] = -1
+        np.testing.assert_allclose(ref.conf, conf, rtol=0, atol=1e-13)
+        far = conf > 1e-9
+        if m.thresholds is not None:
+            far &= np.abs(conf - m.thresholds[best]) > 1e-9
+        assert np.array_equal(ref.pred[far], pred[far]) and far.mean() > 0.9

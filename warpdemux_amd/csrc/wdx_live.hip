@@ -135,6 +135,10 @@ int wdx_live_tick(wdx_ctx *ctx, const float *const *rows, const int32_t *row_len
             if ((rc = launch_svm_predict(ctx->svm, (const float *)(dout + q_dist), n_reads, (double *)(dout + q_prob),
                                          (int32_t *)(dout + q_pred), (double *)(dout + q_conf), s, ctx->knobs)))
                 return rc;
+            // failed reads: pred -1, NaN prob / conf, as every other entry point that runs the tail returns them
+            if ((rc = launch_svm_mask_failed((const int32_t *)(dout + q_status), n_reads, k, (double *)(dout + q_prob),
+                                             (int32_t *)(dout + q_pred), (double *)(dout + q_conf), s)))
+                return rc;
         }
     }
     // one device->host copy of what the caller asked for: [first wanted byte, last wanted byte)
