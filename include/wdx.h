@@ -505,6 +505,32 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);
 int wdx_kernel_time(wdx_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
 int wdx_kernel_time_reset(wdx_ctx *ctx);
+/* Which DTW kernel the latest dispatch through this context took (wdx_dtw_matrix[_dev], wdx_demux_*, wdx_live_tick,
+ * wdx_dtw_svm_predict, wdx_demux_svm_dev; a pipelined minibatch reports at its wdx_demux_submit[_ex]).  Host-side
+ * bookkeeping of the launcher: nothing on the device changes.  The thresholds between the paths are tuning constants;
+ * tests that mean "band<8>, row-major" ask here instead of restating them.  A call that dispatched nothing (no reads, no
+ * references) leaves the record as it was; family is WDX_DTW_NONE until the first dispatch. */
+#define WDX_DTW_NONE 0
+#define WDX_DTW_WAVEFRONT 1 /* anti-diagonal kernel, one 16-lane row per pair                                  */
+#define WDX_DTW_SHORT 2     /* unrolled 25-point / window-15 kernel                                           */
+#define WDX_DTW_BAND 3      /* rolling register band: band_w = 8, 15, 16 or 32                                */
+#define WDX_DTW_SCRATCH 4   /* two DP rows per lane in global scratch (windows beyond 32)                     */
+#define WDX_DTW_SHORT_SVM 5 /* the 25-point kernel with the SVM decision sums in its epilogue                 */
+#define WDX_DTW_LAYOUT_ROW_MAJOR 0     /* lanes = reads, each lane reads its own (n, L) row in place                      */
+#define WDX_DTW_LAYOUT_READ_MINOR 1    /* lanes = reads, transposed copy (L, ld): one coalesced load per sample           */
+#define WDX_DTW_LAYOUT_REFS_AS_LANES 2 /* lanes = references (resident transposed set), the reads are the uniform operand */
+typedef struct wdx_dtw_launch_info {
+    int32_t family;         /* WDX_DTW_*                                                                             */
+    int32_t band_w;         /* template window of the instantiation (band: 8 / 15 / 16 / 32, short: 15), else 0      */
+    int32_t exact_w;        /* 1: the instantiation serves exactly window band_w (no per-cell window mask)           */
+    int32_t layout;         /* WDX_DTW_LAYOUT_* (wavefront and short+svm read row-major rows)                        */
+    int32_t fused_argmin;   /* 1: the DTW kernel wrote the argmin itself, 0: separate kernel or none asked for       */
+    int32_t launches;       /* DTW kernel launches of the dispatch (the scratch-row loop: one per 65 536 lanes)      */
+    int32_t refs_per_block; /* uniform-operand series one block walks (wavefront: 1)                                 */
+    int32_t window;         /* effective window, 1..L                                                                */
+    int64_t grid_x, grid_y; /* of the (last) DTW launch                                                              */
+} wdx_dtw_launch_info;
+int wdx_dtw_last_launch(wdx_ctx *ctx, wdx_dtw_launch_info *info);
 /* Diagnostic build of the fingerprint kernel with s_memtime stamps between its phases:
  * d_prof receives 32 int64 per read for the first prof_reads reads (slots 0..9 = shader-clock
  * stamps at the phase boundaries P0..P7, 10 = suppression iterations, 11 = adapter samples,

@@ -85,21 +85,44 @@ def test_dtw_large_batch_fused_argmin():
     assert (am == lab).mean() > 0.95
 
 
-@pytest.mark.parametrize("w", [None, 0, 1, 2, 5, 8, 9, 15, 16, 17, 25, 32, 33, 60, 110, 500])
-@pytest.mark.parametrize("L", [25, 110])
-def test_dtw_windows(w, L):
+@contextlib.contextmanager
+def _dispatch(no_wavefront):
+    """Both dispatches of a small problem: the anti-diagonal wavefront kernel (default: at most 16 384 pairs, effective
+    window <= 16) or, with WDX_OPT_NO_WAVEFRONT_DTW, the lane-per-pair kernels that serve the same shape in large batches."""
+    ctx = _lib.default_context()
+    ctx.set_option(_lib.OPT_NO_WAVEFRONT_DTW, int(no_wavefront))
+    try:
+        yield
+        if no_wavefront:    # the switch did what the test is about
+            assert ctx.dtw_last_launch().family not in (_lib.DTW_NONE, _lib.DTW_WAVEFRONT)
+    finally:
+        ctx.set_option(_lib.OPT_NO_WAVEFRONT_DTW, 0)
+
+
+def _both_dispatches(*cases):
+    """every case under the default dispatch (its id unchanged) and with the wavefront kernel switched off"""
+    ids = ["-".join(str(v) for v in c) for c in cases]
+    return ([pytest.param(*c, False, id=i) for c, i in zip(cases, ids)] +
+            [pytest.param(*c, True, id=i + "-no_wavefront") for c, i in zip(cases, ids)])
+
+
+@pytest.mark.parametrize("L,w,no_wavefront", _both_dispatches(
+    *[(L, w) for L in [25, 110] for w in [None, 0, 1, 2, 5, 8, 9, 15, 16, 17, 25, 32, 33, 60, 110, 500]]))
+def test_dtw_windows(w, L, no_wavefront):
     rng = np.random.default_rng(3)
     X, Y = rng.normal(size=(70, L)), rng.normal(size=(9, L))
     for p in (0.1, None, 1.5):
         ref = orc.dtw_matrix(X, Y, w, p)
-        _check_dist(pdist.distance_matrix_to(X, Y, window=w, penalty=p, n_jobs=1), ref)
+        with _dispatch(no_wavefront):
+            _check_dist(pdist.distance_matrix_to(X, Y, window=w, penalty=p, n_jobs=1), ref)
 
 
-@pytest.mark.parametrize("L", [1, 2, 3, 14, 15, 16, 28, 29, 30, 31, 57, 200])
-def test_dtw_lengths(L):
+@pytest.mark.parametrize("L,no_wavefront", _both_dispatches(*[(L,) for L in [1, 2, 3, 14, 15, 16, 28, 29, 30, 31, 57, 200]]))
+def test_dtw_lengths(L, no_wavefront):
     rng = np.random.default_rng(L)
     X, Y = rng.normal(size=(65, L)), rng.normal(size=(5, L))
-    _check_dist(pdist.distance_matrix_to(X, Y, window=15, penalty=0.1, n_jobs=1), orc.dtw_matrix(X, Y, 15, 0.1))
+    with _dispatch(no_wavefront):
+        _check_dist(pdist.distance_matrix_to(X, Y, window=15, penalty=0.1, n_jobs=1), orc.dtw_matrix(X, Y, 15, 0.1))
 
 
 @pytest.mark.parametrize("nX", [0, 1, 2, 3, 63, 64, 65])
@@ -118,6 +141,16 @@ def test_dtw_few_reads_many_refs(nX):
 
 
 def test_dtw_nan_inf_and_ties():
+    _nan_inf_and_ties()
+
+
+def test_dtw_nan_inf_and_ties_without_the_wavefront_kernel():
+    """the same 1 300 pairs on band<15>, read-minor (the transpose's NaN flags) + the separate argmin kernel"""
+    with _dispatch(True):
+        _nan_inf_and_ties()
+
+
+def _nan_inf_and_ties():
     rng = np.random.default_rng(6)
     X, Y = rng.normal(size=(130, 110)), rng.normal(size=(10, 110))
     X[3, 17] = np.nan
@@ -1038,7 +1071,10 @@ def test_demux_svm_dev_fused_form_over_class_counts(n_classes, n_train):
     eng.set_svm(m)
     sig, off, a_s, a_e, bc, max_len = eng.synth_packed(spec, 7000, n)
     pf, qf, cf, sf, _, _ = eng.demux_svm(sig, a_s, a_e, offsets=off, max_len=max_len)                      # fused
+    route = eng.ctx.dtw_last_launch()
+    assert (route.family, route.band_w, route.layout) == (_lib.DTW_SHORT_SVM, 15, _lib.DTW_LAYOUT_ROW_MAJOR)
     pu, qu, cu, su, du, _ = eng.demux_svm(sig, a_s, a_e, offsets=off, max_len=max_len, want_dist=True)     # row blocks
+    assert eng.ctx.dtw_last_launch().family == _lib.DTW_SHORT
     torch.cuda.synchronize()
     status = sf.cpu().numpy()
     ok = status == 0
@@ -1677,9 +1713,10 @@ def test_fingerprint_randomised_configs_and_signal_styles(seed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", range(int(os.environ.get("WDX_SOAK_SEEDS", "24"))))
 def test_dtw_randomised_shapes_windows_penalties(seed):
-    """Random series lengths, windows, penalties and batch shapes: every DTW kernel the dispatcher can pick
-    (rolling band 8/15/16/32, unrolled 25x15, wavefront rows for few pairs, scratch rows for wide windows,
-    fused argmin or separate) against the oracle, float32 distances bit for bit."""
+    """Random series lengths, windows, penalties and batch shapes against the oracle, float32 distances bit for bit and
+    the argmin on every row (a NaN row included: the first NaN wins, np.argmin's rule and the device's).  Most
+    draws are small enough for the wavefront kernel: a soak of the dispatcher's inputs, NOT the coverage of its kernels --
+    tests/test_gpu_dtw_dispatch.py pins every kernel, layout and dispatch edge by name."""
     rng = np.random.default_rng(5000 + seed)
     L = int(rng.choice([1, 2, 7, 16, 24, 25, 26, 28, 29, 40, 64, 110, 111, 150]))
     w = rng.choice([None, 0, 1, 2, 3, 8, 9, 15, 16, 17, 31, 32, 33, 40, L, L + 3])
@@ -1696,6 +1733,6 @@ def test_dtw_randomised_shapes_windows_penalties(seed):
     ref = orc.dtw_matrix(X, Y, w, p)
     got, am = pdist.nearest_reference(X, Y, w, p)
     _check_dist(got, ref)
-    ok_rows = ~np.isnan(ref).any(axis=1)
-    assert np.array_equal(am[ok_rows], np.argmin(ref[ok_rows], axis=1))
+    assert np.array_equal(am, orc.argmin_rows(ref))
+    assert np.array_equal(am, np.argmin(ref, axis=1))
     _check_dist(pdist.distance_matrix_to(X, Y, window=w, penalty=p, n_jobs=1), ref)

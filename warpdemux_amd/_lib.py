@@ -50,7 +50,7 @@ EXPORTS = [
     "wdx_fingerprint_batch", "wdx_fingerprint_refine_batch", "wdx_fingerprint_refine_dev", "wdx_fingerprint_dev", "wdx_demux_batch", "wdx_demux_submit", "wdx_demux_wait", "wdx_demux_submit_ex", "wdx_demux_wait_ex",
     "wdx_host_alloc", "wdx_host_alloc_on", "wdx_host_free", "wdx_host_register", "wdx_host_unregister", "wdx_live_tick", "wdx_svm_set_model",
     "wdx_svm_predict_dev", "wdx_dtw_svm_predict", "wdx_demux_svm_dev", "wdx_demux_workspace_bytes", "wdx_demux_dev",
-    "wdx_kernel_timing", "wdx_kernel_time", "wdx_kernel_time_reset", "wdx_synth_lengths_dev",
+    "wdx_kernel_timing", "wdx_kernel_time", "wdx_kernel_time_reset", "wdx_dtw_last_launch", "wdx_synth_lengths_dev",
     "wdx_synth_fill_dev", "wdx_fingerprint_profile_dev", "wdx_calib_read_dev", "wdx_selftest_score_dev", "wdx_selftest_clip_dev",
     "wdx_feeder_ring_bytes", "wdx_feeder_ring_init", "wdx_feeder_serve", "wdx_feeder_run", "wdx_feeder_demux", "wdx_feeder_predict", "wdx_feeder_stop",
     "wdx_feeder_served", "wdx_feeder_stats", "wdx_feeder_alive", "wdx_feeder_selftest",
@@ -89,6 +89,30 @@ class RefineParamsC(C.Structure):
         ("ub_end", C.c_int32),
         ("barcode_segm_events", C.c_int32),
         ("barcode_keep_events", C.c_int32),
+    ]
+
+
+# wdx_dtw_launch_info.family / .layout (include/wdx.h)
+DTW_NONE, DTW_WAVEFRONT, DTW_SHORT, DTW_BAND, DTW_SCRATCH, DTW_SHORT_SVM = range(6)
+DTW_FAMILY_NAMES = ("none", "wavefront", "short", "band", "scratch", "short+svm")
+DTW_LAYOUT_ROW_MAJOR, DTW_LAYOUT_READ_MINOR, DTW_LAYOUT_REFS_AS_LANES = range(3)
+DTW_LAYOUT_NAMES = ("row-major", "read-minor", "refs-as-lanes")
+
+
+class DtwLaunchInfoC(C.Structure):
+    """wdx_dtw_launch_info (include/wdx.h)"""
+
+    _fields_ = [
+        ("family", C.c_int32),
+        ("band_w", C.c_int32),
+        ("exact_w", C.c_int32),
+        ("layout", C.c_int32),
+        ("fused_argmin", C.c_int32),
+        ("launches", C.c_int32),
+        ("refs_per_block", C.c_int32),
+        ("window", C.c_int32),
+        ("grid_x", C.c_int64),
+        ("grid_y", C.c_int64),
     ]
 
 
@@ -294,6 +318,8 @@ def load():
         L.wdx_demux_svm_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp, vp, vp, i64, vp]
         L.wdx_kernel_timing.restype = C.c_int
         L.wdx_kernel_timing.argtypes = [vp, C.c_int]
+        L.wdx_dtw_last_launch.restype = C.c_int
+        L.wdx_dtw_last_launch.argtypes = [vp, P(DtwLaunchInfoC)]
         L.wdx_kernel_time.restype = C.c_int
         L.wdx_kernel_time.argtypes = [vp, C.c_int, P(f64), P(i64)]
         L.wdx_kernel_time_reset.restype = C.c_int
@@ -388,6 +414,12 @@ class Context:
 
     def synchronize(self, stream=None):
         check(self._L.wdx_ctx_synchronize(self.handle, stream))
+
+    def dtw_last_launch(self) -> DtwLaunchInfoC:
+        """Which DTW kernel the latest dispatch through this context took (wdx_dtw_last_launch; tests, diagnostics)."""
+        info = DtwLaunchInfoC()
+        check(self._L.wdx_dtw_last_launch(self.handle, C.byref(info)))
+        return info
 
     def close(self):
         if self._h is not None and self.pid == os.getpid():

@@ -252,6 +252,8 @@ int set_refs_locked(wdx_ctx *ctx, const double *Y, int64_t nY, int64_t L, int32_
     R.window = w_eff;
     R.penalty = penalty;
     R.content_hash = h;
+    R.any_inf = false;
+    for (int64_t i = 0; i < nY * L && !R.any_inf; ++i) R.any_inf = Y[i] - Y[i] != 0.0 && Y[i] == Y[i];   // (+-inf, not NaN)
     return WDX_SUCCESS;
 }
 
@@ -261,9 +263,22 @@ int set_refs_locked(wdx_ctx *ctx, const double *Y, int64_t nY, int64_t L, int32_
 // 0.1-0.3 ms faster that way.
 constexpr int64_t kRowMajorMinReads = 8192;
 
+static int dtw_dev_route(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin, hipStream_t stream);
+
 // DTW of device rows dX (nX, L) against the resident refs -> d_out (nX, nY) [+ argmin]
 int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin,
                    hipStream_t stream) {
+    int rc = dtw_dev_route(ctx, dX, nX, d_out, d_argmin, stream);
+    const DtwRefs &R = ctx->refs;
+    if (rc || !R.any_inf || nX == 0 || R.nY == 0) return rc;
+    // a reference with an infinite sample (never a fingerprint): pairs with the same infinity at one index are NaN in the
+    // reference and +inf out of the kernels -- settled here, then the argmin again (a NaN wins its row)
+    if ((rc = launch_dtw_equal_inf(dX, nX, R.pad, R.Lpad, R.halo, R.nY, R.L, d_out, stream))) return rc;
+    if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
+    return WDX_SUCCESS;
+}
+
+static int dtw_dev_route(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin, hipStream_t stream) {
     DtwRefs &R = ctx->refs;
     if (R.window == 0) {
         set_error("no reference set: call wdx_set_refs first");
@@ -280,7 +295,7 @@ int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int
         {
             Timed t(ctx, WDX_K_DTW, stream);
             if ((rc = launch_dtw_wavefront(dX, nX, R.pad, R.Lpad, R.halo, R.nY, L, R.window, R.penalty,
-                                           d_out, stream)))
+                                           d_out, stream, &ctx->dtw_last)))
                 return rc;
         }
         if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
@@ -292,7 +307,7 @@ int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int
         // the kernel reads the row-major fingerprints as they are (a lane owns a row): no transposed copy
         Timed t(ctx, WDX_K_DTW, stream);
         return launch_dtw(dX, 1, nX, nullptr, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, L, R.window, R.penalty, d_out,
-                          R.nY, 1, d_argmin, nullptr, 0, stream, ctx->knobs, true);
+                          R.nY, 1, d_argmin, nullptr, 0, stream, ctx->knobs, true, &ctx->dtw_last);
     }
     if (lanes_are_reads) {
         const int64_t ld = round_up(nX, 64);
@@ -309,13 +324,13 @@ int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int
             if ((rc = launch_dtw((const double *)ctx->tmp1.p, ld, nX, (const uint8_t *)ctx->tmp2.p,
                                  R.pad, R.Lpad, R.halo, R.nY, R.has_nan, L, R.window, R.penalty,
                                  d_out, R.nY, 1, nullptr, ctx->scratch.p, (int64_t)ctx->scratch.bytes,
-                                 stream, ctx->knobs)))
+                                 stream, ctx->knobs, false, &ctx->dtw_last)))
                 return rc;
             return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
         }
         return launch_dtw((const double *)ctx->tmp1.p, ld, nX, (const uint8_t *)ctx->tmp2.p, R.pad,
                           R.Lpad, R.halo, R.nY, R.has_nan, L, R.window, R.penalty, d_out, R.nY, 1,
-                          d_argmin, ctx->scratch.p, (int64_t)ctx->scratch.bytes, stream, ctx->knobs);
+                          d_argmin, ctx->scratch.p, (int64_t)ctx->scratch.bytes, stream, ctx->knobs, false, &ctx->dtw_last);
     }
     // few reads, many refs (live / per-read calls): lanes = refs, the read is the uniform operand
     const int halo = kMaxRegWindow - 1;
@@ -332,8 +347,10 @@ int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int
         Timed t(ctx, WDX_K_DTW, stream);
         if ((rc = launch_dtw(R.T, R.ldT, R.nY, R.has_nan, (const double *)ctx->tmp1.p, Lpad, halo,
                              nX, (const uint8_t *)ctx->tmp2.p, L, R.window, R.penalty, d_out, 1,
-                             R.nY, nullptr, ctx->scratch.p, (int64_t)ctx->scratch.bytes, stream, ctx->knobs)))
+                             R.nY, nullptr, ctx->scratch.p, (int64_t)ctx->scratch.bytes, stream, ctx->knobs, false,
+                             &ctx->dtw_last)))
             return rc;
+        ctx->dtw_last.layout = WDX_DTW_LAYOUT_REFS_AS_LANES;
     }
     if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
     return WDX_SUCCESS;
@@ -842,7 +859,7 @@ int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
         // failed reads carry NaN fingerprints; the DTW kernel reads the row-major rows in place and flags them
         Timed t(ctx, WDX_K_DTW, s);
         if ((rc = launch_dtw(fpt, 1, n_reads, nullptr, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
-                             R.window, R.penalty, d_dist, R.nY, 1, d_call, nullptr, 0, s, ctx->knobs, true)))
+                             R.window, R.penalty, d_dist, R.nY, 1, d_call, nullptr, 0, s, ctx->knobs, true, &ctx->dtw_last)))
             return rc;
     } else {
         {
@@ -851,8 +868,12 @@ int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
         }
         Timed t(ctx, WDX_K_DTW, s);
         if ((rc = launch_dtw(fptT, ld, n_reads, flags, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
-                             R.window, R.penalty, d_dist, R.nY, 1, d_call, nullptr, 0, s, ctx->knobs)))
+                             R.window, R.penalty, d_dist, R.nY, 1, d_call, nullptr, 0, s, ctx->knobs, false, &ctx->dtw_last)))
             return rc;
+    }
+    if (R.any_inf) {   // (see dtw_dev_locked)
+        if ((rc = launch_dtw_equal_inf(fpt, n_reads, R.pad, R.Lpad, R.halo, R.nY, R.L, d_dist, s))) return rc;
+        if ((rc = launch_argmin(d_dist, n_reads, R.nY, d_call, s))) return rc;
     }
     Timed t(ctx, WDX_K_COUNT, s);
     return launch_count_calls(d_call, d_status, n_reads, R.nY, d_counts, s);
@@ -1245,8 +1266,10 @@ int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, 
     H.status = (int32_t *)(ho + S->slot_off[7]);
     H.pred = bytes[8] ? (int32_t *)(ho + S->slot_off[8]) : nullptr;
     StreamDrain drain(S->stream);
+    S->dtw_last.family = WDX_DTW_NONE;   // (a submit that dispatches no DTW leaves the parent's record as it was)
     if ((rc = demux_batch_enqueue(S, R, *in, p, H, want_svm ? &ctx->svm : nullptr))) return rc;
     drain.done();  // in flight on purpose: wdx_demux_wait synchronises
+    if (S->dtw_last.family != WDX_DTW_NONE) ctx->dtw_last = S->dtw_last;
     S->slot_busy = true;
     return WDX_SUCCESS;
 }
@@ -1472,8 +1495,9 @@ int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
     int64_t rows = block_rows > 0 ? block_rows : (((int64_t)96 << 20) / (4 * R.nY)) / 64 * 64;
     if (rows < 2048) rows = 2048;
     if (rows > n_reads) rows = n_reads;
+    // (R.any_inf: the fused form has no distance matrix for launch_dtw_equal_inf to settle -- the row blocks do)
     const bool fused = !d_dist && R.L == 25 && R.window == 15 && !ctx->knobs.no_short_dtw && !ctx->knobs.svm_scalar && k >= 2 &&
-                       k <= 16 && ctx->svm_chunks > 0;
+                       k <= 16 && ctx->svm_chunks > 0 && !R.any_inf;
     if (!d_dist && !fused && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
     unsigned char *w = (unsigned char *)d_work;
     double *fpt = d_fpt ? d_fpt : (double *)w;
@@ -1506,7 +1530,7 @@ int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
             if ((rc = launch_dtw_svm_partial(fpt, n_reads, (const double *)ctx->svm_refs.p, R.Lpad, R.halo,
                                              (const uint8_t *)ctx->svm_refs.p + rb, R.L, R.window, R.penalty, ctx->svm_coefT,
                                              ctx->svm_chunk_ref0, ctx->svm_chunk_slot, ctx->svm_chunks, k - 1, M.pwr, M.ngamma,
-                                             (double *)ctx->out0.p, s, ctx->knobs.dtw_unfused)))
+                                             (double *)ctx->out0.p, s, ctx->knobs.dtw_unfused, &ctx->dtw_last)))
                 return rc;
         }
         {
@@ -1572,6 +1596,17 @@ int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
     }
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
+    return WDX_SUCCESS;
+}
+
+int wdx_dtw_last_launch(wdx_ctx *ctx, wdx_dtw_launch_info *info) {
+    if (int e = check_ctx(ctx)) return e;
+    if (!info) {
+        set_error("dtw_last_launch: null output");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    *info = ctx->dtw_last;
     return WDX_SUCCESS;
 }
 

@@ -82,6 +82,7 @@ struct DtwRefs {  // resident reference set, both layouts (see DESIGN.md "DTW da
     int window = 0;  // effective window (1..L), 0 = not set
     double penalty = 0;
     uint64_t content_hash = 0;
+    bool any_inf = false;  // a reference holds an infinite sample: dtw_dev_locked runs launch_dtw_equal_inf behind the DTW kernel
 };
 
 // lanes run over the columns of AT (L, ldA) [nA series] -- or, with a_rowmajor, over the rows of an (nA, L)
@@ -93,21 +94,28 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan /
                const double *Bpad, int64_t Lpad, int halo, int64_t nB, const uint8_t *b_nan,
                int64_t L, int window, double penalty, float *out, int64_t sA, int64_t sB,
                int32_t *d_argmin, void *d_scratch, int64_t scratch_bytes, hipStream_t stream,
-               const Knobs &knobs, bool a_rowmajor = false);
+               const Knobs &knobs, bool a_rowmajor = false, wdx_dtw_launch_info *info = nullptr);
 int64_t dtw_scratch_bytes(int64_t L, int window);
 // The shipped models' DTW (25 points, window 15) over references in support-vector order with the SVM decision sums in
 // its epilogue: P[slot][q][read] (wdx_dtw.hip: dtw_short_svm_kernel); gather of the resident references into that order.
 int launch_dtw_svm_partial(const double *X, int64_t nA, const double *Ypad_sv, int64_t Lpad, int halo, const uint8_t *y_nan_sv,
                            int64_t L, int window, double penalty, const double *coefT, const int32_t *chunk_ref0,
                            const int32_t *chunk_slot, int n_chunks, int km1, int pwr, float ngamma, double *P,
-                           hipStream_t stream, int unfused);
+                           hipStream_t stream, int unfused, wdx_dtw_launch_info *info = nullptr);
 int launch_gather_rows(const double *src, const uint8_t *sflag, const int32_t *d_idx, int64_t n, int64_t ld, double *dst,
                        uint8_t *dflag, hipStream_t stream);
 // anti-diagonal wavefront kernel for small problems (latency path)
 bool dtw_wavefront_eligible(int64_t nX, int64_t nY, int64_t L, int window, const Knobs &knobs);
 int launch_dtw_wavefront(const double *X, int64_t nX, const double *Ypad, int64_t Lpad, int halo,
                          int64_t nY, int64_t L, int window, double penalty, float *out,
-                         hipStream_t stream);
+                         hipStream_t stream, wdx_dtw_launch_info *info = nullptr);
+
+// Equal infinities in a read and a reference at ONE index k: x[k] - y[k] is NaN without a NaN sample.  The reference's
+// `if (t < minv)` keeps a NaN diagonal predecessor, so cell (k, k) poisons the main diagonal and the distance is NaN; v_min_f64
+// drops the NaN and the DTW kernels return +inf (row k holds nothing finite).  This pass turns exactly those +inf entries of
+// out (nX, nY) row-major into NaN.  Run only when a reference holds an infinity (DtwRefs::any_inf): never on the product path.
+int launch_dtw_equal_inf(const double *X, int64_t nX, const double *Ypad, int64_t Lpad, int halo, int64_t nY, int64_t L,
+                         float *out, hipStream_t stream);
 
 // (n, L) row-major -> (L, ld) read-minor, plus per-series NaN flag (nullable)
 int launch_transpose(const double *src, int64_t n, int64_t L, double *dstT, int64_t ld,

@@ -48,6 +48,7 @@ struct wdx_ctx {
     bool last_stream_valid = false;
     wdx::Knobs knobs;
     wdx::DtwRefs refs;
+    wdx_dtw_launch_info dtw_last{};  // what the latest DTW dispatch launched (wdx_dtw_last_launch)
     wdx::Buffer refs_pad, refs_T, refs_nan;
     // host-buffer call workspaces
     wdx::Buffer in0, in1, in2, in3, out0, out1, out2, out3, tmp0, tmp1, tmp2, scratch, fp_ws, svm_buf, ref_buf;

@@ -515,6 +515,31 @@ __global__ __launch_bounds__(256) void dtw_wavefront_kernel(
     }
 }
 
+// see wdx_common.h: launch_dtw_equal_inf
+__global__ __launch_bounds__(256) void dtw_equal_inf_kernel(const double *__restrict__ X, int64_t nX, const double *__restrict__ Ypad,
+                                                            int64_t Lpad, int halo, int64_t nY, int L, float *__restrict__ out) {
+    const int64_t npairs = nX * nY;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * blockDim.x) {
+        if (out[q] != __builtin_huge_valf()) continue;   // (finite, NaN already, or -- never -- negative)
+        const double *__restrict__ x = X + (q / nY) * L;
+        const double *__restrict__ y = Ypad + (q % nY) * Lpad + halo;
+        bool hit = false;
+        for (int k = 0; k < L; ++k) hit |= x[k] == y[k] && (x[k] == WDX_INF || x[k] == -WDX_INF);
+        if (hit) out[q] = __builtin_nanf("");
+    }
+}
+
+int launch_dtw_equal_inf(const double *X, int64_t nX, const double *Ypad, int64_t Lpad, int halo, int64_t nY, int64_t L,
+                         float *out, hipStream_t stream) {
+    const int64_t npairs = nX * nY;
+    if (npairs == 0) return WDX_SUCCESS;
+    int64_t blocks = (npairs + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(dtw_equal_inf_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, X, nX, Ypad, Lpad, halo, nY, (int)L, out);
+    WDX_HIP_TRY(hipGetLastError());
+    return WDX_SUCCESS;
+}
+
 int64_t dtw_scratch_bytes(int64_t L, int window) {
     if (window <= kMaxRegWindow) return 0;
     return 2 * (L + 1) * 65536 * (int64_t)sizeof(double);
@@ -523,11 +548,13 @@ int64_t dtw_scratch_bytes(int64_t L, int window) {
 // Row-major X (nX, L) against padded refs; out (nX, nY) row-major.  Caller checked eligibility.
 int launch_dtw_wavefront(const double *X, int64_t nX, const double *Ypad, int64_t Lpad, int halo,
                          int64_t nY, int64_t L, int window, double penalty, float *out,
-                         hipStream_t stream) {
+                         hipStream_t stream, wdx_dtw_launch_info *info) {
     const int w = (window <= 0 || window > L) ? (int)L : window;
     const int64_t npairs = nX * nY;
     if (npairs == 0) return WDX_SUCCESS;
     const size_t lds = (size_t)kWfPairsPerBlock * 2 * (size_t)L * sizeof(double);
+    if (info)
+        *info = {WDX_DTW_WAVEFRONT, 0, 0, WDX_DTW_LAYOUT_ROW_MAJOR, 0, 1, 1, w, (npairs + kWfPairsPerBlock - 1) / kWfPairsPerBlock, 1};
     hipLaunchKernelGGL(dtw_wavefront_kernel, dim3((unsigned)((npairs + kWfPairsPerBlock - 1) / kWfPairsPerBlock)),
                        dim3(256), lds, stream, X, nX, Ypad, Lpad, halo, (int)nY, (int)L, w,
                        penalty * penalty, out);
@@ -544,7 +571,7 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan, 
                int64_t Lpad, int halo, int64_t nB, const uint8_t *b_nan, int64_t L, int window,
                double penalty, float *out, int64_t sA, int64_t sB, int32_t *d_argmin,
                void *d_scratch, int64_t scratch_bytes, hipStream_t stream, const Knobs &knobs,
-               bool a_rowmajor) {
+               bool a_rowmajor, wdx_dtw_launch_info *info) {
     if (nA == 0 || nB == 0) return WDX_SUCCESS;
     if (L <= 0) {
         set_error("DTW series length must be positive");
@@ -566,9 +593,14 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan, 
             set_error("fused argmin is not available on the scratch-row DTW path");
             return WDX_ERR_INVALID;
         }
+        if (info) *info = {WDX_DTW_SCRATCH, 0, 0, WDX_DTW_LAYOUT_READ_MINOR, 0, 0, (int32_t)nB, w, 0, 1};
         for (int64_t a_base = 0; a_base < nA; a_base += nT) {
             int64_t n = nA - a_base < nT ? nA - a_base : nT;
             dim3 grid((unsigned)((n + 63) / 64));
+            if (info) {
+                ++info->launches;
+                info->grid_x = grid.x;
+            }
             hipLaunchKernelGGL(dtw_scratch_kernel, grid, dim3(64), 0, stream, AT, ldA, a_base, nA,
                                a_nan, Bpad, Lpad, halo, (int)nB, b_nan, (int)L, w, p2, out, sA, sB,
                                (double *)d_scratch, nT);
@@ -608,7 +640,10 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan, 
         return WDX_ERR_INVALID;
     }
     dim3 grid((unsigned)gx, (unsigned)((nB + rpb - 1) / rpb));
+    const int32_t layout = a_rowmajor ? WDX_DTW_LAYOUT_ROW_MAJOR : WDX_DTW_LAYOUT_READ_MINOR;
+    if (info) *info = {WDX_DTW_BAND, 0, 0, layout, fused_argmin != nullptr, 1, rpb, w, grid.x, grid.y};
     if (L == 25 && w == 15 && !knobs.no_short_dtw) {
+        if (info) info->family = WDX_DTW_SHORT, info->band_w = 15, info->exact_w = 1;
         if (a_rowmajor)
             hipLaunchKernelGGL((dtw_short_kernel<25, 15, true>), grid, dim3(64), 0, stream, AT, ldA, nA, a_nan, Bpad,
                                Lpad, halo, (int)nB, b_nan, p2, out, sA, sB, fused_argmin, rpb, knobs.dtw_unfused);
@@ -621,6 +656,7 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan, 
     }
 #define WDX_LAUNCH_BAND(WW, EX)                                                                          \
     do {                                                                                                 \
+        if (info) info->band_w = WW, info->exact_w = EX;                                                 \
         if (a_rowmajor)                                                                                  \
             hipLaunchKernelGGL((dtw_band_kernel<WW, EX, true>), grid, dim3(64), 0, stream, AT, ldA, nA,  \
                                a_nan, Bpad, Lpad, halo, (int)nB, b_nan, (int)L, w, p2, out, sA, sB,      \
@@ -706,7 +742,7 @@ __global__ __launch_bounds__(64, 3) void dtw_short_svm_kernel(DtwSvmArgs G) {
 int launch_dtw_svm_partial(const double *X, int64_t nA, const double *Ypad_sv, int64_t Lpad, int halo, const uint8_t *y_nan_sv,
                            int64_t L, int window, double penalty, const double *coefT, const int32_t *chunk_ref0,
                            const int32_t *chunk_slot, int n_chunks, int km1, int pwr, float ngamma, double *P,
-                           hipStream_t stream, int unfused) {
+                           hipStream_t stream, int unfused, wdx_dtw_launch_info *info) {
     if (nA == 0 || n_chunks == 0) return WDX_SUCCESS;
     if (L != 25 || window != 15 || km1 < 1 || km1 > 15) {
         set_error("the fused DTW + SVM path serves the shipped shape (25-point fingerprints, window 15, <= 16 classes)");
@@ -714,6 +750,7 @@ int launch_dtw_svm_partial(const double *X, int64_t nA, const double *Ypad_sv, i
     }
     DtwSvmArgs G{X, nA, Ypad_sv, Lpad, halo, y_nan_sv, penalty * penalty, coefT, chunk_ref0, chunk_slot, km1, pwr, ngamma, P, unfused};
     dim3 grid((unsigned)((nA + 63) / 64), (unsigned)n_chunks);
+    if (info) *info = {WDX_DTW_SHORT_SVM, 15, 1, WDX_DTW_LAYOUT_ROW_MAJOR, 0, 1, 0, 15, grid.x, grid.y};
     hipLaunchKernelGGL((dtw_short_svm_kernel<25, 15>), grid, dim3(64), 0, stream, G);
     WDX_HIP_TRY(hipGetLastError());
     return WDX_SUCCESS;
