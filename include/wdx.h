@@ -132,6 +132,7 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
                                          * reference's are run again on its six operations (wdx_dtw.hip: dtw_unsettled) | 1 the six
                                          * operations only (A/B) | 2 fused and every pair run again (tests) | 3 fused, never run again
                                          * (diagnostic: NOT the reference's results) */
+#define WDX_OPT_MLP_CHUNK_ROWS 17       /* wdx_dtw_mlp_predict: rows per DTW + MLP pass (0 = built-in; tests walk several chunks) */
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -459,6 +460,60 @@ int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
  * set (wdx_set_refs with model._X, window, penalty) -> SVM tail.  Outputs host, nullable. */
 int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf);
 
+/* ---- classifier tail of DTW_MLP.predict (models/dtw_mlp.py:74-93 + models/utils.py:45-61): the float32 distance
+ *      rows -> zero or more StandardScaler steps -> MLPClassifier.predict_proba -> argmax, label map, top1-top2 margin,
+ *      per-class thresholds.  The model lives in its own slot of the context: a resident SVM is untouched.
+ *      Working dtype = result_type(float32, coefs_ dtype): a float32 model runs every layer in float32 (matrix cores:
+ *      v_mfma_f32_16x16x4_f32), a float64 model in float64 (v_mfma_f64_16x16x4_f64).  Probabilities and margins cross
+ *      the ABI as float64; for a float32 model each is the float32 result widened exactly.
+ *      Limits: 1..WDX_MLP_MAX_LAYERS-1 hidden layers of 1..WDX_MLP_MAX_WIDTH units, k = 2..16 classes (softmax over k
+ *      output units, or one logistic output unit for k = 2), at most WDX_MLP_MAX_SCALERS scaler steps; beyond them
+ *      WDX_ERR_UNSUPPORTED, a malformed model WDX_ERR_INVALID.  A refused model leaves the previous one resident.
+ *      A row whose (scaled) input holds a NaN or an infinity -- scikit-learn refuses the whole call -- gets pred -1 and
+ *      NaN probabilities / margin and is counted. */
+#define WDX_MLP_MAX_LAYERS 5   /* weight matrices: hidden layers + the output layer */
+#define WDX_MLP_MAX_WIDTH 512
+#define WDX_MLP_MAX_SCALERS 4
+#define WDX_MLP_ACT_IDENTITY 0
+#define WDX_MLP_ACT_LOGISTIC 1
+#define WDX_MLP_ACT_TANH 2
+#define WDX_MLP_ACT_RELU 3
+typedef struct wdx_mlp_model {
+    int32_t n_layers;          /* weight matrices = len(coefs_), 2..WDX_MLP_MAX_LAYERS                               */
+    int32_t dtype_bytes;       /* working dtype: 4 = float32, 8 = float64                                            */
+    int32_t hidden_activation; /* WDX_MLP_ACT_* of the hidden layers (MLPClassifier.activation)                      */
+    int32_t n_classes;         /* k = len(classes_); output units: k (softmax) or 1 (logistic, k == 2)               */
+    int32_t n_scalers;         /* StandardScaler steps ahead of the MLP, 0..WDX_MLP_MAX_SCALERS                     */
+    int32_t pad_;
+    int32_t sizes[WDX_MLP_MAX_LAYERS + 1]; /* sizes[0] = n_in = len(model._X), sizes[i + 1] = fan-out of layer i       */
+    const void *coefs[WDX_MLP_MAX_LAYERS];      /* layer i: (sizes[i], sizes[i + 1]) row-major, working dtype          */
+    const void *intercepts[WDX_MLP_MAX_LAYERS]; /* layer i: sizes[i + 1], working dtype                                 */
+    const double *scaler_mean[WDX_MLP_MAX_SCALERS];  /* step s: mean_ [n_in] float64, NULL = with_mean False            */
+    const double *scaler_scale[WDX_MLP_MAX_SCALERS]; /* step s: scale_ [n_in] float64, NULL = with_std False            */
+    const int32_t *label_map;  /* [k] class index -> barcode label (model.label_mapper); nullable                     */
+    const double *thresholds;  /* [k] model.thresholds; nullable = no thresholding                                    */
+} wdx_mlp_model;
+/* Copies every array at set time (synchronises the context's stream first). */
+int wdx_mlp_set_model(wdx_ctx *ctx, const wdx_mlp_model *m);
+/* d_dist: (n, n_in) float32 DEVICE rows; outputs DEVICE, nullable: d_prob (n,k) float64, d_pred int32[n], d_conf
+ * float64[n]; d_n_nonfinite: nullable DEVICE int64, INCREMENTED by the rows with a non-finite input.  Enqueued on
+ * `stream`; no synchronisation.  WDX_ERR_NO_REFS without a model. */
+int wdx_mlp_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred, double *d_conf,
+                        int64_t *d_n_nonfinite, void *stream);
+/* DTW_MLP.predict on host buffers: X (n, L) float64 fingerprints -> DTW against the resident reference set (wdx_set_refs
+ * with model._X, window, penalty; its nY must equal n_in) -> MLP tail, in row chunks whose distances stay on the device.
+ * Outputs host, nullable; n_nonfinite (nullable, host) receives the count of rows with a non-finite distance. */
+int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf,
+                        int64_t *n_nonfinite);
+/* wdx_demux_svm_dev's row-block path with the MLP tail: raw adapter rows -> fingerprint -> DTW row blocks of `block_rows`
+ * reads (0 = blocks of <= 96 MiB of distances) -> MLP tail.  Reads whose fingerprint failed get pred -1 and NaN and are
+ * not counted in d_n_nonfinite (nullable DEVICE int64, incremented).  d_work: wdx_demux_workspace_bytes(n_reads, K). */
+int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                      int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
+                      const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
+                      double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
+                      int64_t block_rows, void *stream);
+
 /* ---- multi-GPU: the only exchange on the path ---------------------------------------
  * Reads shard over one process per GPU with no data-path collective; after the last batch the per-barcode
  * call histogram -- the engine's form of the reference's shared run counters `ridx_dict`
@@ -500,6 +555,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_FINGERPRINT_CLIP 7 /* clip_bounds_kernel alone (median / MAD / clip bounds ahead of the main kernel) */
 #define WDX_K_FINGERPRINT_TAIL 8 /* fingerprint_split_tail_kernel alone (the split main kernel's second half; its time is part of
                                     WDX_K_FINGERPRINT_MAIN, which brackets the tile-kernel / tail-kernel launch pairs) */
+#define WDX_K_MLP 9              /* the MLP tail kernel (wdx_mlp_predict_dev, wdx_dtw_mlp_predict, wdx_demux_mlp_dev) */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

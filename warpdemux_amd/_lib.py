@@ -24,6 +24,7 @@ WDX_ERR_UNSUPPORTED = -4
 WDX_ERR_NO_REFS = -5
 
 K_FINGERPRINT, K_DTW, K_TRANSPOSE, K_COUNT, K_SVM, K_REDUCE, K_FINGERPRINT_MAIN, K_FINGERPRINT_CLIP, K_FINGERPRINT_TAIL = 0, 1, 2, 3, 4, 5, 6, 7, 8
+K_MLP = 9
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -37,6 +38,7 @@ OPT_NO_WAVE_CLIP_LONG = 13
 OPT_NO_CLIP_REUSE = 14
 OPT_NO_SPLIT_TAIL = 15
 OPT_DTW_UNFUSED = 16
+OPT_MLP_CHUNK_ROWS = 17
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -54,6 +56,7 @@ EXPORTS = [
     "wdx_synth_fill_dev", "wdx_fingerprint_profile_dev", "wdx_calib_read_dev", "wdx_selftest_score_dev", "wdx_selftest_clip_dev",
     "wdx_feeder_ring_bytes", "wdx_feeder_ring_init", "wdx_feeder_serve", "wdx_feeder_run", "wdx_feeder_demux", "wdx_feeder_predict", "wdx_feeder_stop",
     "wdx_feeder_served", "wdx_feeder_stats", "wdx_feeder_alive", "wdx_feeder_selftest",
+    "wdx_mlp_set_model", "wdx_mlp_predict_dev", "wdx_dtw_mlp_predict", "wdx_demux_mlp_dev",
 ]
 
 
@@ -133,6 +136,23 @@ class SvmModelC(C.Structure):
         ("probB", C.c_void_p),
         ("label_map", C.c_void_p),
         ("thresholds", C.c_void_p),
+    ]
+
+
+# wdx_mlp_model (include/wdx.h)
+MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_SCALERS = 5, 512, 4
+MLP_ACT = {"identity": 0, "logistic": 1, "tanh": 2, "relu": 3}   # WDX_MLP_ACT_*
+
+
+class MlpModelC(C.Structure):
+    """wdx_mlp_model (include/wdx.h)"""
+
+    _fields_ = [
+        ("n_layers", C.c_int32), ("dtype_bytes", C.c_int32), ("hidden_activation", C.c_int32), ("n_classes", C.c_int32),
+        ("n_scalers", C.c_int32), ("pad_", C.c_int32), ("sizes", C.c_int32 * (MLP_MAX_LAYERS + 1)),
+        ("coefs", C.c_void_p * MLP_MAX_LAYERS), ("intercepts", C.c_void_p * MLP_MAX_LAYERS),
+        ("scaler_mean", C.c_void_p * MLP_MAX_SCALERS), ("scaler_scale", C.c_void_p * MLP_MAX_SCALERS),
+        ("label_map", C.c_void_p), ("thresholds", C.c_void_p),
     ]
 
 
@@ -362,6 +382,15 @@ def load():
         L.wdx_feeder_alive.argtypes = [vp]
         L.wdx_feeder_selftest.restype = C.c_int
         L.wdx_feeder_selftest.argtypes = [vp, i32]
+        L.wdx_mlp_set_model.restype = C.c_int
+        L.wdx_mlp_set_model.argtypes = [vp, P(MlpModelC)]
+        L.wdx_mlp_predict_dev.restype = C.c_int
+        L.wdx_mlp_predict_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
+        L.wdx_dtw_mlp_predict.restype = C.c_int
+        L.wdx_dtw_mlp_predict.argtypes = [vp, vp, i64, vp, vp, vp, P(i64)]
+        L.wdx_demux_mlp_dev.restype = C.c_int
+        L.wdx_demux_mlp_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp, vp, vp, vp,
+                                        i64, vp]
         _lib = L
         return L
 

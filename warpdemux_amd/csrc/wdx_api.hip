@@ -427,7 +427,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     comm_destroy(ctx);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->svm_fused, &ctx->svm_refs,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf})
         b->release();
     ctx->pin_in.release();
@@ -466,6 +466,7 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
         case WDX_OPT_NO_SPLIT_TAIL: ctx->knobs.no_split = value != 0; break;
         case WDX_OPT_DTW_UNFUSED: ctx->knobs.dtw_unfused = (value >= 0 && value <= 3) ? (int)value : 0; break;
         case WDX_OPT_MAX_LAUNCH_SLICE: ctx->knobs.max_launch_slice = value > 0 ? value : 0; break;
+        case WDX_OPT_MLP_CHUNK_ROWS: ctx->knobs.mlp_chunk_rows = value > 0 ? value : 0; break;
         default:
             set_error("unknown option %d", (int)option);
             return WDX_ERR_INVALID;
@@ -1596,6 +1597,237 @@ int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
     }
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
+    return WDX_SUCCESS;
+}
+
+int wdx_mlp_set_model(wdx_ctx *ctx, const wdx_mlp_model *m) {
+    WDX_ENTER(ctx);
+    // every check before anything of the resident model is touched: a refused model keeps the previous one
+    if (!m || (m->dtype_bytes != 4 && m->dtype_bytes != 8) || m->n_classes < 2 || m->n_layers < 1 || m->n_scalers < 0 ||
+        m->hidden_activation < WDX_MLP_ACT_IDENTITY || m->hidden_activation > WDX_MLP_ACT_RELU) {
+        set_error("mlp_set_model: need a float32 / float64 model with >= 2 classes, layers and a known activation");
+        return WDX_ERR_INVALID;
+    }
+    const int nl = m->n_layers, k = m->n_classes;
+    if (nl < 2 || nl > WDX_MLP_MAX_LAYERS) {
+        set_error("mlp_set_model: %d hidden layers (1..%d supported)", nl - 1, WDX_MLP_MAX_LAYERS - 1);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (k > 16) {
+        set_error("mlp_set_model: %d classes (2..16 supported)", k);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (m->n_scalers > WDX_MLP_MAX_SCALERS) {
+        set_error("mlp_set_model: %d scaler steps (at most %d supported)", m->n_scalers, WDX_MLP_MAX_SCALERS);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    for (int i = 0; i <= nl; ++i)
+        if (m->sizes[i] < 1) {
+            set_error("mlp_set_model: layer size %d of entry %d", m->sizes[i], i);
+            return WDX_ERR_INVALID;
+        }
+    for (int i = 0; i < nl; ++i)
+        if (!m->coefs[i] || !m->intercepts[i]) {
+            set_error("mlp_set_model: layer %d has no coefficients / intercepts", i);
+            return WDX_ERR_INVALID;
+        }
+    const int nout = m->sizes[nl];
+    if (nout != k && !(nout == 1 && k == 2)) {
+        set_error("mlp_set_model: %d output units for %d classes", nout, k);
+        return WDX_ERR_INVALID;
+    }
+    int widest = 16;
+    for (int i = 1; i < nl; ++i) {
+        if (m->sizes[i] > WDX_MLP_MAX_WIDTH) {
+            set_error("mlp_set_model: hidden layer of %d units (at most %d supported)", m->sizes[i], WDX_MLP_MAX_WIDTH);
+            return WDX_ERR_UNSUPPORTED;
+        }
+        widest = std::max(widest, m->sizes[i]);
+    }
+    const int64_t n_in = m->sizes[0];
+    const size_t T = (size_t)m->dtype_bytes;
+    // one device block: [doubles: scaler mean / scale steps | thresholds][working dtype: W_i | b_i ...][int32: label map]
+    size_t nd = (m->thresholds ? (size_t)k : 0);
+    for (int s_ = 0; s_ < m->n_scalers; ++s_) nd += (m->scaler_mean[s_] ? n_in : 0) + (m->scaler_scale[s_] ? n_in : 0);
+    size_t nw = 0;
+    for (int i = 0; i < nl; ++i) nw += (size_t)m->sizes[i] * m->sizes[i + 1] + (size_t)m->sizes[i + 1];
+    const size_t bytes = nd * 8 + round_up((int64_t)(nw * T), 8) + (m->label_map ? (size_t)k * 4 : 0);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((rc = use_stream(ctx, ctx->stream))) return rc;
+    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
+    WDX_HIP_TRY(hipDeviceSynchronize());  // (nor one on a caller's stream: the model is replaced in place)
+    std::vector<unsigned char> h(bytes);
+    ctx->mlp_set = false;  // not set until the upload below has succeeded
+    if ((rc = ctx->mlp_buf.ensure(bytes))) return rc;
+    MlpDev M{};
+    unsigned char *dev = (unsigned char *)ctx->mlp_buf.p;
+    size_t o = 0;
+    for (int s_ = 0; s_ < m->n_scalers; ++s_) {
+        for (int which = 0; which < 2; ++which) {
+            const double *src = which ? m->scaler_scale[s_] : m->scaler_mean[s_];
+            if (!src) continue;
+            memcpy(h.data() + o, src, (size_t)n_in * 8);
+            (which ? M.scale[s_] : M.mean[s_]) = (const double *)(dev + o);
+            o += (size_t)n_in * 8;
+        }
+    }
+    if (m->thresholds) {
+        memcpy(h.data() + o, m->thresholds, (size_t)k * 8);
+        M.thresholds = (const double *)(dev + o);
+        o += (size_t)k * 8;
+    }
+    for (int i = 0; i < nl; ++i) {
+        const size_t wb = (size_t)m->sizes[i] * m->sizes[i + 1] * T, bb = (size_t)m->sizes[i + 1] * T;
+        memcpy(h.data() + o, m->coefs[i], wb);
+        M.coef[i] = dev + o;
+        o += wb;
+        memcpy(h.data() + o, m->intercepts[i], bb);
+        M.bias[i] = dev + o;
+        o += bb;
+    }
+    o = (size_t)round_up((int64_t)o, 8);
+    if (m->label_map) {
+        memcpy(h.data() + o, m->label_map, (size_t)k * 4);
+        M.label_map = (const int32_t *)(dev + o);
+    }
+    WDX_HIP_TRY(hipMemcpy(ctx->mlp_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    for (int i = 0; i <= nl; ++i) M.sizes[i] = m->sizes[i];
+    M.n_layers = nl;
+    M.n_scalers = m->n_scalers;
+    M.dtype_bytes = m->dtype_bytes;
+    M.hidden_act = m->hidden_activation;
+    M.k = k;
+    M.ld = (int)round_up(widest, 16) + 1;
+    ctx->mlp = M;
+    ctx->mlp_set = true;
+    return WDX_SUCCESS;
+}
+
+int wdx_mlp_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred, double *d_conf,
+                        int64_t *d_n_nonfinite, void *stream) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->mlp_set) {
+        set_error("no MLP model: call wdx_mlp_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (n < 0 || (n > 0 && !d_dist)) {
+        set_error("mlp_predict_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
+    Timed t(ctx, WDX_K_MLP, (hipStream_t)stream);
+    return launch_mlp_predict(ctx->mlp, d_dist, n, nullptr, d_prob, d_pred, d_conf, d_n_nonfinite, (hipStream_t)stream);
+}
+
+int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf,
+                        int64_t *n_nonfinite) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if (R.window == 0 || !ctx->mlp_set) {
+        set_error("dtw_mlp_predict needs wdx_set_refs and wdx_mlp_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (R.nY != ctx->mlp.sizes[0]) {
+        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
+        return WDX_ERR_INVALID;
+    }
+    if (n < 0 || (n > 0 && !X)) {
+        set_error("dtw_mlp_predict: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (n_nonfinite) *n_nonfinite = 0;
+    if (n == 0) return WDX_SUCCESS;
+    hipStream_t s = ctx->stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int k = ctx->mlp.k;
+    // rows per pass: the (rows, nY) float32 distance block stays <= 1 GiB and never leaves HBM
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)1 << 30) / (4 * (int64_t)R.nY)));
+    if (ctx->knobs.mlp_chunk_rows > 0) chunk = std::min<int64_t>(chunk, ctx->knobs.mlp_chunk_rows);
+    if ((rc = ctx->in0.ensure((size_t)(chunk * R.L) * 8))) return rc;
+    if ((rc = ctx->out0.ensure((size_t)(chunk * R.nY) * 4))) return rc;
+    if ((rc = ctx->out1.ensure((size_t)chunk * k * 8))) return rc;
+    if ((rc = ctx->out2.ensure((size_t)chunk * 4))) return rc;
+    if ((rc = ctx->out3.ensure((size_t)chunk * 8 + 8))) return rc;
+    int64_t *d_cnt = (int64_t *)((unsigned char *)ctx->out3.p + (size_t)chunk * 8);
+    int64_t h_cnt = 0;
+    StreamDrain drain(s);
+    WDX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t m = std::min(chunk, n - r0);
+        WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X + r0 * R.L, (size_t)(m * R.L) * 8, hipMemcpyHostToDevice, s));
+        if ((rc = dtw_dev_locked(ctx, (const double *)ctx->in0.p, m, (float *)ctx->out0.p, nullptr, s))) return rc;
+        {
+            Timed t(ctx, WDX_K_MLP, s);
+            if ((rc = launch_mlp_predict(ctx->mlp, (const float *)ctx->out0.p, m, nullptr, (double *)ctx->out1.p,
+                                         (int32_t *)ctx->out2.p, (double *)ctx->out3.p, d_cnt, s)))
+                return rc;
+        }
+        if (prob) WDX_HIP_TRY(hipMemcpyAsync(prob + r0 * k, ctx->out1.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
+        if (pred) WDX_HIP_TRY(hipMemcpyAsync(pred + r0, ctx->out2.p, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+        if (conf) WDX_HIP_TRY(hipMemcpyAsync(conf + r0, ctx->out3.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    }
+    WDX_HIP_TRY(hipMemcpyAsync(&h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipStreamSynchronize(s));
+    drain.done();
+    if (n_nonfinite) *n_nonfinite = h_cnt;
+    return WDX_SUCCESS;
+}
+
+int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                      int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
+                      const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
+                      double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
+                      int64_t block_rows, void *stream) {
+    WDX_ENTER(ctx);
+    if (n_reads < 0 || !p || block_rows < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
+        set_error("demux_mlp_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if (R.window == 0 || !ctx->mlp_set) {
+        set_error("demux_mlp_dev needs wdx_set_refs and wdx_mlp_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (R.nY != ctx->mlp.sizes[0]) {
+        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
+        return WDX_ERR_INVALID;
+    }
+    const int64_t K = p->barcode_num_events;
+    if (K != R.L) {
+        set_error("barcode_num_events (%lld) != reference length (%lld)", (long long)K, (long long)R.L);
+        return WDX_ERR_INVALID;
+    }
+    if (n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
+    const int k = ctx->mlp.k;
+    // rows per block: the (rows, nY) float32 distances of a block stay in the memory-side cache (<= 96 MiB)
+    int64_t rows = block_rows > 0 ? block_rows : std::max<int64_t>(2048, (((int64_t)96 << 20) / (4 * R.nY)) / 64 * 64);
+    if (rows > n_reads) rows = n_reads;
+    if (!d_dist && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
+    unsigned char *w = (unsigned char *)d_work;
+    double *fpt = d_fpt ? d_fpt : (double *)w;
+    void *fp_ws = w + ((n_reads * K * 8 + 255) / 256) * 256;   // (fingerprint workspace behind the fingerprints)
+    {
+        Timed t(ctx, WDX_K_FINGERPRINT, s);
+        if ((rc = launch_fingerprint(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, *p,
+                                     fpt, nullptr, nullptr, d_status, s, fp_ws, ctx->knobs, &t.n_launches, nullptr, 0, 0,
+                                     nullptr, &t.main, (double *)ctx->fp_big.p)))
+            return rc;
+    }
+    for (int64_t r0 = 0; r0 < n_reads; r0 += rows) {
+        const int64_t m = std::min(rows, n_reads - r0);
+        float *dblk = d_dist ? d_dist + r0 * R.nY : (float *)ctx->out0.p;
+        if ((rc = dtw_dev_locked(ctx, fpt + r0 * K, m, dblk, nullptr, s))) return rc;
+        Timed t(ctx, WDX_K_MLP, s);
+        if ((rc = launch_mlp_predict(ctx->mlp, dblk, m, d_status + r0, d_prob ? d_prob + r0 * k : nullptr,
+                                     d_pred ? d_pred + r0 : nullptr, d_conf ? d_conf + r0 : nullptr, d_n_nonfinite, s)))
+            return rc;
+    }
     return WDX_SUCCESS;
 }
 

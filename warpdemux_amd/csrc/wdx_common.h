@@ -41,6 +41,7 @@ struct Knobs {
     int64_t max_launch_slice = 0;    // WDX_OPT_MAX_LAUNCH_SLICE: upper bound of one launch slice of the fingerprint chain (0 = built-in)
     bool no_split = false;           // WDX_OPT_NO_SPLIT_TAIL: the main fast kernel in one piece (A/B, tests)
     int dtw_unfused = 0;             // WDX_OPT_DTW_UNFUSED: 0 fused cells + settle | 1 six operations only | 2 / 3 tests, diagnostics
+    int64_t mlp_chunk_rows = 0;      // WDX_OPT_MLP_CHUNK_ROWS: rows per pass of wdx_dtw_mlp_predict (0 = built-in)
 };
 
 // A launch over more workgroups than grid.x admits is cut into slices (block_base != 0 from the second on).  The built-in
@@ -192,6 +193,22 @@ int launch_svm_finish(const SvmDev &M, const double *d_P, int halves, int64_t n,
                       double *d_conf, hipStream_t stream);
 int launch_svm_mask_failed(const int32_t *d_status, int64_t n, int k, double *d_prob, int32_t *d_pred, double *d_conf,
                            hipStream_t stream);
+
+// ---- MLP tail (wdx_mlp.hip) -----------------------------------------------------------------------
+constexpr int kMaxMlpWidth = 512;  // widest hidden layer (WDX_MLP_MAX_WIDTH)
+struct MlpDev {  // device-resident [StandardScaler]* + MLPClassifier + label map / thresholds
+    const void *coef[WDX_MLP_MAX_LAYERS], *bias[WDX_MLP_MAX_LAYERS];  // working dtype
+    const double *mean[WDX_MLP_MAX_SCALERS], *scale[WDX_MLP_MAX_SCALERS];  // nullable per step
+    const int32_t *label_map;  // nullable
+    const double *thresholds;  // nullable
+    int sizes[WDX_MLP_MAX_LAYERS + 1];
+    int n_layers, n_scalers, dtype_bytes, hidden_act, k;
+    int ld;  // row stride (elements) of the two LDS activation buffers
+};
+// d_status (nullable): rows with status != WDX_READ_OK get pred -1 and NaN, uncounted; d_n_nonfinite (nullable) is
+// INCREMENTED by the rows whose (scaled) input holds a NaN or an infinity
+int launch_mlp_predict(const MlpDev &M, const float *d_dist, int64_t n, const int32_t *d_status, double *d_prob,
+                       int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, hipStream_t stream);
 
 // row r of a page-locked (n, stride) host minibatch, samples [st[r], st[r] + len[r]) -> dst + off[r] (device), read over
 // the bus by a copy kernel

@@ -23,7 +23,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 9;
+constexpr int kNumTimed = 10;
 
 // RAII: make the context's device current for the duration of one entry point and put the caller's
 // device back afterwards (a host thread that also drives torch must not find its device switched).
@@ -68,6 +68,10 @@ struct wdx_ctx {
     const int32_t *svm_chunk_ref0 = nullptr, *svm_chunk_slot = nullptr;
     int svm_chunks = 0, svm_halves = 0;
     int64_t svm_refs_gen = -1, svm_model_gen = 0, svm_refs_model_gen = -1;
+    // MLP tail (wdx_mlp_set_model): its own slot, independent of the SVM's
+    wdx::Buffer mlp_buf;
+    wdx::MlpDev mlp{};
+    bool mlp_set = false;
     wdx::Comm *comm = nullptr;
     // pipelined minibatches (wdx_demux_submit / wdx_demux_wait): up to WDX_MAX_SLOTS child contexts, each with its own stream and
     // workspaces, sharing this context's resident reference set; the fields below describe a child's batch in flight

@@ -200,6 +200,54 @@ class DemuxEngine:
             self._stream()))
         return out
 
+    # -- MLP classifier tail (DTW_MLP) -------------------------------------------------
+    def set_mlp(self, model):
+        """``model``: a warpdemux_amd.models.DTW_MLP whose ``_X`` is the resident reference set."""
+        if model._X.shape != (self.nY, self.K):
+            raise ValueError("the MLP's training set must be the engine's reference set")
+        self._mlp_model = model   # keeps the host arrays alive during the upload
+        m = model.to_c()
+        self.ctx._mlp_owner = None
+        _lib.check(self.L.wdx_mlp_set_model(self.ctx.handle, C.byref(m)))
+        self.ctx._mlp_owner = model
+        self.mlp_classes = model.k
+
+    def mlp_predict(self, dist, n_nonfinite=None):
+        """(prob f64 (n,k), pred i32 (n,), conf f64 (n,)) from a device (n, nY) float32 distance matrix (wdx_mlp_predict_dev);
+        ``n_nonfinite``: optional int64 (1,) device tensor, incremented by the rows with a non-finite input."""
+        torch = self.torch
+        n = int(dist.shape[0])
+        prob = torch.empty((n, self.mlp_classes), dtype=torch.float64, device=self.tdev)
+        pred = torch.empty(n, dtype=torch.int32, device=self.tdev)
+        conf = torch.empty(n, dtype=torch.float64, device=self.tdev)
+        _lib.check(self.L.wdx_mlp_predict_dev(self.ctx.handle, _dp(dist), n, _dp(prob), _dp(pred), _dp(conf),
+                                              _dp(n_nonfinite), self._stream()))
+        return prob, pred, conf
+
+    def demux_mlp(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, want_dist=False,
+                  want_fpt=False, block_rows: int = 0, n_nonfinite=None, out=None):
+        """demux_svm with the MLP tail (wdx_demux_mlp_dev): raw rows -> fingerprint -> DTW row blocks -> MLP tail.  Returns
+        (prob f64 (n,k), pred i32 (n,), conf f64 (n,), status i32 (n,), dist f32 (n,nY) or None, fpt f64 (n,K) or None)."""
+        torch = self.torch
+        n = int(a_start.shape[0])
+        if out is None:
+            out = (torch.empty((n, self.mlp_classes), dtype=torch.float64, device=self.tdev),
+                   torch.empty(n, dtype=torch.int32, device=self.tdev),
+                   torch.empty(n, dtype=torch.float64, device=self.tdev),
+                   torch.empty(n, dtype=torch.int32, device=self.tdev),
+                   torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev) if want_dist else None,
+                   torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None)
+        prob, pred, conf, status, dist, fpt = out
+        need = int(self.L.wdx_demux_workspace_bytes(n, self.K))
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
+        pc = self.params.to_c()
+        _lib.check(self.L.wdx_demux_mlp_dev(
+            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+            C.byref(pc), _dp(fpt), _dp(status), _dp(dist), _dp(prob), _dp(pred), _dp(conf), _dp(n_nonfinite),
+            _dp(self._work), int(block_rows), self._stream()))
+        return out
+
     # -- synthetic inputs, generated in HBM ----------------------------------------------------------
     def synth_packed(self, spec: synth.SynthSpec, first_read: int, n_reads: int):
         """(sig f32[total], offsets i64[n+1], a_start i32[n], a_end i32[n], barcode i32[n]) on device,

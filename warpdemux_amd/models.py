@@ -1,4 +1,4 @@
-"""MI355X counterpart of ``warpdemux.models.dtw_svm.DTW_SVM``.
+"""MI355X counterparts of ``warpdemux.models.dtw_svm.DTW_SVM`` and ``dtw_mlp.DTW_MLP``.
 
 Same ``predict`` signature and outputs as the reference (/root/reference/warpdemux/models/dtw_svm.py:54-98):
 DTW distances to ``_X`` -> ``exp(-gamma * d**pwr_dist)`` -> ``SVC.predict_proba`` -> ``process_probs``
@@ -128,3 +128,186 @@ class DTW_SVM:
         if return_df:
             return predictions_to_df(y_pred, y_prob, conf, self.label_mapper)
         return y_pred, y_prob
+
+
+def _sklearn_mlp_parts(est):
+    """(scaler steps [(mean_ or None, scale_ or None)], MLPClassifier) of ``model.model``: zero or more
+    StandardScaler steps and one MLPClassifier (BaseDTWModel types it Union[Pipeline, SVC]).  Anything else is refused."""
+    from sklearn.neural_network import MLPClassifier
+    from sklearn.pipeline import Pipeline
+    from sklearn.preprocessing import StandardScaler
+
+    steps = [s for _, s in est.steps] if isinstance(est, Pipeline) else [est]
+    steps = [s for s in steps if s is not None and s != "passthrough"]
+    if not steps or not isinstance(steps[-1], MLPClassifier):
+        raise ValueError("expected an MLPClassifier, optionally behind StandardScaler steps")
+    scalers = []
+    for s in steps[:-1]:
+        # (subclasses such as warpdemux's WeightedStandardScaler only change fit: transform is StandardScaler's)
+        if not isinstance(s, StandardScaler) or type(s).transform is not StandardScaler.transform:
+            raise ValueError(f"unsupported pipeline step {type(s).__name__}: only StandardScaler steps may precede the MLP")
+        mean = getattr(s, "mean_", None) if s.with_mean else None
+        scale = getattr(s, "scale_", None) if s.with_std else None
+        scalers.append((mean, scale))
+    return scalers, steps[-1]
+
+
+class DTW_MLP:
+    """``warpdemux.models.dtw_mlp.DTW_MLP`` with the classifier tail resident on one GPU context: DTW distances to
+    ``_X`` -> StandardScaler steps -> ``MLPClassifier.predict_proba`` -> ``process_probs``, the (n, len(_X)) distance
+    matrix never leaving HBM.  The working dtype is scikit-learn's: ``result_type(float32, coefs_[0].dtype)``."""
+
+    def __init__(self, _X: np.ndarray, coefs, intercepts, activation: str, label_mapper: Dict[int, int],
+                 thresholds: Optional[np.ndarray], window: int, penalty: float, scalers=(), n_classes: Optional[int] = None,
+                 noise_class: bool = False, block_size: Optional[int] = None, out_activation: Optional[str] = None,
+                 device: Optional[int] = None):
+        self._X = np.ascontiguousarray(_X, dtype=np.float64)
+        self.window, self.penalty, self.block_size = window, penalty, block_size
+        self.dtype = np.result_type(np.float32, np.asarray(coefs[0]).dtype)
+        if self.dtype not in (np.float32, np.float64):
+            raise ValueError(f"unsupported MLP dtype {self.dtype}")
+        self._coefs = [np.ascontiguousarray(c, dtype=self.dtype) for c in coefs]
+        self._intercepts = [np.ascontiguousarray(b, dtype=self.dtype) for b in intercepts]
+        if activation not in _lib.MLP_ACT:
+            raise ValueError(f"unknown activation {activation!r}")
+        self.activation = activation
+        n_out = self._coefs[-1].shape[1]
+        self.out_activation = out_activation or ("logistic" if n_out == 1 else "softmax")
+        if (self.out_activation == "logistic") != (n_out == 1) or self.out_activation not in ("logistic", "softmax"):
+            raise ValueError(f"unsupported output layer: {self.out_activation} over {n_out} units")
+        self._scalers = [(None if m is None else np.ascontiguousarray(m, dtype=np.float64),
+                          None if s is None else np.ascontiguousarray(s, dtype=np.float64)) for m, s in scalers]
+        self.n_outputs = n_out
+        self.k = 2 if n_out == 1 else n_out
+        self.label_mapper = dict(label_mapper)
+        self.n_classes = n_classes
+        self.noise_class = noise_class
+        self.thresholds = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        self._label_arr = np.array([self.label_mapper[i] for i in range(self.k)], dtype=np.int32)
+        self._device = device
+
+    @classmethod
+    def from_reference(cls, model, device: Optional[int] = None) -> "DTW_MLP":
+        """From a reference ``DTW_MLP`` instance: reads ``model.model`` (an MLPClassifier, or a Pipeline of StandardScaler
+        steps and one), ``_X``, ``window``, ``penalty``, ``block_size``, ``label_mapper``, ``thresholds``."""
+        scalers, mlp = _sklearn_mlp_parts(model.model)
+        return cls(
+            _X=model._X, coefs=mlp.coefs_, intercepts=mlp.intercepts_, activation=mlp.activation,
+            out_activation=mlp.out_activation_, scalers=scalers, label_mapper=model.label_mapper,
+            thresholds=model.thresholds, window=model.window, penalty=model.penalty, block_size=model.block_size,
+            n_classes=getattr(model, "n_classes", None), noise_class=getattr(model, "noise_class", False), device=device,
+        )
+
+    @property
+    def is_trained(self):
+        return self._X is not None
+
+    def num_bcs(self) -> int:
+        """dtw_mlp.py:95-100"""
+        if self.n_classes is not None:
+            return self.n_classes
+        if self.label_mapper is not None:
+            return len(self.label_mapper) - self.noise_class
+        raise ValueError("No number of barcodes available.")
+
+    def to_c(self) -> "_lib.MlpModelC":
+        """wdx_mlp_model view of the host arrays (valid while ``self`` is alive)."""
+        m = _lib.MlpModelC()
+        nl = len(self._coefs)
+        m.n_layers = nl
+        m.dtype_bytes = self.dtype.itemsize
+        m.hidden_activation = _lib.MLP_ACT[self.activation]
+        m.n_classes = self.k
+        m.n_scalers = len(self._scalers)
+        if nl > _lib.MLP_MAX_LAYERS or len(self._scalers) > _lib.MLP_MAX_SCALERS:
+            return m   # (the counts alone: the library refuses the model before it reads an array)
+        m.sizes[0] = self._coefs[0].shape[0]
+        for i, (c, b) in enumerate(zip(self._coefs, self._intercepts)):
+            m.sizes[i + 1] = c.shape[1]
+            m.coefs[i] = c.ctypes.data
+            m.intercepts[i] = b.ctypes.data
+        for i, (mean, scale) in enumerate(self._scalers):
+            m.scaler_mean[i] = None if mean is None else mean.ctypes.data
+            m.scaler_scale[i] = None if scale is None else scale.ctypes.data
+        m.label_map = self._label_arr.ctypes.data
+        m.thresholds = None if self.thresholds is None else self.thresholds.ctypes.data
+        return m
+
+    def _ensure_resident(self):
+        """References and MLP on the process's context (see DTW_SVM._ensure_resident); the MLP slot is separate from
+        the SVM's, so a resident SVM stays as it is."""
+        ctx = _lib.default_context(self._device)
+        L = _lib.load()
+        _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(self._X), self._X.shape[0], self._X.shape[1],
+                                  int(self.window) if self.window else 0, float(self.penalty) if self.penalty else 0.0))
+        if getattr(ctx, "_mlp_owner", None) is not self:
+            ctx._mlp_owner = None
+            m = self.to_c()
+            _lib.check(L.wdx_mlp_set_model(ctx.handle, C.byref(m)))
+            ctx._mlp_owner = self
+        return ctx
+
+    def _nonfinite_message(self, X) -> str:
+        """scikit-learn's first line for the distances of X (error path only: the distances are recomputed to the host)."""
+        from .parallel_distances import distance_matrix_to
+
+        D = distance_matrix_to(X, self._X, window=self.window, penalty=self.penalty, n_jobs=1)
+        inf_msg = "Input X contains infinity or a value too large for dtype('float32')."
+        for mean, scale in self._scalers:     # StandardScaler.transform: allow-nan validation
+            if np.isinf(D).any():
+                return inf_msg
+            with np.errstate(all="ignore"):
+                if mean is not None:
+                    D -= mean
+                if scale is not None:
+                    D /= scale
+        if np.isnan(D).any():
+            return "Input X contains NaN."
+        return inf_msg
+
+    def predict(self, X: np.ndarray, nproc: int = -1, block_size: Optional[int] = None, pbar: bool = False,
+                pbar_kwargs: dict = {}, return_df: bool = False) -> Union[Tuple[np.ndarray, np.ndarray], "object"]:
+        """(y_pred, y_prob) or the predictions DataFrame -- dtw_mlp.py:44-93.  ``nproc`` / ``block_size`` keep the
+        reference's validation (distance_matrix_to wants block_size when nproc != 1) but nothing is forked."""
+        if not self.is_trained:
+            msg = "Model not trained yet."
+            logging.error(msg)
+            raise ValueError(msg)
+        X = np.asarray(X)
+        if X.ndim == 1:
+            X = X.reshape(1, -1)
+        if X.shape[1] != self._X.shape[1]:
+            raise ValueError("X must have the same shape in axis 1 as the consensus sequences "
+                             f" ({self._X.shape}).")
+        if nproc != 1 and (self.block_size if block_size is None else block_size) is None:
+            msg = "block_size must be specified when using parallel."
+            logging.error(msg)
+            raise ValueError(msg)
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = X.shape[0]
+        ctx = self._ensure_resident()
+        y_prob = np.empty((n, self.k), dtype=np.float64)
+        y_pred = np.empty(n, dtype=np.int32)
+        conf = np.empty(n, dtype=np.float64)
+        bad = C.c_int64(0)
+        _lib.check(_lib.load().wdx_dtw_mlp_predict(ctx.handle, _lib.ptr(X), n, _lib.ptr(y_prob), _lib.ptr(y_pred),
+                                                   _lib.ptr(conf), C.byref(bad)))
+        if bad.value:
+            raise ValueError(self._nonfinite_message(X))
+        y_prob = y_prob.astype(self.dtype)      # exact: float32 models return float32 values widened
+        y_pred = y_pred.astype(np.int64)
+        if return_df:
+            if self.label_mapper is None:
+                raise ValueError("Label mapper is not set.")
+            return predictions_to_df(y_pred, y_prob, conf.astype(self.dtype), self.label_mapper)
+        return y_pred, y_prob
+
+
+def from_reference(model, device: Optional[int] = None):
+    """Device counterpart of a loaded reference model (``warpdemux.file_proc.load_model``), by its class name."""
+    name = type(model).__name__
+    if name == "DTW_SVM":
+        return DTW_SVM.from_reference(model, device=device)
+    if name == "DTW_MLP":
+        return DTW_MLP.from_reference(model, device=device)
+    raise NotImplementedError(f"no device model for {name} (DTW_SVM and DTW_MLP are supported)")
