@@ -185,6 +185,20 @@ int use_stream(wdx_ctx *ctx, hipStream_t s) {
     return WDX_SUCCESS;
 }
 
+int fingerprint_stage(wdx_ctx *B, const FpReads &in, const wdx_seg_params &p, const FpOut &out, void *d_ws,
+                      hipStream_t s, const RefineDev *rf, bool main_events) {
+    if (int rc = B->fp_big.ensure((size_t)fingerprint_big_bytes(in.max_len))) return rc;
+    Timed t(B, WDX_K_FINGERPRINT, s);
+    return launch_fingerprint(in, p, out, s, d_ws, B->knobs, &t.n_launches, nullptr, 0, 0, rf,
+                              main_events ? &t.main : nullptr, (double *)B->fp_big.p);
+}
+
+int check_ref_length(const DtwRefs &R, const wdx_seg_params &p) {
+    if (p.barcode_num_events == R.L) return WDX_SUCCESS;
+    set_error("barcode_num_events (%lld) != reference length (%lld)", (long long)p.barcode_num_events, (long long)R.L);
+    return WDX_ERR_INVALID;
+}
+
 }  // namespace wdx
 
 using namespace wdx;
@@ -580,12 +594,8 @@ int wdx_fingerprint_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
     std::lock_guard<std::mutex> g(ctx->mu);
     if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
-    Timed t(ctx, WDX_K_FINGERPRINT, (hipStream_t)stream);
-    return launch_fingerprint(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start,
-                              d_a_end, d_ok, *p, d_fpt, d_dwell, d_stats, d_status,
-                              (hipStream_t)stream, ctx->fp_ws.p, ctx->knobs, &t.n_launches, nullptr, 0, 0, nullptr,
-                              &t.main, (double *)ctx->fp_big.p);
+    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
+    return fingerprint_stage(ctx, in, *p, FpOut{d_fpt, d_dwell, d_stats, d_status}, ctx->fp_ws.p, (hipStream_t)stream);
 }
 
 int wdx_fingerprint_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
@@ -611,7 +621,6 @@ int wdx_fingerprint_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
     const size_t qb = ((size_t)rp->n_query * 8 + 15) / 16 * 16;
     {
         const void *before = ctx->ref_buf.p;
@@ -638,10 +647,8 @@ int wdx_fingerprint_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *
     } rf_guard{rf};
     if ((rc = fill_refine_dev(*rp, (const double *)ctx->ref_buf.p, d_refine_idx, &rf))) return rc;
     set_refine_ws(rf, ctx->ref_ws.p);
-    Timed t(ctx, WDX_K_FINGERPRINT, s);
-    return launch_fingerprint(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, pv, d_fpt,
-                              d_dwell, d_stats, d_status, s, ctx->fp_ws.p, ctx->knobs, &t.n_launches, nullptr, 0, 0, rf,
-                              nullptr, (double *)ctx->fp_big.p);
+    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
+    return fingerprint_stage(ctx, in, pv, FpOut{d_fpt, d_dwell, d_stats, d_status}, ctx->fp_ws.p, s, rf, false);
 }
 
 int wdx_fingerprint_profile_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
@@ -657,8 +664,8 @@ int wdx_fingerprint_profile_dev(wdx_ctx *ctx, const float *d_sig, const int64_t 
     std::lock_guard<std::mutex> g(ctx->mu);
     if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    rc = launch_fingerprint(d_sig, d_row_off, nullptr, stride, max_len, n_reads, d_a_start, d_a_end,
-                            nullptr, *p, nullptr, nullptr, nullptr, d_status, (hipStream_t)stream,
+    const FpReads in{d_sig, d_row_off, nullptr, stride, max_len, n_reads, d_a_start, d_a_end, nullptr};
+    rc = launch_fingerprint(in, *p, FpOut{nullptr, nullptr, nullptr, d_status}, (hipStream_t)stream,
                             fast_path ? ctx->fp_ws.p : nullptr, ctx->knobs, nullptr, d_prof, prof_reads,
                             fast_path == 2 ? -2 : stop_phase);   // (-2: the split pair's diagnostic build)
     if (rc == WDX_SUCCESS && fast_path && prof_reads > 0 && stop_phase == 0) {
@@ -721,7 +728,6 @@ static int fingerprint_batch_impl(wdx_ctx *ctx, const float *sig, int64_t n_read
     if ((rc = ctx->out2.ensure((size_t)n_reads * 6 * 8))) return rc;
     if ((rc = ctx->out3.ensure((size_t)n_reads * 4))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
     RefineDev *rf = nullptr;
     struct RfGuard {
         RefineDev *&r;
@@ -757,17 +763,10 @@ static int fingerprint_batch_impl(wdx_ctx *ctx, const float *sig, int64_t n_read
     WDX_HIP_TRY(hipMemcpyAsync(ctx->in1.p, a_start, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
     WDX_HIP_TRY(hipMemcpyAsync(ctx->in2.p, a_end, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
     if (ok) WDX_HIP_TRY(hipMemcpyAsync(ctx->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
-    {
-        Timed t(ctx, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint((const float *)ctx->in0.p, nullptr, nullptr, stride, max_len,
-                                     n_reads, (const int32_t *)ctx->in1.p,
-                                     (const int32_t *)ctx->in2.p,
-                                     ok ? (const uint8_t *)ctx->in3.p : nullptr, *p,
-                                     (double *)ctx->out0.p, (int64_t *)ctx->out1.p,
-                                     (double *)ctx->out2.p, (int32_t *)ctx->out3.p, s, ctx->fp_ws.p,
-                                     ctx->knobs, &t.n_launches, nullptr, 0, 0, rf, nullptr, (double *)ctx->fp_big.p)))
-            return rc;
-    }
+    const FpReads in{(const float *)ctx->in0.p, nullptr, nullptr, stride, max_len, n_reads, (const int32_t *)ctx->in1.p,
+                     (const int32_t *)ctx->in2.p, ok ? (const uint8_t *)ctx->in3.p : nullptr};
+    const FpOut out{(double *)ctx->out0.p, (int64_t *)ctx->out1.p, (double *)ctx->out2.p, (int32_t *)ctx->out3.p};
+    if ((rc = fingerprint_stage(ctx, in, *p, out, ctx->fp_ws.p, s, rf, false))) return rc;
     WDX_HIP_TRY(hipMemcpyAsync(fpt, ctx->out0.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
     WDX_HIP_TRY(hipMemcpyAsync(dwell, ctx->out1.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
     WDX_HIP_TRY(hipMemcpyAsync(stats, ctx->out2.p, (size_t)n_reads * 48, hipMemcpyDeviceToHost, s));
@@ -802,12 +801,24 @@ int wdx_fingerprint_refine_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads
                                   status);
 }
 
+}  // extern "C"
+
+DemuxWork wdx::demux_work_layout(int64_t n_reads, int64_t K, bool with_T) {
+    DemuxWork W;
+    W.ld = round_up(n_reads > 0 ? n_reads : 1, 64);
+    W.fptT = round_up(n_reads * K * 8, 256);
+    W.flags = W.fptT + (with_T ? K * W.ld * 8 : 0);
+    W.fp_ws = W.flags + (with_T ? round_up(W.ld, 256) : 0);
+    // (the unrounded pieces plus 512 for the two roundings: what callers have always been told to allocate)
+    W.bytes = n_reads * K * 8 + (with_T ? K * W.ld * 8 + W.ld : 0) + 512 + fingerprint_workspace_bytes(n_reads);
+    return W;
+}
+
+extern "C" {
+
 int64_t wdx_demux_workspace_bytes(int64_t n_reads, int32_t K) {
     if (n_reads < 0 || K < 1) return 0;
-    // [fpt (n,K) f64][small batches only: fptT (K,ld) f64 + nan flags ld][slow-path lists]
-    const int64_t ld = round_up(n_reads > 0 ? n_reads : 1, 64);
-    const int64_t small = n_reads < kRowMajorMinReads ? (int64_t)K * ld * 8 + ld : 0;
-    return n_reads * K * 8 + small + 512 + fingerprint_workspace_bytes(n_reads);
+    return demux_work_layout(n_reads, K, n_reads < kRowMajorMinReads).bytes;   // (small batches: wdx_demux_dev transposes)
 }
 
 int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
@@ -829,11 +840,7 @@ int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
         return WDX_ERR_NO_REFS;
     }
     const int64_t K = p->barcode_num_events;
-    if (K != R.L) {
-        set_error("barcode_num_events (%lld) != reference length (%lld)", (long long)K,
-                  (long long)R.L);
-        return WDX_ERR_INVALID;
-    }
+    if ((rc = check_ref_length(R, *p))) return rc;
     if (dtw_scratch_bytes(R.L, R.window)) {
         set_error("demux_dev needs window <= %d", kMaxRegWindow);
         return WDX_ERR_UNSUPPORTED;
@@ -841,21 +848,15 @@ int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
     if (n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
-    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
     unsigned char *w = (unsigned char *)d_work;
     double *fpt = d_fpt ? d_fpt : (double *)w;
     const bool rowmajor = n_reads >= kRowMajorMinReads;
-    const int64_t ld = round_up(n_reads, 64);
-    double *fptT = (double *)(w + ((n_reads * K * 8 + 255) / 256) * 256);
-    uint8_t *flags = (uint8_t *)(fptT + (rowmajor ? 0 : K * ld));
-    void *fp_ws = (unsigned char *)flags + (rowmajor ? 0 : ((ld + 255) / 256) * 256);
-    {
-        Timed t(ctx, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start,
-                                     d_a_end, d_ok, *p, fpt, d_dwell, d_stats, d_status, s, fp_ws,
-                                     ctx->knobs, &t.n_launches, nullptr, 0, 0, nullptr, &t.main, (double *)ctx->fp_big.p)))
-            return rc;
-    }
+    const DemuxWork W = demux_work_layout(n_reads, K, !rowmajor);
+    const int64_t ld = W.ld;
+    double *fptT = (double *)(w + W.fptT);
+    uint8_t *flags = w + W.flags;
+    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
+    if ((rc = fingerprint_stage(ctx, in, *p, FpOut{fpt, d_dwell, d_stats, d_status}, w + W.fp_ws, s))) return rc;
     if (rowmajor) {
         // failed reads carry NaN fingerprints; the DTW kernel reads the row-major rows in place and flags them
         Timed t(ctx, WDX_K_DTW, s);
@@ -939,7 +940,6 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
         if ((rc = B->mb_conf.ensure((size_t)n_reads * 8))) return rc;
     }
     if ((rc = B->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    if ((rc = B->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
     int64_t *d_dwell = H.dwell ? (int64_t *)B->mb_dwell.p : nullptr;
     double *d_stats = H.stats ? (double *)B->mb_stats.p : nullptr;
     // (Letting the FINGERPRINT kernel read a page-locked minibatch in place over the bus was measured and lost: 1.80 M
@@ -953,6 +953,8 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
     // the original row's samples [st_r, en_r), adapter bounds shifted by st_r: the same window, bit for bit.  (iii) Rows the
     // CALLER packed (wdx_minibatch_in.row_off; the feeder's workers): one flat copy of exactly the windows.
     const float *sig_dev = nullptr;  // the minibatch as the device sees it, when it is page-locked
+    const uint8_t *d_ok = ok ? (const uint8_t *)B->in3.p : nullptr;
+    const FpOut out{(double *)B->out0.p, d_dwell, d_stats, (int32_t *)B->out3.p};
     if (!packed_in && col1 > col0 && (double)win_total < 0.85 * (double)((col1 - col0) * n_reads)) {
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, sig) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer)
@@ -972,12 +974,8 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
         WDX_HIP_TRY(hipMemcpyAsync(d_as, a_start, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
         WDX_HIP_TRY(hipMemcpyAsync(d_ae, a_end, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
         if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
-        Timed t(B, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint((const float *)B->in0.p, d_off, d_len, 0, max_len, n_reads, d_as, d_ae,
-                                     ok ? (const uint8_t *)B->in3.p : nullptr, *p, (double *)B->out0.p, d_dwell, d_stats,
-                                     (int32_t *)B->out3.p, s, B->fp_ws.p, B->knobs, &t.n_launches, nullptr, 0, 0, nullptr,
-                                     &t.main, (double *)B->fp_big.p)))
-            return rc;
+        const FpReads rd{(const float *)B->in0.p, d_off, d_len, 0, max_len, n_reads, d_as, d_ae, d_ok};
+        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s))) return rc;
     } else if (sig_dev) {
         // host images (page-locked, owned by the slot until its copy has run): off int64[n+1] | st int32[n] | len
         // int32[n] | a_start' int32[n] | a_end' int32[n]
@@ -1008,12 +1006,8 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
                       *d_ae = d_as + n_reads;
         if ((rc = launch_pack_windows(sig_dev, stride, n_reads, d_off, d_st, d_len, (float *)B->in0.p, s))) return rc;
         if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
-        Timed t(B, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint((const float *)B->in0.p, d_off, d_len, 0, max_len, n_reads, d_as, d_ae,
-                                     ok ? (const uint8_t *)B->in3.p : nullptr, *p, (double *)B->out0.p, d_dwell, d_stats,
-                                     (int32_t *)B->out3.p, s, B->fp_ws.p, B->knobs, &t.n_launches, nullptr, 0, 0, nullptr,
-                                     &t.main, (double *)B->fp_big.p)))
-            return rc;
+        const FpReads rd{(const float *)B->in0.p, d_off, d_len, 0, max_len, n_reads, d_as, d_ae, d_ok};
+        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s))) return rc;
     } else {
         const float *d_sig = (const float *)B->in0.p;
         if (col1 > col0)
@@ -1023,13 +1017,9 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
         WDX_HIP_TRY(hipMemcpyAsync(B->in1.p, a_start, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
         WDX_HIP_TRY(hipMemcpyAsync(B->in2.p, a_end, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
         if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
-        Timed t(B, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint(d_sig, nullptr, nullptr, stride, max_len, n_reads,
-                                     (const int32_t *)B->in1.p, (const int32_t *)B->in2.p,
-                                     ok ? (const uint8_t *)B->in3.p : nullptr, *p, (double *)B->out0.p,
-                                     d_dwell, d_stats, (int32_t *)B->out3.p, s, B->fp_ws.p, B->knobs, &t.n_launches,
-                                     nullptr, 0, 0, nullptr, &t.main, (double *)B->fp_big.p)))
-            return rc;
+        const FpReads rd{d_sig, nullptr, nullptr, stride, max_len, n_reads, (const int32_t *)B->in1.p,
+                         (const int32_t *)B->in2.p, d_ok};
+        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s))) return rc;
     }
     if (R.nY > 0) {
         if ((rc = dtw_dev_locked(B, (const double *)B->out0.p, n_reads, (float *)B->out1.p,
@@ -1043,14 +1033,8 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
         if (svm) {
             // the classifier tail on the distance rows that are on the device anyway (models/dtw_svm.py:90-93, models/utils.py:45-61);
             // failed reads: pred -1, NaN probabilities (the reference never shows them to the model)
-            {
-                Timed t(B, WDX_K_SVM, s);
-                if ((rc = launch_svm_predict(*svm, (const float *)B->out1.p, n_reads, (double *)B->mb_prob.p,
-                                             (int32_t *)B->mb_pred.p, (double *)B->mb_conf.p, s, B->knobs)))
-                    return rc;
-            }
-            if ((rc = launch_svm_mask_failed((const int32_t *)B->out3.p, n_reads, svm->k, (double *)B->mb_prob.p,
-                                             (int32_t *)B->mb_pred.p, (double *)B->mb_conf.p, s)))
+            if ((rc = svm_tail(B, *svm, (const float *)B->out1.p, n_reads, (const int32_t *)B->out3.p, (double *)B->mb_prob.p,
+                               (int32_t *)B->mb_pred.p, (double *)B->mb_conf.p, s)))
                 return rc;
             if (H.prob) WDX_HIP_TRY(hipMemcpyAsync(H.prob, B->mb_prob.p, (size_t)n_reads * svm->k * 8, hipMemcpyDeviceToHost, s));
             if (H.pred) WDX_HIP_TRY(hipMemcpyAsync(H.pred, B->mb_pred.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
@@ -1075,11 +1059,7 @@ static int demux_check_args(wdx_ctx *ctx, const char *who, int64_t n_reads, int6
         set_error("no reference set: call wdx_set_refs first");
         return WDX_ERR_NO_REFS;
     }
-    if (p->barcode_num_events != R.L) {
-        set_error("barcode_num_events (%lld) != reference length (%lld)", (long long)p->barcode_num_events,
-                  (long long)R.L);
-        return WDX_ERR_INVALID;
-    }
+    if (int rc = check_ref_length(R, *p)) return rc;
     if (n_refs != R.nY) {
         set_error("%s: the caller sized `dist` for %lld references but %lld are resident", who, (long long)n_refs,
                   (long long)R.nY);
@@ -1348,487 +1328,6 @@ int wdx_demux_wait(wdx_ctx *ctx, int32_t slot, double *fpt, float *dist, int32_t
     out.dist = dist;
     out.fpt = fpt;
     return wdx_demux_wait_ex(ctx, slot, &out);
-}
-
-int wdx_svm_set_model(wdx_ctx *ctx, const wdx_svm_model *m) {
-    WDX_ENTER(ctx);
-    if (!m || m->n_classes < 2 || m->n_classes > 16 || m->n_sv < 1 || m->n_train < 1 || !m->n_support ||
-        !m->support || !m->dual_coef || !m->rho || !m->probA || !m->probB || m->pwr_dist < 1) {
-        set_error("svm_set_model: need 2..16 classes, support vectors, coefficients and Platt parameters");
-        return WDX_ERR_INVALID;
-    }
-    const int k = m->n_classes, nsv = m->n_sv, np = k * (k - 1) / 2;
-    int64_t tot = 0;
-    std::vector<int32_t> start(k);
-    for (int c = 0; c < k; ++c) {
-        if (m->n_support[c] < 0) {
-            set_error("svm_set_model: negative n_support");
-            return WDX_ERR_INVALID;
-        }
-        start[c] = (int32_t)tot;
-        tot += m->n_support[c];
-    }
-    if (tot != nsv) {
-        set_error("svm_set_model: sum(n_support) != n_sv");
-        return WDX_ERR_INVALID;
-    }
-    for (int s_ = 0; s_ < nsv; ++s_)
-        if (m->support[s_] < 0 || m->support[s_] >= m->n_train) {
-            set_error("svm_set_model: support index out of range");
-            return WDX_ERR_INVALID;
-        }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = use_stream(ctx, ctx->stream))) return rc;
-    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
-    // one device block: [doubles: dual_coef | rho | probA | probB | thresholds][int32: n_support | start | support | label_map]
-    const size_t nd = (size_t)(k - 1) * nsv + 3 * (size_t)np + (size_t)k;
-    const size_t ni = 3 * (size_t)k + (size_t)nsv;
-    ctx->svm_set = false;  // not set until the upload below has succeeded
-    if ((rc = ctx->svm_buf.ensure(nd * 8 + ni * 4))) return rc;
-    std::vector<unsigned char> h(nd * 8 + ni * 4);
-    double *hd = reinterpret_cast<double *>(h.data());
-    int32_t *hi = reinterpret_cast<int32_t *>(h.data() + nd * 8);
-    size_t o = 0;
-    memcpy(hd + o, m->dual_coef, (size_t)(k - 1) * nsv * 8); o += (size_t)(k - 1) * nsv;
-    memcpy(hd + o, m->rho, (size_t)np * 8); o += np;
-    memcpy(hd + o, m->probA, (size_t)np * 8); o += np;
-    memcpy(hd + o, m->probB, (size_t)np * 8); o += np;
-    if (m->thresholds) memcpy(hd + o, m->thresholds, (size_t)k * 8);
-    memcpy(hi, m->n_support, (size_t)k * 4);
-    memcpy(hi + k, start.data(), (size_t)k * 4);
-    memcpy(hi + 2 * k, m->support, (size_t)nsv * 4);
-    if (m->label_map) memcpy(hi + 2 * k + nsv, m->label_map, (size_t)k * 4);
-    WDX_HIP_TRY(hipMemcpy(ctx->svm_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
-    const double *dd = reinterpret_cast<const double *>(ctx->svm_buf.p);
-    const int32_t *di = reinterpret_cast<const int32_t *>(reinterpret_cast<const unsigned char *>(ctx->svm_buf.p) + nd * 8);
-    SvmDev &S = ctx->svm;
-    S.dual_coef = dd;
-    S.rho = dd + (size_t)(k - 1) * nsv;
-    S.probA = S.rho + np;
-    S.probB = S.probA + np;
-    S.thresholds = m->thresholds ? S.probB + np : nullptr;
-    S.n_support = di;
-    S.start = di + k;
-    S.support = di + 2 * k;
-    S.label_map = m->label_map ? di + 2 * k + nsv : nullptr;
-    S.k = k;
-    S.n_sv = nsv;
-    S.n_train = m->n_train;
-    S.pwr = m->pwr_dist;
-    S.ngamma = (float)(-m->gamma);
-    // for the fused DTW + SVM path (wdx_demux_svm_dev): coefficients vector-major, two chunks per class
-    {
-        const int H = 2, nch = k * H;
-        const size_t cb = (size_t)nsv * (k - 1) * 8, ib = (size_t)(2 * nch + 1) * 4;
-        if ((rc = ctx->svm_fused.ensure(cb + ib))) return rc;
-        std::vector<unsigned char> hf(cb + ib);
-        double *ct = reinterpret_cast<double *>(hf.data());
-        for (int s_ = 0; s_ < nsv; ++s_)
-            for (int q = 0; q < k - 1; ++q) ct[(size_t)s_ * (k - 1) + q] = m->dual_coef[(size_t)q * nsv + s_];
-        int32_t *ref0 = reinterpret_cast<int32_t *>(hf.data() + cb), *slot = ref0 + nch + 1;
-        for (int c = 0; c < k; ++c) {
-            const int half = (m->n_support[c] + 1) / 2;
-            ref0[2 * c] = start[c];
-            ref0[2 * c + 1] = start[c] + half;
-            slot[2 * c] = 2 * c;
-            slot[2 * c + 1] = 2 * c + 1;
-        }
-        ref0[nch] = nsv;
-        WDX_HIP_TRY(hipMemcpy(ctx->svm_fused.p, hf.data(), hf.size(), hipMemcpyHostToDevice));
-        ctx->svm_coefT = reinterpret_cast<const double *>(ctx->svm_fused.p);
-        ctx->svm_chunk_ref0 = reinterpret_cast<const int32_t *>(reinterpret_cast<const unsigned char *>(ctx->svm_fused.p) + cb);
-        ctx->svm_chunk_slot = ctx->svm_chunk_ref0 + nch + 1;
-        ctx->svm_chunks = nch;
-        ctx->svm_halves = H;
-        ++ctx->svm_model_gen;
-    }
-    ctx->svm_set = true;
-    return WDX_SUCCESS;
-}
-
-int wdx_svm_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred,
-                        double *d_conf, void *stream) {
-    WDX_ENTER(ctx);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->svm_set) {
-        set_error("no SVM model: call wdx_svm_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (n < 0 || (n > 0 && !d_dist)) {
-        set_error("svm_predict_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
-    Timed t(ctx, WDX_K_SVM, (hipStream_t)stream);
-    return launch_svm_predict(ctx->svm, d_dist, n, d_prob, d_pred, d_conf, (hipStream_t)stream, ctx->knobs);
-}
-
-int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
-                      int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
-                      const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
-                      double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, int64_t block_rows, void *stream) {
-    WDX_ENTER(ctx);
-    if (n_reads < 0 || !p || block_rows < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
-        set_error("demux_svm_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->svm_set) {
-        set_error("demux_svm_dev needs wdx_set_refs and wdx_svm_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->svm.n_train) {
-        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)R.nY, ctx->svm.n_train);
-        return WDX_ERR_INVALID;
-    }
-    const int64_t K = p->barcode_num_events;
-    if (K != R.L) {
-        set_error("barcode_num_events (%lld) != reference length (%lld)", (long long)K, (long long)R.L);
-        return WDX_ERR_INVALID;
-    }
-    if (n_reads == 0) return WDX_SUCCESS;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
-    const int k = ctx->svm.k;
-    // rows per block: the (rows, nY) float32 distances of a block stay in the memory-side cache (<= 96 MiB)
-    int64_t rows = block_rows > 0 ? block_rows : (((int64_t)96 << 20) / (4 * R.nY)) / 64 * 64;
-    if (rows < 2048) rows = 2048;
-    if (rows > n_reads) rows = n_reads;
-    // (R.any_inf: the fused form has no distance matrix for launch_dtw_equal_inf to settle -- the row blocks do)
-    const bool fused = !d_dist && R.L == 25 && R.window == 15 && !ctx->knobs.no_short_dtw && !ctx->knobs.svm_scalar && k >= 2 &&
-                       k <= 16 && ctx->svm_chunks > 0 && !R.any_inf;
-    if (!d_dist && !fused && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
-    unsigned char *w = (unsigned char *)d_work;
-    double *fpt = d_fpt ? d_fpt : (double *)w;
-    void *fp_ws = w + ((n_reads * K * 8 + 255) / 256) * 256;   // (fingerprint workspace behind the fingerprints)
-    {
-        Timed t(ctx, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, *p,
-                                     fpt, nullptr, nullptr, d_status, s, fp_ws, ctx->knobs, &t.n_launches, nullptr, 0, 0,
-                                     nullptr, &t.main, (double *)ctx->fp_big.p)))
-            return rc;
-    }
-    // Fused form (the distances are not asked for, the shipped shape): dtw_short_svm_kernel over the references in
-    // support-vector order leaves the decision sums P[slot][q][read] -- 16 (k - 1) k bytes per read instead of 4 nY -- and
-    // the tail only adds them up, takes the sigmoids and runs the coupling.  No distance matrix, no row blocks.
-    if (fused) {
-        const SvmDev &M = ctx->svm;
-        if (ctx->svm_refs_gen != ctx->refs_gen || ctx->svm_refs_model_gen != ctx->svm_model_gen) {
-            const size_t rb = (size_t)M.n_sv * R.Lpad * 8;
-            if ((rc = ctx->svm_refs.ensure(rb + (size_t)M.n_sv))) return rc;
-            if ((rc = launch_gather_rows(R.pad, R.has_nan, M.support, M.n_sv, R.Lpad, (double *)ctx->svm_refs.p,
-                                         (uint8_t *)ctx->svm_refs.p + rb, s)))
-                return rc;
-            ctx->svm_refs_gen = ctx->refs_gen;
-            ctx->svm_refs_model_gen = ctx->svm_model_gen;
-        }
-        const size_t rb = (size_t)M.n_sv * R.Lpad * 8;
-        if ((rc = ctx->out0.ensure((size_t)ctx->svm_chunks * (k - 1) * (size_t)n_reads * 8))) return rc;
-        {
-            Timed t(ctx, WDX_K_DTW, s);
-            if ((rc = launch_dtw_svm_partial(fpt, n_reads, (const double *)ctx->svm_refs.p, R.Lpad, R.halo,
-                                             (const uint8_t *)ctx->svm_refs.p + rb, R.L, R.window, R.penalty, ctx->svm_coefT,
-                                             ctx->svm_chunk_ref0, ctx->svm_chunk_slot, ctx->svm_chunks, k - 1, M.pwr, M.ngamma,
-                                             (double *)ctx->out0.p, s, ctx->knobs.dtw_unfused, &ctx->dtw_last)))
-                return rc;
-        }
-        {
-            Timed t(ctx, WDX_K_SVM, s);
-            if ((rc = launch_svm_finish(M, (const double *)ctx->out0.p, ctx->svm_halves, n_reads, d_prob, d_pred, d_conf, s)))
-                return rc;
-        }
-        return launch_svm_mask_failed(d_status, n_reads, k, d_prob, d_pred, d_conf, s);
-    }
-    for (int64_t r0 = 0; r0 < n_reads; r0 += rows) {
-        const int64_t m = std::min(rows, n_reads - r0);
-        float *dblk = d_dist ? d_dist + r0 * R.nY : (float *)ctx->out0.p;
-        if ((rc = dtw_dev_locked(ctx, fpt + r0 * K, m, dblk, nullptr, s))) return rc;
-        Timed t(ctx, WDX_K_SVM, s);
-        if ((rc = launch_svm_predict(ctx->svm, dblk, m, d_prob ? d_prob + r0 * k : nullptr, d_pred ? d_pred + r0 : nullptr,
-                                     d_conf ? d_conf + r0 : nullptr, s, ctx->knobs)))
-            return rc;
-    }
-    return launch_svm_mask_failed(d_status, n_reads, k, d_prob, d_pred, d_conf, s);
-}
-
-int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf) {
-    WDX_ENTER(ctx);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->svm_set) {
-        set_error("dtw_svm_predict needs wdx_set_refs and wdx_svm_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->svm.n_train) {
-        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)R.nY, ctx->svm.n_train);
-        return WDX_ERR_INVALID;
-    }
-    if (n < 0 || (n > 0 && !X)) {
-        set_error("dtw_svm_predict: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    if (n == 0) return WDX_SUCCESS;
-    hipStream_t s = ctx->stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->svm.k;
-    // rows per pass: the (rows, nY) float32 distance block stays <= 1 GiB and never leaves HBM
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)1 << 30) / (4 * (int64_t)R.nY)));
-    if ((rc = ctx->in0.ensure((size_t)(chunk * R.L) * 8))) return rc;
-    if ((rc = ctx->out0.ensure((size_t)(chunk * R.nY) * 4))) return rc;
-    if ((rc = ctx->out1.ensure((size_t)chunk * k * 8))) return rc;
-    if ((rc = ctx->out2.ensure((size_t)chunk * 4))) return rc;
-    if ((rc = ctx->out3.ensure((size_t)chunk * 8))) return rc;
-    StreamDrain drain(s);
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int64_t m = std::min(chunk, n - r0);
-        WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X + r0 * R.L, (size_t)(m * R.L) * 8, hipMemcpyHostToDevice, s));
-        if ((rc = dtw_dev_locked(ctx, (const double *)ctx->in0.p, m, (float *)ctx->out0.p, nullptr, s))) return rc;
-        {
-            Timed t(ctx, WDX_K_SVM, s);
-            if ((rc = launch_svm_predict(ctx->svm, (const float *)ctx->out0.p, m, (double *)ctx->out1.p,
-                                         (int32_t *)ctx->out2.p, (double *)ctx->out3.p, s, ctx->knobs)))
-                return rc;
-        }
-        if (prob) WDX_HIP_TRY(hipMemcpyAsync(prob + r0 * k, ctx->out1.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
-        if (pred) WDX_HIP_TRY(hipMemcpyAsync(pred + r0, ctx->out2.p, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-        if (conf) WDX_HIP_TRY(hipMemcpyAsync(conf + r0, ctx->out3.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-    }
-    WDX_HIP_TRY(hipStreamSynchronize(s));
-    drain.done();
-    return WDX_SUCCESS;
-}
-
-int wdx_mlp_set_model(wdx_ctx *ctx, const wdx_mlp_model *m) {
-    WDX_ENTER(ctx);
-    // every check before anything of the resident model is touched: a refused model keeps the previous one
-    if (!m || (m->dtype_bytes != 4 && m->dtype_bytes != 8) || m->n_classes < 2 || m->n_layers < 1 || m->n_scalers < 0 ||
-        m->hidden_activation < WDX_MLP_ACT_IDENTITY || m->hidden_activation > WDX_MLP_ACT_RELU) {
-        set_error("mlp_set_model: need a float32 / float64 model with >= 2 classes, layers and a known activation");
-        return WDX_ERR_INVALID;
-    }
-    const int nl = m->n_layers, k = m->n_classes;
-    if (nl < 2 || nl > WDX_MLP_MAX_LAYERS) {
-        set_error("mlp_set_model: %d hidden layers (1..%d supported)", nl - 1, WDX_MLP_MAX_LAYERS - 1);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (k > 16) {
-        set_error("mlp_set_model: %d classes (2..16 supported)", k);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (m->n_scalers > WDX_MLP_MAX_SCALERS) {
-        set_error("mlp_set_model: %d scaler steps (at most %d supported)", m->n_scalers, WDX_MLP_MAX_SCALERS);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    for (int i = 0; i <= nl; ++i)
-        if (m->sizes[i] < 1) {
-            set_error("mlp_set_model: layer size %d of entry %d", m->sizes[i], i);
-            return WDX_ERR_INVALID;
-        }
-    for (int i = 0; i < nl; ++i)
-        if (!m->coefs[i] || !m->intercepts[i]) {
-            set_error("mlp_set_model: layer %d has no coefficients / intercepts", i);
-            return WDX_ERR_INVALID;
-        }
-    const int nout = m->sizes[nl];
-    if (nout != k && !(nout == 1 && k == 2)) {
-        set_error("mlp_set_model: %d output units for %d classes", nout, k);
-        return WDX_ERR_INVALID;
-    }
-    int widest = 16;
-    for (int i = 1; i < nl; ++i) {
-        if (m->sizes[i] > WDX_MLP_MAX_WIDTH) {
-            set_error("mlp_set_model: hidden layer of %d units (at most %d supported)", m->sizes[i], WDX_MLP_MAX_WIDTH);
-            return WDX_ERR_UNSUPPORTED;
-        }
-        widest = std::max(widest, m->sizes[i]);
-    }
-    const int64_t n_in = m->sizes[0];
-    const size_t T = (size_t)m->dtype_bytes;
-    // one device block: [doubles: scaler mean / scale steps | thresholds][working dtype: W_i | b_i ...][int32: label map]
-    size_t nd = (m->thresholds ? (size_t)k : 0);
-    for (int s_ = 0; s_ < m->n_scalers; ++s_) nd += (m->scaler_mean[s_] ? n_in : 0) + (m->scaler_scale[s_] ? n_in : 0);
-    size_t nw = 0;
-    for (int i = 0; i < nl; ++i) nw += (size_t)m->sizes[i] * m->sizes[i + 1] + (size_t)m->sizes[i + 1];
-    const size_t bytes = nd * 8 + round_up((int64_t)(nw * T), 8) + (m->label_map ? (size_t)k * 4 : 0);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = use_stream(ctx, ctx->stream))) return rc;
-    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
-    WDX_HIP_TRY(hipDeviceSynchronize());  // (nor one on a caller's stream: the model is replaced in place)
-    std::vector<unsigned char> h(bytes);
-    ctx->mlp_set = false;  // not set until the upload below has succeeded
-    if ((rc = ctx->mlp_buf.ensure(bytes))) return rc;
-    MlpDev M{};
-    unsigned char *dev = (unsigned char *)ctx->mlp_buf.p;
-    size_t o = 0;
-    for (int s_ = 0; s_ < m->n_scalers; ++s_) {
-        for (int which = 0; which < 2; ++which) {
-            const double *src = which ? m->scaler_scale[s_] : m->scaler_mean[s_];
-            if (!src) continue;
-            memcpy(h.data() + o, src, (size_t)n_in * 8);
-            (which ? M.scale[s_] : M.mean[s_]) = (const double *)(dev + o);
-            o += (size_t)n_in * 8;
-        }
-    }
-    if (m->thresholds) {
-        memcpy(h.data() + o, m->thresholds, (size_t)k * 8);
-        M.thresholds = (const double *)(dev + o);
-        o += (size_t)k * 8;
-    }
-    for (int i = 0; i < nl; ++i) {
-        const size_t wb = (size_t)m->sizes[i] * m->sizes[i + 1] * T, bb = (size_t)m->sizes[i + 1] * T;
-        memcpy(h.data() + o, m->coefs[i], wb);
-        M.coef[i] = dev + o;
-        o += wb;
-        memcpy(h.data() + o, m->intercepts[i], bb);
-        M.bias[i] = dev + o;
-        o += bb;
-    }
-    o = (size_t)round_up((int64_t)o, 8);
-    if (m->label_map) {
-        memcpy(h.data() + o, m->label_map, (size_t)k * 4);
-        M.label_map = (const int32_t *)(dev + o);
-    }
-    WDX_HIP_TRY(hipMemcpy(ctx->mlp_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
-    for (int i = 0; i <= nl; ++i) M.sizes[i] = m->sizes[i];
-    M.n_layers = nl;
-    M.n_scalers = m->n_scalers;
-    M.dtype_bytes = m->dtype_bytes;
-    M.hidden_act = m->hidden_activation;
-    M.k = k;
-    M.ld = (int)round_up(widest, 16) + 1;
-    ctx->mlp = M;
-    ctx->mlp_set = true;
-    return WDX_SUCCESS;
-}
-
-int wdx_mlp_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred, double *d_conf,
-                        int64_t *d_n_nonfinite, void *stream) {
-    WDX_ENTER(ctx);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->mlp_set) {
-        set_error("no MLP model: call wdx_mlp_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (n < 0 || (n > 0 && !d_dist)) {
-        set_error("mlp_predict_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
-    Timed t(ctx, WDX_K_MLP, (hipStream_t)stream);
-    return launch_mlp_predict(ctx->mlp, d_dist, n, nullptr, d_prob, d_pred, d_conf, d_n_nonfinite, (hipStream_t)stream);
-}
-
-int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf,
-                        int64_t *n_nonfinite) {
-    WDX_ENTER(ctx);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->mlp_set) {
-        set_error("dtw_mlp_predict needs wdx_set_refs and wdx_mlp_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->mlp.sizes[0]) {
-        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
-        return WDX_ERR_INVALID;
-    }
-    if (n < 0 || (n > 0 && !X)) {
-        set_error("dtw_mlp_predict: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    if (n_nonfinite) *n_nonfinite = 0;
-    if (n == 0) return WDX_SUCCESS;
-    hipStream_t s = ctx->stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->mlp.k;
-    // rows per pass: the (rows, nY) float32 distance block stays <= 1 GiB and never leaves HBM
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)1 << 30) / (4 * (int64_t)R.nY)));
-    if (ctx->knobs.mlp_chunk_rows > 0) chunk = std::min<int64_t>(chunk, ctx->knobs.mlp_chunk_rows);
-    if ((rc = ctx->in0.ensure((size_t)(chunk * R.L) * 8))) return rc;
-    if ((rc = ctx->out0.ensure((size_t)(chunk * R.nY) * 4))) return rc;
-    if ((rc = ctx->out1.ensure((size_t)chunk * k * 8))) return rc;
-    if ((rc = ctx->out2.ensure((size_t)chunk * 4))) return rc;
-    if ((rc = ctx->out3.ensure((size_t)chunk * 8 + 8))) return rc;
-    int64_t *d_cnt = (int64_t *)((unsigned char *)ctx->out3.p + (size_t)chunk * 8);
-    int64_t h_cnt = 0;
-    StreamDrain drain(s);
-    WDX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int64_t m = std::min(chunk, n - r0);
-        WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X + r0 * R.L, (size_t)(m * R.L) * 8, hipMemcpyHostToDevice, s));
-        if ((rc = dtw_dev_locked(ctx, (const double *)ctx->in0.p, m, (float *)ctx->out0.p, nullptr, s))) return rc;
-        {
-            Timed t(ctx, WDX_K_MLP, s);
-            if ((rc = launch_mlp_predict(ctx->mlp, (const float *)ctx->out0.p, m, nullptr, (double *)ctx->out1.p,
-                                         (int32_t *)ctx->out2.p, (double *)ctx->out3.p, d_cnt, s)))
-                return rc;
-        }
-        if (prob) WDX_HIP_TRY(hipMemcpyAsync(prob + r0 * k, ctx->out1.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
-        if (pred) WDX_HIP_TRY(hipMemcpyAsync(pred + r0, ctx->out2.p, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-        if (conf) WDX_HIP_TRY(hipMemcpyAsync(conf + r0, ctx->out3.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-    }
-    WDX_HIP_TRY(hipMemcpyAsync(&h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, s));
-    WDX_HIP_TRY(hipStreamSynchronize(s));
-    drain.done();
-    if (n_nonfinite) *n_nonfinite = h_cnt;
-    return WDX_SUCCESS;
-}
-
-int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
-                      int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
-                      const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
-                      double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
-                      int64_t block_rows, void *stream) {
-    WDX_ENTER(ctx);
-    if (n_reads < 0 || !p || block_rows < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
-        set_error("demux_mlp_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->mlp_set) {
-        set_error("demux_mlp_dev needs wdx_set_refs and wdx_mlp_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->mlp.sizes[0]) {
-        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
-        return WDX_ERR_INVALID;
-    }
-    const int64_t K = p->barcode_num_events;
-    if (K != R.L) {
-        set_error("barcode_num_events (%lld) != reference length (%lld)", (long long)K, (long long)R.L);
-        return WDX_ERR_INVALID;
-    }
-    if (n_reads == 0) return WDX_SUCCESS;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
-    const int k = ctx->mlp.k;
-    // rows per block: the (rows, nY) float32 distances of a block stay in the memory-side cache (<= 96 MiB)
-    int64_t rows = block_rows > 0 ? block_rows : std::max<int64_t>(2048, (((int64_t)96 << 20) / (4 * R.nY)) / 64 * 64);
-    if (rows > n_reads) rows = n_reads;
-    if (!d_dist && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
-    unsigned char *w = (unsigned char *)d_work;
-    double *fpt = d_fpt ? d_fpt : (double *)w;
-    void *fp_ws = w + ((n_reads * K * 8 + 255) / 256) * 256;   // (fingerprint workspace behind the fingerprints)
-    {
-        Timed t(ctx, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, *p,
-                                     fpt, nullptr, nullptr, d_status, s, fp_ws, ctx->knobs, &t.n_launches, nullptr, 0, 0,
-                                     nullptr, &t.main, (double *)ctx->fp_big.p)))
-            return rc;
-    }
-    for (int64_t r0 = 0; r0 < n_reads; r0 += rows) {
-        const int64_t m = std::min(rows, n_reads - r0);
-        float *dblk = d_dist ? d_dist + r0 * R.nY : (float *)ctx->out0.p;
-        if ((rc = dtw_dev_locked(ctx, fpt + r0 * K, m, dblk, nullptr, s))) return rc;
-        Timed t(ctx, WDX_K_MLP, s);
-        if ((rc = launch_mlp_predict(ctx->mlp, dblk, m, d_status + r0, d_prob ? d_prob + r0 * k : nullptr,
-                                     d_pred ? d_pred + r0 : nullptr, d_conf ? d_conf + r0 : nullptr, d_n_nonfinite, s)))
-            return rc;
-    }
-    return WDX_SUCCESS;
 }
 
 int wdx_dtw_last_launch(wdx_ctx *ctx, wdx_dtw_launch_info *info) {

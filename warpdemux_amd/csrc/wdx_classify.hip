@@ -1,0 +1,517 @@
+// C ABI of libwdx_hip.so, classifier tails (include/wdx.h): the SVM and the MLP behind the DTW distances.  Host code only: the
+// kernels are in wdx_svm.hip / wdx_mlp.hip / wdx_dtw.hip.  The two tails share one host path each for "raw rows -> fingerprints
+// -> DTW row blocks -> tail" (wdx_demux_{svm,mlp}_dev) and "host rows in chunks -> DTW -> tail" (wdx_dtw_{svm,mlp}_predict);
+// what differs between them -- the resident-model checks, the SVM's fused route, the MLP's counter -- is in the entry points.
+#include "wdx_ctx.h"
+
+#include <string.h>
+
+#include <algorithm>
+
+using namespace wdx;
+
+namespace wdx {
+
+int svm_tail(wdx_ctx *B, const SvmDev &M, const float *d_dist, int64_t n, const int32_t *d_status, double *d_prob,
+             int32_t *d_pred, double *d_conf, hipStream_t s) {
+    {
+        Timed t(B, WDX_K_SVM, s);
+        if (int rc = launch_svm_predict(M, d_dist, n, d_prob, d_pred, d_conf, s, B->knobs)) return rc;
+    }
+    return d_status ? launch_svm_mask_failed(d_status, n, M.k, d_prob, d_pred, d_conf, s) : WDX_SUCCESS;
+}
+
+}  // namespace wdx
+
+// rows per block of wdx_demux_{svm,mlp}_dev when the caller names none: the (rows, nY) float32 distances of a block stay in
+// the memory-side cache (<= 96 MiB)
+static int64_t default_block_rows(int64_t nY) { return std::max<int64_t>(2048, (((int64_t)96 << 20) / (4 * nY)) / 64 * 64); }
+
+// What wdx_demux_{svm,mlp}_dev do between their own checks and their tails: the fingerprints of the reads into d_fpt, or
+// into the front of d_work when the caller does not want them (*fpt says where), the fingerprint workspace behind them.
+static int demux_fingerprints(wdx_ctx *ctx, const FpReads &in, const wdx_seg_params &p, double *d_fpt, int32_t *d_status,
+                              void *d_work, hipStream_t s, const double **fpt) {
+    double *f = d_fpt ? d_fpt : (double *)d_work;
+    *fpt = f;
+    void *fp_ws = (unsigned char *)d_work + demux_work_layout(in.n_reads, p.barcode_num_events, false).fp_ws;
+    return fingerprint_stage(ctx, in, p, FpOut{f, nullptr, nullptr, d_status}, fp_ws, s);
+}
+
+// DTW of the fingerprint rows against the resident references, `rows` at a time; every block's distances (in d_dist when the
+// caller wants them, else in out0, which the caller has sized) go to tail(distances, first row, rows) while they are hot.
+template <class Tail>
+static int dtw_row_blocks(wdx_ctx *ctx, const double *fpt, int64_t n_reads, int64_t rows, float *d_dist, hipStream_t s,
+                          Tail tail) {
+    const DtwRefs &R = ctx->refs;
+    for (int64_t r0 = 0; r0 < n_reads; r0 += rows) {
+        const int64_t m = std::min(rows, n_reads - r0);
+        float *dblk = d_dist ? d_dist + r0 * R.nY : (float *)ctx->out0.p;
+        if (int rc = dtw_dev_locked(ctx, fpt + r0 * R.L, m, dblk, nullptr, s)) return rc;
+        if (int rc = tail(dblk, r0, m)) return rc;
+    }
+    return WDX_SUCCESS;
+}
+
+// Host rows X (n, L) through DTW and a tail, `chunk` rows per pass: the (chunk, nY) float32 distance block stays <= 1 GiB and
+// never leaves HBM.  Workspaces: in0 rows | out0 distances | out1 prob (chunk, k) | out2 pred | out3 conf (+ tail_bytes that
+// the caller keeps behind them).
+static int64_t host_chunk_rows(int64_t n, int64_t nY) {
+    return std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)1 << 30) / (4 * nY)));
+}
+static int ensure_chunk_buffers(wdx_ctx *ctx, int64_t chunk, int k, size_t tail_bytes) {
+    const DtwRefs &R = ctx->refs;
+    int rc;
+    if ((rc = ctx->in0.ensure((size_t)(chunk * R.L) * 8))) return rc;
+    if ((rc = ctx->out0.ensure((size_t)(chunk * R.nY) * 4))) return rc;
+    if ((rc = ctx->out1.ensure((size_t)chunk * k * 8))) return rc;
+    if ((rc = ctx->out2.ensure((size_t)chunk * 4))) return rc;
+    return ctx->out3.ensure((size_t)chunk * 8 + tail_bytes);
+}
+// ... enqueued on s: copy in, DTW, tail(distances, first row, rows) writing out1 / out2 / out3, copies out.  The caller
+// holds the StreamDrain and synchronises.
+template <class Tail>
+static int dtw_predict_chunks(wdx_ctx *ctx, const double *X, int64_t n, int64_t chunk, int k, double *prob, int32_t *pred,
+                              double *conf, hipStream_t s, Tail tail) {
+    const DtwRefs &R = ctx->refs;
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t m = std::min(chunk, n - r0);
+        WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X + r0 * R.L, (size_t)(m * R.L) * 8, hipMemcpyHostToDevice, s));
+        if (int rc = dtw_dev_locked(ctx, (const double *)ctx->in0.p, m, (float *)ctx->out0.p, nullptr, s)) return rc;
+        if (int rc = tail((const float *)ctx->out0.p, r0, m)) return rc;
+        if (prob) WDX_HIP_TRY(hipMemcpyAsync(prob + r0 * k, ctx->out1.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
+        if (pred) WDX_HIP_TRY(hipMemcpyAsync(pred + r0, ctx->out2.p, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+        if (conf) WDX_HIP_TRY(hipMemcpyAsync(conf + r0, ctx->out3.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    }
+    return WDX_SUCCESS;
+}
+
+// Fused form of wdx_demux_svm_dev (the distances are not asked for, the shipped shape): dtw_short_svm_kernel over the
+// references in support-vector order leaves the decision sums P[slot][q][read] -- 16 (k - 1) k bytes per read instead of 4 nY
+// -- and the tail only adds them up, takes the sigmoids and runs the coupling.  No distance matrix, no row blocks.
+static int svm_fused_route(wdx_ctx *ctx, const double *fpt, int64_t n_reads, double *d_prob, int32_t *d_pred, double *d_conf,
+                           hipStream_t s) {
+    const DtwRefs &R = ctx->refs;
+    const SvmDev &M = ctx->svm;
+    const int k = M.k;
+    int rc;
+    if (ctx->svm_refs_gen != ctx->refs_gen || ctx->svm_refs_model_gen != ctx->svm_model_gen) {
+        const size_t rb = (size_t)M.n_sv * R.Lpad * 8;
+        if ((rc = ctx->svm_refs.ensure(rb + (size_t)M.n_sv))) return rc;
+        if ((rc = launch_gather_rows(R.pad, R.has_nan, M.support, M.n_sv, R.Lpad, (double *)ctx->svm_refs.p,
+                                     (uint8_t *)ctx->svm_refs.p + rb, s)))
+            return rc;
+        ctx->svm_refs_gen = ctx->refs_gen;
+        ctx->svm_refs_model_gen = ctx->svm_model_gen;
+    }
+    const size_t rb = (size_t)M.n_sv * R.Lpad * 8;
+    if ((rc = ctx->out0.ensure((size_t)ctx->svm_chunks * (k - 1) * (size_t)n_reads * 8))) return rc;
+    {
+        Timed t(ctx, WDX_K_DTW, s);
+        if ((rc = launch_dtw_svm_partial(fpt, n_reads, (const double *)ctx->svm_refs.p, R.Lpad, R.halo,
+                                         (const uint8_t *)ctx->svm_refs.p + rb, R.L, R.window, R.penalty, ctx->svm_coefT,
+                                         ctx->svm_chunk_ref0, ctx->svm_chunk_slot, ctx->svm_chunks, k - 1, M.pwr, M.ngamma,
+                                         (double *)ctx->out0.p, s, ctx->knobs.dtw_unfused, &ctx->dtw_last)))
+            return rc;
+    }
+    {
+        Timed t(ctx, WDX_K_SVM, s);
+        if ((rc = launch_svm_finish(M, (const double *)ctx->out0.p, ctx->svm_halves, n_reads, d_prob, d_pred, d_conf, s)))
+            return rc;
+    }
+    return WDX_SUCCESS;
+}
+
+extern "C" {
+
+int wdx_svm_set_model(wdx_ctx *ctx, const wdx_svm_model *m) {
+    WDX_ENTER(ctx);
+    if (!m || m->n_classes < 2 || m->n_classes > 16 || m->n_sv < 1 || m->n_train < 1 || !m->n_support ||
+        !m->support || !m->dual_coef || !m->rho || !m->probA || !m->probB || m->pwr_dist < 1) {
+        set_error("svm_set_model: need 2..16 classes, support vectors, coefficients and Platt parameters");
+        return WDX_ERR_INVALID;
+    }
+    const int k = m->n_classes, nsv = m->n_sv, np = k * (k - 1) / 2;
+    int64_t tot = 0;
+    std::vector<int32_t> start(k);
+    for (int c = 0; c < k; ++c) {
+        if (m->n_support[c] < 0) {
+            set_error("svm_set_model: negative n_support");
+            return WDX_ERR_INVALID;
+        }
+        start[c] = (int32_t)tot;
+        tot += m->n_support[c];
+    }
+    if (tot != nsv) {
+        set_error("svm_set_model: sum(n_support) != n_sv");
+        return WDX_ERR_INVALID;
+    }
+    for (int s_ = 0; s_ < nsv; ++s_)
+        if (m->support[s_] < 0 || m->support[s_] >= m->n_train) {
+            set_error("svm_set_model: support index out of range");
+            return WDX_ERR_INVALID;
+        }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((rc = use_stream(ctx, ctx->stream))) return rc;
+    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
+    // one device block: [doubles: dual_coef | rho | probA | probB | thresholds][int32: n_support | start | support | label_map]
+    const size_t nd = (size_t)(k - 1) * nsv + 3 * (size_t)np + (size_t)k;
+    const size_t ni = 3 * (size_t)k + (size_t)nsv;
+    ctx->svm_set = false;  // not set until the upload below has succeeded
+    if ((rc = ctx->svm_buf.ensure(nd * 8 + ni * 4))) return rc;
+    std::vector<unsigned char> h(nd * 8 + ni * 4);
+    double *hd = reinterpret_cast<double *>(h.data());
+    int32_t *hi = reinterpret_cast<int32_t *>(h.data() + nd * 8);
+    size_t o = 0;
+    memcpy(hd + o, m->dual_coef, (size_t)(k - 1) * nsv * 8); o += (size_t)(k - 1) * nsv;
+    memcpy(hd + o, m->rho, (size_t)np * 8); o += np;
+    memcpy(hd + o, m->probA, (size_t)np * 8); o += np;
+    memcpy(hd + o, m->probB, (size_t)np * 8); o += np;
+    if (m->thresholds) memcpy(hd + o, m->thresholds, (size_t)k * 8);
+    memcpy(hi, m->n_support, (size_t)k * 4);
+    memcpy(hi + k, start.data(), (size_t)k * 4);
+    memcpy(hi + 2 * k, m->support, (size_t)nsv * 4);
+    if (m->label_map) memcpy(hi + 2 * k + nsv, m->label_map, (size_t)k * 4);
+    WDX_HIP_TRY(hipMemcpy(ctx->svm_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    const double *dd = reinterpret_cast<const double *>(ctx->svm_buf.p);
+    const int32_t *di = reinterpret_cast<const int32_t *>(reinterpret_cast<const unsigned char *>(ctx->svm_buf.p) + nd * 8);
+    SvmDev &S = ctx->svm;
+    S.dual_coef = dd;
+    S.rho = dd + (size_t)(k - 1) * nsv;
+    S.probA = S.rho + np;
+    S.probB = S.probA + np;
+    S.thresholds = m->thresholds ? S.probB + np : nullptr;
+    S.n_support = di;
+    S.start = di + k;
+    S.support = di + 2 * k;
+    S.label_map = m->label_map ? di + 2 * k + nsv : nullptr;
+    S.k = k;
+    S.n_sv = nsv;
+    S.n_train = m->n_train;
+    S.pwr = m->pwr_dist;
+    S.ngamma = (float)(-m->gamma);
+    // for the fused DTW + SVM path (wdx_demux_svm_dev): coefficients vector-major, two chunks per class
+    {
+        const int H = 2, nch = k * H;
+        const size_t cb = (size_t)nsv * (k - 1) * 8, ib = (size_t)(2 * nch + 1) * 4;
+        if ((rc = ctx->svm_fused.ensure(cb + ib))) return rc;
+        std::vector<unsigned char> hf(cb + ib);
+        double *ct = reinterpret_cast<double *>(hf.data());
+        for (int s_ = 0; s_ < nsv; ++s_)
+            for (int q = 0; q < k - 1; ++q) ct[(size_t)s_ * (k - 1) + q] = m->dual_coef[(size_t)q * nsv + s_];
+        int32_t *ref0 = reinterpret_cast<int32_t *>(hf.data() + cb), *slot = ref0 + nch + 1;
+        for (int c = 0; c < k; ++c) {
+            const int half = (m->n_support[c] + 1) / 2;
+            ref0[2 * c] = start[c];
+            ref0[2 * c + 1] = start[c] + half;
+            slot[2 * c] = 2 * c;
+            slot[2 * c + 1] = 2 * c + 1;
+        }
+        ref0[nch] = nsv;
+        WDX_HIP_TRY(hipMemcpy(ctx->svm_fused.p, hf.data(), hf.size(), hipMemcpyHostToDevice));
+        ctx->svm_coefT = reinterpret_cast<const double *>(ctx->svm_fused.p);
+        ctx->svm_chunk_ref0 = reinterpret_cast<const int32_t *>(reinterpret_cast<const unsigned char *>(ctx->svm_fused.p) + cb);
+        ctx->svm_chunk_slot = ctx->svm_chunk_ref0 + nch + 1;
+        ctx->svm_chunks = nch;
+        ctx->svm_halves = H;
+        ++ctx->svm_model_gen;
+    }
+    ctx->svm_set = true;
+    return WDX_SUCCESS;
+}
+
+int wdx_svm_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred,
+                        double *d_conf, void *stream) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->svm_set) {
+        set_error("no SVM model: call wdx_svm_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (n < 0 || (n > 0 && !d_dist)) {
+        set_error("svm_predict_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
+    return svm_tail(ctx, ctx->svm, d_dist, n, nullptr, d_prob, d_pred, d_conf, (hipStream_t)stream);
+}
+
+int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                      int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
+                      const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
+                      double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, int64_t block_rows, void *stream) {
+    WDX_ENTER(ctx);
+    if (n_reads < 0 || !p || block_rows < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
+        set_error("demux_svm_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if (R.window == 0 || !ctx->svm_set) {
+        set_error("demux_svm_dev needs wdx_set_refs and wdx_svm_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (R.nY != ctx->svm.n_train) {
+        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)R.nY, ctx->svm.n_train);
+        return WDX_ERR_INVALID;
+    }
+    if ((rc = check_ref_length(R, *p))) return rc;
+    if (n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int k = ctx->svm.k;
+    // ASYMMETRY, kept: an explicit block_rows below 2048 is raised to 2048 here; wdx_demux_mlp_dev honours it
+    const int64_t rows = std::min(n_reads, block_rows > 0 ? std::max<int64_t>(block_rows, 2048) : default_block_rows(R.nY));
+    // (R.any_inf: the fused form has no distance matrix for launch_dtw_equal_inf to settle -- the row blocks do)
+    const bool fused = !d_dist && R.L == 25 && R.window == 15 && !ctx->knobs.no_short_dtw && !ctx->knobs.svm_scalar && k >= 2 &&
+                       k <= 16 && ctx->svm_chunks > 0 && !R.any_inf;
+    if (!d_dist && !fused && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
+    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
+    const double *fpt = nullptr;
+    if ((rc = demux_fingerprints(ctx, in, *p, d_fpt, d_status, d_work, s, &fpt))) return rc;
+    if (fused)
+        rc = svm_fused_route(ctx, fpt, n_reads, d_prob, d_pred, d_conf, s);
+    else
+        rc = dtw_row_blocks(ctx, fpt, n_reads, rows, d_dist, s, [&](const float *dblk, int64_t r0, int64_t m) {
+            return svm_tail(ctx, ctx->svm, dblk, m, nullptr, d_prob ? d_prob + r0 * k : nullptr, d_pred ? d_pred + r0 : nullptr,
+                            d_conf ? d_conf + r0 : nullptr, s);
+        });
+    if (rc) return rc;
+    // failed reads are masked ONCE over all reads, behind the last block
+    return launch_svm_mask_failed(d_status, n_reads, k, d_prob, d_pred, d_conf, s);
+}
+
+int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if (R.window == 0 || !ctx->svm_set) {
+        set_error("dtw_svm_predict needs wdx_set_refs and wdx_svm_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (R.nY != ctx->svm.n_train) {
+        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)R.nY, ctx->svm.n_train);
+        return WDX_ERR_INVALID;
+    }
+    if (n < 0 || (n > 0 && !X)) {
+        set_error("dtw_svm_predict: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (n == 0) return WDX_SUCCESS;
+    hipStream_t s = ctx->stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int k = ctx->svm.k;
+    const int64_t chunk = host_chunk_rows(n, R.nY);
+    if ((rc = ensure_chunk_buffers(ctx, chunk, k, 0))) return rc;
+    StreamDrain drain(s);
+    if ((rc = dtw_predict_chunks(ctx, X, n, chunk, k, prob, pred, conf, s, [&](const float *d, int64_t, int64_t m) {
+            return svm_tail(ctx, ctx->svm, d, m, nullptr, (double *)ctx->out1.p, (int32_t *)ctx->out2.p, (double *)ctx->out3.p, s);
+        })))
+        return rc;
+    WDX_HIP_TRY(hipStreamSynchronize(s));
+    drain.done();
+    return WDX_SUCCESS;
+}
+
+int wdx_mlp_set_model(wdx_ctx *ctx, const wdx_mlp_model *m) {
+    WDX_ENTER(ctx);
+    // every check before anything of the resident model is touched: a refused model keeps the previous one
+    if (!m || (m->dtype_bytes != 4 && m->dtype_bytes != 8) || m->n_classes < 2 || m->n_layers < 1 || m->n_scalers < 0 ||
+        m->hidden_activation < WDX_MLP_ACT_IDENTITY || m->hidden_activation > WDX_MLP_ACT_RELU) {
+        set_error("mlp_set_model: need a float32 / float64 model with >= 2 classes, layers and a known activation");
+        return WDX_ERR_INVALID;
+    }
+    const int nl = m->n_layers, k = m->n_classes;
+    if (nl < 2 || nl > WDX_MLP_MAX_LAYERS) {
+        set_error("mlp_set_model: %d hidden layers (1..%d supported)", nl - 1, WDX_MLP_MAX_LAYERS - 1);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (k > 16) {
+        set_error("mlp_set_model: %d classes (2..16 supported)", k);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (m->n_scalers > WDX_MLP_MAX_SCALERS) {
+        set_error("mlp_set_model: %d scaler steps (at most %d supported)", m->n_scalers, WDX_MLP_MAX_SCALERS);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    for (int i = 0; i <= nl; ++i)
+        if (m->sizes[i] < 1) {
+            set_error("mlp_set_model: layer size %d of entry %d", m->sizes[i], i);
+            return WDX_ERR_INVALID;
+        }
+    for (int i = 0; i < nl; ++i)
+        if (!m->coefs[i] || !m->intercepts[i]) {
+            set_error("mlp_set_model: layer %d has no coefficients / intercepts", i);
+            return WDX_ERR_INVALID;
+        }
+    const int nout = m->sizes[nl];
+    if (nout != k && !(nout == 1 && k == 2)) {
+        set_error("mlp_set_model: %d output units for %d classes", nout, k);
+        return WDX_ERR_INVALID;
+    }
+    int widest = 16;
+    for (int i = 1; i < nl; ++i) {
+        if (m->sizes[i] > WDX_MLP_MAX_WIDTH) {
+            set_error("mlp_set_model: hidden layer of %d units (at most %d supported)", m->sizes[i], WDX_MLP_MAX_WIDTH);
+            return WDX_ERR_UNSUPPORTED;
+        }
+        widest = std::max(widest, m->sizes[i]);
+    }
+    const int64_t n_in = m->sizes[0];
+    const size_t T = (size_t)m->dtype_bytes;
+    // one device block: [doubles: scaler mean / scale steps | thresholds][working dtype: W_i | b_i ...][int32: label map]
+    size_t nd = (m->thresholds ? (size_t)k : 0);
+    for (int s_ = 0; s_ < m->n_scalers; ++s_) nd += (m->scaler_mean[s_] ? n_in : 0) + (m->scaler_scale[s_] ? n_in : 0);
+    size_t nw = 0;
+    for (int i = 0; i < nl; ++i) nw += (size_t)m->sizes[i] * m->sizes[i + 1] + (size_t)m->sizes[i + 1];
+    const size_t bytes = nd * 8 + round_up((int64_t)(nw * T), 8) + (m->label_map ? (size_t)k * 4 : 0);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((rc = use_stream(ctx, ctx->stream))) return rc;
+    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
+    // ASYMMETRY, kept: wdx_svm_set_model has no device-wide synchronisation
+    WDX_HIP_TRY(hipDeviceSynchronize());  // (nor one on a caller's stream: the model is replaced in place)
+    std::vector<unsigned char> h(bytes);
+    ctx->mlp_set = false;  // not set until the upload below has succeeded
+    if ((rc = ctx->mlp_buf.ensure(bytes))) return rc;
+    MlpDev M{};
+    unsigned char *dev = (unsigned char *)ctx->mlp_buf.p;
+    size_t o = 0;
+    for (int s_ = 0; s_ < m->n_scalers; ++s_) {
+        for (int which = 0; which < 2; ++which) {
+            const double *src = which ? m->scaler_scale[s_] : m->scaler_mean[s_];
+            if (!src) continue;
+            memcpy(h.data() + o, src, (size_t)n_in * 8);
+            (which ? M.scale[s_] : M.mean[s_]) = (const double *)(dev + o);
+            o += (size_t)n_in * 8;
+        }
+    }
+    if (m->thresholds) {
+        memcpy(h.data() + o, m->thresholds, (size_t)k * 8);
+        M.thresholds = (const double *)(dev + o);
+        o += (size_t)k * 8;
+    }
+    for (int i = 0; i < nl; ++i) {
+        const size_t wb = (size_t)m->sizes[i] * m->sizes[i + 1] * T, bb = (size_t)m->sizes[i + 1] * T;
+        memcpy(h.data() + o, m->coefs[i], wb);
+        M.coef[i] = dev + o;
+        o += wb;
+        memcpy(h.data() + o, m->intercepts[i], bb);
+        M.bias[i] = dev + o;
+        o += bb;
+    }
+    o = (size_t)round_up((int64_t)o, 8);
+    if (m->label_map) {
+        memcpy(h.data() + o, m->label_map, (size_t)k * 4);
+        M.label_map = (const int32_t *)(dev + o);
+    }
+    WDX_HIP_TRY(hipMemcpy(ctx->mlp_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    for (int i = 0; i <= nl; ++i) M.sizes[i] = m->sizes[i];
+    M.n_layers = nl;
+    M.n_scalers = m->n_scalers;
+    M.dtype_bytes = m->dtype_bytes;
+    M.hidden_act = m->hidden_activation;
+    M.k = k;
+    M.ld = (int)round_up(widest, 16) + 1;
+    ctx->mlp = M;
+    ctx->mlp_set = true;
+    return WDX_SUCCESS;
+}
+
+int wdx_mlp_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred, double *d_conf,
+                        int64_t *d_n_nonfinite, void *stream) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->mlp_set) {
+        set_error("no MLP model: call wdx_mlp_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (n < 0 || (n > 0 && !d_dist)) {
+        set_error("mlp_predict_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
+    Timed t(ctx, WDX_K_MLP, (hipStream_t)stream);
+    return launch_mlp_predict(ctx->mlp, d_dist, n, nullptr, d_prob, d_pred, d_conf, d_n_nonfinite, (hipStream_t)stream);
+}
+
+int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf,
+                        int64_t *n_nonfinite) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if (R.window == 0 || !ctx->mlp_set) {
+        set_error("dtw_mlp_predict needs wdx_set_refs and wdx_mlp_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (R.nY != ctx->mlp.sizes[0]) {
+        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
+        return WDX_ERR_INVALID;
+    }
+    if (n < 0 || (n > 0 && !X)) {
+        set_error("dtw_mlp_predict: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (n_nonfinite) *n_nonfinite = 0;
+    if (n == 0) return WDX_SUCCESS;
+    hipStream_t s = ctx->stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int k = ctx->mlp.k;
+    int64_t chunk = host_chunk_rows(n, R.nY);
+    if (ctx->knobs.mlp_chunk_rows > 0) chunk = std::min<int64_t>(chunk, ctx->knobs.mlp_chunk_rows);
+    if ((rc = ensure_chunk_buffers(ctx, chunk, k, 8))) return rc;   // (+ 8: the non-finite counter behind conf)
+    int64_t *d_cnt = (int64_t *)((unsigned char *)ctx->out3.p + (size_t)chunk * 8);
+    int64_t h_cnt = 0;
+    StreamDrain drain(s);
+    WDX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
+    if ((rc = dtw_predict_chunks(ctx, X, n, chunk, k, prob, pred, conf, s, [&](const float *d, int64_t, int64_t m) {
+            Timed t(ctx, WDX_K_MLP, s);
+            return launch_mlp_predict(ctx->mlp, d, m, nullptr, (double *)ctx->out1.p, (int32_t *)ctx->out2.p,
+                                      (double *)ctx->out3.p, d_cnt, s);
+        })))
+        return rc;
+    WDX_HIP_TRY(hipMemcpyAsync(&h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipStreamSynchronize(s));
+    drain.done();
+    if (n_nonfinite) *n_nonfinite = h_cnt;
+    return WDX_SUCCESS;
+}
+
+int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                      int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
+                      const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
+                      double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
+                      int64_t block_rows, void *stream) {
+    WDX_ENTER(ctx);
+    if (n_reads < 0 || !p || block_rows < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
+        set_error("demux_mlp_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if (R.window == 0 || !ctx->mlp_set) {
+        set_error("demux_mlp_dev needs wdx_set_refs and wdx_mlp_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (R.nY != ctx->mlp.sizes[0]) {
+        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
+        return WDX_ERR_INVALID;
+    }
+    if ((rc = check_ref_length(R, *p))) return rc;
+    if (n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int k = ctx->mlp.k;
+    // ASYMMETRY, kept: an explicit block_rows is honoured as given; wdx_demux_svm_dev raises it to 2048
+    const int64_t rows = std::min(n_reads, block_rows > 0 ? block_rows : default_block_rows(R.nY));
+    if (!d_dist && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
+    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
+    const double *fpt = nullptr;
+    if ((rc = demux_fingerprints(ctx, in, *p, d_fpt, d_status, d_work, s, &fpt))) return rc;
+    // (failed reads are masked by the kernel itself, block by block: its d_status argument)
+    return dtw_row_blocks(ctx, fpt, n_reads, rows, d_dist, s, [&](const float *dblk, int64_t r0, int64_t m) {
+        Timed t(ctx, WDX_K_MLP, s);
+        return launch_mlp_predict(ctx->mlp, dblk, m, d_status + r0, d_prob ? d_prob + r0 * k : nullptr,
+                                  d_pred ? d_pred + r0 : nullptr, d_conf ? d_conf + r0 : nullptr, d_n_nonfinite, s);
+    });
+}
+
+}  // extern "C"

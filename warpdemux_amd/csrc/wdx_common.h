@@ -151,14 +151,26 @@ struct MainEvents {
     std::pair<hipEvent_t, hipEvent_t> (*take)(void *) = nullptr;
     void *take_arg = nullptr;
 };
-int launch_fingerprint(const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len,
-                       int64_t stride, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
-                       const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params &p,
-                       double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_status,
-                       hipStream_t stream, void *d_ws /* fingerprint_workspace_bytes(n) or null */,
-                       const Knobs &knobs, int64_t *n_launches = nullptr, long long *d_prof = nullptr,
-                       int64_t prof_reads = 0, int stop_phase = 0, const struct RefineDev *rf = nullptr,
-                       MainEvents *main_ev = nullptr,
+// The reads of one fingerprint call and where its results go (device pointers; named members, because d_a_start, d_a_end
+// and d_row_len are three adjacent const int32_t * and a transposed positional argument compiles).
+struct FpReads {
+    const float *sig;
+    const int64_t *row_off;  // packed rows: int64[n_reads + 1] (then stride is ignored); null = (n_reads, stride) rows
+    const int32_t *row_len;  // nullable
+    int64_t stride, max_len, n_reads;
+    const int32_t *a_start, *a_end;
+    const uint8_t *ok;  // nullable
+};
+struct FpOut {
+    double *fpt;
+    int64_t *dwell;  // nullable
+    double *stats;   // nullable
+    int32_t *status;
+};
+int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &out, hipStream_t stream,
+                       void *d_ws /* fingerprint_workspace_bytes(n) or null */, const Knobs &knobs,
+                       int64_t *n_launches = nullptr, long long *d_prof = nullptr, int64_t prof_reads = 0,
+                       int stop_phase = 0, const struct RefineDev *rf = nullptr, MainEvents *main_ev = nullptr,
                        double *d_big = nullptr /* fingerprint_big_bytes(max_len) bytes, or null */);
 int64_t fingerprint_workspace_bytes(int64_t n_reads);
 // device bytes of the fast kernels' hand-over records for the refinement branch (RefineDev::ws), zero-initialised

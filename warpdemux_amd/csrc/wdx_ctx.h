@@ -1,5 +1,5 @@
-// The opaque context behind include/wdx.h's wdx_ctx (internal; shared by wdx_api.hip, wdx_comm.hip
-// and wdx_live.hip).  Nothing here computes results.
+// The opaque context behind include/wdx.h's wdx_ctx (internal; shared by wdx_api.hip, wdx_classify.hip,
+// wdx_comm.hip and wdx_live.hip).  Nothing here computes results.
 #pragma once
 #include "wdx_common.h"
 
@@ -118,6 +118,27 @@ int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int
                    hipStream_t stream);
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+// (wdx_api.hip) The fingerprint stage as every entry point but the profiling one runs it: `B` (the context, or the
+// pipeline slot that owns the stream) supplies fp_big for max_len, the knobs and the WDX_K_FINGERPRINT event scope.
+// main_events = false leaves the main / clip / tail kernel pairs unrecorded (they go back to the pool):
+// wdx_fingerprint_refine_dev, the host-batch call (fingerprint_batch_impl) and wdx_live_tick have never recorded them.
+// Kept as found: neither DESIGN.md nor DESIGN_HISTORY.md gives a reason.
+int fingerprint_stage(wdx_ctx *B, const FpReads &in, const wdx_seg_params &p, const FpOut &out, void *d_ws,
+                      hipStream_t s, const RefineDev *rf = nullptr, bool main_events = true);
+// (wdx_api.hip) "barcode_num_events != reference length" check of every entry that fingerprints and then runs the DTW
+int check_ref_length(const DtwRefs &R, const wdx_seg_params &p);
+// (wdx_api.hip) Byte offsets of the pieces of a caller's d_work, and its size (wdx_demux_workspace_bytes):
+// [fpt (n,K) f64][with_T only: fptT (K,ld) f64 | nan flags ld][fingerprint workspace], pieces on 256-byte boundaries.
+// with_T: the read-minor copy wdx_demux_dev makes of a small batch; the classifier entries pass false.
+struct DemuxWork {
+    int64_t ld, fptT, flags, fp_ws, bytes;
+};
+DemuxWork demux_work_layout(int64_t n_reads, int64_t K, bool with_T);
+// (wdx_classify.hip) SVM tail on a device distance block (n, n_train) under WDX_K_SVM; with d_status (nullable) the
+// failed reads are masked right behind it: pred -1, NaN probabilities (the reference never shows them to the model)
+int svm_tail(wdx_ctx *B, const SvmDev &M, const float *d_dist, int64_t n, const int32_t *d_status, double *d_prob,
+             int32_t *d_pred, double *d_conf, hipStream_t s);
 
 }  // namespace wdx
 

@@ -1730,13 +1730,10 @@ static int fast_combo(const wdx_seg_params &p) {
 }
 static bool fast_combo_exact_only(int combo) { return combo >= 9; }
 
-int launch_fingerprint(const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len,
-                       int64_t stride, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
-                       const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params &p,
-                       double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_status,
-                       hipStream_t stream, void *d_ws, const Knobs &knobs, int64_t *n_launches,
-                       long long *d_prof, int64_t prof_reads, int stop_phase, const RefineDev *rf,
-                       MainEvents *main_ev, double *d_big) {
+int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &out, hipStream_t stream, void *d_ws,
+                       const Knobs &knobs, int64_t *n_launches, long long *d_prof, int64_t prof_reads, int stop_phase,
+                       const RefineDev *rf, MainEvents *main_ev, double *d_big) {
+    const int64_t max_len = in.max_len, n_reads = in.n_reads;
     if (n_reads == 0) return WDX_SUCCESS;
     if (n_reads > 0x7fffffffLL) {
         set_error("at most 2^31-1 reads per call");
@@ -1767,8 +1764,8 @@ int launch_fingerprint(const float *d_sig, const int64_t *d_row_off, const int32
     // fingerprint_big_kernel at the end (needs the caller's fingerprint_big_bytes(max_len) buffer; without it they
     // are reported WDX_READ_FAIL_UNKNOWN as windows beyond WDX_MAX_ADAPTER_SAMPLES always are)
     const bool with_huge = max_len > kExactLdsCap && d_big != nullptr && !d_prof;
-    FpArgs A{d_sig, d_row_off, d_row_len, stride, n_reads, d_a_start, d_a_end, d_ok,
-             p,     d_fpt,     d_dwell,   d_stats, d_status, cap, 0, d_prof, prof_reads, stop_phase, 1, RefineDev{},
+    FpArgs A{in.sig, in.row_off, in.row_len, in.stride, n_reads, in.a_start, in.a_end, in.ok,
+             p,      out.fpt,    out.dwell,  out.stats, out.status, cap, 0, d_prof, prof_reads, stop_phase, 1, RefineDev{},
              d_big, with_huge ? 1 : 0, knobs.exact_no_list ? 1 : 0};
     {
         const uint64_t e1 = (uint64_t)(p.num_events > 0 ? p.num_events : 1);

@@ -30,10 +30,7 @@ int wdx_live_tick(wdx_ctx *ctx, const float *const *rows, const int32_t *row_len
         return WDX_ERR_NO_REFS;
     }
     const int64_t K = p->barcode_num_events;
-    if (K != R.L) {
-        set_error("barcode_num_events (%lld) != reference length (%lld)", (long long)K, (long long)R.L);
-        return WDX_ERR_INVALID;
-    }
+    if ((rc = check_ref_length(R, *p))) return rc;
     if (n_refs != R.nY) {
         set_error("live_tick: the caller sized `dist` for %lld references but %lld are resident", (long long)n_refs,
                   (long long)R.nY);
@@ -108,21 +105,15 @@ int wdx_live_tick(wdx_ctx *ctx, const float *const *rows, const int32_t *row_len
     if ((rc = ctx->out0.ensure(out_bytes))) return rc;
     if ((rc = ctx->pin_out.ensure(out_bytes))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    if ((rc = ctx->fp_big.ensure((size_t)fingerprint_big_bytes(max_len)))) return rc;
     unsigned char *din = (unsigned char *)ctx->in0.p, *dout = (unsigned char *)ctx->out0.p;
     unsigned char *hout = (unsigned char *)ctx->pin_out.p;
 
     StreamDrain drain(s);
     WDX_HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, s));
-    {
-        Timed t(ctx, WDX_K_FINGERPRINT, s);
-        if ((rc = launch_fingerprint((const float *)(din + o_sig), (const int64_t *)(din + o_off), nullptr, 0,
-                                     max_len, n_reads, (const int32_t *)(din + o_zero), (const int32_t *)(din + o_len),
-                                     (const uint8_t *)(din + o_ok), *p, (double *)(dout + q_fpt), nullptr, nullptr,
-                                     (int32_t *)(dout + q_status), s, ctx->fp_ws.p, ctx->knobs, &t.n_launches, nullptr, 0,
-                                     0, nullptr, nullptr, (double *)ctx->fp_big.p)))
-            return rc;
-    }
+    const FpReads in{(const float *)(din + o_sig), (const int64_t *)(din + o_off), nullptr, 0, max_len, n_reads,
+                     (const int32_t *)(din + o_zero), (const int32_t *)(din + o_len), (const uint8_t *)(din + o_ok)};
+    const FpOut out{(double *)(dout + q_fpt), nullptr, nullptr, (int32_t *)(dout + q_status)};
+    if ((rc = fingerprint_stage(ctx, in, *p, out, ctx->fp_ws.p, s, nullptr, false))) return rc;
     if (R.nY > 0) {
         if ((rc = dtw_dev_locked(ctx, (const double *)(dout + q_fpt), n_reads, (float *)(dout + q_dist),
                                  (int32_t *)(dout + q_call), s)))
@@ -130,16 +121,10 @@ int wdx_live_tick(wdx_ctx *ctx, const float *const *rows, const int32_t *row_len
         if ((rc = launch_count_calls((int32_t *)(dout + q_call), (const int32_t *)(dout + q_status), n_reads, R.nY,
                                      nullptr, s)))
             return rc;
-        if (use_svm) {
-            Timed t(ctx, WDX_K_SVM, s);
-            if ((rc = launch_svm_predict(ctx->svm, (const float *)(dout + q_dist), n_reads, (double *)(dout + q_prob),
-                                         (int32_t *)(dout + q_pred), (double *)(dout + q_conf), s, ctx->knobs)))
-                return rc;
-            // failed reads: pred -1, NaN prob / conf, as every other entry point that runs the tail returns them
-            if ((rc = launch_svm_mask_failed((const int32_t *)(dout + q_status), n_reads, k, (double *)(dout + q_prob),
-                                             (int32_t *)(dout + q_pred), (double *)(dout + q_conf), s)))
-                return rc;
-        }
+        // failed reads: pred -1, NaN prob / conf, as every other entry point that runs the tail returns them
+        if (use_svm && (rc = svm_tail(ctx, ctx->svm, (const float *)(dout + q_dist), n_reads, (const int32_t *)(dout + q_status),
+                                      (double *)(dout + q_prob), (int32_t *)(dout + q_pred), (double *)(dout + q_conf), s)))
+            return rc;
     }
     // one device->host copy of what the caller asked for: [first wanted byte, last wanted byte)
     size_t lo = q_status, hi = q_call + b_call;

@@ -85,20 +85,16 @@ class DemuxEngine:
                 counts=counts if counts is not None else torch.zeros(self.nY + 1, dtype=torch.int64, device=self.tdev),
                 fpt=torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None,
             )
-        need = int(self.L.wdx_demux_workspace_bytes(n, self.K))
-        if self._work is None or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
         pc = self.params.to_c()
         _lib.check(self.L.wdx_demux_dev(
             self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n,
             _dp(a_start), _dp(a_end), _dp(ok), C.byref(pc), _dp(out.fpt), None, None,
-            _dp(out.status), _dp(out.dist), _dp(out.call), _dp(out.counts), _dp(self._work),
+            _dp(out.status), _dp(out.dist), _dp(out.call), _dp(out.counts), _dp(self._ensure_work(n)),
             self._stream()))
         return out
 
     def fingerprint(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, want_stats: bool = True):
-        """Fingerprint stage only -> (fpt f64 (n,K), dwell i64 (n,K), stats f64 (n,6) or None, status i32).  Without the six
-        statistics a large RNA004 batch takes the split main kernel (tile kernel + tail kernel), like `demux` does."""
+        """Fingerprint stage only -> (fpt f64 (n,K), dwell i64 (n,K), stats f64 (n,6) or None, status i32)."""
         torch = self.torch
         n = int(a_start.shape[0])
         fpt = torch.empty((n, self.K), dtype=torch.float64, device=self.tdev)
@@ -151,102 +147,87 @@ class DemuxEngine:
         _lib.check(self.L.wdx_dtw_matrix_dev(self.ctx.handle, _dp(X), n, _dp(dist), _dp(am), self._stream()))
         return dist, am
 
-    # -- classifier tail -----------------------------------------------------------
+    # -- classifier tails: SVM and MLP (DTW_MLP) ---------------------------------
+    def _ensure_work(self, n):
+        need = int(self.L.wdx_demux_workspace_bytes(n, self.K))
+        if self._work is None or self._work.numel() < need:
+            self._work = self.torch.empty(need, dtype=self.torch.uint8, device=self.tdev)
+        return self._work
+
+    def _set_model(self, model, kind, setter):
+        """Upload ``model`` through ``setter`` and record it as the owner of the context's ``kind`` slot."""
+        if model._X.shape != (self.nY, self.K):
+            raise ValueError(f"the {kind.upper()}'s training set must be the engine's reference set")
+        setattr(self, f"_{kind}_model", model)   # keeps the host arrays alive during the upload
+        m = model.to_c()
+        setattr(self.ctx, f"_{kind}_owner", None)
+        _lib.check(setter(self.ctx.handle, C.byref(m)))
+        setattr(self.ctx, f"_{kind}_owner", model)
+
+    def _tail_predict(self, entry, k, dist, *extra):
+        """``entry`` (wdx_{svm,mlp}_predict_dev) on a device distance matrix; ``extra``: arguments between conf and the stream."""
+        torch = self.torch
+        n = int(dist.shape[0])
+        prob = torch.empty((n, k), dtype=torch.float64, device=self.tdev)
+        pred = torch.empty(n, dtype=torch.int32, device=self.tdev)
+        conf = torch.empty(n, dtype=torch.float64, device=self.tdev)
+        _lib.check(entry(self.ctx.handle, _dp(dist), n, _dp(prob), _dp(pred), _dp(conf), *extra, self._stream()))
+        return prob, pred, conf
+
+    def _demux_tail(self, entry, k, sig, a_start, a_end, offsets, stride, max_len, ok, want_dist, want_fpt, block_rows, out,
+                    *extra):
+        """``entry`` (wdx_demux_{svm,mlp}_dev) on raw rows; ``extra``: arguments between conf and the workspace."""
+        torch = self.torch
+        n = int(a_start.shape[0])
+        if out is None:
+            out = (torch.empty((n, k), dtype=torch.float64, device=self.tdev),
+                   torch.empty(n, dtype=torch.int32, device=self.tdev),
+                   torch.empty(n, dtype=torch.float64, device=self.tdev),
+                   torch.empty(n, dtype=torch.int32, device=self.tdev),
+                   torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev) if want_dist else None,
+                   torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None)
+        prob, pred, conf, status, dist, fpt = out
+        pc = self.params.to_c()
+        _lib.check(entry(
+            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+            C.byref(pc), _dp(fpt), _dp(status), _dp(dist), _dp(prob), _dp(pred), _dp(conf), *extra,
+            _dp(self._ensure_work(n)), int(block_rows), self._stream()))
+        return out
+
     def set_svm(self, model):
         """``model``: a warpdemux_amd.models.DTW_SVM whose ``_X`` is the resident reference set."""
-        if model._X.shape != (self.nY, self.K):
-            raise ValueError("the SVM's training set must be the engine's reference set")
-        self._svm_model = model   # keeps the host arrays alive during the upload
-        m = model.to_c()
-        self.ctx._svm_owner = None
-        _lib.check(self.L.wdx_svm_set_model(self.ctx.handle, C.byref(m)))
-        self.ctx._svm_owner = model
+        self._set_model(model, "svm", self.L.wdx_svm_set_model)
         self.n_classes = model.n_classes
 
     def svm_predict(self, dist):
         """(prob f64 (n,k), pred i32 (n,), conf f64 (n,)) from a device (n, nY) float32 distance matrix:
         models/dtw_svm.py:90-93 + models/utils.py:45-61."""
-        torch = self.torch
-        n = int(dist.shape[0])
-        prob = torch.empty((n, self.n_classes), dtype=torch.float64, device=self.tdev)
-        pred = torch.empty(n, dtype=torch.int32, device=self.tdev)
-        conf = torch.empty(n, dtype=torch.float64, device=self.tdev)
-        _lib.check(self.L.wdx_svm_predict_dev(self.ctx.handle, _dp(dist), n, _dp(prob), _dp(pred), _dp(conf),
-                                              self._stream()))
-        return prob, pred, conf
+        return self._tail_predict(self.L.wdx_svm_predict_dev, self.n_classes, dist)
 
     def demux_svm(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, want_dist=False,
                   want_fpt=False, block_rows: int = 0, out=None):
         """The shipped models' whole path, device-resident (wdx_demux_svm_dev): raw rows -> fingerprint -> DTW against
         the resident training set -> SVM tail.  Returns (prob f64 (n,k), pred i32 (n,), conf f64 (n,), status i32 (n,),
         dist f32 (n,nY) or None, fpt f64 (n,K) or None); ``out`` = such a tuple from an earlier call is reused."""
-        torch = self.torch
-        n = int(a_start.shape[0])
-        if out is None:
-            out = (torch.empty((n, self.n_classes), dtype=torch.float64, device=self.tdev),
-                   torch.empty(n, dtype=torch.int32, device=self.tdev),
-                   torch.empty(n, dtype=torch.float64, device=self.tdev),
-                   torch.empty(n, dtype=torch.int32, device=self.tdev),
-                   torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev) if want_dist else None,
-                   torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None)
-        prob, pred, conf, status, dist, fpt = out
-        need = int(self.L.wdx_demux_workspace_bytes(n, self.K))
-        if self._work is None or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
-        pc = self.params.to_c()
-        _lib.check(self.L.wdx_demux_svm_dev(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
-            C.byref(pc), _dp(fpt), _dp(status), _dp(dist), _dp(prob), _dp(pred), _dp(conf), _dp(self._work), int(block_rows),
-            self._stream()))
-        return out
+        return self._demux_tail(self.L.wdx_demux_svm_dev, self.n_classes, sig, a_start, a_end, offsets, stride, max_len, ok,
+                                want_dist, want_fpt, block_rows, out)
 
-    # -- MLP classifier tail (DTW_MLP; DESIGN.md 4.7) -------------------------------------------------
     def set_mlp(self, model):
         """``model``: a warpdemux_amd.models.DTW_MLP whose ``_X`` is the resident reference set."""
-        if model._X.shape != (self.nY, self.K):
-            raise ValueError("the MLP's training set must be the engine's reference set")
-        self._mlp_model = model   # keeps the host arrays alive during the upload
-        m = model.to_c()
-        self.ctx._mlp_owner = None
-        _lib.check(self.L.wdx_mlp_set_model(self.ctx.handle, C.byref(m)))
-        self.ctx._mlp_owner = model
+        self._set_model(model, "mlp", self.L.wdx_mlp_set_model)
         self.mlp_classes = model.k
 
     def mlp_predict(self, dist, n_nonfinite=None):
         """(prob f64 (n,k), pred i32 (n,), conf f64 (n,)) from a device (n, nY) float32 distance matrix (wdx_mlp_predict_dev);
         ``n_nonfinite``: optional int64 (1,) device tensor, incremented by the rows with a non-finite input."""
-        torch = self.torch
-        n = int(dist.shape[0])
-        prob = torch.empty((n, self.mlp_classes), dtype=torch.float64, device=self.tdev)
-        pred = torch.empty(n, dtype=torch.int32, device=self.tdev)
-        conf = torch.empty(n, dtype=torch.float64, device=self.tdev)
-        _lib.check(self.L.wdx_mlp_predict_dev(self.ctx.handle, _dp(dist), n, _dp(prob), _dp(pred), _dp(conf),
-                                              _dp(n_nonfinite), self._stream()))
-        return prob, pred, conf
+        return self._tail_predict(self.L.wdx_mlp_predict_dev, self.mlp_classes, dist, _dp(n_nonfinite))
 
     def demux_mlp(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, want_dist=False,
                   want_fpt=False, block_rows: int = 0, n_nonfinite=None, out=None):
         """demux_svm with the MLP tail (wdx_demux_mlp_dev): raw rows -> fingerprint -> DTW row blocks -> MLP tail.  Returns
         (prob f64 (n,k), pred i32 (n,), conf f64 (n,), status i32 (n,), dist f32 (n,nY) or None, fpt f64 (n,K) or None)."""
-        torch = self.torch
-        n = int(a_start.shape[0])
-        if out is None:
-            out = (torch.empty((n, self.mlp_classes), dtype=torch.float64, device=self.tdev),
-                   torch.empty(n, dtype=torch.int32, device=self.tdev),
-                   torch.empty(n, dtype=torch.float64, device=self.tdev),
-                   torch.empty(n, dtype=torch.int32, device=self.tdev),
-                   torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev) if want_dist else None,
-                   torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None)
-        prob, pred, conf, status, dist, fpt = out
-        need = int(self.L.wdx_demux_workspace_bytes(n, self.K))
-        if self._work is None or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
-        pc = self.params.to_c()
-        _lib.check(self.L.wdx_demux_mlp_dev(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
-            C.byref(pc), _dp(fpt), _dp(status), _dp(dist), _dp(prob), _dp(pred), _dp(conf), _dp(n_nonfinite),
-            _dp(self._work), int(block_rows), self._stream()))
-        return out
+        return self._demux_tail(self.L.wdx_demux_mlp_dev, self.mlp_classes, sig, a_start, a_end, offsets, stride, max_len, ok,
+                                want_dist, want_fpt, block_rows, out, _dp(n_nonfinite))
 
     # -- synthetic inputs, generated in HBM ----------------------------------------------------------
     def synth_packed(self, spec: synth.SynthSpec, first_read: int, n_reads: int):

@@ -30,17 +30,73 @@ def predictions_to_df(y_pred, y_prob, conf, label_mapper):
     )
 
 
-class DTW_SVM:
+class _ResidentDTWModel:
+    """What DTW_SVM and DTW_MLP share: the reference fingerprints, the DTW parameters and the label map on the host, the
+    upload to the process's context, and ``predict``'s validation.  Subclasses name their context slot (``_owner_attr``),
+    the library's setter (``_setter``) and the text of the column-mismatch error (``_column_error``)."""
+
+    _owner_attr: str
+    _setter: str
+
+    def _init_common(self, _X, window, penalty, block_size, label_mapper, thresholds, device):
+        self._X = np.ascontiguousarray(_X, dtype=np.float64)
+        self.window, self.penalty, self.block_size = window, penalty, block_size
+        self.label_mapper = dict(label_mapper)
+        self.thresholds = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        self._device = device
+
+    @property
+    def is_trained(self):
+        return self._X is not None
+
+    def _ensure_resident(self):
+        """References and model parameters on the process's context.  The context holds ONE reference set and ONE
+        model per slot (the SVM's and the MLP's are separate) at a time and other calls (distance_matrix_to,
+        set_references, another model of the same class) may have replaced either: the reference set is re-submitted on
+        every call (the library compares a content hash and uploads only on change), the model whenever this object is
+        not the one the context last received."""
+        ctx = _lib.default_context(self._device)
+        L = _lib.load()
+        _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(self._X), self._X.shape[0], self._X.shape[1],
+                                  int(self.window) if self.window else 0, float(self.penalty) if self.penalty else 0.0))
+        if getattr(ctx, self._owner_attr, None) is not self:
+            setattr(ctx, self._owner_attr, None)
+            m = self.to_c()
+            _lib.check(getattr(L, self._setter)(ctx.handle, C.byref(m)))
+            setattr(ctx, self._owner_attr, self)
+        return ctx
+
+    def _predict_inputs(self, X, nproc, block_size, k):
+        """``predict``'s prologue: (context, contiguous float64 X, y_prob (n, k), y_pred int32 (n,), conf (n,))."""
+        if not self.is_trained:
+            msg = "Model not trained yet."
+            logging.error(msg)
+            raise ValueError(msg)
+        X = np.asarray(X)
+        if X.ndim == 1:
+            X = X.reshape(1, -1)
+        if X.shape[1] != self._X.shape[1]:
+            raise ValueError(self._column_error())
+        if nproc != 1 and (self.block_size if block_size is None else block_size) is None:
+            msg = "block_size must be specified when using parallel."
+            logging.error(msg)
+            raise ValueError(msg)
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = X.shape[0]
+        ctx = self._ensure_resident()
+        return ctx, X, np.empty((n, k), dtype=np.float64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64)
+
+
+class DTW_SVM(_ResidentDTWModel):
     """Holds the reference fingerprints and the SVC parameters resident on one GPU context."""
+
+    _owner_attr, _setter = "_svm_owner", "wdx_svm_set_model"
 
     def __init__(self, _X: np.ndarray, n_support, support, dual_coef, rho, probA, probB,
                  label_mapper: Dict[int, int], thresholds: Optional[np.ndarray], window: int, penalty: float,
                  gamma: float = 1.0, pwr_dist: int = 1, block_size: Optional[int] = None, device: Optional[int] = None):
-        self._X = np.ascontiguousarray(_X, dtype=np.float64)
-        self.window, self.penalty, self.block_size = window, penalty, block_size
+        self._init_common(_X, window, penalty, block_size, label_mapper, thresholds, device)
         self.gamma, self.pwr_dist = float(gamma), int(pwr_dist)
-        self.label_mapper = dict(label_mapper)
-        self.thresholds = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
         self._n_support = np.ascontiguousarray(n_support, dtype=np.int32)
         self._support = np.ascontiguousarray(support, dtype=np.int32)
         self._dual_coef = np.ascontiguousarray(dual_coef, dtype=np.float64)
@@ -49,7 +105,6 @@ class DTW_SVM:
         self._probB = np.ascontiguousarray(probB, dtype=np.float64)
         self.n_classes = int(self._n_support.size)
         self._label_arr = np.array([self.label_mapper[i] for i in range(self.n_classes)], dtype=np.int32)
-        self._device = device
 
     @classmethod
     def from_reference(cls, model, device: Optional[int] = None) -> "DTW_SVM":
@@ -66,10 +121,6 @@ class DTW_SVM:
         )
 
     @property
-    def is_trained(self):
-        return self._X is not None
-
-    @property
     def num_bcs(self):
         return self.n_classes
 
@@ -82,47 +133,15 @@ class DTW_SVM:
             None if self.thresholds is None else self.thresholds.ctypes.data,
         )
 
-    def _ensure_resident(self):
-        """References and SVM parameters on the process's context.  The context holds ONE reference set and ONE
-        model at a time and other calls (distance_matrix_to, set_references, another DTW_SVM) may have replaced
-        either: the reference set is re-submitted on every call (the library compares a content hash and uploads
-        only on change), the model whenever this object is not the one the context last received."""
-        ctx = _lib.default_context(self._device)
-        L = _lib.load()
-        _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(self._X), self._X.shape[0], self._X.shape[1],
-                                  int(self.window) if self.window else 0, float(self.penalty) if self.penalty else 0.0))
-        if getattr(ctx, "_svm_owner", None) is not self:
-            ctx._svm_owner = None
-            m = self.to_c()
-            _lib.check(L.wdx_svm_set_model(ctx.handle, C.byref(m)))
-            ctx._svm_owner = self
-        return ctx
+    def _column_error(self) -> str:
+        return f"X must have the same number of columns as the training data  ({self._X.shape[1]})."
 
     def predict(self, X: np.ndarray, nproc: int = -1, block_size: Optional[int] = None, pbar: bool = False,
                 pbar_kwargs: dict = {}, return_df: bool = False) -> Union[Tuple[np.ndarray, np.ndarray], "object"]:
         """(y_pred, y_prob) or the predictions DataFrame -- dtw_svm.py:54-98.  ``nproc`` / ``block_size``
         keep the reference's validation (block_size required when nproc != 1) but nothing is forked."""
-        if not self.is_trained:
-            msg = "Model not trained yet."
-            logging.error(msg)
-            raise ValueError(msg)
-        X = np.asarray(X)
-        if X.ndim == 1:
-            X = X.reshape(1, -1)
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError("X must have the same number of columns as the training data "
-                             f" ({self._X.shape[1]}).")
-        if nproc != 1 and (self.block_size if block_size is None else block_size) is None:
-            msg = "block_size must be specified when using parallel."
-            logging.error(msg)
-            raise ValueError(msg)
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        n = X.shape[0]
-        ctx = self._ensure_resident()
-        y_prob = np.empty((n, self.n_classes), dtype=np.float64)
-        y_pred = np.empty(n, dtype=np.int32)
-        conf = np.empty(n, dtype=np.float64)
-        _lib.check(_lib.load().wdx_dtw_svm_predict(ctx.handle, _lib.ptr(X), n, _lib.ptr(y_prob), _lib.ptr(y_pred),
+        ctx, X, y_prob, y_pred, conf = self._predict_inputs(X, nproc, block_size, self.n_classes)
+        _lib.check(_lib.load().wdx_dtw_svm_predict(ctx.handle, _lib.ptr(X), X.shape[0], _lib.ptr(y_prob), _lib.ptr(y_pred),
                                                    _lib.ptr(conf)))
         y_pred = y_pred.astype(np.int64)
         if return_df:
@@ -152,17 +171,19 @@ def _sklearn_mlp_parts(est):
     return scalers, steps[-1]
 
 
-class DTW_MLP:
+class DTW_MLP(_ResidentDTWModel):
     """``warpdemux.models.dtw_mlp.DTW_MLP`` with the classifier tail resident on one GPU context: DTW distances to
     ``_X`` -> StandardScaler steps -> ``MLPClassifier.predict_proba`` -> ``process_probs``, the (n, len(_X)) distance
-    matrix never leaving HBM.  The working dtype is scikit-learn's: ``result_type(float32, coefs_[0].dtype)``."""
+    matrix never leaving HBM.  The working dtype is scikit-learn's: ``result_type(float32, coefs_[0].dtype)``.  The MLP
+    slot of the context is separate from the SVM's, so a resident SVM stays as it is."""
+
+    _owner_attr, _setter = "_mlp_owner", "wdx_mlp_set_model"
 
     def __init__(self, _X: np.ndarray, coefs, intercepts, activation: str, label_mapper: Dict[int, int],
                  thresholds: Optional[np.ndarray], window: int, penalty: float, scalers=(), n_classes: Optional[int] = None,
                  noise_class: bool = False, block_size: Optional[int] = None, out_activation: Optional[str] = None,
                  device: Optional[int] = None):
-        self._X = np.ascontiguousarray(_X, dtype=np.float64)
-        self.window, self.penalty, self.block_size = window, penalty, block_size
+        self._init_common(_X, window, penalty, block_size, label_mapper, thresholds, device)
         self.dtype = np.result_type(np.float32, np.asarray(coefs[0]).dtype)
         if self.dtype not in (np.float32, np.float64):
             raise ValueError(f"unsupported MLP dtype {self.dtype}")
@@ -179,12 +200,9 @@ class DTW_MLP:
                           None if s is None else np.ascontiguousarray(s, dtype=np.float64)) for m, s in scalers]
         self.n_outputs = n_out
         self.k = 2 if n_out == 1 else n_out
-        self.label_mapper = dict(label_mapper)
         self.n_classes = n_classes
         self.noise_class = noise_class
-        self.thresholds = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
         self._label_arr = np.array([self.label_mapper[i] for i in range(self.k)], dtype=np.int32)
-        self._device = device
 
     @classmethod
     def from_reference(cls, model, device: Optional[int] = None) -> "DTW_MLP":
@@ -197,10 +215,6 @@ class DTW_MLP:
             thresholds=model.thresholds, window=model.window, penalty=model.penalty, block_size=model.block_size,
             n_classes=getattr(model, "n_classes", None), noise_class=getattr(model, "noise_class", False), device=device,
         )
-
-    @property
-    def is_trained(self):
-        return self._X is not None
 
     def num_bcs(self) -> int:
         """dtw_mlp.py:95-100"""
@@ -233,19 +247,8 @@ class DTW_MLP:
         m.thresholds = None if self.thresholds is None else self.thresholds.ctypes.data
         return m
 
-    def _ensure_resident(self):
-        """References and MLP on the process's context (see DTW_SVM._ensure_resident); the MLP slot is separate from
-        the SVM's, so a resident SVM stays as it is."""
-        ctx = _lib.default_context(self._device)
-        L = _lib.load()
-        _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(self._X), self._X.shape[0], self._X.shape[1],
-                                  int(self.window) if self.window else 0, float(self.penalty) if self.penalty else 0.0))
-        if getattr(ctx, "_mlp_owner", None) is not self:
-            ctx._mlp_owner = None
-            m = self.to_c()
-            _lib.check(L.wdx_mlp_set_model(ctx.handle, C.byref(m)))
-            ctx._mlp_owner = self
-        return ctx
+    def _column_error(self) -> str:
+        return f"X must have the same shape in axis 1 as the consensus sequences  ({self._X.shape})."
 
     def _nonfinite_message(self, X) -> str:
         """scikit-learn's first line for the distances of X (error path only: the distances are recomputed to the host)."""
@@ -269,28 +272,9 @@ class DTW_MLP:
                 pbar_kwargs: dict = {}, return_df: bool = False) -> Union[Tuple[np.ndarray, np.ndarray], "object"]:
         """(y_pred, y_prob) or the predictions DataFrame -- dtw_mlp.py:44-93.  ``nproc`` / ``block_size`` keep the
         reference's validation (distance_matrix_to wants block_size when nproc != 1) but nothing is forked."""
-        if not self.is_trained:
-            msg = "Model not trained yet."
-            logging.error(msg)
-            raise ValueError(msg)
-        X = np.asarray(X)
-        if X.ndim == 1:
-            X = X.reshape(1, -1)
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError("X must have the same shape in axis 1 as the consensus sequences "
-                             f" ({self._X.shape}).")
-        if nproc != 1 and (self.block_size if block_size is None else block_size) is None:
-            msg = "block_size must be specified when using parallel."
-            logging.error(msg)
-            raise ValueError(msg)
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        n = X.shape[0]
-        ctx = self._ensure_resident()
-        y_prob = np.empty((n, self.k), dtype=np.float64)
-        y_pred = np.empty(n, dtype=np.int32)
-        conf = np.empty(n, dtype=np.float64)
+        ctx, X, y_prob, y_pred, conf = self._predict_inputs(X, nproc, block_size, self.k)
         bad = C.c_int64(0)
-        _lib.check(_lib.load().wdx_dtw_mlp_predict(ctx.handle, _lib.ptr(X), n, _lib.ptr(y_prob), _lib.ptr(y_pred),
+        _lib.check(_lib.load().wdx_dtw_mlp_predict(ctx.handle, _lib.ptr(X), X.shape[0], _lib.ptr(y_prob), _lib.ptr(y_pred),
                                                    _lib.ptr(conf), C.byref(bad)))
         if bad.value:
             raise ValueError(self._nonfinite_message(X))
