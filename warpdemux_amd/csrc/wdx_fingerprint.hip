@@ -1568,22 +1568,29 @@ __global__ __launch_bounds__(BLOCK) void fingerprint_refine_tail_kernel(FpArgs A
 }
 
 #ifndef WDX_DEV_KERNELS_ONLY  // (development: a TU that instantiates single kernels includes this file with the macro set)
+// fn(base, n) over n_items in slices of at most launch_slice_limit(builtin): FULL slices and a remainder (the fast kernels'
+// launch_sliced cuts equal slices instead); stops at fn's first error
+template <class Fn>
+static int for_each_slice(int64_t n_items, int64_t builtin, Fn fn) {
+    const int64_t slice = launch_slice_limit(builtin);
+    for (int64_t base = 0; base < n_items; base += slice)
+        if (int rc = fn(base, std::min(slice, n_items - base))) return rc;
+    return WDX_SUCCESS;
+}
+
 static int launch_refine_tail(FpArgs A, unsigned *slow_count, int32_t *slow_list, hipStream_t stream) {
     static LdsAttr attr_t;
     const size_t lds_t = refine_tail_lds_bytes();
     if (int rc = attr_t.ensure(fingerprint_refine_tail_kernel<256>, lds_t)) return rc;
-    const int64_t slice = launch_slice_limit(1 << 22);
-    for (int64_t base = 0; base < A.n_reads; base += slice) {
-        const int64_t n = A.n_reads - base < slice ? A.n_reads - base : slice;
-        A.block_base = base;
-        if (int rc = launch_refine_match_wave(A, n, stream)) return rc;
-        if (refine_tail_wave_takes(A)) {
-            if (int rc = launch_refine_tail_wave(A, n, slow_count, slow_list, stream)) return rc;
-        } else {
+    if (int rc = for_each_slice(A.n_reads, 1 << 22, [&](int64_t base, int64_t n) {
+            A.block_base = base;
+            if (int rc = launch_refine_match_wave(A, n, stream)) return rc;
+            if (refine_tail_wave_takes(A)) return launch_refine_tail_wave(A, n, slow_count, slow_list, stream);
             hipLaunchKernelGGL((fingerprint_refine_tail_kernel<256>), dim3((unsigned)n), dim3(256), lds_t, stream, A, slow_count,
                                slow_list);
-        }
-    }
+            return (int)WDX_SUCCESS;
+        }))
+        return rc;
     WDX_HIP_TRY(hipGetLastError());
     return WDX_SUCCESS;
 }
@@ -1631,14 +1638,12 @@ static int launch_fp_chunks(FpArgs A, size_t lds, hipStream_t stream, int64_t *n
     static LdsAttr attr;
     if (int rc = attr.ensure(fingerprint_kernel<BLOCK, PROF>, lds)) return rc;
     // HIP drops work when grid.x * block.x reaches 2^32: launch in slices of 2^21 reads
-    const int64_t slice = launch_slice_limit(1 << 21);
-    for (int64_t base = 0; base < A.n_reads; base += slice) {
-        const int64_t n = A.n_reads - base < slice ? A.n_reads - base : slice;
+    (void)for_each_slice(A.n_reads, 1 << 21, [&](int64_t base, int64_t n) {
         A.block_base = base;
-        hipLaunchKernelGGL((fingerprint_kernel<BLOCK, PROF>), dim3((unsigned)n), dim3(BLOCK), lds,
-                           stream, A);
+        hipLaunchKernelGGL((fingerprint_kernel<BLOCK, PROF>), dim3((unsigned)n), dim3(BLOCK), lds, stream, A);
         if (n_launches) ++*n_launches;
-    }
+        return (int)WDX_SUCCESS;
+    });
     WDX_HIP_TRY(hipGetLastError());
     return WDX_SUCCESS;
 }
@@ -1689,547 +1694,7 @@ int launch_score_selftest(const double *dm, const double *vs, int64_t n, double 
     return WDX_SUCCESS;
 }
 
-// eight counters (five used) | one ClipRec per read | five read lists (slow, big0, big1, retry, big2: see launch_fingerprint)
-// | large batches: the split main kernel's peak lists for one launch slice (kSplitRecBytes per read, 16-byte aligned)
-// | 16 diagnostic counters (WDX_OPT_DEBUG_OCCUPANCY: why reads were handed to the exact kernel) at the very end -- in the
-// caller's workspace, i.e. per context and per call, ordered by the call's stream
-static int64_t split_ws_offset(int64_t n_reads) { return (32 + 40 * (n_reads > 0 ? n_reads : 0) + 15) / 16 * 16; }
-static int64_t dbg_ws_offset(int64_t n_reads) {
-    // (the lists of one slice for every batch size: 4.6 KB per read -- the launch chain is for batches of 2048 reads and
-    // more by default, but WDX_OPT_FAST_CHAIN_MIN_READS sends smaller ones through it: the randomised parameter tests)
-    return split_ws_offset(n_reads) + (int64_t)kSplitRecBytes * std::min<int64_t>(n_reads > 0 ? n_reads : 0, kSplitSlice);
-}
-int64_t fingerprint_workspace_bytes(int64_t n_reads) { return dbg_ws_offset(n_reads) + 64; }
-
-// The fast kernels exist for three (window width, suppression reach) combinations -- the shipped parameter triples:
-//   1: W = 12, d <= 9  (RNA004: 110, 6, 12)      every instantiation of the launch chain
-//   2: W = 18, d <= 9  (tRNA triple: 120, 9, 18; the tRNA config itself also refines -> exact kernel)
-//   3: W = 30, d <= 17 (RNA002 triple: 110, 15, 30)
-// 2 runs the 5120-sample instantiation as main kernel for large batches (then 6144 and 8192 behind it, like 1); 3 the
-// 6144-sample one, and the 8192-sample one for longer windows and retries.
-//   4 .. 6: W = 6 / 24 / 36, d <= 17 (round 5: the other multiples of the tile's six positions per lane -- configurations
-//           nobody ships, but `--export segmentation.running_stat_width=...` is one flag away, and the exact kernel
-//           behind this gate runs at a fifteenth of the rate); instantiated like 3 (NBT = 2, 6144-sample main kernel)
-//   7, 8: W = 12 / 18 with 9 < d <= 17: the same, for the shipped widths with a longer suppression reach.
-static int fast_combo(const wdx_seg_params &p) {
-    if (p.min_obs_per_base < 1) return 0;
-    if (p.running_stat_width == 12 && p.min_obs_per_base <= 9) return 1;
-    if (p.running_stat_width == 18 && p.min_obs_per_base <= 9) return 2;
-    if (p.running_stat_width == 30 && p.min_obs_per_base <= 17) return 3;
-    if (p.running_stat_width == 6 && p.min_obs_per_base <= 17) return 4;
-    if (p.running_stat_width == 24 && p.min_obs_per_base <= 17) return 5;
-    if (p.running_stat_width == 36 && p.min_obs_per_base <= 17) return 6;
-    if (p.running_stat_width == 12 && p.min_obs_per_base <= 17) return 7;   // (9 < d <= 17: the NBT = 2 form of the width)
-    if (p.running_stat_width == 18 && p.min_obs_per_base <= 17) return 8;
-    // 9 .. 37 (round 6): every other width from 7 to 35, d <= 17 -- widths that are not multiples of six, on the fast kernels'
-    // EXACT-scores pass (the partner window's statistics come from another slot of a lane one further); no approximate keys,
-    // no retry launch.  combo = 9 + (W - 7)
-    if (p.min_obs_per_base <= 17 && p.running_stat_width >= 7 && p.running_stat_width <= 35 && p.running_stat_width % 6 != 0)
-        return 9 + (p.running_stat_width - 7);
-    return 0;
-}
-static bool fast_combo_exact_only(int combo) { return combo >= 9; }
-
-int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &out, hipStream_t stream, void *d_ws,
-                       const Knobs &knobs, int64_t *n_launches, long long *d_prof, int64_t prof_reads, int stop_phase,
-                       const RefineDev *rf, MainEvents *main_ev, double *d_big) {
-    const int64_t max_len = in.max_len, n_reads = in.n_reads;
-    if (n_reads == 0) return WDX_SUCCESS;
-    if (n_reads > 0x7fffffffLL) {
-        set_error("at most 2^31-1 reads per call");
-        return WDX_ERR_INVALID;
-    }
-    LaunchSliceScope slice_scope(knobs.max_launch_slice);
-    if (p.num_events < 1 || p.num_events > kMaxEvents) {
-        set_error("num_events must be in [1, %d]", kMaxEvents);
-        return p.num_events < 1 ? WDX_ERR_INVALID : WDX_ERR_UNSUPPORTED;
-    }
-    if (p.barcode_num_events < 1 || p.barcode_num_events > kSegCap) {
-        set_error("barcode_num_events must be in [1, %d]", kSegCap);
-        return WDX_ERR_INVALID;
-    }
-    if (p.running_stat_width < 0 || p.running_stat_width > kMaxW) {
-        set_error("running_stat_width must be in [0, %d]", kMaxW);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (p.padding < 0) {
-        set_error("padding must be >= 0");
-        return WDX_ERR_INVALID;
-    }
-    int64_t cap64 = max_len;
-    if (cap64 > kExactLdsCap) cap64 = kExactLdsCap;
-    if (cap64 < 64) cap64 = 64;
-    int cap = (int)((cap64 + 63) / 64 * 64);
-    // windows of kExactLdsCap+1 .. kBigCap samples: left alone by every launch below and taken by
-    // fingerprint_big_kernel at the end (needs the caller's fingerprint_big_bytes(max_len) buffer; without it they
-    // are reported WDX_READ_FAIL_UNKNOWN as windows beyond WDX_MAX_ADAPTER_SAMPLES always are)
-    const bool with_huge = max_len > kExactLdsCap && d_big != nullptr && !d_prof;
-    FpArgs A{in.sig, in.row_off, in.row_len, in.stride, n_reads, in.a_start, in.a_end, in.ok,
-             p,      out.fpt,    out.dwell,  out.stats, out.status, cap, 0, d_prof, prof_reads, stop_phase, 1, RefineDev{},
-             d_big, with_huge ? 1 : 0, knobs.exact_no_list ? 1 : 0};
-    {
-        const uint64_t e1 = (uint64_t)(p.num_events > 0 ? p.num_events : 1);
-        A.e_magic1 = (unsigned)std::min<uint64_t>(((1ull << 32) + e1 - 1) / e1, 0xffffffffull);   // (E = 1: 2^32 - 1 -> q = n - 1, rounded up to n)
-        A.e_magic2 = (unsigned)(((1ull << 32) + 2 * e1 - 1) / (2 * e1));
-    }
-    if (rf) {
-        if (!rf->query || rf->nq < 1 || rf->nq > kRefineMaxQuery || p.num_events + 1 > kRefineMaxSeries) {
-            set_error("consensus refinement: the query must have 1..%d points and num_events + 1 <= %d", kRefineMaxQuery,
-                      kRefineMaxSeries);
-            return WDX_ERR_UNSUPPORTED;
-        }
-        if (rf->E2 < 1 || rf->E2 > kMaxEvents || rf->psi1b < 0 || rf->psi2b < 0) {
-            set_error("consensus refinement: barcode_num_events[0] must be in [1, %d], psi >= 0", kMaxEvents);
-            return WDX_ERR_INVALID;
-        }
-        A.rf = *rf;
-    }
-    const size_t lds = fp_lds_bytes(cap);
-    if (lds > 160 * 1024) {
-        set_error("fingerprint LDS carve-up (%zu B) exceeds 160 KiB", lds);
-        return WDX_ERR_INVALID;
-    }
-    (void)hipGetLastError();  // do not inherit a stale error from an earlier failed call
-    const bool small = lds <= 80 * 1024;
-    if (d_prof && !d_ws) return small ? launch_fp_chunks<512, true>(A, lds, stream, n_launches)
-                                      : launch_fp_chunks<1024, true>(A, lds, stream, n_launches);
-
-    // fast path for the common case + exact slow path for whatever it declines
-    // (the fast kernels take reads whose EFFECTIVE parameters are window width 12 and distance <= 9; with a configured
-    // width other than 12 or a configured distance beyond 9 only a few very short reads would qualify -- sig_proc.py:
-    // 526-533 shrinks the parameters for those -- and a launch chain whose main kernel declines nearly every read
-    // costs more than it saves: 1.62 against 1.99 M reads/s on the RNA002 triple (110, 15, 30))
-    const bool fast_ok = d_ws && p.sig_norm == WDX_NORM_NONE &&   // (accept_less_cpts: the fast kernels hand over the reads it concerns)
-                         p.num_events <= kFSeg - 2 && p.barcode_num_events <= p.num_events + 1 &&
-                         fast_combo(p) != 0 && (fast_combo(p) == 1 || !d_prof) && cap >= 512 && !knobs.exact_path &&
-                         (!rf || (rf->ws && !d_prof && p.num_events + 1 <= 128));
-    if (fast_ok) {
-        // A chain of launches, each handing what it cannot take to the next through device-side lists:
-        //   main    one workgroup per read; the instantiation follows the longest adapter window of the batch:
-        //           4096 or (large batches) 5120 samples at FIVE workgroups per CU, else 6144 at four.  A fifth
-        //           resident workgroup is worth 1.16x (tools/probes/occupancy_probe.py); 89 % of RNA004 adapter
-        //           windows fit 5120 samples
-        //   big0    windows (and peak lists) beyond the main instantiation -> 6144-sample list kernel
-        //   big1    beyond that -> 8192-sample list kernel (three workgroups per CU)
-        //   retry   reads whose approximate score keys left an order decision inside the error band (about 2 in
-        //           1000) -> 8192-sample list kernel with exact scores
-        //   slow    everything else (NaNs, other window widths, long plateaus, ...) -> the exact general kernel
-        // Small batches (live ticks) skip the approximate keys, and with them the retry launch, and go straight
-        // to the 6144-sample instantiation: there a launch costs more than the arithmetic saved.
-        // Peak-list capacities: local maxima of the score curve run at ~N/5.6 (>= N/5.0 observed); the capacities
-        // leave headroom within the LDS budget of the instantiation's occupancy; overflows move up the chain.
-        const int64_t chain_min = knobs.fast_chain_min > 0 ? knobs.fast_chain_min : 2048;
-        const bool large_batch = n_reads >= chain_min;
-        const int combo = fast_combo(p);
-        const bool approx = large_batch && !knobs.fast_exact_scores && !fast_combo_exact_only(combo);
-        const int nbt = combo >= 3 ? 2 : 1;
-        int capF = cap <= 4096 ? 4096 : (large_batch ? 5120 : 6144);
-        if (knobs.fast_main_cap == 5120 || knobs.fast_main_cap == 6144) capF = knobs.fast_main_cap;  // experiments
-        if (combo == 2) capF = large_batch ? 5120 : 6144;  // width 18: five workgroups per CU too (91 VGPRs)
-        if (combo >= 3) capF = 6144;  // width 30 / reach 17 (and the round-5 widths): 115 VGPRs, four waves per SIMD either way
-        // (LDS is allocated in 1280-byte granules: five workgroups per CU need <= 32 000 B each, four <= 40 960 B --
-        // hipOccupancyMaxActiveBlocksPerMultiprocessor does not know and reports five at 32 640 B)
-        // Large batches: the clip bounds of the MAIN kernel's reads are computed ahead of it by clip_bounds_kernel (one wave
-        // per read, wdx_clip.hip) and the main kernel starts at the clip (EXT instantiation).  Small batches (live ticks:
-        // every launch counts) keep the in-kernel radix selects.
-        const bool ext = large_batch || capF == 5120;
-        int capP = capF == 4096 ? 1152 : (capF == 5120 ? 980 : 1376);
-        // with the threshold filter of the appends (kPeakTauLo) a read lists ~340 peaks instead of ~830: 512 entries leave the
-        // 5120-sample main kernel at 26.8 KB of LDS -- six workgroups per CU (a longer list moves on to the list kernels).
-        // (the width-30 instantiations, NBT = 2, are bound by their registers at four: they keep the long lists, except
-        // the streaming form)
-        const bool filt = approx && !knobs.no_peak_filter;   // (the launches on approximate keys below)
-        if (ext && filt && nbt == 1 && capF <= 5120) capP = 512;
-        // the NBT = 2 widths' 6144-sample main kernel at FIVE workgroups per CU: 96 VGPRs (launch bound) and the filtered
-        // 512-entry list -- 31 000 B of LDS (five need <= 32 000); longer lists move on to the list kernel
-        // (not width 6: its reach-3 lists are the longest -- 512 entries overflow for most reads, 23.3 -> 22.8 M reads/s)
-        if (ext && filt && nbt == 2 && capF == 6144 && kWideWgPerCu == 5 && p.running_stat_width >= 12) capP = 512;
-        if (knobs.fast_peak_cap > 0) capP = knobs.fast_peak_cap;  // experiment knob (wdx_ctx_set_option)
-        const size_t flds = fast_lds_bytes(capF, capP, nbt);
-        unsigned *count = reinterpret_cast<unsigned *>(d_ws);  // [0] slow, [1] big0, [2] big1, [3] retry, [4] big2, [5] back
-        ClipRec *clip = reinterpret_cast<ClipRec *>(reinterpret_cast<unsigned char *>(d_ws) + 32);
-        int32_t *list = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(d_ws) + 32 + 16 * n_reads);
-        int32_t *big0 = list + n_reads, *big1 = big0 + n_reads, *retry = big1 + n_reads, *big2 = retry + n_reads;
-        WDX_HIP_TRY(hipMemsetAsync(count, 0, 32, stream));
-        const bool chain = !(d_prof && stop_phase > 0);         // (ablation timing: the main kernel alone)
-        const bool with_big0 = chain && capF == 5120;            // windows of 5121..6144 samples, peak-list overflows
-        // windows beyond 6144 samples, up to WDX_MAX_ADAPTER_SAMPLES: the streaming fast kernel (at 8 000 samples it is
-        // faster than the striding 8192-sample list kernel, which then only serves list overflows and exact-score retries)
-        // (odd widths are instantiated without the streaming form: their windows beyond 8192 samples take the exact kernel)
-        const bool has_stream = !(fast_combo_exact_only(combo) && (p.running_stat_width & 1));
-        const bool with_stream = chain && ext && capF >= 5120 && max_len > 6144 && has_stream;
-        const bool with_big1 = chain && capF >= 5120 && cap > 6144 && !with_stream;  // windows of 6145..8192 samples
-        A.exact_scores = approx ? 0 : 1;
-        A.peak_filter = knobs.no_peak_filter ? 0 : 1;   // (only the approximate-keys launches look at it)
-        unsigned *d_reasons = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(d_ws) + dbg_ws_offset(n_reads));
-        if (knobs.debug_occ) {   // (diagnostic: 16 counters at the end of this call's workspace, zeroed on its stream)
-            WDX_HIP_TRY(hipMemsetAsync(d_reasons, 0, 64, stream));
-            A.dbg_reasons = d_reasons;
-        }
-        FastArgs F{A, capF, capP, count, list, nullptr, nullptr, nullptr, nullptr, 0u, approx ? count + 3 : nullptr,
-                   approx ? retry : nullptr, nullptr};
-        if (with_big0) {
-            F.big_count = count + 1;
-            F.big_list = big0;
-        } else if (with_stream) {
-            F.big_count = count + 4;
-            F.big_list = big2;
-        } else if (with_big1) {
-            F.big_count = count + 2;
-            F.big_list = big1;
-        }
-        F.clip = ext ? clip : nullptr;
-        void (*kern_st)(FastArgs) = combo == 2 ? fingerprint_fast_stream_kernel<18, 1>
-                                    : (combo == 3 ? fingerprint_fast_stream_kernel<30, 2> : fingerprint_fast_stream_kernel<kFW, 1>);
-        void (*kern)(FastArgs) = nullptr;
-        // the SPLIT pair of the main launch (tile kernel + tail kernel) and of the 6144-sample list launch, where they exist
-        void (*kern_a)(FastArgs) = nullptr, (*kern_b)(FastArgs) = nullptr, (*kern_a1)(FastArgs) = nullptr;
-        void (*kern_l1)(FastArgs) = fingerprint_fast_list1_kernel<kNptLarge>;   // 6144 samples, one workgroup per entry
-        void (*kern_ls)(FastArgs) = fingerprint_fast_list_kernel<kNptHuge>;     // 8192 samples, striding
-        int slot = 0;
-        // (the NBT = 2 widths: one set of four kernels each)
-        auto wide_set = [&](auto fw_t) {
-            constexpr int FWx = decltype(fw_t)::value;
-            kern = ext ? fingerprint_fast_kernel<kNptLarge, false, FWx, 2, true> : fingerprint_fast_kernel<kNptLarge, false, FWx, 2, false>;
-            kern_l1 = fingerprint_fast_list1_kernel<kNptLarge, FWx, 2>;
-            kern_ls = fingerprint_fast_list_kernel<kNptHuge, FWx, 2>;
-            kern_st = fingerprint_fast_stream_kernel<FWx, 2>;
-            slot = 2;
-            if constexpr (FWx >= 12 && FWx % 6 == 0) {   // (the widths whose EXT main kernel runs the filtered 512-entry list)
-                kern_a = fingerprint_fast_kernel<kNptLarge, false, FWx, 2, true, true>;
-                kern_b = fingerprint_split_tail_kernel<FWx, 2>;
-            }
-        };
-        if (combo == 2) {
-            kern = capF == 5120 ? fingerprint_fast_kernel<kNptMid, false, 18, 1, true>
-                                : (ext ? fingerprint_fast_kernel<kNptLarge, false, 18, 1, true>
-                                       : fingerprint_fast_kernel<kNptLarge, false, 18, 1, false>);
-            kern_l1 = fingerprint_fast_list1_kernel<kNptLarge, 18, 1>;
-            kern_ls = fingerprint_fast_list_kernel<kNptHuge, 18, 1>;
-            slot = capF == 5120 ? 1 : 2;
-            if (capF == 5120) {
-                kern_a = fingerprint_fast_kernel<kNptMid, false, 18, 1, true, true>;
-                kern_b = fingerprint_split_tail_kernel<18, 1>;
-                kern_a1 = fingerprint_fast_list1_kernel<kNptLarge, 18, 1, true>;
-            }
-        } else if (combo == 3) {
-            wide_set(std::integral_constant<int, 30>{});
-        } else if (combo == 4) {
-            wide_set(std::integral_constant<int, 6>{});
-        } else if (combo == 5) {
-            wide_set(std::integral_constant<int, 24>{});
-        } else if (combo == 6) {
-            wide_set(std::integral_constant<int, 36>{});
-        } else if (combo == 7) {
-            wide_set(std::integral_constant<int, 12>{});
-        } else if (combo == 8) {
-            wide_set(std::integral_constant<int, 18>{});
-        } else if (combo >= 9) {
-            // the exact-scores-only widths: instantiated in wdx_fingerprint_w1.hip / _w2.hip
-            FastKernelSet ks{};
-            if (!exact_only_kernels_a(p.running_stat_width, ext, ks) && !exact_only_kernels_b(p.running_stat_width, ext, ks) &&
-                !exact_only_kernels_c(p.running_stat_width, ext, ks) && !exact_only_kernels_d(p.running_stat_width, ext, ks)) {
-                set_error("no fast kernels for running_stat_width %d", (int)p.running_stat_width);
-                return WDX_ERR_INVALID;
-            }
-            kern = ks.main;
-            kern_l1 = ks.l1;
-            kern_ls = ks.ls;
-            kern_st = ks.st;
-            slot = 2;
-        } else if (capF == 4096) {
-            kern = ext ? (d_prof ? fingerprint_fast_kernel<kNptSmall, true, kFW, 1, true> : fingerprint_fast_kernel<kNptSmall, false, kFW, 1, true>)
-                       : (d_prof ? fingerprint_fast_kernel<kNptSmall, true> : fingerprint_fast_kernel<kNptSmall, false>);
-        } else if (capF == 5120) {
-            kern = d_prof ? fingerprint_fast_kernel<kNptMid, true, kFW, 1, true> : fingerprint_fast_kernel<kNptMid, false, kFW, 1, true>;
-            slot = 1;
-            kern_a = fingerprint_fast_kernel<kNptMid, false, kFW, 1, true, true>;
-            kern_b = fingerprint_split_tail_kernel<kFW, 1>;
-            kern_a1 = fingerprint_fast_list1_kernel<kNptLarge, kFW, 1, true>;
-        } else {
-            kern = ext ? (d_prof ? fingerprint_fast_kernel<kNptLarge, true, kFW, 1, true> : fingerprint_fast_kernel<kNptLarge, false, kFW, 1, true>)
-                       : (d_prof ? fingerprint_fast_kernel<kNptLarge, true> : fingerprint_fast_kernel<kNptLarge, false>);
-            slot = 2;
-        }
-        static LdsAttr attr_fast[40][12];
-        if (int rc = attr_fast[combo - 1][(ext ? 6 : 0) + (d_prof ? 3 : 0) + slot].ensure(kern, flds)) return rc;
-        if (knobs.debug_occ) {
-            int nb = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, FB, flds);
-            fprintf(stderr, "[wdx] fast kernel capF=%d capP=%d lds=%zu B -> %d workgroups/CU%s\n", capF, capP, flds, nb,
-                    approx ? ", approximate score keys" : "");
-        }
-        // one workgroup per read (or list entry); grid.x * block.x must stay below 2^32: equal launch slices of at
-        // most 2^31 / FB workgroups
-        auto launch_sliced = [&](void (*k)(FastArgs), FastArgs &fa, int64_t n_wg, size_t lds_bytes, bool counted) {
-            const int64_t max_slice = launch_slice_limit((1ll << 31) / FB), n_slices = (n_wg + max_slice - 1) / max_slice;
-            const int64_t slice = (n_wg + n_slices - 1) / n_slices;
-            for (int64_t base = 0; base < n_wg; base += slice) {
-                const int64_t n = n_wg - base < slice ? n_wg - base : slice;
-                fa.a.block_base = base;
-                hipLaunchKernelGGL(k, dim3((unsigned)n), dim3(FB), lds_bytes, stream, fa);
-                if (counted && n_launches) ++*n_launches;
-            }
-        };
-        if (ext) {
-            // A1 for the main kernel's reads (windows of 256 .. capF samples; longer ones are flagged CLIP_NONE and the
-            // main kernel hands them to the lists before it would look at their record)
-            if (main_ev && main_ev->c_first) (void)hipEventRecord(main_ev->c_first, stream);
-            if (int rc = launch_clip_bounds(A, clip, capF, stream)) return rc;
-            if (F.big_list) {   // the windows beyond capF go on the main kernel's hand-over list here (one atomic per 64 reads)
-                if (int rc = launch_route_long_windows(A, capF, F.big_count, F.big_list, stream)) return rc;
-                F.routed = 1;
-            }
-            if (main_ev && main_ev->c_first) {
-                (void)hipEventRecord(main_ev->c_second, stream);
-                main_ev->c_recorded = true;
-            }
-        }
-        // The SPLIT form of the main kernel (large batches on approximate keys with the filtered 512-entry list -- the RNA004
-        // triple, width 18, and the NBT = 2 widths from 12 up): the workgroup-per-read kernel ends after the tile pass and exports
-        // the <= 256 peaks that can matter, one WAVE per read does the rest (fingerprint_split_tail_kernel) -- launch pairs over
-        // slices of kSplitSlice reads, whose lists live in the workspace behind the read lists.  Not for the diagnostic builds
-        // (the one-piece kernel serves those).
-        // (not the refinement branch: measured 2.36 against 2.15 ms per 32 768 tRNA-like reads with the one-piece kernel)
-        // (stop_phase == -2: the diagnostic build of the RNA004 pair, wdx_fingerprint_profile_dev's fast_path = 2)
-        const bool prof_split = d_prof && stop_phase == -2 && combo == 1 && capF == 5120;
-        if (prof_split) kern_a = fingerprint_fast_kernel<kNptMid, true, kFW, 1, true, true>;
-        const bool split = kern_a && ext && approx && filt && capP == 512 && chain && (!d_prof || prof_split) && !rf && !knobs.no_split;
-        if (main_ev && main_ev->first) (void)hipEventRecord(main_ev->first, stream);
-        if (split) {
-            static LdsAttr attr_split[40], attr_split_prof;
-            if (int rc = (prof_split ? attr_split_prof : attr_split[combo - 1]).ensure(kern_a, flds)) return rc;
-            F.split_ws = reinterpret_cast<unsigned char *>(d_ws) + split_ws_offset(n_reads);
-            const int64_t slice = launch_slice_limit(kSplitSlice);
-            for (int64_t base = 0; base < n_reads; base += slice) {
-                const int64_t m = std::min<int64_t>(slice, n_reads - base);
-                F.split_base = base;
-                F.split_n = m;
-                F.a.block_base = base;
-                hipLaunchKernelGGL(kern_a, dim3((unsigned)m), dim3(FB), flds, stream, F);
-                if (n_launches) ++*n_launches;
-                std::pair<hipEvent_t, hipEvent_t> tp{nullptr, nullptr};
-                if (main_ev && main_ev->first && main_ev->take) tp = main_ev->take(main_ev->take_arg);
-                if (tp.first) (void)hipEventRecord(tp.first, stream);
-                F.a.block_base = 0;
-                hipLaunchKernelGGL(kern_b, dim3((unsigned)((m + kSplitWaves - 1) / kSplitWaves)), dim3(kSplitWaves * 64), 0, stream, F);
-                if (tp.first) {
-                    (void)hipEventRecord(tp.second, stream);
-                    main_ev->tail.push_back(tp);
-                }
-            }
-            F.a.block_base = 0;
-        } else {
-            launch_sliced(kern, F, n_reads, flds, true);
-        }
-        if (main_ev && main_ev->first) {
-            (void)hipEventRecord(main_ev->second, stream);
-            main_ev->recorded = true;
-        }
-        // the list kernels
-        const int64_t grid = n_reads < 1024 ? n_reads : 1024;  // striding kernels: every CU busy, nothing more
-        const int capF1 = 6144, capP1 = 1376, capF2 = 8192, capP2 = 1856;
-        const size_t flds1 = fast_lds_bytes(capF1, capP1, nbt), flds2 = fast_lds_bytes(capF2, capP2, nbt);
-        // the same kernels behind filtered appends (the approximate-keys launches; the exact-scores retry keeps the long
-        // lists): 512 entries -> five workgroups per CU at 6144 samples, four at 8192
-        // (the striding 8192-sample kernel is NOT an EXT instantiation: its in-kernel medians put their 2112-word histogram
-        // where the peak list will be, so its list region must hold 8448 bytes -- 768 entries, not 512)
-        const int capP1f = filt && nbt == 1 ? 512 : capP1, capP2f = filt && nbt == 1 ? 768 : capP2;
-        const size_t flds1f = fast_lds_bytes(capF1, capP1f, nbt), flds2f = fast_lds_bytes(capF2, capP2f, nbt);
-        static LdsAttr attr_l1[40], attr_huge[40];
-        if (with_big0 || (approx && chain))
-            if (int rc = attr_l1[combo - 1].ensure(kern_l1, flds1)) return rc;
-        if (with_big0 || with_big1 || with_stream || (approx && chain))
-            if (int rc = attr_huge[combo - 1].ensure(kern_ls, flds2)) return rc;
-        if (with_big0) {
-            // 11 % of RNA004 adapter windows are longer than 5120 samples: a grid for a quarter of the batch, one
-            // workgroup per list entry, and the striding 8192-sample kernel for whatever lies beyond it
-            const int64_t g1 = std::min<int64_t>(n_reads, std::max<int64_t>(1024, n_reads / 4));
-            FastArgs F1{A, capF1, capP1f, count, list, with_stream ? count + 4 : (with_big1 ? count + 2 : nullptr),
-                        with_stream ? big2 : (with_big1 ? big1 : nullptr), count + 1, big0, 0u, F.retry_count, F.retry_list, clip};
-            if (int rc = launch_clip_bounds_list(A, clip, count + 1, big0, g1, stream)) return rc;
-            if (split && kern_a1 && capP1f == 512) {
-                // the same pair over the list's entries (slot = workgroup of the slice; most of the grid lies past the list's end
-                // and leaves at once, in both kernels)
-                static LdsAttr attr_split1[40];
-                if (int rc = attr_split1[combo - 1].ensure(kern_a1, flds1f)) return rc;
-                F1.split_ws = F.split_ws;
-                const int64_t slice = launch_slice_limit(kSplitSlice);
-                for (int64_t base = 0; base < g1; base += slice) {
-                    const int64_t m = std::min<int64_t>(slice, g1 - base);
-                    F1.split_base = base;
-                    F1.split_n = m;
-                    F1.a.block_base = base;
-                    hipLaunchKernelGGL(kern_a1, dim3((unsigned)m), dim3(FB), flds1f, stream, F1);
-                    F1.a.block_base = 0;
-                    hipLaunchKernelGGL(kern_b, dim3((unsigned)((m + kSplitWaves - 1) / kSplitWaves)), dim3(kSplitWaves * 64), 0, stream, F1);
-                }
-                F1.a.block_base = 0;
-            } else {
-                launch_sliced(kern_l1, F1, g1, flds1f, false);
-            }
-            if (g1 < n_reads) {
-                FastArgs F1b{A, capF2, capP2f, count, list, with_stream ? count + 4 : nullptr, with_stream ? big2 : nullptr,
-                             count + 1, big0, (unsigned)g1, F.retry_count, F.retry_list, nullptr};
-                hipLaunchKernelGGL(kern_ls, dim3((unsigned)grid), dim3(FB), flds2f,
-                                   stream, F1b);
-            }
-        }
-        if (with_big1) {
-            FastArgs F2{A, capF2, capP2f, count, list, nullptr, nullptr, count + 2, big1, 0u, F.retry_count, F.retry_list, nullptr};
-            hipLaunchKernelGGL(kern_ls, dim3((unsigned)grid), dim3(FB), flds2f, stream,
-                               F2);
-        }
-        if (with_stream) {
-            // windows of 6145 .. 16384 samples (RNA002: max_obs_trace + 2 * padding = 15 200): their clip bounds by one
-            // workgroup per list entry (samples in LDS), then the streaming form of the fast body -- its LDS is the peak
-            // list plus two tile buffers, whatever the window length: four workgroups per CU up to 12 288 samples, three
-            // up to 16 384.  One workgroup per entry; the list's length is only known on the device.  With windows beyond
-            // 8192 samples in the batch (RNA002-length reads: every read is on this list) the grids cover the batch; up to
-            // 8192 the long windows are a tail of the batch (687 of 10 M synthetic RNA004 reads) and, for batches of more
-            // than 2 M reads, the grids cover a sixteenth of it -- a workgroup past the list's end leaves at once, but 10 M of
-            // them cost a millisecond per launch -- with the striding 8192-sample kernel behind them for whatever lies
-            // beyond.  Doubts and refusals go to the exact kernel.
-            const int scap = max_len <= 8192 ? 8192 : (max_len <= 12288 ? 12288 : 16384);
-            const int capPs = filt ? (scap == 8192 ? 1024 : (scap == 12288 ? 1280 : 1536))   // (the list from kPeakTauLo up)
-                                   : (scap == 8192 ? 1700 : (scap == 12288 ? 2520 : 3400));
-            const size_t lds_cb = clip_block_lds_bytes(scap), lds_st = fast_stream_lds_bytes(capPs, nbt);
-            static LdsAttr attr_cb, attr_st[40];
-            if (int rc = attr_cb.ensure(clip_bounds_block_kernel, lds_cb)) return rc;
-            if (int rc = attr_st[combo - 1].ensure(kern_st, lds_st)) return rc;
-            // (WDX_OPT_MAX_LAUNCH_SLICE, the tests' switch for the multi-launch paths, also selects the bounded grids)
-            const int64_t g5 = (scap == 8192 && (n_reads > (1ll << 21) || knobs.max_launch_slice > 0))
-                                   ? std::max<int64_t>(1, n_reads / 16) : n_reads;
-            const int64_t max_slice = launch_slice_limit(1ll << 22);
-            // the one-wave clip kernel first (samples in registers, no barriers: twice the block kernel's rate per sample at
-            // two workgroups of four reads per CU) for the windows its register file holds -- 8192 samples at 128 per lane,
-            // 13 312 at 208; the workgroup kernel then finds a record for those and serves the rest: longer windows, and
-            // the ones the wave form may not decide (negative samples it cannot clamp away)
-            if (!knobs.no_wave_clip_long)
-                if (int rc = launch_clip_bounds_list(A, clip, count + 4, big2, g5, stream, scap == 8192 ? 8192 : kClipWaveLongCap, true))
-                    return rc;
-            for (int64_t base = 0; base < g5; base += max_slice) {
-                ClipBlockArgs CB{A, clip, count + 4, big2, scap};
-                CB.a.block_base = base;
-                hipLaunchKernelGGL(clip_bounds_block_kernel, dim3((unsigned)std::min<int64_t>(max_slice, g5 - base)), dim3(FB),
-                                   lds_cb, stream, CB);
-            }
-            FastArgs F5{A, 16384, capPs, count, list, nullptr, nullptr, count + 4, big2, 0u, nullptr, nullptr, clip};
-            // batches of long windows (beyond 8192 samples: the grids cover the batch anyway): a read with a decision inside
-            // the error band, or whose cut does not clear the append filter's threshold, is redone by a second launch of the
-            // same kernel on exact scores with the unfiltered list capacity -- instead of the exact general kernel, which
-            // serves such a window at a twentieth of the rate.  (The 8192-sample list's slots are free: big1 is not in use
-            // when the streaming kernel is.)
-            const bool st_retry = approx && scap > 8192;
-            if (st_retry) {
-                F5.retry_count = count + 2;
-                F5.retry_list = big1;
-            }
-            launch_sliced(kern_st, F5, g5, lds_st, false);
-            if (st_retry) {
-                const int capPx = scap == 12288 ? 2520 : 3400;
-                const size_t lds_x = fast_stream_lds_bytes(capPx, nbt);
-                if (int rc = attr_st[combo - 1].ensure(kern_st, lds_x)) return rc;
-                FastArgs F6{A, 16384, capPx, count, list, nullptr, nullptr, count + 2, big1, 0u, nullptr, nullptr, clip};
-                F6.a.exact_scores = 1;
-                launch_sliced(kern_st, F6, n_reads, lds_x, false);
-            }
-            if (g5 < n_reads) {
-                FastArgs F5b{A, capF2, capP2f, count, list, nullptr, nullptr, count + 4, big2, (unsigned)g5, F.retry_count,
-                             F.retry_list, nullptr};
-                hipLaunchKernelGGL(kern_ls, dim3((unsigned)grid), dim3(FB), flds2f, stream, F5b);
-            }
-        }
-        if (approx && chain) {
-            // about 2 reads in 1000: a grid for 1/64 of the batch on the 6144-sample instantiation with exact scores
-            // (a window beyond 6144 samples moves on to the slow path), the striding kernel beyond
-            const int64_t g3 = std::min<int64_t>(n_reads, std::max<int64_t>(1024, n_reads / 64));
-            FastArgs F3{A, capF1, capP1, count, list, nullptr, nullptr, count + 3, retry, 0u, nullptr, nullptr, clip};
-            F3.a.exact_scores = 1;
-            launch_sliced(kern_l1, F3, g3, flds1, false);
-            if (g3 < n_reads) {
-                FastArgs F3b{F3.a, capF2, capP2, count, list, nullptr, nullptr, count + 3, retry, (unsigned)g3, nullptr,
-                             nullptr, nullptr};
-                hipLaunchKernelGGL(kern_ls, dim3((unsigned)grid), dim3(FB), flds2,
-                                   stream, F3b);
-            }
-        }
-        WDX_HIP_TRY(hipGetLastError());
-        if (!chain) return WDX_SUCCESS;  // (ablation timing of the main kernel: the lists are left unprocessed)
-        // the exact kernels take the clip bounds of a read that has a CLIP_OK record (every read of the batch has a record by
-        // now: the main clip kernel writes one per read, the list forms fill in the longer windows) instead of redoing the
-        // two workgroup-wide medians
-        if (ext && !knobs.no_clip_reuse) A.clip = clip;
-        if (rf) {
-            // refinement branch: the exact kernel segments the adapters of the slow list's reads and leaves them, like the
-            // fast kernels theirs, to the refinement kernels (reads it cannot hand over it refines in place); barcode
-            // tails beyond the tail kernel's capacity come back on a list of their own for the exact kernel's full form
-            int32_t *back = big2 + n_reads;
-            A.refine_record = 1;
-            if (int rc = small ? launch_fp_list<512>(A, lds, count, list, stream)
-                               : launch_fp_list<1024>(A, lds, count, list, stream))
-                return rc;
-            A.refine_record = 0;
-            if (int rc = launch_refine_tail(A, count + 5, back, stream)) return rc;
-            // (a grid-stride kernel: one workgroup per CU serves this list, which is empty unless barcodes are very long --
-            // 2048 workgroups of ~100 KB that only find it empty cost 70 us)
-            if (int rc = small ? launch_fp_list<512>(A, lds, count + 5, back, stream, 256)
-                               : launch_fp_list<1024>(A, lds, count + 5, back, stream, 256))
-                return rc;
-        } else if (int rc = small ? launch_fp_list<512>(A, lds, count, list, stream)
-                                  : launch_fp_list<1024>(A, lds, count, list, stream))
-            return rc;
-        if (with_huge)
-            if (int rc = launch_fp_big(A, cap, count, list, stream)) return rc;
-        if (knobs.debug_occ) {  // (diagnostic: synchronises)
-            unsigned c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            WDX_HIP_TRY(hipMemcpyAsync(c, count, 32, hipMemcpyDeviceToHost, stream));
-            WDX_HIP_TRY(hipStreamSynchronize(stream));
-            // (counter 2 is the 8192-sample list when the streaming kernel is not in the chain, else the streaming kernel's
-            // own exact-scores retry list)
-            fprintf(stderr, "[wdx] of %lld reads: %u beyond the main instantiation, %u %s, %u to the "
-                            "streaming kernel, %u redone with exact scores, %u on the exact general kernel\n", (long long)n_reads,
-                    c[1], c[2], with_stream ? "redone by the streaming kernel on exact scores" : "to the 8192-sample list kernel",
-                    c[4], c[3], c[0]);
-            {
-                unsigned h[16];
-                WDX_HIP_TRY(hipMemcpyAsync(h, d_reasons, 64, hipMemcpyDeviceToHost, stream));
-                WDX_HIP_TRY(hipStreamSynchronize(stream));
-                fprintf(stderr, "[wdx] handed to the exact kernel by the fast kernels, by reason (0 parameter gate / window, 1 NaN or negative, "
-                                "2 sums not provably exact, 3 plateau or peak-list capacity, 4 neighbourhood, 5 kept-list capacity, 6 tie at the "
-                                "top-E cut, 7 doubt without a retry list, 8 fewer peaks than events with accept_less_cpts):");
-                for (int i = 0; i < 10; ++i) fprintf(stderr, " %u", h[i]);
-                fprintf(stderr, "\n");
-            }
-            if (rf)
-                fprintf(stderr, "[wdx] refinement: %u reads back from the tail kernel to the exact kernel (%u for a run of equal scores across a "
-                                "tile's end, %u beyond the peak list)\n", c[5], c[6], c[7]);
-            if (ext) {
-                std::vector<ClipRec> h((size_t)n_reads);
-                WDX_HIP_TRY(hipMemcpy(h.data(), clip, sizeof(ClipRec) * (size_t)n_reads, hipMemcpyDeviceToHost));
-                long long f[4] = {0, 0, 0, 0};
-                for (const ClipRec &cr : h) ++f[cr.flag & 3];
-                fprintf(stderr, "[wdx] clip_bounds_kernel flags: %lld not taken, %lld ok, %lld NaN / negative, %lld sums not "
-                                "provably exact\n", f[0], f[1], f[2], f[3]);
-            }
-        }
-        return WDX_SUCCESS;
-    }
-    // The exact kernel for the whole batch (a window width or suppression reach without a fast instantiation, a signal
-    // normalisation, WDX_OPT_EXACT_PATH): large batches still get their clip bounds from the one-wave kernel first (windows
-    // up to 13 312 samples; 4.5 ms per million reads against the exact kernel's ~100 for its two workgroup-wide medians)
-    if (d_ws && !d_prof && !knobs.no_clip_reuse && n_reads >= (knobs.fast_chain_min > 0 ? knobs.fast_chain_min : 2048)) {
-        ClipRec *clip = reinterpret_cast<ClipRec *>(reinterpret_cast<unsigned char *>(d_ws) + 32);
-        const int ccap = max_len <= 4096 ? 4096 : (max_len <= 5120 ? 5120 : (max_len <= 6144 ? 6144 : (max_len <= 8192 ? 8192 : kClipWaveLongCap)));
-        if (int rc = launch_clip_bounds(A, clip, ccap, stream)) return rc;
-        A.clip = clip;
-    }
-    if (int rc = small ? launch_fp_chunks<512, false>(A, lds, stream, n_launches)
-                       : launch_fp_chunks<1024, false>(A, lds, stream, n_launches))
-        return rc;
-    if (with_huge) return launch_fp_big(A, cap, nullptr, nullptr, stream);
-    return WDX_SUCCESS;
-}
+#include "wdx_fingerprint_launch.inc"
 #endif  // WDX_DEV_KERNELS_ONLY
 
 }  // namespace wdx

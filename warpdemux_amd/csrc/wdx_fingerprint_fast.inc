@@ -2706,14 +2706,18 @@ __global__ __launch_bounds__(FB, 4 * FB / 256) void fingerprint_fast_stream_kern
     fast_body<kNptStream, false, FW, NBT, true, true>(F, (int64_t)F.in_list[k]);
 }
 
-// The four kernels of one NBT = 2 width (main, 6144-sample list, striding 8192-sample list, streaming), as launch_fingerprint
-// uses them.  The widths on exact scores only are instantiated in translation units of their own (wdx_fingerprint_w1.hip,
+// The kernels of one (width, NBT) combination (main, 6144-sample list, striding 8192-sample list, streaming, and the split
+// forms where they exist), as the launch chain uses them (wdx_fingerprint_launch.inc).  The widths on exact scores only are
+// instantiated in translation units of their own (wdx_fingerprint_w1.hip,
 // _w2.hip: the build compiles them side by side -- one unit with every width took seven minutes).
 struct FastKernelSet {
     void (*main)(FastArgs);
     void (*l1)(FastArgs);
     void (*ls)(FastArgs);
     void (*st)(FastArgs);
+    void (*tile)(FastArgs) = nullptr;   // the split pair of the main launch: tile kernel ...
+    void (*tail)(FastArgs) = nullptr;   // ... and tail kernel (one wave per read)
+    void (*l1s)(FastArgs) = nullptr;    // the tile kernel of the 6144-sample list launch (its tail kernel is `tail`)
 };
 // (exact-scores-only widths: no retry launch and capF = 6144, so the one-workgroup-per-entry list kernel is never launched
 // for them: l1 stays null; odd widths do without the streaming form too -- windows beyond 8192 samples take the exact kernel)

@@ -88,7 +88,7 @@ __device__ __forceinline__ int rdiv_half_even(unsigned n, unsigned den, unsigned
 }
 
 // Clip bounds of one read, computed ahead of the fast kernels' launch chain by clip_bounds_kernel (one wave per read,
-// wdx_fingerprint_clip.inc).  flag: CLIP_NONE = not computed (failed detection, window outside the kernel's range),
+// wdx_clip.hip).  flag: CLIP_NONE = not computed (failed detection, window outside the kernel's range),
 // CLIP_OK = bounds valid and every partial sum of the clipped samples exactly representable, CLIP_NAN_NEG = a
 // negative sample / -0.0 / infinity / NaN in the window, CLIP_INEXACT = the exactness gate fails.
 struct alignas(16) ClipRec {
