@@ -316,6 +316,52 @@ typedef struct wdx_minibatch_out {
 int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, const wdx_seg_params *p, int64_t n_refs,
                         uint32_t want);
 int wdx_demux_wait_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out);
+/* ---- raw int16 ADC minibatches, calibrated on the device -------------------------------------------------------
+ * The reference's reader makes its float32 rows from int16 ADC samples (file_proc.py:258, read_record.signal_pa); a
+ * caller that hands over the int16 samples and the two calibration numbers of every read moves 2 bytes per sample
+ * over the bus instead of 4.  THE CONTRACT: read r with row_len[r] samples adc, offset[r], scale[r] stands for the
+ * float32 row
+ *     pa[i] = scale[r] * ((float)adc[i] + offset[r])    i < row_len[r]     float32 add, THEN float32 multiply: two
+ *                                                                          roundings, never one fused operation
+ *     pa[i] = NaN                                       row_len[r] <= i < stride
+ * (the calibrated samples, then the NaN tail of file_proc.py:255-260; NumPy form: warpdemux_amd.sig_proc.calibrate_adc),
+ * and every *_adc entry point returns, bit for bit, what its float32 counterpart returns on those rows -- status,
+ * fingerprints, dwell times, statistics, distances, call, prob / pred / conf, failed reads and windows that run into
+ * the NaN tail included.  A caller whose reader calibrates by another formula must not use this path.
+ * Two copy kernels do the work ahead of the unchanged fingerprint chain (wdx_adc.hip): pack_windows_adc_kernel reads
+ * the adapter windows of a page-locked minibatch over the bus, decode_adc_kernel decodes rows that arrived by a DMA
+ * copy (pageable minibatches, rows the caller packed). */
+typedef struct wdx_minibatch_adc_in {
+    const int16_t *adc;        /* (n_reads, stride) int16 rows, or the packed rows when row_off != NULL                */
+    int64_t n_reads, stride;   /* stride = samples of the float32 row (NaN tail included); ignored for packed rows     */
+    const int32_t *row_len;    /* REQUIRED: ADC samples of read r, 0 .. stride (there is no NaN tail to find the end by) */
+    const float *offset, *scale; /* REQUIRED: float32[n_reads] calibration of every read                               */
+    const int64_t *row_off;    /* packed: int64[n_reads + 1], multiples of 8, row r holds its row_len[r] samples at
+                                  adc[row_off[r] ..); a_start / a_end are relative to the row; NULL = minibatch layout */
+    const int32_t *row_win;    /* packed only, nullable: samples of the float32 row r stands for, row_win[r] - row_len[r]
+                                  of them the NaN tail (a worker that copies a window which runs past the read's end);
+                                  NULL = row_len                                                                        */
+    const int32_t *a_start, *a_end;
+    const uint8_t *ok;         /* nullable                                                                              */
+} wdx_minibatch_adc_in;
+/* wdx_demux_submit_ex for int16 rows (pair it with wdx_demux_wait_ex): the same three ways in -- 2-D copy of the column
+ * range, window pack over the bus for a page-locked minibatch, rows the caller packed.  WDX_ERR_INVALID: row_len /
+ * offset / scale NULL, row_len[r] outside 0 .. stride (packed: beyond the row's slice), row_off not ascending in
+ * multiples of 8. */
+int wdx_demux_submit_adc(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_adc_in *in, const wdx_seg_params *p, int64_t n_refs,
+                         uint32_t want);
+/* Blocking forms on the context's own stream: wdx_fingerprint_batch / wdx_demux_batch for int16 rows (outputs as there). */
+int wdx_fingerprint_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, const wdx_seg_params *p, double *fpt,
+                              int64_t *dwell, double *stats, int32_t *status);
+int wdx_demux_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, const wdx_seg_params *p, int64_t n_refs, double *fpt,
+                        float *dist, int32_t *call, int32_t *status);
+/* The decode alone, on DEVICE buffers: d_out (n_reads, stride) float32 = the rows of the contract above.  d_adc:
+ * (n_reads, stride) int16, or packed rows at d_row_off int64[n_reads] (multiples of 8; NULL = r * stride); d_row_len
+ * int32[n_reads] (clamped to 0 .. stride); d_offset / d_scale float32[n_reads].  Enqueued on `stream`; no
+ * synchronisation. */
+int wdx_calibrate_adc_dev(wdx_ctx *ctx, const int16_t *d_adc, const int64_t *d_row_off, const int32_t *d_row_len,
+                          int64_t stride, int64_t n_reads, const float *d_offset, const float *d_scale, float *d_out,
+                          void *stream);
 /* Page-locked host memory for minibatch buffers the caller fills (what file_proc.py:244-260 allocates with
  * np.full): the GPU reads it directly.  Needs no context; free with wdx_host_free. */
 int wdx_host_alloc(size_t bytes, void **out);
@@ -355,6 +401,12 @@ int wdx_host_unregister(void *p);
  *                                        row are copied into a free slot (packed rows), the worker sleeps on the slot
  *                                        (futex) until the results are there.  WDX_ERR_NO_DEVICE when the feeder has
  *                                        stopped or died (a dead feeder is noticed even while it is an unreaped zombie)
+ *        wdx_feeder_run_adc(ring, job)   the same for a ring whose slots hold int16 ADC samples (geometry.sample_format =
+ *                                        WDX_FEEDER_SAMPLES_INT16): the worker copies the int16 windows and the reads'
+ *                                        offset / scale, the server submits through wdx_demux_submit_adc -- half the bytes
+ *                                        in the worker's memcpy, in the ring and over the bus; results bit-identical to
+ *                                        wdx_feeder_run on the calibrated rows.  A float32 job on an int16 ring, and the
+ *                                        reverse, is WDX_ERR_INVALID
  *        wdx_feeder_demux(ring, ...)     wdx_demux_batch's arguments through wdx_feeder_run (status, call, dist)
  *        wdx_feeder_predict(ring, X, ..) DTW_SVM.predict on (n, n_events) float64 fingerprints the worker holds
  *        wdx_feeder_stop(ring)           ends wdx_feeder_serve: minibatches in flight are finished and handed over, READY
@@ -363,11 +415,13 @@ int wdx_host_unregister(void *p);
  *      A worker that dies while it holds a slot does not leak it: the slot's owner pid is part of its state word, and the
  *      serve loop (and any claimant that finds the ring full) gives slots of dead owners back to the ring. */
 #define WDX_FEEDER_MAX_RING_SLOTS 32
+#define WDX_FEEDER_SAMPLES_FLOAT32 0 /* wdx_feeder_run / wdx_feeder_demux                                    */
+#define WDX_FEEDER_SAMPLES_INT16 1   /* wdx_feeder_run_adc: 2 bytes per sample + offset / scale per read     */
 typedef struct wdx_feeder_geometry {
     int32_t n_slots;
     int32_t n_events;    /* K of fpt / dwell (0: no room for WDX_WANT_FPT / _DWELL / _STATS)      */
     int32_t n_classes;   /* k of prob (0: no room for WDX_WANT_SVM / wdx_feeder_predict), <= 16  */
-    int32_t pad_;
+    int32_t sample_format; /* WDX_FEEDER_SAMPLES_*: what a slot's sample region holds (0 = float32)  */
     int64_t max_reads, max_stride, n_refs;
 } wdx_feeder_geometry;
 typedef struct wdx_feeder_job {
@@ -386,10 +440,29 @@ typedef struct wdx_feeder_job {
     int32_t *pred;
     double *conf;
 } wdx_feeder_job;
+/* wdx_feeder_job for int16 rows: the minibatch as wdx_minibatch_adc_in's minibatch layout describes it */
+typedef struct wdx_feeder_job_adc {
+    const int16_t *adc;        /* (n_reads, stride) int16 rows                                                   */
+    int64_t n_reads, stride;
+    const int32_t *row_len;    /* ADC samples of read r, 0 .. stride                                             */
+    const float *offset, *scale;
+    const int32_t *a_start, *a_end;
+    const uint8_t *ok;         /* nullable                                                                       */
+    uint32_t want, pad_;
+    int32_t *status, *call;    /* outputs as in wdx_feeder_job                                                   */
+    float *dist;
+    double *fpt;
+    int64_t *dwell;
+    double *stats;
+    double *prob;
+    int32_t *pred;
+    double *conf;
+} wdx_feeder_job_adc;
 size_t wdx_feeder_ring_bytes(const wdx_feeder_geometry *g);
 int wdx_feeder_ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p);
 int wdx_feeder_serve(wdx_ctx *ctx, void *ring);
 int wdx_feeder_run(void *ring, const wdx_feeder_job *job);
+int wdx_feeder_run_adc(void *ring, const wdx_feeder_job_adc *job);
 int wdx_feeder_demux(void *ring, const float *sig, int64_t n_reads, int64_t stride, const int32_t *a_start,
                      const int32_t *a_end, const uint8_t *ok, int64_t n_refs, float *dist, int32_t *call, int32_t *status);
 int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int32_t *pred, double *conf);

@@ -14,6 +14,10 @@ modes   sync   sig_proc.demux_batch on a pageable minibatch (what an unmodified 
                so many small contexts take turns while one context's streams overlap
 --jitter N     adapter_start ~ U{100 .. 100 + N} per read: rows carry whole reads (page-locked minibatches then go through
                the packed staging, only the windows cross the bus)
+--adc          the same modes fed with int16 ADC rows (the minibatch quantised to scale ~0.1755, per-read offset): 2 bytes
+               per sample in the worker's fill, in the feeder's ring and over the bus, calibrated on the device
+               (sig_proc.demux_batch_adc / MinibatchPipeline.submit_adc / Feeder(adc=True)); the oracle check then runs on
+               sig_proc.calibrate_adc of those rows, so the float32 and the int16 rate come from one tool
 --refill       every iteration first copies the minibatch from a pageable array into the buffer it submits (the
                worker's own fill, which the reference does into its pageable array too)
 
@@ -33,6 +37,19 @@ sys.path.insert(0, ROOT)
 N_READS, STRIDE, K, N_REFS, WINDOW, PENALTY = 1000, 10000, 110, 10, 15, 0.1
 
 
+def quantise(mb, wid):
+    """--adc: (adc int16, row_len, offset, scale) of a generated minibatch -- what a pod5 file holds of such reads"""
+    import numpy as np
+
+    n = mb.shape[0]
+    rng = np.random.default_rng(1000 + wid)
+    scale = (0.1755 * (1.0 + 0.02 * rng.uniform(-1, 1, n))).astype(np.float32)
+    offset = (-240.0 + rng.uniform(-20, 20, n)).astype(np.float32)
+    row_len = np.isfinite(mb).sum(axis=1).astype(np.int32)
+    q = np.rint(np.nan_to_num(mb.astype(np.float64)) / scale[:, None].astype(np.float64) - offset[:, None].astype(np.float64))
+    return np.clip(q, -32768, 32767).astype(np.int16), row_len, offset, scale
+
+
 def worker(wid, args, barrier, q):
     import numpy as np
 
@@ -44,6 +61,12 @@ def worker(wid, args, barrier, q):
         mb, a_s, a_e, _ = synth.generate_minibatch(spec, 1000 * wid, N_READS, STRIDE, start_jitter=args.jitter)
         refs = np.random.default_rng(0).normal(size=(N_REFS, K))
         params = sig_proc.SegParams(barcode_num_events=K)
+        cal = ()
+        if args.adc:      # from here on `mb` is the int16 minibatch; `rows` = the float32 rows it stands for (oracle check)
+            mb, *cal = quantise(mb, wid)
+            rows = sig_proc.calibrate_adc(mb, *cal)
+        else:
+            rows = mb
         if args.mode == "sync":
             sig_proc.set_references(refs, WINDOW, PENALTY)
             src = mb.copy() if args.refill else None
@@ -51,6 +74,8 @@ def worker(wid, args, barrier, q):
             def step():
                 if src is not None:
                     np.copyto(mb, src)
+                if args.adc:
+                    return sig_proc.demux_batch_adc(mb, *cal, a_s, a_e, params, want_dist=True)
                 return sig_proc.demux_batch(mb, a_s, a_e, params, want_dist=True)
 
             for _ in range(3):
@@ -64,24 +89,25 @@ def worker(wid, args, barrier, q):
             dt = time.perf_counter() - t0
         else:
             pipe = pipeline.MinibatchPipeline(refs, WINDOW, PENALTY, params)
-            bufs = [pipeline.pinned_empty((N_READS, STRIDE), np.float32) for _ in range(2)]
+            bufs = [pipeline.pinned_empty((N_READS, STRIDE), mb.dtype) for _ in range(2)]
+            submit = (lambda s_: pipe.submit_adc(s_, bufs[s_], *cal, a_s, a_e)) if args.adc else (lambda s_: pipe.submit(s_, bufs[s_], a_s, a_e))
             for b in bufs:
                 np.copyto(b, mb)
             for _ in range(2):
                 for s in (0, 1):
-                    pipe.submit(s, bufs[s], a_s, a_e)
+                    submit(s)
                 for s in (0, 1):
                     res = pipe.wait(s)
             barrier.wait()
             t0 = time.perf_counter()
             n = 0
-            pipe.submit(0, bufs[0], a_s, a_e)
+            submit(0)
             k = 1
             while time.perf_counter() - t0 < args.seconds:
                 s = k & 1
                 if args.refill:
                     np.copyto(bufs[s], mb)       # the worker's fill of the next minibatch, overlapping the one in flight
-                pipe.submit(s, bufs[s], a_s, a_e)
+                submit(s)
                 res = pipe.wait(s ^ 1)
                 n += 1
                 k += 1
@@ -89,7 +115,7 @@ def worker(wid, args, barrier, q):
             n += 1
             dt = time.perf_counter() - t0
             pipe.close()
-        fpt, dwell, stats, status = orc.fingerprint_batch(mb, a_s, a_e, orc.SegParams(barcode_num_events=K))
+        fpt, dwell, stats, status = orc.fingerprint_batch(rows, a_s, a_e, orc.SegParams(barcode_num_events=K))
         ok = status == 0
         D = orc.dtw_matrix(fpt[ok], refs, WINDOW, PENALTY)
         parity = bool(np.array_equal(res.status, status) and np.array_equal(res.dist[ok].view(np.uint32), D.view(np.uint32))
@@ -128,11 +154,11 @@ def feeder_mode(args):
                         pwr_dist=int(g["pwr_dist"]), block_size=int(g["block_size"]))
         KF = 25
         params = sig_proc.SegParams(barcode_num_events=KF)
-        feeder = Feeder(model=model, params=params, max_reads=N_READS, stride=STRIDE, n_slots=args.slots)
+        feeder = Feeder(model=model, params=params, max_reads=N_READS, stride=STRIDE, n_slots=args.slots, adc=args.adc)
     else:
         refs = np.random.default_rng(0).normal(size=(N_REFS, K))
         params = sig_proc.SegParams(barcode_num_events=K)
-        feeder = Feeder(refs, WINDOW, PENALTY, params, max_reads=N_READS, stride=STRIDE, n_slots=args.slots)
+        feeder = Feeder(refs, WINDOW, PENALTY, params, max_reads=N_READS, stride=STRIDE, n_slots=args.slots, adc=args.adc)
     res_q = ctx.Queue()
     start = ctx.Barrier(P)
 
@@ -142,20 +168,27 @@ def feeder_mode(args):
         try:
             spec = synth.SynthSpec(n_barcodes=N_REFS)
             mb, a_s, a_e, _ = synth.generate_minibatch(spec, 1000 * pid, N_READS, STRIDE, start_jitter=args.jitter)
+            rows = mb
+            if args.adc:
+                mb, *cal = quantise(mb, pid)
+                rows = sig_proc.calibrate_adc(mb, *cal)
+                call = lambda: feeder.detect_and_predict_adc(mb, *cal, a_s, a_e)    # noqa: E731
+            else:
+                call = lambda: feeder.detect_and_predict(mb, a_s, a_e)              # noqa: E731
             src = mb.copy() if args.refill else None
             for _ in range(2):
-                fb, (y_pred, y_prob) = feeder.detect_and_predict(mb, a_s, a_e)
+                fb, (y_pred, y_prob) = call()
             start.wait()
             t0 = time.perf_counter()
             n = 0
             while time.perf_counter() - t0 < args.seconds:
                 if src is not None:
                     np.copyto(mb, src)                # the worker's own fill of its minibatch
-                fb, (y_pred, y_prob) = feeder.detect_and_predict(mb, a_s, a_e)
+                fb, (y_pred, y_prob) = call()
                 n += 1
             dt = time.perf_counter() - t0
             m = 64       # (the oracle's DTW against 2 601 references: a sample of the minibatch)
-            fpt, dwell, stats, status = orc.fingerprint_batch(mb[:m], a_s[:m], a_e[:m], orc.SegParams(barcode_num_events=KF))
+            fpt, dwell, stats, status = orc.fingerprint_batch(rows[:m], a_s[:m], a_e[:m], orc.SegParams(barcode_num_events=KF))
             okk = status == 0
             D = orc.dtw_matrix(fpt[okk], np.ascontiguousarray(g["X_train"], dtype=np.float64), int(g["window"]), float(g["penalty"]))
             Kq = np.exp(-float(g["gamma"]) * np.power(D, int(g["pwr_dist"])))
@@ -182,19 +215,26 @@ def feeder_mode(args):
         try:
             spec = synth.SynthSpec(n_barcodes=N_REFS)
             mb, a_s, a_e, _ = synth.generate_minibatch(spec, 1000 * pid, N_READS, STRIDE, start_jitter=args.jitter)
+            rows = mb
+            if args.adc:
+                mb, *cal = quantise(mb, pid)
+                rows = sig_proc.calibrate_adc(mb, *cal)
+                call = lambda: feeder.demux_batch_adc(mb, *cal, a_s, a_e)    # noqa: E731
+            else:
+                call = lambda: feeder.demux_batch(mb, a_s, a_e)              # noqa: E731
             src = mb.copy() if args.refill else None
             for _ in range(2):
-                res = feeder.demux_batch(mb, a_s, a_e)
+                res = call()
             start.wait()
             t0 = time.perf_counter()
             n = 0
             while time.perf_counter() - t0 < args.seconds:
                 if src is not None:
                     np.copyto(mb, src)                # the worker's own fill of its minibatch
-                res = feeder.demux_batch(mb, a_s, a_e)
+                res = call()
                 n += 1
             dt = time.perf_counter() - t0
-            fpt, dwell, stats, status = orc.fingerprint_batch(mb, a_s, a_e, orc.SegParams(barcode_num_events=K))
+            fpt, dwell, stats, status = orc.fingerprint_batch(rows, a_s, a_e, orc.SegParams(barcode_num_events=K))
             okk = status == 0
             D = orc.dtw_matrix(fpt[okk], refs, WINDOW, PENALTY)
             parity = bool(np.array_equal(res.status, status) and np.array_equal(res.dist[okk].view(np.uint32), D.view(np.uint32)) and
@@ -225,7 +265,7 @@ def feeder_mode(args):
             return 1
         reads = sum(r["minibatches"] for r in res) * N_READS
         wall = max(r["seconds"] for r in res)
-        out = {"workers": P, "mode": args.mode, "slots": args.slots, "gpu_facing_processes": 1, "refill": bool(args.refill),
+        out = {"workers": P, "mode": args.mode, "adc": bool(args.adc), "slots": args.slots, "gpu_facing_processes": 1, "refill": bool(args.refill),
                "start_jitter": args.jitter, "reads_per_s": reads / wall, "minibatches": sum(r["minibatches"] for r in res),
                "seconds": wall, "ms_per_minibatch_per_worker": 1e3 * wall / (sum(r["minibatches"] for r in res) / P),
                "served_by_the_feeder": feeder.served(), "parity": all(r["parity"] for r in res)}
@@ -248,6 +288,7 @@ def main():
     ap.add_argument("--slots", type=int, default=16, help="feeder mode: ring slots (<= 32; at most 8 of them are in flight on the device)")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--refill", action="store_true")
+    ap.add_argument("--adc", action="store_true", help="feed int16 ADC rows (2 bytes per sample, calibrated on the device)")
     ap.add_argument("--jitter", type=int, default=0, help="adapter_start ~ U{100 .. 100 + JITTER} per read (rows carry whole "
                     "reads, file_proc.py:244-260); 0 = every adapter starts at sample 100")
     args = ap.parse_args()
@@ -268,7 +309,7 @@ def main():
         sys.exit(1)
     reads = sum(r["minibatches"] for r in res) * N_READS
     wall = max(r["seconds"] for r in res)
-    out = {"workers": args.workers, "mode": args.mode, "refill": bool(args.refill), "start_jitter": args.jitter,
+    out = {"workers": args.workers, "mode": args.mode, "adc": bool(args.adc), "refill": bool(args.refill), "start_jitter": args.jitter,
            "reads_per_s": reads / wall,
            "minibatches": sum(r["minibatches"] for r in res), "seconds": wall,
            "ms_per_minibatch_per_worker": 1e3 * wall / (sum(r["minibatches"] for r in res) / args.workers),

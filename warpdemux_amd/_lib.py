@@ -57,6 +57,7 @@ EXPORTS = [
     "wdx_feeder_ring_bytes", "wdx_feeder_ring_init", "wdx_feeder_serve", "wdx_feeder_run", "wdx_feeder_demux", "wdx_feeder_predict", "wdx_feeder_stop",
     "wdx_feeder_served", "wdx_feeder_stats", "wdx_feeder_alive", "wdx_feeder_selftest",
     "wdx_mlp_set_model", "wdx_mlp_predict_dev", "wdx_dtw_mlp_predict", "wdx_demux_mlp_dev",
+    "wdx_demux_submit_adc", "wdx_fingerprint_batch_adc", "wdx_demux_batch_adc", "wdx_calibrate_adc_dev", "wdx_feeder_run_adc",
 ]
 
 
@@ -168,6 +169,16 @@ class MinibatchInC(C.Structure):
     ]
 
 
+class MinibatchAdcInC(C.Structure):
+    """wdx_minibatch_adc_in (include/wdx.h)"""
+
+    _fields_ = [
+        ("adc", C.c_void_p), ("n_reads", C.c_int64), ("stride", C.c_int64), ("row_len", C.c_void_p), ("offset", C.c_void_p),
+        ("scale", C.c_void_p), ("row_off", C.c_void_p), ("row_win", C.c_void_p), ("a_start", C.c_void_p), ("a_end", C.c_void_p),
+        ("ok", C.c_void_p),
+    ]
+
+
 class MinibatchOutC(C.Structure):
     """wdx_minibatch_out (include/wdx.h)"""
 
@@ -181,9 +192,12 @@ class FeederGeometryC(C.Structure):
     """wdx_feeder_geometry (include/wdx.h)"""
 
     _fields_ = [
-        ("n_slots", C.c_int32), ("n_events", C.c_int32), ("n_classes", C.c_int32), ("pad_", C.c_int32),
+        ("n_slots", C.c_int32), ("n_events", C.c_int32), ("n_classes", C.c_int32), ("sample_format", C.c_int32),
         ("max_reads", C.c_int64), ("max_stride", C.c_int64), ("n_refs", C.c_int64),
     ]
+
+
+FEEDER_SAMPLES_FLOAT32, FEEDER_SAMPLES_INT16 = 0, 1   # WDX_FEEDER_SAMPLES_*
 
 
 class FeederJobC(C.Structure):
@@ -192,6 +206,18 @@ class FeederJobC(C.Structure):
     _fields_ = [
         ("sig", C.c_void_p), ("n_reads", C.c_int64), ("stride", C.c_int64), ("a_start", C.c_void_p), ("a_end", C.c_void_p),
         ("ok", C.c_void_p), ("want", C.c_uint32), ("pad_", C.c_uint32),
+        ("status", C.c_void_p), ("call", C.c_void_p), ("dist", C.c_void_p), ("fpt", C.c_void_p), ("dwell", C.c_void_p),
+        ("stats", C.c_void_p), ("prob", C.c_void_p), ("pred", C.c_void_p), ("conf", C.c_void_p),
+    ]
+
+
+class FeederJobAdcC(C.Structure):
+    """wdx_feeder_job_adc (include/wdx.h)"""
+
+    _fields_ = [
+        ("adc", C.c_void_p), ("n_reads", C.c_int64), ("stride", C.c_int64), ("row_len", C.c_void_p), ("offset", C.c_void_p),
+        ("scale", C.c_void_p), ("a_start", C.c_void_p), ("a_end", C.c_void_p), ("ok", C.c_void_p), ("want", C.c_uint32),
+        ("pad_", C.c_uint32),
         ("status", C.c_void_p), ("call", C.c_void_p), ("dist", C.c_void_p), ("fpt", C.c_void_p), ("dwell", C.c_void_p),
         ("stats", C.c_void_p), ("prob", C.c_void_p), ("pred", C.c_void_p), ("conf", C.c_void_p),
     ]
@@ -391,6 +417,16 @@ def load():
         L.wdx_demux_mlp_dev.restype = C.c_int
         L.wdx_demux_mlp_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp, vp, vp, vp,
                                         i64, vp]
+        L.wdx_demux_submit_adc.restype = C.c_int
+        L.wdx_demux_submit_adc.argtypes = [vp, i32, P(MinibatchAdcInC), P(SegParamsC), i64, C.c_uint32]
+        L.wdx_fingerprint_batch_adc.restype = C.c_int
+        L.wdx_fingerprint_batch_adc.argtypes = [vp, P(MinibatchAdcInC), P(SegParamsC), vp, vp, vp, vp]
+        L.wdx_demux_batch_adc.restype = C.c_int
+        L.wdx_demux_batch_adc.argtypes = [vp, P(MinibatchAdcInC), P(SegParamsC), i64, vp, vp, vp, vp]
+        L.wdx_calibrate_adc_dev.restype = C.c_int
+        L.wdx_calibrate_adc_dev.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp]
+        L.wdx_feeder_run_adc.restype = C.c_int
+        L.wdx_feeder_run_adc.argtypes = [vp, P(FeederJobAdcC)]
         _lib = L
         return L
 

@@ -441,7 +441,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     comm_destroy(ctx);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf})
         b->release();
     ctx->pin_in.release();
@@ -897,15 +897,14 @@ struct MbHostOut {  // host destinations of one minibatch; null = not wanted (st
     double *conf = nullptr;
 };
 
-static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch_in &in, const wdx_seg_params *p,
-                               const MbHostOut &H, const SvmDev *svm) {
+// The float32 rows of one minibatch -> device, and the fingerprint stage on them (on B->stream).
+static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const wdx_seg_params *p, const FpOut &out) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const float *sig = in.sig;
     const int64_t n_reads = in.n_reads, stride = in.stride;
     const int32_t *a_start = in.a_start, *a_end = in.a_end;
     const uint8_t *ok = in.ok;
-    const int64_t K = p->barcode_num_events;
     const bool packed_in = in.row_off != nullptr;
     int64_t max_len = 0, col0 = stride, col1 = 0;  // columns [col0, col1) hold every adapter window of the batch
     int64_t win_total = 0;
@@ -923,25 +922,10 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
         }
     }
     const size_t sb = (size_t)(packed_in ? in.row_off[n_reads] : n_reads * stride) * sizeof(float);
-    const size_t db = (size_t)(n_reads * (R.nY > 0 ? R.nY : 1)) * sizeof(float);
     if ((rc = B->in0.ensure(sb ? sb : 4))) return rc;
     if ((rc = B->in1.ensure((size_t)n_reads * 4))) return rc;
     if ((rc = B->in2.ensure((size_t)n_reads * 4))) return rc;
     if ((rc = B->in3.ensure((size_t)n_reads))) return rc;
-    if ((rc = B->out0.ensure((size_t)(n_reads * K) * 8))) return rc;
-    if ((rc = B->out1.ensure(db))) return rc;
-    if ((rc = B->out2.ensure((size_t)n_reads * 4))) return rc;
-    if ((rc = B->out3.ensure((size_t)n_reads * 4))) return rc;
-    if (H.dwell && (rc = B->mb_dwell.ensure((size_t)(n_reads * K) * 8))) return rc;
-    if (H.stats && (rc = B->mb_stats.ensure((size_t)n_reads * 48))) return rc;
-    if (svm) {
-        if ((rc = B->mb_prob.ensure((size_t)n_reads * svm->k * 8))) return rc;
-        if ((rc = B->mb_pred.ensure((size_t)n_reads * 4))) return rc;
-        if ((rc = B->mb_conf.ensure((size_t)n_reads * 8))) return rc;
-    }
-    if ((rc = B->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    int64_t *d_dwell = H.dwell ? (int64_t *)B->mb_dwell.p : nullptr;
-    double *d_stats = H.stats ? (double *)B->mb_stats.p : nullptr;
     // (Letting the FINGERPRINT kernel read a page-locked minibatch in place over the bus was measured and lost: 1.80 M
     // reads/s against 2.46 M with a DMA copy, which runs at 49 GB/s.)
     // Three ways in.  (i) The 2-D DMA copy of the column range that holds every adapter window of the batch -- all a
@@ -954,7 +938,6 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
     // CALLER packed (wdx_minibatch_in.row_off; the feeder's workers): one flat copy of exactly the windows.
     const float *sig_dev = nullptr;  // the minibatch as the device sees it, when it is page-locked
     const uint8_t *d_ok = ok ? (const uint8_t *)B->in3.p : nullptr;
-    const FpOut out{(double *)B->out0.p, d_dwell, d_stats, (int32_t *)B->out3.p};
     if (!packed_in && col1 > col0 && (double)win_total < 0.85 * (double)((col1 - col0) * n_reads)) {
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, sig) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer)
@@ -1021,6 +1004,179 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
                          (const int32_t *)B->in2.p, d_ok};
         if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s))) return rc;
     }
+    return WDX_SUCCESS;
+}
+
+// Argument checks of every *_adc entry point: host arithmetic only, so a bad descriptor is refused before (and without) a
+// device.
+static int adc_check_args(const char *who, const wdx_minibatch_adc_in *in) {
+    if (!in) {
+        set_error("%s: null minibatch", who);
+        return WDX_ERR_INVALID;
+    }
+    const int64_t n = in->n_reads;
+    if (n < 0 || (!in->row_off && (in->stride < 0 || in->stride > INT32_MAX)) ||
+        (n > 0 && (!in->adc || !in->a_start || !in->a_end))) {
+        set_error("%s: bad arguments", who);
+        return WDX_ERR_INVALID;
+    }
+    if (n > 0 && !in->row_len) {
+        set_error("%s: int16 rows need row_len (there is no NaN tail to find a read's end by)", who);
+        return WDX_ERR_INVALID;
+    }
+    if (n > 0 && (!in->offset || !in->scale)) {
+        set_error("%s: int16 rows need offset and scale of every read", who);
+        return WDX_ERR_INVALID;
+    }
+    if (in->row_win && !in->row_off) {
+        set_error("%s: row_win belongs to packed rows (row_off)", who);
+        return WDX_ERR_INVALID;
+    }
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t len = in->row_len[r];
+        if (in->row_off) {
+            const int64_t o0 = in->row_off[r], o1 = in->row_off[r + 1];
+            if (o0 < 0 || (o0 & 7) || o1 < o0) {
+                set_error("%s: packed row %lld: row_off must ascend in multiples of 8 (16-byte groups of int16)", who, (long long)r);
+                return WDX_ERR_INVALID;
+            }
+            if (len < 0 || len > o1 - o0 || (in->row_win && in->row_win[r] < 0)) {
+                set_error("%s: packed row %lld: row_len %lld does not fit its %lld samples", who, (long long)r, (long long)len,
+                          (long long)(o1 - o0));
+                return WDX_ERR_INVALID;
+            }
+        } else if (len < 0 || len > in->stride) {
+            set_error("%s: row_len[%lld] = %lld is outside 0 .. stride (%lld)", who, (long long)r, (long long)len,
+                      (long long)in->stride);
+            return WDX_ERR_INVALID;
+        }
+    }
+    return WDX_SUCCESS;
+}
+
+// The int16 ADC rows of one minibatch -> calibrated float32 windows in a PACKED device buffer (wdx_adc.hip), and the
+// fingerprint stage on them.  The same three ways in as the float32 rows: (i) 2-D DMA copy of the int16 columns that hold
+// the windows, then decode_adc_kernel; (ii) a page-locked minibatch: pack_windows_adc_kernel reads the windows over the
+// bus; (iii) rows the caller packed: one flat copy, then decode_adc_kernel.  Row r of the packed buffer = samples
+// [st_r, en_r) of the float32 row the read stands for, st_r rounded down to a multiple of 8 (16-byte groups of int16),
+// adapter bounds shifted by st_r: the same window, bit for bit.
+static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const wdx_seg_params *p, const FpOut &out) {
+    int rc = WDX_SUCCESS;
+    hipStream_t s = B->stream;
+    const int64_t n = A.n_reads, stride = A.stride;
+    const bool packed_in = A.row_off != nullptr;
+    // host images (page-locked, owned by the slot until its copy has run):
+    // dst_off int64[n+1] | src_off int64[n] | n_out int32[n] | n_valid int32[n] | a_start' int32[n] | a_end' int32[n] |
+    // offset float[n] | scale float[n]
+    const size_t ib = (size_t)(n + 1) * 8 + (size_t)n * 8 + (size_t)n * 24;
+    if ((rc = B->pk_host.ensure(ib))) return rc;
+    if ((rc = B->pk_idx.ensure(ib))) return rc;
+    if ((rc = B->in3.ensure((size_t)n))) return rc;
+    int64_t *h_dst = (int64_t *)B->pk_host.p, *h_src = h_dst + n + 1;
+    int32_t *h_out = (int32_t *)(h_src + n), *h_valid = h_out + n, *h_as = h_valid + n, *h_ae = h_as + n;
+    float *h_cal = (float *)(h_ae + n);
+    int64_t acc = 0, max_len = 0, col0 = stride, col1 = 0, win_total = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        const bool dead = A.ok && !A.ok[r];
+        int64_t st = (int64_t)A.a_start[r] - p->padding, en = (int64_t)A.a_end[r] + p->padding;
+        int64_t first = 0, row = 0, valid = 0;   // first sample taken, samples of the packed row, of them from the read
+        if (packed_in) {
+            row = A.row_win ? (int64_t)A.row_win[r] : (int64_t)A.row_len[r];
+            valid = std::min<int64_t>(A.row_len[r], row);
+            if (st < 0) st = 0;
+            if (en > row) en = row;
+            h_src[r] = A.row_off[r];
+        } else {
+            // the window start is clamped to the row BEFORE it is aligned: a start beyond the row (a failed detection's
+            // garbage) takes nothing instead of samples of the next row
+            st = std::min<int64_t>(std::max<int64_t>(st, 0), stride);
+            if (en > stride) en = stride;
+            if (en > st && !dead) {
+                first = st & ~(int64_t)7;
+                row = en - first;
+                valid = std::min<int64_t>(std::max<int64_t>((int64_t)A.row_len[r] - first, 0), row);
+            }
+            h_src[r] = r * stride + first;
+            if (valid > 0) {
+                win_total += valid;
+                col0 = std::min(col0, first);
+                col1 = std::max(col1, first + valid);
+            }
+        }
+        if (!dead && en - st > max_len) max_len = en - st;
+        h_dst[r] = acc;
+        h_out[r] = (int32_t)row;
+        h_valid[r] = (int32_t)valid;
+        h_as[r] = A.a_start[r] - (int32_t)first;
+        h_ae[r] = A.a_end[r] - (int32_t)first;
+        h_cal[r] = A.offset[r];
+        h_cal[n + r] = A.scale[r];
+        acc += (row + 7) & ~(int64_t)7;   // (rows start on 32-byte boundaries)
+    }
+    h_dst[n] = acc;
+    if ((rc = B->in0.ensure((size_t)(acc ? acc : 1) * sizeof(float)))) return rc;
+    WDX_HIP_TRY(hipMemcpyAsync(B->pk_idx.p, B->pk_host.p, ib, hipMemcpyHostToDevice, s));
+    const int64_t *d_dst = (const int64_t *)B->pk_idx.p, *d_src = d_dst + n + 1;
+    const int32_t *d_out = (const int32_t *)(d_src + n), *d_valid = d_out + n, *d_as = d_valid + n, *d_ae = d_as + n;
+    const float *d_cal = (const float *)(d_ae + n);
+    AdcRows rows{nullptr, d_src, 0, d_valid, d_cal, d_cal + n, (float *)B->in0.p, d_dst, 0, d_out};
+    const int16_t *adc_dev = nullptr;  // the minibatch as the device sees it, when it is page-locked
+    if (!packed_in && col1 > col0 && (double)win_total < 0.85 * (double)((col1 - col0) * n)) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, A.adc) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer)
+            adc_dev = (const int16_t *)at.devicePointer;
+        else
+            (void)hipGetLastError();
+    }
+    if (adc_dev) {
+        rows.src = adc_dev;
+    } else {
+        const size_t sb = (size_t)(packed_in ? A.row_off[n] : n * stride) * sizeof(int16_t);
+        if ((rc = B->in_adc.ensure(sb ? sb : 2))) return rc;
+        if (packed_in) {
+            if (sb) WDX_HIP_TRY(hipMemcpyAsync(B->in_adc.p, A.adc, sb, hipMemcpyHostToDevice, s));
+        } else if (col1 > col0) {
+            WDX_HIP_TRY(hipMemcpy2DAsync((int16_t *)B->in_adc.p + col0, (size_t)stride * sizeof(int16_t), A.adc + col0,
+                                         (size_t)stride * sizeof(int16_t), (size_t)(col1 - col0) * sizeof(int16_t), (size_t)n,
+                                         hipMemcpyHostToDevice, s));
+        }
+        rows.src = (const int16_t *)B->in_adc.p;
+    }
+    if ((rc = launch_adc_rows(rows, n, adc_dev != nullptr, s))) return rc;
+    if (A.ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, A.ok, (size_t)n, hipMemcpyHostToDevice, s));
+    const FpReads rd{(const float *)B->in0.p, d_dst, d_out, 0, max_len, n, d_as, d_ae, A.ok ? (const uint8_t *)B->in3.p : nullptr};
+    return fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s);
+}
+// One minibatch as demux_batch_enqueue takes it: float32 rows or int16 ADC rows (exactly one is set).
+struct MbIn {
+    const wdx_minibatch_in *f = nullptr;
+    const wdx_minibatch_adc_in *adc = nullptr;
+    int64_t n_reads() const { return adc ? adc->n_reads : f->n_reads; }
+};
+
+static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, const wdx_seg_params *p,
+                               const MbHostOut &H, const SvmDev *svm) {
+    int rc = WDX_SUCCESS;
+    hipStream_t s = B->stream;
+    const int64_t n_reads = in.n_reads();
+    const int64_t K = p->barcode_num_events;
+    const size_t db = (size_t)(n_reads * (R.nY > 0 ? R.nY : 1)) * sizeof(float);
+    if ((rc = B->out0.ensure((size_t)(n_reads * K) * 8))) return rc;
+    if ((rc = B->out1.ensure(db))) return rc;
+    if ((rc = B->out2.ensure((size_t)n_reads * 4))) return rc;
+    if ((rc = B->out3.ensure((size_t)n_reads * 4))) return rc;
+    if (H.dwell && (rc = B->mb_dwell.ensure((size_t)(n_reads * K) * 8))) return rc;
+    if (H.stats && (rc = B->mb_stats.ensure((size_t)n_reads * 48))) return rc;
+    if (svm) {
+        if ((rc = B->mb_prob.ensure((size_t)n_reads * svm->k * 8))) return rc;
+        if ((rc = B->mb_pred.ensure((size_t)n_reads * 4))) return rc;
+        if ((rc = B->mb_conf.ensure((size_t)n_reads * 8))) return rc;
+    }
+    if ((rc = B->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
+    int64_t *d_dwell = H.dwell ? (int64_t *)B->mb_dwell.p : nullptr;
+    double *d_stats = H.stats ? (double *)B->mb_stats.p : nullptr;
+    const FpOut out{(double *)B->out0.p, d_dwell, d_stats, (int32_t *)B->out3.p};
+    if ((rc = in.adc ? fingerprint_adc_rows(B, *in.adc, p, out) : fingerprint_float_rows(B, *in.f, p, out))) return rc;
     if (R.nY > 0) {
         if ((rc = dtw_dev_locked(B, (const double *)B->out0.p, n_reads, (float *)B->out1.p,
                                  (int32_t *)B->out2.p, s)))
@@ -1048,7 +1204,7 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const wdx_minibatch
     return WDX_SUCCESS;
 }
 
-static int demux_check_args(wdx_ctx *ctx, const char *who, int64_t n_reads, int64_t stride, const float *sig,
+static int demux_check_args(wdx_ctx *ctx, const char *who, int64_t n_reads, int64_t stride, const void *sig,
                             const int32_t *a_start, const int32_t *a_end, const wdx_seg_params *p, int64_t n_refs) {
     if (n_reads < 0 || stride < 0 || !p || (n_reads > 0 && (!sig || !a_start || !a_end))) {
         set_error("%s: bad arguments", who);
@@ -1068,22 +1224,22 @@ static int demux_check_args(wdx_ctx *ctx, const char *who, int64_t n_reads, int6
     return WDX_SUCCESS;
 }
 
-int wdx_demux_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64_t stride,
-                    const int32_t *a_start, const int32_t *a_end, const uint8_t *ok,
-                    const wdx_seg_params *p, int64_t n_refs, double *fpt, float *dist, int32_t *call,
-                    int32_t *status) {
+// wdx_demux_batch / wdx_demux_batch_adc: one minibatch on the context's own stream, one synchronisation
+static int demux_batch_blocking(wdx_ctx *ctx, const char *who, const MbIn &in, const void *rows, int64_t stride,
+                                const int32_t *a_start, const int32_t *a_end, const wdx_seg_params *p, int64_t n_refs,
+                                double *fpt, float *dist, int32_t *call, int32_t *status) {
     WDX_ENTER(ctx);
+    const int64_t n_reads = in.n_reads();
     if (n_reads > 0 && (!call || !status)) {
-        set_error("demux_batch: bad arguments");
+        set_error("%s: bad arguments", who);
         return WDX_ERR_INVALID;
     }
     std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = demux_check_args(ctx, "demux_batch", n_reads, stride, sig, a_start, a_end, p, n_refs))) return rc;
+    if ((rc = demux_check_args(ctx, who, n_reads, stride, rows, a_start, a_end, p, n_refs))) return rc;
     if (n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = ctx->stream;
     if ((rc = use_stream(ctx, s))) return rc;
     StreamDrain drain(s);
-    const wdx_minibatch_in in{sig, n_reads, stride, nullptr, nullptr, a_start, a_end, ok};
     MbHostOut H;
     H.status = status;
     H.call = call;
@@ -1095,6 +1251,79 @@ int wdx_demux_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64_t str
     if (ctx->refs.nY == 0)
         for (int64_t r = 0; r < n_reads; ++r) call[r] = -1;
     return WDX_SUCCESS;
+}
+
+int wdx_demux_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64_t stride,
+                    const int32_t *a_start, const int32_t *a_end, const uint8_t *ok,
+                    const wdx_seg_params *p, int64_t n_refs, double *fpt, float *dist, int32_t *call,
+                    int32_t *status) {
+    const wdx_minibatch_in in{sig, n_reads, stride, nullptr, nullptr, a_start, a_end, ok};
+    MbIn mb;
+    mb.f = &in;
+    return demux_batch_blocking(ctx, "demux_batch", mb, sig, stride, a_start, a_end, p, n_refs, fpt, dist, call, status);
+}
+
+int wdx_demux_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, const wdx_seg_params *p, int64_t n_refs, double *fpt,
+                        float *dist, int32_t *call, int32_t *status) {
+    if (int e = adc_check_args("demux_batch_adc", in)) return e;
+    MbIn mb;
+    mb.adc = in;
+    return demux_batch_blocking(ctx, "demux_batch_adc", mb, in->adc, in->row_off ? 0 : in->stride, in->a_start, in->a_end, p,
+                                n_refs, fpt, dist, call, status);
+}
+
+// wdx_fingerprint_batch for int16 rows: the minibatch path above with no reference set (nothing behind the fingerprint
+// stage runs), so that the int16 rows have ONE way in
+int wdx_fingerprint_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, const wdx_seg_params *p, double *fpt,
+                              int64_t *dwell, double *stats, int32_t *status) {
+    if (int e = adc_check_args("fingerprint_batch_adc", in)) return e;
+    WDX_ENTER(ctx);
+    const int64_t n_reads = in->n_reads;
+    if (!p || (n_reads > 0 && (!fpt || !dwell || !stats || !status))) {
+        set_error("fingerprint_batch_adc: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (p->barcode_num_events < 1) {
+        set_error("barcode_num_events must be >= 1");
+        return WDX_ERR_INVALID;
+    }
+    if (n_reads == 0) return WDX_SUCCESS;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hipStream_t s = ctx->stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    StreamDrain drain(s);
+    MbIn mb;
+    mb.adc = in;
+    MbHostOut H;
+    H.status = status;
+    H.fpt = fpt;
+    H.dwell = dwell;
+    H.stats = stats;
+    if ((rc = demux_batch_enqueue(ctx, DtwRefs{}, mb, p, H, nullptr))) return rc;
+    WDX_HIP_TRY(hipStreamSynchronize(s));
+    drain.done();
+    return WDX_SUCCESS;
+}
+
+int wdx_calibrate_adc_dev(wdx_ctx *ctx, const int16_t *d_adc, const int64_t *d_row_off, const int32_t *d_row_len,
+                          int64_t stride, int64_t n_reads, const float *d_offset, const float *d_scale, float *d_out,
+                          void *stream) {
+    if (n_reads < 0 || stride < 0 || stride > INT32_MAX || (n_reads > 0 && stride > 0 && (!d_adc || !d_out))) {
+        set_error("calibrate_adc_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (n_reads > 0 && !d_row_len) {
+        set_error("calibrate_adc_dev: int16 rows need row_len (there is no NaN tail to find a read's end by)");
+        return WDX_ERR_INVALID;
+    }
+    if (n_reads > 0 && (!d_offset || !d_scale)) {
+        set_error("calibrate_adc_dev: int16 rows need offset and scale of every read");
+        return WDX_ERR_INVALID;
+    }
+    WDX_ENTER(ctx);
+    if (n_reads == 0 || stride == 0) return WDX_SUCCESS;
+    const AdcRows rows{d_adc, d_row_off, stride, d_row_len, d_offset, d_scale, d_out, nullptr, stride, nullptr};
+    return launch_adc_rows(rows, n_reads, false, (hipStream_t)stream);
 }
 
 // ---- pipelined minibatches: two slots per context, submit / wait -------------------------------------------------
@@ -1157,6 +1386,9 @@ int wdx_host_free(void *p) {
     return WDX_SUCCESS;
 }
 
+// wdx_demux_submit_ex / wdx_demux_submit_adc behind their own argument checks (the context's mutex is held)
+static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want);
+
 int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, const wdx_seg_params *p, int64_t n_refs,
                         uint32_t want) {
     WDX_ENTER(ctx);
@@ -1182,6 +1414,27 @@ int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, 
             }
         }
     }
+    MbIn mb;
+    mb.f = in;
+    return demux_submit_locked(ctx, slot, mb, p, want);
+}
+
+int wdx_demux_submit_adc(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_adc_in *in, const wdx_seg_params *p, int64_t n_refs,
+                         uint32_t want) {
+    if (int e = adc_check_args("demux_submit_adc", in)) return e;
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((rc = demux_check_args(ctx, "demux_submit_adc", in->n_reads, in->row_off ? 0 : in->stride, in->adc, in->a_start,
+                               in->a_end, p, n_refs)))
+        return rc;
+    MbIn mb;
+    mb.adc = in;
+    return demux_submit_locked(ctx, slot, mb, p, want);
+}
+
+static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want) {
+    int rc = WDX_SUCCESS;
+    const int64_t n_reads = in.n_reads();
     const bool want_svm = (want & WDX_WANT_SVM) != 0;
     if (want_svm) {
         if (!ctx->svm_set) {
@@ -1248,7 +1501,7 @@ int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, 
     H.pred = bytes[8] ? (int32_t *)(ho + S->slot_off[8]) : nullptr;
     StreamDrain drain(S->stream);
     S->dtw_last.family = WDX_DTW_NONE;   // (a submit that dispatches no DTW leaves the parent's record as it was)
-    if ((rc = demux_batch_enqueue(S, R, *in, p, H, want_svm ? &ctx->svm : nullptr))) return rc;
+    if ((rc = demux_batch_enqueue(S, R, in, p, H, want_svm ? &ctx->svm : nullptr))) return rc;
     drain.done();  // in flight on purpose: wdx_demux_wait synchronises
     if (S->dtw_last.family != WDX_DTW_NONE) ctx->dtw_last = S->dtw_last;
     S->slot_busy = true;

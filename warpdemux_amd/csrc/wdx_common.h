@@ -228,4 +228,23 @@ int launch_pack_windows(const float *src_dev, int64_t stride, int64_t n_reads, c
                         const int32_t *d_len, float *dst, hipStream_t stream);
 int launch_calib_read(const float *p, int64_t n, float *out, hipStream_t stream);
 
+// ---- int16 ADC rows -> calibrated float32 rows (wdx_adc.hip) --------------------------------------
+// Where read r's samples are and where they go (all arrays DEVICE memory; `src` itself may be a mapped host pointer):
+//   source       src + (src_off ? src_off[r] : r * src_stride), n_valid[r] samples (clamped to 0 .. the row's n)
+//   destination  dst + (dst_off ? dst_off[r] : r * dst_stride), n = n_out ? n_out[r] : dst_stride samples:
+//                scale[r] * ((float)adc + offset[r]) for the first n_valid[r], NaN behind them
+struct AdcRows {
+    const int16_t *src;
+    const int64_t *src_off;
+    int64_t src_stride;
+    const int32_t *n_valid;
+    const float *offset, *scale;
+    float *dst;
+    const int64_t *dst_off;
+    int64_t dst_stride;
+    const int32_t *n_out;
+};
+// over_the_bus: pack_windows_adc_kernel (src = a page-locked host minibatch), else decode_adc_kernel
+int launch_adc_rows(const AdcRows &A, int64_t n_reads, bool over_the_bus, hipStream_t stream);
+
 }  // namespace wdx

@@ -58,6 +58,7 @@ struct wdx_ctx {
     std::vector<double> ref_query_host;  // the consensus query resident in ref_buf (wdx_fingerprint_refine_dev uploads on change)
     wdx::Buffer pk_idx;       // packed staging of a page-locked minibatch: window offsets / first columns / shifted bounds
     wdx::PinnedBuffer pk_host;  // ... and their host images (kept until the slot's copy has run)
+    wdx::Buffer in_adc;       // int16 ADC rows as they arrived by DMA copy, ahead of decode_adc_kernel (wdx_adc.hip)
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     wdx::SvmDev svm{};
     bool svm_set = false;

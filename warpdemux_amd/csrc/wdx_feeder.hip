@@ -15,7 +15,9 @@
 //
 // A worker copies only what the kernels read: samples [a_start - padding, a_end + padding) of each row, back to back
 // (PACKED rows, wdx_minibatch_in.row_off) -- 18.7 MB instead of 40 MB per 1000-read minibatch on both of the worker's
-// copies' sides (its own memcpy and the feeder's DMA).
+// copies' sides (its own memcpy and the feeder's DMA).  A ring laid out for int16 samples (wdx_feeder_geometry.sample_format
+// = WDX_FEEDER_SAMPLES_INT16, wdx_feeder_run_adc) halves that again: the worker copies the raw ADC windows and each read's
+// offset / scale, the server submits through wdx_demux_submit_adc and the device calibrates (wdx_adc.hip).
 //
 // Slot life cycle.  One futex word per slot: (owner pid << 8) | phase, FREE -> FILLING (a worker owns it) -> READY ->
 // INFLIGHT (submitted) -> DONE -> FREE.  Workers claim FREE slots by compare-and-swap -- which records the owner in the
@@ -46,7 +48,7 @@
 
 namespace wdx {
 
-constexpr uint32_t kFeederMagic = 0x57444632u;  // "WDF2"
+constexpr uint32_t kFeederMagic = 0x57444633u;  // "WDF3"
 // Ring slots and in-flight slots are different things: a ring slot is held by its worker while the worker COPIES its
 // minibatch in (milliseconds) and again while it copies the results out, the context keeps at most WDX_MAX_SLOTS of
 // them in flight on the device.  With as many ring slots as in-flight slots the ring is what sixteen workers queue for.
@@ -72,11 +74,15 @@ struct FeederRing {
     uint32_t magic, n_slots;
     int64_t max_reads, max_stride, n_refs;
     int32_t n_events, n_classes;
+    int32_t sample_format, pad_;   // WDX_FEEDER_SAMPLES_*: what the sample region of a slot holds
     wdx_seg_params params;   // what every minibatch is fingerprinted with (workers read `padding` to pack their rows)
     // byte offsets of the data regions (each holds n_slots consecutive per-slot pieces)
     uint64_t off_sig, off_roff, off_rlen, off_as, off_ae, off_ok, off_dist, off_call, off_status, off_fpt, off_dwell, off_stats,
         off_prob, off_pred, off_conf, bytes;
-    uint64_t sig_floats;     // per-slot capacity of the sample region
+    uint64_t sig_floats;     // per-slot capacity of the sample region, in 4-byte units
+    // bytes from one slot's sample region to the next; int16 rings keep the reads' calibration behind the samples:
+    // offset float32[max_reads] | scale float32[max_reads] | row_win int32[max_reads] at byte sig_floats * 4
+    uint64_t sig_slot_bytes;
     uint32_t seq;        // futex: bumped by a worker that made a slot READY
     uint32_t free_seq;   // futex: bumped by whoever made a slot FREE
     uint32_t stop;       // 1: wdx_feeder_stop was called (or the server is leaving)
@@ -164,14 +170,17 @@ struct Geo {
 };
 static bool geometry(const wdx_feeder_geometry *g, Geo &G, size_t &sig_floats) {
     if (!g || g->n_slots < 1 || g->n_slots > kMaxRingSlots || g->max_reads < 1 || g->max_stride < 1 || g->n_refs < 0 ||
-        g->n_events < 0 || g->n_classes < 0 || g->n_classes > 16)
+        g->n_events < 0 || g->n_classes < 0 || g->n_classes > 16 ||
+        (g->sample_format != WDX_FEEDER_SAMPLES_FLOAT32 && g->sample_format != WDX_FEEDER_SAMPLES_INT16))
         return false;
     const size_t mr = (size_t)g->max_reads;
     // a packed row starts on a 16-byte boundary: up to 3 + 3 floats of slack per row; fingerprints for
     // wdx_feeder_predict (max_reads x n_events doubles) use the same region
     sig_floats = mr * (size_t)((g->max_stride + 3) / 4 * 4 + 4);
+    // int16 samples: rows start on 16-byte boundaries = 8 samples, 7 + 7 of slack per row, two samples per 4-byte unit
+    if (g->sample_format == WDX_FEEDER_SAMPLES_INT16) sig_floats = mr * (size_t)((g->max_stride + 7) / 8 * 8 + 8) / 2;
     if ((size_t)g->n_events * 2 * mr > sig_floats) sig_floats = (size_t)g->n_events * 2 * mr;
-    G.sig = align_up(sig_floats * 4, 4096);
+    G.sig = align_up(sig_floats * 4 + (g->sample_format == WDX_FEEDER_SAMPLES_INT16 ? mr * 12 : 0), 4096);
     G.roff = align_up((mr + 1) * 8, 4096);
     G.rlen = G.i32 = align_up(mr * 4, 4096);
     G.ok = align_up(mr, 4096);
@@ -221,8 +230,10 @@ int wdx_feeder_ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, 
     R->n_refs = g->n_refs;
     R->n_events = g->n_events;
     R->n_classes = g->n_classes;
+    R->sample_format = g->sample_format;
     R->params = *p;
     R->sig_floats = sf;
+    R->sig_slot_bytes = G.sig;
     const size_t ns = (size_t)g->n_slots;
     size_t o = align_up(sizeof(FeederRing), 4096);
     R->off_sig = o;    o += ns * G.sig;
@@ -334,7 +345,7 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
     __atomic_store_n(&R->server_pid, (int32_t)getpid(), __ATOMIC_RELEASE);
     const pid_t parent = getppid();   // (the process that created the ring: when it is gone, nobody will stop us)
     const size_t mr = (size_t)R->max_reads, nY = (size_t)R->n_refs, K = (size_t)R->n_events, kc = (size_t)R->n_classes;
-    auto sig_of = [&](uint32_t s) { return (float *)(base + R->off_sig) + (size_t)s * align_up((size_t)R->sig_floats * 4, 4096) / 4; };
+    auto sig_of = [&](uint32_t s) { return (float *)(base + R->off_sig + (size_t)s * R->sig_slot_bytes); };
     auto roff_of = [&](uint32_t s) { return (int64_t *)(base + R->off_roff + (size_t)s * align_up((mr + 1) * 8, 4096)); };
     auto i32_of = [&](uint64_t off, uint32_t s) { return (int32_t *)(base + off + (size_t)s * align_up(mr * 4, 4096)); };
     auto ok_of = [&](uint32_t s) { return (uint8_t *)(base + R->off_ok + (size_t)s * align_up(mr, 4096)); };
@@ -421,16 +432,33 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
             int cs = 0;
             while (cbusy[cs] && cs < WDX_MAX_SLOTS - 1) ++cs;
             if (cbusy[cs]) break;   // (every context slot lost to refused waits: nothing can be submitted)
-            wdx_minibatch_in in{};
-            in.sig = sig_of(s);
-            in.n_reads = S.n_reads;
-            in.stride = 0;
-            in.row_off = roff_of(s);
-            in.row_len = i32_of(R->off_rlen, s);
-            in.a_start = i32_of(R->off_as, s);
-            in.a_end = i32_of(R->off_ae, s);
-            in.ok = S.has_ok ? ok_of(s) : nullptr;
-            const int rc = wdx_demux_submit_ex(ctx, cs, &in, &R->params, (int64_t)nY, S.want);
+            int rc;
+            if (R->sample_format == WDX_FEEDER_SAMPLES_INT16) {
+                const float *cal = sig_of(s) + R->sig_floats;
+                wdx_minibatch_adc_in in{};
+                in.adc = (const int16_t *)sig_of(s);
+                in.n_reads = S.n_reads;
+                in.row_len = i32_of(R->off_rlen, s);
+                in.offset = cal;
+                in.scale = cal + mr;
+                in.row_off = roff_of(s);
+                in.row_win = (const int32_t *)(cal + 2 * mr);
+                in.a_start = i32_of(R->off_as, s);
+                in.a_end = i32_of(R->off_ae, s);
+                in.ok = S.has_ok ? ok_of(s) : nullptr;
+                rc = wdx_demux_submit_adc(ctx, cs, &in, &R->params, (int64_t)nY, S.want);
+            } else {
+                wdx_minibatch_in in{};
+                in.sig = sig_of(s);
+                in.n_reads = S.n_reads;
+                in.stride = 0;
+                in.row_off = roff_of(s);
+                in.row_len = i32_of(R->off_rlen, s);
+                in.a_start = i32_of(R->off_as, s);
+                in.a_end = i32_of(R->off_ae, s);
+                in.ok = S.has_ok ? ok_of(s) : nullptr;
+                rc = wdx_demux_submit_ex(ctx, cs, &in, &R->params, (int64_t)nY, S.want);
+            }
             if (rc == WDX_SUCCESS) {
                 st(&S.state, word_of(owner_of(v), kInflight));
                 cbusy[cs] = true;
@@ -554,56 +582,99 @@ static int publish_and_wait(FeederRing *R, int s, uint32_t my_gen) {
     return WDX_SUCCESS;
 }
 
-}  // namespace wdx
-
-extern "C" {
+// One minibatch as a worker hands it over: wdx_feeder_job's float32 rows or wdx_feeder_job_adc's int16 rows (is_adc:
+// row_len / offset / scale are set); the outputs are the job's.
+struct WorkerRows {
+    bool is_adc = false;
+    const float *sig = nullptr;
+    const int16_t *adc = nullptr;
+    int64_t n_reads = 0, stride = 0;
+    const int32_t *row_len = nullptr;
+    const float *offset = nullptr, *scale = nullptr;
+    const int32_t *a_start = nullptr, *a_end = nullptr;
+    const uint8_t *ok = nullptr;
+    uint32_t want = 0;
+    wdx_minibatch_out out{};
+};
 
 // A worker process: one minibatch through the feeder -- no context, NO HIP call.  Blocks until the results are there.
-int wdx_feeder_run(void *ring, const wdx_feeder_job *job) {
-    FeederRing *R = (FeederRing *)ring;
-    if (int rc = ring_check(R)) return rc;
-    if (!job) {
-        set_error("feeder_run: null job");
+static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const WorkerRows &job) {
+    const bool is_adc = job.is_adc;
+    const int64_t n_reads = job.n_reads, stride = job.stride;
+    const uint32_t want = job.want;
+    const wdx_minibatch_out &O = job.out;
+    if (n_reads < 0 || stride < 0 || (n_reads > 0 && (!(job.sig || job.adc) || !job.a_start || !job.a_end || !O.status))) {
+        set_error("%s: bad arguments", who);
         return WDX_ERR_INVALID;
     }
-    const int64_t n_reads = job->n_reads, stride = job->stride;
-    const uint32_t want = job->want;
-    if (n_reads < 0 || stride < 0 || (n_reads > 0 && (!job->sig || !job->a_start || !job->a_end || !job->status))) {
-        set_error("feeder_run: bad arguments");
+    if (is_adc != (R->sample_format == WDX_FEEDER_SAMPLES_INT16)) {
+        set_error("%s: %s rows on a ring laid out for %s samples (wdx_feeder_geometry.sample_format)", who,
+                  is_adc ? "int16" : "float32", is_adc ? "float32" : "int16");
         return WDX_ERR_INVALID;
+    }
+    if (is_adc && n_reads > 0) {
+        if (!job.row_len) {
+            set_error("%s: int16 rows need row_len (there is no NaN tail to find a read's end by)", who);
+            return WDX_ERR_INVALID;
+        }
+        if (!job.offset || !job.scale) {
+            set_error("%s: int16 rows need offset and scale of every read", who);
+            return WDX_ERR_INVALID;
+        }
+        for (int64_t r = 0; r < n_reads; ++r)
+            if (job.row_len[r] < 0 || (int64_t)job.row_len[r] > stride) {
+                set_error("%s: row_len[%lld] = %d is outside 0 .. stride (%lld)", who, (long long)r, (int)job.row_len[r],
+                          (long long)stride);
+                return WDX_ERR_INVALID;
+            }
     }
     if (n_reads > R->max_reads) {
-        set_error("feeder_run: %lld reads do not fit the ring's %lld-read slots", (long long)n_reads, (long long)R->max_reads);
+        set_error("%s: %lld reads do not fit the ring's %lld-read slots", who, (long long)n_reads, (long long)R->max_reads);
         return WDX_ERR_INVALID;
     }
     if ((want & ~(WDX_WANT_FPT | WDX_WANT_DIST | WDX_WANT_DWELL | WDX_WANT_STATS | WDX_WANT_SVM)) ||
         ((want & (WDX_WANT_FPT | WDX_WANT_DWELL | WDX_WANT_STATS)) && R->n_events == 0) || ((want & WDX_WANT_SVM) && R->n_classes == 0)) {
-        set_error("feeder_run: the ring was laid out without room for an output that is asked for (n_events %d, n_classes %d)",
+        set_error("%s: the ring was laid out without room for an output that is asked for (n_events %d, n_classes %d)", who,
                   (int)R->n_events, (int)R->n_classes);
         return WDX_ERR_INVALID;
     }
-    if (n_reads > 0 && (((want & WDX_WANT_FPT) && !job->fpt) || ((want & WDX_WANT_DWELL) && !job->dwell) ||
-                        ((want & WDX_WANT_STATS) && !job->stats) || ((want & WDX_WANT_DIST) && R->n_refs > 0 && !job->dist) ||
-                        ((want & WDX_WANT_SVM) && (!job->prob || !job->pred || !job->conf)))) {
-        set_error("feeder_run: an output that is asked for has no destination");
+    if (n_reads > 0 && (((want & WDX_WANT_FPT) && !O.fpt) || ((want & WDX_WANT_DWELL) && !O.dwell) ||
+                        ((want & WDX_WANT_STATS) && !O.stats) || ((want & WDX_WANT_DIST) && R->n_refs > 0 && !O.dist) ||
+                        ((want & WDX_WANT_SVM) && (!O.prob || !O.pred || !O.conf)))) {
+        set_error("%s: an output that is asked for has no destination", who);
         return WDX_ERR_INVALID;
     }
     if (n_reads == 0) return WDX_SUCCESS;
     // the windows, packed: row r = samples [st & ~3, en) of the caller's row, st = a_start - padding, en = a_end + padding
-    // clamped to the row (extract_adapter, sig_proc.py:388-389); every row starts on a 16-byte boundary
+    // clamped to the row (extract_adapter, sig_proc.py:388-389); every row starts on a 16-byte boundary.
+    // int16 rows: [st & ~7, en) with st clamped to the row BEFORE it is aligned (nothing outside the caller's row is ever
+    // read), of which the `valid` samples below the read's row_len are copied -- the rest is the NaN tail the device writes.
     const int64_t pad = R->params.padding;
-    int64_t need = 0;
-    for (int64_t r = 0; r < n_reads; ++r) {
-        int64_t s0 = (int64_t)job->a_start[r] - pad, e0 = (int64_t)job->a_end[r] + pad;
+    struct Win {
+        int64_t s0, len, valid;   // first sample, samples of the packed row, of them copied
+    };
+    auto window = [&](int64_t r) {
+        int64_t s0 = (int64_t)job.a_start[r] - pad, e0 = (int64_t)job.a_end[r] + pad;
         if (s0 < 0) s0 = 0;
         if (e0 > stride) e0 = stride;
-        if (e0 < s0 || (job->ok && !job->ok[r])) e0 = s0;
-        s0 &= ~(int64_t)3;
-        need += ((e0 - s0) + 3) & ~(int64_t)3;
-    }
-    if ((uint64_t)need > R->sig_floats) {
-        set_error("feeder_run: the minibatch's adapter windows (%lld samples) do not fit a ring slot (%llu)", (long long)need,
-                  (unsigned long long)R->sig_floats);
+        const bool dead = job.ok && !job.ok[r];
+        if (!is_adc) {
+            if (e0 < s0 || dead) e0 = s0;
+            s0 &= ~(int64_t)3;
+            return Win{s0, e0 - s0, e0 - s0};
+        }
+        if (s0 > stride) s0 = stride;
+        if (e0 <= s0 || dead) return Win{0, 0, 0};
+        s0 &= ~(int64_t)7;
+        const int64_t v = (int64_t)job.row_len[r] - s0;
+        return Win{s0, e0 - s0, v < 0 ? 0 : (v > e0 - s0 ? e0 - s0 : v)};
+    };
+    const int64_t al = is_adc ? 7 : 3;      // rows start on 16-byte boundaries
+    int64_t need = 0;
+    for (int64_t r = 0; r < n_reads; ++r) need += (window(r).valid + al) & ~al;
+    if ((uint64_t)need > R->sig_floats * (is_adc ? 2u : 1u)) {
+        set_error("%s: the minibatch's adapter windows (%lld samples) do not fit a ring slot (%llu)", who, (long long)need,
+                  (unsigned long long)(R->sig_floats * (is_adc ? 2u : 1u)));
         return WDX_ERR_INVALID;
     }
     int s = -1;
@@ -611,28 +682,33 @@ int wdx_feeder_run(void *ring, const wdx_feeder_job *job) {
     unsigned char *base = (unsigned char *)ring;
     FeederSlot &S = R->slot[s];
     const size_t mr = (size_t)R->max_reads, nY = (size_t)R->n_refs, K = (size_t)R->n_events, kc = (size_t)R->n_classes;
-    float *dsig = (float *)(base + R->off_sig + (size_t)s * align_up((size_t)R->sig_floats * 4, 4096));
+    unsigned char *dsig = base + R->off_sig + (size_t)s * R->sig_slot_bytes;
+    float *cal = (float *)(dsig + R->sig_floats * 4);   // int16 rings: offset | scale | row_win
     int64_t *roff = (int64_t *)(base + R->off_roff + (size_t)s * align_up((mr + 1) * 8, 4096));
     auto i32_of = [&](uint64_t off) { return (int32_t *)(base + off + (size_t)s * align_up(mr * 4, 4096)); };
     int32_t *rlen = i32_of(R->off_rlen), *ras = i32_of(R->off_as), *rae = i32_of(R->off_ae);
+    int32_t *rwin = is_adc ? (int32_t *)(cal + 2 * mr) : nullptr;
+    const size_t esz = is_adc ? 2 : 4;
+    const unsigned char *src = is_adc ? (const unsigned char *)job.adc : (const unsigned char *)job.sig;
     int64_t acc = 0;
     for (int64_t r = 0; r < n_reads; ++r) {
-        int64_t s0 = (int64_t)job->a_start[r] - pad, e0 = (int64_t)job->a_end[r] + pad;
-        if (s0 < 0) s0 = 0;
-        if (e0 > stride) e0 = stride;
-        if (e0 < s0 || (job->ok && !job->ok[r])) e0 = s0;
-        s0 &= ~(int64_t)3;
+        const Win w = window(r);
         roff[r] = acc;
-        rlen[r] = (int32_t)(e0 - s0);
-        ras[r] = job->a_start[r] - (int32_t)s0;
-        rae[r] = job->a_end[r] - (int32_t)s0;
-        if (e0 > s0) memcpy(dsig + acc, job->sig + r * stride + s0, (size_t)(e0 - s0) * 4);
-        acc += ((e0 - s0) + 3) & ~(int64_t)3;
+        rlen[r] = (int32_t)w.valid;
+        if (rwin) rwin[r] = (int32_t)w.len;
+        ras[r] = job.a_start[r] - (int32_t)w.s0;
+        rae[r] = job.a_end[r] - (int32_t)w.s0;
+        if (w.valid > 0) memcpy(dsig + (size_t)acc * esz, src + (size_t)(r * stride + w.s0) * esz, (size_t)w.valid * esz);
+        acc += (w.valid + al) & ~al;
     }
     roff[n_reads] = acc;
-    if (job->ok) memcpy(base + R->off_ok + (size_t)s * align_up(mr, 4096), job->ok, (size_t)n_reads);
+    if (is_adc) {
+        memcpy(cal, job.offset, (size_t)n_reads * 4);
+        memcpy(cal + mr, job.scale, (size_t)n_reads * 4);
+    }
+    if (job.ok) memcpy(base + R->off_ok + (size_t)s * align_up(mr, 4096), job.ok, (size_t)n_reads);
     S.n_reads = n_reads;
-    S.has_ok = job->ok ? 1u : 0u;
+    S.has_ok = job.ok ? 1u : 0u;
     S.want = want;
     S.mode = kModeRows;
     S.rc = WDX_SUCCESS;
@@ -641,23 +717,70 @@ int wdx_feeder_run(void *ring, const wdx_feeder_job *job) {
     int rc = S.rc;
     if (rc == WDX_SUCCESS) {
         const size_t n = (size_t)n_reads;
-        memcpy(job->status, i32_of(R->off_status), n * 4);
-        if (job->call) memcpy(job->call, i32_of(R->off_call), n * 4);
+        memcpy(O.status, i32_of(R->off_status), n * 4);
+        if (O.call) memcpy(O.call, i32_of(R->off_call), n * 4);
         if ((want & WDX_WANT_DIST) && nY)
-            memcpy(job->dist, base + R->off_dist + (size_t)s * align_up(mr * nY * 4, 4096), n * nY * 4);
-        if (want & WDX_WANT_FPT) memcpy(job->fpt, base + R->off_fpt + (size_t)s * align_up(mr * K * 8, 4096), n * K * 8);
-        if (want & WDX_WANT_DWELL) memcpy(job->dwell, base + R->off_dwell + (size_t)s * align_up(mr * K * 8, 4096), n * K * 8);
-        if (want & WDX_WANT_STATS) memcpy(job->stats, base + R->off_stats + (size_t)s * align_up(mr * 48, 4096), n * 48);
+            memcpy(O.dist, base + R->off_dist + (size_t)s * align_up(mr * nY * 4, 4096), n * nY * 4);
+        if (want & WDX_WANT_FPT) memcpy(O.fpt, base + R->off_fpt + (size_t)s * align_up(mr * K * 8, 4096), n * K * 8);
+        if (want & WDX_WANT_DWELL) memcpy(O.dwell, base + R->off_dwell + (size_t)s * align_up(mr * K * 8, 4096), n * K * 8);
+        if (want & WDX_WANT_STATS) memcpy(O.stats, base + R->off_stats + (size_t)s * align_up(mr * 48, 4096), n * 48);
         if (want & WDX_WANT_SVM) {
-            memcpy(job->prob, base + R->off_prob + (size_t)s * align_up(mr * kc * 8, 4096), n * kc * 8);
-            memcpy(job->pred, i32_of(R->off_pred), n * 4);
-            memcpy(job->conf, base + R->off_conf + (size_t)s * align_up(mr * 8, 4096), n * 8);
+            memcpy(O.prob, base + R->off_prob + (size_t)s * align_up(mr * kc * 8, 4096), n * kc * 8);
+            memcpy(O.pred, i32_of(R->off_pred), n * 4);
+            memcpy(O.conf, base + R->off_conf + (size_t)s * align_up(mr * 8, 4096), n * 8);
         }
     } else {
         set_error("feeder: %s", S.err);
     }
     release_slot(R, s);
     return rc;
+}
+
+}  // namespace wdx
+
+extern "C" {
+
+int wdx_feeder_run(void *ring, const wdx_feeder_job *job) {
+    FeederRing *R = (FeederRing *)ring;
+    if (int rc = ring_check(R)) return rc;
+    if (!job) {
+        set_error("feeder_run: null job");
+        return WDX_ERR_INVALID;
+    }
+    WorkerRows w;
+    w.sig = job->sig;
+    w.n_reads = job->n_reads;
+    w.stride = job->stride;
+    w.a_start = job->a_start;
+    w.a_end = job->a_end;
+    w.ok = job->ok;
+    w.want = job->want;
+    w.out = wdx_minibatch_out{job->status, job->call, job->dist, job->fpt, job->dwell, job->stats, job->prob, job->pred, job->conf};
+    return feeder_run_rows(R, ring, "feeder_run", w);
+}
+
+// The same for a ring of int16 samples: the raw ADC windows and the reads' offset / scale go into the slot
+int wdx_feeder_run_adc(void *ring, const wdx_feeder_job_adc *job) {
+    FeederRing *R = (FeederRing *)ring;
+    if (int rc = ring_check(R)) return rc;
+    if (!job) {
+        set_error("feeder_run_adc: null job");
+        return WDX_ERR_INVALID;
+    }
+    WorkerRows w;
+    w.is_adc = true;
+    w.adc = job->adc;
+    w.n_reads = job->n_reads;
+    w.stride = job->stride;
+    w.row_len = job->row_len;
+    w.offset = job->offset;
+    w.scale = job->scale;
+    w.a_start = job->a_start;
+    w.a_end = job->a_end;
+    w.ok = job->ok;
+    w.want = job->want;
+    w.out = wdx_minibatch_out{job->status, job->call, job->dist, job->fpt, job->dwell, job->stats, job->prob, job->pred, job->conf};
+    return feeder_run_rows(R, ring, "feeder_run_adc", w);
 }
 
 // wdx_demux_batch's arguments and outputs (bit-identical results) through the feeder
@@ -707,7 +830,7 @@ int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int
         int s = -1;
         if (int rc = claim_slot(R, s)) return rc;
         FeederSlot &S = R->slot[s];
-        memcpy(base + R->off_sig + (size_t)s * align_up((size_t)R->sig_floats * 4, 4096), X + r0 * (int64_t)K, (size_t)m * K * 8);
+        memcpy(base + R->off_sig + (size_t)s * R->sig_slot_bytes, X + r0 * (int64_t)K, (size_t)m * K * 8);
         S.n_reads = m;
         S.has_ok = 0u;
         S.want = WDX_WANT_SVM;

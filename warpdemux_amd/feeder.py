@@ -79,10 +79,17 @@ class Feeder:
     inherited object.  `max_reads` x `stride` = the largest minibatch a slot holds (file_proc's 1000 x sig_preload_size).
 
     Either `refs` (+ `window`, `penalty`): nearest-reference calls only -- or `model`, a `warpdemux_amd.models.DTW_SVM`
-    (`DTW_SVM.from_reference(loaded_model)`): its `_X` are the references and `predict` / `detect_and_predict` are served."""
+    (`DTW_SVM.from_reference(loaded_model)`): its `_X` are the references and `predict` / `detect_and_predict` are served.
+
+    ``adc=True``: the ring's slots hold int16 ADC samples and the workers call `fingerprint_batch_adc` /
+    `demux_batch_adc` / `detect_and_predict_adc` with the raw samples and ``row_len`` / ``offset`` / ``scale`` per read --
+    half the bytes in the worker's copy, in the ring and over the bus; the device calibrates by the formula of
+    `sig_proc.calibrate_adc`, and the results are those of the float32 calls on its rows, bit for bit.  The float32 calls
+    are refused on such a ring, and the ``*_adc`` calls on a float32 ring."""
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, max_reads: int = 1000,
-                 stride: int = 10000, n_slots: int = 16, device: int = 0, start_timeout: float = 120.0, model=None):
+                 stride: int = 10000, n_slots: int = 16, device: int = 0, start_timeout: float = 120.0, model=None,
+                 adc: bool = False):
         if model is not None:
             if refs is not None:
                 raise ValueError("pass either refs or model (whose _X are the references)")
@@ -103,7 +110,10 @@ class Feeder:
         self.nY, self.K = (int(v) for v in refs.shape)
         self.max_reads, self.stride, self.n_slots = int(max_reads), int(stride), int(n_slots)
         self.L = _lib.load()
-        geo = _lib.FeederGeometryC(self.n_slots, self.K, self.n_classes, 0, self.max_reads, self.stride, self.nY)
+        self.adc = bool(adc)
+        geo = _lib.FeederGeometryC(self.n_slots, self.K, self.n_classes,
+                                   _lib.FEEDER_SAMPLES_INT16 if self.adc else _lib.FEEDER_SAMPLES_FLOAT32, self.max_reads,
+                                   self.stride, self.nY)
         nbytes = int(self.L.wdx_feeder_ring_bytes(C.byref(geo)))
         if nbytes == 0:
             raise ValueError("bad ring geometry")
@@ -141,7 +151,14 @@ class Feeder:
         ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
         if want & _lib.WANT_SVM and self.model is None:
             raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
-        out = {
+        out = self._outputs(n, want)
+        job = _lib.FeederJobC(_lib.addr(sig), n, stride, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok), int(want), 0,
+                              *[_lib.addr(out[k]) for k in ("status", "call", "dist", "fpt", "dwell", "stats", "prob", "pred", "conf")])
+        _lib.check(self.L.wdx_feeder_run(C.c_void_p(self._base), C.byref(job)))
+        return out
+
+    def _outputs(self, n: int, want: int) -> dict:
+        return {
             "status": np.empty(n, dtype=np.int32),
             "call": np.empty(n, dtype=np.int32),
             "dist": np.empty((n, self.nY), dtype=np.float32) if want & _lib.WANT_DIST else None,
@@ -152,10 +169,52 @@ class Feeder:
             "pred": np.empty(n, dtype=np.int32) if want & _lib.WANT_SVM else None,
             "conf": np.empty(n, dtype=np.float64) if want & _lib.WANT_SVM else None,
         }
-        job = _lib.FeederJobC(_lib.addr(sig), n, stride, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok), int(want), 0,
-                              *[_lib.addr(out[k]) for k in ("status", "call", "dist", "fpt", "dwell", "stats", "prob", "pred", "conf")])
-        _lib.check(self.L.wdx_feeder_run(C.c_void_p(self._base), C.byref(job)))
+
+    def _run_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success, want: int):
+        """One int16 minibatch through wdx_feeder_run_adc.  Shapes and dtypes of EVERY array, `success` included, are
+        checked before anything is passed by address; `adc` must be C-contiguous int16 (it is never copied here)."""
+        a = adc if isinstance(adc, np.ndarray) else np.asarray(adc)
+        if a.ndim != 2 or a.dtype != np.int16 or not a.flags.c_contiguous:
+            raise ValueError("adc must be a C-contiguous 2-D (n_reads, stride) int16 array")
+        n, stride = a.shape
+        r_len = np.ascontiguousarray(row_len, dtype=np.int32)
+        off = np.ascontiguousarray(offset, dtype=np.float32)
+        sc = np.ascontiguousarray(scale, dtype=np.float32)
+        a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
+        a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
+        ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
+        for name, v in (("row_len", r_len), ("offset", off), ("scale", sc), ("adapter_start", a_s), ("adapter_end", a_e),
+                        ("success", ok)):
+            if v is not None and v.shape != (n,):
+                raise ValueError(f"{name} must have one entry per read")
+        if want & _lib.WANT_SVM and self.model is None:
+            raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
+        out = self._outputs(n, want)
+        job = _lib.FeederJobAdcC(_lib.addr(a), n, stride, _lib.addr(r_len), _lib.addr(off), _lib.addr(sc), _lib.addr(a_s),
+                                 _lib.addr(a_e), _lib.addr(ok), int(want), 0,
+                                 *[_lib.addr(out[k]) for k in ("status", "call", "dist", "fpt", "dwell", "stats", "prob", "pred", "conf")])
+        _lib.check(self.L.wdx_feeder_run_adc(C.c_void_p(self._base), C.byref(job)))
         return out
+
+    def demux_batch_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None,
+                        want_dist: bool = True) -> DemuxBatch:
+        """`demux_batch` for an int16 ADC minibatch (a ``Feeder(adc=True)``)."""
+        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success, _lib.WANT_DIST if want_dist else 0)
+        return DemuxBatch(o["status"], o["call"], o["dist"], None)
+
+    def fingerprint_batch_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None) -> FingerprintBatch:
+        """`fingerprint_batch` for an int16 ADC minibatch (a ``Feeder(adc=True)``)."""
+        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success,
+                          _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS)
+        return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"])
+
+    def detect_and_predict_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None,
+                               return_df: bool = False):
+        """`detect_and_predict` for an int16 ADC minibatch (a ``Feeder(adc=True)``): the reference worker's whole
+        minibatch from the raw samples the pod5 file holds."""
+        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success,
+                          _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | _lib.WANT_SVM)
+        return self._fpt_and_predictions(o, return_df)
 
     def demux_batch(self, signals, adapter_start, adapter_end, success=None, want_dist: bool = True) -> DemuxBatch:
         """Status, nearest-reference call and (optionally) the distance rows -- `sig_proc.demux_batch`'s result, bit for
@@ -176,6 +235,9 @@ class Feeder:
         like the reference, which only ever shows the model the successful fingerprints."""
         o = self._run(signals, adapter_start, adapter_end, success,
                       _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | _lib.WANT_SVM)
+        return self._fpt_and_predictions(o, return_df)
+
+    def _fpt_and_predictions(self, o: dict, return_df: bool):
         fb = FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"])
         okr = o["status"] == 0
         y_pred, y_prob, conf = o["pred"][okr].astype(np.int64), o["prob"][okr], o["conf"][okr]

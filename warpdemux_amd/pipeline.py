@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .sig_proc import DemuxBatch, SegParams
+from .sig_proc import DemuxBatch, SegParams, adc_minibatch
 
 
 def pinned_empty(shape, dtype=np.float32, device: Optional[int] = None) -> np.ndarray:
@@ -106,6 +106,21 @@ class MinibatchPipeline:
                                            int(want_dist)))
         self._held[slot] = (sig, a_s, a_e, ok, n, bool(want_dist), bool(want_fpt))
 
+    def submit_adc(self, slot: int, adc, row_len, offset, scale, adapter_start, adapter_end, success=None, want_dist=True,
+                   want_fpt=False, row_off=None, row_win=None):
+        """`submit` for an int16 ADC minibatch (wdx_demux_submit_adc): ``adc`` (n_reads, stride) int16 -- fill a
+        ``pinned_empty(shape, np.int16)`` buffer and only the adapter windows cross the bus, 2 bytes per sample --
+        with ``row_len`` / ``offset`` / ``scale`` per read; the device calibrates (`sig_proc.calibrate_adc` states the
+        formula).  With ``row_off`` the rows are packed by the caller (`sig_proc.adc_minibatch`).  `wait(slot)` returns
+        what `submit` + `wait` return on the calibrated rows, bit for bit.  Nothing passed here may be modified before
+        `wait(slot)`."""
+        if not 0 <= int(slot) < self.N_SLOTS:
+            raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
+        desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success, row_off, row_win)
+        want = (_lib.WANT_FPT if want_fpt else 0) | (_lib.WANT_DIST if want_dist else 0)
+        _lib.check(self.L.wdx_demux_submit_adc(self.ctx.handle, int(slot), C.byref(desc), C.byref(self._pc), self.nY, want))
+        self._held[slot] = (kept, None, None, None, n, bool(want_dist), bool(want_fpt))
+
     def wait(self, slot: int) -> DemuxBatch:
         held = self._held[slot] if 0 <= int(slot) < self.N_SLOTS else None
         if held is None:
@@ -128,7 +143,8 @@ class MinibatchPipeline:
     def run(self, minibatches):
         """Drive an iterable of (signals, adapter_start, adapter_end[, success]) through both slots; yields one
         DemuxBatch per minibatch, in order.  The iterable is advanced (= the caller's fill runs) while the previous
-        minibatch is in flight.
+        minibatch is in flight.  A tuple whose first entry is an int16 array is an ADC minibatch: (adc, row_len, offset,
+        scale, adapter_start, adapter_end[, success, ...]), the arguments of `submit_adc`.
 
         Order per minibatch k: wait(k - 2), THEN next(iterable), then submit(k) -- so a generator that refills two
         rotating page-locked buffers never writes into a buffer whose submit has not been waited
@@ -145,7 +161,10 @@ class MinibatchPipeline:
                 mb = next(it)
             except StopIteration:
                 break
-            self.submit(slot, *mb)
+            if isinstance(mb[0], np.ndarray) and mb[0].dtype == np.int16:
+                self.submit_adc(slot, *mb)
+            else:
+                self.submit(slot, *mb)
             pending.append(slot)
             k += 1
         for slot in pending:

@@ -247,6 +247,99 @@ def fingerprint_batch(signals, adapter_start, adapter_end, params: SegParams, su
     return FingerprintBatch(fpt, dwell, stats, status)
 
 
+def calibrate_adc(adc, row_len, offset, scale, stride=None) -> np.ndarray:
+    """THE CONTRACT of the int16 way in, in NumPy: the float32 minibatch the ``*_adc`` entry points stand for.
+
+    Row r holds ``scale[r] * (float32(adc[r, i]) + offset[r])`` for ``i < row_len[r]`` -- a float32 add, then a float32
+    multiply: two roundings, never one fused operation -- and NaN from there to ``stride`` (the NaN tail of
+    file_proc.py:255-260).  Every ``*_adc`` call returns, bit for bit, what its float32 counterpart returns on this array.
+    A reader that calibrates by another formula (another order of operations, float64 arithmetic) is not served by the
+    int16 path: compare its rows with this function's first."""
+    adc = np.asarray(adc)
+    if adc.ndim != 2 or adc.dtype != np.int16:
+        raise ValueError("adc must be a 2-D (n_reads, stride) int16 array")
+    n, width = adc.shape
+    stride = width if stride is None else int(stride)
+    if stride < width:
+        raise ValueError("stride must not be smaller than the rows of adc")
+    row_len = np.asarray(row_len, dtype=np.int64)
+    off = np.asarray(offset, dtype=np.float32)
+    sc = np.asarray(scale, dtype=np.float32)
+    if row_len.shape != (n,) or off.shape != (n,) or sc.shape != (n,):
+        raise ValueError("row_len, offset and scale must have one entry per read")
+    if n and (row_len.min() < 0 or row_len.max() > width):
+        raise ValueError("row_len must be within 0 .. the rows of adc")
+    out = np.full((n, stride), np.nan, dtype=np.float32)
+    summed = adc.astype(np.float32) + off[:, None]     # float32 + float32 -> float32, rounded once
+    np.multiply(summed, sc[:, None], out=summed)       # ... and once more
+    live = np.arange(width)[None, :] < row_len[:, None]
+    out[:, :width][live] = summed[live]
+    return out
+
+
+def adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success=None, row_off=None, row_win=None):
+    """Check an int16 minibatch before anything of it is passed by address -- shapes and dtypes of every array,
+    ``success`` included -- and lay it out as `_lib.MinibatchAdcInC`.  Returns ``(descriptor, n_reads, kept)``; `kept`
+    holds the arrays the descriptor points into.  ``adc`` itself is never copied or converted: an array that is not
+    C-contiguous int16 is refused (the point of this path is the bytes that do not move).
+
+    ``row_off`` (int64[n + 1], multiples of 8): `adc` is 1-D and holds packed rows, row r = its ``row_len[r]`` samples at
+    ``adc[row_off[r]:]``, adapter bounds relative to the row; ``row_win`` (optional) = samples of the float32 row it
+    stands for, the surplus over ``row_len`` being NaN tail."""
+    a = adc if isinstance(adc, np.ndarray) else np.asarray(adc)
+    if a.dtype != np.int16 or not a.flags.c_contiguous:
+        raise ValueError("adc must be a C-contiguous int16 array (it is passed by address, never converted)")
+    r_len = np.ascontiguousarray(row_len, dtype=np.int32)
+    n = int(r_len.shape[0]) if r_len.ndim == 1 else -1
+    if row_off is None:
+        if a.ndim != 2 or a.shape[0] != n:
+            raise ValueError("adc must be a 2-D (n_reads, stride) array with one row_len per row")
+        stride = int(a.shape[1])
+        if row_win is not None:
+            raise ValueError("row_win belongs to packed rows (row_off)")
+        r_off = r_win = None
+    else:
+        r_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        if a.ndim != 1 or n < 0 or r_off.shape != (n + 1,):
+            raise ValueError("packed rows: adc must be 1-D, row_off int64[n_reads + 1]")
+        if n and (r_off[0] < 0 or r_off[-1] > a.shape[0] or (np.diff(r_off) < 0).any()):
+            raise ValueError("packed rows: row_off must ascend within adc")
+        stride = 0
+        r_win = None if row_win is None else np.ascontiguousarray(row_win, dtype=np.int32)
+        if r_win is not None and r_win.shape != (n,):
+            raise ValueError("row_win must have one entry per read")
+    off = np.ascontiguousarray(offset, dtype=np.float32)
+    sc = np.ascontiguousarray(scale, dtype=np.float32)
+    a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
+    a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
+    ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
+    for name, v in (("offset", off), ("scale", sc), ("adapter_start", a_s), ("adapter_end", a_e), ("success", ok)):
+        if v is not None and v.shape != (n,):
+            raise ValueError(f"{name} must have one entry per read")
+    kept = (a, r_len, off, sc, r_off, r_win, a_s, a_e, ok)
+    desc = _lib.MinibatchAdcInC(_lib.addr(a), n, stride, _lib.addr(r_len), _lib.addr(off), _lib.addr(sc), _lib.addr(r_off),
+                                _lib.addr(r_win), _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok))
+    return desc, n, kept
+
+
+def fingerprint_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, params: SegParams, success=None,
+                          device=None) -> FingerprintBatch:
+    """`fingerprint_batch` for a (n_reads, stride) int16 ADC minibatch: 2 bytes per sample over the bus, calibrated on the
+    device.  Bit-identical to ``fingerprint_batch(calibrate_adc(adc, row_len, offset, scale), ...)``."""
+    desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success)
+    pc = params.to_c()
+    K = params.barcode_num_events
+    fpt = np.empty((n, K), dtype=np.float64)
+    dwell = np.empty((n, K), dtype=np.int64)
+    stats = np.empty((n, 6), dtype=np.float64)
+    status = np.empty(n, dtype=np.int32)
+    ctx = _lib.default_context(device)
+    _lib.check(_lib.load().wdx_fingerprint_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), _lib.ptr(fpt), _lib.ptr(dwell),
+                                                     _lib.ptr(stats), _lib.ptr(status)))
+    del kept
+    return FingerprintBatch(fpt, dwell, stats, status)
+
+
 def fingerprint_refine_batch(signals, adapter_start, adapter_end, params: SegParams, refine: RefineParams, success=None,
                              device=None) -> FingerprintBatch:
     """Consensus-refinement branch on a (n_reads, stride) float32 minibatch; K = refine.barcode_keep_events."""
@@ -353,6 +446,28 @@ def demux_batch(signals, adapter_start, adapter_end, params: SegParams, success=
     _lib.check(_lib.load().wdx_demux_batch(
         ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc),
         n_held, _lib.ptr(fpt), _lib.ptr(dist), _lib.ptr(call), _lib.ptr(status)))
+    return DemuxBatch(status, call, dist, fpt)
+
+
+def demux_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, params: SegParams, success=None, want_dist=True,
+                    want_fpt=False, device=None) -> DemuxBatch:
+    """`demux_batch` for a (n_reads, stride) int16 ADC minibatch (wdx_demux_batch_adc); bit-identical to `demux_batch` on
+    ``calibrate_adc(adc, row_len, offset, scale)``."""
+    desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success)
+    pc = params.to_c()
+    ctx = _lib.default_context(device)
+    held = getattr(ctx, "_demux_refs", None)
+    if held is None:
+        raise _lib.WdxError("demux_batch_adc: no reference set -- call set_references() first")
+    n_held = int(held[0].shape[0])
+    dist = np.empty((n, n_held), dtype=np.float32) if want_dist else None
+    fpt = np.empty((n, params.barcode_num_events), dtype=np.float64) if want_fpt else None
+    call = np.empty(n, dtype=np.int32)
+    status = np.empty(n, dtype=np.int32)
+    _ensure_references(ctx)
+    _lib.check(_lib.load().wdx_demux_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), n_held, _lib.ptr(fpt), _lib.ptr(dist),
+                                               _lib.ptr(call), _lib.ptr(status)))
+    del kept
     return DemuxBatch(status, call, dist, fpt)
 
 
