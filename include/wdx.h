@@ -362,6 +362,39 @@ int wdx_demux_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, const wdx_
 int wdx_calibrate_adc_dev(wdx_ctx *ctx, const int16_t *d_adc, const int64_t *d_row_off, const int32_t *d_row_len,
                           int64_t stride, int64_t n_reads, const float *d_offset, const float *d_scale, float *d_out,
                           void *stream);
+/* ---- consensus refinement (wdx_refine_params) through the pipelined minibatches ----------------------------------
+ * The tRNA models' branch on the same slots, for float32 rows (`in`) or int16 ADC rows (`in_adc`): exactly one of the
+ * two is non-NULL, and all three ways in of either format work as above.  K = rp->barcode_keep_events for fpt, dwell and
+ * the DTW (p->barcode_num_events is ignored, as in wdx_fingerprint_refine_batch); rp and its query are HOST memory and
+ * are copied before the call returns, so slots in flight may carry different rp.
+ *   n_refs > 0    DTW against the resident references: K must equal their length and n_refs the resident nY
+ *                 (WDX_ERR_INVALID otherwise); WDX_WANT_SVM as in wdx_demux_submit_ex -- a read whose status is not 0,
+ *                 WDX_READ_FAIL_CONSENSUS included, gets pred -1 and NaN prob / conf
+ *   n_refs == 0   fingerprint only: no resident references are needed, nothing behind the fingerprint stage runs, call
+ *                 is -1 for every read; WDX_WANT_DIST / WDX_WANT_SVM are WDX_ERR_INVALID
+ * Limits and their codes are those of wdx_fingerprint_refine_batch (n_query 1..96, num_events <= 127).
+ * WDX_WANT_REFINE_IDX asks for refine_idx (n, 3) int32 -- the numbers wdx_fingerprint_refine_batch returns for the same
+ * reads, whichever way the rows came in: sig_barcode_start counts from the first sample of the read's adapter window
+ * (max(0, a_start - padding) of ITS row), which no packing, cropping or decoding moves.
+ * wdx_demux_wait_refine is wdx_demux_wait_ex plus refine_idx: required when the slot asked for it, WDX_ERR_INVALID (the
+ * slot stays busy) when it did not; wdx_demux_wait_ex completes a refine slot that did not ask for refine_idx and refuses
+ * one that did.  Bit-identical to wdx_fingerprint_refine_batch [+ wdx_dtw_matrix + wdx_dtw_svm_predict] on the same rows. */
+#define WDX_WANT_REFINE_IDX 0x20u /* refine_idx (n, 3) int32, as wdx_fingerprint_refine_batch */
+int wdx_demux_submit_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, const wdx_minibatch_adc_in *in_adc,
+                            const wdx_seg_params *p, const wdx_refine_params *rp, int64_t n_refs, uint32_t want);
+int wdx_demux_wait_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out, int32_t *refine_idx);
+/* wdx_demux_dev with the refinement branch in front: refine fingerprint (K = rp->barcode_keep_events = the reference
+ * length) -> DTW -> argmin -> histogram, enqueued on `stream`; d_counts slot nY counts every read whose status is not 0.
+ * d_refine_idx (n_reads, 3) int32 DEVICE, nullable.  rp and its query are HOST memory (copied before the call returns).
+ * d_work: wdx_demux_refine_workspace_bytes(n_reads, K) bytes = wdx_demux_workspace_bytes plus the refinement kernels'
+ * hand-over records (1 632 bytes per read). */
+int64_t wdx_demux_refine_workspace_bytes(int64_t n_reads, int32_t barcode_keep_events);
+int wdx_demux_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len,
+                         int64_t stride, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                         const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                         const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell, double *d_stats,
+                         int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts,
+                         void *d_work, void *stream);
 /* Page-locked host memory for minibatch buffers the caller fills (what file_proc.py:244-260 allocates with
  * np.full): the GPU reads it directly.  Needs no context; free with wdx_host_free. */
 int wdx_host_alloc(size_t bytes, void **out);
@@ -463,6 +496,19 @@ int wdx_feeder_ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, 
 int wdx_feeder_serve(wdx_ctx *ctx, void *ring);
 int wdx_feeder_run(void *ring, const wdx_feeder_job *job);
 int wdx_feeder_run_adc(void *ring, const wdx_feeder_job_adc *job);
+/* A ring whose minibatches take the consensus-refinement branch (tRNA models).  wdx_feeder_ring_bytes_refine /
+ * wdx_feeder_ring_init_refine size and lay it out: the layout of wdx_feeder_ring_init, rp and its query (<= 96 doubles)
+ * kept behind the ring header, and a refine_idx region per slot; n_events, when not 0, must equal
+ * rp->barcode_keep_events; g->n_refs == 0 makes a fingerprint-only ring (the serving context needs no references; only
+ * WDX_WANT_FPT / _DWELL / _STATS / _REFINE_IDX are served).  A bad rp is refused with the codes of
+ * wdx_fingerprint_refine_batch.  A ring made by wdx_feeder_ring_init keeps its byte layout and behaviour.
+ * wdx_feeder_serve, wdx_feeder_run and wdx_feeder_run_adc see the ring's kind and do the rest; wdx_feeder_run_refine is
+ * either of the two run calls (exactly one job is non-NULL) plus refine_idx (n_reads, 3) int32, which
+ * WDX_WANT_REFINE_IDX in the job's `want` asks for -- on a refine ring only, WDX_ERR_INVALID on another. */
+size_t wdx_feeder_ring_bytes_refine(const wdx_feeder_geometry *g);
+int wdx_feeder_ring_init_refine(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p,
+                                const wdx_refine_params *rp);
+int wdx_feeder_run_refine(void *ring, const wdx_feeder_job *job, const wdx_feeder_job_adc *job_adc, int32_t *refine_idx);
 int wdx_feeder_demux(void *ring, const float *sig, int64_t n_reads, int64_t stride, const int32_t *a_start,
                      const int32_t *a_end, const uint8_t *ok, int64_t n_refs, float *dist, int32_t *call, int32_t *status);
 int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int32_t *pred, double *conf);

@@ -21,6 +21,12 @@ modes   sync   sig_proc.demux_batch on a pageable minibatch (what an unmodified 
 --refill       every iteration first copies the minibatch from a pageable array into the buffer it submits (the
                worker's own fill, which the reference does into its pageable array too)
 
+--refine       the tRNA flow: every minibatch takes the consensus-refinement branch (the tRNA parameter set and the consensus
+               of fixture g8) and only the ReadResult arrays come back -- fingerprints, dwell times, statistics, refine_idx;
+               the classifier of those models runs on the host.  sync = sig_proc.fingerprint_refine_batch on each worker's
+               own context (all there was before the refine minibatch paths), pipe = MinibatchPipeline(None, refine=...),
+               feeder = Feeder(refine=...) without references; pipe and feeder also take --adc
+
 The parent never touches the GPU; every child creates its context after the fork.  Each worker checks its results
 against the CPU oracle once (outside the timed loop).  Prints one JSON line.
 """
@@ -48,6 +54,170 @@ def quantise(mb, wid):
     row_len = np.isfinite(mb).sum(axis=1).astype(np.int32)
     q = np.rint(np.nan_to_num(mb.astype(np.float64)) / scale[:, None].astype(np.float64) - offset[:, None].astype(np.float64))
     return np.clip(q, -32768, 32767).astype(np.int16), row_len, offset, scale
+
+
+REFINE_SEG = dict(min_obs_per_base=9, running_stat_width=18, num_events=120)
+REFINE_KEEP = 25
+
+
+def refine_setup():
+    """(SegParams, RefineParams) of the tRNA flow"""
+    import numpy as np
+
+    from warpdemux_amd import sig_proc
+
+    with np.load(os.path.join(ROOT, "tests", "golden", "g8_refine.npz")) as g:
+        query = np.ascontiguousarray(g["consensus"], dtype=np.float64)
+    return (sig_proc.SegParams(barcode_num_events=REFINE_KEEP, **REFINE_SEG),
+            sig_proc.RefineParams(query=query, barcode_segm_events=25, barcode_keep_events=REFINE_KEEP))
+
+
+def refine_minibatch(wid, query, jitter):
+    """1000 reads that carry the consensus between a random lead and a 30-event barcode, 12 .. 59 samples per event"""
+    import numpy as np
+
+    rng = np.random.default_rng(7000 + wid)
+    mb = np.full((N_READS, STRIDE), np.nan, dtype=np.float32)
+    a_s, a_e = np.empty(N_READS, dtype=np.int32), np.empty(N_READS, dtype=np.int32)
+    for i in range(N_READS):
+        lv = np.concatenate([rng.normal(0, 1, int(rng.integers(2, 34))), query if rng.random() > 0.1 else rng.normal(0, 1, query.size),
+                             rng.normal(0, 1, 30)]) * 12.0 + 85.0
+        dw = rng.integers(12, 60, lv.size)
+        x = (np.repeat(lv, dw) + rng.normal(0, 1.5, int(dw.sum()))).astype(np.float32)
+        j = int(rng.integers(0, jitter + 1))
+        x = x[:STRIDE - 200 - j]
+        mb[i, j:j + x.size] = x
+        mb[i, :j] = 85.0
+        a_s[i], a_e[i] = j + 100, j + x.size - 100
+    return mb, a_s, a_e
+
+
+def refine_parity(fb, rows, a_s, a_e, m=48):
+    """the first m reads against the CPU oracle's refinement entry"""
+    import numpy as np
+
+    from oracle import wdx_oracle as orc
+
+    hp, hr = refine_setup()
+    fpt, dwell, stats, idx, status = orc.fingerprint_refine_batch(
+        rows[:m], a_s[:m], a_e[:m], orc.SegParams(barcode_num_events=REFINE_KEEP, **REFINE_SEG),
+        orc.RefineParams(query=hr.query, barcode_segm_events=25, barcode_keep_events=REFINE_KEEP))
+    good, rep = status == 0, (status == 0) | (status == 6)
+    return bool(np.array_equal(fb.status[:m], status) and np.array_equal(fb.fpt[:m][good].view(np.uint64), fpt[good].view(np.uint64))
+                and np.array_equal(fb.dwell[:m][good], dwell[good]) and np.array_equal(fb.refine_idx[:m][rep], idx[rep])
+                and np.array_equal(fb.stats[:m][rep].view(np.uint64), stats[rep].view(np.uint64)) and good.sum() > m // 4)
+
+
+def refine_loop(wid, args, start, q, feeder=None):
+    """one worker of the --refine modes: sync (its own context, the blocking call), pipe (its own context, two slots) or
+    feeder (no context: the shared ring)"""
+    import numpy as np
+
+    from warpdemux_amd import pipeline, sig_proc
+
+    try:
+        hp, hr = refine_setup()
+        mb, a_s, a_e = refine_minibatch(wid, hr.query, args.jitter)
+        rows, cal = mb, ()
+        if args.adc:
+            mb, *cal = quantise(mb, wid)
+            rows = sig_proc.calibrate_adc(mb, *cal)
+        src = mb.copy() if args.refill else None
+        pipe = None
+        if args.mode == "pipe":
+            pipe = pipeline.MinibatchPipeline(None, params=hp, refine=hr)
+            bufs = [pipeline.pinned_empty((N_READS, STRIDE), mb.dtype) for _ in range(2)]
+            for b in bufs:
+                np.copyto(b, mb)
+            submit = (lambda s_: pipe.submit_adc(s_, bufs[s_], *cal, a_s, a_e)) if args.adc else (lambda s_: pipe.submit(s_, bufs[s_], a_s, a_e))
+            for _ in range(2):
+                submit(0)
+                fb = pipe.wait(0).fingerprints
+            start.wait()
+            t0 = time.perf_counter()
+            n, k = 0, 1
+            submit(0)
+            while time.perf_counter() - t0 < args.seconds:
+                s = k & 1
+                if src is not None:
+                    np.copyto(bufs[s], src)
+                submit(s)
+                fb = pipe.wait(s ^ 1).fingerprints
+                n += 1
+                k += 1
+            fb = pipe.wait((k - 1) & 1).fingerprints
+            n += 1
+        else:
+            if feeder is not None:
+                call = (lambda: feeder.fingerprint_batch_adc(mb, *cal, a_s, a_e)) if args.adc else (lambda: feeder.fingerprint_batch(mb, a_s, a_e))
+            else:
+                call = lambda: sig_proc.fingerprint_refine_batch(mb, a_s, a_e, hp, hr)    # noqa: E731
+            for _ in range(2):
+                fb = call()
+            start.wait()
+            t0 = time.perf_counter()
+            n = 0
+            while time.perf_counter() - t0 < args.seconds:
+                if src is not None:
+                    np.copyto(mb, src)
+                fb = call()
+                n += 1
+        dt = time.perf_counter() - t0
+        if pipe is not None:
+            pipe.close()
+        q.put({"worker": wid, "minibatches": n, "seconds": dt, "parity": refine_parity(fb, rows, a_s, a_e)})
+    except Exception as e:  # noqa: BLE001
+        try:
+            start.abort()
+        except Exception:  # noqa: BLE001
+            pass
+        q.put({"worker": wid, "error": f"{type(e).__name__}: {e}"})
+
+
+def refine_mode(args):
+    """--refine: P forked workers on the tRNA flow; the parent makes no GPU call (the feeder is created before the fork)"""
+    if args.mode not in ("sync", "pipe", "feeder") or (args.adc and args.mode == "sync"):
+        print(json.dumps({"error": "--refine takes the modes sync, pipe, feeder; --adc with pipe and feeder"}))
+        return 1
+    ctx = mp.get_context("fork")
+    feeder = None
+    if args.mode == "feeder":
+        from warpdemux_amd.feeder import Feeder
+
+        hp, hr = refine_setup()
+        feeder = Feeder(refine=hr, params=hp, max_reads=N_READS, stride=STRIDE, n_slots=args.slots, adc=args.adc)
+    start, q = ctx.Barrier(args.workers), ctx.Queue()
+    procs = [ctx.Process(target=refine_loop, args=(w, args, start, q, feeder)) for w in range(args.workers)]
+    try:
+        for p in procs:
+            p.start()
+        res = []
+        try:
+            for _ in procs:
+                res.append(q.get(timeout=600))
+        except Exception as e:  # noqa: BLE001  (queue.Empty: a child hangs)
+            res.append({"error": f"parent {type(e).__name__}: {e}"})
+        errs = [r for r in res if "error" in r]
+        for p in procs:
+            p.join(0.0 if errs else 60)
+        if errs:
+            print(json.dumps({"error": errs}))
+            return 1
+        mbs = sum(r["minibatches"] for r in res)
+        wall = max(r["seconds"] for r in res)
+        out = {"workers": args.workers, "mode": args.mode, "refine": True, "adc": bool(args.adc), "refill": bool(args.refill),
+               "start_jitter": args.jitter, "gpu_facing_processes": 1 if feeder is not None else args.workers,
+               "reads_per_s": mbs * N_READS / wall, "minibatches": mbs, "seconds": wall,
+               "ms_per_minibatch_per_worker": 1e3 * wall / (mbs / args.workers), "parity": all(r["parity"] for r in res)}
+        print(json.dumps(out))
+        return 0 if out["parity"] else 2
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+                p.join(10)
+        if feeder is not None:
+            feeder.close()
 
 
 def worker(wid, args, barrier, q):
@@ -291,7 +461,11 @@ def main():
     ap.add_argument("--adc", action="store_true", help="feed int16 ADC rows (2 bytes per sample, calibrated on the device)")
     ap.add_argument("--jitter", type=int, default=0, help="adapter_start ~ U{100 .. 100 + JITTER} per read (rows carry whole "
                     "reads, file_proc.py:244-260); 0 = every adapter starts at sample 100")
+    ap.add_argument("--refine", action="store_true", help="the tRNA flow: consensus refinement, fingerprints only (modes sync, pipe, "
+                    "feeder; --adc with pipe and feeder)")
     args = ap.parse_args()
+    if args.refine:
+        sys.exit(refine_mode(args))
     if args.mode in ("feeder", "feeder_full"):
         sys.exit(feeder_mode(args))
     ctx = mp.get_context("fork")      # the reference's start method (file_proc.py:1197)

@@ -58,6 +58,8 @@ EXPORTS = [
     "wdx_feeder_served", "wdx_feeder_stats", "wdx_feeder_alive", "wdx_feeder_selftest",
     "wdx_mlp_set_model", "wdx_mlp_predict_dev", "wdx_dtw_mlp_predict", "wdx_demux_mlp_dev",
     "wdx_demux_submit_adc", "wdx_fingerprint_batch_adc", "wdx_demux_batch_adc", "wdx_calibrate_adc_dev", "wdx_feeder_run_adc",
+    "wdx_demux_submit_refine", "wdx_demux_wait_refine", "wdx_demux_refine_workspace_bytes", "wdx_demux_refine_dev",
+    "wdx_feeder_ring_bytes_refine", "wdx_feeder_ring_init_refine", "wdx_feeder_run_refine",
 ]
 
 
@@ -158,6 +160,7 @@ class MlpModelC(C.Structure):
 
 
 WANT_FPT, WANT_DIST, WANT_DWELL, WANT_STATS, WANT_SVM = 0x01, 0x02, 0x04, 0x08, 0x10   # WDX_WANT_*
+WANT_REFINE_IDX = 0x20   # refine minibatches only (wdx_demux_submit_refine, a refine feeder ring)
 
 
 class MinibatchInC(C.Structure):
@@ -427,6 +430,22 @@ def load():
         L.wdx_calibrate_adc_dev.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp]
         L.wdx_feeder_run_adc.restype = C.c_int
         L.wdx_feeder_run_adc.argtypes = [vp, P(FeederJobAdcC)]
+        L.wdx_demux_submit_refine.restype = C.c_int
+        L.wdx_demux_submit_refine.argtypes = [vp, i32, P(MinibatchInC), P(MinibatchAdcInC), P(SegParamsC), P(RefineParamsC), i64,
+                                              C.c_uint32]
+        L.wdx_demux_wait_refine.restype = C.c_int
+        L.wdx_demux_wait_refine.argtypes = [vp, i32, P(MinibatchOutC), vp]
+        L.wdx_demux_refine_workspace_bytes.restype = i64
+        L.wdx_demux_refine_workspace_bytes.argtypes = [i64, i32]
+        L.wdx_demux_refine_dev.restype = C.c_int
+        L.wdx_demux_refine_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, P(SegParamsC), P(RefineParamsC), vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_feeder_ring_bytes_refine.restype = C.c_size_t
+        L.wdx_feeder_ring_bytes_refine.argtypes = [P(FeederGeometryC)]
+        L.wdx_feeder_ring_init_refine.restype = C.c_int
+        L.wdx_feeder_ring_init_refine.argtypes = [vp, C.c_size_t, P(FeederGeometryC), P(SegParamsC), P(RefineParamsC)]
+        L.wdx_feeder_run_refine.restype = C.c_int
+        L.wdx_feeder_run_refine.argtypes = [vp, P(FeederJobC), P(FeederJobAdcC), vp]
         _lib = L
         return L
 

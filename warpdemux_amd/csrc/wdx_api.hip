@@ -199,6 +199,45 @@ int check_ref_length(const DtwRefs &R, const wdx_seg_params &p) {
     return WDX_ERR_INVALID;
 }
 
+struct RefineDevGuard {   // frees what fill_refine_dev made (launch_fingerprint copies it into the kernels' arguments)
+    RefineDev *&r;
+    ~RefineDevGuard() { free_refine_dev(r); }
+};
+
+// The refinement branch's device state for n_reads reads on stream s, everything but the rows themselves:
+//   * the consensus comes from the host (84 doubles) and is kept resident in B->ref_buf: uploaded only when its content
+//     changes, and then synchronously after the stream has drained (no reliance on how the runtime stages pageable copies;
+//     ADVICE r3) -- so rp->query is free again when this returns;
+//   * d_idx (nullable) starts as -1 (reads that fail before the match);
+//   * the hand-over records of the fast kernels in d_ws (null: B->ref_ws) start untouched: only the state word of every
+//     record is cleared, 4 of its 1632 bytes.
+static int refine_prepare(wdx_ctx *B, const wdx_refine_params &rp, int64_t n_reads, int32_t *d_idx, void *d_ws, hipStream_t s,
+                          RefineDev **rf) {
+    int rc = WDX_SUCCESS;
+    const size_t qb = ((size_t)rp.n_query * 8 + 15) / 16 * 16;
+    {
+        const void *before = B->ref_buf.p;
+        if ((rc = B->ref_buf.ensure(qb))) return rc;
+        if (B->ref_buf.p != before) B->ref_query_host.clear();  // (a new block: nothing is resident in it)
+    }
+    if (!d_ws) {
+        const size_t wb = (size_t)fingerprint_refine_ws_bytes(n_reads);
+        if ((rc = B->ref_ws.ensure(wb ? wb : 8))) return rc;
+        d_ws = B->ref_ws.p;
+    }
+    if (B->ref_query_host.size() != (size_t)rp.n_query ||
+        memcmp(B->ref_query_host.data(), rp.query, (size_t)rp.n_query * 8) != 0) {
+        WDX_HIP_TRY(hipStreamSynchronize(s));
+        WDX_HIP_TRY(hipMemcpy(B->ref_buf.p, rp.query, (size_t)rp.n_query * 8, hipMemcpyHostToDevice));
+        B->ref_query_host.assign(rp.query, rp.query + rp.n_query);
+    }
+    if (d_idx) WDX_HIP_TRY(hipMemsetAsync(d_idx, 0xff, (size_t)n_reads * 12, s));
+    WDX_HIP_TRY(hipMemset2DAsync(d_ws, (size_t)fingerprint_refine_ws_bytes(1), 0, 4, (size_t)n_reads, s));
+    if ((rc = fill_refine_dev(rp, (const double *)B->ref_buf.p, d_idx, rf))) return rc;
+    set_refine_ws(*rf, d_ws);
+    return WDX_SUCCESS;
+}
+
 }  // namespace wdx
 
 using namespace wdx;
@@ -442,7 +481,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
                       &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf,
-                      &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf})
+                      &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf, &ctx->mb_ridx})
         b->release();
     ctx->pin_in.release();
     ctx->pin_out.release();
@@ -621,32 +660,9 @@ int wdx_fingerprint_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    const size_t qb = ((size_t)rp->n_query * 8 + 15) / 16 * 16;
-    {
-        const void *before = ctx->ref_buf.p;
-        if ((rc = ctx->ref_buf.ensure(qb))) return rc;
-        if (ctx->ref_buf.p != before) ctx->ref_query_host.clear();  // (a new block: nothing is resident in it)
-    }
-    const size_t wb = (size_t)fingerprint_refine_ws_bytes(n_reads);
-    if ((rc = ctx->ref_ws.ensure(wb ? wb : 8))) return rc;
-    // the consensus comes from the host (84 doubles) and is kept resident: uploaded only when its content changes, and
-    // then synchronously after the stream has drained (no reliance on how the runtime stages pageable copies)
-    if (ctx->ref_query_host.size() != (size_t)rp->n_query ||
-        memcmp(ctx->ref_query_host.data(), rp->query, (size_t)rp->n_query * 8) != 0) {
-        WDX_HIP_TRY(hipStreamSynchronize(s));
-        WDX_HIP_TRY(hipMemcpy(ctx->ref_buf.p, rp->query, (size_t)rp->n_query * 8, hipMemcpyHostToDevice));
-        ctx->ref_query_host.assign(rp->query, rp->query + rp->n_query);
-    }
-    WDX_HIP_TRY(hipMemsetAsync(d_refine_idx, 0xff, (size_t)n_reads * 12, s));
-    // (only the state word of every hand-over record: 4 of its 1632 bytes)
-    WDX_HIP_TRY(hipMemset2DAsync(ctx->ref_ws.p, (size_t)fingerprint_refine_ws_bytes(1), 0, 4, (size_t)n_reads, s));
     RefineDev *rf = nullptr;
-    struct RfGuard {
-        RefineDev *&r;
-        ~RfGuard() { free_refine_dev(r); }
-    } rf_guard{rf};
-    if ((rc = fill_refine_dev(*rp, (const double *)ctx->ref_buf.p, d_refine_idx, &rf))) return rc;
-    set_refine_ws(rf, ctx->ref_ws.p);
+    RefineDevGuard rf_guard{rf};
+    if ((rc = refine_prepare(ctx, *rp, n_reads, d_refine_idx, nullptr, s, &rf))) return rc;
     const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
     return fingerprint_stage(ctx, in, pv, FpOut{d_fpt, d_dwell, d_stats, d_status}, ctx->fp_ws.p, s, rf, false);
 }
@@ -821,12 +837,19 @@ int64_t wdx_demux_workspace_bytes(int64_t n_reads, int32_t K) {
     return demux_work_layout(n_reads, K, n_reads < kRowMajorMinReads).bytes;   // (small batches: wdx_demux_dev transposes)
 }
 
-int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
-                  const int32_t *d_row_len, int64_t stride, int64_t max_len, int64_t n_reads,
-                  const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
-                  const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell, double *d_stats,
-                  int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts, void *d_work,
-                  void *stream) {
+int64_t wdx_demux_refine_workspace_bytes(int64_t n_reads, int32_t K) {
+    const int64_t base = wdx_demux_workspace_bytes(n_reads, K);
+    return base ? round_up(base, 256) + fingerprint_refine_ws_bytes(n_reads) : 0;
+}
+
+// wdx_demux_dev; with rp the fingerprint stage takes the refinement branch (wdx_demux_refine_dev: `p` carries
+// K = rp->barcode_keep_events already, the hand-over records live behind the plain call's pieces of d_work)
+static int demux_dev_body(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
+                          const int32_t *d_row_len, int64_t stride, int64_t max_len, int64_t n_reads,
+                          const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
+                          const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell,
+                          double *d_stats, int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call,
+                          int64_t *d_counts, void *d_work, void *stream) {
     WDX_ENTER(ctx);
     if (n_reads < 0 || !p ||
         (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_dist || !d_call || !d_work))) {
@@ -856,7 +879,11 @@ int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
     double *fptT = (double *)(w + W.fptT);
     uint8_t *flags = w + W.flags;
     const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    if ((rc = fingerprint_stage(ctx, in, *p, FpOut{fpt, d_dwell, d_stats, d_status}, w + W.fp_ws, s))) return rc;
+    RefineDev *rf = nullptr;
+    RefineDevGuard rf_guard{rf};
+    if (rp && (rc = refine_prepare(ctx, *rp, n_reads, d_refine_idx, w + round_up(W.bytes, 256), s, &rf))) return rc;
+    if ((rc = fingerprint_stage(ctx, in, *p, FpOut{fpt, d_dwell, d_stats, d_status}, w + W.fp_ws, s, rf, rf == nullptr)))
+        return rc;
     if (rowmajor) {
         // failed reads carry NaN fingerprints; the DTW kernel reads the row-major rows in place and flags them
         Timed t(ctx, WDX_K_DTW, s);
@@ -881,6 +908,36 @@ int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
     return launch_count_calls(d_call, d_status, n_reads, R.nY, d_counts, s);
 }
 
+int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
+                  const int32_t *d_row_len, int64_t stride, int64_t max_len, int64_t n_reads,
+                  const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
+                  const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell, double *d_stats,
+                  int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts, void *d_work,
+                  void *stream) {
+    return demux_dev_body(ctx, d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, p, nullptr,
+                          d_fpt, d_dwell, d_stats, nullptr, d_status, d_dist, d_call, d_counts, d_work, stream);
+}
+
+int wdx_demux_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len,
+                         int64_t stride, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                         const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                         const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell, double *d_stats,
+                         int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts,
+                         void *d_work, void *stream) {
+    if (!p || !rp || !rp->query) {
+        set_error("demux_refine_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (rp->n_query < 1) {
+        set_error("consensus refinement: empty query");
+        return WDX_ERR_INVALID;
+    }
+    wdx_seg_params pv = *p;
+    pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs and of the DTW
+    return demux_dev_body(ctx, d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, &pv, rp, d_fpt,
+                          d_dwell, d_stats, d_refine_idx, d_status, d_dist, d_call, d_counts, d_work, stream);
+}
+
 // Body of the fused host-buffer call.  `B` owns the stream and every workspace that is touched (the context itself
 // for wdx_demux_batch; one of its pipeline slots for wdx_demux_submit[_ex]), `R` is the resident reference set
 // (read-only device memory of the parent context), `svm` the parent's resident model when the SVM tail is asked for.
@@ -897,8 +954,10 @@ struct MbHostOut {  // host destinations of one minibatch; null = not wanted (st
     double *conf = nullptr;
 };
 
-// The float32 rows of one minibatch -> device, and the fingerprint stage on them (on B->stream).
-static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const wdx_seg_params *p, const FpOut &out) {
+// The float32 rows of one minibatch -> device, and the fingerprint stage on them (on B->stream); rf: the refinement
+// branch (its sig_barcode_start counts from the window's first sample, which none of the three ways in moves).
+static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const wdx_seg_params *p, const FpOut &out,
+                                  const RefineDev *rf) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const float *sig = in.sig;
@@ -958,7 +1017,7 @@ static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const 
         WDX_HIP_TRY(hipMemcpyAsync(d_ae, a_end, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
         if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
         const FpReads rd{(const float *)B->in0.p, d_off, d_len, 0, max_len, n_reads, d_as, d_ae, d_ok};
-        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s))) return rc;
+        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s, rf, rf == nullptr))) return rc;
     } else if (sig_dev) {
         // host images (page-locked, owned by the slot until its copy has run): off int64[n+1] | st int32[n] | len
         // int32[n] | a_start' int32[n] | a_end' int32[n]
@@ -990,7 +1049,7 @@ static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const 
         if ((rc = launch_pack_windows(sig_dev, stride, n_reads, d_off, d_st, d_len, (float *)B->in0.p, s))) return rc;
         if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
         const FpReads rd{(const float *)B->in0.p, d_off, d_len, 0, max_len, n_reads, d_as, d_ae, d_ok};
-        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s))) return rc;
+        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s, rf, rf == nullptr))) return rc;
     } else {
         const float *d_sig = (const float *)B->in0.p;
         if (col1 > col0)
@@ -1002,7 +1061,7 @@ static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const 
         if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
         const FpReads rd{d_sig, nullptr, nullptr, stride, max_len, n_reads, (const int32_t *)B->in1.p,
                          (const int32_t *)B->in2.p, d_ok};
-        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s))) return rc;
+        if ((rc = fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s, rf, rf == nullptr))) return rc;
     }
     return WDX_SUCCESS;
 }
@@ -1060,7 +1119,8 @@ static int adc_check_args(const char *who, const wdx_minibatch_adc_in *in) {
 // bus; (iii) rows the caller packed: one flat copy, then decode_adc_kernel.  Row r of the packed buffer = samples
 // [st_r, en_r) of the float32 row the read stands for, st_r rounded down to a multiple of 8 (16-byte groups of int16),
 // adapter bounds shifted by st_r: the same window, bit for bit.
-static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const wdx_seg_params *p, const FpOut &out) {
+static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const wdx_seg_params *p, const FpOut &out,
+                                const RefineDev *rf) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const int64_t n = A.n_reads, stride = A.stride;
@@ -1145,7 +1205,7 @@ static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const
     if ((rc = launch_adc_rows(rows, n, adc_dev != nullptr, s))) return rc;
     if (A.ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, A.ok, (size_t)n, hipMemcpyHostToDevice, s));
     const FpReads rd{(const float *)B->in0.p, d_dst, d_out, 0, max_len, n, d_as, d_ae, A.ok ? (const uint8_t *)B->in3.p : nullptr};
-    return fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s);
+    return fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s, rf, rf == nullptr);
 }
 // One minibatch as demux_batch_enqueue takes it: float32 rows or int16 ADC rows (exactly one is set).
 struct MbIn {
@@ -1153,9 +1213,15 @@ struct MbIn {
     const wdx_minibatch_adc_in *adc = nullptr;
     int64_t n_reads() const { return adc ? adc->n_reads : f->n_reads; }
 };
+// The refinement branch of one minibatch: p->barcode_num_events is rp->barcode_keep_events already; h_idx = the host
+// destination of refine_idx (null: not wanted)
+struct MbRefine {
+    const wdx_refine_params *rp = nullptr;
+    int32_t *h_idx = nullptr;
+};
 
 static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, const wdx_seg_params *p,
-                               const MbHostOut &H, const SvmDev *svm) {
+                               const MbHostOut &H, const SvmDev *svm, const MbRefine *rfn = nullptr) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const int64_t n_reads = in.n_reads();
@@ -1176,7 +1242,13 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, con
     int64_t *d_dwell = H.dwell ? (int64_t *)B->mb_dwell.p : nullptr;
     double *d_stats = H.stats ? (double *)B->mb_stats.p : nullptr;
     const FpOut out{(double *)B->out0.p, d_dwell, d_stats, (int32_t *)B->out3.p};
-    if ((rc = in.adc ? fingerprint_adc_rows(B, *in.adc, p, out) : fingerprint_float_rows(B, *in.f, p, out))) return rc;
+    RefineDev *rf = nullptr;
+    RefineDevGuard rf_guard{rf};
+    if (rfn) {
+        if ((rc = B->mb_ridx.ensure((size_t)n_reads * 12))) return rc;
+        if ((rc = refine_prepare(B, *rfn->rp, n_reads, (int32_t *)B->mb_ridx.p, nullptr, s, &rf))) return rc;
+    }
+    if ((rc = in.adc ? fingerprint_adc_rows(B, *in.adc, p, out, rf) : fingerprint_float_rows(B, *in.f, p, out, rf))) return rc;
     if (R.nY > 0) {
         if ((rc = dtw_dev_locked(B, (const double *)B->out0.p, n_reads, (float *)B->out1.p,
                                  (int32_t *)B->out2.p, s)))
@@ -1201,15 +1273,19 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, con
     if (H.fpt) WDX_HIP_TRY(hipMemcpyAsync(H.fpt, B->out0.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
     if (H.dwell) WDX_HIP_TRY(hipMemcpyAsync(H.dwell, d_dwell, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
     if (H.stats) WDX_HIP_TRY(hipMemcpyAsync(H.stats, d_stats, (size_t)n_reads * 48, hipMemcpyDeviceToHost, s));
+    if (rfn && rfn->h_idx) WDX_HIP_TRY(hipMemcpyAsync(rfn->h_idx, B->mb_ridx.p, (size_t)n_reads * 12, hipMemcpyDeviceToHost, s));
     return WDX_SUCCESS;
 }
 
+// need_refs = false: a fingerprint-only refine minibatch (n_refs == 0), which reads no reference set
 static int demux_check_args(wdx_ctx *ctx, const char *who, int64_t n_reads, int64_t stride, const void *sig,
-                            const int32_t *a_start, const int32_t *a_end, const wdx_seg_params *p, int64_t n_refs) {
+                            const int32_t *a_start, const int32_t *a_end, const wdx_seg_params *p, int64_t n_refs,
+                            bool need_refs = true) {
     if (n_reads < 0 || stride < 0 || !p || (n_reads > 0 && (!sig || !a_start || !a_end))) {
         set_error("%s: bad arguments", who);
         return WDX_ERR_INVALID;
     }
+    if (!need_refs) return WDX_SUCCESS;
     DtwRefs &R = ctx->refs;
     if (R.window == 0) {
         set_error("no reference set: call wdx_set_refs first");
@@ -1387,7 +1463,26 @@ int wdx_host_free(void *p) {
 }
 
 // wdx_demux_submit_ex / wdx_demux_submit_adc behind their own argument checks (the context's mutex is held)
-static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want);
+// rp: the refinement branch (p->barcode_num_events = rp->barcode_keep_events already); no_refs: fingerprint only
+static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want,
+                               const wdx_refine_params *rp = nullptr, bool no_refs = false);
+
+// packed float32 rows: offsets ascending on 16-byte boundaries, every row inside its slice
+static int packed_rows_check(const wdx_minibatch_in *in) {
+    const int64_t n_reads = in->n_reads;
+    if (n_reads > 0 && !in->row_len) {
+        set_error("demux_submit: packed rows need row_len");
+        return WDX_ERR_INVALID;
+    }
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const int64_t o0 = in->row_off[r], o1 = in->row_off[r + 1];
+        if (o0 < 0 || (o0 & 3) || o1 < o0 || in->row_len[r] < 0 || (int64_t)in->row_len[r] > o1 - o0) {
+            set_error("demux_submit: packed row %lld: offsets must ascend in multiples of 4 and hold row_len samples", (long long)r);
+            return WDX_ERR_INVALID;
+        }
+    }
+    return WDX_SUCCESS;
+}
 
 int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, const wdx_seg_params *p, int64_t n_refs,
                         uint32_t want) {
@@ -1401,22 +1496,50 @@ int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, 
     if ((rc = demux_check_args(ctx, "demux_submit", n_reads, in->row_off ? 0 : in->stride, in->sig, in->a_start, in->a_end, p,
                                n_refs)))
         return rc;
-    if (in->row_off) {  // packed rows: offsets ascending on 16-byte boundaries, every row inside its slice
-        if (n_reads > 0 && !in->row_len) {
-            set_error("demux_submit: packed rows need row_len");
-            return WDX_ERR_INVALID;
-        }
-        for (int64_t r = 0; r < n_reads; ++r) {
-            const int64_t o0 = in->row_off[r], o1 = in->row_off[r + 1];
-            if (o0 < 0 || (o0 & 3) || o1 < o0 || in->row_len[r] < 0 || (int64_t)in->row_len[r] > o1 - o0) {
-                set_error("demux_submit: packed row %lld: offsets must ascend in multiples of 4 and hold row_len samples", (long long)r);
-                return WDX_ERR_INVALID;
-            }
-        }
-    }
+    if (in->row_off && (rc = packed_rows_check(in))) return rc;
     MbIn mb;
     mb.f = in;
     return demux_submit_locked(ctx, slot, mb, p, want);
+}
+
+int wdx_demux_submit_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, const wdx_minibatch_adc_in *in_adc,
+                            const wdx_seg_params *p, const wdx_refine_params *rp, int64_t n_refs, uint32_t want) {
+    if ((in != nullptr) == (in_adc != nullptr)) {
+        set_error("demux_submit_refine: exactly one of in / in_adc must be given");
+        return WDX_ERR_INVALID;
+    }
+    if (in_adc)
+        if (int e = adc_check_args("demux_submit_refine", in_adc)) return e;
+    WDX_ENTER(ctx);
+    if (!p || !rp || !rp->query || n_refs < 0) {
+        set_error("demux_submit_refine: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (rp->n_query < 1) {
+        set_error("consensus refinement: empty query");
+        return WDX_ERR_INVALID;
+    }
+    if (rp->barcode_keep_events < 1) {
+        set_error("barcode_num_events must be >= 1");
+        return WDX_ERR_INVALID;
+    }
+    if (n_refs == 0 && (want & (WDX_WANT_DIST | WDX_WANT_SVM))) {
+        set_error("demux_submit_refine: a fingerprint-only minibatch (n_refs = 0) has no distances and no SVM tail");
+        return WDX_ERR_INVALID;
+    }
+    wdx_seg_params pv = *p;
+    pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs and of the DTW
+    std::lock_guard<std::mutex> g(ctx->mu);
+    MbIn mb;
+    mb.f = in;
+    mb.adc = in_adc;
+    const bool packed = in ? in->row_off != nullptr : in_adc->row_off != nullptr;
+    if ((rc = demux_check_args(ctx, "demux_submit_refine", mb.n_reads(), packed ? 0 : (in ? in->stride : in_adc->stride),
+                               in ? (const void *)in->sig : (const void *)in_adc->adc, in ? in->a_start : in_adc->a_start,
+                               in ? in->a_end : in_adc->a_end, &pv, n_refs, n_refs > 0)))
+        return rc;
+    if (in && in->row_off && (rc = packed_rows_check(in))) return rc;
+    return demux_submit_locked(ctx, slot, mb, &pv, want, rp, n_refs == 0);
 }
 
 int wdx_demux_submit_adc(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_adc_in *in, const wdx_seg_params *p, int64_t n_refs,
@@ -1432,7 +1555,8 @@ int wdx_demux_submit_adc(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_adc_in 
     return demux_submit_locked(ctx, slot, mb, p, want);
 }
 
-static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want) {
+static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want,
+                               const wdx_refine_params *rp, bool no_refs) {
     int rc = WDX_SUCCESS;
     const int64_t n_reads = in.n_reads();
     const bool want_svm = (want & WDX_WANT_SVM) != 0;
@@ -1457,8 +1581,9 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
     WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));
     S->knobs = ctx->knobs;
     S->timing = ctx->timing;  // (timed like the parent's own launches; wdx_kernel_time sums the slots' events)
-    S->refs = ctx->refs;  // device pointers of the parent's resident set (read-only; wdx_set_refs drains the slots)
-    const DtwRefs &R = ctx->refs;
+    const DtwRefs none{};
+    const DtwRefs &R = no_refs ? none : ctx->refs;
+    S->refs = R;  // device pointers of the parent's resident set (read-only; wdx_set_refs drains the slots)
     const int64_t K = p->barcode_num_events;
     const int64_t k = want_svm ? ctx->svm.k : 0;
     // page-locked output block of the slot, 8-byte aligned pieces:
@@ -1478,6 +1603,9 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
         S->slot_off[q] = off;
         off += (bytes[q] + 7) / 8 * 8;
     }
+    S->slot_want_ridx = rp && (want & WDX_WANT_REFINE_IDX);
+    S->slot_off_ridx = off;   // [refine_idx i32 n*3] behind the nine
+    if (S->slot_want_ridx) off += (n * 12 + 7) / 8 * 8;
     if ((rc = S->pin_out.ensure(off + 8))) return rc;
     unsigned char *ho = (unsigned char *)S->pin_out.p;
     S->slot_n = n_reads;
@@ -1501,7 +1629,10 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
     H.pred = bytes[8] ? (int32_t *)(ho + S->slot_off[8]) : nullptr;
     StreamDrain drain(S->stream);
     S->dtw_last.family = WDX_DTW_NONE;   // (a submit that dispatches no DTW leaves the parent's record as it was)
-    if ((rc = demux_batch_enqueue(S, R, in, p, H, want_svm ? &ctx->svm : nullptr))) return rc;
+    MbRefine rfn;
+    rfn.rp = rp;
+    rfn.h_idx = S->slot_want_ridx ? (int32_t *)(ho + S->slot_off_ridx) : nullptr;
+    if ((rc = demux_batch_enqueue(S, R, in, p, H, want_svm ? &ctx->svm : nullptr, rp ? &rfn : nullptr))) return rc;
     drain.done();  // in flight on purpose: wdx_demux_wait synchronises
     if (S->dtw_last.family != WDX_DTW_NONE) ctx->dtw_last = S->dtw_last;
     S->slot_busy = true;
@@ -1515,7 +1646,8 @@ int wdx_demux_submit(wdx_ctx *ctx, int32_t slot, const float *sig, int64_t n_rea
     return wdx_demux_submit_ex(ctx, slot, &in, p, n_refs, (want_fpt ? WDX_WANT_FPT : 0u) | (want_dist ? WDX_WANT_DIST : 0u));
 }
 
-int wdx_demux_wait_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out) {
+// wdx_demux_wait_ex / wdx_demux_wait_refine: refine_idx must be given exactly when the slot asked for it
+static int demux_wait_body(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out, int32_t *refine_idx) {
     WDX_ENTER(ctx);
     if (!out) {
         set_error("demux_wait: null output block");
@@ -1546,6 +1678,14 @@ int wdx_demux_wait_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out) 
             set_error("demux_wait: an output that was not requested at wdx_demux_submit");
             return WDX_ERR_INVALID;
         }
+        if (S->slot_n > 0 && refine_idx && !S->slot_want_ridx) {
+            set_error("demux_wait: refine_idx was not requested at wdx_demux_submit_refine");
+            return WDX_ERR_INVALID;
+        }
+        if (S->slot_n > 0 && !refine_idx && S->slot_want_ridx) {
+            set_error("demux_wait: the slot holds a refine_idx (WDX_WANT_REFINE_IDX): wdx_demux_wait_refine takes it");
+            return WDX_ERR_INVALID;
+        }
         S->slot_waiting = true;
     }
     // (the wait itself runs outside the parent's mutex: the other slots can be submitted meanwhile)
@@ -1571,7 +1711,16 @@ int wdx_demux_wait_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out) 
     if (out->conf) memcpy(out->conf, ho + S->slot_off[4], nn * 8);
     if (out->dist && S->slot_nY > 0) memcpy(out->dist, ho + S->slot_off[5], nn * S->slot_nY * 4);
     if (out->pred) memcpy(out->pred, ho + S->slot_off[8], nn * 4);
+    if (refine_idx) memcpy(refine_idx, ho + S->slot_off_ridx, nn * 12);
     return WDX_SUCCESS;
+}
+
+int wdx_demux_wait_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out) {
+    return demux_wait_body(ctx, slot, out, nullptr);
+}
+
+int wdx_demux_wait_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out, int32_t *refine_idx) {
+    return demux_wait_body(ctx, slot, out, refine_idx);
 }
 
 int wdx_demux_wait(wdx_ctx *ctx, int32_t slot, double *fpt, float *dist, int32_t *call, int32_t *status) {

@@ -82,6 +82,11 @@ struct wdx_ctx {
     int64_t slot_n = 0, slot_K = 0, slot_nY = 0, slot_k = 0;
     size_t slot_off[9] = {};  // fpt, dwell, stats, prob, conf, dist, call, status, pred in the slot's page-locked block
     wdx::Buffer mb_dwell, mb_stats, mb_prob, mb_pred, mb_conf;  // device side of the optional minibatch outputs
+    // a refine minibatch (wdx_demux_submit_refine): its refine_idx on the device and in the page-locked block; the
+    // consensus query lives in the slot's own ref_buf / ref_query_host, the hand-over records in its ref_ws
+    wdx::Buffer mb_ridx;
+    bool slot_want_ridx = false;
+    size_t slot_off_ridx = 0;
     // timing
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[wdx::kNumTimed];

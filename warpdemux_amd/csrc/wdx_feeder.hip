@@ -74,7 +74,7 @@ struct FeederRing {
     uint32_t magic, n_slots;
     int64_t max_reads, max_stride, n_refs;
     int32_t n_events, n_classes;
-    int32_t sample_format, pad_;   // WDX_FEEDER_SAMPLES_*: what the sample region of a slot holds
+    int32_t sample_format, kind;   // WDX_FEEDER_SAMPLES_*: what the sample region of a slot holds; kRingPlain / kRingRefine
     wdx_seg_params params;   // what every minibatch is fingerprinted with (workers read `padding` to pack their rows)
     // byte offsets of the data regions (each holds n_slots consecutive per-slot pieces)
     uint64_t off_sig, off_roff, off_rlen, off_as, off_ae, off_ok, off_dist, off_call, off_status, off_fpt, off_dwell, off_stats,
@@ -94,6 +94,24 @@ struct FeederRing {
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// A refine ring (wdx_feeder_ring_init_refine) keeps this behind the FeederRing record, inside the header area; a plain
+// ring (kind 0, the word wdx_feeder_ring_init has always left zero) has nothing there and keeps its layout byte for byte.
+enum : int32_t { kRingPlain = 0, kRingRefine = 1 };
+constexpr int kRingMaxQuery = 96;    // wdx_refine_params.n_query's limit
+constexpr int kRingMaxSeries = 128;  // ... and that of num_events + 1
+struct FeederRefine {
+    wdx_refine_params rp;   // (rp.query is a pointer of the process that made the ring: every user points it at `query`)
+    double query[kRingMaxQuery];
+    uint64_t off_ridx;      // per-slot refine_idx regions, max_reads * 3 int32 each
+};
+static inline size_t refine_ext_offset() { return align_up(sizeof(FeederRing), 16); }
+static inline size_t ring_header_bytes(bool refine) {
+    return align_up(refine ? refine_ext_offset() + sizeof(FeederRefine) : sizeof(FeederRing), 4096);
+}
+static inline FeederRefine *refine_ext(FeederRing *R) {
+    return R->kind == kRingRefine ? (FeederRefine *)((unsigned char *)R + refine_ext_offset()) : nullptr;
+}
 
 static long futex(uint32_t *addr, int op, uint32_t val, const struct timespec *to) {
     return syscall(SYS_futex, addr, op, val, to, nullptr, 0);
@@ -200,17 +218,53 @@ using namespace wdx;
 
 extern "C" {
 
-size_t wdx_feeder_ring_bytes(const wdx_feeder_geometry *g) {
+static size_t ring_bytes(const wdx_feeder_geometry *g, bool refine) {
     Geo G;
     size_t sf;
     if (!geometry(g, G, sf)) return 0;
     const size_t per_slot = G.sig + G.roff + G.rlen + 2 * G.i32 + G.ok + G.dist + 2 * G.i32 + 2 * G.fpt + G.stats + G.prob +
-                            (g->n_classes ? G.i32 : 0) + G.f64;
-    return align_up(sizeof(FeederRing), 4096) + (size_t)g->n_slots * per_slot;
+                            (g->n_classes ? G.i32 : 0) + G.f64 + (refine ? align_up((size_t)g->max_reads * 12, 4096) : 0);
+    return ring_header_bytes(refine) + (size_t)g->n_slots * per_slot;
 }
 
+size_t wdx_feeder_ring_bytes(const wdx_feeder_geometry *g) { return ring_bytes(g, false); }
+size_t wdx_feeder_ring_bytes_refine(const wdx_feeder_geometry *g) { return ring_bytes(g, true); }
+
+static int ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p, const wdx_refine_params *rp);
+
 int wdx_feeder_ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p) {
-    const size_t need = wdx_feeder_ring_bytes(g);
+    return ring_init(mem, bytes, g, p, nullptr);
+}
+
+int wdx_feeder_ring_init_refine(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p,
+                                const wdx_refine_params *rp) {
+    if (!rp || !rp->query) {
+        set_error("feeder_ring_init_refine: null refinement parameters");
+        return WDX_ERR_INVALID;
+    }
+    // the limits of wdx_fingerprint_refine_batch, with its codes: a ring no minibatch could be served from is refused here
+    if (rp->n_query < 1) {
+        set_error("consensus refinement: empty query");
+        return WDX_ERR_INVALID;
+    }
+    if (rp->n_query > kRingMaxQuery || (p && p->num_events + 1 > kRingMaxSeries)) {
+        set_error("consensus refinement: the query must have 1..%d points and num_events + 1 <= %d", kRingMaxQuery, kRingMaxSeries);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (rp->barcode_keep_events < 1) {
+        set_error("barcode_num_events must be >= 1");
+        return WDX_ERR_INVALID;
+    }
+    return ring_init(mem, bytes, g, p, rp);
+}
+
+// rp == nullptr: the plain ring, exactly the bytes wdx_feeder_ring_init has always written
+static int ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p_in, const wdx_refine_params *rp) {
+    const size_t need = ring_bytes(g, rp != nullptr);
+    wdx_seg_params pv{};
+    if (p_in) pv = *p_in;
+    if (rp) pv.barcode_num_events = rp->barcode_keep_events;   // K of every minibatch of a refine ring
+    const wdx_seg_params *p = p_in ? &pv : nullptr;
     if (!mem || !p || need == 0 || bytes < need || ((uintptr_t)mem & 4095u)) {
         set_error("feeder_ring_init: need parameters and a page-aligned block of %zu bytes for this geometry", need);
         return WDX_ERR_INVALID;
@@ -235,7 +289,7 @@ int wdx_feeder_ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, 
     R->sig_floats = sf;
     R->sig_slot_bytes = G.sig;
     const size_t ns = (size_t)g->n_slots;
-    size_t o = align_up(sizeof(FeederRing), 4096);
+    size_t o = ring_header_bytes(rp != nullptr);
     R->off_sig = o;    o += ns * G.sig;
     R->off_roff = o;   o += ns * G.roff;
     R->off_rlen = o;   o += ns * G.rlen;
@@ -251,6 +305,16 @@ int wdx_feeder_ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, 
     R->off_prob = o;   o += ns * G.prob;
     R->off_pred = o;   o += g->n_classes ? ns * G.i32 : 0;
     R->off_conf = o;   o += ns * G.f64;
+    if (rp) {
+        R->kind = kRingRefine;
+        FeederRefine *X = refine_ext(R);
+        memset(X, 0, sizeof(FeederRefine));
+        X->rp = *rp;
+        X->rp.query = nullptr;
+        memcpy(X->query, rp->query, (size_t)rp->n_query * 8);
+        X->off_ridx = o;
+        o += ns * align_up((size_t)g->max_reads * 12, 4096);
+    }
     R->bytes = o;
     __atomic_store_n(&R->magic, kFeederMagic, __ATOMIC_RELEASE);
     return WDX_SUCCESS;
@@ -354,6 +418,14 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
     auto stats_of = [&](uint32_t s) { return (double *)(base + R->off_stats + (size_t)s * align_up(mr * 48, 4096)); };
     auto prob_of = [&](uint32_t s) { return (double *)(base + R->off_prob + (size_t)s * align_up(mr * kc * 8, 4096)); };
     auto conf_of = [&](uint32_t s) { return (double *)(base + R->off_conf + (size_t)s * align_up(mr * 8, 4096)); };
+    // a refine ring: every minibatch goes through wdx_demux_submit_refine / wdx_demux_wait_refine with the ring's rp
+    FeederRefine *const X = refine_ext(R);
+    wdx_refine_params rp{};
+    if (X) {
+        rp = X->rp;
+        rp.query = X->query;
+    }
+    auto ridx_of = [&](uint32_t s) { return (int32_t *)(base + X->off_ridx + (size_t)s * align_up(mr * 12, 4096)); };
     // ring slots in flight, oldest first, each on one of the context's WDX_MAX_SLOTS submit / wait slots
     struct Fly { int ring, cslot; } fifo[WDX_MAX_SLOTS];
     int head = 0, count = 0;
@@ -390,7 +462,8 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
             out.pred = i32_of(R->off_pred, s);
             out.conf = conf_of(s);
         }
-        int rc = wdx_demux_wait_ex(ctx, f.cslot, &out);
+        int32_t *const ridx = (X && (want & WDX_WANT_REFINE_IDX)) ? ridx_of(s) : nullptr;
+        int rc = wdx_demux_wait_refine(ctx, f.cslot, &out, ridx);
         if (rc == WDX_ERR_INVALID) {
             // by contract the context slot still holds the minibatch: take it out with the two outputs every batch has,
             // and keep the slot marked busy if even that is refused (it is lost to this serve loop, not reused)
@@ -400,7 +473,7 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
             wdx_minibatch_out two{};
             two.status = out.status;
             two.call = out.call;
-            if (wdx_demux_wait_ex(ctx, f.cslot, &two) != WDX_ERR_INVALID) cbusy[f.cslot] = false;
+            if (wdx_demux_wait_refine(ctx, f.cslot, &two, ridx) != WDX_ERR_INVALID) cbusy[f.cslot] = false;
             set_error("%s", keep);
         } else {
             cbusy[f.cslot] = false;
@@ -446,7 +519,8 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
                 in.a_start = i32_of(R->off_as, s);
                 in.a_end = i32_of(R->off_ae, s);
                 in.ok = S.has_ok ? ok_of(s) : nullptr;
-                rc = wdx_demux_submit_adc(ctx, cs, &in, &R->params, (int64_t)nY, S.want);
+                rc = X ? wdx_demux_submit_refine(ctx, cs, nullptr, &in, &R->params, &rp, (int64_t)nY, S.want)
+                       : wdx_demux_submit_adc(ctx, cs, &in, &R->params, (int64_t)nY, S.want);
             } else {
                 wdx_minibatch_in in{};
                 in.sig = sig_of(s);
@@ -457,7 +531,8 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
                 in.a_start = i32_of(R->off_as, s);
                 in.a_end = i32_of(R->off_ae, s);
                 in.ok = S.has_ok ? ok_of(s) : nullptr;
-                rc = wdx_demux_submit_ex(ctx, cs, &in, &R->params, (int64_t)nY, S.want);
+                rc = X ? wdx_demux_submit_refine(ctx, cs, &in, nullptr, &R->params, &rp, (int64_t)nY, S.want)
+                       : wdx_demux_submit_ex(ctx, cs, &in, &R->params, (int64_t)nY, S.want);
             }
             if (rc == WDX_SUCCESS) {
                 st(&S.state, word_of(owner_of(v), kInflight));
@@ -595,6 +670,7 @@ struct WorkerRows {
     const uint8_t *ok = nullptr;
     uint32_t want = 0;
     wdx_minibatch_out out{};
+    int32_t *refine_idx = nullptr;   // WDX_WANT_REFINE_IDX (a refine ring)
 };
 
 // A worker process: one minibatch through the feeder -- no context, NO HIP call.  Blocks until the results are there.
@@ -632,7 +708,15 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
         set_error("%s: %lld reads do not fit the ring's %lld-read slots", who, (long long)n_reads, (long long)R->max_reads);
         return WDX_ERR_INVALID;
     }
-    if ((want & ~(WDX_WANT_FPT | WDX_WANT_DIST | WDX_WANT_DWELL | WDX_WANT_STATS | WDX_WANT_SVM)) ||
+    if ((want & WDX_WANT_REFINE_IDX) && R->kind != kRingRefine) {
+        set_error("%s: WDX_WANT_REFINE_IDX on a ring without refinement (wdx_feeder_ring_init_refine)", who);
+        return WDX_ERR_INVALID;
+    }
+    if (R->kind == kRingRefine && R->n_refs == 0 && (want & (WDX_WANT_DIST | WDX_WANT_SVM))) {
+        set_error("%s: a fingerprint-only ring (n_refs = 0) serves no distances and no SVM tail", who);
+        return WDX_ERR_INVALID;
+    }
+    if ((want & ~(WDX_WANT_FPT | WDX_WANT_DIST | WDX_WANT_DWELL | WDX_WANT_STATS | WDX_WANT_SVM | WDX_WANT_REFINE_IDX)) ||
         ((want & (WDX_WANT_FPT | WDX_WANT_DWELL | WDX_WANT_STATS)) && R->n_events == 0) || ((want & WDX_WANT_SVM) && R->n_classes == 0)) {
         set_error("%s: the ring was laid out without room for an output that is asked for (n_events %d, n_classes %d)", who,
                   (int)R->n_events, (int)R->n_classes);
@@ -640,7 +724,8 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
     }
     if (n_reads > 0 && (((want & WDX_WANT_FPT) && !O.fpt) || ((want & WDX_WANT_DWELL) && !O.dwell) ||
                         ((want & WDX_WANT_STATS) && !O.stats) || ((want & WDX_WANT_DIST) && R->n_refs > 0 && !O.dist) ||
-                        ((want & WDX_WANT_SVM) && (!O.prob || !O.pred || !O.conf)))) {
+                        ((want & WDX_WANT_SVM) && (!O.prob || !O.pred || !O.conf)) ||
+                        ((want & WDX_WANT_REFINE_IDX) && !job.refine_idx))) {
         set_error("%s: an output that is asked for has no destination", who);
         return WDX_ERR_INVALID;
     }
@@ -729,6 +814,8 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
             memcpy(O.pred, i32_of(R->off_pred), n * 4);
             memcpy(O.conf, base + R->off_conf + (size_t)s * align_up(mr * 8, 4096), n * 8);
         }
+        if (want & WDX_WANT_REFINE_IDX)
+            memcpy(job.refine_idx, base + refine_ext(R)->off_ridx + (size_t)s * align_up(mr * 12, 4096), n * 12);
     } else {
         set_error("feeder: %s", S.err);
     }
@@ -740,7 +827,7 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
 
 extern "C" {
 
-int wdx_feeder_run(void *ring, const wdx_feeder_job *job) {
+static int feeder_run_float(void *ring, const wdx_feeder_job *job, int32_t *refine_idx) {
     FeederRing *R = (FeederRing *)ring;
     if (int rc = ring_check(R)) return rc;
     if (!job) {
@@ -748,6 +835,7 @@ int wdx_feeder_run(void *ring, const wdx_feeder_job *job) {
         return WDX_ERR_INVALID;
     }
     WorkerRows w;
+    w.refine_idx = refine_idx;
     w.sig = job->sig;
     w.n_reads = job->n_reads;
     w.stride = job->stride;
@@ -759,8 +847,10 @@ int wdx_feeder_run(void *ring, const wdx_feeder_job *job) {
     return feeder_run_rows(R, ring, "feeder_run", w);
 }
 
+int wdx_feeder_run(void *ring, const wdx_feeder_job *job) { return feeder_run_float(ring, job, nullptr); }
+
 // The same for a ring of int16 samples: the raw ADC windows and the reads' offset / scale go into the slot
-int wdx_feeder_run_adc(void *ring, const wdx_feeder_job_adc *job) {
+static int feeder_run_int16(void *ring, const wdx_feeder_job_adc *job, int32_t *refine_idx) {
     FeederRing *R = (FeederRing *)ring;
     if (int rc = ring_check(R)) return rc;
     if (!job) {
@@ -768,6 +858,7 @@ int wdx_feeder_run_adc(void *ring, const wdx_feeder_job_adc *job) {
         return WDX_ERR_INVALID;
     }
     WorkerRows w;
+    w.refine_idx = refine_idx;
     w.is_adc = true;
     w.adc = job->adc;
     w.n_reads = job->n_reads;
@@ -781,6 +872,17 @@ int wdx_feeder_run_adc(void *ring, const wdx_feeder_job_adc *job) {
     w.want = job->want;
     w.out = wdx_minibatch_out{job->status, job->call, job->dist, job->fpt, job->dwell, job->stats, job->prob, job->pred, job->conf};
     return feeder_run_rows(R, ring, "feeder_run_adc", w);
+}
+
+int wdx_feeder_run_adc(void *ring, const wdx_feeder_job_adc *job) { return feeder_run_int16(ring, job, nullptr); }
+
+// either run call plus the destination of refine_idx (wdx_feeder_job has no room for the pointer)
+int wdx_feeder_run_refine(void *ring, const wdx_feeder_job *job, const wdx_feeder_job_adc *job_adc, int32_t *refine_idx) {
+    if ((job != nullptr) == (job_adc != nullptr)) {
+        set_error("feeder_run_refine: exactly one of job / job_adc must be given");
+        return WDX_ERR_INVALID;
+    }
+    return job ? feeder_run_float(ring, job, refine_idx) : feeder_run_int16(ring, job_adc, refine_idx);
 }
 
 // wdx_demux_batch's arguments and outputs (bit-identical results) through the feeder

@@ -53,6 +53,7 @@ class DemuxEngine:
         self.params = params or SegParams(barcode_num_events=int(np.asarray(refs).shape[1]))
         self.set_refs(refs, window, penalty)
         self._work = None
+        self._refine_work = None
         self._synth_tables = {}
 
     # -- reference set ---------------------------------------------------------------------------
@@ -129,6 +130,36 @@ class DemuxEngine:
             self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
             C.byref(pc), C.byref(rc), _dp(fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(status), self._stream()))
         return fpt, dwell, stats, idx, status
+
+    def demux_refine(self, sig, a_start, a_end, refine, *, offsets=None, stride=0, max_len: int, ok=None, counts=None):
+        """`demux` with the consensus-refinement branch in front (wdx_demux_refine_dev): refine fingerprint -> DTW -> call
+        -> histogram on the current stream; ``refine.barcode_keep_events`` must equal the reference length.  Returns
+        (DemuxResult with fpt, dwell i64 (n,K), stats f64 (n,6), refine_idx i32 (n,3))."""
+        torch = self.torch
+        n = int(a_start.shape[0])
+        if offsets is None and not stride:
+            if sig.dim() != 2:
+                raise ValueError("packed reads need `offsets`, a minibatch needs 2-D `sig` or `stride`")
+            stride = int(sig.shape[1])
+        K = int(refine.barcode_keep_events)
+        out = DemuxResult(
+            dist=torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev),
+            call=torch.empty(n, dtype=torch.int32, device=self.tdev),
+            status=torch.empty(n, dtype=torch.int32, device=self.tdev),
+            counts=counts if counts is not None else torch.zeros(self.nY + 1, dtype=torch.int64, device=self.tdev),
+            fpt=torch.empty((n, K), dtype=torch.float64, device=self.tdev))
+        dwell = torch.empty((n, K), dtype=torch.int64, device=self.tdev)
+        stats = torch.empty((n, 6), dtype=torch.float64, device=self.tdev)
+        idx = torch.empty((n, 3), dtype=torch.int32, device=self.tdev)
+        need = int(self.L.wdx_demux_refine_workspace_bytes(n, K))
+        if self._refine_work is None or self._refine_work.numel() < need:
+            self._refine_work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
+        pc, rc = self.params.to_c(), refine.to_c()
+        _lib.check(self.L.wdx_demux_refine_dev(
+            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+            C.byref(pc), C.byref(rc), _dp(out.fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(out.status), _dp(out.dist),
+            _dp(out.call), _dp(out.counts), _dp(self._refine_work), self._stream()))
+        return out, dwell, stats, idx
 
     def dtw(self, X, want_argmin=True, out=None):
         """Device DTW of (n, L) float64 rows against the resident refs.  ``out=(dist, argmin)`` reuses the

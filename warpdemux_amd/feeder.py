@@ -21,6 +21,13 @@ What comes back is what the reference's worker needs from a minibatch (file_proc
         ... in a worker:  fb, preds = feeder.detect_and_predict(minibatch, adapter_start, adapter_end, success, return_df=True)
     feeder.close()
 
+``Feeder(..., refine=RefineParams(...))`` serves the tRNA models' consensus-refinement branch (the ring keeps the
+refinement parameters and the consensus query): `fingerprint_batch[_adc]` then returns what
+`sig_proc.fingerprint_refine_batch` returns, ``refine_idx`` included, and `sig_proc.read_results_from_batch(fb, drs, ids,
+refined=True)` makes the reference's ReadResults of it.  Such a feeder may be created without references
+(``refs=None, model=None``): a tRNA worker's classifier (catboost on the raw fingerprint) runs on the host and needs the
+fingerprints only.
+
 A worker that dies while it holds a slot does not cost the ring that slot, and a feeder process that dies is noticed
 by the workers (`WdxNoDevice`) even while it is a zombie nobody has reaped (wdx_feeder.hip).
 """
@@ -35,7 +42,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .sig_proc import DemuxBatch, FingerprintBatch, SegParams
+from .sig_proc import DemuxBatch, FingerprintBatch, RefineParams, SegParams
 
 MAX_SLOTS = 32      # ring slots (WDX_FEEDER_MAX_RING_SLOTS); the feeder keeps at most 8 of them in flight on the device
 
@@ -47,8 +54,9 @@ def _serve(shm_name: str, refs, window, penalty, model, device: int, ready):
     try:
         L = _lib.load()
         ctx = _lib.Context(device)
-        _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(refs), refs.shape[0], refs.shape[1], int(window) if window else 0,
-                                  float(penalty) if penalty else 0.0))
+        if refs.shape[0]:   # (a fingerprint-only refine ring has none)
+            _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(refs), refs.shape[0], refs.shape[1], int(window) if window else 0,
+                                      float(penalty) if penalty else 0.0))
         if model is not None:
             m = model.to_c()
             _lib.check(L.wdx_svm_set_model(ctx.handle, C.byref(m)))
@@ -85,24 +93,32 @@ class Feeder:
     `demux_batch_adc` / `detect_and_predict_adc` with the raw samples and ``row_len`` / ``offset`` / ``scale`` per read --
     half the bytes in the worker's copy, in the ring and over the bus; the device calibrates by the formula of
     `sig_proc.calibrate_adc`, and the results are those of the float32 calls on its rows, bit for bit.  The float32 calls
-    are refused on such a ring, and the ``*_adc`` calls on a float32 ring."""
+    are refused on such a ring, and the ``*_adc`` calls on a float32 ring.
+
+    ``refine``: every minibatch takes the consensus-refinement branch with these parameters (K =
+    ``refine.barcode_keep_events``); with it, and only with it, ``refs`` and ``model`` may both be None: a fingerprint-only
+    feeder, on which `demux_batch`, `detect_and_predict` and `predict` are refused."""
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, max_reads: int = 1000,
                  stride: int = 10000, n_slots: int = 16, device: int = 0, start_timeout: float = 120.0, model=None,
-                 adc: bool = False):
+                 adc: bool = False, refine: Optional[RefineParams] = None):
         if model is not None:
             if refs is not None:
                 raise ValueError("pass either refs or model (whose _X are the references)")
             refs, window, penalty = model._X, model.window, model.penalty
         if refs is None:
-            raise ValueError("refs or model is required")
+            if refine is None:
+                raise ValueError("refs or model is required")
+            refs = np.zeros((0, int(refine.barcode_keep_events)), dtype=np.float64)
         refs = np.ascontiguousarray(refs, dtype=np.float64)
         if refs.ndim != 2:
             raise ValueError("refs must be (nY, L)")
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
-        self.params = params or SegParams(barcode_num_events=int(refs.shape[1]))
-        if self.params.barcode_num_events != refs.shape[1]:
+        self.refine = refine
+        K = int(refine.barcode_keep_events) if refine is not None else int(refs.shape[1])
+        self.params = params or SegParams(barcode_num_events=K)
+        if K != refs.shape[1] or (refine is None and self.params.barcode_num_events != K):
             raise ValueError("barcode_num_events must equal the reference length")
         self.model = model
         self.n_classes = int(model.n_classes) if model is not None else 0
@@ -114,14 +130,24 @@ class Feeder:
         geo = _lib.FeederGeometryC(self.n_slots, self.K, self.n_classes,
                                    _lib.FEEDER_SAMPLES_INT16 if self.adc else _lib.FEEDER_SAMPLES_FLOAT32, self.max_reads,
                                    self.stride, self.nY)
-        nbytes = int(self.L.wdx_feeder_ring_bytes(C.byref(geo)))
+        pc = self.params.to_c()
+        rc = refine.to_c() if refine is not None else None
+        nbytes = int((self.L.wdx_feeder_ring_bytes if rc is None else self.L.wdx_feeder_ring_bytes_refine)(C.byref(geo)))
         if nbytes == 0:
             raise ValueError("bad ring geometry")
-        self._shm = shared_memory.SharedMemory(create=True, size=nbytes)
-        self._owner = os.getpid()
-        self._base = C.addressof(C.c_char.from_buffer(self._shm.buf))
-        pc = self.params.to_c()
-        _lib.check(self.L.wdx_feeder_ring_init(C.c_void_p(self._base), nbytes, C.byref(geo), C.byref(pc)))
+        self._shm = self._proc = None
+        shm = shared_memory.SharedMemory(create=True, size=nbytes)
+        base = C.addressof(C.c_char.from_buffer(shm.buf))
+        init = (self.L.wdx_feeder_ring_init(C.c_void_p(base), nbytes, C.byref(geo), C.byref(pc)) if rc is None else
+                self.L.wdx_feeder_ring_init_refine(C.c_void_p(base), nbytes, C.byref(geo), C.byref(pc), C.byref(rc)))
+        if init != _lib.WDX_SUCCESS:   # (a refused ring -- e.g. a query beyond 96 points -- leaves no shared memory behind)
+            try:
+                shm.close()
+            except BufferError:
+                pass
+            shm.unlink()
+            _lib.check(init)
+        self._shm, self._owner, self._base = shm, os.getpid(), base
         ctx = mp.get_context("fork")
         ready = ctx.Event()
         self._proc = ctx.Process(target=_serve, args=(self._shm.name, refs, window, penalty, model, int(device), ready),
@@ -154,7 +180,10 @@ class Feeder:
         out = self._outputs(n, want)
         job = _lib.FeederJobC(_lib.addr(sig), n, stride, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok), int(want), 0,
                               *[_lib.addr(out[k]) for k in ("status", "call", "dist", "fpt", "dwell", "stats", "prob", "pred", "conf")])
-        _lib.check(self.L.wdx_feeder_run(C.c_void_p(self._base), C.byref(job)))
+        if want & _lib.WANT_REFINE_IDX:
+            _lib.check(self.L.wdx_feeder_run_refine(C.c_void_p(self._base), C.byref(job), None, _lib.ptr(out["refine_idx"])))
+        else:
+            _lib.check(self.L.wdx_feeder_run(C.c_void_p(self._base), C.byref(job)))
         return out
 
     def _outputs(self, n: int, want: int) -> dict:
@@ -168,7 +197,17 @@ class Feeder:
             "prob": np.empty((n, self.n_classes), dtype=np.float64) if want & _lib.WANT_SVM else None,
             "pred": np.empty(n, dtype=np.int32) if want & _lib.WANT_SVM else None,
             "conf": np.empty(n, dtype=np.float64) if want & _lib.WANT_SVM else None,
+            "refine_idx": np.empty((n, 3), dtype=np.int32) if want & _lib.WANT_REFINE_IDX else None,
         }
+
+    def _fpt_want(self) -> int:
+        """the ReadResult arrays of a minibatch; on a refine feeder with refine_idx"""
+        return (_lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS |
+                (_lib.WANT_REFINE_IDX if self.refine is not None else 0))
+
+    def _need_refs(self, what: str):
+        if self.nY == 0:
+            raise ValueError(f"{what} needs references or a model: this feeder is fingerprint-only (Feeder(refine=...))")
 
     def _run_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success, want: int):
         """One int16 minibatch through wdx_feeder_run_adc.  Shapes and dtypes of EVERY array, `success` included, are
@@ -193,52 +232,55 @@ class Feeder:
         job = _lib.FeederJobAdcC(_lib.addr(a), n, stride, _lib.addr(r_len), _lib.addr(off), _lib.addr(sc), _lib.addr(a_s),
                                  _lib.addr(a_e), _lib.addr(ok), int(want), 0,
                                  *[_lib.addr(out[k]) for k in ("status", "call", "dist", "fpt", "dwell", "stats", "prob", "pred", "conf")])
-        _lib.check(self.L.wdx_feeder_run_adc(C.c_void_p(self._base), C.byref(job)))
+        if want & _lib.WANT_REFINE_IDX:
+            _lib.check(self.L.wdx_feeder_run_refine(C.c_void_p(self._base), None, C.byref(job), _lib.ptr(out["refine_idx"])))
+        else:
+            _lib.check(self.L.wdx_feeder_run_adc(C.c_void_p(self._base), C.byref(job)))
         return out
 
     def demux_batch_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None,
                         want_dist: bool = True) -> DemuxBatch:
         """`demux_batch` for an int16 ADC minibatch (a ``Feeder(adc=True)``)."""
+        self._need_refs("demux_batch_adc")
         o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success, _lib.WANT_DIST if want_dist else 0)
         return DemuxBatch(o["status"], o["call"], o["dist"], None)
 
     def fingerprint_batch_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None) -> FingerprintBatch:
         """`fingerprint_batch` for an int16 ADC minibatch (a ``Feeder(adc=True)``)."""
-        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success,
-                          _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS)
-        return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"])
+        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success, self._fpt_want())
+        return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
 
     def detect_and_predict_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None,
                                return_df: bool = False):
         """`detect_and_predict` for an int16 ADC minibatch (a ``Feeder(adc=True)``): the reference worker's whole
         minibatch from the raw samples the pod5 file holds."""
-        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success,
-                          _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | _lib.WANT_SVM)
+        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success, self._fpt_want() | _lib.WANT_SVM)
         return self._fpt_and_predictions(o, return_df)
 
     def demux_batch(self, signals, adapter_start, adapter_end, success=None, want_dist: bool = True) -> DemuxBatch:
         """Status, nearest-reference call and (optionally) the distance rows -- `sig_proc.demux_batch`'s result, bit for
         bit.  Callable from any process that inherited this object; blocks until the results are there."""
+        self._need_refs("demux_batch")
         o = self._run(signals, adapter_start, adapter_end, success, _lib.WANT_DIST if want_dist else 0)
         return DemuxBatch(o["status"], o["call"], o["dist"], None)
 
     def fingerprint_batch(self, signals, adapter_start, adapter_end, success=None) -> FingerprintBatch:
         """`sig_proc.fingerprint_batch`'s result (fingerprints, dwell times, the six statistics, status), bit for bit:
-        what `sig_proc.read_results_from_batch` turns into the reference's ReadResult records."""
-        o = self._run(signals, adapter_start, adapter_end, success, _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS)
-        return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"])
+        what `sig_proc.read_results_from_batch` turns into the reference's ReadResult records.  On a refine feeder:
+        `sig_proc.fingerprint_refine_batch`'s result, ``refine_idx`` included."""
+        o = self._run(signals, adapter_start, adapter_end, success, self._fpt_want())
+        return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
 
     def detect_and_predict(self, signals, adapter_start, adapter_end, success=None, return_df: bool = False):
         """The two halves of the reference worker's minibatch (file_proc.py:418-450) from one pass over the rows:
         `(FingerprintBatch, predictions)` with predictions = `(y_pred, y_prob)` or, with ``return_df``, the predictions
         DataFrame of `DTW_SVM.predict(np.vstack(fpts), return_df=True)` -- one row per SUCCESSFUL read, in read order,
         like the reference, which only ever shows the model the successful fingerprints."""
-        o = self._run(signals, adapter_start, adapter_end, success,
-                      _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | _lib.WANT_SVM)
+        o = self._run(signals, adapter_start, adapter_end, success, self._fpt_want() | _lib.WANT_SVM)
         return self._fpt_and_predictions(o, return_df)
 
     def _fpt_and_predictions(self, o: dict, return_df: bool):
-        fb = FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"])
+        fb = FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
         okr = o["status"] == 0
         y_pred, y_prob, conf = o["pred"][okr].astype(np.int64), o["prob"][okr], o["conf"][okr]
         if return_df:

@@ -12,17 +12,23 @@ file_proc.py:244-260) with "process minibatch k".  `MinibatchPipeline` gives tha
 
 Results are bit-identical to `demux_batch` (same kernels).  INTEGRATION.md shows the four-line change in
 ``file_proc``'s loop.
+
+``MinibatchPipeline(..., refine=RefineParams(...))`` runs the consensus-refinement branch of the tRNA models on the same
+slots (wdx_demux_submit_refine / wdx_demux_wait_refine): `wait` then returns a `RefineMinibatch` -- the arrays of
+`sig_proc.fingerprint_refine_batch`, bit for bit, plus call / dist when there are references; ``refs=None`` is a
+fingerprint-only pipeline (the tRNA classifier runs on the host).
 """
 from __future__ import annotations
 
 import ctypes as C
 import weakref
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from .sig_proc import DemuxBatch, SegParams, adc_minibatch
+from .sig_proc import DemuxBatch, FingerprintBatch, RefineParams, SegParams, adc_minibatch
 
 
 def pinned_empty(shape, dtype=np.float32, device: Optional[int] = None) -> np.ndarray:
@@ -62,29 +68,52 @@ def register_host(arr: np.ndarray):
     return lambda: L.wdx_host_unregister(p)
 
 
+@dataclass
+class RefineMinibatch:
+    """What `MinibatchPipeline.wait` returns for a refine pipeline: `fingerprints` (with ``refine_idx``) is
+    `sig_proc.fingerprint_refine_batch`'s result; call is -1 everywhere and dist None without references."""
+
+    fingerprints: FingerprintBatch
+    call: np.ndarray
+    dist: Optional[np.ndarray]
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.fingerprints.status
+
+
 class MinibatchPipeline:
     """Minibatches in flight against one resident reference set (model._X): two slots for a worker's own loop, up to
-    MAX_SLOTS for a feeder process that serves many producers."""
+    MAX_SLOTS for a feeder process that serves many producers.  ``refine``: every minibatch takes the
+    consensus-refinement branch (K = ``refine.barcode_keep_events``); then ``refs`` may be None (fingerprints only)."""
 
     N_SLOTS = 2
 
     def __init__(self, refs, window=None, penalty=None, params: Optional[SegParams] = None, device: int = 0,
-                 n_slots: int = 2):
+                 n_slots: int = 2, refine: Optional[RefineParams] = None):
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
         self.N_SLOTS = int(n_slots)
+        self.refine = refine
+        if refs is None:
+            if refine is None:
+                raise ValueError("refs is required (only a refine pipeline can be fingerprint-only)")
+            refs = np.zeros((0, int(refine.barcode_keep_events)), dtype=np.float64)
         refs = np.ascontiguousarray(refs, dtype=np.float64)
         if refs.ndim != 2:
             raise ValueError("refs must be (nY, L)")
-        self.params = params or SegParams(barcode_num_events=int(refs.shape[1]))
-        if self.params.barcode_num_events != refs.shape[1]:
+        K = int(refine.barcode_keep_events) if refine is not None else int(refs.shape[1])
+        self.params = params or SegParams(barcode_num_events=K)
+        if K != refs.shape[1] or (refine is None and self.params.barcode_num_events != K):
             raise ValueError("barcode_num_events must equal the reference length")
         self.nY, self.K = (int(v) for v in refs.shape)
         self.L = _lib.load()
         self.ctx = _lib.Context(device)
-        _lib.check(self.L.wdx_set_refs(self.ctx.handle, _lib.ptr(refs), self.nY, self.K,
-                                       int(window) if window else 0, float(penalty) if penalty else 0.0))
+        if self.nY:
+            _lib.check(self.L.wdx_set_refs(self.ctx.handle, _lib.ptr(refs), self.nY, self.K,
+                                           int(window) if window else 0, float(penalty) if penalty else 0.0))
         self._pc = self.params.to_c()
+        self._rc = refine.to_c() if refine is not None else None
         self._held = [None] * self.N_SLOTS     # the submitted arrays must outlive the copy-in
 
     def submit(self, slot: int, signals, adapter_start, adapter_end, success=None, want_dist=True, want_fpt=False):
@@ -101,10 +130,23 @@ class MinibatchPipeline:
         ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
         if not 0 <= int(slot) < self.N_SLOTS:
             raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
+        if self.refine is not None:
+            desc = _lib.MinibatchInC(_lib.addr(sig), n, stride, None, None, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok))
+            want_dist = bool(want_dist) and self.nY > 0
+            _lib.check(self.L.wdx_demux_submit_refine(self.ctx.handle, int(slot), C.byref(desc), None, C.byref(self._pc),
+                                                      C.byref(self._rc), self.nY, self._refine_want(want_dist)))
+            self._held[slot] = (sig, a_s, a_e, ok, n, want_dist, True)
+            return
         _lib.check(self.L.wdx_demux_submit(self.ctx.handle, int(slot), _lib.ptr(sig), n, stride, _lib.ptr(a_s),
                                            _lib.ptr(a_e), _lib.ptr(ok), C.byref(self._pc), self.nY, int(want_fpt),
                                            int(want_dist)))
         self._held[slot] = (sig, a_s, a_e, ok, n, bool(want_dist), bool(want_fpt))
+
+    @staticmethod
+    def _refine_want(want_dist: bool) -> int:
+        """a refine minibatch always brings the ReadResult arrays back (a tRNA worker classifies them on the host)"""
+        return (_lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | _lib.WANT_REFINE_IDX |
+                (_lib.WANT_DIST if want_dist else 0))
 
     def submit_adc(self, slot: int, adc, row_len, offset, scale, adapter_start, adapter_end, success=None, want_dist=True,
                    want_fpt=False, row_off=None, row_win=None):
@@ -117,15 +159,24 @@ class MinibatchPipeline:
         if not 0 <= int(slot) < self.N_SLOTS:
             raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
         desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success, row_off, row_win)
+        if self.refine is not None:
+            want_dist = bool(want_dist) and self.nY > 0
+            _lib.check(self.L.wdx_demux_submit_refine(self.ctx.handle, int(slot), None, C.byref(desc), C.byref(self._pc),
+                                                      C.byref(self._rc), self.nY, self._refine_want(want_dist)))
+            self._held[slot] = (kept, None, None, None, n, want_dist, True)
+            return
         want = (_lib.WANT_FPT if want_fpt else 0) | (_lib.WANT_DIST if want_dist else 0)
         _lib.check(self.L.wdx_demux_submit_adc(self.ctx.handle, int(slot), C.byref(desc), C.byref(self._pc), self.nY, want))
         self._held[slot] = (kept, None, None, None, n, bool(want_dist), bool(want_fpt))
 
-    def wait(self, slot: int) -> DemuxBatch:
+    def wait(self, slot: int):
+        """`DemuxBatch` of the minibatch on `slot`; a refine pipeline returns a `RefineMinibatch`."""
         held = self._held[slot] if 0 <= int(slot) < self.N_SLOTS else None
         if held is None:
             raise ValueError(f"nothing was submitted on slot {slot}")
         n, want_dist, want_fpt = held[4:]
+        if self.refine is not None:
+            return self._wait_refine(slot, n, want_dist)
         dist = np.empty((n, self.nY), dtype=np.float32) if want_dist else None
         fpt = np.empty((n, self.K), dtype=np.float64) if want_fpt else None
         call = np.empty(n, dtype=np.int32)
@@ -139,6 +190,20 @@ class MinibatchPipeline:
             self._held[slot] = None
         _lib.check(rc)
         return DemuxBatch(status, call, dist, fpt)
+
+    def _wait_refine(self, slot: int, n: int, want_dist: bool) -> RefineMinibatch:
+        fb = FingerprintBatch(np.empty((n, self.K), dtype=np.float64), np.empty((n, self.K), dtype=np.int64),
+                              np.empty((n, 6), dtype=np.float64), np.empty(n, dtype=np.int32),
+                              np.empty((n, 3), dtype=np.int32))
+        call = np.empty(n, dtype=np.int32)
+        dist = np.empty((n, self.nY), dtype=np.float32) if want_dist else None
+        out = _lib.MinibatchOutC(_lib.addr(fb.status), _lib.addr(call), _lib.addr(dist), _lib.addr(fb.fpt), _lib.addr(fb.dwell),
+                                 _lib.addr(fb.stats), None, None, None)
+        rc = self.L.wdx_demux_wait_refine(self.ctx.handle, int(slot), C.byref(out), _lib.ptr(fb.refine_idx))
+        if rc != _lib.WDX_ERR_INVALID:   # (as in `wait`: an argument error leaves the minibatch in flight)
+            self._held[slot] = None
+        _lib.check(rc)
+        return RefineMinibatch(fb, call, dist)
 
     def run(self, minibatches):
         """Drive an iterable of (signals, adapter_start, adapter_end[, success]) through both slots; yields one
