@@ -133,6 +133,7 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
                                          * operations only (A/B) | 2 fused and every pair run again (tests) | 3 fused, never run again
                                          * (diagnostic: NOT the reference's results) */
 #define WDX_OPT_MLP_CHUNK_ROWS 17       /* wdx_dtw_mlp_predict: rows per DTW + MLP pass (0 = built-in; tests walk several chunks) */
+#define WDX_OPT_BOOST_CHUNK_ROWS 18     /* wdx_boost_predict: rows per pass (0 = built-in; tests walk several chunks) */
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -633,6 +634,59 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
                       double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
                       int64_t block_rows, void *stream);
 
+/* ---- classifier tail of Fpt_Boost.predict (models/fpt_boost.py + models/utils.py:45-61): the float64 fingerprint rows
+ *      themselves (no DTW, no reference set) -> an ensemble of oblivious (symmetric) trees over float features ->
+ *      scale * sum + bias -> softmax (dim == k) or sigmoid (dim == 1, k == 2) -> argmax, label map, top1-top2 margin,
+ *      per-class thresholds.  The model lives in its own slot of the context: a resident SVM or MLP is untouched.
+ *      The contract is the NumPy restatement in tests/helpers/boost_ref.py; parity with CatBoost itself is
+ *      NOT pinned.  Layout, explicit so that a loader fixes conventions and the kernel does not:
+ *        tree t has depth[t] splits, stored at split_*[sum(depth[:t]) + i]; split i sets BIT i of the leaf index when
+ *        (float)x[split_feature] > split_border (float32 compare; equality false; a NaN feature gives split_nan_true);
+ *        its 2^depth[t] * dim leaf values follow those of the trees before it, leaf-major, class fastest:
+ *        leaf_values[leaf_base(t) + leaf * dim + c].
+ *      raw_c = scale * (sum over trees, tree 0 first, one float64 add per tree) + bias[c]: float64 multiply, then add.
+ *      Limits: 1..254 features, depth 0..16, dim 1..16, k 2..16, >= 1 tree; beyond them WDX_ERR_UNSUPPORTED, a malformed
+ *      model WDX_ERR_INVALID.  A model that is refused, or whose staging copy or upload fails, leaves the previous one
+ *      resident. */
+#define WDX_BOOST_MAX_FEATURES 254
+#define WDX_BOOST_MAX_DEPTH 16
+typedef struct wdx_boost_model {
+    int32_t n_trees;
+    int32_t n_features;            /* columns of a fingerprint row                                                     */
+    int32_t dim;                   /* values per leaf: n_classes (MultiClass) or 1 (Logloss, n_classes == 2)           */
+    int32_t n_classes;             /* k                                                                                */
+    const int32_t *depth;          /* [n_trees]                                                                        */
+    const int32_t *split_feature;  /* [sum(depth)] column index, 0..n_features-1                                       */
+    const float *split_border;     /* [sum(depth)]                                                                     */
+    const uint8_t *split_nan_true; /* [sum(depth)] 1: a NaN feature takes the "greater" branch (AsTrue), 0: it does not;
+                                      nullable = all 0                                                                 */
+    const double *leaf_values;     /* [sum(2^depth[t]) * dim]                                                          */
+    double scale;
+    const double *bias;            /* [dim]                                                                            */
+    const int32_t *label_map;      /* [k] class index -> barcode label; nullable                                       */
+    const double *thresholds;      /* [k]; nullable = no thresholding                                                  */
+} wdx_boost_model;
+/* Copies every array at set time (synchronises first). */
+int wdx_boost_set_model(wdx_ctx *ctx, const wdx_boost_model *m);
+/* d_fpt: (n, n_features) float64 DEVICE rows; d_status: nullable DEVICE int32[n], rows with status != WDX_READ_OK get
+ * pred -1 and NaN raw / probabilities / margin.  Outputs DEVICE, nullable: d_raw (n, dim) float64, d_prob (n, k) float64,
+ * d_pred int32[n], d_conf float64[n].  Enqueued on `stream`; no synchronisation.  WDX_ERR_NO_REFS without a model. */
+int wdx_boost_predict_dev(wdx_ctx *ctx, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
+                          double *d_prob, int32_t *d_pred, double *d_conf, void *stream);
+/* Fpt_Boost.predict on host buffers: X (n, n_features) float64, in row chunks; outputs host, nullable. */
+int wdx_boost_predict(wdx_ctx *ctx, const double *X, int64_t n, double *raw, double *prob, int32_t *pred, double *conf);
+/* The tRNA flow in one call: raw adapter rows -> fingerprint stage (with rp: the consensus-refinement branch, K =
+ * rp->barcode_keep_events; rp NULL: the plain fingerprint, K = p->barcode_num_events) -> boost tail.  K must equal the
+ * model's n_features (WDX_ERR_INVALID).  Needs no reference set.  Everything DEVICE, enqueued on `stream`, no
+ * synchronisation: d_status int32[n]; d_refine_idx int32 (n, 3), nullable (written with rp only); d_fpt (n, K), d_raw
+ * (n, dim), d_prob (n, k), d_pred, d_conf nullable.  Reads whose fingerprint failed get pred -1 and NaN.
+ * d_work: wdx_demux_refine_workspace_bytes(n_reads, K) bytes (without rp wdx_demux_workspace_bytes(n_reads, K) is enough). */
+int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                        int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
+                        const uint8_t *d_ok, const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt,
+                        int32_t *d_refine_idx, int32_t *d_status, double *d_raw, double *d_prob, int32_t *d_pred,
+                        double *d_conf, void *d_work, void *stream);
+
 /* ---- multi-GPU: the only exchange on the path ---------------------------------------
  * Reads shard over one process per GPU with no data-path collective; after the last batch the per-barcode
  * call histogram -- the engine's form of the reference's shared run counters `ridx_dict`
@@ -675,6 +729,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_FINGERPRINT_TAIL 8 /* fingerprint_split_tail_kernel alone (the split main kernel's second half; its time is part of
                                     WDX_K_FINGERPRINT_MAIN, which brackets the tile-kernel / tail-kernel launch pairs) */
 #define WDX_K_MLP 9              /* the MLP tail kernel (wdx_mlp_predict_dev, wdx_dtw_mlp_predict, wdx_demux_mlp_dev) */
+#define WDX_K_BOOST 10           /* the boost tail kernel (wdx_boost_predict_dev, wdx_boost_predict, wdx_demux_boost_dev) */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

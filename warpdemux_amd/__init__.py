@@ -5,6 +5,7 @@ Host side is Python over a C-ABI shared library (include/wdx.h, warpdemux_amd/cs
 * ``parallel_distances`` -- drop-in for ``warpdemux.parallel_distances`` (same four functions)
 * ``sig_proc``           -- batched ``detect_results_to_fpt`` + ``ReadResult`` mirror
 * ``engine``             -- device-resident fused pipeline (raw adapter rows -> distances -> calls)
+* ``models``             -- device counterparts of the model classes: ``DTW_SVM``, ``DTW_MLP``, ``Fpt_Boost``
 * ``dist``               -- one-process-per-GPU sharding + call-count all-reduce
 * ``synth``              -- deterministic synthetic RNA004-like adapter signals
 """

@@ -25,6 +25,7 @@ WDX_ERR_NO_REFS = -5
 
 K_FINGERPRINT, K_DTW, K_TRANSPOSE, K_COUNT, K_SVM, K_REDUCE, K_FINGERPRINT_MAIN, K_FINGERPRINT_CLIP, K_FINGERPRINT_TAIL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 K_MLP = 9
+K_BOOST = 10
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -39,6 +40,7 @@ OPT_NO_CLIP_REUSE = 14
 OPT_NO_SPLIT_TAIL = 15
 OPT_DTW_UNFUSED = 16
 OPT_MLP_CHUNK_ROWS = 17
+OPT_BOOST_CHUNK_ROWS = 18
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -60,6 +62,7 @@ EXPORTS = [
     "wdx_demux_submit_adc", "wdx_fingerprint_batch_adc", "wdx_demux_batch_adc", "wdx_calibrate_adc_dev", "wdx_feeder_run_adc",
     "wdx_demux_submit_refine", "wdx_demux_wait_refine", "wdx_demux_refine_workspace_bytes", "wdx_demux_refine_dev",
     "wdx_feeder_ring_bytes_refine", "wdx_feeder_ring_init_refine", "wdx_feeder_run_refine",
+    "wdx_boost_set_model", "wdx_boost_predict_dev", "wdx_boost_predict", "wdx_demux_boost_dev",
 ]
 
 
@@ -156,6 +159,21 @@ class MlpModelC(C.Structure):
         ("coefs", C.c_void_p * MLP_MAX_LAYERS), ("intercepts", C.c_void_p * MLP_MAX_LAYERS),
         ("scaler_mean", C.c_void_p * MLP_MAX_SCALERS), ("scaler_scale", C.c_void_p * MLP_MAX_SCALERS),
         ("label_map", C.c_void_p), ("thresholds", C.c_void_p),
+    ]
+
+
+# wdx_boost_model (include/wdx.h)
+BOOST_MAX_FEATURES, BOOST_MAX_DEPTH, BOOST_MAX_DIM = 254, 16, 16
+
+
+class BoostModelC(C.Structure):
+    """wdx_boost_model (include/wdx.h)"""
+
+    _fields_ = [
+        ("n_trees", C.c_int32), ("n_features", C.c_int32), ("dim", C.c_int32), ("n_classes", C.c_int32),
+        ("depth", C.c_void_p), ("split_feature", C.c_void_p), ("split_border", C.c_void_p), ("split_nan_true", C.c_void_p),
+        ("leaf_values", C.c_void_p), ("scale", C.c_double), ("bias", C.c_void_p), ("label_map", C.c_void_p),
+        ("thresholds", C.c_void_p),
     ]
 
 
@@ -446,6 +464,15 @@ def load():
         L.wdx_feeder_ring_init_refine.argtypes = [vp, C.c_size_t, P(FeederGeometryC), P(SegParamsC), P(RefineParamsC)]
         L.wdx_feeder_run_refine.restype = C.c_int
         L.wdx_feeder_run_refine.argtypes = [vp, P(FeederJobC), P(FeederJobAdcC), vp]
+        L.wdx_boost_set_model.restype = C.c_int
+        L.wdx_boost_set_model.argtypes = [vp, P(BoostModelC)]
+        L.wdx_boost_predict_dev.restype = C.c_int
+        L.wdx_boost_predict_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp]
+        L.wdx_boost_predict.restype = C.c_int
+        L.wdx_boost_predict.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+        L.wdx_demux_boost_dev.restype = C.c_int
+        L.wdx_demux_boost_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, P(SegParamsC), P(RefineParamsC), vp, vp, vp,
+                                          vp, vp, vp, vp, vp, vp]
         _lib = L
         return L
 

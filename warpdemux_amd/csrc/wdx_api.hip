@@ -199,11 +199,6 @@ int check_ref_length(const DtwRefs &R, const wdx_seg_params &p) {
     return WDX_ERR_INVALID;
 }
 
-struct RefineDevGuard {   // frees what fill_refine_dev made (launch_fingerprint copies it into the kernels' arguments)
-    RefineDev *&r;
-    ~RefineDevGuard() { free_refine_dev(r); }
-};
-
 // The refinement branch's device state for n_reads reads on stream s, everything but the rows themselves:
 //   * the consensus comes from the host (84 doubles) and is kept resident in B->ref_buf: uploaded only when its content
 //     changes, and then synchronously after the stream has drained (no reliance on how the runtime stages pageable copies;
@@ -211,8 +206,8 @@ struct RefineDevGuard {   // frees what fill_refine_dev made (launch_fingerprint
 //   * d_idx (nullable) starts as -1 (reads that fail before the match);
 //   * the hand-over records of the fast kernels in d_ws (null: B->ref_ws) start untouched: only the state word of every
 //     record is cleared, 4 of its 1632 bytes.
-static int refine_prepare(wdx_ctx *B, const wdx_refine_params &rp, int64_t n_reads, int32_t *d_idx, void *d_ws, hipStream_t s,
-                          RefineDev **rf) {
+int refine_prepare(wdx_ctx *B, const wdx_refine_params &rp, int64_t n_reads, int32_t *d_idx, void *d_ws, hipStream_t s,
+                   RefineDev **rf) {
     int rc = WDX_SUCCESS;
     const size_t qb = ((size_t)rp.n_query * 8 + 15) / 16 * 16;
     {
@@ -480,7 +475,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     comm_destroy(ctx);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf, &ctx->mb_ridx})
         b->release();
     ctx->pin_in.release();
@@ -520,6 +515,7 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
         case WDX_OPT_DTW_UNFUSED: ctx->knobs.dtw_unfused = (value >= 0 && value <= 3) ? (int)value : 0; break;
         case WDX_OPT_MAX_LAUNCH_SLICE: ctx->knobs.max_launch_slice = value > 0 ? value : 0; break;
         case WDX_OPT_MLP_CHUNK_ROWS: ctx->knobs.mlp_chunk_rows = value > 0 ? value : 0; break;
+        case WDX_OPT_BOOST_CHUNK_ROWS: ctx->knobs.boost_chunk_rows = value > 0 ? value : 0; break;
         default:
             set_error("unknown option %d", (int)option);
             return WDX_ERR_INVALID;

@@ -1,5 +1,6 @@
-// C ABI of libwdx_hip.so, classifier tails (include/wdx.h): the SVM and the MLP behind the DTW distances.  Host code only: the
-// kernels are in wdx_svm.hip / wdx_mlp.hip / wdx_dtw.hip.  The two tails share one host path each for "raw rows -> fingerprints
+// C ABI of libwdx_hip.so, classifier tails (include/wdx.h): the SVM and the MLP behind the DTW distances, and the boosted
+// trees on the fingerprints themselves (at the end of the file; no DTW).  Host code only: the kernels are in wdx_svm.hip /
+// wdx_mlp.hip / wdx_boost.hip / wdx_dtw.hip.  The two tails share one host path each for "raw rows -> fingerprints
 // -> DTW row blocks -> tail" (wdx_demux_{svm,mlp}_dev) and "host rows in chunks -> DTW -> tail" (wdx_dtw_{svm,mlp}_predict);
 // what differs between them -- the resident-model checks, the SVM's fused route, the MLP's counter -- is in the entry points.
 #include "wdx_ctx.h"
@@ -7,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <new>
 
 using namespace wdx;
 
@@ -512,6 +514,225 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
         return launch_mlp_predict(ctx->mlp, dblk, m, d_status + r0, d_prob ? d_prob + r0 * k : nullptr,
                                   d_pred ? d_pred + r0 : nullptr, d_conf ? d_conf + r0 : nullptr, d_n_nonfinite, s);
     });
+}
+
+// ---- Fpt_Boost: oblivious trees on the fingerprint rows (wdx_boost.hip) ----------------------------------
+
+static int boost_tail(wdx_ctx *B, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw, double *d_prob,
+                      int32_t *d_pred, double *d_conf, hipStream_t s) {
+    Timed t(B, WDX_K_BOOST, s);
+    return launch_boost_predict(B->boost, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, s);
+}
+
+int wdx_boost_set_model(wdx_ctx *ctx, const wdx_boost_model *m) {
+    WDX_ENTER(ctx);
+    // every check before anything of the resident model is touched: a refused model keeps the previous one
+    if (!m || m->n_trees < 1 || m->n_features < 1 || m->dim < 1 || m->n_classes < 2 || !m->depth || !m->leaf_values ||
+        !m->bias) {
+        set_error("boost_set_model: need >= 1 tree, >= 1 feature, >= 2 classes, depths, leaf values and a bias");
+        return WDX_ERR_INVALID;
+    }
+    const int nt = m->n_trees, F = m->n_features, dim = m->dim, k = m->n_classes;
+    if (F > WDX_BOOST_MAX_FEATURES) {
+        set_error("boost_set_model: %d features (1..%d supported)", F, WDX_BOOST_MAX_FEATURES);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (dim > 16 || k > 16) {
+        set_error("boost_set_model: %d values per leaf for %d classes (1..16 and 2..16 supported)", dim, k);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (dim != k && !(dim == 1 && k == 2)) {
+        set_error("boost_set_model: %d values per leaf for %d classes", dim, k);
+        return WDX_ERR_INVALID;
+    }
+    size_t n_splits = 0, n_leaves = 0;
+    for (int t = 0; t < nt; ++t) {
+        const int d = m->depth[t];
+        if (d < 0) {
+            set_error("boost_set_model: tree %d has depth %d", t, d);
+            return WDX_ERR_INVALID;
+        }
+        if (d > WDX_BOOST_MAX_DEPTH) {
+            set_error("boost_set_model: tree %d has depth %d (0..%d supported)", t, d, WDX_BOOST_MAX_DEPTH);
+            return WDX_ERR_UNSUPPORTED;
+        }
+        n_splits += (size_t)d;
+        n_leaves += (size_t)1 << d;
+    }
+    if (n_splits > 0x7fffffff) {
+        set_error("boost_set_model: too many splits");
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (n_splits && (!m->split_feature || !m->split_border)) {
+        set_error("boost_set_model: splits without features / borders");
+        return WDX_ERR_INVALID;
+    }
+    for (size_t i = 0; i < n_splits; ++i)
+        if (m->split_feature[i] < 0 || m->split_feature[i] >= F) {
+            set_error("boost_set_model: split %lld tests feature %d of %d", (long long)i, m->split_feature[i], F);
+            return WDX_ERR_INVALID;
+        }
+    // one device block: [doubles: leaves | bias | thresholds][trees][splits][int32: label map]
+    const size_t nd = n_leaves * dim + (size_t)dim + (m->thresholds ? (size_t)k : 0);
+    const size_t o_trees = nd * 8, o_splits = o_trees + (size_t)nt * sizeof(BoostTree);
+    const size_t o_labels = o_splits + n_splits * sizeof(BoostSplit);
+    const size_t bytes = o_labels + (m->label_map ? (size_t)k * 4 : 0);
+    std::vector<unsigned char> h;
+    try {
+        h.resize(bytes);
+    } catch (const std::bad_alloc &) {  // any number of trees is accepted: the staging copy can be refused by the host
+        set_error("boost_set_model: no host memory for a staging copy of %zu bytes", bytes);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    double *hd = reinterpret_cast<double *>(h.data());
+    memcpy(hd, m->leaf_values, n_leaves * dim * 8);
+    memcpy(hd + n_leaves * dim, m->bias, (size_t)dim * 8);
+    if (m->thresholds) memcpy(hd + n_leaves * dim + dim, m->thresholds, (size_t)k * 8);
+    BoostTree *ht = reinterpret_cast<BoostTree *>(h.data() + o_trees);
+    BoostSplit *hs = reinterpret_cast<BoostSplit *>(h.data() + o_splits);
+    {
+        size_t s0 = 0, l0 = 0;
+        for (int t = 0; t < nt; ++t) {
+            ht[t] = BoostTree{(int32_t)s0, m->depth[t], (int64_t)l0};
+            s0 += (size_t)m->depth[t];
+            l0 += ((size_t)1 << m->depth[t]) * dim;
+        }
+    }
+    for (size_t i = 0; i < n_splits; ++i)
+        hs[i] = BoostSplit{(uint32_t)m->split_feature[i] | ((m->split_nan_true && m->split_nan_true[i]) ? 0x100u : 0u),
+                           m->split_border[i]};
+    if (m->label_map) memcpy(h.data() + o_labels, m->label_map, (size_t)k * 4);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((rc = use_stream(ctx, ctx->stream))) return rc;
+    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    WDX_HIP_TRY(hipDeviceSynchronize());  // no kernel on any stream may still be reading the previous model (as the MLP's)
+    // upload into a block of its own and swap only after it has succeeded: a failed allocation or copy keeps the previous model
+    Buffer nb;
+    if ((rc = nb.ensure(bytes))) return rc;
+    if (hipError_t e = hipMemcpy(nb.p, h.data(), bytes, hipMemcpyHostToDevice); e != hipSuccess) {
+        set_error("boost_set_model: hipMemcpy of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+        nb.release();
+        return WDX_ERR_HIP;
+    }
+    ctx->boost_buf.release();
+    ctx->boost_buf = nb;
+    const unsigned char *dev = (const unsigned char *)ctx->boost_buf.p;
+    BoostDev M{};
+    M.leaves = (const double *)dev;
+    M.bias = M.leaves + n_leaves * dim;
+    M.thresholds = m->thresholds ? M.bias + dim : nullptr;
+    M.trees = (const BoostTree *)(dev + o_trees);
+    M.splits = (const BoostSplit *)(dev + o_splits);
+    M.label_map = m->label_map ? (const int32_t *)(dev + o_labels) : nullptr;
+    M.scale = m->scale;
+    M.n_trees = nt;
+    M.n_features = F;
+    M.dim = dim;
+    M.k = k;
+    ctx->boost = M;  // (every pointer of the previous model is replaced here, in one step with its block above)
+    ctx->boost_set = true;
+    return WDX_SUCCESS;
+}
+
+int wdx_boost_predict_dev(wdx_ctx *ctx, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
+                          double *d_prob, int32_t *d_pred, double *d_conf, void *stream) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->boost_set) {
+        set_error("no boost model: call wdx_boost_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (n < 0 || (n > 0 && !d_fpt)) {
+        set_error("boost_predict_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
+    return boost_tail(ctx, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, (hipStream_t)stream);
+}
+
+int wdx_boost_predict(wdx_ctx *ctx, const double *X, int64_t n, double *raw, double *prob, int32_t *pred, double *conf) {
+    WDX_ENTER(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->boost_set) {
+        set_error("no boost model: call wdx_boost_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (n < 0 || (n > 0 && !X)) {
+        set_error("boost_predict: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (n == 0) return WDX_SUCCESS;
+    hipStream_t s = ctx->stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const BoostDev &M = ctx->boost;
+    const int F = M.n_features, dim = M.dim, k = M.k;
+    // rows per pass: the float64 rows of a chunk stay <= 1 GiB.  Workspaces: in0 rows | out0 raw | out1 prob | out2 pred | out3 conf
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)1 << 30) / (8 * F)));
+    if (ctx->knobs.boost_chunk_rows > 0) chunk = std::min<int64_t>(chunk, ctx->knobs.boost_chunk_rows);
+    if ((rc = ctx->in0.ensure((size_t)(chunk * F) * 8))) return rc;
+    if ((rc = ctx->out0.ensure((size_t)(chunk * dim) * 8))) return rc;
+    if ((rc = ctx->out1.ensure((size_t)(chunk * k) * 8))) return rc;
+    if ((rc = ctx->out2.ensure((size_t)chunk * 4))) return rc;
+    if ((rc = ctx->out3.ensure((size_t)chunk * 8))) return rc;
+    StreamDrain drain(s);
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t c = std::min(chunk, n - r0);
+        WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X + r0 * F, (size_t)(c * F) * 8, hipMemcpyHostToDevice, s));
+        if ((rc = boost_tail(ctx, (const double *)ctx->in0.p, nullptr, c, (double *)ctx->out0.p, (double *)ctx->out1.p,
+                             (int32_t *)ctx->out2.p, (double *)ctx->out3.p, s)))
+            return rc;
+        if (raw) WDX_HIP_TRY(hipMemcpyAsync(raw + r0 * dim, ctx->out0.p, (size_t)(c * dim) * 8, hipMemcpyDeviceToHost, s));
+        if (prob) WDX_HIP_TRY(hipMemcpyAsync(prob + r0 * k, ctx->out1.p, (size_t)(c * k) * 8, hipMemcpyDeviceToHost, s));
+        if (pred) WDX_HIP_TRY(hipMemcpyAsync(pred + r0, ctx->out2.p, (size_t)c * 4, hipMemcpyDeviceToHost, s));
+        if (conf) WDX_HIP_TRY(hipMemcpyAsync(conf + r0, ctx->out3.p, (size_t)c * 8, hipMemcpyDeviceToHost, s));
+    }
+    WDX_HIP_TRY(hipStreamSynchronize(s));
+    drain.done();
+    return WDX_SUCCESS;
+}
+
+int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                        int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
+                        const uint8_t *d_ok, const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt,
+                        int32_t *d_refine_idx, int32_t *d_status, double *d_raw, double *d_prob, int32_t *d_pred,
+                        double *d_conf, void *d_work, void *stream) {
+    WDX_ENTER(ctx);
+    if (n_reads < 0 || !p || (rp && !rp->query) ||
+        (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
+        set_error("demux_boost_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (rp && rp->n_query < 1) {
+        set_error("consensus refinement: empty query");
+        return WDX_ERR_INVALID;
+    }
+    wdx_seg_params pv = *p;
+    if (rp) pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs
+    const int64_t K = pv.barcode_num_events;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->boost_set) {
+        set_error("demux_boost_dev needs wdx_boost_set_model first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (K != ctx->boost.n_features) {
+        set_error("%s (%lld) != the boost model's features (%d)", rp ? "barcode_keep_events" : "barcode_num_events",
+                  (long long)K, ctx->boost.n_features);
+        return WDX_ERR_INVALID;
+    }
+    if (n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    // d_work as wdx_demux_refine_dev lays it out: [fpt][fingerprint workspace] | the refinement kernels' hand-over records
+    unsigned char *w = (unsigned char *)d_work;
+    const DemuxWork W = demux_work_layout(n_reads, K, false);
+    double *fpt = d_fpt ? d_fpt : (double *)w;
+    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
+    RefineDev *rf = nullptr;
+    RefineDevGuard rf_guard{rf};
+    if (rp && (rc = refine_prepare(ctx, *rp, n_reads, d_refine_idx, w + round_up(W.bytes, 256), s, &rf))) return rc;
+    if ((rc = fingerprint_stage(ctx, in, pv, FpOut{fpt, nullptr, nullptr, d_status}, w + W.fp_ws, s, rf, rf == nullptr)))
+        return rc;
+    return boost_tail(ctx, fpt, d_status, n_reads, d_raw, d_prob, d_pred, d_conf, s);
 }
 
 }  // extern "C"

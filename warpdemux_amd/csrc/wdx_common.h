@@ -42,6 +42,7 @@ struct Knobs {
     bool no_split = false;           // WDX_OPT_NO_SPLIT_TAIL: the main fast kernel in one piece (A/B, tests)
     int dtw_unfused = 0;             // WDX_OPT_DTW_UNFUSED: 0 fused cells + settle | 1 six operations only | 2 / 3 tests, diagnostics
     int64_t mlp_chunk_rows = 0;      // WDX_OPT_MLP_CHUNK_ROWS: rows per pass of wdx_dtw_mlp_predict (0 = built-in)
+    int64_t boost_chunk_rows = 0;    // WDX_OPT_BOOST_CHUNK_ROWS: rows per pass of wdx_boost_predict (0 = built-in)
 };
 
 // A launch over more workgroups than grid.x admits is cut into slices (block_base != 0 from the second on).  The built-in
@@ -221,6 +222,30 @@ struct MlpDev {  // device-resident [StandardScaler]* + MLPClassifier + label ma
 // INCREMENTED by the rows whose (scaled) input holds a NaN or an infinity
 int launch_mlp_predict(const MlpDev &M, const float *d_dist, int64_t n, const int32_t *d_status, double *d_prob,
                        int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, hipStream_t stream);
+
+// ---- boost tail (wdx_boost.hip) --------------------------------------------------------------------
+constexpr int kMaxBoostFeatures = WDX_BOOST_MAX_FEATURES;  // (the widest fingerprint the kernels write: kSegCap)
+struct BoostTree {   // 16 bytes, read through wave-uniform loads
+    int32_t split0;  // first split of the tree in `splits`
+    int32_t depth;
+    int64_t leaf0;   // first leaf value of the tree in `leaves`
+};
+struct BoostSplit {  // 8 bytes
+    uint32_t feat;   // bits 0..7 the feature, bit 8 the NaN rule (1: a NaN feature sets the bit)
+    float border;
+};
+struct BoostDev {  // device-resident oblivious-tree ensemble + label map / thresholds
+    const BoostTree *trees;
+    const BoostSplit *splits;
+    const double *leaves, *bias;
+    const int32_t *label_map;  // nullable
+    const double *thresholds;  // nullable
+    double scale;
+    int n_trees, n_features, dim, k;
+};
+// d_status (nullable): rows with status != WDX_READ_OK get pred -1 and NaN raw / prob / conf
+int launch_boost_predict(const BoostDev &M, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
+                         double *d_prob, int32_t *d_pred, double *d_conf, hipStream_t stream);
 
 // row r of a page-locked (n, stride) host minibatch, samples [st[r], st[r] + len[r]) -> dst + off[r] (device), read over
 // the bus by a copy kernel

@@ -23,7 +23,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 10;
+constexpr int kNumTimed = 11;
 
 // RAII: make the context's device current for the duration of one entry point and put the caller's
 // device back afterwards (a host thread that also drives torch must not find its device switched).
@@ -73,6 +73,10 @@ struct wdx_ctx {
     wdx::Buffer mlp_buf;
     wdx::MlpDev mlp{};
     bool mlp_set = false;
+    // boost tail (wdx_boost_set_model): its own slot, independent of the SVM's and the MLP's
+    wdx::Buffer boost_buf;
+    wdx::BoostDev boost{};
+    bool boost_set = false;
     wdx::Comm *comm = nullptr;
     // pipelined minibatches (wdx_demux_submit / wdx_demux_wait): up to WDX_MAX_SLOTS child contexts, each with its own stream and
     // workspaces, sharing this context's resident reference set; the fields below describe a child's batch in flight
@@ -132,6 +136,14 @@ inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 // Kept as found: neither DESIGN.md nor DESIGN_HISTORY.md gives a reason.
 int fingerprint_stage(wdx_ctx *B, const FpReads &in, const wdx_seg_params &p, const FpOut &out, void *d_ws,
                       hipStream_t s, const RefineDev *rf = nullptr, bool main_events = true);
+// (wdx_api.hip) The refinement branch's device state for n_reads reads on stream s (see its definition); *rf is freed by
+// the caller's RefineDevGuard
+struct RefineDevGuard {   // frees what fill_refine_dev made (launch_fingerprint copies it into the kernels' arguments)
+    RefineDev *&r;
+    ~RefineDevGuard() { free_refine_dev(r); }
+};
+int refine_prepare(wdx_ctx *B, const wdx_refine_params &rp, int64_t n_reads, int32_t *d_idx, void *d_ws, hipStream_t s,
+                   RefineDev **rf);
 // (wdx_api.hip) "barcode_num_events != reference length" check of every entry that fingerprints and then runs the DTW
 int check_ref_length(const DtwRefs &R, const wdx_seg_params &p);
 // (wdx_api.hip) Byte offsets of the pieces of a caller's d_work, and its size (wdx_demux_workspace_bytes):

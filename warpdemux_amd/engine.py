@@ -178,7 +178,7 @@ class DemuxEngine:
         _lib.check(self.L.wdx_dtw_matrix_dev(self.ctx.handle, _dp(X), n, _dp(dist), _dp(am), self._stream()))
         return dist, am
 
-    # -- classifier tails: SVM and MLP (DTW_MLP) ---------------------------------
+    # -- classifier tails: SVM, MLP (DTW_MLP), boosted trees (Fpt_Boost; 4.8) --------
     def _ensure_work(self, n):
         need = int(self.L.wdx_demux_workspace_bytes(n, self.K))
         if self._work is None or self._work.numel() < need:
@@ -259,6 +259,62 @@ class DemuxEngine:
         (prob f64 (n,k), pred i32 (n,), conf f64 (n,), status i32 (n,), dist f32 (n,nY) or None, fpt f64 (n,K) or None)."""
         return self._demux_tail(self.L.wdx_demux_mlp_dev, self.mlp_classes, sig, a_start, a_end, offsets, stride, max_len, ok,
                                 want_dist, want_fpt, block_rows, out, _dp(n_nonfinite))
+
+    def set_boost(self, model):
+        """``model``: a warpdemux_amd.models.Fpt_Boost; its features are the fingerprint's K columns.  Needs no reference set:
+        the engine's own stays as it is."""
+        self._boost_model = model   # keeps the host arrays alive during the upload
+        m = model.to_c()
+        self.ctx._boost_owner = None
+        _lib.check(self.L.wdx_boost_set_model(self.ctx.handle, C.byref(m)))
+        self.ctx._boost_owner = model
+        self.boost_classes, self.boost_dim, self.boost_features = model.k, model.dim, model.n_features
+
+    def boost_predict(self, fpt, status=None, want_raw=False):
+        """(prob f64 (n,k), pred i32 (n,), conf f64 (n,)[, raw f64 (n,dim)]) from device (n, K) float64 fingerprints
+        (wdx_boost_predict_dev); ``status``: optional int32 (n,) device tensor, rows with a non-zero status get -1 / NaN."""
+        torch = self.torch
+        n = int(fpt.shape[0])
+        if fpt.dtype != torch.float64 or not fpt.is_contiguous() or fpt.dim() != 2 or int(fpt.shape[1]) != self.boost_features:
+            raise ValueError(f"fpt must be a contiguous float64 (n, {self.boost_features}) device tensor")
+        prob = torch.empty((n, self.boost_classes), dtype=torch.float64, device=self.tdev)
+        pred = torch.empty(n, dtype=torch.int32, device=self.tdev)
+        conf = torch.empty(n, dtype=torch.float64, device=self.tdev)
+        raw = torch.empty((n, self.boost_dim), dtype=torch.float64, device=self.tdev) if want_raw else None
+        _lib.check(self.L.wdx_boost_predict_dev(self.ctx.handle, _dp(fpt), _dp(status), n, _dp(raw), _dp(prob), _dp(pred),
+                                                _dp(conf), self._stream()))
+        return (prob, pred, conf, raw) if want_raw else (prob, pred, conf)
+
+    def demux_boost(self, sig, a_start, a_end, refine=None, *, offsets=None, stride=0, max_len: int, ok=None, want_fpt=False,
+                    want_raw=False):
+        """The tRNA flow in one call (wdx_demux_boost_dev): raw rows -> fingerprint (with ``refine``, a RefineParams: the
+        consensus-refinement branch, K = refine.barcode_keep_events; else K = params.barcode_num_events) -> boost tail, on
+        the current stream.  Returns (prob f64 (n,k), pred i32 (n,), conf f64 (n,), status i32 (n,), refine_idx i32 (n,3) or
+        None, fpt f64 (n,K) or None, raw f64 (n,dim) or None)."""
+        torch = self.torch
+        n = int(a_start.shape[0])
+        if offsets is None and not stride:
+            if sig.dim() != 2:
+                raise ValueError("packed reads need `offsets`, a minibatch needs 2-D `sig` or `stride`")
+            stride = int(sig.shape[1])
+        K = int(refine.barcode_keep_events) if refine is not None else int(self.params.barcode_num_events)
+        prob = torch.empty((n, self.boost_classes), dtype=torch.float64, device=self.tdev)
+        pred = torch.empty(n, dtype=torch.int32, device=self.tdev)
+        conf = torch.empty(n, dtype=torch.float64, device=self.tdev)
+        status = torch.empty(n, dtype=torch.int32, device=self.tdev)
+        idx = torch.empty((n, 3), dtype=torch.int32, device=self.tdev) if refine is not None else None
+        fpt = torch.empty((n, K), dtype=torch.float64, device=self.tdev) if want_fpt else None
+        raw = torch.empty((n, self.boost_dim), dtype=torch.float64, device=self.tdev) if want_raw else None
+        need = int(self.L.wdx_demux_refine_workspace_bytes(n, K))
+        if self._refine_work is None or self._refine_work.numel() < need:
+            self._refine_work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
+        pc = self.params.to_c()
+        rc = refine.to_c() if refine is not None else None
+        _lib.check(self.L.wdx_demux_boost_dev(
+            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+            C.byref(pc), C.byref(rc) if rc is not None else None, _dp(fpt), _dp(idx), _dp(status), _dp(raw), _dp(prob),
+            _dp(pred), _dp(conf), _dp(self._refine_work), self._stream()))
+        return prob, pred, conf, status, idx, fpt, raw
 
     # -- synthetic inputs, generated in HBM ----------------------------------------------------------
     def synth_packed(self, spec: synth.SynthSpec, first_read: int, n_reads: int):

@@ -1,4 +1,5 @@
-"""MI355X counterparts of ``warpdemux.models.dtw_svm.DTW_SVM`` and ``dtw_mlp.DTW_MLP``.
+"""MI355X counterparts of ``warpdemux.models.dtw_svm.DTW_SVM``, ``dtw_mlp.DTW_MLP`` and
+``fpt_boost.Fpt_Boost`` (at the end of the file: oblivious trees on the fingerprints themselves, no DTW).
 
 Same ``predict`` signature and outputs as the reference (/root/reference/warpdemux/models/dtw_svm.py:54-98):
 DTW distances to ``_X`` -> ``exp(-gamma * d**pwr_dist)`` -> ``SVC.predict_proba`` -> ``process_probs``
@@ -287,6 +288,222 @@ class DTW_MLP(_ResidentDTWModel):
         return y_pred, y_prob
 
 
+_NAN_TRUE = {"AsIs": 0, "AsFalse": 0, "AsTrue": 1}   # features_info.float_features[*].nan_value_treatment
+
+
+class Fpt_Boost:
+    """``warpdemux.models.fpt_boost.Fpt_Boost`` with the classifier resident on one GPU context (wdx_boost.hip; DESIGN.md
+    4.8): an ensemble of oblivious trees over the float64 fingerprint (rounded to float32 once) -> ``scale * sum + bias`` ->
+    softmax / sigmoid -> ``process_probs``.  No DTW and no reference set.  The contract is the NumPy restatement in
+    tests/helpers/boost_ref.py; parity with CatBoost's own evaluation is not pinned.
+
+    ``trees``: a sequence of ``(features int[depth], borders float32[depth], nan_true bool[depth], leaves float64
+    (2**depth, dim))``; split ``i`` of a tree sets bit ``i`` of the leaf index, ``leaves[leaf, c]`` is class ``c``'s value.
+    The boost slot of the context is separate from the SVM's and the MLP's."""
+
+    _owner_attr = "_boost_owner"
+
+    def __init__(self, trees, n_features: int, scale: float, bias, label_mapper: Optional[Dict[int, int]],
+                 thresholds: Optional[np.ndarray] = None, n_classes: Optional[int] = None, noise_class: bool = False,
+                 device: Optional[int] = None):
+        bias = np.atleast_1d(np.asarray(bias, dtype=np.float64))
+        self.dim = int(bias.size)
+        self.k = 2 if self.dim == 1 else self.dim
+        self.n_features = int(n_features)
+        self._depth = np.array([len(t[0]) for t in trees], dtype=np.int32)
+        cat = lambda i, dt: np.ascontiguousarray(   # noqa: E731
+            np.concatenate([np.asarray(t[i], dtype=dt).ravel() for t in trees]) if len(trees) else np.zeros(0, dt), dtype=dt)
+        self._split_feature = cat(0, np.int32)
+        self._split_border = cat(1, np.float32)
+        self._split_nan_true = cat(2, np.uint8)
+        for t, d in zip(trees, self._depth):
+            if np.asarray(t[3]).size != (1 << int(d)) * self.dim or not (len(t[1]) == len(t[2]) == d):
+                raise ValueError(f"a tree of depth {d} needs {d} borders / NaN rules and {(1 << int(d)) * self.dim} leaf values")
+        self._leaf_values = cat(3, np.float64)
+        self.scale = float(scale)
+        self._bias = np.ascontiguousarray(bias)
+        self.label_mapper = None if label_mapper is None else dict(label_mapper)
+        self.thresholds = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        self.n_classes, self.noise_class = n_classes, noise_class
+        self._device = device
+        self._check_limits()
+        if self.label_mapper:
+            self._label_arr = np.array([self.label_mapper[i] for i in range(self.k)], dtype=np.int32)
+        if self.thresholds is not None and self.thresholds.size != self.k:
+            raise ValueError(f"{self.thresholds.size} thresholds for {self.k} classes")
+
+    def _check_limits(self):
+        """The kernel's limits (include/wdx.h), refused here as the library would."""
+        if len(self._depth) < 1:   # (an untrained model: predict says so)
+            return
+        if not 1 <= self.n_features <= _lib.BOOST_MAX_FEATURES:
+            raise NotImplementedError(f"{self.n_features} features (1..{_lib.BOOST_MAX_FEATURES} supported)")
+        if self._depth.max() > _lib.BOOST_MAX_DEPTH:
+            raise NotImplementedError(f"tree depth {int(self._depth.max())} (0..{_lib.BOOST_MAX_DEPTH} supported)")
+        if self.dim > _lib.BOOST_MAX_DIM:
+            raise NotImplementedError(f"{self.dim} classes (2..{_lib.BOOST_MAX_DIM} supported)")
+        if self._split_feature.size and not (0 <= self._split_feature.min() and self._split_feature.max() < self.n_features):
+            raise ValueError("a split tests a feature the model does not have")
+
+    # -- loaders: the two conventions of CatBoost's JSON model format are fixed HERE (and in the tests' restatement) ------
+    @classmethod
+    def from_json(cls, path_or_dict, label_mapper, thresholds=None, n_classes=None, noise_class=False,
+                  device: Optional[int] = None) -> "Fpt_Boost":
+        """From a CatBoost JSON model (``save_model(..., format="json")``), a path or the parsed dict.  Read:
+        ``oblivious_trees[*].splits[*].{float_feature_index, border, split_type}`` (``splits[i]`` sets bit ``i`` of the leaf
+        index), ``oblivious_trees[*].leaf_values`` (leaf-major, class fastest: ``leaf_values[leaf * dim + c]``),
+        ``features_info.float_features[*].nan_value_treatment``, ``scale_and_bias`` and the class count
+        (``model_info.class_params``, else the length of the bias)."""
+        if isinstance(path_or_dict, dict):
+            js = path_or_dict
+        else:
+            import json
+
+            with open(path_or_dict) as fh:
+                js = json.load(fh)
+        if "oblivious_trees" not in js:
+            if "trees" in js:
+                raise NotImplementedError("non-symmetric trees are not supported (oblivious trees only)")
+            raise ValueError("not a CatBoost JSON model: no 'oblivious_trees'")
+        info = js.get("features_info", {})
+        for key, what in (("categorical_features", "categorical"), ("text_features", "text"),
+                          ("embedding_features", "embedding"), ("ctrs", "categorical (ctr)")):
+            if info.get(key):
+                raise NotImplementedError(f"{what} features are not supported (float features only)")
+        ff = info.get("float_features") or []
+        if not ff:
+            raise ValueError("no float features in features_info")
+        # a split names a float feature by its position in float_features; the column of X is its flat index
+        column = [int(f.get("flat_feature_index", f.get("feature_index", i))) for i, f in enumerate(ff)]
+        nan_true = []
+        for f in ff:
+            tr = f.get("nan_value_treatment", "AsIs")
+            if tr not in _NAN_TRUE:
+                raise NotImplementedError(f"nan_value_treatment {tr!r}")
+            nan_true.append(_NAN_TRUE[tr])
+        n_features = max(column) + 1
+        sb = js.get("scale_and_bias", [1.0, [0.0]])
+        scale = float(sb[0])
+        bias = np.atleast_1d(np.asarray(sb[1], dtype=np.float64))
+        trees_js = js["oblivious_trees"]
+        if not trees_js:
+            raise ValueError("a boost model needs at least one tree")
+        # values per leaf: the first tree's table over its leaf count
+        d0 = len(trees_js[0].get("splits") or [])
+        dim, rem = divmod(len(trees_js[0]["leaf_values"]), 1 << min(d0, 40))
+        if rem or dim < 1:
+            raise ValueError("leaf_values is not a multiple of 2**depth")
+        if bias.size == 1 and dim > 1:
+            bias = np.repeat(bias, dim)
+        if bias.size != dim:
+            raise ValueError(f"{bias.size} bias values for {dim} values per leaf")
+        cp = (js.get("model_info") or {}).get("class_params") or {}
+        names = cp.get("class_names") or cp.get("class_to_label") or []
+        k = len(names) if names else (2 if dim == 1 else dim)
+        if k != (2 if dim == 1 else dim):
+            raise ValueError(f"{k} classes for {dim} values per leaf")
+        if dim > _lib.BOOST_MAX_DIM:
+            raise NotImplementedError(f"{dim} classes (2..{_lib.BOOST_MAX_DIM} supported)")
+        trees = []
+        for t in trees_js:
+            sp = t.get("splits") or []
+            if len(sp) > _lib.BOOST_MAX_DEPTH:
+                raise NotImplementedError(f"tree depth {len(sp)} (0..{_lib.BOOST_MAX_DEPTH} supported)")
+            for s_ in sp:
+                if s_.get("split_type", "FloatFeature") != "FloatFeature":
+                    raise NotImplementedError(f"split type {s_.get('split_type')!r} is not supported (FloatFeature only)")
+            idx = [int(s_["float_feature_index"]) for s_ in sp]
+            if any(i < 0 or i >= len(ff) for i in idx):
+                raise ValueError("a split names a float feature the model does not have")
+            lv = np.asarray(t["leaf_values"], dtype=np.float64)
+            if lv.size != (1 << len(sp)) * dim:
+                raise ValueError(f"a tree of depth {len(sp)} has {lv.size} leaf values, expected {(1 << len(sp)) * dim}")
+            trees.append(([column[i] for i in idx], [np.float32(s_["border"]) for s_ in sp], [nan_true[i] for i in idx],
+                          lv.reshape(1 << len(sp), dim)))
+        return cls(trees, n_features, scale, bias, label_mapper, thresholds, n_classes=n_classes, noise_class=noise_class,
+                   device=device)
+
+    @classmethod
+    def from_reference(cls, model, device: Optional[int] = None) -> "Fpt_Boost":
+        """From a reference ``Fpt_Boost`` instance: ``model.model.save_model(tmp, format="json")`` in a temporary
+        directory, then ``from_json``.  (``model.model`` is only asked to write itself; nothing here imports its library.)"""
+        import os
+        import tempfile
+
+        if getattr(model, "model", None) is None:
+            msg = "Model not trained."
+            logging.error(msg)
+            raise ValueError(msg)
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "model.json")
+            model.model.save_model(path, format="json")
+            return cls.from_json(path, model.label_mapper, model.thresholds, n_classes=getattr(model, "n_classes", None),
+                                 noise_class=getattr(model, "noise_class", False), device=device)
+
+    @property
+    def is_trained(self):
+        return len(self._depth) > 0
+
+    @property
+    def num_bcs(self) -> int:
+        """fpt_base.py:37-46"""
+        if self.n_classes is not None:
+            return self.n_classes
+        if self.label_mapper is not None:
+            return len(self.label_mapper) - self.noise_class
+        raise ValueError("Label mapper or n_classes not set.")
+
+    def to_c(self) -> "_lib.BoostModelC":
+        """wdx_boost_model view of the host arrays (valid while ``self`` is alive)."""
+        return _lib.BoostModelC(
+            int(self._depth.size), self.n_features, self.dim, self.k, self._depth.ctypes.data,
+            self._split_feature.ctypes.data, self._split_border.ctypes.data, self._split_nan_true.ctypes.data,
+            self._leaf_values.ctypes.data, self.scale, self._bias.ctypes.data,
+            self._label_arr.ctypes.data if self.label_mapper else None,
+            None if self.thresholds is None else self.thresholds.ctypes.data,
+        )
+
+    def _ensure_resident(self):
+        ctx = _lib.default_context(self._device)
+        if getattr(ctx, self._owner_attr, None) is not self:
+            setattr(ctx, self._owner_attr, None)
+            m = self.to_c()
+            _lib.check(_lib.load().wdx_boost_set_model(ctx.handle, C.byref(m)))
+            setattr(ctx, self._owner_attr, self)
+        return ctx
+
+    def predict_raw(self, X: np.ndarray):
+        """(raw float64 (n, dim), y_prob float64 (n, k), y_pred int64 (n,), conf float64 (n,)) of ``X`` (n, n_features)."""
+        if not self.is_trained:
+            msg = "Model not trained."
+            logging.error(msg)
+            raise ValueError(msg)
+        if not self.label_mapper:
+            msg = "Label mapper not set."
+            logging.error(msg)
+            raise ValueError(msg)
+        X = np.asarray(X)
+        if X.ndim == 1:
+            X = X.reshape(1, -1)
+        if X.ndim != 2 or X.shape[1] != self.n_features:
+            raise ValueError(f"X must have the model's number of features as columns  ({self.n_features}).")
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = X.shape[0]
+        ctx = self._ensure_resident()
+        raw, y_prob = np.empty((n, self.dim), dtype=np.float64), np.empty((n, self.k), dtype=np.float64)
+        y_pred, conf = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64)
+        _lib.check(_lib.load().wdx_boost_predict(ctx.handle, _lib.ptr(X), n, _lib.ptr(raw), _lib.ptr(y_prob), _lib.ptr(y_pred),
+                                                 _lib.ptr(conf)))
+        return raw, y_prob, y_pred.astype(np.int64), conf
+
+    def predict(self, X: np.ndarray, return_df: bool = False, **kwargs) -> Union[Tuple[np.ndarray, np.ndarray], "object"]:
+        """(y_pred, conf) or the predictions DataFrame -- fpt_boost.py:14-52.  Additional arguments are accepted and ignored."""
+        _, y_prob, y_pred, conf = self.predict_raw(X)
+        if return_df:
+            return predictions_to_df(y_pred, y_prob, conf, self.label_mapper)
+        return y_pred, conf
+
+
 def from_reference(model, device: Optional[int] = None):
     """Device counterpart of a loaded reference model (``warpdemux.file_proc.load_model``), by its class name."""
     name = type(model).__name__
@@ -294,4 +511,6 @@ def from_reference(model, device: Optional[int] = None):
         return DTW_SVM.from_reference(model, device=device)
     if name == "DTW_MLP":
         return DTW_MLP.from_reference(model, device=device)
-    raise NotImplementedError(f"no device model for {name} (DTW_SVM and DTW_MLP are supported)")
+    if name == "Fpt_Boost":
+        return Fpt_Boost.from_reference(model, device=device)
+    raise NotImplementedError(f"no device model for {name} (DTW_SVM, DTW_MLP and Fpt_Boost are supported)")
