@@ -134,6 +134,9 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
                                          * (diagnostic: NOT the reference's results) */
 #define WDX_OPT_MLP_CHUNK_ROWS 17       /* wdx_dtw_mlp_predict: rows per DTW + MLP pass (0 = built-in; tests walk several chunks) */
 #define WDX_OPT_BOOST_CHUNK_ROWS 18     /* wdx_boost_predict: rows per pass (0 = built-in; tests walk several chunks) */
+#define WDX_OPT_BOOST_KERNEL 19         /* boost tail: 0 (default) the kernel is chosen by batch size (WDX_BOOST_SMALL_MAX_READS) |
+                                         * 1 the lane-per-read kernel only | 2 the tree-parallel kernel only (A/B, tests); both
+                                         * give the same bits */
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -297,6 +300,16 @@ int wdx_demux_wait(wdx_ctx *ctx, int32_t slot, double *fpt, float *dist, int32_t
 #define WDX_WANT_DWELL 0x04u /* dwell (n, K) int64                                        */
 #define WDX_WANT_STATS 0x08u /* stats (n, 6) float64 (order: wdx_fingerprint_batch)       */
 #define WDX_WANT_SVM 0x10u   /* prob (n, k) float64, pred int32[n], conf float64[n]       */
+/* WDX_WANT_BOOST (0x40, below WDX_WANT_REFINE_IDX): prob / pred / conf of the resident BOOST model (wdx_boost_set_model) on
+ * the fingerprints this minibatch produced -- the tRNA models' classifier; wdx_demux_submit_ex, _adc and _refine take it.
+ *   - never together with WDX_WANT_SVM (WDX_ERR_INVALID); without a resident boost model WDX_ERR_NO_REFS; K (refine:
+ *     rp->barcode_keep_events) must equal the model's n_features (WDX_ERR_INVALID); a refused submit leaves the slot free
+ *   - n_refs == 0 is legal on wdx_demux_submit_ex / _adc when, and only when, this bit is set: no reference set is needed,
+ *     call is -1 for every read, WDX_WANT_DIST is WDX_ERR_INVALID.  With resident references and n_refs = nY the DTW, call
+ *     and dist run as before, beside the boost tail
+ *   - a read whose status is not 0 gets pred -1 and NaN prob / conf
+ *   - wdx_demux_wait_ex / _refine hand prob / pred / conf over when the slot asked for either tail
+ * Bit-identical to wdx_fingerprint[_refine]_batch followed by wdx_boost_predict on those fingerprints. */
 typedef struct wdx_minibatch_in {
     const float *sig;          /* (n_reads, stride) rows, or the packed rows when row_off != NULL             */
     int64_t n_reads, stride;   /* stride is ignored for packed rows                                          */
@@ -372,7 +385,8 @@ int wdx_calibrate_adc_dev(wdx_ctx *ctx, const int16_t *d_adc, const int64_t *d_r
  *                 (WDX_ERR_INVALID otherwise); WDX_WANT_SVM as in wdx_demux_submit_ex -- a read whose status is not 0,
  *                 WDX_READ_FAIL_CONSENSUS included, gets pred -1 and NaN prob / conf
  *   n_refs == 0   fingerprint only: no resident references are needed, nothing behind the fingerprint stage runs, call
- *                 is -1 for every read; WDX_WANT_DIST / WDX_WANT_SVM are WDX_ERR_INVALID
+ *                 is -1 for every read; WDX_WANT_DIST / WDX_WANT_SVM are WDX_ERR_INVALID (WDX_WANT_BOOST is served: the boost
+ *                 tail needs no references)
  * Limits and their codes are those of wdx_fingerprint_refine_batch (n_query 1..96, num_events <= 127).
  * WDX_WANT_REFINE_IDX asks for refine_idx (n, 3) int32 -- the numbers wdx_fingerprint_refine_batch returns for the same
  * reads, whichever way the rows came in: sig_barcode_start counts from the first sample of the read's adapter window
@@ -381,6 +395,7 @@ int wdx_calibrate_adc_dev(wdx_ctx *ctx, const int16_t *d_adc, const int64_t *d_r
  * slot stays busy) when it did not; wdx_demux_wait_ex completes a refine slot that did not ask for refine_idx and refuses
  * one that did.  Bit-identical to wdx_fingerprint_refine_batch [+ wdx_dtw_matrix + wdx_dtw_svm_predict] on the same rows. */
 #define WDX_WANT_REFINE_IDX 0x20u /* refine_idx (n, 3) int32, as wdx_fingerprint_refine_batch */
+#define WDX_WANT_BOOST 0x40u      /* prob (n, k) float64, pred int32[n], conf float64[n] of the resident boost model */
 int wdx_demux_submit_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, const wdx_minibatch_adc_in *in_adc,
                             const wdx_seg_params *p, const wdx_refine_params *rp, int64_t n_refs, uint32_t want);
 int wdx_demux_wait_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *out, int32_t *refine_idx);
@@ -443,6 +458,12 @@ int wdx_host_unregister(void *p);
  *                                        reverse, is WDX_ERR_INVALID
  *        wdx_feeder_demux(ring, ...)     wdx_demux_batch's arguments through wdx_feeder_run (status, call, dist)
  *        wdx_feeder_predict(ring, X, ..) DTW_SVM.predict on (n, n_events) float64 fingerprints the worker holds
+ *        wdx_feeder_predict_boost(..)    Fpt_Boost.predict on them: the server calls wdx_boost_predict
+ *      WDX_WANT_BOOST in a job's `want` (plain and refine rings, rings with n_refs == 0 included; the ring needs n_classes > 0
+ *      and n_events > 0; never together with WDX_WANT_SVM): prob / pred / conf of the serving context's boost model
+ *      (wdx_boost_set_model).  Checked per minibatch: a model whose k is not the ring's n_classes, or whose n_features is not
+ *      n_events, answers that minibatch WDX_ERR_INVALID and the ring keeps serving.  A plain ring with n_refs == 0 serves
+ *      minibatches with WDX_WANT_BOOST only.
  *        wdx_feeder_stop(ring)           ends wdx_feeder_serve: minibatches in flight are finished and handed over, READY
  *                                        ones that were never submitted are answered WDX_ERR_NO_DEVICE, new claims are
  *                                        refused
@@ -454,7 +475,7 @@ int wdx_host_unregister(void *p);
 typedef struct wdx_feeder_geometry {
     int32_t n_slots;
     int32_t n_events;    /* K of fpt / dwell (0: no room for WDX_WANT_FPT / _DWELL / _STATS)      */
-    int32_t n_classes;   /* k of prob (0: no room for WDX_WANT_SVM / wdx_feeder_predict), <= 16  */
+    int32_t n_classes;   /* k of prob (0: no room for WDX_WANT_SVM / WDX_WANT_BOOST / wdx_feeder_predict[_boost]), <= 16 */
     int32_t sample_format; /* WDX_FEEDER_SAMPLES_*: what a slot's sample region holds (0 = float32)  */
     int64_t max_reads, max_stride, n_refs;
 } wdx_feeder_geometry;
@@ -513,6 +534,7 @@ int wdx_feeder_run_refine(void *ring, const wdx_feeder_job *job, const wdx_feede
 int wdx_feeder_demux(void *ring, const float *sig, int64_t n_reads, int64_t stride, const int32_t *a_start,
                      const int32_t *a_end, const uint8_t *ok, int64_t n_refs, float *dist, int32_t *call, int32_t *status);
 int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int32_t *pred, double *conf);
+int wdx_feeder_predict_boost(void *ring, const double *X, int64_t n, double *prob, int32_t *pred, double *conf);
 int wdx_feeder_stop(void *ring);
 int wdx_feeder_served(void *ring, int64_t *minibatches);   /* minibatches handed back so far */
 /* served minibatches, slots taken back from dead workers, slots FREE right now (outputs nullable) */
@@ -650,6 +672,14 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
  *      resident. */
 #define WDX_BOOST_MAX_FEATURES 254
 #define WDX_BOOST_MAX_DEPTH 16
+/* Two kernels serve the tail (wdx_boost.hip), with the same bits in every output: one lane per read (large batches), and
+ * a tree-parallel one for minibatch-sized batches -- a workgroup per WDX_BOOST_SMALL_READS reads, the trees in chunks of
+ * WDX_BOOST_TREE_CHUNK.  By default a call of at most WDX_BOOST_SMALL_MAX_READS rows takes the tree-parallel kernel (the
+ * largest batch of the sweep in DESIGN.md 4.8, at every point of which it was the faster one; nothing beyond it has been
+ * measured, so larger calls stay on the lane-per-read kernel). */
+#define WDX_BOOST_SMALL_READS 16
+#define WDX_BOOST_TREE_CHUNK 1024
+#define WDX_BOOST_SMALL_MAX_READS 65536
 typedef struct wdx_boost_model {
     int32_t n_trees;
     int32_t n_features;            /* columns of a fingerprint row                                                     */
@@ -666,7 +696,10 @@ typedef struct wdx_boost_model {
     const int32_t *label_map;      /* [k] class index -> barcode label; nullable                                       */
     const double *thresholds;      /* [k]; nullable = no thresholding                                                  */
 } wdx_boost_model;
-/* Copies every array at set time (synchronises first). */
+/* Copies every array at set time.  It waits for the device first, so the boost tails of minibatches already submitted
+ * (WDX_WANT_BOOST) have finished with the previous model: they hand over its answers, and every later submit reads the new
+ * one (wdx_svm_set_model's rule: a slot in flight keeps what it was submitted with).  The class count a slot's prob is
+ * sized by is fixed at its submit. */
 int wdx_boost_set_model(wdx_ctx *ctx, const wdx_boost_model *m);
 /* d_fpt: (n, n_features) float64 DEVICE rows; d_status: nullable DEVICE int32[n], rows with status != WDX_READ_OK get
  * pred -1 and NaN raw / probabilities / margin.  Outputs DEVICE, nullable: d_raw (n, dim) float64, d_prob (n, k) float64,
@@ -729,7 +762,8 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_FINGERPRINT_TAIL 8 /* fingerprint_split_tail_kernel alone (the split main kernel's second half; its time is part of
                                     WDX_K_FINGERPRINT_MAIN, which brackets the tile-kernel / tail-kernel launch pairs) */
 #define WDX_K_MLP 9              /* the MLP tail kernel (wdx_mlp_predict_dev, wdx_dtw_mlp_predict, wdx_demux_mlp_dev) */
-#define WDX_K_BOOST 10           /* the boost tail kernel (wdx_boost_predict_dev, wdx_boost_predict, wdx_demux_boost_dev) */
+#define WDX_K_BOOST 10           /* the boost tail, whichever of its two kernels ran (wdx_boost_predict_dev, wdx_boost_predict,
+                                    wdx_demux_boost_dev, WDX_WANT_BOOST minibatches) */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

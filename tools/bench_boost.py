@@ -1,6 +1,7 @@
 """Fpt_Boost tail: the boost kernel alone, and the tRNA flow in one call with and without it.
 
     python tools/bench_boost.py [--out profiles/NAME.json] [--parent-tree DIR] [--rows N] [--reads N]
+    python tools/bench_boost.py --sweep [--out profiles/NAME.json] [--launches N]
 
 The sizes of the shipped tRNA models are not known here (their files are not available), so two ASSUMED sizes stand in:
 CatBoost's defaults (1 000 trees, depth 6, 4 classes) and a small model (100 trees, depth 4, 4 classes), both over the 25
@@ -13,6 +14,13 @@ leaves are gathered).
                its library built), on the same seeded reads -- the baseline;
            (b) `demux_refine` of this tree;
            (c) `demux_boost` with each model: reads/s, WDX_K_BOOST per call and its share of fingerprint + boost kernel time.
+  --sweep  the two boost kernels against each other on minibatch-sized batches (WDX_OPT_BOOST_KERNEL): the
+           HIP-event time of ONE wdx_boost_predict_dev launch for n in SWEEP_N and both models, options 1 (lane per read, the
+           baseline) and 2 (tree-parallel) alternated in one process, every shape warmed up, --launches launches per point
+           and pass, two passes per kernel; the spread of a point is the larger of the two kernels' differences between
+           their passes' medians.  `n_small` = the largest swept n up to which, for BOTH models, the tree-parallel median
+           beats the baseline's by more than that spread (0 if it does not at n = 1000): the value
+           WDX_BOOST_SMALL_MAX_READS is set from.
 The alternative a user had before -- fingerprints to the host and CatBoost with thread_count=1 -- is NOT measured: CatBoost is
 not installed here.  One JSON document on stdout (and in --out).
 """
@@ -118,6 +126,77 @@ def leg_kernel(rows, reps):
     return out
 
 
+SWEEP_N = (64, 256, 512, 1000, 4096, 16384, 65536)
+
+
+def leg_sweep(launches):
+    import torch
+
+    from warpdemux_amd import _lib
+
+    eng, *_ = _engine_and_reads(8)
+    gen = torch.Generator(eng.tdev).manual_seed(1)
+    X = torch.randn((max(SWEEP_N), K_FPT), dtype=torch.float64, device=eng.tdev, generator=gen)
+    names = {1: "lane_per_read", 2: "tree_parallel"}
+
+    def point(option, x):
+        """per-launch HIP-event times (ms) of `launches` launches"""
+        eng.ctx.set_option(_lib.OPT_BOOST_KERNEL, option)
+        ms = []
+        for _ in range(launches):
+            eng.kernel_time_reset()
+            eng.boost_predict(x)
+            ms.append(eng.kernel_time(_lib.K_BOOST)[0])
+        return ms
+
+    out, wins = {}, {}
+    eng.kernel_timing(True)
+    try:
+        for name in MODELS:
+            eng.set_boost(_model(name))
+            table = {}
+            for n in SWEEP_N:
+                x = X[:n].contiguous()
+                same = True
+                for option in (1, 2):   # warm-up of the shape under both kernels, and the two must agree
+                    eng.ctx.set_option(_lib.OPT_BOOST_KERNEL, option)
+                    res = [t.clone() for t in eng.boost_predict(x, want_raw=True)]
+                    for _ in range(10):
+                        eng.boost_predict(x)
+                    if option == 1:
+                        first = res
+                    else:
+                        same = all(torch.equal(a, b) for a, b in zip(first, res))
+                torch.cuda.synchronize()
+                passes = {1: [], 2: []}
+                for _ in range(2):
+                    for option in (1, 2):
+                        passes[option].append(point(option, x))
+                row = dict(bit_identical=bool(same))
+                for option in (1, 2):
+                    meds = [float(np.median(p)) for p in passes[option]]
+                    row[names[option]] = dict(median_ms=float(np.median(np.concatenate(passes[option]))), pass_medians_ms=meds,
+                                              spread_ms=abs(meds[0] - meds[1]), min_ms=float(np.min(passes[option])))
+                spread = max(row[names[1]]["spread_ms"], row[names[2]]["spread_ms"])
+                gain = row[names[1]]["median_ms"] - row[names[2]]["median_ms"]
+                row.update(spread_ms=spread, gain_ms=gain, tree_parallel_wins=bool(gain > spread),
+                           speedup=row[names[1]]["median_ms"] / row[names[2]]["median_ms"])
+                table[str(n)] = row
+                wins.setdefault(n, []).append(row["tree_parallel_wins"])
+            out[name] = table
+    finally:
+        eng.ctx.set_option(_lib.OPT_BOOST_KERNEL, 0)
+        eng.close()
+    n_small = 0
+    if all(wins[1000]):
+        for n in SWEEP_N:
+            if not all(wins[n]):
+                break
+            n_small = n
+    return dict(launches_per_point_and_pass=launches, passes=2, sweep=out, n_small=n_small,
+                built_with_small_max_reads=_lib.BOOST_SMALL_MAX_READS)
+
+
 def leg_flow(n, reps):
     from warpdemux_amd import _lib
 
@@ -142,11 +221,22 @@ def main():
     ap.add_argument("--reads", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--leg-a", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--sweep", action="store_true", help="the two boost kernels on minibatch-sized batches (see above)")
+    ap.add_argument("--launches", type=int, default=200)
     args = ap.parse_args()
     if args.leg_a:   # child process: sys.path[0] is the parent tree
         print(json.dumps(leg_demux_refine(args.reads, args.reps)))
         return
     sys.path.insert(0, ROOT)
+    if args.sweep:
+        doc = dict(assumption="model sizes are assumed (CatBoost defaults and a small model)", n_features=K_FPT,
+                   **leg_sweep(args.launches))
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(text + "\n")
+        return
     doc = dict(assumption="model sizes are assumed (CatBoost defaults and a small model): the shipped tRNA models' sizes are "
                           "unknown; parity with CatBoost is unpinned and the host CatBoost path is not measured",
                n_features=K_FPT, reps=args.reps)

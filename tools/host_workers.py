@@ -26,6 +26,11 @@ modes   sync   sig_proc.demux_batch on a pageable minibatch (what an unmodified 
                the classifier of those models runs on the host.  sync = sig_proc.fingerprint_refine_batch on each worker's
                own context (all there was before the refine minibatch paths), pipe = MinibatchPipeline(None, refine=...),
                feeder = Feeder(refine=...) without references; pipe and feeder also take --adc
+--boost NAME   with --refine --mode feeder: the feeder holds an Fpt_Boost model of an ASSUMED size (tools/bench_boost.py:
+               default_1000x6x4 or small_100x4x4) and every worker calls detect_and_predict[_adc] -- the ReadResult arrays
+               AND the prediction from one pass (WDX_WANT_BOOST); without it the same run is fingerprint-only, which is all
+               the host-fed paths did for a tRNA run before.  The prediction is checked against the model's own host call
+               on the returned fingerprints in a child process after the timed loop
 
 The parent never touches the GPU; every child creates its context after the fork.  Each worker checks its results
 against the CPU oracle once (outside the timed loop).  Prints one JSON line.
@@ -148,7 +153,10 @@ def refine_loop(wid, args, start, q, feeder=None):
             fb = pipe.wait((k - 1) & 1).fingerprints
             n += 1
         else:
-            if feeder is not None:
+            if feeder is not None and args.boost:
+                both = (lambda: feeder.detect_and_predict_adc(mb, *cal, a_s, a_e)) if args.adc else (lambda: feeder.detect_and_predict(mb, a_s, a_e))
+                call = lambda: both()[0]    # noqa: E731
+            elif feeder is not None:
                 call = (lambda: feeder.fingerprint_batch_adc(mb, *cal, a_s, a_e)) if args.adc else (lambda: feeder.fingerprint_batch(mb, a_s, a_e))
             else:
                 call = lambda: sig_proc.fingerprint_refine_batch(mb, a_s, a_e, hp, hr)    # noqa: E731
@@ -165,7 +173,12 @@ def refine_loop(wid, args, start, q, feeder=None):
         dt = time.perf_counter() - t0
         if pipe is not None:
             pipe.close()
-        q.put({"worker": wid, "minibatches": n, "seconds": dt, "parity": refine_parity(fb, rows, a_s, a_e)})
+        parity = refine_parity(fb, rows, a_s, a_e)
+        if feeder is not None and args.boost:   # the one-pass prediction against `predict` on the fingerprints it came with
+            fb2, (y_pred, y_prob) = both()
+            p_pred, p_prob = feeder.predict(fb2.fpt[fb2.status == 0])
+            parity = parity and bool(np.array_equal(y_pred, p_pred) and np.array_equal(y_prob, p_prob) and len(y_pred) > 0)
+        q.put({"worker": wid, "minibatches": n, "seconds": dt, "parity": parity})
     except Exception as e:  # noqa: BLE001
         try:
             start.abort()
@@ -176,8 +189,8 @@ def refine_loop(wid, args, start, q, feeder=None):
 
 def refine_mode(args):
     """--refine: P forked workers on the tRNA flow; the parent makes no GPU call (the feeder is created before the fork)"""
-    if args.mode not in ("sync", "pipe", "feeder") or (args.adc and args.mode == "sync"):
-        print(json.dumps({"error": "--refine takes the modes sync, pipe, feeder; --adc with pipe and feeder"}))
+    if args.mode not in ("sync", "pipe", "feeder") or (args.adc and args.mode == "sync") or (args.boost and args.mode != "feeder"):
+        print(json.dumps({"error": "--refine takes the modes sync, pipe, feeder; --adc with pipe and feeder; --boost with feeder"}))
         return 1
     ctx = mp.get_context("fork")
     feeder = None
@@ -185,7 +198,13 @@ def refine_mode(args):
         from warpdemux_amd.feeder import Feeder
 
         hp, hr = refine_setup()
-        feeder = Feeder(refine=hr, params=hp, max_reads=N_READS, stride=STRIDE, n_slots=args.slots, adc=args.adc)
+        model = None
+        if args.boost:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            import bench_boost
+
+            model = bench_boost._model(args.boost)
+        feeder = Feeder(refine=hr, params=hp, max_reads=N_READS, stride=STRIDE, n_slots=args.slots, adc=args.adc, model=model)
     start, q = ctx.Barrier(args.workers), ctx.Queue()
     procs = [ctx.Process(target=refine_loop, args=(w, args, start, q, feeder)) for w in range(args.workers)]
     try:
@@ -205,7 +224,7 @@ def refine_mode(args):
             return 1
         mbs = sum(r["minibatches"] for r in res)
         wall = max(r["seconds"] for r in res)
-        out = {"workers": args.workers, "mode": args.mode, "refine": True, "adc": bool(args.adc), "refill": bool(args.refill),
+        out = {"workers": args.workers, "mode": args.mode, "refine": True, "boost": args.boost, "adc": bool(args.adc), "refill": bool(args.refill),
                "start_jitter": args.jitter, "gpu_facing_processes": 1 if feeder is not None else args.workers,
                "reads_per_s": mbs * N_READS / wall, "minibatches": mbs, "seconds": wall,
                "ms_per_minibatch_per_worker": 1e3 * wall / (mbs / args.workers), "parity": all(r["parity"] for r in res)}
@@ -461,6 +480,8 @@ def main():
     ap.add_argument("--adc", action="store_true", help="feed int16 ADC rows (2 bytes per sample, calibrated on the device)")
     ap.add_argument("--jitter", type=int, default=0, help="adapter_start ~ U{100 .. 100 + JITTER} per read (rows carry whole "
                     "reads, file_proc.py:244-260); 0 = every adapter starts at sample 100")
+    ap.add_argument("--boost", choices=["default_1000x6x4", "small_100x4x4"], default=None,
+                    help="--refine --mode feeder: classify on the device with an Fpt_Boost model of this assumed size (WDX_WANT_BOOST)")
     ap.add_argument("--refine", action="store_true", help="the tRNA flow: consensus refinement, fingerprints only (modes sync, pipe, "
                     "feeder; --adc with pipe and feeder)")
     args = ap.parse_args()

@@ -41,6 +41,7 @@ OPT_NO_SPLIT_TAIL = 15
 OPT_DTW_UNFUSED = 16
 OPT_MLP_CHUNK_ROWS = 17
 OPT_BOOST_CHUNK_ROWS = 18
+OPT_BOOST_KERNEL = 19   # 0 by batch size | 1 lane-per-read | 2 tree-parallel
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -62,7 +63,7 @@ EXPORTS = [
     "wdx_demux_submit_adc", "wdx_fingerprint_batch_adc", "wdx_demux_batch_adc", "wdx_calibrate_adc_dev", "wdx_feeder_run_adc",
     "wdx_demux_submit_refine", "wdx_demux_wait_refine", "wdx_demux_refine_workspace_bytes", "wdx_demux_refine_dev",
     "wdx_feeder_ring_bytes_refine", "wdx_feeder_ring_init_refine", "wdx_feeder_run_refine",
-    "wdx_boost_set_model", "wdx_boost_predict_dev", "wdx_boost_predict", "wdx_demux_boost_dev",
+    "wdx_boost_set_model", "wdx_boost_predict_dev", "wdx_boost_predict", "wdx_demux_boost_dev", "wdx_feeder_predict_boost",
 ]
 
 
@@ -164,6 +165,9 @@ class MlpModelC(C.Structure):
 
 # wdx_boost_model (include/wdx.h)
 BOOST_MAX_FEATURES, BOOST_MAX_DEPTH, BOOST_MAX_DIM = 254, 16, 16
+# the tree-parallel kernel (wdx_boost.hip): reads per workgroup, trees per chunk, and the largest batch that takes it by
+# default (WDX_BOOST_SMALL_READS / _TREE_CHUNK / _SMALL_MAX_READS; 0 would mean through OPT_BOOST_KERNEL only)
+BOOST_SMALL_READS, BOOST_TREE_CHUNK, BOOST_SMALL_MAX_READS = 16, 1024, 65536
 
 
 class BoostModelC(C.Structure):
@@ -179,6 +183,7 @@ class BoostModelC(C.Structure):
 
 WANT_FPT, WANT_DIST, WANT_DWELL, WANT_STATS, WANT_SVM = 0x01, 0x02, 0x04, 0x08, 0x10   # WDX_WANT_*
 WANT_REFINE_IDX = 0x20   # refine minibatches only (wdx_demux_submit_refine, a refine feeder ring)
+WANT_BOOST = 0x40        # prob / pred / conf of the resident boost model on the minibatch's fingerprints (never with WANT_SVM)
 
 
 class MinibatchInC(C.Structure):
@@ -473,6 +478,8 @@ def load():
         L.wdx_demux_boost_dev.restype = C.c_int
         L.wdx_demux_boost_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, P(SegParamsC), P(RefineParamsC), vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]
+        L.wdx_feeder_predict_boost.restype = C.c_int
+        L.wdx_feeder_predict_boost.argtypes = [vp, vp, i64, vp, vp, vp]
         _lib = L
         return L
 

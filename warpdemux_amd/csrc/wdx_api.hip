@@ -516,6 +516,7 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
         case WDX_OPT_MAX_LAUNCH_SLICE: ctx->knobs.max_launch_slice = value > 0 ? value : 0; break;
         case WDX_OPT_MLP_CHUNK_ROWS: ctx->knobs.mlp_chunk_rows = value > 0 ? value : 0; break;
         case WDX_OPT_BOOST_CHUNK_ROWS: ctx->knobs.boost_chunk_rows = value > 0 ? value : 0; break;
+        case WDX_OPT_BOOST_KERNEL: ctx->knobs.boost_kernel = (value >= 0 && value <= 2) ? (int)value : 0; break;
         default:
             set_error("unknown option %d", (int)option);
             return WDX_ERR_INVALID;
@@ -1217,7 +1218,8 @@ struct MbRefine {
 };
 
 static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, const wdx_seg_params *p,
-                               const MbHostOut &H, const SvmDev *svm, const MbRefine *rfn = nullptr) {
+                               const MbHostOut &H, const SvmDev *svm, const MbRefine *rfn = nullptr,
+                               const BoostDev *boost = nullptr) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const int64_t n_reads = in.n_reads();
@@ -1229,8 +1231,8 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, con
     if ((rc = B->out3.ensure((size_t)n_reads * 4))) return rc;
     if (H.dwell && (rc = B->mb_dwell.ensure((size_t)(n_reads * K) * 8))) return rc;
     if (H.stats && (rc = B->mb_stats.ensure((size_t)n_reads * 48))) return rc;
-    if (svm) {
-        if ((rc = B->mb_prob.ensure((size_t)n_reads * svm->k * 8))) return rc;
+    if (svm || boost) {   // (never both: demux_submit_locked)
+        if ((rc = B->mb_prob.ensure((size_t)n_reads * (svm ? svm->k : boost->k) * 8))) return rc;
         if ((rc = B->mb_pred.ensure((size_t)n_reads * 4))) return rc;
         if ((rc = B->mb_conf.ensure((size_t)n_reads * 8))) return rc;
     }
@@ -1264,6 +1266,16 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, con
             if (H.pred) WDX_HIP_TRY(hipMemcpyAsync(H.pred, B->mb_pred.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
             if (H.conf) WDX_HIP_TRY(hipMemcpyAsync(H.conf, B->mb_conf.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
         }
+    }
+    if (boost) {
+        // Fpt_Boost.predict on the fingerprint rows themselves, which are on the device anyway (models/fpt_boost.py): no
+        // references, no distances; the kernel gives failed reads pred -1 and NaN
+        if ((rc = boost_tail(B, *boost, (const double *)B->out0.p, (const int32_t *)B->out3.p, n_reads, nullptr,
+                             (double *)B->mb_prob.p, (int32_t *)B->mb_pred.p, (double *)B->mb_conf.p, s)))
+            return rc;
+        if (H.prob) WDX_HIP_TRY(hipMemcpyAsync(H.prob, B->mb_prob.p, (size_t)n_reads * boost->k * 8, hipMemcpyDeviceToHost, s));
+        if (H.pred) WDX_HIP_TRY(hipMemcpyAsync(H.pred, B->mb_pred.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
+        if (H.conf) WDX_HIP_TRY(hipMemcpyAsync(H.conf, B->mb_conf.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
     }
     WDX_HIP_TRY(hipMemcpyAsync(H.status, B->out3.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
     if (H.fpt) WDX_HIP_TRY(hipMemcpyAsync(H.fpt, B->out0.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
@@ -1463,6 +1475,17 @@ int wdx_host_free(void *p) {
 static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want,
                                const wdx_refine_params *rp = nullptr, bool no_refs = false);
 
+// wdx_demux_submit_ex / _adc with n_refs == 0: legal when, and only when, WDX_WANT_BOOST is set (the boost tail reads the
+// fingerprints, not a reference set); there are no distances then
+static bool boost_without_refs(int64_t n_refs, uint32_t want) { return n_refs == 0 && (want & WDX_WANT_BOOST) != 0; }
+static int boost_without_refs_check(const char *who, uint32_t want) {
+    if (want & WDX_WANT_DIST) {
+        set_error("%s: a minibatch without references (n_refs = 0) has no distances", who);
+        return WDX_ERR_INVALID;
+    }
+    return WDX_SUCCESS;
+}
+
 // packed float32 rows: offsets ascending on 16-byte boundaries, every row inside its slice
 static int packed_rows_check(const wdx_minibatch_in *in) {
     const int64_t n_reads = in->n_reads;
@@ -1489,13 +1512,15 @@ int wdx_demux_submit_ex(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, 
     }
     std::lock_guard<std::mutex> g(ctx->mu);
     const int64_t n_reads = in->n_reads;
+    const bool no_refs = boost_without_refs(n_refs, want);
+    if (no_refs && (rc = boost_without_refs_check("demux_submit", want))) return rc;
     if ((rc = demux_check_args(ctx, "demux_submit", n_reads, in->row_off ? 0 : in->stride, in->sig, in->a_start, in->a_end, p,
-                               n_refs)))
+                               n_refs, !no_refs)))
         return rc;
     if (in->row_off && (rc = packed_rows_check(in))) return rc;
     MbIn mb;
     mb.f = in;
-    return demux_submit_locked(ctx, slot, mb, p, want);
+    return demux_submit_locked(ctx, slot, mb, p, want, nullptr, no_refs);
 }
 
 int wdx_demux_submit_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *in, const wdx_minibatch_adc_in *in_adc,
@@ -1543,19 +1568,36 @@ int wdx_demux_submit_adc(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_adc_in 
     if (int e = adc_check_args("demux_submit_adc", in)) return e;
     WDX_ENTER(ctx);
     std::lock_guard<std::mutex> g(ctx->mu);
+    const bool no_refs = boost_without_refs(n_refs, want);
+    if (no_refs && (rc = boost_without_refs_check("demux_submit_adc", want))) return rc;
     if ((rc = demux_check_args(ctx, "demux_submit_adc", in->n_reads, in->row_off ? 0 : in->stride, in->adc, in->a_start,
-                               in->a_end, p, n_refs)))
+                               in->a_end, p, n_refs, !no_refs)))
         return rc;
     MbIn mb;
     mb.adc = in;
-    return demux_submit_locked(ctx, slot, mb, p, want);
+    return demux_submit_locked(ctx, slot, mb, p, want, nullptr, no_refs);
 }
 
 static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const wdx_seg_params *p, uint32_t want,
                                const wdx_refine_params *rp, bool no_refs) {
     int rc = WDX_SUCCESS;
     const int64_t n_reads = in.n_reads();
-    const bool want_svm = (want & WDX_WANT_SVM) != 0;
+    const bool want_svm = (want & WDX_WANT_SVM) != 0, want_boost = (want & WDX_WANT_BOOST) != 0;
+    if (want_svm && want_boost) {
+        set_error("demux_submit: WDX_WANT_SVM and WDX_WANT_BOOST share prob / pred / conf: ask for one of them");
+        return WDX_ERR_INVALID;
+    }
+    if (want_boost) {
+        if (!ctx->boost_set) {
+            set_error("demux_submit: WDX_WANT_BOOST needs wdx_boost_set_model first");
+            return WDX_ERR_NO_REFS;
+        }
+        if (p->barcode_num_events != ctx->boost.n_features) {
+            set_error("%s (%d) != the boost model's features (%d)", rp ? "barcode_keep_events" : "barcode_num_events",
+                      (int)p->barcode_num_events, ctx->boost.n_features);
+            return WDX_ERR_INVALID;
+        }
+    }
     if (want_svm) {
         if (!ctx->svm_set) {
             set_error("demux_submit: WDX_WANT_SVM needs wdx_svm_set_model first");
@@ -1581,19 +1623,20 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
     const DtwRefs &R = no_refs ? none : ctx->refs;
     S->refs = R;  // device pointers of the parent's resident set (read-only; wdx_set_refs drains the slots)
     const int64_t K = p->barcode_num_events;
-    const int64_t k = want_svm ? ctx->svm.k : 0;
+    const int64_t k = want_svm ? ctx->svm.k : (want_boost ? ctx->boost.k : 0);
+    const bool want_tail = want_svm || want_boost;
     // page-locked output block of the slot, 8-byte aligned pieces:
     // [fpt f64 n*K][dwell i64 n*K][stats f64 n*6][prob f64 n*k][conf f64 n][dist f32 n*nY][call i32 n][status i32 n][pred i32 n]
     const size_t n = (size_t)n_reads;
     const size_t bytes[9] = {(want & WDX_WANT_FPT) ? n * K * 8 : 0,
                              (want & WDX_WANT_DWELL) ? n * K * 8 : 0,
                              (want & WDX_WANT_STATS) ? n * 48 : 0,
-                             want_svm ? n * (size_t)k * 8 : 0,
-                             want_svm ? n * 8 : 0,
+                             want_tail ? n * (size_t)k * 8 : 0,
+                             want_tail ? n * 8 : 0,
                              ((want & WDX_WANT_DIST) && R.nY > 0) ? n * (size_t)R.nY * 4 : 0,
                              n * 4,
                              n * 4,
-                             want_svm ? n * 4 : 0};
+                             want_tail ? n * 4 : 0};
     size_t off = 0;
     for (int q = 0; q < 9; ++q) {
         S->slot_off[q] = off;
@@ -1628,7 +1671,10 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
     MbRefine rfn;
     rfn.rp = rp;
     rfn.h_idx = S->slot_want_ridx ? (int32_t *)(ho + S->slot_off_ridx) : nullptr;
-    if ((rc = demux_batch_enqueue(S, R, in, p, H, want_svm ? &ctx->svm : nullptr, rp ? &rfn : nullptr))) return rc;
+    const BoostDev boost = ctx->boost;   // (by value: the kernel's arguments are this model, whatever is set later)
+    if ((rc = demux_batch_enqueue(S, R, in, p, H, want_svm ? &ctx->svm : nullptr, rp ? &rfn : nullptr,
+                                  want_boost ? &boost : nullptr)))
+        return rc;
     drain.done();  // in flight on purpose: wdx_demux_wait synchronises
     if (S->dtw_last.family != WDX_DTW_NONE) ctx->dtw_last = S->dtw_last;
     S->slot_busy = true;
@@ -1670,7 +1716,7 @@ static int demux_wait_body(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *
         const uint32_t w = S->slot_want;
         if (S->slot_n > 0 && ((out->fpt && !(w & WDX_WANT_FPT)) || (out->dist && !(w & WDX_WANT_DIST) && S->slot_nY > 0) ||
                               (out->dwell && !(w & WDX_WANT_DWELL)) || (out->stats && !(w & WDX_WANT_STATS)) ||
-                              ((out->prob || out->pred || out->conf) && !(w & WDX_WANT_SVM)))) {
+                              ((out->prob || out->pred || out->conf) && !(w & (WDX_WANT_SVM | WDX_WANT_BOOST))))) {
             set_error("demux_wait: an output that was not requested at wdx_demux_submit");
             return WDX_ERR_INVALID;
         }

@@ -23,6 +23,12 @@ int svm_tail(wdx_ctx *B, const SvmDev &M, const float *d_dist, int64_t n, const 
     return d_status ? launch_svm_mask_failed(d_status, n, M.k, d_prob, d_pred, d_conf, s) : WDX_SUCCESS;
 }
 
+int boost_tail(wdx_ctx *B, const BoostDev &M, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
+               double *d_prob, int32_t *d_pred, double *d_conf, hipStream_t s) {
+    Timed t(B, WDX_K_BOOST, s);
+    return launch_boost_predict(M, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, s, B->knobs);
+}
+
 }  // namespace wdx
 
 // rows per block of wdx_demux_{svm,mlp}_dev when the caller names none: the (rows, nY) float32 distances of a block stay in
@@ -518,11 +524,6 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
 
 // ---- Fpt_Boost: oblivious trees on the fingerprint rows (wdx_boost.hip) ----------------------------------
 
-static int boost_tail(wdx_ctx *B, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw, double *d_prob,
-                      int32_t *d_pred, double *d_conf, hipStream_t s) {
-    Timed t(B, WDX_K_BOOST, s);
-    return launch_boost_predict(B->boost, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, s);
-}
 
 int wdx_boost_set_model(wdx_ctx *ctx, const wdx_boost_model *m) {
     WDX_ENTER(ctx);
@@ -647,7 +648,7 @@ int wdx_boost_predict_dev(wdx_ctx *ctx, const double *d_fpt, const int32_t *d_st
         return WDX_ERR_INVALID;
     }
     if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
-    return boost_tail(ctx, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, (hipStream_t)stream);
+    return boost_tail(ctx, ctx->boost, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, (hipStream_t)stream);
 }
 
 int wdx_boost_predict(wdx_ctx *ctx, const double *X, int64_t n, double *raw, double *prob, int32_t *pred, double *conf) {
@@ -678,7 +679,7 @@ int wdx_boost_predict(wdx_ctx *ctx, const double *X, int64_t n, double *raw, dou
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t c = std::min(chunk, n - r0);
         WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X + r0 * F, (size_t)(c * F) * 8, hipMemcpyHostToDevice, s));
-        if ((rc = boost_tail(ctx, (const double *)ctx->in0.p, nullptr, c, (double *)ctx->out0.p, (double *)ctx->out1.p,
+        if ((rc = boost_tail(ctx, ctx->boost, (const double *)ctx->in0.p, nullptr, c, (double *)ctx->out0.p, (double *)ctx->out1.p,
                              (int32_t *)ctx->out2.p, (double *)ctx->out3.p, s)))
             return rc;
         if (raw) WDX_HIP_TRY(hipMemcpyAsync(raw + r0 * dim, ctx->out0.p, (size_t)(c * dim) * 8, hipMemcpyDeviceToHost, s));
@@ -732,7 +733,7 @@ int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
     if (rp && (rc = refine_prepare(ctx, *rp, n_reads, d_refine_idx, w + round_up(W.bytes, 256), s, &rf))) return rc;
     if ((rc = fingerprint_stage(ctx, in, pv, FpOut{fpt, nullptr, nullptr, d_status}, w + W.fp_ws, s, rf, rf == nullptr)))
         return rc;
-    return boost_tail(ctx, fpt, d_status, n_reads, d_raw, d_prob, d_pred, d_conf, s);
+    return boost_tail(ctx, ctx->boost, fpt, d_status, n_reads, d_raw, d_prob, d_pred, d_conf, s);
 }
 
 }  // extern "C"

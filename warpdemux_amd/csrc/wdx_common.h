@@ -43,6 +43,7 @@ struct Knobs {
     int dtw_unfused = 0;             // WDX_OPT_DTW_UNFUSED: 0 fused cells + settle | 1 six operations only | 2 / 3 tests, diagnostics
     int64_t mlp_chunk_rows = 0;      // WDX_OPT_MLP_CHUNK_ROWS: rows per pass of wdx_dtw_mlp_predict (0 = built-in)
     int64_t boost_chunk_rows = 0;    // WDX_OPT_BOOST_CHUNK_ROWS: rows per pass of wdx_boost_predict (0 = built-in)
+    int boost_kernel = 0;            // WDX_OPT_BOOST_KERNEL: 0 by batch size | 1 lane-per-read | 2 tree-parallel
 };
 
 // A launch over more workgroups than grid.x admits is cut into slices (block_base != 0 from the second on).  The built-in
@@ -245,7 +246,7 @@ struct BoostDev {  // device-resident oblivious-tree ensemble + label map / thre
 };
 // d_status (nullable): rows with status != WDX_READ_OK get pred -1 and NaN raw / prob / conf
 int launch_boost_predict(const BoostDev &M, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
-                         double *d_prob, int32_t *d_pred, double *d_conf, hipStream_t stream);
+                         double *d_prob, int32_t *d_pred, double *d_conf, hipStream_t stream, const Knobs &knobs);
 
 // row r of a page-locked (n, stride) host minibatch, samples [st[r], st[r] + len[r]) -> dst + off[r] (device), read over
 // the bus by a copy kernel

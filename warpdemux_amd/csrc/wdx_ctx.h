@@ -157,6 +157,10 @@ DemuxWork demux_work_layout(int64_t n_reads, int64_t K, bool with_T);
 // failed reads are masked right behind it: pred -1, NaN probabilities (the reference never shows them to the model)
 int svm_tail(wdx_ctx *B, const SvmDev &M, const float *d_dist, int64_t n, const int32_t *d_status, double *d_prob,
              int32_t *d_pred, double *d_conf, hipStream_t s);
+// (wdx_classify.hip) boost tail on device fingerprint rows (n, M.n_features) under WDX_K_BOOST, with B's knobs; the kernel
+// masks the reads whose d_status (nullable) is not 0 itself
+int boost_tail(wdx_ctx *B, const BoostDev &M, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
+               double *d_prob, int32_t *d_pred, double *d_conf, hipStream_t s);
 
 }  // namespace wdx
 

@@ -12,6 +12,8 @@
 // ReadResults' arrays (fingerprint, dwell times, six statistics, status: WDX_WANT_FPT / _DWELL / _STATS), the
 // nearest-reference call and distance rows, and the DTW_SVM prediction (WDX_WANT_SVM: prob / pred / conf) -- one pass
 // over the rows for all of it.  wdx_feeder_predict is model.predict() on fingerprints the worker already holds.
+// WDX_WANT_BOOST / wdx_feeder_predict_boost are the same two for the tRNA models' class (Fpt_Boost, wdx_boost_set_model):
+// the trees run on the fingerprints themselves, so such a ring needs no references (n_refs == 0, plain or refine).
 //
 // A worker copies only what the kernels read: samples [a_start - padding, a_end + padding) of each row, back to back
 // (PACKED rows, wdx_minibatch_in.row_off) -- 18.7 MB instead of 40 MB per 1000-read minibatch on both of the worker's
@@ -457,7 +459,7 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
         if (want & WDX_WANT_FPT) out.fpt = (double *)fptlike_of(R->off_fpt, s);
         if (want & WDX_WANT_DWELL) out.dwell = (int64_t *)fptlike_of(R->off_dwell, s);
         if (want & WDX_WANT_STATS) out.stats = stats_of(s);
-        if (want & WDX_WANT_SVM) {
+        if (want & (WDX_WANT_SVM | WDX_WANT_BOOST)) {
             out.prob = prob_of(s);
             out.pred = i32_of(R->off_pred, s);
             out.conf = conf_of(s);
@@ -481,6 +483,16 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
         hand_over(s, rc);
         return rc;
     };
+    // WDX_WANT_BOOST / wdx_feeder_predict_boost, checked per minibatch: the slot's prob region holds n_classes doubles per
+    // read and the fingerprints have n_events columns, so a resident model of another shape must not be run into it
+    auto boost_fits = [&]() -> bool {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        if (!ctx->boost_set) return true;   // (the call itself answers WDX_ERR_NO_REFS)
+        if ((size_t)ctx->boost.k == kc && (size_t)ctx->boost.n_features == K) return true;
+        set_error("feeder: the boost model has %d classes and %d features, the ring was laid out for %d and %d", ctx->boost.k,
+                  ctx->boost.n_features, (int)kc, (int)K);
+        return false;
+    };
     int idle_rounds = 0;
     while (!ld(&R->stop)) {
         if (getppid() != parent) break;   // orphaned: the parent died without wdx_feeder_stop
@@ -497,9 +509,19 @@ int wdx_feeder_serve(wdx_ctx *ctx, void *ring) {
                 // model.predict on fingerprints the worker holds (models/dtw_svm.py:54-98): a synchronous call on the
                 // context's own stream -- milliseconds, beside the slots in flight
                 st(&S.state, word_of(owner_of(v), kInflight));
-                const int rc = wdx_dtw_svm_predict(ctx, (const double *)sig_of(s), S.n_reads, prob_of(s), i32_of(R->off_pred, s),
-                                                   conf_of(s));
+                int rc;
+                if (S.want & WDX_WANT_BOOST)   // Fpt_Boost.predict (models/fpt_boost.py): no DTW, no references
+                    rc = boost_fits() ? wdx_boost_predict(ctx, (const double *)sig_of(s), S.n_reads, nullptr, prob_of(s),
+                                                          i32_of(R->off_pred, s), conf_of(s))
+                                      : WDX_ERR_INVALID;
+                else
+                    rc = wdx_dtw_svm_predict(ctx, (const double *)sig_of(s), S.n_reads, prob_of(s), i32_of(R->off_pred, s),
+                                             conf_of(s));
                 hand_over(s, rc);
+                continue;
+            }
+            if ((S.want & WDX_WANT_BOOST) && !boost_fits()) {
+                hand_over(s, WDX_ERR_INVALID);
                 continue;
             }
             int cs = 0;
@@ -712,19 +734,25 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
         set_error("%s: WDX_WANT_REFINE_IDX on a ring without refinement (wdx_feeder_ring_init_refine)", who);
         return WDX_ERR_INVALID;
     }
+    if ((want & WDX_WANT_SVM) && (want & WDX_WANT_BOOST)) {
+        set_error("%s: WDX_WANT_SVM and WDX_WANT_BOOST share prob / pred / conf: ask for one of them", who);
+        return WDX_ERR_INVALID;
+    }
     if (R->kind == kRingRefine && R->n_refs == 0 && (want & (WDX_WANT_DIST | WDX_WANT_SVM))) {
         set_error("%s: a fingerprint-only ring (n_refs = 0) serves no distances and no SVM tail", who);
         return WDX_ERR_INVALID;
     }
-    if ((want & ~(WDX_WANT_FPT | WDX_WANT_DIST | WDX_WANT_DWELL | WDX_WANT_STATS | WDX_WANT_SVM | WDX_WANT_REFINE_IDX)) ||
-        ((want & (WDX_WANT_FPT | WDX_WANT_DWELL | WDX_WANT_STATS)) && R->n_events == 0) || ((want & WDX_WANT_SVM) && R->n_classes == 0)) {
+    constexpr uint32_t kTails = WDX_WANT_SVM | WDX_WANT_BOOST;
+    if ((want & ~(WDX_WANT_FPT | WDX_WANT_DIST | WDX_WANT_DWELL | WDX_WANT_STATS | kTails | WDX_WANT_REFINE_IDX)) ||
+        ((want & (WDX_WANT_FPT | WDX_WANT_DWELL | WDX_WANT_STATS | WDX_WANT_BOOST)) && R->n_events == 0) ||
+        ((want & kTails) && R->n_classes == 0)) {
         set_error("%s: the ring was laid out without room for an output that is asked for (n_events %d, n_classes %d)", who,
                   (int)R->n_events, (int)R->n_classes);
         return WDX_ERR_INVALID;
     }
     if (n_reads > 0 && (((want & WDX_WANT_FPT) && !O.fpt) || ((want & WDX_WANT_DWELL) && !O.dwell) ||
                         ((want & WDX_WANT_STATS) && !O.stats) || ((want & WDX_WANT_DIST) && R->n_refs > 0 && !O.dist) ||
-                        ((want & WDX_WANT_SVM) && (!O.prob || !O.pred || !O.conf)) ||
+                        ((want & kTails) && (!O.prob || !O.pred || !O.conf)) ||
                         ((want & WDX_WANT_REFINE_IDX) && !job.refine_idx))) {
         set_error("%s: an output that is asked for has no destination", who);
         return WDX_ERR_INVALID;
@@ -809,7 +837,7 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
         if (want & WDX_WANT_FPT) memcpy(O.fpt, base + R->off_fpt + (size_t)s * align_up(mr * K * 8, 4096), n * K * 8);
         if (want & WDX_WANT_DWELL) memcpy(O.dwell, base + R->off_dwell + (size_t)s * align_up(mr * K * 8, 4096), n * K * 8);
         if (want & WDX_WANT_STATS) memcpy(O.stats, base + R->off_stats + (size_t)s * align_up(mr * 48, 4096), n * 48);
-        if (want & WDX_WANT_SVM) {
+        if (want & kTails) {
             memcpy(O.prob, base + R->off_prob + (size_t)s * align_up(mr * kc * 8, 4096), n * kc * 8);
             memcpy(O.pred, i32_of(R->off_pred), n * 4);
             memcpy(O.conf, base + R->off_conf + (size_t)s * align_up(mr * 8, 4096), n * 8);
@@ -913,16 +941,18 @@ int wdx_feeder_demux(void *ring, const float *sig, int64_t n_reads, int64_t stri
     return wdx_feeder_run(ring, &job);
 }
 
-// DTW_SVM.predict (models/dtw_svm.py:54-98) on fingerprints the worker holds: X (n, n_events) float64 -> prob / pred / conf
-int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int32_t *pred, double *conf) {
+// model.predict on fingerprints the worker holds: X (n, n_events) float64 -> prob / pred / conf.  tail = WDX_WANT_SVM:
+// DTW_SVM.predict (models/dtw_svm.py:54-98); WDX_WANT_BOOST: Fpt_Boost.predict (models/fpt_boost.py)
+static int feeder_predict_rows(void *ring, const char *who, uint32_t tail, const double *X, int64_t n, double *prob,
+                               int32_t *pred, double *conf) {
     FeederRing *R = (FeederRing *)ring;
     if (int rc = ring_check(R)) return rc;
     if (n < 0 || (n > 0 && (!X || !prob || !pred || !conf))) {
-        set_error("feeder_predict: bad arguments");
+        set_error("%s: bad arguments", who);
         return WDX_ERR_INVALID;
     }
     if (R->n_classes == 0 || R->n_events == 0) {
-        set_error("feeder_predict: the ring was laid out without a model (n_classes / n_events)");
+        set_error("%s: the ring was laid out without a model (n_classes / n_events)", who);
         return WDX_ERR_INVALID;
     }
     unsigned char *base = (unsigned char *)ring;
@@ -935,7 +965,7 @@ int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int
         memcpy(base + R->off_sig + (size_t)s * R->sig_slot_bytes, X + r0 * (int64_t)K, (size_t)m * K * 8);
         S.n_reads = m;
         S.has_ok = 0u;
-        S.want = WDX_WANT_SVM;
+        S.want = tail;
         S.mode = kModePredict;
         S.rc = WDX_SUCCESS;
         const uint32_t my_gen = ++S.gen;
@@ -952,6 +982,14 @@ int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int
         if (rc) return rc;
     }
     return WDX_SUCCESS;
+}
+
+int wdx_feeder_predict(void *ring, const double *X, int64_t n, double *prob, int32_t *pred, double *conf) {
+    return feeder_predict_rows(ring, "feeder_predict", WDX_WANT_SVM, X, n, prob, pred, conf);
+}
+
+int wdx_feeder_predict_boost(void *ring, const double *X, int64_t n, double *prob, int32_t *pred, double *conf) {
+    return feeder_predict_rows(ring, "feeder_predict_boost", WDX_WANT_BOOST, X, n, prob, pred, conf);
 }
 
 }  // extern "C"

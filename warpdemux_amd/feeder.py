@@ -25,8 +25,11 @@ What comes back is what the reference's worker needs from a minibatch (file_proc
 refinement parameters and the consensus query): `fingerprint_batch[_adc]` then returns what
 `sig_proc.fingerprint_refine_batch` returns, ``refine_idx`` included, and `sig_proc.read_results_from_batch(fb, drs, ids,
 refined=True)` makes the reference's ReadResults of it.  Such a feeder may be created without references
-(``refs=None, model=None``): a tRNA worker's classifier (catboost on the raw fingerprint) runs on the host and needs the
-fingerprints only.
+(``refs=None, model=None``) and then serves the fingerprints only.
+
+``Feeder(model=Fpt_Boost, refs=None, refine=..., adc=...)`` serves the tRNA models' classifier as well
+(`models.Fpt_Boost`, resident on the feeder's context; WDX_WANT_BOOST): `detect_and_predict[_adc]` and `predict` return
+what they return for a `DTW_SVM` -- the ReadResult arrays and the prediction from ONE pass, no references needed.
 
 A worker that dies while it holds a slot does not cost the ring that slot, and a feeder process that dies is noticed
 by the workers (`WdxNoDevice`) even while it is a zombie nobody has reaped (wdx_feeder.hip).
@@ -59,7 +62,8 @@ def _serve(shm_name: str, refs, window, penalty, model, device: int, ready):
                                       float(penalty) if penalty else 0.0))
         if model is not None:
             m = model.to_c()
-            _lib.check(L.wdx_svm_set_model(ctx.handle, C.byref(m)))
+            set_model = L.wdx_boost_set_model if isinstance(m, _lib.BoostModelC) else L.wdx_svm_set_model
+            _lib.check(set_model(ctx.handle, C.byref(m)))
         base = C.addressof(C.c_char.from_buffer(shm.buf))
         # (wdx_feeder_serve announces itself in the ring -- server_pid + heartbeat -- once the ring is page-locked; the
         # parent polls wdx_feeder_alive after this event)
@@ -97,19 +101,26 @@ class Feeder:
 
     ``refine``: every minibatch takes the consensus-refinement branch with these parameters (K =
     ``refine.barcode_keep_events``); with it, and only with it, ``refs`` and ``model`` may both be None: a fingerprint-only
-    feeder, on which `demux_batch`, `detect_and_predict` and `predict` are refused."""
+    feeder, on which `demux_batch`, `detect_and_predict` and `predict` are refused.
+
+    ``model`` may also be a `warpdemux_amd.models.Fpt_Boost` (the tRNA models): it classifies the fingerprints themselves, so
+    ``refs`` may be None with or without ``refine`` (`demux_batch` is then refused) or given beside it; K must equal
+    ``model.n_features``."""
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, max_reads: int = 1000,
                  stride: int = 10000, n_slots: int = 16, device: int = 0, start_timeout: float = 120.0, model=None,
                  adc: bool = False, refine: Optional[RefineParams] = None):
-        if model is not None:
+        self.boost = model is not None and not hasattr(model, "_X")   # an Fpt_Boost: no references of its own
+        if model is not None and not self.boost:
             if refs is not None:
                 raise ValueError("pass either refs or model (whose _X are the references)")
             refs, window, penalty = model._X, model.window, model.penalty
         if refs is None:
-            if refine is None:
+            if refine is None and not self.boost:
                 raise ValueError("refs or model is required")
-            refs = np.zeros((0, int(refine.barcode_keep_events)), dtype=np.float64)
+            k0 = int(refine.barcode_keep_events) if refine is not None else (
+                int(params.barcode_num_events) if params is not None else int(model.n_features))
+            refs = np.zeros((0, k0), dtype=np.float64)
         refs = np.ascontiguousarray(refs, dtype=np.float64)
         if refs.ndim != 2:
             raise ValueError("refs must be (nY, L)")
@@ -120,8 +131,11 @@ class Feeder:
         self.params = params or SegParams(barcode_num_events=K)
         if K != refs.shape[1] or (refine is None and self.params.barcode_num_events != K):
             raise ValueError("barcode_num_events must equal the reference length")
+        if self.boost and K != int(model.n_features):
+            raise ValueError(f"the fingerprints have {K} events but the boost model takes {int(model.n_features)} features")
         self.model = model
-        self.n_classes = int(model.n_classes) if model is not None else 0
+        self.n_classes = (int(model.k) if self.boost else int(model.n_classes)) if model is not None else 0
+        self._tail = _lib.WANT_BOOST if self.boost else _lib.WANT_SVM
         self.label_mapper = dict(model.label_mapper) if model is not None else None
         self.nY, self.K = (int(v) for v in refs.shape)
         self.max_reads, self.stride, self.n_slots = int(max_reads), int(stride), int(n_slots)
@@ -175,7 +189,7 @@ class Feeder:
         if a_s.shape != (n,) or a_e.shape != (n,):
             raise ValueError("adapter_start/adapter_end must have one entry per read")
         ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
-        if want & _lib.WANT_SVM and self.model is None:
+        if want & (_lib.WANT_SVM | _lib.WANT_BOOST) and self.model is None:
             raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
         out = self._outputs(n, want)
         job = _lib.FeederJobC(_lib.addr(sig), n, stride, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok), int(want), 0,
@@ -194,20 +208,24 @@ class Feeder:
             "fpt": np.empty((n, self.K), dtype=np.float64) if want & _lib.WANT_FPT else None,
             "dwell": np.empty((n, self.K), dtype=np.int64) if want & _lib.WANT_DWELL else None,
             "stats": np.empty((n, 6), dtype=np.float64) if want & _lib.WANT_STATS else None,
-            "prob": np.empty((n, self.n_classes), dtype=np.float64) if want & _lib.WANT_SVM else None,
-            "pred": np.empty(n, dtype=np.int32) if want & _lib.WANT_SVM else None,
-            "conf": np.empty(n, dtype=np.float64) if want & _lib.WANT_SVM else None,
+            "prob": np.empty((n, self.n_classes), dtype=np.float64) if want & (_lib.WANT_SVM | _lib.WANT_BOOST) else None,
+            "pred": np.empty(n, dtype=np.int32) if want & (_lib.WANT_SVM | _lib.WANT_BOOST) else None,
+            "conf": np.empty(n, dtype=np.float64) if want & (_lib.WANT_SVM | _lib.WANT_BOOST) else None,
             "refine_idx": np.empty((n, 3), dtype=np.int32) if want & _lib.WANT_REFINE_IDX else None,
         }
 
     def _fpt_want(self) -> int:
-        """the ReadResult arrays of a minibatch; on a refine feeder with refine_idx"""
+        """the ReadResult arrays of a minibatch; on a refine feeder with refine_idx.  A plain minibatch without references
+        is legal with WDX_WANT_BOOST only (wdx_demux_submit_ex), so a boost feeder without references and without ``refine``
+        always asks for the tail; `fingerprint_batch[_adc]` leaves its prediction behind."""
         return (_lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS |
-                (_lib.WANT_REFINE_IDX if self.refine is not None else 0))
+                (_lib.WANT_REFINE_IDX if self.refine is not None else 0) |
+                (_lib.WANT_BOOST if self.boost and self.refine is None and self.nY == 0 else 0))
 
     def _need_refs(self, what: str):
         if self.nY == 0:
-            raise ValueError(f"{what} needs references or a model: this feeder is fingerprint-only (Feeder(refine=...))")
+            raise ValueError(f"{what} needs references or a DTW model: this feeder is fingerprint-only"
+                             + (" behind its boost model" if self.boost else " (Feeder(refine=...))"))
 
     def _run_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success, want: int):
         """One int16 minibatch through wdx_feeder_run_adc.  Shapes and dtypes of EVERY array, `success` included, are
@@ -226,7 +244,7 @@ class Feeder:
                         ("success", ok)):
             if v is not None and v.shape != (n,):
                 raise ValueError(f"{name} must have one entry per read")
-        if want & _lib.WANT_SVM and self.model is None:
+        if want & (_lib.WANT_SVM | _lib.WANT_BOOST) and self.model is None:
             raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
         out = self._outputs(n, want)
         job = _lib.FeederJobAdcC(_lib.addr(a), n, stride, _lib.addr(r_len), _lib.addr(off), _lib.addr(sc), _lib.addr(a_s),
@@ -254,7 +272,7 @@ class Feeder:
                                return_df: bool = False):
         """`detect_and_predict` for an int16 ADC minibatch (a ``Feeder(adc=True)``): the reference worker's whole
         minibatch from the raw samples the pod5 file holds."""
-        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success, self._fpt_want() | _lib.WANT_SVM)
+        o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success, self._fpt_want() | self._tail)
         return self._fpt_and_predictions(o, return_df)
 
     def demux_batch(self, signals, adapter_start, adapter_end, success=None, want_dist: bool = True) -> DemuxBatch:
@@ -276,7 +294,7 @@ class Feeder:
         `(FingerprintBatch, predictions)` with predictions = `(y_pred, y_prob)` or, with ``return_df``, the predictions
         DataFrame of `DTW_SVM.predict(np.vstack(fpts), return_df=True)` -- one row per SUCCESSFUL read, in read order,
         like the reference, which only ever shows the model the successful fingerprints."""
-        o = self._run(signals, adapter_start, adapter_end, success, self._fpt_want() | _lib.WANT_SVM)
+        o = self._run(signals, adapter_start, adapter_end, success, self._fpt_want() | self._tail)
         return self._fpt_and_predictions(o, return_df)
 
     def _fpt_and_predictions(self, o: dict, return_df: bool):
@@ -290,7 +308,8 @@ class Feeder:
         return fb, (y_pred, y_prob)
 
     def predict(self, X, return_df: bool = False):
-        """`DTW_SVM.predict` (models/dtw_svm.py:54-98) through the feeder: (y_pred, y_prob) or the predictions DataFrame."""
+        """`DTW_SVM.predict` (models/dtw_svm.py:54-98) through the feeder: (y_pred, y_prob) or the predictions DataFrame;
+        with an `Fpt_Boost` model the same two from `wdx_feeder_predict_boost`."""
         if self.model is None:
             raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
         X = np.asarray(X)
@@ -303,8 +322,8 @@ class Feeder:
         y_prob = np.empty((n, self.n_classes), dtype=np.float64)
         y_pred = np.empty(n, dtype=np.int32)
         conf = np.empty(n, dtype=np.float64)
-        _lib.check(self.L.wdx_feeder_predict(C.c_void_p(self._base), _lib.ptr(X), n, _lib.ptr(y_prob), _lib.ptr(y_pred),
-                                             _lib.ptr(conf)))
+        call = self.L.wdx_feeder_predict_boost if self.boost else self.L.wdx_feeder_predict
+        _lib.check(call(C.c_void_p(self._base), _lib.ptr(X), n, _lib.ptr(y_prob), _lib.ptr(y_pred), _lib.ptr(conf)))
         y_pred = y_pred.astype(np.int64)
         if return_df:
             from .models import predictions_to_df

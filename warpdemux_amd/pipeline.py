@@ -16,7 +16,12 @@ Results are bit-identical to `demux_batch` (same kernels).  INTEGRATION.md shows
 ``MinibatchPipeline(..., refine=RefineParams(...))`` runs the consensus-refinement branch of the tRNA models on the same
 slots (wdx_demux_submit_refine / wdx_demux_wait_refine): `wait` then returns a `RefineMinibatch` -- the arrays of
 `sig_proc.fingerprint_refine_batch`, bit for bit, plus call / dist when there are references; ``refs=None`` is a
-fingerprint-only pipeline (the tRNA classifier runs on the host).
+fingerprint-only pipeline.
+
+``MinibatchPipeline(refs=None, ..., model=Fpt_Boost, refine=...)`` is the tRNA flow from one pass: the model
+(`models.Fpt_Boost`, the class of both tRNA models) is resident on the device and every minibatch asks for WDX_WANT_BOOST,
+so `wait` returns a `BoostMinibatch` -- the ReadResult arrays and ``Fpt_Boost.predict`` of the fingerprints (prob / pred /
+conf; failed reads -1 / NaN).  It needs no references, with or without ``refine``.
 """
 from __future__ import annotations
 
@@ -82,23 +87,47 @@ class RefineMinibatch:
         return self.fingerprints.status
 
 
+@dataclass
+class BoostMinibatch:
+    """What `MinibatchPipeline.wait` returns for a pipeline with a boost model: `fingerprints` is
+    `sig_proc.fingerprint_batch`'s (with ``refine``: `fingerprint_refine_batch`'s) result, prob / pred / conf what
+    ``Fpt_Boost.predict_raw`` gives on the fingerprints -- pred int64 labels, -1 for rejected and for failed reads, whose
+    prob / conf are NaN; call is -1 everywhere and dist None without references."""
+
+    fingerprints: FingerprintBatch
+    call: np.ndarray
+    dist: Optional[np.ndarray]
+    prob: np.ndarray
+    pred: np.ndarray
+    conf: np.ndarray
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.fingerprints.status
+
+
 class MinibatchPipeline:
     """Minibatches in flight against one resident reference set (model._X): two slots for a worker's own loop, up to
     MAX_SLOTS for a feeder process that serves many producers.  ``refine``: every minibatch takes the
-    consensus-refinement branch (K = ``refine.barcode_keep_events``); then ``refs`` may be None (fingerprints only)."""
+    consensus-refinement branch (K = ``refine.barcode_keep_events``); then ``refs`` may be None (fingerprints only).
+    ``model``: a `models.Fpt_Boost` kept resident on the device; every minibatch brings its prediction back
+    (`BoostMinibatch`), ``refs`` may be None, and K must equal ``model.n_features``."""
 
     N_SLOTS = 2
 
-    def __init__(self, refs, window=None, penalty=None, params: Optional[SegParams] = None, device: int = 0,
-                 n_slots: int = 2, refine: Optional[RefineParams] = None):
+    def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, device: int = 0,
+                 n_slots: int = 2, refine: Optional[RefineParams] = None, model=None):
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
         self.N_SLOTS = int(n_slots)
         self.refine = refine
+        self.model = model
         if refs is None:
-            if refine is None:
-                raise ValueError("refs is required (only a refine pipeline can be fingerprint-only)")
-            refs = np.zeros((0, int(refine.barcode_keep_events)), dtype=np.float64)
+            if refine is None and model is None:
+                raise ValueError("refs is required (only a refine pipeline or one with a boost model can do without)")
+            k0 = int(refine.barcode_keep_events) if refine is not None else (
+                int(params.barcode_num_events) if params is not None else int(model.n_features))
+            refs = np.zeros((0, k0), dtype=np.float64)
         refs = np.ascontiguousarray(refs, dtype=np.float64)
         if refs.ndim != 2:
             raise ValueError("refs must be (nY, L)")
@@ -106,12 +135,17 @@ class MinibatchPipeline:
         self.params = params or SegParams(barcode_num_events=K)
         if K != refs.shape[1] or (refine is None and self.params.barcode_num_events != K):
             raise ValueError("barcode_num_events must equal the reference length")
+        if model is not None and K != int(model.n_features):
+            raise ValueError(f"the fingerprints have {K} events but the boost model takes {int(model.n_features)} features")
         self.nY, self.K = (int(v) for v in refs.shape)
         self.L = _lib.load()
         self.ctx = _lib.Context(device)
         if self.nY:
             _lib.check(self.L.wdx_set_refs(self.ctx.handle, _lib.ptr(refs), self.nY, self.K,
                                            int(window) if window else 0, float(penalty) if penalty else 0.0))
+        if model is not None:
+            m = model.to_c()
+            _lib.check(self.L.wdx_boost_set_model(self.ctx.handle, C.byref(m)))
         self._pc = self.params.to_c()
         self._rc = refine.to_c() if refine is not None else None
         self._held = [None] * self.N_SLOTS     # the submitted arrays must outlive the copy-in
@@ -130,11 +164,10 @@ class MinibatchPipeline:
         ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
         if not 0 <= int(slot) < self.N_SLOTS:
             raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
-        if self.refine is not None:
+        if self.refine is not None or self.model is not None:
             desc = _lib.MinibatchInC(_lib.addr(sig), n, stride, None, None, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok))
             want_dist = bool(want_dist) and self.nY > 0
-            _lib.check(self.L.wdx_demux_submit_refine(self.ctx.handle, int(slot), C.byref(desc), None, C.byref(self._pc),
-                                                      C.byref(self._rc), self.nY, self._refine_want(want_dist)))
+            self._submit_all(slot, desc, None, want_dist)
             self._held[slot] = (sig, a_s, a_e, ok, n, want_dist, True)
             return
         _lib.check(self.L.wdx_demux_submit(self.ctx.handle, int(slot), _lib.ptr(sig), n, stride, _lib.ptr(a_s),
@@ -142,11 +175,21 @@ class MinibatchPipeline:
                                            int(want_dist)))
         self._held[slot] = (sig, a_s, a_e, ok, n, bool(want_dist), bool(want_fpt))
 
-    @staticmethod
-    def _refine_want(want_dist: bool) -> int:
-        """a refine minibatch always brings the ReadResult arrays back (a tRNA worker classifies them on the host)"""
-        return (_lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | _lib.WANT_REFINE_IDX |
-                (_lib.WANT_DIST if want_dist else 0))
+    def _submit_all(self, slot: int, desc, desc_adc, want_dist: bool):
+        """a refine minibatch, and one of a pipeline with a boost model, always brings the ReadResult arrays back -- with a
+        model, its prediction too (WDX_WANT_BOOST)"""
+        want = (_lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | (_lib.WANT_DIST if want_dist else 0) |
+                (_lib.WANT_REFINE_IDX if self.refine is not None else 0) | (_lib.WANT_BOOST if self.model is not None else 0))
+        f = None if desc is None else C.byref(desc)
+        a = None if desc_adc is None else C.byref(desc_adc)
+        if self.refine is not None:
+            rc = self.L.wdx_demux_submit_refine(self.ctx.handle, int(slot), f, a, C.byref(self._pc), C.byref(self._rc), self.nY,
+                                                want)
+        elif desc_adc is not None:
+            rc = self.L.wdx_demux_submit_adc(self.ctx.handle, int(slot), a, C.byref(self._pc), self.nY, want)
+        else:
+            rc = self.L.wdx_demux_submit_ex(self.ctx.handle, int(slot), f, C.byref(self._pc), self.nY, want)
+        _lib.check(rc)
 
     def submit_adc(self, slot: int, adc, row_len, offset, scale, adapter_start, adapter_end, success=None, want_dist=True,
                    want_fpt=False, row_off=None, row_win=None):
@@ -159,10 +202,9 @@ class MinibatchPipeline:
         if not 0 <= int(slot) < self.N_SLOTS:
             raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
         desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success, row_off, row_win)
-        if self.refine is not None:
+        if self.refine is not None or self.model is not None:
             want_dist = bool(want_dist) and self.nY > 0
-            _lib.check(self.L.wdx_demux_submit_refine(self.ctx.handle, int(slot), None, C.byref(desc), C.byref(self._pc),
-                                                      C.byref(self._rc), self.nY, self._refine_want(want_dist)))
+            self._submit_all(slot, None, desc, want_dist)
             self._held[slot] = (kept, None, None, None, n, want_dist, True)
             return
         want = (_lib.WANT_FPT if want_fpt else 0) | (_lib.WANT_DIST if want_dist else 0)
@@ -170,13 +212,14 @@ class MinibatchPipeline:
         self._held[slot] = (kept, None, None, None, n, bool(want_dist), bool(want_fpt))
 
     def wait(self, slot: int):
-        """`DemuxBatch` of the minibatch on `slot`; a refine pipeline returns a `RefineMinibatch`."""
+        """`DemuxBatch` of the minibatch on `slot`; a refine pipeline returns a `RefineMinibatch`, one with a boost model a
+        `BoostMinibatch`."""
         held = self._held[slot] if 0 <= int(slot) < self.N_SLOTS else None
         if held is None:
             raise ValueError(f"nothing was submitted on slot {slot}")
         n, want_dist, want_fpt = held[4:]
-        if self.refine is not None:
-            return self._wait_refine(slot, n, want_dist)
+        if self.refine is not None or self.model is not None:
+            return self._wait_all(slot, n, want_dist)
         dist = np.empty((n, self.nY), dtype=np.float32) if want_dist else None
         fpt = np.empty((n, self.K), dtype=np.float64) if want_fpt else None
         call = np.empty(n, dtype=np.int32)
@@ -191,18 +234,23 @@ class MinibatchPipeline:
         _lib.check(rc)
         return DemuxBatch(status, call, dist, fpt)
 
-    def _wait_refine(self, slot: int, n: int, want_dist: bool) -> RefineMinibatch:
+    def _wait_all(self, slot: int, n: int, want_dist: bool):
         fb = FingerprintBatch(np.empty((n, self.K), dtype=np.float64), np.empty((n, self.K), dtype=np.int64),
                               np.empty((n, 6), dtype=np.float64), np.empty(n, dtype=np.int32),
-                              np.empty((n, 3), dtype=np.int32))
+                              np.empty((n, 3), dtype=np.int32) if self.refine is not None else None)
         call = np.empty(n, dtype=np.int32)
         dist = np.empty((n, self.nY), dtype=np.float32) if want_dist else None
+        prob = pred = conf = None
+        if self.model is not None:
+            prob, pred, conf = np.empty((n, int(self.model.k))), np.empty(n, dtype=np.int32), np.empty(n)
         out = _lib.MinibatchOutC(_lib.addr(fb.status), _lib.addr(call), _lib.addr(dist), _lib.addr(fb.fpt), _lib.addr(fb.dwell),
-                                 _lib.addr(fb.stats), None, None, None)
+                                 _lib.addr(fb.stats), _lib.addr(prob), _lib.addr(pred), _lib.addr(conf))
         rc = self.L.wdx_demux_wait_refine(self.ctx.handle, int(slot), C.byref(out), _lib.ptr(fb.refine_idx))
         if rc != _lib.WDX_ERR_INVALID:   # (as in `wait`: an argument error leaves the minibatch in flight)
             self._held[slot] = None
         _lib.check(rc)
+        if self.model is not None:
+            return BoostMinibatch(fb, call, dist, prob, pred.astype(np.int64), conf)
         return RefineMinibatch(fb, call, dist)
 
     def run(self, minibatches):
