@@ -560,6 +560,57 @@ int wdx_live_tick(wdx_ctx *ctx, const float *const *rows, const int32_t *row_len
                   int64_t n_refs, int32_t use_svm, double *fpt, float *dist, int32_t *call, int32_t *status,
                   double *prob, int32_t *pred, double *conf);
 
+/* The live tick for every shipped model kind (file_proc.load_model: DTW_SVM, DTW_MLP, Fpt_Boost) and for int16 chunks:
+ * wdx_live_tick is the float32 + plain fingerprint + [SVM] corner of this call, and both run the same tick body.
+ *   in->rows / in->adc_rows  exactly one is non-NULL: one pointer per read to its float32 samples, or to its int16 ADC
+ *                            samples with in->offset / in->scale float32[n].  int16 rows follow the *_adc contract above
+ *                            word for word -- pa = scale * ((float)adc + offset), add then multiply, two roundings, and NaN
+ *                            behind the read's last sample: only the adapter windows are packed into the staging block, as
+ *                            int16 (2 bytes per sample over the bus), and decode_adc_kernel calibrates them on the device.
+ *                            A window that runs past its read's end therefore reads the NaN tail, exactly as on an int16
+ *                            minibatch whose stride holds the whole window (wdx_minibatch_adc_in.row_win); the float32 rows
+ *                            are ragged and end with the read, so there the window is cut at row_len, as in wdx_live_tick
+ *   in->tail                 WDX_LIVE_TAIL_*: which classifier runs behind the fingerprints.  prob (n, k) / pred / conf come
+ *                            back when tail != NONE (each nullable); a read whose status is not 0 gets pred -1 and NaN
+ *                              _SVM    needs resident references and wdx_svm_set_model (WDX_ERR_NO_REFS otherwise)
+ *                              _MLP    needs resident references and wdx_mlp_set_model (WDX_ERR_NO_REFS otherwise); rows
+ *                                      with a non-finite scaled input get pred -1 and NaN, as in wdx_demux_mlp_dev, and are
+ *                                      counted in *n_nonfinite (nullable; failed reads are not counted)
+ *                              _BOOST  needs wdx_boost_set_model (WDX_ERR_NO_REFS otherwise); K must equal the model's
+ *                                      n_features (WDX_ERR_INVALID)
+ *   rp                       NULL = the plain branch; else the consensus-refinement branch as in wdx_demux_submit_refine
+ *                            (K = rp->barcode_keep_events, p->barcode_num_events is ignored).  Refinement is served with
+ *                            tail NONE or BOOST; with the SVM or the MLP tail it is WDX_ERR_INVALID
+ *   n_refs                   with a resident reference set: its nY (WDX_ERR_INVALID otherwise), and K must equal its length;
+ *                            DTW, call and dist run beside whatever tail is asked for.  Without one, n_refs must be 0 and
+ *                            the tail NONE or BOOST: call is -1 for every read, WDX_WANT_DIST is WDX_ERR_INVALID
+ *   want                     WDX_WANT_FPT | _DIST | _DWELL | _STATS | _REFINE_IDX (the last with rp only); any other bit --
+ *                            WDX_WANT_SVM and WDX_WANT_BOOST included: `tail` selects the tail -- is WDX_ERR_INVALID.  A
+ *                            wanted output needs its array in `out` / `refine_idx`.  status (required) and call (nullable)
+ *                            always come back
+ * One host->device copy of the staging block, the kernel chain on the context's own stream, one device->host copy of the
+ * wanted outputs (every kernel writes its piece of one output block in place), one synchronisation.  n_reads == 0 returns
+ * WDX_SUCCESS and touches nothing.  A refused call leaves the context as it was.  Bit-identical to wdx_fingerprint_batch[_adc] /
+ * wdx_fingerprint_refine_batch / wdx_demux_batch / wdx_dtw_svm_predict / wdx_dtw_mlp_predict / wdx_boost_predict on the same
+ * windows. */
+#define WDX_LIVE_TAIL_NONE 0
+#define WDX_LIVE_TAIL_SVM 1
+#define WDX_LIVE_TAIL_MLP 2
+#define WDX_LIVE_TAIL_BOOST 3
+typedef struct wdx_live_in {
+    const float *const *rows;        /* float32 rows: rows[r] -> row_len[r] samples; NULL when adc_rows is given      */
+    const int16_t *const *adc_rows;  /* int16 rows: adc_rows[r] -> row_len[r] ADC samples; NULL when rows is given    */
+    const float *offset, *scale;     /* int16 rows: float32[n_reads] calibration of every read                        */
+    const int32_t *row_len;
+    int64_t n_reads;
+    const int32_t *a_start, *a_end;
+    const uint8_t *ok;               /* nullable                                                                      */
+    int32_t tail;                    /* WDX_LIVE_TAIL_*                                                               */
+    int32_t pad_;
+} wdx_live_in;
+int wdx_live_tick_ex(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p, const wdx_refine_params *rp, int64_t n_refs,
+                     uint32_t want, const wdx_minibatch_out *out, int32_t *refine_idx, int64_t *n_nonfinite);
+
 /* ---- N1: classifier tail of DTW_SVM.predict (models/dtw_svm.py:90-93 + models/utils.py:45-61):
  *      K = exp(-gamma * d^pwr_dist) -> SVC.predict_proba(K) (libsvm, precomputed kernel) -> argmax,
  *      label map, top1-top2 margin, per-class thresholds.  Arrays are HOST pointers, copied at set time. */

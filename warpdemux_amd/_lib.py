@@ -64,6 +64,7 @@ EXPORTS = [
     "wdx_demux_submit_refine", "wdx_demux_wait_refine", "wdx_demux_refine_workspace_bytes", "wdx_demux_refine_dev",
     "wdx_feeder_ring_bytes_refine", "wdx_feeder_ring_init_refine", "wdx_feeder_run_refine",
     "wdx_boost_set_model", "wdx_boost_predict_dev", "wdx_boost_predict", "wdx_demux_boost_dev", "wdx_feeder_predict_boost",
+    "wdx_live_tick_ex",
 ]
 
 
@@ -211,6 +212,19 @@ class MinibatchOutC(C.Structure):
     _fields_ = [
         ("status", C.c_void_p), ("call", C.c_void_p), ("dist", C.c_void_p), ("fpt", C.c_void_p), ("dwell", C.c_void_p),
         ("stats", C.c_void_p), ("prob", C.c_void_p), ("pred", C.c_void_p), ("conf", C.c_void_p),
+    ]
+
+
+LIVE_TAIL_NONE, LIVE_TAIL_SVM, LIVE_TAIL_MLP, LIVE_TAIL_BOOST = 0, 1, 2, 3   # WDX_LIVE_TAIL_*
+
+
+class LiveInC(C.Structure):
+    """wdx_live_in (include/wdx.h)"""
+
+    _fields_ = [
+        ("rows", C.c_void_p), ("adc_rows", C.c_void_p), ("offset", C.c_void_p), ("scale", C.c_void_p), ("row_len", C.c_void_p),
+        ("n_reads", C.c_int64), ("a_start", C.c_void_p), ("a_end", C.c_void_p), ("ok", C.c_void_p), ("tail", C.c_int32),
+        ("pad_", C.c_int32),
     ]
 
 
@@ -480,6 +494,9 @@ def load():
                                           vp, vp, vp, vp, vp, vp]
         L.wdx_feeder_predict_boost.restype = C.c_int
         L.wdx_feeder_predict_boost.argtypes = [vp, vp, i64, vp, vp, vp]
+        L.wdx_live_tick_ex.restype = C.c_int
+        L.wdx_live_tick_ex.argtypes = [vp, P(LiveInC), P(SegParamsC), P(RefineParamsC), i64, C.c_uint32, P(MinibatchOutC), vp,
+                                       P(i64)]
         _lib = L
         return L
 
