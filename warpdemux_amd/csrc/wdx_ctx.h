@@ -1,5 +1,5 @@
-// The opaque context behind include/wdx.h's wdx_ctx (internal; shared by wdx_api.hip, wdx_classify.hip,
-// wdx_comm.hip and wdx_live.hip).  Nothing here computes results.
+// The opaque context behind include/wdx.h's wdx_ctx (internal; shared by wdx_api.hip, wdx_minibatch.hip,
+// wdx_classify.hip, wdx_comm.hip and wdx_live.hip).  Nothing here computes results.
 #pragma once
 #include "wdx_common.h"
 
@@ -55,7 +55,7 @@ struct wdx_ctx {
     wdx::Buffer ref_ws;  // refinement branch: the fast kernels' hand-over records (fingerprint_refine_ws_bytes)
     wdx::Buffer fp_big;  // score curves of adapter windows beyond the exact kernel's LDS capacity (fingerprint_big_bytes)
     wdx::PinnedBuffer pin_in, pin_out;  // staging of small (live-tick sized) host-buffer calls
-    std::vector<double> ref_query_host;  // the consensus query resident in ref_buf (wdx_fingerprint_refine_dev uploads on change)
+    std::vector<double> ref_query_host;  // the consensus query resident in ref_buf (refine_prepare uploads on change)
     wdx::Buffer pk_idx;       // packed staging of a page-locked minibatch: window offsets / first columns / shifted bounds
     wdx::PinnedBuffer pk_host;  // ... and their host images (kept until the slot's copy has run)
     wdx::Buffer in_adc;       // int16 ADC rows as they arrived by DMA copy, ahead of decode_adc_kernel (wdx_adc.hip)
@@ -86,8 +86,8 @@ struct wdx_ctx {
     int64_t slot_n = 0, slot_K = 0, slot_nY = 0, slot_k = 0;
     size_t slot_off[9] = {};  // fpt, dwell, stats, prob, conf, dist, call, status, pred in the slot's page-locked block
     wdx::Buffer mb_dwell, mb_stats, mb_prob, mb_pred, mb_conf;  // device side of the optional minibatch outputs
-    // a refine minibatch (wdx_demux_submit_refine): its refine_idx on the device and in the page-locked block; the
-    // consensus query lives in the slot's own ref_buf / ref_query_host, the hand-over records in its ref_ws
+    // a refine minibatch (wdx_demux_submit_refine; wdx_fingerprint_refine_batch on the context itself): its refine_idx on the device
+    // and, for a slot, in the page-locked block; the consensus query lives in its own ref_buf / ref_query_host, the records in ref_ws
     wdx::Buffer mb_ridx;
     bool slot_want_ridx = false;
     size_t slot_off_ridx = 0;
@@ -132,8 +132,8 @@ inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 // (wdx_api.hip) The fingerprint stage as every entry point but the profiling one runs it: `B` (the context, or the
 // pipeline slot that owns the stream) supplies fp_big for max_len, the knobs and the WDX_K_FINGERPRINT event scope.
 // main_events = false leaves the main / clip / tail kernel pairs unrecorded (they go back to the pool):
-// wdx_fingerprint_refine_dev, the host-batch call (fingerprint_batch_impl) and wdx_live_tick have never recorded them.
-// Kept as found: neither DESIGN.md nor DESIGN_HISTORY.md gives a reason.
+// wdx_fingerprint_refine_dev, the host-batch call (wdx_minibatch.hip: fingerprint_batch_impl) and wdx_live_tick have never
+// recorded them.  Kept as found: neither DESIGN.md nor DESIGN_HISTORY.md gives a reason.
 int fingerprint_stage(wdx_ctx *B, const FpReads &in, const wdx_seg_params &p, const FpOut &out, void *d_ws,
                       hipStream_t s, const RefineDev *rf = nullptr, bool main_events = true);
 // (wdx_api.hip) The refinement branch's device state for n_reads reads on stream s (see its definition); *rf is freed by

@@ -35,6 +35,7 @@
 //     "server gone", never on `stop` alone, and never frees a slot the server may still write to; new claims are
 //     refused from `stop` on.  A generation counter per slot guards against stale hand-overs.
 #include "wdx_ctx.h"
+#include "wdx_window.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -758,33 +759,16 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
         return WDX_ERR_INVALID;
     }
     if (n_reads == 0) return WDX_SUCCESS;
-    // the windows, packed: row r = samples [st & ~3, en) of the caller's row, st = a_start - padding, en = a_end + padding
-    // clamped to the row (extract_adapter, sig_proc.py:388-389); every row starts on a 16-byte boundary.
-    // int16 rows: [st & ~7, en) with st clamped to the row BEFORE it is aligned (nothing outside the caller's row is ever
-    // read), of which the `valid` samples below the read's row_len are copied -- the rest is the NaN tail the device writes.
-    const int64_t pad = R->params.padding;
-    struct Win {
-        int64_t s0, len, valid;   // first sample, samples of the packed row, of them copied
-    };
+    // the windows, packed (wdx_window.h): float32 rows from a multiple of 4 samples, int16 rows from a multiple of 8, so
+    // that every row starts on a 16-byte boundary; of an int16 row the `valid` samples below the read's row_len are copied
+    // -- the rest is the NaN tail the device writes.
+    const WindowOpts wo{R->params.padding, is_adc ? 8 : 4, 0};
     auto window = [&](int64_t r) {
-        int64_t s0 = (int64_t)job.a_start[r] - pad, e0 = (int64_t)job.a_end[r] + pad;
-        if (s0 < 0) s0 = 0;
-        if (e0 > stride) e0 = stride;
-        const bool dead = job.ok && !job.ok[r];
-        if (!is_adc) {
-            if (e0 < s0 || dead) e0 = s0;
-            s0 &= ~(int64_t)3;
-            return Win{s0, e0 - s0, e0 - s0};
-        }
-        if (s0 > stride) s0 = stride;
-        if (e0 <= s0 || dead) return Win{0, 0, 0};
-        s0 &= ~(int64_t)7;
-        const int64_t v = (int64_t)job.row_len[r] - s0;
-        return Win{s0, e0 - s0, v < 0 ? 0 : (v > e0 - s0 ? e0 - s0 : v)};
+        return adapter_window(job.a_start[r], job.a_end[r], stride, job.ok && !job.ok[r], wo, is_adc ? (int64_t)job.row_len[r] : -1);
     };
-    const int64_t al = is_adc ? 7 : 3;      // rows start on 16-byte boundaries
-    int64_t need = 0;
-    for (int64_t r = 0; r < n_reads; ++r) need += (window(r).valid + al) & ~al;
+    PackedOffset fit(wo.align);
+    for (int64_t r = 0; r < n_reads; ++r) fit.take(window(r).valid);
+    const int64_t need = fit.next;
     if ((uint64_t)need > R->sig_floats * (is_adc ? 2u : 1u)) {
         set_error("%s: the minibatch's adapter windows (%lld samples) do not fit a ring slot (%llu)", who, (long long)need,
                   (unsigned long long)(R->sig_floats * (is_adc ? 2u : 1u)));
@@ -803,18 +787,17 @@ static int feeder_run_rows(FeederRing *R, void *ring, const char *who, const Wor
     int32_t *rwin = is_adc ? (int32_t *)(cal + 2 * mr) : nullptr;
     const size_t esz = is_adc ? 2 : 4;
     const unsigned char *src = is_adc ? (const unsigned char *)job.adc : (const unsigned char *)job.sig;
-    int64_t acc = 0;
+    PackedOffset pos(wo.align);
     for (int64_t r = 0; r < n_reads; ++r) {
-        const Win w = window(r);
-        roff[r] = acc;
+        const Window w = window(r);
+        roff[r] = pos.take(w.valid);
         rlen[r] = (int32_t)w.valid;
-        if (rwin) rwin[r] = (int32_t)w.len;
-        ras[r] = job.a_start[r] - (int32_t)w.s0;
-        rae[r] = job.a_end[r] - (int32_t)w.s0;
-        if (w.valid > 0) memcpy(dsig + (size_t)acc * esz, src + (size_t)(r * stride + w.s0) * esz, (size_t)w.valid * esz);
-        acc += (w.valid + al) & ~al;
+        if (rwin) rwin[r] = (int32_t)w.row;
+        ras[r] = w.a_start;
+        rae[r] = w.a_end;
+        if (w.valid > 0) memcpy(dsig + (size_t)roff[r] * esz, src + (size_t)(r * stride + w.first) * esz, (size_t)w.valid * esz);
     }
-    roff[n_reads] = acc;
+    roff[n_reads] = pos.next;
     if (is_adc) {
         memcpy(cal, job.offset, (size_t)n_reads * 4);
         memcpy(cal + mr, job.scale, (size_t)n_reads * 4);

@@ -16,6 +16,7 @@
 //   D2H   the wanted pieces of the output block, which lie at its front back to back
 // No new kernel: every producer writes its piece of the output block in place, so nothing has to be gathered.
 #include "wdx_ctx.h"
+#include "wdx_window.h"
 
 #include <string.h>
 
@@ -183,24 +184,24 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
     //          row r stands for win[r] float32 samples, the first valid[r] of them the read's own, the rest the NaN tail
     //          of the *_adc contract (a window that runs past the read's end: wdx_minibatch_adc_in.row_win); decoded
     //          rows start on 32-byte boundaries of the float32 buffer (in1), as fingerprint_adc_rows lays them out
-    int64_t total = 0, max_len = 0, dst_total = 0;
+    // float32: the window inside the read, taken from its very first sample.  int16: a ragged row has no limit -- a window that
+    // runs past the read's end keeps its NaN tail -- and a window beyond the kernels' limit keeps one sample more than the
+    // limit, which is what reports it.
+    const WindowOpts wo{p->padding, 1, adc ? (int64_t)WDX_MAX_ADAPTER_SAMPLES + 1 : 0};
+    auto window = [&](int64_t r) {
+        return adapter_window(a_start[r], a_end[r], adc ? kNoRowLimit : (int64_t)row_len[r], ok && !ok[r], wo, adc ? (int64_t)row_len[r] : -1);
+    };
+    // staged samples back to back (int16: every row on a 16-byte boundary); decoded int16 rows on 32-byte boundaries
+    const int64_t src_round = adc ? 8 : 1, dst_round = 8;
+    int64_t max_len = 0;
+    PackedOffset fit(src_round), dfit(dst_round);   // (the sizing pass; the fill pass below counts again)
     for (int64_t r = 0; r < n_reads; ++r) {
-        if (ok && !ok[r]) continue;
-        const int64_t st = std::max<int64_t>(0, (int64_t)a_start[r] - p->padding);
-        int64_t en = (int64_t)a_end[r] + p->padding;
-        if (!adc) en = std::min<int64_t>(row_len[r], en);
-        // (int16: a window beyond the kernels' limit keeps one sample more than the limit, which is what reports it)
-        else en = std::min<int64_t>(en, st + WDX_MAX_ADAPTER_SAMPLES + 1);
-        if (en <= st) continue;
-        max_len = std::max(max_len, en - st);
-        if (adc) {
-            const int64_t valid = std::min(std::max<int64_t>((int64_t)row_len[r] - st, 0), en - st);
-            total += (valid + 7) & ~(int64_t)7;
-            dst_total += (en - st + 7) & ~(int64_t)7;
-        } else {
-            total += en - st;
-        }
+        const Window w = window(r);
+        max_len = std::max(max_len, w.win);
+        fit.take(w.valid);
+        dfit.take(w.row);
     }
+    const int64_t total = fit.next, dst_total = dfit.next;
     size_t o_off = 0, o_src = 0, o_zero, o_len, o_valid = 0, o_cal = 0, o_ok, o_sig, in_bytes;
     if (adc) {
         o_src = (n + 1) * 8;
@@ -226,39 +227,26 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
     int32_t *h_zero = (int32_t *)(hin + o_zero), *h_len = (int32_t *)(hin + o_len), *h_valid = (int32_t *)(hin + o_valid);
     float *h_cal = (float *)(hin + o_cal);
     uint8_t *h_ok = hin + o_ok;
-    int64_t pos = 0, dpos = 0;
+    PackedOffset pos(src_round), dpos(dst_round);
     for (int64_t r = 0; r < n_reads; ++r) {
+        const Window w = window(r);
+        const int64_t at = pos.take(w.valid);
         h_zero[r] = 0;
-        int64_t win = 0, valid = 0;
-        const bool good = !ok || ok[r];
-        const int64_t st = std::max<int64_t>(0, (int64_t)a_start[r] - p->padding);
-        if (good) {
-            int64_t en = (int64_t)a_end[r] + p->padding;
-            if (!adc) en = std::min<int64_t>(row_len[r], en);
-            else en = std::min<int64_t>(en, st + WDX_MAX_ADAPTER_SAMPLES + 1);
-            if (en > st) {
-                win = en - st;
-                valid = adc ? std::min(std::max<int64_t>((int64_t)row_len[r] - st, 0), win) : win;
-            }
-        }
-        h_len[r] = (int32_t)win;
-        h_ok[r] = good ? 1 : 0;
+        h_len[r] = (int32_t)w.row;
+        h_ok[r] = (!ok || ok[r]) ? 1 : 0;
         if (adc) {
-            h_off[r] = dpos;
-            h_src[r] = pos;
-            h_valid[r] = (int32_t)valid;
+            h_off[r] = dpos.take(w.row);
+            h_src[r] = at;
+            h_valid[r] = (int32_t)w.valid;
             h_cal[r] = in->offset[r];
             h_cal[n + r] = in->scale[r];
-            if (valid > 0) memcpy((int16_t *)(hin + o_sig) + pos, in->adc_rows[r] + st, (size_t)valid * 2);
-            pos += (valid + 7) & ~(int64_t)7;
-            dpos += (win + 7) & ~(int64_t)7;
+            if (w.valid > 0) memcpy((int16_t *)(hin + o_sig) + at, in->adc_rows[r] + w.first, (size_t)w.valid * 2);
         } else {
-            h_off[r] = pos;
-            if (win > 0) memcpy((float *)(hin + o_sig) + pos, in->rows[r] + st, (size_t)win * 4);
-            pos += win;
+            h_off[r] = at;
+            if (w.valid > 0) memcpy((float *)(hin + o_sig) + at, in->rows[r] + w.first, (size_t)w.valid * 4);
         }
     }
-    h_off[n_reads] = adc ? dpos : pos;
+    h_off[n_reads] = adc ? dpos.next : pos.next;
 
     // ---- the output block -------------------------------------------------------------------------------------------
     const int k = tail == WDX_LIVE_TAIL_SVM ? ctx->svm.k : tail == WDX_LIVE_TAIL_MLP ? ctx->mlp.k

@@ -135,7 +135,7 @@ int launch_synth_fill(uint64_t seed, int64_t first_read, int64_t n, int32_t n_ba
     return WDX_SUCCESS;
 }
 
-// ---- packed staging of a page-locked minibatch (wdx_api.hip: demux_batch_enqueue) ------------------------------------
+// ---- packed staging of a page-locked minibatch (wdx_minibatch.hip: fingerprint_float_rows) ------------------------------------
 // One workgroup per read: dword loads from the mapped host row (16 in flight per thread: the bus is 49 GB/s and ~1.5 us
 // away), coalesced dword stores to the packed device row.
 __global__ __launch_bounds__(256) void pack_windows_kernel(const float *__restrict__ src, int64_t stride, const int64_t *__restrict__ off,
