@@ -316,12 +316,14 @@ static int dtw_dev_route(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_ou
 // DTW of device rows dX (nX, L) against the resident refs -> d_out (nX, nY) [+ argmin]
 int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin,
                    hipStream_t stream) {
-    int rc = dtw_dev_route(ctx, dX, nX, d_out, d_argmin, stream);
-    const DtwRefs &R = ctx->refs;
-    if (rc || !R.any_inf || nX == 0 || R.nY == 0) return rc;
-    // a reference with an infinite sample (never a fingerprint): pairs with the same infinity at one index are NaN in the
-    // reference and +inf out of the kernels -- settled here, then the argmin again (a NaN wins its row)
-    if ((rc = launch_dtw_equal_inf(dX, nX, R.pad, R.Lpad, R.halo, R.nY, R.L, d_out, stream))) return rc;
+    if (int rc = dtw_dev_route(ctx, dX, nX, d_out, d_argmin, stream)) return rc;
+    return dtw_settle_inf(ctx->refs, dX, nX, d_out, d_argmin, stream);
+}
+
+// a reference with an infinite sample (never a fingerprint)
+int dtw_settle_inf(const DtwRefs &R, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin, hipStream_t stream) {
+    if (!R.any_inf || nX == 0 || R.nY == 0) return WDX_SUCCESS;
+    if (int rc = launch_dtw_equal_inf(dX, nX, R.pad, R.Lpad, R.halo, R.nY, R.L, d_out, stream)) return rc;
     if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
     return WDX_SUCCESS;
 }
@@ -641,27 +643,20 @@ int wdx_fingerprint_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *
                                int64_t *d_dwell, double *d_stats, int32_t *d_refine_idx, int32_t *d_status,
                                void *stream) {
     WDX_ENTER(ctx);
-    if (n_reads < 0 || !p_in || !rp || !rp->query ||
-        (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_refine_idx))) {
+    if (n_reads < 0 || !rp || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_refine_idx))) {
         set_error("fingerprint_refine_dev: bad arguments");
         return WDX_ERR_INVALID;
     }
-    if (rp->n_query < 1) {
-        set_error("consensus refinement: empty query");
-        return WDX_ERR_INVALID;
-    }
+    wdx_seg_params pv;
+    if ((rc = refine_seg_params("fingerprint_refine_dev", p_in, rp, &pv))) return rc;
     if (n_reads == 0) return WDX_SUCCESS;
-    wdx_seg_params pv = *p_in;
-    pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs
     std::lock_guard<std::mutex> g(ctx->mu);
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    RefineDev *rf = nullptr;
-    RefineDevGuard rf_guard{rf};
-    if ((rc = refine_prepare(ctx, *rp, n_reads, d_refine_idx, nullptr, s, &rf))) return rc;
     const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    return fingerprint_stage(ctx, in, pv, FpOut{d_fpt, d_dwell, d_stats, d_status}, ctx->fp_ws.p, s, rf, false);
+    return demux_chain(ctx, DtwRefs{}, in, pv, rp, d_refine_idx, nullptr, ctx->fp_ws.p, false, ChainTail{},
+                       ChainOut{FpOut{d_fpt, d_dwell, d_stats, d_status}}, s);
 }
 
 int wdx_fingerprint_profile_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
@@ -775,10 +770,7 @@ static int demux_dev_body(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row
                              R.window, R.penalty, d_dist, R.nY, 1, d_call, nullptr, 0, s, ctx->knobs, false, &ctx->dtw_last)))
             return rc;
     }
-    if (R.any_inf) {   // (see dtw_dev_locked)
-        if ((rc = launch_dtw_equal_inf(fpt, n_reads, R.pad, R.Lpad, R.halo, R.nY, R.L, d_dist, s))) return rc;
-        if ((rc = launch_argmin(d_dist, n_reads, R.nY, d_call, s))) return rc;
-    }
+    if ((rc = dtw_settle_inf(R, fpt, n_reads, d_dist, d_call, s))) return rc;
     Timed t(ctx, WDX_K_COUNT, s);
     return launch_count_calls(d_call, d_status, n_reads, R.nY, d_counts, s);
 }
@@ -799,16 +791,12 @@ int wdx_demux_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_
                          const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell, double *d_stats,
                          int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts,
                          void *d_work, void *stream) {
-    if (!p || !rp || !rp->query) {
+    if (!rp) {
         set_error("demux_refine_dev: bad arguments");
         return WDX_ERR_INVALID;
     }
-    if (rp->n_query < 1) {
-        set_error("consensus refinement: empty query");
-        return WDX_ERR_INVALID;
-    }
-    wdx_seg_params pv = *p;
-    pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs and of the DTW
+    wdx_seg_params pv;
+    if (int e = refine_seg_params("demux_refine_dev", p, rp, &pv)) return e;
     return demux_dev_body(ctx, d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, &pv, rp, d_fpt,
                           d_dwell, d_stats, d_refine_idx, d_status, d_dist, d_call, d_counts, d_work, stream);
 }

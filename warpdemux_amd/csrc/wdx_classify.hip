@@ -2,7 +2,7 @@
 // trees on the fingerprints themselves (at the end of the file; no DTW).  Host code only: the kernels are in wdx_svm.hip /
 // wdx_mlp.hip / wdx_boost.hip / wdx_dtw.hip.  The two tails share one host path each for "raw rows -> fingerprints
 // -> DTW row blocks -> tail" (wdx_demux_{svm,mlp}_dev) and "host rows in chunks -> DTW -> tail" (wdx_dtw_{svm,mlp}_predict);
-// what differs between them -- the resident-model checks, the SVM's fused route, the MLP's counter -- is in the entry points.
+// what differs between them -- the SVM's fused route, the MLP's counter -- is in the entry points (model checks: tail_ready).
 #include "wdx_ctx.h"
 
 #include <string.h>
@@ -254,14 +254,7 @@ int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
     }
     std::lock_guard<std::mutex> g(ctx->mu);
     DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->svm_set) {
-        set_error("demux_svm_dev needs wdx_set_refs and wdx_svm_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->svm.n_train) {
-        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)R.nY, ctx->svm.n_train);
-        return WDX_ERR_INVALID;
-    }
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_SVM, R.nY, 0, false, "demux_svm_dev"))) return rc;
     if ((rc = check_ref_length(R, *p))) return rc;
     if (n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
@@ -292,14 +285,7 @@ int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
     WDX_ENTER(ctx);
     std::lock_guard<std::mutex> g(ctx->mu);
     DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->svm_set) {
-        set_error("dtw_svm_predict needs wdx_set_refs and wdx_svm_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->svm.n_train) {
-        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)R.nY, ctx->svm.n_train);
-        return WDX_ERR_INVALID;
-    }
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_SVM, R.nY, 0, false, "dtw_svm_predict"))) return rc;
     if (n < 0 || (n > 0 && !X)) {
         set_error("dtw_svm_predict: bad arguments");
         return WDX_ERR_INVALID;
@@ -446,14 +432,7 @@ int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
     WDX_ENTER(ctx);
     std::lock_guard<std::mutex> g(ctx->mu);
     DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->mlp_set) {
-        set_error("dtw_mlp_predict needs wdx_set_refs and wdx_mlp_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->mlp.sizes[0]) {
-        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
-        return WDX_ERR_INVALID;
-    }
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_MLP, R.nY, 0, false, "dtw_mlp_predict"))) return rc;
     if (n < 0 || (n > 0 && !X)) {
         set_error("dtw_mlp_predict: bad arguments");
         return WDX_ERR_INVALID;
@@ -495,14 +474,7 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
     }
     std::lock_guard<std::mutex> g(ctx->mu);
     DtwRefs &R = ctx->refs;
-    if (R.window == 0 || !ctx->mlp_set) {
-        set_error("demux_mlp_dev needs wdx_set_refs and wdx_mlp_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (R.nY != ctx->mlp.sizes[0]) {
-        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)R.nY, ctx->mlp.sizes[0]);
-        return WDX_ERR_INVALID;
-    }
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_MLP, R.nY, 0, false, "demux_mlp_dev"))) return rc;
     if ((rc = check_ref_length(R, *p))) return rc;
     if (n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
@@ -698,28 +670,15 @@ int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
                         int32_t *d_refine_idx, int32_t *d_status, double *d_raw, double *d_prob, int32_t *d_pred,
                         double *d_conf, void *d_work, void *stream) {
     WDX_ENTER(ctx);
-    if (n_reads < 0 || !p || (rp && !rp->query) ||
-        (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
+    if (n_reads < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
         set_error("demux_boost_dev: bad arguments");
         return WDX_ERR_INVALID;
     }
-    if (rp && rp->n_query < 1) {
-        set_error("consensus refinement: empty query");
-        return WDX_ERR_INVALID;
-    }
-    wdx_seg_params pv = *p;
-    if (rp) pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs
+    wdx_seg_params pv;
+    if ((rc = refine_seg_params("demux_boost_dev", p, rp, &pv))) return rc;
     const int64_t K = pv.barcode_num_events;
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->boost_set) {
-        set_error("demux_boost_dev needs wdx_boost_set_model first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (K != ctx->boost.n_features) {
-        set_error("%s (%lld) != the boost model's features (%d)", rp ? "barcode_keep_events" : "barcode_num_events",
-                  (long long)K, ctx->boost.n_features);
-        return WDX_ERR_INVALID;
-    }
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_BOOST, 0, K, rp != nullptr, "demux_boost_dev"))) return rc;
     if (n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
@@ -728,12 +687,13 @@ int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
     const DemuxWork W = demux_work_layout(n_reads, K, false);
     double *fpt = d_fpt ? d_fpt : (double *)w;
     const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    RefineDev *rf = nullptr;
-    RefineDevGuard rf_guard{rf};
-    if (rp && (rc = refine_prepare(ctx, *rp, n_reads, d_refine_idx, w + round_up(W.bytes, 256), s, &rf))) return rc;
-    if ((rc = fingerprint_stage(ctx, in, pv, FpOut{fpt, nullptr, nullptr, d_status}, w + W.fp_ws, s, rf, rf == nullptr)))
-        return rc;
-    return boost_tail(ctx, ctx->boost, fpt, d_status, n_reads, d_raw, d_prob, d_pred, d_conf, s);
+    ChainTail tail;
+    tail.kind = WDX_LIVE_TAIL_BOOST;
+    tail.boost = &ctx->boost;
+    ChainOut out{FpOut{fpt, nullptr, nullptr, d_status}};
+    out.raw = d_raw, out.prob = d_prob, out.pred = d_pred, out.conf = d_conf;
+    // (no DTW here, whatever is resident: an empty reference set)
+    return demux_chain(ctx, DtwRefs{}, in, pv, rp, d_refine_idx, w + round_up(W.bytes, 256), w + W.fp_ws, !rp, tail, out, s);
 }
 
 }  // extern "C"

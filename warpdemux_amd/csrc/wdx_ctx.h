@@ -1,11 +1,15 @@
 // The opaque context behind include/wdx.h's wdx_ctx (internal; shared by wdx_api.hip, wdx_minibatch.hip,
-// wdx_classify.hip, wdx_comm.hip and wdx_live.hip).  Nothing here computes results.
+// wdx_chain.hip, wdx_classify.hip, wdx_comm.hip and wdx_live.hip).  Nothing here computes results.
 #pragma once
 #include "wdx_common.h"
+#include "wdx_refine_args.h"
 
 #include <mutex>
 #include <utility>
 #include <vector>
+
+// kept out of the library's dynamic symbol table
+#define WDX_INTERNAL __attribute__((visibility("hidden")))
 
 namespace wdx {
 
@@ -126,6 +130,11 @@ int set_refs_locked(wdx_ctx *ctx, const double *Y, int64_t nY, int64_t L, int32_
 // DTW of device rows dX (nX, L) against the resident refs -> d_out (nX, nY) [+ argmin]
 int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin,
                    hipStream_t stream);
+// (wdx_api.hip) behind a DTW launch when a resident reference holds an infinite sample (R.any_inf): pairs with the same
+// infinity at one index are NaN in the reference and +inf out of the kernels -- settled here, then the argmin again (a NaN
+// wins its row)
+WDX_INTERNAL int dtw_settle_inf(const DtwRefs &R, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin,
+                                hipStream_t stream);
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
@@ -161,6 +170,32 @@ int svm_tail(wdx_ctx *B, const SvmDev &M, const float *d_dist, int64_t n, const 
 // masks the reads whose d_status (nullable) is not 0 itself
 int boost_tail(wdx_ctx *B, const BoostDev &M, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
                double *d_prob, int32_t *d_pred, double *d_conf, hipStream_t s);
+
+// (wdx_chain.hip) "Is this model usable here": a DTW tail has its reference set and the tail's model is resident
+// (WDX_ERR_NO_REFS otherwise), and the model fits -- the SVM was trained on nY references, the MLP takes nY inputs, the boost
+// model K features (WDX_ERR_INVALID otherwise; refined: K is rp->barcode_keep_events and is named so).  tail: WDX_LIVE_TAIL_*.
+WDX_INTERNAL int tail_ready(const wdx_ctx *ctx, int tail, int64_t nY, int64_t K, bool refined, const char *who);
+
+// (wdx_chain.hip) The device chain of the host minibatches, the live tick and wdx_demux_boost_dev, enqueued on s:
+//   [refine_prepare]  with rp: d_refine_idx (nullable) = -1, the hand-over records in d_refine_ws (null: B->ref_ws) reset
+//   fingerprint stage on rd into out.fp, workspace d_fp_ws
+//   [DTW + call]      when R.nY > 0: out.dist (n, nY), out.call, out.counts (nullable)
+//   [tail]            SVM / MLP on out.dist (without a reference, R.nY == 0, their outputs are left alone), boost on out.fp.fpt;
+//                     failed reads: pred -1, NaN prob / conf
+// It sizes no buffer and copies nothing to the host.  `B` owns the stream's workspaces, the knobs and the event scopes.
+struct ChainTail {
+    int kind = WDX_LIVE_TAIL_NONE;   // WDX_LIVE_TAIL_*, and the model of that kind
+    const SvmDev *svm = nullptr; const MlpDev *mlp = nullptr; const BoostDev *boost = nullptr;
+};
+struct ChainOut {
+    FpOut fp;
+    float *dist = nullptr; int32_t *call = nullptr; int64_t *counts = nullptr;   // dist / call: null when no DTW runs
+    double *raw = nullptr, *prob = nullptr, *conf = nullptr; int32_t *pred = nullptr;
+    int64_t *n_nonfinite = nullptr;   // MLP tail: zeroed, then counted into
+};
+WDX_INTERNAL int demux_chain(wdx_ctx *B, const DtwRefs &R, const FpReads &rd, const wdx_seg_params &p, const wdx_refine_params *rp,
+                int32_t *d_refine_idx, void *d_refine_ws, void *d_fp_ws, bool main_events, const ChainTail &tail,
+                const ChainOut &out, hipStream_t s);
 
 }  // namespace wdx
 

@@ -241,33 +241,24 @@ int wdx_feeder_ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, 
 
 int wdx_feeder_ring_init_refine(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p,
                                 const wdx_refine_params *rp) {
-    if (!rp || !rp->query) {
+    if (!rp) {
         set_error("feeder_ring_init_refine: null refinement parameters");
         return WDX_ERR_INVALID;
     }
     // the limits of wdx_fingerprint_refine_batch, with its codes: a ring no minibatch could be served from is refused here
-    if (rp->n_query < 1) {
-        set_error("consensus refinement: empty query");
-        return WDX_ERR_INVALID;
-    }
-    if (rp->n_query > kRingMaxQuery || (p && p->num_events + 1 > kRingMaxSeries)) {
+    // (reported behind a null or empty query and ahead of barcode_keep_events, as they always were)
+    if (rp->query && rp->n_query >= 1 && (rp->n_query > kRingMaxQuery || (p && p->num_events + 1 > kRingMaxSeries))) {
         set_error("consensus refinement: the query must have 1..%d points and num_events + 1 <= %d", kRingMaxQuery, kRingMaxSeries);
         return WDX_ERR_UNSUPPORTED;
     }
-    if (rp->barcode_keep_events < 1) {
-        set_error("barcode_num_events must be >= 1");
-        return WDX_ERR_INVALID;
-    }
-    return ring_init(mem, bytes, g, p, rp);
+    wdx_seg_params pv;   // K of every minibatch of a refine ring
+    if (int e = refine_seg_params("feeder_ring_init_refine", p, rp, &pv, kRefineQuery | kRefineKeep)) return e;
+    return ring_init(mem, bytes, g, &pv, rp);
 }
 
 // rp == nullptr: the plain ring, exactly the bytes wdx_feeder_ring_init has always written
-static int ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p_in, const wdx_refine_params *rp) {
+static int ring_init(void *mem, size_t bytes, const wdx_feeder_geometry *g, const wdx_seg_params *p, const wdx_refine_params *rp) {
     const size_t need = ring_bytes(g, rp != nullptr);
-    wdx_seg_params pv{};
-    if (p_in) pv = *p_in;
-    if (rp) pv.barcode_num_events = rp->barcode_keep_events;   // K of every minibatch of a refine ring
-    const wdx_seg_params *p = p_in ? &pv : nullptr;
     if (!mem || !p || need == 0 || bytes < need || ((uintptr_t)mem & 4095u)) {
         set_error("feeder_ring_init: need parameters and a page-aligned block of %zu bytes for this geometry", need);
         return WDX_ERR_INVALID;

@@ -79,20 +79,12 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
         return WDX_ERR_INVALID;
     }
     if (n_reads == 0) return WDX_SUCCESS;   // (and nothing was touched, *n_nonfinite included)
-    if (rp) {
-        if (!rp->query) {
-            set_error("live_tick: bad arguments");
-            return WDX_ERR_INVALID;
-        }
-        if (rp->n_query < 1) {
-            set_error("consensus refinement: empty query");
-            return WDX_ERR_INVALID;
-        }
-        if (tail == WDX_LIVE_TAIL_SVM || tail == WDX_LIVE_TAIL_MLP) {
-            set_error("live_tick: consensus refinement is served with no tail or the boost tail (no DTW model is trained on "
-                      "refined fingerprints)");
-            return WDX_ERR_INVALID;
-        }
+    wdx_seg_params pv;   // K of the outputs, of the DTW and of the boost tail
+    if ((rc = refine_seg_params("live_tick", p_in, rp, &pv))) return rc;
+    if (rp && (tail == WDX_LIVE_TAIL_SVM || tail == WDX_LIVE_TAIL_MLP)) {
+        set_error("live_tick: consensus refinement is served with no tail or the boost tail (no DTW model is trained on "
+                  "refined fingerprints)");
+        return WDX_ERR_INVALID;
     }
     if ((want & WDX_WANT_REFINE_IDX) && (!rp || !refine_idx)) {
         set_error("live_tick: WDX_WANT_REFINE_IDX needs refinement parameters and a refine_idx array");
@@ -103,8 +95,6 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
         set_error("live_tick: an output `want` asks for has no array");
         return WDX_ERR_INVALID;
     }
-    wdx_seg_params pv = *p_in;
-    if (rp) pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs, of the DTW and of the boost tail
     const wdx_seg_params *p = &pv;
     const int64_t K = p->barcode_num_events;
     if (K < 1) {
@@ -137,27 +127,8 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
         set_error("live_tick: use_svm needs wdx_svm_set_model with a model trained on the resident reference set");
         return WDX_ERR_NO_REFS;
     }
-    if (tail == WDX_LIVE_TAIL_MLP) {
-        if (!ctx->mlp_set) {
-            set_error("live_tick: the MLP tail needs wdx_set_refs and wdx_mlp_set_model first");
-            return WDX_ERR_NO_REFS;
-        }
-        if (nY != ctx->mlp.sizes[0]) {
-            set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)nY, ctx->mlp.sizes[0]);
-            return WDX_ERR_INVALID;
-        }
-    }
-    if (tail == WDX_LIVE_TAIL_BOOST) {
-        if (!ctx->boost_set) {
-            set_error("live_tick: the boost tail needs wdx_boost_set_model first");
-            return WDX_ERR_NO_REFS;
-        }
-        if (K != ctx->boost.n_features) {
-            set_error("%s (%d) != the boost model's features (%d)", rp ? "barcode_keep_events" : "barcode_num_events", (int)K,
-                      ctx->boost.n_features);
-            return WDX_ERR_INVALID;
-        }
-    }
+    // (the SVM's two refusals above share one code here and nowhere else: kept as found)
+    if (tail != WDX_LIVE_TAIL_SVM && (rc = tail_ready(ctx, tail, nY, K, rp != nullptr, "live_tick"))) return rc;
     if (p->padding < 0) {
         set_error("padding must be >= 0");
         return WDX_ERR_INVALID;
@@ -280,8 +251,6 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
             *d_pred = (int32_t *)(dout + B.off[P_PRED]);
     int64_t *d_cnt = (int64_t *)(dout + B.off[P_CNT]);
 
-    RefineDev *rf = nullptr;
-    RefineDevGuard rf_guard{rf};
     StreamDrain drain(s);
     WDX_HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, s));
     const float *d_sig = (const float *)(din + o_sig);
@@ -293,27 +262,17 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
         if ((rc = launch_adc_rows(rows, n_reads, false, s))) return rc;
         d_sig = (const float *)ctx->in1.p;
     }
-    if (rp && (rc = refine_prepare(ctx, *rp, n_reads, need[P_RIDX] ? (int32_t *)(dout + B.off[P_RIDX]) : nullptr, nullptr, s, &rf)))
-        return rc;
     const FpReads rd{d_sig, (const int64_t *)(din + o_off), adc ? (const int32_t *)(din + o_len) : nullptr, 0, max_len, n_reads,
                      (const int32_t *)(din + o_zero), (const int32_t *)(din + o_len), (const uint8_t *)(din + o_ok)};
-    const FpOut fo{d_fpt, need[P_DWELL] ? (int64_t *)(dout + B.off[P_DWELL]) : nullptr,
-                   need[P_STATS] ? (double *)(dout + B.off[P_STATS]) : nullptr, d_status};
-    if ((rc = fingerprint_stage(ctx, rd, *p, fo, ctx->fp_ws.p, s, rf, false))) return rc;
-    if (run_dtw) {
-        if ((rc = dtw_dev_locked(ctx, d_fpt, n_reads, d_dist, d_call, s))) return rc;
-        if ((rc = launch_count_calls(d_call, d_status, n_reads, nY, nullptr, s))) return rc;
-    }
-    // failed reads: pred -1, NaN prob / conf, as every other entry point that runs a tail returns them
-    if (run_tail && tail == WDX_LIVE_TAIL_SVM) {
-        if ((rc = svm_tail(ctx, ctx->svm, d_dist, n_reads, d_status, d_prob, d_pred, d_conf, s))) return rc;
-    } else if (run_tail && tail == WDX_LIVE_TAIL_MLP) {
-        WDX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-        Timed t(ctx, WDX_K_MLP, s);
-        if ((rc = launch_mlp_predict(ctx->mlp, d_dist, n_reads, d_status, d_prob, d_pred, d_conf, d_cnt, s))) return rc;
-    } else if (run_tail) {
-        if ((rc = boost_tail(ctx, ctx->boost, d_fpt, d_status, n_reads, nullptr, d_prob, d_pred, d_conf, s))) return rc;
-    }
+    ChainTail ct;
+    ct.kind = tail;
+    ct.svm = &ctx->svm, ct.mlp = &ctx->mlp, ct.boost = &ctx->boost;
+    ChainOut co{FpOut{d_fpt, need[P_DWELL] ? (int64_t *)(dout + B.off[P_DWELL]) : nullptr,
+                      need[P_STATS] ? (double *)(dout + B.off[P_STATS]) : nullptr, d_status}};
+    co.dist = d_dist, co.call = d_call, co.prob = d_prob, co.pred = d_pred, co.conf = d_conf, co.n_nonfinite = d_cnt;
+    // main_events = false, with and without refinement: wdx_live_tick has never recorded them (wdx_ctx.h: fingerprint_stage)
+    int32_t *d_ridx = need[P_RIDX] ? (int32_t *)(dout + B.off[P_RIDX]) : nullptr;
+    if ((rc = demux_chain(ctx, resident ? R : DtwRefs{}, rd, *p, rp, d_ridx, nullptr, ctx->fp_ws.p, false, ct, co, s))) return rc;
     // one device->host copy: the wanted pieces are the front of the block
     WDX_HIP_TRY(hipMemcpyAsync(hout, dout, B.copy_bytes, hipMemcpyDeviceToHost, s));
     WDX_HIP_TRY(hipStreamSynchronize(s));

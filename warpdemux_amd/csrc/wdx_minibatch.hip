@@ -23,11 +23,10 @@ struct MbHostOut {  // host destinations of one minibatch; null = not wanted (st
 };
 
 // Way (i) in of float32 rows of one stride, pageable or not: the 2-D DMA copy of the columns that hold every adapter window
-// of the batch into B->in0, a_start / a_end / ok into in1 / in2 / in3 (the caller sized all four), and the fingerprint
-// stage on them.  The rows are NaN-padded to sig_preload_size (file_proc.py:244-260) and the kernels never read outside
-// [start, stop), so nothing else has to travel.
-static int fingerprint_float_columns(wdx_ctx *B, const wdx_minibatch_in &in, const WindowBatch &wb, const wdx_seg_params &p,
-                                     const FpOut &out, const RefineDev *rf, bool main_events) {
+// of the batch into B->in0, a_start / a_end / ok into in1 / in2 / in3 (the caller sized all four); *rd = the reads as the
+// fingerprint stage takes them.  The rows are NaN-padded to sig_preload_size (file_proc.py:244-260) and the kernels never
+// read outside [start, stop), so nothing else has to travel.
+static int fingerprint_float_columns(wdx_ctx *B, const wdx_minibatch_in &in, const WindowBatch &wb, FpReads *rd) {
     hipStream_t s = B->stream;
     const int64_t n_reads = in.n_reads, stride = in.stride;
     if (wb.col1 > wb.col0)
@@ -37,15 +36,14 @@ static int fingerprint_float_columns(wdx_ctx *B, const wdx_minibatch_in &in, con
     WDX_HIP_TRY(hipMemcpyAsync(B->in1.p, in.a_start, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
     WDX_HIP_TRY(hipMemcpyAsync(B->in2.p, in.a_end, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
     if (in.ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, in.ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
-    const FpReads rd{(const float *)B->in0.p, nullptr, nullptr, stride, wb.max_len, n_reads, (const int32_t *)B->in1.p,
-                     (const int32_t *)B->in2.p, in.ok ? (const uint8_t *)B->in3.p : nullptr};
-    return fingerprint_stage(B, rd, p, out, B->fp_ws.p, s, rf, main_events);
+    *rd = FpReads{(const float *)B->in0.p, nullptr, nullptr, stride, wb.max_len, n_reads, (const int32_t *)B->in1.p,
+                  (const int32_t *)B->in2.p, in.ok ? (const uint8_t *)B->in3.p : nullptr};
+    return WDX_SUCCESS;
 }
 
-// The float32 rows of one minibatch -> device, and the fingerprint stage on them (on B->stream); rf: the refinement
-// branch (its sig_barcode_start counts from the window's first sample, which none of the three ways in moves).
-static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const wdx_seg_params *p, const FpOut &out,
-                                  const RefineDev *rf) {
+// The float32 rows of one minibatch -> device (on B->stream); *rd = the reads as the fingerprint stage takes them.  (The
+// refinement branch's sig_barcode_start counts from the window's first sample, which none of the three ways in moves.)
+static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const wdx_seg_params *p, FpReads *rd) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const float *sig = in.sig;
@@ -93,10 +91,10 @@ static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const 
         WDX_HIP_TRY(hipMemcpyAsync(d_as, a_start, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
         WDX_HIP_TRY(hipMemcpyAsync(d_ae, a_end, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
         if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
-        const FpReads rd{(const float *)B->in0.p, d_off, d_len, 0, wb.max_len, n_reads, d_as, d_ae, d_ok};
-        return fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s, rf, rf == nullptr);
+        *rd = FpReads{(const float *)B->in0.p, d_off, d_len, 0, wb.max_len, n_reads, d_as, d_ae, d_ok};
+        return WDX_SUCCESS;
     }
-    if (!sig_dev) return fingerprint_float_columns(B, in, wb, *p, out, rf, rf == nullptr);
+    if (!sig_dev) return fingerprint_float_columns(B, in, wb, rd);
     // host images (page-locked, owned by the slot until its copy has run): off int64[n+1] | st int32[n] | len
     // int32[n] | a_start' int32[n] | a_end' int32[n]
     const size_t ib = (size_t)(n_reads + 1) * 8 + (size_t)n_reads * 16;
@@ -122,8 +120,8 @@ static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const 
                   *d_ae = d_as + n_reads;
     if ((rc = launch_pack_windows(sig_dev, stride, n_reads, d_off, d_st, d_len, (float *)B->in0.p, s))) return rc;
     if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
-    const FpReads rd{(const float *)B->in0.p, d_off, d_len, 0, wb.max_len, n_reads, d_as, d_ae, d_ok};
-    return fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s, rf, rf == nullptr);
+    *rd = FpReads{(const float *)B->in0.p, d_off, d_len, 0, wb.max_len, n_reads, d_as, d_ae, d_ok};
+    return WDX_SUCCESS;
 }
 
 // Argument checks of every *_adc entry point: host arithmetic only, so a bad descriptor is refused before (and without) a
@@ -173,13 +171,12 @@ static int adc_check_args(const char *who, const wdx_minibatch_adc_in *in) {
     return WDX_SUCCESS;
 }
 
-// The int16 ADC rows of one minibatch -> calibrated float32 windows in a PACKED device buffer (wdx_adc.hip), and the
-// fingerprint stage on them.  The same three ways in as the float32 rows: (i) 2-D DMA copy of the int16 columns that hold
+// The int16 ADC rows of one minibatch -> calibrated float32 windows in a PACKED device buffer (wdx_adc.hip); *rd = the reads
+// as the fingerprint stage takes them.  The same three ways in as the float32 rows: (i) 2-D DMA copy of the int16 columns that hold
 // the windows, then decode_adc_kernel; (ii) a page-locked minibatch: pack_windows_adc_kernel reads the windows over the
 // bus; (iii) rows the caller packed: one flat copy, then decode_adc_kernel.  Row r of the packed buffer = the window of the
 // float32 row the read stands for, its start rounded down to a multiple of 8 (16-byte groups of int16; wdx_window.h).
-static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const wdx_seg_params *p, const FpOut &out,
-                                const RefineDev *rf) {
+static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const wdx_seg_params *p, FpReads *rd) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const int64_t n = A.n_reads, stride = A.stride;
@@ -253,8 +250,8 @@ static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const
     }
     if ((rc = launch_adc_rows(rows, n, adc_dev != nullptr, s))) return rc;
     if (A.ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, A.ok, (size_t)n, hipMemcpyHostToDevice, s));
-    const FpReads rd{(const float *)B->in0.p, d_dst, d_out, 0, wb.max_len, n, d_as, d_ae, A.ok ? (const uint8_t *)B->in3.p : nullptr};
-    return fingerprint_stage(B, rd, *p, out, B->fp_ws.p, s, rf, rf == nullptr);
+    *rd = FpReads{(const float *)B->in0.p, d_dst, d_out, 0, wb.max_len, n, d_as, d_ae, A.ok ? (const uint8_t *)B->in3.p : nullptr};
+    return WDX_SUCCESS;
 }
 
 // wdx_fingerprint_batch / wdx_fingerprint_refine_batch: float32 rows of one stride through way (i) on the context's own
@@ -264,20 +261,20 @@ static int fingerprint_batch_impl(wdx_ctx *ctx, const float *sig, int64_t n_read
                                   const wdx_seg_params *p_in, const wdx_refine_params *rp, double *fpt, int64_t *dwell,
                                   double *stats, int32_t *refine_idx, int32_t *status) {
     WDX_ENTER(ctx);
-    if (!p_in || (rp && (!rp->query || !refine_idx)) || n_reads < 0 || stride < 0 ||
+    if ((rp && !refine_idx) || n_reads < 0 || stride < 0 ||
         (n_reads > 0 && (!sig || !a_start || !a_end || !fpt || !dwell || !stats || !status))) {
         set_error("fingerprint_batch: bad arguments");
         return WDX_ERR_INVALID;
     }
-    wdx_seg_params pv = *p_in;
-    if (rp) pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs
+    wdx_seg_params pv;   // (an empty batch succeeds whatever the query's length, as it always has)
+    if ((rc = refine_seg_params("fingerprint_batch", p_in, rp, &pv, n_reads > 0 ? kRefineQuery : 0u))) return rc;
     if (n_reads == 0) return WDX_SUCCESS;
     std::lock_guard<std::mutex> g(ctx->mu);
     hipStream_t s = ctx->stream;
     if ((rc = use_stream(ctx, s))) return rc;
     const int64_t K = pv.barcode_num_events;
-    if (K < 1 || (rp && rp->n_query < 1)) {
-        set_error(K < 1 ? "barcode_num_events must be >= 1" : "consensus refinement: empty query");
+    if (K < 1) {
+        set_error("barcode_num_events must be >= 1");
         return WDX_ERR_INVALID;
     }
     WindowBatch wb(stride);
@@ -294,13 +291,13 @@ static int fingerprint_batch_impl(wdx_ctx *ctx, const float *sig, int64_t n_read
     if ((rc = ctx->out3.ensure((size_t)n_reads * 4))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
     if (rp && (rc = ctx->mb_ridx.ensure((size_t)n_reads * 12))) return rc;
-    RefineDev *rf = nullptr;
-    RefineDevGuard rf_guard{rf};
     StreamDrain drain(s);
-    if (rp && (rc = refine_prepare(ctx, *rp, n_reads, (int32_t *)ctx->mb_ridx.p, nullptr, s, &rf))) return rc;
     const wdx_minibatch_in in{sig, n_reads, stride, nullptr, nullptr, a_start, a_end, ok};
-    const FpOut out{(double *)ctx->out0.p, (int64_t *)ctx->out1.p, (double *)ctx->out2.p, (int32_t *)ctx->out3.p};
-    if ((rc = fingerprint_float_columns(ctx, in, wb, pv, out, rf, false))) return rc;
+    FpReads rd;
+    if ((rc = fingerprint_float_columns(ctx, in, wb, &rd))) return rc;
+    const ChainOut out{FpOut{(double *)ctx->out0.p, (int64_t *)ctx->out1.p, (double *)ctx->out2.p, (int32_t *)ctx->out3.p}};
+    int32_t *d_ridx = (int32_t *)ctx->mb_ridx.p;
+    if ((rc = demux_chain(ctx, DtwRefs{}, rd, pv, rp, d_ridx, nullptr, ctx->fp_ws.p, false, ChainTail{}, out, s))) return rc;
     WDX_HIP_TRY(hipMemcpyAsync(fpt, ctx->out0.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
     WDX_HIP_TRY(hipMemcpyAsync(dwell, ctx->out1.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
     WDX_HIP_TRY(hipMemcpyAsync(stats, ctx->out2.p, (size_t)n_reads * 48, hipMemcpyDeviceToHost, s));
@@ -350,8 +347,7 @@ struct MbRefine {
 // Everything is ENQUEUED on B->stream -- copies in, the kernel chain, copies out to the host destinations (caller arrays
 // or the slot's page-locked block); the caller synchronises.
 static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, const wdx_seg_params *p,
-                               const MbHostOut &H, const SvmDev *svm, const MbRefine *rfn = nullptr,
-                               const BoostDev *boost = nullptr) {
+                               const MbHostOut &H, const ChainTail &tail = ChainTail{}, const MbRefine *rfn = nullptr) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
     const int64_t n_reads = in.n_reads();
@@ -363,49 +359,29 @@ static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, con
     if ((rc = B->out3.ensure((size_t)n_reads * 4))) return rc;
     if (H.dwell && (rc = B->mb_dwell.ensure((size_t)(n_reads * K) * 8))) return rc;
     if (H.stats && (rc = B->mb_stats.ensure((size_t)n_reads * 48))) return rc;
-    if (svm || boost) {   // (never both: demux_submit_locked)
-        if ((rc = B->mb_prob.ensure((size_t)n_reads * (svm ? svm->k : boost->k) * 8))) return rc;
+    const size_t pb = (size_t)n_reads * (tail.svm ? tail.svm->k : tail.boost ? tail.boost->k : 0) * 8;   // (never both)
+    if (pb) {
+        if ((rc = B->mb_prob.ensure(pb))) return rc;
         if ((rc = B->mb_pred.ensure((size_t)n_reads * 4))) return rc;
         if ((rc = B->mb_conf.ensure((size_t)n_reads * 8))) return rc;
     }
     if ((rc = B->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
     int64_t *d_dwell = H.dwell ? (int64_t *)B->mb_dwell.p : nullptr;
     double *d_stats = H.stats ? (double *)B->mb_stats.p : nullptr;
-    const FpOut out{(double *)B->out0.p, d_dwell, d_stats, (int32_t *)B->out3.p};
-    RefineDev *rf = nullptr;
-    RefineDevGuard rf_guard{rf};
-    if (rfn) {
-        if ((rc = B->mb_ridx.ensure((size_t)n_reads * 12))) return rc;
-        if ((rc = refine_prepare(B, *rfn->rp, n_reads, (int32_t *)B->mb_ridx.p, nullptr, s, &rf))) return rc;
-    }
-    if ((rc = in.adc ? fingerprint_adc_rows(B, *in.adc, p, out, rf) : fingerprint_float_rows(B, *in.f, p, out, rf))) return rc;
+    if (rfn && (rc = B->mb_ridx.ensure((size_t)n_reads * 12))) return rc;
+    FpReads rd;
+    if ((rc = in.adc ? fingerprint_adc_rows(B, *in.adc, p, &rd) : fingerprint_float_rows(B, *in.f, p, &rd))) return rc;
+    ChainOut out{FpOut{(double *)B->out0.p, d_dwell, d_stats, (int32_t *)B->out3.p}};
+    out.dist = (float *)B->out1.p, out.call = (int32_t *)B->out2.p;
+    out.prob = (double *)B->mb_prob.p, out.pred = (int32_t *)B->mb_pred.p, out.conf = (double *)B->mb_conf.p;
+    const wdx_refine_params *rp = rfn ? rfn->rp : nullptr;
+    if ((rc = demux_chain(B, R, rd, *p, rp, (int32_t *)B->mb_ridx.p, nullptr, B->fp_ws.p, !rp, tail, out, s))) return rc;
     if (R.nY > 0) {
-        if ((rc = dtw_dev_locked(B, (const double *)B->out0.p, n_reads, (float *)B->out1.p,
-                                 (int32_t *)B->out2.p, s)))
-            return rc;
-        if ((rc = launch_count_calls((int32_t *)B->out2.p, (const int32_t *)B->out3.p, n_reads, R.nY,
-                                     nullptr, s)))
-            return rc;
         if (H.call) WDX_HIP_TRY(hipMemcpyAsync(H.call, B->out2.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
         if (H.dist) WDX_HIP_TRY(hipMemcpyAsync(H.dist, B->out1.p, db, hipMemcpyDeviceToHost, s));
-        if (svm) {
-            // the classifier tail on the distance rows that are on the device anyway (models/dtw_svm.py:90-93, models/utils.py:45-61);
-            // failed reads: pred -1, NaN probabilities (the reference never shows them to the model)
-            if ((rc = svm_tail(B, *svm, (const float *)B->out1.p, n_reads, (const int32_t *)B->out3.p, (double *)B->mb_prob.p,
-                               (int32_t *)B->mb_pred.p, (double *)B->mb_conf.p, s)))
-                return rc;
-            if (H.prob) WDX_HIP_TRY(hipMemcpyAsync(H.prob, B->mb_prob.p, (size_t)n_reads * svm->k * 8, hipMemcpyDeviceToHost, s));
-            if (H.pred) WDX_HIP_TRY(hipMemcpyAsync(H.pred, B->mb_pred.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
-            if (H.conf) WDX_HIP_TRY(hipMemcpyAsync(H.conf, B->mb_conf.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
-        }
     }
-    if (boost) {
-        // Fpt_Boost.predict on the fingerprint rows themselves, which are on the device anyway (models/fpt_boost.py): no
-        // references, no distances; the kernel gives failed reads pred -1 and NaN
-        if ((rc = boost_tail(B, *boost, (const double *)B->out0.p, (const int32_t *)B->out3.p, n_reads, nullptr,
-                             (double *)B->mb_prob.p, (int32_t *)B->mb_pred.p, (double *)B->mb_conf.p, s)))
-            return rc;
-        if (H.prob) WDX_HIP_TRY(hipMemcpyAsync(H.prob, B->mb_prob.p, (size_t)n_reads * boost->k * 8, hipMemcpyDeviceToHost, s));
+    if (pb && (tail.boost || R.nY > 0)) {
+        if (H.prob) WDX_HIP_TRY(hipMemcpyAsync(H.prob, B->mb_prob.p, pb, hipMemcpyDeviceToHost, s));
         if (H.pred) WDX_HIP_TRY(hipMemcpyAsync(H.pred, B->mb_pred.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
         if (H.conf) WDX_HIP_TRY(hipMemcpyAsync(H.conf, B->mb_conf.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
     }
@@ -461,7 +437,7 @@ static int demux_batch_blocking(wdx_ctx *ctx, const char *who, const MbIn &in, c
     H.call = call;
     H.dist = dist;
     H.fpt = fpt;
-    if ((rc = demux_batch_enqueue(ctx, ctx->refs, in, p, H, nullptr))) return rc;
+    if ((rc = demux_batch_enqueue(ctx, ctx->refs, in, p, H))) return rc;
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
     if (ctx->refs.nY == 0)
@@ -515,7 +491,7 @@ int wdx_fingerprint_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, cons
     H.fpt = fpt;
     H.dwell = dwell;
     H.stats = stats;
-    if ((rc = demux_batch_enqueue(ctx, DtwRefs{}, mb, p, H, nullptr))) return rc;
+    if ((rc = demux_batch_enqueue(ctx, DtwRefs{}, mb, p, H))) return rc;
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
     return WDX_SUCCESS;
@@ -602,24 +578,16 @@ int wdx_demux_submit_refine(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_in *
     if (in_adc)
         if (int e = adc_check_args("demux_submit_refine", in_adc)) return e;
     WDX_ENTER(ctx);
-    if (!p || !rp || !rp->query || n_refs < 0) {
+    if (!rp || n_refs < 0) {
         set_error("demux_submit_refine: bad arguments");
         return WDX_ERR_INVALID;
     }
-    if (rp->n_query < 1) {
-        set_error("consensus refinement: empty query");
-        return WDX_ERR_INVALID;
-    }
-    if (rp->barcode_keep_events < 1) {
-        set_error("barcode_num_events must be >= 1");
-        return WDX_ERR_INVALID;
-    }
+    wdx_seg_params pv;   // K of the outputs and of the DTW
+    if ((rc = refine_seg_params("demux_submit_refine", p, rp, &pv, kRefineQuery | kRefineKeep))) return rc;
     if (n_refs == 0 && (want & (WDX_WANT_DIST | WDX_WANT_SVM))) {
         set_error("demux_submit_refine: a fingerprint-only minibatch (n_refs = 0) has no distances and no SVM tail");
         return WDX_ERR_INVALID;
     }
-    wdx_seg_params pv = *p;
-    pv.barcode_num_events = rp->barcode_keep_events;  // K of the outputs and of the DTW
     std::lock_guard<std::mutex> g(ctx->mu);
     MbIn mb;
     mb.f = in;
@@ -657,27 +625,12 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
         set_error("demux_submit: WDX_WANT_SVM and WDX_WANT_BOOST share prob / pred / conf: ask for one of them");
         return WDX_ERR_INVALID;
     }
-    if (want_boost) {
-        if (!ctx->boost_set) {
-            set_error("demux_submit: WDX_WANT_BOOST needs wdx_boost_set_model first");
-            return WDX_ERR_NO_REFS;
-        }
-        if (p->barcode_num_events != ctx->boost.n_features) {
-            set_error("%s (%d) != the boost model's features (%d)", rp ? "barcode_keep_events" : "barcode_num_events",
-                      (int)p->barcode_num_events, ctx->boost.n_features);
-            return WDX_ERR_INVALID;
-        }
-    }
-    if (want_svm) {
-        if (!ctx->svm_set) {
-            set_error("demux_submit: WDX_WANT_SVM needs wdx_svm_set_model first");
-            return WDX_ERR_NO_REFS;
-        }
-        if (ctx->refs.nY != ctx->svm.n_train) {
-            set_error("reference set has %lld rows but the SVM was trained on %d", (long long)ctx->refs.nY, ctx->svm.n_train);
-            return WDX_ERR_INVALID;
-        }
-    }
+    const BoostDev boost = ctx->boost;   // (by value: the kernel's arguments are this model, whatever is set later)
+    ChainTail tail;
+    tail.kind = want_svm ? WDX_LIVE_TAIL_SVM : want_boost ? WDX_LIVE_TAIL_BOOST : WDX_LIVE_TAIL_NONE;
+    tail.svm = want_svm ? &ctx->svm : nullptr;
+    tail.boost = want_boost ? &boost : nullptr;
+    if ((rc = tail_ready(ctx, tail.kind, ctx->refs.nY, p->barcode_num_events, rp != nullptr, "demux_submit"))) return rc;
     wdx_ctx *S = nullptr;
     if ((rc = slot_get(ctx, slot, &S))) return rc;
     if (S->slot_busy) {
@@ -741,10 +694,7 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
     MbRefine rfn;
     rfn.rp = rp;
     rfn.h_idx = S->slot_want_ridx ? (int32_t *)(ho + S->slot_off_ridx) : nullptr;
-    const BoostDev boost = ctx->boost;   // (by value: the kernel's arguments are this model, whatever is set later)
-    if ((rc = demux_batch_enqueue(S, R, in, p, H, want_svm ? &ctx->svm : nullptr, rp ? &rfn : nullptr,
-                                  want_boost ? &boost : nullptr)))
-        return rc;
+    if ((rc = demux_batch_enqueue(S, R, in, p, H, tail, rp ? &rfn : nullptr))) return rc;
     drain.done();  // in flight on purpose: wdx_demux_wait synchronises
     if (S->dtw_last.family != WDX_DTW_NONE) ctx->dtw_last = S->dtw_last;
     S->slot_busy = true;
