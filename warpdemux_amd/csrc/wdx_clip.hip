@@ -6,9 +6,10 @@
 // kernel's wave-cycles for 2.9 k of its 10.5 k VALU instructions per read, with ~18 of its ~50 barriers.
 //
 // One wave owns one read and keeps ALL its samples in registers (NPL per lane: the 18 KB are read from HBM once more
-// -- the chain used 9 % of the HBM rate -- and never touch LDS); LDS holds only the wave's 2048-bin histogram (8.5 KB
-// per wave; one wave = one read = one workgroup, see kClipWaves).  There is no barrier anywhere: what one lane writes
-// to LDS the others read in program order (DS operations of a wave execute in issue order).
+// -- the chain used 9 % of the HBM rate -- and never touch LDS); LDS holds only the wave's 2048-bin histogram (8 KB
+// per wave, the 64-word member list lies over it; one wave = one read = one workgroup, see kClipWaves).  There is no
+// barrier anywhere: what one lane writes to LDS the others read in program order (DS operations of a wave execute in
+// issue order).
 //   * extremes of the raw bit patterns (non-negative samples: the pattern orders like the value and is the key;
 //     negative samples -- outliers by construction of the statistic -- are clamped to the smallest non-negative one,
 //     which leaves both medians unchanged under two conditions that are checked); an infinity or a NaN ->
@@ -34,7 +35,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // (one read = one wave = one workgroup: with four reads per workgroup a finished wave's registers and LDS waited for the slowest
 // of the four -- reads differ by their > 64-member levels -- and the kernel ran 45.1 instead of 38.9 ms per 10 M reads)
 constexpr int kClipWaves = 1;                       // reads per workgroup
-constexpr int kClipWaveWords = kHB + 64;            // histogram | member list
+constexpr int kClipWaveWords = kHB;                 // histogram; the member list lies over its first 64 words (8 192 B)
 
 struct ClipArgs {
     FpArgs a;
@@ -53,6 +54,11 @@ __device__ __forceinline__ unsigned clip_xor1(unsigned x) { return WDX_DPP(0u, x
 __device__ __forceinline__ unsigned clip_xor4(unsigned x) {
     return (unsigned)__builtin_amdgcn_ds_swizzle((int)x, 0x101f);  // bit mode: and 0x1f, xor 4
 }
+// a wave-uniform value computed on the VALU, moved to a scalar register where it is defined (it is live beside the samples
+// for the rest of the kernel; every use is uniform)
+__device__ __forceinline__ float clip_uniform(float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
 __device__ __forceinline__ void clip_wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -65,7 +71,7 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
     const int lane = threadIdx.x & 63;
     const wdx_seg_params &P = A.p;
     unsigned *hist = lds;          // kHB words
-    unsigned *wl = lds + kHB;      // 64 words
+    unsigned *wl = lds;            // 64 words OVER the histogram: written only once a level has B, cnt and kin in registers
 
     // A0 extract_adapter (as fast_body)
     const int64_t row_off = A.row_off ? A.row_off[r] : r * A.stride;
@@ -165,22 +171,33 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
         if (lane == 0) recs[r] = out;
         return;
     }
-    // lanes of the last group that lie past the window: valid[q] <=> the sample they hold is theirs
+    // lanes of the last group that lie past the window: valid[q] <=> the sample they hold is theirs, q >= inv (ONE register
+    // from the first call to the second: how far the lane's load was pulled back into the window)
     const unsigned last4 = (unsigned)(n - 4);
     const unsigned i_last = (unsigned)((ng - 1) * 64 + lane) * 4u;  // this lane's first index in the last group
+    unsigned inv = i_last - min(i_last, last4);
+    asm volatile("" : "+v"(inv));
     auto pad_last_group = [&](unsigned padkey) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < NG; ++j) {
             if (j == ng - 1) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const bool valid = min(i_last, last4) + (unsigned)q >= i_last;
+                    const bool valid = (unsigned)q >= inv;
                     u[4 * j + q] = valid ? u[4 * j + q] : padkey;
                 }
             }
         }
     };
     pad_last_group(umx);
+
+    // the lane for an LDS address, as an opaque copy: lane * 4, * 8 and * 16 are then made where they are used instead of
+    // living beside the samples from the first level to the last
+    auto lane_now = [&]() __attribute__((always_inline)) -> int {
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        return l;
+    };
 
     // every element of the groups that hold data, highest group first: ONE dispatch on ng (a compare tree) and then
     // straight fall-through, instead of a test per group and pass
@@ -239,9 +256,9 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
         // the ranking are dependent chains and go first among the SIMD's waves: 38.9 -> 38.5 ms per 10 M reads)
         __builtin_amdgcn_s_setprio(0);
         {
-            uint4 *h4 = reinterpret_cast<uint4 *>(hist);
+            uint4 *h4 = reinterpret_cast<uint4 *>(hist) + lane_now();
 #pragma unroll
-            for (int q = 0; q < kHB / 256; ++q) h4[q * 64 + lane] = make_uint4(0, 0, 0, 0);
+            for (int q = 0; q < kHB / 256; ++q) h4[q * 64] = make_uint4(0, 0, 0, 0);
         }
         clip_wave_fence();
         if constexpr (MODE == 1) {
@@ -282,30 +299,35 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
         unsigned B, cnt, kin;
         {
             const uint2 *h2 = reinterpret_cast<const uint2 *>(hist);
-            unsigned s[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const uint2 v = h2[q * 64 + lane];
-                s[q] = v.x + v.y;
-            }
-            // lanes 0..31 keep chunk q, lanes 32..63 chunk q + 8
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const auto sw = __builtin_amdgcn_permlane32_swap(s[q], s[q + 8], false, false);
-                s[q] = sw[0] + sw[1];
-            }
-            // rows of 16: row 0 chunk q, row 1 chunk q + 4, row 2 chunk q + 8, row 3 chunk q + 12
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(s[q], s[q + 4], false, false);
-                s[q] = sw[0] + sw[1];
-            }
+            const uint2 *h2l = h2 + lane_now();
+            // (in eight stages of two chunk rows, each carried on as ONE partial sum: all sixteen rows at once are 48
+            // registers beside the samples; the sums are those of the one-stage tree, in its order)
+            auto row = [&](int q) __attribute__((always_inline)) -> unsigned {
+                const uint2 v = h2l[q * 64];
+                return v.x + v.y;
+            };
+            // rows q and q + 8: lanes 0..31 keep chunk q, lanes 32..63 chunk q + 8
+            auto half = [&](int q) __attribute__((always_inline)) -> unsigned {
+                const auto sw = __builtin_amdgcn_permlane32_swap(row(q), row(q + 8), false, false);
+                unsigned t = sw[0] + sw[1];
+                asm volatile("" : "+v"(t));  // (one stage's loads are not hoisted over the previous stage's sums)
+                return t;
+            };
+            // rows of 16 lanes: row 0 chunk q, row 1 chunk q + 4, row 2 chunk q + 8, row 3 chunk q + 12
+            auto quad = [&](int q) __attribute__((always_inline)) -> unsigned {
+                const unsigned x = half(q), y = half(q + 4);
+                const auto sw = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+                return sw[0] + sw[1];
+            };
             const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {  // lane bit 3: + 2
-                const unsigned keep = b3 ? s[q + 2] : s[q], give = b3 ? s[q] : s[q + 2];
-                s[q] = keep + clip_xor8(give);
-            }
+            auto pair = [&](int q) __attribute__((always_inline)) -> unsigned {  // lane bit 3: + 2
+                const unsigned x = quad(q), y = quad(q + 2);
+                const unsigned keep = b3 ? y : x, give = b3 ? x : y;
+                return keep + clip_xor8(give);
+            };
+            unsigned s[2];
+            s[0] = pair(0);
+            s[1] = pair(1);
             {  // lane bit 2: + 1
                 const unsigned keep = b2 ? s[1] : s[0], give = b2 ? s[0] : s[1];
                 s[0] = keep + clip_xor4(give);
@@ -318,7 +340,7 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
             const int fl = (int)__builtin_ctzll(mk);  // (mk != 0: the histogram holds m > k keys)
             const unsigned qs = (unsigned)fl >> 2;
             const unsigned k2 = k - (unsigned)__builtin_amdgcn_readlane((int)(incl - T), fl);
-            const uint2 c = h2[qs * 64 + lane];
+            const uint2 c = h2l[qs * 64];
             const unsigned ps = c.x + c.y;
             const unsigned incl2 = wave_incl_scan_u32(ps);
             const unsigned long long mk2 = __ballot(incl2 > k2);
@@ -356,6 +378,9 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
         };
         if (cnt <= 64u) {
             // gather without LDS atomics: the wave's count is a scalar, a member's slot comes from the ballot
+            // (the member list lies over the histogram, which is dead from here on -- B, cnt and kin are in registers, a
+            // further level clears it before use: no write to wl may move ahead of the last histogram read)
+            clip_wave_fence();
             unsigned wc = 0;
             const float m2 = opaque(med), s2 = opaque(lin_scale);
             auto put = [&](bool mbr, unsigned key) __attribute__((always_inline)) {
@@ -385,7 +410,7 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
                 });
             }
             clip_wave_fence();
-            const unsigned mine = (unsigned)lane < cnt ? wl[lane] : 0xffffffffu;
+            const unsigned mine = (unsigned)lane < cnt ? wl[lane_now()] : 0xffffffffu;
             unsigned rank = 0;
             for (unsigned j = 0; j < cnt; ++j) {
                 const unsigned o = (unsigned)__builtin_amdgcn_readlane((int)mine, (int)j);
@@ -462,17 +487,17 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
         if (lane == 0) recs[r] = out;
         return;
     }
-    med = odd ? __uint_as_float(klo) : (__uint_as_float(klo) + __uint_as_float(khi)) / 2.0f;
+    med = clip_uniform(odd ? __uint_as_float(klo) : (__uint_as_float(klo) + __uint_as_float(khi)) / 2.0f);
     // |x - med| is monotone on either side of med: its largest value is attained at one of the data extremes
     const float xmin = __uint_as_float(umn), xmax = __uint_as_float(umx);  // (xmin: of the clamped samples)
-    const float dmin_ = fabsf(xmin - med), dmax_ = fabsf(xmax - med);
-    const float dmax = fmaxf(dmin_, dmax_);
+    const float dmin_ = clip_uniform(fabsf(xmin - med)), dmax_ = clip_uniform(fabsf(xmax - med));
+    const float dmax = clip_uniform(fmaxf(dmin_, dmax_));
     const unsigned dmaxk = __float_as_uint(dmax);
     // lanes past the window: the sample whose key is the largest
     pad_last_group(__float_as_uint(dmin_ > dmax_ ? xmin : xmax));
     // (dmax == 0: every sample equals med and the select returns at once; else 0 < dmax < inf -- the extremes are
     // finite.  A dmax so small that the scale overflows (< 6e-36) is left to the exact kernel.)
-    lin_scale = dmax > 0.0f ? (float)(kHB - 1) / dmax : 1.0f;
+    lin_scale = clip_uniform(dmax > 0.0f ? (float)(kHB - 1) / dmax : 1.0f);
     if (!(lin_scale > 0.0f && lin_scale < 3.0e38f)) {
         out.flag = defer ? CLIP_NONE : CLIP_INEXACT;
         if (lane == 0) recs[r] = out;
@@ -505,13 +530,15 @@ __device__ __forceinline__ void clip_wave(const FpArgs &A, ClipRec *recs, const 
     if (lane == 0) recs[r] = out;
 }
 
-// workgroups per CU the register budget admits (512 VGPRs per SIMD lane, NPL of them are the samples)
-constexpr int clip_wgs_per_cu(int npl) { return (npl <= 80 ? 4 : (npl <= 128 ? 3 : 2)) * (4 / kClipWaves); }
+// waves per SIMD an instantiation is meant to reach: the second argument of __launch_bounds__ is the least number of
+// WAVES PER EXECUTION UNIT (SIMD) the compiler must leave room for, which bounds the registers (512 VGPRs per SIMD lane in
+// granules of 8: 96 at five waves, 128 at four, 168 at three, 256 at two; NPL of them are the samples)
+constexpr int clip_waves_per_simd(int npl) { return npl <= 80 ? 5 : (npl <= 96 ? 4 : (npl <= 128 ? 3 : 2)); }
 
 template <int NPL>
-__global__ __launch_bounds__(kClipWaves * 64, clip_wgs_per_cu(NPL)) void clip_bounds_kernel(ClipArgs C) {
+__global__ __launch_bounds__(kClipWaves * 64, clip_waves_per_simd(NPL)) void clip_bounds_kernel(ClipArgs C) {
     __shared__ __attribute__((aligned(16))) unsigned clip_lds[kClipWaves][kClipWaveWords];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wave = kClipWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t r = C.a.block_base + (int64_t)blockIdx.x * kClipWaves + wave;
     if (r >= C.a.n_reads) return;
     clip_wave<NPL>(C.a, C.rec, r, C.cap, clip_lds[wave]);
@@ -520,9 +547,9 @@ __global__ __launch_bounds__(kClipWaves * 64, clip_wgs_per_cu(NPL)) void clip_bo
 // the reads of a device-side list (the main kernel's hand-overs to the 6144-sample list kernel): one wave per entry,
 // waves past the end of the list and reads that already have their record leave at once
 template <int NPL>
-__global__ __launch_bounds__(kClipWaves * 64, clip_wgs_per_cu(NPL)) void clip_bounds_list_kernel(ClipArgs C) {
+__global__ __launch_bounds__(kClipWaves * 64, clip_waves_per_simd(NPL)) void clip_bounds_list_kernel(ClipArgs C) {
     __shared__ __attribute__((aligned(16))) unsigned clip_lds[kClipWaves][kClipWaveWords];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wave = kClipWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t k = C.a.block_base + (int64_t)blockIdx.x * kClipWaves + wave;
     if (k >= (int64_t)*C.in_count) return;
     const int64_t r = C.in_list[k];
