@@ -248,3 +248,28 @@ def test_python_front_doors_check_every_array_before_passing_it_by_address():
         kw.update(bad)
         with pytest.raises(ValueError):
             sig_proc.adc_minibatch(**kw)
+
+
+def test_float_front_doors_check_every_array_before_passing_it_by_address():
+    """the float32 counterpart: the shared check and the three blocking calls over it.  Every refusal is a ValueError raised
+    before a context is asked for -- on a machine without a device a WdxError here would mean the check came too late"""
+    from warpdemux_amd import _marshal
+
+    n, stride = 4, 32
+    sig, a, ok = np.zeros((n, stride), np.float32), np.zeros(n, np.int32), np.ones(n, np.uint8)
+    got = _marshal.minibatch(sig, a, a, ok)
+    assert got[4:] == (n, stride) and got[0] is sig and got[1].dtype == got[2].dtype == np.int32 and got[3].dtype == np.uint8
+    assert _marshal.minibatch(sig.astype(np.float64)[:, ::2], list(a), a, None)[3:] == (None, n, stride // 2)
+    params = sig_proc.SegParams()
+    refine = sig_proc.RefineParams(query=np.linspace(-1.0, 1.0, 84))
+    doors = (_marshal.minibatch,
+             lambda s, a_s, a_e, su: sig_proc.fingerprint_batch(s, a_s, a_e, params, success=su),
+             lambda s, a_s, a_e, su: sig_proc.fingerprint_refine_batch(s, a_s, a_e, params, refine, success=su),
+             lambda s, a_s, a_e, su: sig_proc.demux_batch(s, a_s, a_e, params, success=su))
+    for door in doors:
+        for bad in (dict(signals=sig[0]), dict(adapter_start=a[:-1]), dict(adapter_end=np.zeros(n + 1, np.int32)),
+                    dict(success=np.ones(n - 1, np.uint8)), dict(success=np.ones((n, 2), np.uint8))):
+            kw = dict(signals=sig, adapter_start=a, adapter_end=a, success=ok)
+            kw.update(bad)
+            with pytest.raises(ValueError):
+                door(kw["signals"], kw["adapter_start"], kw["adapter_end"], kw["success"])

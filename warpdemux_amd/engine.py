@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib, synth
+from . import _lib, _marshal, synth
 from .sig_proc import SegParams
 
 
@@ -65,8 +65,7 @@ class DemuxEngine:
         if self.params.barcode_num_events != self.K:
             raise ValueError(
                 f"barcode_num_events ({self.params.barcode_num_events}) must equal the reference length ({self.K})")
-        _lib.check(self.L.wdx_set_refs(self.ctx.handle, _lib.ptr(refs), self.nY, self.K,
-                                       int(window) if window else 0, float(penalty) if penalty else 0.0))
+        _marshal.set_refs(self.ctx, refs, window, penalty)
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
@@ -185,14 +184,13 @@ class DemuxEngine:
             self._work = self.torch.empty(need, dtype=self.torch.uint8, device=self.tdev)
         return self._work
 
-    def _set_model(self, model, kind, setter):
-        """Upload ``model`` through ``setter`` and record it as the owner of the context's ``kind`` slot."""
-        if model._X.shape != (self.nY, self.K):
+    def _set_model(self, model, kind):
+        """Upload ``model`` and record it as the owner of the context's ``kind`` slot."""
+        if kind != "boost" and model._X.shape != (self.nY, self.K):
             raise ValueError(f"the {kind.upper()}'s training set must be the engine's reference set")
         setattr(self, f"_{kind}_model", model)   # keeps the host arrays alive during the upload
-        m = model.to_c()
         setattr(self.ctx, f"_{kind}_owner", None)
-        _lib.check(setter(self.ctx.handle, C.byref(m)))
+        _marshal.set_model(self.ctx, model)
         setattr(self.ctx, f"_{kind}_owner", model)
 
     def _tail_predict(self, entry, k, dist, *extra):
@@ -227,7 +225,7 @@ class DemuxEngine:
 
     def set_svm(self, model):
         """``model``: a warpdemux_amd.models.DTW_SVM whose ``_X`` is the resident reference set."""
-        self._set_model(model, "svm", self.L.wdx_svm_set_model)
+        self._set_model(model, "svm")
         self.n_classes = model.n_classes
 
     def svm_predict(self, dist):
@@ -245,7 +243,7 @@ class DemuxEngine:
 
     def set_mlp(self, model):
         """``model``: a warpdemux_amd.models.DTW_MLP whose ``_X`` is the resident reference set."""
-        self._set_model(model, "mlp", self.L.wdx_mlp_set_model)
+        self._set_model(model, "mlp")
         self.mlp_classes = model.k
 
     def mlp_predict(self, dist, n_nonfinite=None):
@@ -263,11 +261,7 @@ class DemuxEngine:
     def set_boost(self, model):
         """``model``: a warpdemux_amd.models.Fpt_Boost; its features are the fingerprint's K columns.  Needs no reference set:
         the engine's own stays as it is."""
-        self._boost_model = model   # keeps the host arrays alive during the upload
-        m = model.to_c()
-        self.ctx._boost_owner = None
-        _lib.check(self.L.wdx_boost_set_model(self.ctx.handle, C.byref(m)))
-        self.ctx._boost_owner = model
+        self._set_model(model, "boost")
         self.boost_classes, self.boost_dim, self.boost_features = model.k, model.dim, model.n_features
 
     def boost_predict(self, fpt, status=None, want_raw=False):

@@ -44,8 +44,8 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
-from .sig_proc import DemuxBatch, FingerprintBatch, RefineParams, SegParams
+from . import _lib, _marshal
+from .sig_proc import DemuxBatch, FingerprintBatch, RefineParams, SegParams, fingerprints
 
 MAX_SLOTS = 32      # ring slots (WDX_FEEDER_MAX_RING_SLOTS); the feeder keeps at most 8 of them in flight on the device
 
@@ -58,12 +58,9 @@ def _serve(shm_name: str, refs, window, penalty, model, device: int, ready):
         L = _lib.load()
         ctx = _lib.Context(device)
         if refs.shape[0]:   # (a fingerprint-only refine ring has none)
-            _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(refs), refs.shape[0], refs.shape[1], int(window) if window else 0,
-                                      float(penalty) if penalty else 0.0))
+            _marshal.set_refs(ctx, refs, window, penalty)
         if model is not None:
-            m = model.to_c()
-            set_model = L.wdx_boost_set_model if isinstance(m, _lib.BoostModelC) else L.wdx_svm_set_model
-            _lib.check(set_model(ctx.handle, C.byref(m)))
+            _marshal.set_model(ctx, model)
         base = C.addressof(C.c_char.from_buffer(shm.buf))
         # (wdx_feeder_serve announces itself in the ring -- server_pid + heartbeat -- once the ring is page-locked; the
         # parent polls wdx_feeder_alive after this event)
@@ -110,34 +107,14 @@ class Feeder:
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, max_reads: int = 1000,
                  stride: int = 10000, n_slots: int = 16, device: int = 0, start_timeout: float = 120.0, model=None,
                  adc: bool = False, refine: Optional[RefineParams] = None):
-        self.boost = model is not None and not hasattr(model, "_X")   # an Fpt_Boost: no references of its own
-        if model is not None and not self.boost:
-            if refs is not None:
-                raise ValueError("pass either refs or model (whose _X are the references)")
-            refs, window, penalty = model._X, model.window, model.penalty
-        if refs is None:
-            if refine is None and not self.boost:
-                raise ValueError("refs or model is required")
-            k0 = int(refine.barcode_keep_events) if refine is not None else (
-                int(params.barcode_num_events) if params is not None else int(model.n_features))
-            refs = np.zeros((0, k0), dtype=np.float64)
-        refs = np.ascontiguousarray(refs, dtype=np.float64)
-        if refs.ndim != 2:
-            raise ValueError("refs must be (nY, L)")
+        d = _marshal.deployment(refs, window, penalty, params, model, refine, who="Feeder", models=("DTW_SVM", "Fpt_Boost"),
+                                bare_refine=True, refine_dtw=True, nothing_to_serve="refs or model is required")
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
-        self.refine = refine
-        K = int(refine.barcode_keep_events) if refine is not None else int(refs.shape[1])
-        self.params = params or SegParams(barcode_num_events=K)
-        if K != refs.shape[1] or (refine is None and self.params.barcode_num_events != K):
-            raise ValueError("barcode_num_events must equal the reference length")
-        if self.boost and K != int(model.n_features):
-            raise ValueError(f"the fingerprints have {K} events but the boost model takes {int(model.n_features)} features")
-        self.model = model
-        self.n_classes = (int(model.k) if self.boost else int(model.n_classes)) if model is not None else 0
+        self.boost = d.kind == _lib.LIVE_TAIL_BOOST     # an Fpt_Boost: no references of its own
+        self.refine, self.model, self.params, self.nY, self.K, self.n_classes = refine, model, d.params, d.nY, d.K, d.n_classes
         self._tail = _lib.WANT_BOOST if self.boost else _lib.WANT_SVM
         self.label_mapper = dict(model.label_mapper) if model is not None else None
-        self.nY, self.K = (int(v) for v in refs.shape)
         self.max_reads, self.stride, self.n_slots = int(max_reads), int(stride), int(n_slots)
         self.L = _lib.load()
         self.adc = bool(adc)
@@ -164,7 +141,7 @@ class Feeder:
         self._shm, self._owner, self._base = shm, os.getpid(), base
         ctx = mp.get_context("fork")
         ready = ctx.Event()
-        self._proc = ctx.Process(target=_serve, args=(self._shm.name, refs, window, penalty, model, int(device), ready),
+        self._proc = ctx.Process(target=_serve, args=(self._shm.name, d.refs, d.window, d.penalty, model, int(device), ready),
                                  daemon=True)
         self._proc.start()
         import time
@@ -179,21 +156,10 @@ class Feeder:
 
     # ---- one minibatch ------------------------------------------------------------------------------------------------
     def _run(self, signals, adapter_start, adapter_end, success, want: int):
-        sig = np.asarray(signals)
-        if sig.ndim != 2:
-            raise ValueError("signals must be a 2-D (n_reads, stride) array")
-        sig = np.ascontiguousarray(sig, dtype=np.float32)
-        n, stride = sig.shape
-        a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-        a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-        if a_s.shape != (n,) or a_e.shape != (n,):
-            raise ValueError("adapter_start/adapter_end must have one entry per read")
-        ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
-        if want & (_lib.WANT_SVM | _lib.WANT_BOOST) and self.model is None:
-            raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
+        sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
         out = self._outputs(n, want)
         job = _lib.FeederJobC(_lib.addr(sig), n, stride, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok), int(want), 0,
-                              *[_lib.addr(out[k]) for k in ("status", "call", "dist", "fpt", "dwell", "stats", "prob", "pred", "conf")])
+                              *_marshal.out_addrs(out))
         if want & _lib.WANT_REFINE_IDX:
             _lib.check(self.L.wdx_feeder_run_refine(C.c_void_p(self._base), C.byref(job), None, _lib.ptr(out["refine_idx"])))
         else:
@@ -201,18 +167,9 @@ class Feeder:
         return out
 
     def _outputs(self, n: int, want: int) -> dict:
-        return {
-            "status": np.empty(n, dtype=np.int32),
-            "call": np.empty(n, dtype=np.int32),
-            "dist": np.empty((n, self.nY), dtype=np.float32) if want & _lib.WANT_DIST else None,
-            "fpt": np.empty((n, self.K), dtype=np.float64) if want & _lib.WANT_FPT else None,
-            "dwell": np.empty((n, self.K), dtype=np.int64) if want & _lib.WANT_DWELL else None,
-            "stats": np.empty((n, 6), dtype=np.float64) if want & _lib.WANT_STATS else None,
-            "prob": np.empty((n, self.n_classes), dtype=np.float64) if want & (_lib.WANT_SVM | _lib.WANT_BOOST) else None,
-            "pred": np.empty(n, dtype=np.int32) if want & (_lib.WANT_SVM | _lib.WANT_BOOST) else None,
-            "conf": np.empty(n, dtype=np.float64) if want & (_lib.WANT_SVM | _lib.WANT_BOOST) else None,
-            "refine_idx": np.empty((n, 3), dtype=np.int32) if want & _lib.WANT_REFINE_IDX else None,
-        }
+        if want & _marshal.WANT_TAIL and self.model is None:
+            raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
+        return _marshal.outputs(n, self.K, self.nY, self.n_classes, want)
 
     def _fpt_want(self) -> int:
         """the ReadResult arrays of a minibatch; on a refine feeder with refine_idx.  A plain minibatch without references
@@ -229,27 +186,13 @@ class Feeder:
 
     def _run_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success, want: int):
         """One int16 minibatch through wdx_feeder_run_adc.  Shapes and dtypes of EVERY array, `success` included, are
-        checked before anything is passed by address; `adc` must be C-contiguous int16 (it is never copied here)."""
-        a = adc if isinstance(adc, np.ndarray) else np.asarray(adc)
-        if a.ndim != 2 or a.dtype != np.int16 or not a.flags.c_contiguous:
-            raise ValueError("adc must be a C-contiguous 2-D (n_reads, stride) int16 array")
-        n, stride = a.shape
-        r_len = np.ascontiguousarray(row_len, dtype=np.int32)
-        off = np.ascontiguousarray(offset, dtype=np.float32)
-        sc = np.ascontiguousarray(scale, dtype=np.float32)
-        a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-        a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-        ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
-        for name, v in (("row_len", r_len), ("offset", off), ("scale", sc), ("adapter_start", a_s), ("adapter_end", a_e),
-                        ("success", ok)):
-            if v is not None and v.shape != (n,):
-                raise ValueError(f"{name} must have one entry per read")
-        if want & (_lib.WANT_SVM | _lib.WANT_BOOST) and self.model is None:
-            raise ValueError("this feeder was created without a model (Feeder(model=DTW_SVM...))")
+        checked before anything is passed by address; `adc` must be a C-contiguous 2-D int16 array (it is never copied
+        here; a ring's slots hold rows, not packed reads)."""
+        a, n, stride, r_len, off, sc, _, _, a_s, a_e, ok = _marshal.adc_rows(adc, row_len, offset, scale, adapter_start,
+                                                                             adapter_end, success)
         out = self._outputs(n, want)
         job = _lib.FeederJobAdcC(_lib.addr(a), n, stride, _lib.addr(r_len), _lib.addr(off), _lib.addr(sc), _lib.addr(a_s),
-                                 _lib.addr(a_e), _lib.addr(ok), int(want), 0,
-                                 *[_lib.addr(out[k]) for k in ("status", "call", "dist", "fpt", "dwell", "stats", "prob", "pred", "conf")])
+                                 _lib.addr(a_e), _lib.addr(ok), int(want), 0, *_marshal.out_addrs(out))
         if want & _lib.WANT_REFINE_IDX:
             _lib.check(self.L.wdx_feeder_run_refine(C.c_void_p(self._base), None, C.byref(job), _lib.ptr(out["refine_idx"])))
         else:
@@ -266,7 +209,7 @@ class Feeder:
     def fingerprint_batch_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None) -> FingerprintBatch:
         """`fingerprint_batch` for an int16 ADC minibatch (a ``Feeder(adc=True)``)."""
         o = self._run_adc(adc, row_len, offset, scale, adapter_start, adapter_end, success, self._fpt_want())
-        return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
+        return fingerprints(o)
 
     def detect_and_predict_adc(self, adc, row_len, offset, scale, adapter_start, adapter_end, success=None,
                                return_df: bool = False):
@@ -287,7 +230,7 @@ class Feeder:
         what `sig_proc.read_results_from_batch` turns into the reference's ReadResult records.  On a refine feeder:
         `sig_proc.fingerprint_refine_batch`'s result, ``refine_idx`` included."""
         o = self._run(signals, adapter_start, adapter_end, success, self._fpt_want())
-        return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
+        return fingerprints(o)
 
     def detect_and_predict(self, signals, adapter_start, adapter_end, success=None, return_df: bool = False):
         """The two halves of the reference worker's minibatch (file_proc.py:418-450) from one pass over the rows:
@@ -298,7 +241,7 @@ class Feeder:
         return self._fpt_and_predictions(o, return_df)
 
     def _fpt_and_predictions(self, o: dict, return_df: bool):
-        fb = FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
+        fb = fingerprints(o)
         okr = o["status"] == 0
         y_pred, y_prob, conf = o["pred"][okr].astype(np.int64), o["prob"][okr], o["conf"][okr]
         if return_df:

@@ -29,7 +29,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _marshal
 from .sig_proc import RefineParams, SegParams
 
 
@@ -47,23 +47,9 @@ class TickResult:
     refine_idx: Optional[np.ndarray] = None   # (n, 3) int32 seg_cons_query_start / _end, sig_barcode_start (want_refine_idx)
 
 
-def _model_kind(model) -> int:
-    from . import models
-
-    if model is None:
-        return _lib.LIVE_TAIL_NONE
-    if isinstance(model, models.DTW_SVM):
-        return _lib.LIVE_TAIL_SVM
-    if isinstance(model, models.DTW_MLP):
-        return _lib.LIVE_TAIL_MLP
-    if isinstance(model, models.Fpt_Boost):
-        return _lib.LIVE_TAIL_BOOST
-    raise ValueError(f"LiveDemux serves models.DTW_SVM, DTW_MLP and Fpt_Boost, not {type(model).__name__}")
-
-
 _DT = {np.float32: np.dtype(np.float32), np.int16: np.dtype(np.int16)}
-_SETTER = {_lib.LIVE_TAIL_SVM: "wdx_svm_set_model", _lib.LIVE_TAIL_MLP: "wdx_mlp_set_model",
-           _lib.LIVE_TAIL_BOOST: "wdx_boost_set_model"}
+# every array a tick can bring back: allocated once per capacity, narrowed per tick (`_marshal.out_addrs`)
+_ALL = _lib.WANT_FPT | _lib.WANT_DIST | _lib.WANT_DWELL | _lib.WANT_STATS | _lib.WANT_REFINE_IDX
 
 
 class LiveDemux:
@@ -87,49 +73,21 @@ class LiveDemux:
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, *, model=None,
                  refine: Optional[RefineParams] = None, adc: bool = False, device: int = 0, max_reads: int = 512,
                  max_samples: int = 10000):
-        self.tail = _model_kind(model)
-        self.model = model
-        if self.tail in (_lib.LIVE_TAIL_SVM, _lib.LIVE_TAIL_MLP):
-            refs, window, penalty = model._X, model.window, model.penalty
-        if refine is not None:
-            if not isinstance(refine, RefineParams) or refine.query is None or np.size(refine.query) == 0:
-                raise ValueError("refine must be a sig_proc.RefineParams with a consensus query")
-            if self.tail in (_lib.LIVE_TAIL_SVM, _lib.LIVE_TAIL_MLP):
-                raise ValueError("consensus refinement is served without a model or with an Fpt_Boost, not with a "
-                                 f"{type(model).__name__}")
-        if refs is None:
-            if self.tail != _lib.LIVE_TAIL_BOOST:
-                raise ValueError("refs may only be None with an Fpt_Boost model (its tail needs no references)")
-            self.nY, ref_len = 0, None
-        else:
-            refs = np.ascontiguousarray(refs, dtype=np.float64)
-            if refs.ndim != 2:
-                raise ValueError("refs must be (nY, K)")
-            self.nY, ref_len = refs.shape
-        if refine is not None:
-            self.K, k_name = int(refine.barcode_keep_events), "refine.barcode_keep_events"
-            self.params = params or SegParams()
-        else:
-            default_k = ref_len if ref_len is not None else model.n_features
-            self.params = params or SegParams(barcode_num_events=default_k)
-            self.K, k_name = int(self.params.barcode_num_events), "barcode_num_events"
-        if ref_len is not None and self.K != ref_len:
-            raise ValueError(f"{k_name} ({self.K}) must equal the reference length ({ref_len})")
-        if self.tail == _lib.LIVE_TAIL_BOOST and self.K != model.n_features:
-            raise ValueError(f"{k_name} ({self.K}) must equal the boost model's n_features ({model.n_features})")
-        self.refine = refine
+        d = _marshal.deployment(
+            refs, window, penalty, params, model, refine, who="LiveDemux", models=("DTW_SVM", "DTW_MLP", "Fpt_Boost"),
+            bare_refine=False, refine_dtw=False,
+            nothing_to_serve="refs may only be None with an Fpt_Boost model (its tail needs no references)")
+        self.tail, self.model, self.refine, self.params, self.nY, self.K, self.k = (d.kind, model, refine, d.params, d.nY, d.K,
+                                                                                   d.n_classes)
         self._pc = self.params.to_c()
         self._rc = None if refine is None else refine.to_c()
-        self.k = 0 if model is None else (model.n_classes if self.tail == _lib.LIVE_TAIL_SVM else model.k)
 
         self.L = _lib.load()
         self.ctx = _lib.Context(device)      # this object's own context = own stream + staging buffers
-        if refs is not None:
-            _lib.check(self.L.wdx_set_refs(self.ctx.handle, _lib.ptr(refs), self.nY, ref_len,
-                                           int(window) if window else 0, float(penalty) if penalty else 0.0))
+        if self.nY:
+            _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:
-            self._m = model.to_c()
-            _lib.check(getattr(self.L, _SETTER[self.tail])(self.ctx.handle, C.byref(self._m)))
+            _marshal.set_model(self.ctx, model)
         self._cap = 0
         self._reserve(max_reads)
         # first tick at full size now: staging buffers and workspaces are allocated before the run starts
@@ -148,16 +106,7 @@ class LiveDemux:
         self._cap = n
         self._rows = np.zeros(n, dtype=np.uintp)    # the tick's pointer table
         self._len = np.empty(n, dtype=np.int32)
-        self._status = np.empty(n, dtype=np.int32)
-        self._call = np.empty(n, dtype=np.int32)
-        self._dist = np.empty((n, self.nY), dtype=np.float32)
-        self._fpt = np.empty((n, self.K), dtype=np.float64)
-        self._dwell = np.empty((n, self.K), dtype=np.int64)
-        self._stats = np.empty((n, 6), dtype=np.float64)
-        self._ridx = np.empty((n, 3), dtype=np.int32)
-        self._prob = np.empty((n, max(self.k, 1)), dtype=np.float64)
-        self._pred = np.empty(n, dtype=np.int32)
-        self._conf = np.empty(n, dtype=np.float64)
+        self._out = _marshal.outputs(n, self.K, self.nY, self.k, _ALL | (_marshal.WANT_TAIL if self.k else 0))
 
     def tick(self, rows: Sequence[np.ndarray], adapter_start, adapter_end, success=None, want_dist=True,
              want_fpt=False, want_dwell=False, want_stats=False, want_refine_idx=False) -> TickResult:
@@ -175,10 +124,8 @@ class LiveDemux:
         ``fingerprint_batch_adc`` / ``demux_batch_adc`` on a minibatch of the same reads.  (So a window that runs past its
         read's end reads NaN here, as on a minibatch; :meth:`tick`, whose rows end with the read, cuts the window there.)
         Available on any LiveDemux, next to :meth:`tick`."""
-        off = np.ascontiguousarray(offset, dtype=np.float32)
-        sc = np.ascontiguousarray(scale, dtype=np.float32)
-        if off.shape != (len(adc_rows),) or sc.shape != (len(adc_rows),):
-            raise ValueError("offset/scale must have one entry per read")
+        n = len(adc_rows)
+        off, sc = _marshal.per_read(n, np.float32, "offset/scale", offset), _marshal.per_read(n, np.float32, "offset/scale", scale)
         return self._tick(adc_rows, np.int16, off, sc, adapter_start, adapter_end, success, want_dist, want_fpt, want_dwell,
                           want_stats, want_refine_idx)
 
@@ -204,33 +151,25 @@ class LiveDemux:
             lens.append(r.size)
         self._rows[:n] = ptrs
         self._len[:n] = lens
-        a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-        a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-        if a_s.shape != (n,) or a_e.shape != (n,):
-            raise ValueError("adapter_start/adapter_end must have one entry per read")
-        ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
-        if ok is not None and ok.shape != (n,):
-            raise ValueError("success must have one entry per read")
+        a_s, a_e, ok = _marshal.windows(n, adapter_start, adapter_end, success)
         if want_refine_idx and self.refine is None:
             raise ValueError("want_refine_idx needs a LiveDemux built with refine")
-        tail = self.tail != _lib.LIVE_TAIL_NONE
+        tail = _marshal.WANT_TAIL if self.tail != _lib.LIVE_TAIL_NONE else 0
         want_dist = bool(want_dist) and self.nY > 0
         rows_p = _lib.addr(self._rows)
         desc = _lib.LiveInC(None if adc else rows_p, rows_p if adc else None, _lib.addr(off), _lib.addr(sc), _lib.addr(self._len),
                             n, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok), self.tail, 0)
         bad = C.c_int64(0)
+        o = self._out
 
         def run(with_fpt):
             want = ((_lib.WANT_FPT if with_fpt else 0) | (_lib.WANT_DIST if want_dist else 0)
                     | (_lib.WANT_DWELL if want_dwell else 0) | (_lib.WANT_STATS if want_stats else 0)
                     | (_lib.WANT_REFINE_IDX if want_refine_idx else 0))
-            out = _lib.MinibatchOutC(_lib.addr(self._status), _lib.addr(self._call), _lib.addr(self._dist) if want_dist else None,
-                                     _lib.addr(self._fpt) if with_fpt else None, _lib.addr(self._dwell) if want_dwell else None,
-                                     _lib.addr(self._stats) if want_stats else None, _lib.addr(self._prob) if tail else None,
-                                     _lib.addr(self._pred) if tail else None, _lib.addr(self._conf) if tail else None)
+            out = _marshal.out_c(o, want | tail)     # (the tail is named in `desc`, not in the bits the library reads)
             _lib.check(self.L.wdx_live_tick_ex(self.ctx.handle, C.byref(desc), C.byref(self._pc),
                                                None if self._rc is None else C.byref(self._rc), self.nY, want, C.byref(out),
-                                               _lib.ptr(self._ridx) if want_refine_idx else None, C.byref(bad)))
+                                               _lib.ptr(o["refine_idx"]) if want_refine_idx else None, C.byref(bad)))
 
         run(want_fpt)
         if bad.value:
@@ -238,17 +177,19 @@ class LiveDemux:
             # made from the fingerprints: the error path fetches them with a second tick, so that no good tick pays for them
             if not want_fpt:
                 run(True)
-            raise ValueError(self.model._nonfinite_message(self._fpt[:n][self._status[:n] == 0]))
+            raise ValueError(self.model._nonfinite_message(o["fpt"][:n][o["status"][:n] == 0]))
         del keep
-        status = self._status[:n].copy()
+        status = o["status"][:n].copy()
         pred = None
         if tail:
-            pred = self._pred[:n].astype(np.int64)
+            pred = o["pred"][:n].astype(np.int64)
             pred[status != 0] = -1
-        return TickResult(status, self._call[:n].copy(), self._dist[:n].copy() if want_dist else None,
-                          self._fpt[:n].copy() if want_fpt else None, self._prob[:n, :self.k].copy() if tail else None,
-                          pred, self._conf[:n].copy() if tail else None, self._dwell[:n].copy() if want_dwell else None,
-                          self._stats[:n].copy() if want_stats else None, self._ridx[:n].copy() if want_refine_idx else None)
+
+        def got(name, wanted):
+            return o[name][:n].copy() if wanted else None
+
+        return TickResult(status, got("call", True), got("dist", want_dist), got("fpt", want_fpt), got("prob", tail), pred,
+                          got("conf", tail), got("dwell", want_dwell), got("stats", want_stats), got("refine_idx", want_refine_idx))
 
     def close(self):
         self.ctx.close()

@@ -15,7 +15,7 @@ from typing import Dict, Optional, Tuple, Union
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _marshal
 
 
 def predictions_to_df(y_pred, y_prob, conf, label_mapper):
@@ -31,13 +31,22 @@ def predictions_to_df(y_pred, y_prob, conf, label_mapper):
     )
 
 
+def _own_slot(ctx, model):
+    """``model`` into its slot of ``ctx`` unless it is the one the context last received there (``model._owner_attr``); no
+    owner is recorded while the upload runs, so a refused model does not pass for the resident one."""
+    if getattr(ctx, model._owner_attr, None) is not model:
+        setattr(ctx, model._owner_attr, None)
+        _marshal.set_model(ctx, model)
+        setattr(ctx, model._owner_attr, model)
+    return ctx
+
+
 class _ResidentDTWModel:
     """What DTW_SVM and DTW_MLP share: the reference fingerprints, the DTW parameters and the label map on the host, the
-    upload to the process's context, and ``predict``'s validation.  Subclasses name their context slot (``_owner_attr``),
-    the library's setter (``_setter``) and the text of the column-mismatch error (``_column_error``)."""
+    upload to the process's context, and ``predict``'s validation.  Subclasses name their context slot (``_owner_attr``)
+    and the text of the column-mismatch error (``_column_error``)."""
 
     _owner_attr: str
-    _setter: str
 
     def _init_common(self, _X, window, penalty, block_size, label_mapper, thresholds, device):
         self._X = np.ascontiguousarray(_X, dtype=np.float64)
@@ -57,15 +66,8 @@ class _ResidentDTWModel:
         every call (the library compares a content hash and uploads only on change), the model whenever this object is
         not the one the context last received."""
         ctx = _lib.default_context(self._device)
-        L = _lib.load()
-        _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(self._X), self._X.shape[0], self._X.shape[1],
-                                  int(self.window) if self.window else 0, float(self.penalty) if self.penalty else 0.0))
-        if getattr(ctx, self._owner_attr, None) is not self:
-            setattr(ctx, self._owner_attr, None)
-            m = self.to_c()
-            _lib.check(getattr(L, self._setter)(ctx.handle, C.byref(m)))
-            setattr(ctx, self._owner_attr, self)
-        return ctx
+        _marshal.set_refs(ctx, self._X, self.window, self.penalty)
+        return _own_slot(ctx, self)
 
     def _predict_inputs(self, X, nproc, block_size, k):
         """``predict``'s prologue: (context, contiguous float64 X, y_prob (n, k), y_pred int32 (n,), conf (n,))."""
@@ -91,7 +93,7 @@ class _ResidentDTWModel:
 class DTW_SVM(_ResidentDTWModel):
     """Holds the reference fingerprints and the SVC parameters resident on one GPU context."""
 
-    _owner_attr, _setter = "_svm_owner", "wdx_svm_set_model"
+    _owner_attr = "_svm_owner"
 
     def __init__(self, _X: np.ndarray, n_support, support, dual_coef, rho, probA, probB,
                  label_mapper: Dict[int, int], thresholds: Optional[np.ndarray], window: int, penalty: float,
@@ -178,7 +180,7 @@ class DTW_MLP(_ResidentDTWModel):
     matrix never leaving HBM.  The working dtype is scikit-learn's: ``result_type(float32, coefs_[0].dtype)``.  The MLP
     slot of the context is separate from the SVM's, so a resident SVM stays as it is."""
 
-    _owner_attr, _setter = "_mlp_owner", "wdx_mlp_set_model"
+    _owner_attr = "_mlp_owner"
 
     def __init__(self, _X: np.ndarray, coefs, intercepts, activation: str, label_mapper: Dict[int, int],
                  thresholds: Optional[np.ndarray], window: int, penalty: float, scalers=(), n_classes: Optional[int] = None,
@@ -464,13 +466,7 @@ class Fpt_Boost:
         )
 
     def _ensure_resident(self):
-        ctx = _lib.default_context(self._device)
-        if getattr(ctx, self._owner_attr, None) is not self:
-            setattr(ctx, self._owner_attr, None)
-            m = self.to_c()
-            _lib.check(_lib.load().wdx_boost_set_model(ctx.handle, C.byref(m)))
-            setattr(ctx, self._owner_attr, self)
-        return ctx
+        return _own_slot(_lib.default_context(self._device), self)
 
     def predict_raw(self, X: np.ndarray):
         """(raw float64 (n, dim), y_prob float64 (n, k), y_pred int64 (n,), conf float64 (n,)) of ``X`` (n, n_features)."""

@@ -32,8 +32,8 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
-from .sig_proc import DemuxBatch, FingerprintBatch, RefineParams, SegParams, adc_minibatch
+from . import _lib, _marshal
+from .sig_proc import DemuxBatch, FingerprintBatch, RefineParams, SegParams, adc_minibatch, fingerprints
 
 
 def pinned_empty(shape, dtype=np.float32, device: Optional[int] = None) -> np.ndarray:
@@ -120,66 +120,48 @@ class MinibatchPipeline:
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
         self.N_SLOTS = int(n_slots)
-        self.refine = refine
-        self.model = model
-        if refs is None:
-            if refine is None and model is None:
-                raise ValueError("refs is required (only a refine pipeline or one with a boost model can do without)")
-            k0 = int(refine.barcode_keep_events) if refine is not None else (
-                int(params.barcode_num_events) if params is not None else int(model.n_features))
-            refs = np.zeros((0, k0), dtype=np.float64)
-        refs = np.ascontiguousarray(refs, dtype=np.float64)
-        if refs.ndim != 2:
-            raise ValueError("refs must be (nY, L)")
-        K = int(refine.barcode_keep_events) if refine is not None else int(refs.shape[1])
-        self.params = params or SegParams(barcode_num_events=K)
-        if K != refs.shape[1] or (refine is None and self.params.barcode_num_events != K):
-            raise ValueError("barcode_num_events must equal the reference length")
-        if model is not None and K != int(model.n_features):
-            raise ValueError(f"the fingerprints have {K} events but the boost model takes {int(model.n_features)} features")
-        self.nY, self.K = (int(v) for v in refs.shape)
+        d = _marshal.deployment(
+            refs, window, penalty, params, model, refine, who="MinibatchPipeline", models=("Fpt_Boost",), bare_refine=True,
+            refine_dtw=True,
+            nothing_to_serve="refs is required (only a refine pipeline or one with a boost model can do without)")
+        self.refine, self.model, self.params, self.nY, self.K, self._n_classes = refine, model, d.params, d.nY, d.K, d.n_classes
         self.L = _lib.load()
         self.ctx = _lib.Context(device)
         if self.nY:
-            _lib.check(self.L.wdx_set_refs(self.ctx.handle, _lib.ptr(refs), self.nY, self.K,
-                                           int(window) if window else 0, float(penalty) if penalty else 0.0))
+            _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:
-            m = model.to_c()
-            _lib.check(self.L.wdx_boost_set_model(self.ctx.handle, C.byref(m)))
+            _marshal.set_model(self.ctx, model)
         self._pc = self.params.to_c()
         self._rc = refine.to_c() if refine is not None else None
-        self._held = [None] * self.N_SLOTS     # the submitted arrays must outlive the copy-in
+        # a refine minibatch, and one of a pipeline with a boost model, always brings the ReadResult arrays back -- with a
+        # model, its prediction too (WDX_WANT_BOOST) -- through the wdx_minibatch_in / _out entry points
+        self._all = 0
+        if refine is not None or model is not None:
+            self._all = (_lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | (_lib.WANT_REFINE_IDX if refine is not None else 0) |
+                         (_lib.WANT_BOOST if model is not None else 0))
+        self._held = [None] * self.N_SLOTS     # (the submitted arrays, which must outlive the copy-in; n_reads; want)
+
+    def _want(self, slot: int, want_dist, want_fpt) -> int:
+        if not 0 <= int(slot) < self.N_SLOTS:
+            raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
+        if self._all:
+            return self._all | (_lib.WANT_DIST if want_dist and self.nY > 0 else 0)
+        return (_lib.WANT_FPT if want_fpt else 0) | (_lib.WANT_DIST if want_dist else 0)
 
     def submit(self, slot: int, signals, adapter_start, adapter_end, success=None, want_dist=True, want_fpt=False):
         """Enqueue one minibatch on `slot` (0 or 1) and return.  `signals` must not be modified before `wait(slot)`."""
-        sig = np.asarray(signals)
-        if sig.ndim != 2:
-            raise ValueError("signals must be a 2-D (n_reads, stride) array")
-        sig = np.ascontiguousarray(sig, dtype=np.float32)
-        n, stride = sig.shape
-        a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-        a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-        if a_s.shape != (n,) or a_e.shape != (n,):
-            raise ValueError("adapter_start/adapter_end must have one entry per read")
-        ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
-        if not 0 <= int(slot) < self.N_SLOTS:
-            raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
-        if self.refine is not None or self.model is not None:
+        sig, a_s, a_e, ok, n, stride = kept = _marshal.minibatch(signals, adapter_start, adapter_end, success)
+        want = self._want(slot, want_dist, want_fpt)
+        if self._all:
             desc = _lib.MinibatchInC(_lib.addr(sig), n, stride, None, None, _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok))
-            want_dist = bool(want_dist) and self.nY > 0
-            self._submit_all(slot, desc, None, want_dist)
-            self._held[slot] = (sig, a_s, a_e, ok, n, want_dist, True)
-            return
-        _lib.check(self.L.wdx_demux_submit(self.ctx.handle, int(slot), _lib.ptr(sig), n, stride, _lib.ptr(a_s),
-                                           _lib.ptr(a_e), _lib.ptr(ok), C.byref(self._pc), self.nY, int(want_fpt),
-                                           int(want_dist)))
-        self._held[slot] = (sig, a_s, a_e, ok, n, bool(want_dist), bool(want_fpt))
+            self._submit_all(slot, desc, None, want)
+        else:
+            _lib.check(self.L.wdx_demux_submit(self.ctx.handle, int(slot), _lib.ptr(sig), n, stride, _lib.ptr(a_s),
+                                               _lib.ptr(a_e), _lib.ptr(ok), C.byref(self._pc), self.nY, int(bool(want_fpt)),
+                                               int(bool(want_dist))))
+        self._held[slot] = (kept, n, want)
 
-    def _submit_all(self, slot: int, desc, desc_adc, want_dist: bool):
-        """a refine minibatch, and one of a pipeline with a boost model, always brings the ReadResult arrays back -- with a
-        model, its prediction too (WDX_WANT_BOOST)"""
-        want = (_lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS | (_lib.WANT_DIST if want_dist else 0) |
-                (_lib.WANT_REFINE_IDX if self.refine is not None else 0) | (_lib.WANT_BOOST if self.model is not None else 0))
+    def _submit_all(self, slot: int, desc, desc_adc, want: int):
         f = None if desc is None else C.byref(desc)
         a = None if desc_adc is None else C.byref(desc_adc)
         if self.refine is not None:
@@ -199,17 +181,10 @@ class MinibatchPipeline:
         formula).  With ``row_off`` the rows are packed by the caller (`sig_proc.adc_minibatch`).  `wait(slot)` returns
         what `submit` + `wait` return on the calibrated rows, bit for bit.  Nothing passed here may be modified before
         `wait(slot)`."""
-        if not 0 <= int(slot) < self.N_SLOTS:
-            raise ValueError(f"slot must be in [0, {self.N_SLOTS})")
+        want = self._want(slot, want_dist, want_fpt)
         desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success, row_off, row_win)
-        if self.refine is not None or self.model is not None:
-            want_dist = bool(want_dist) and self.nY > 0
-            self._submit_all(slot, None, desc, want_dist)
-            self._held[slot] = (kept, None, None, None, n, want_dist, True)
-            return
-        want = (_lib.WANT_FPT if want_fpt else 0) | (_lib.WANT_DIST if want_dist else 0)
-        _lib.check(self.L.wdx_demux_submit_adc(self.ctx.handle, int(slot), C.byref(desc), C.byref(self._pc), self.nY, want))
-        self._held[slot] = (kept, None, None, None, n, bool(want_dist), bool(want_fpt))
+        self._submit_all(slot, None, desc, want)
+        self._held[slot] = (kept, n, want)
 
     def wait(self, slot: int):
         """`DemuxBatch` of the minibatch on `slot`; a refine pipeline returns a `RefineMinibatch`, one with a boost model a
@@ -217,41 +192,25 @@ class MinibatchPipeline:
         held = self._held[slot] if 0 <= int(slot) < self.N_SLOTS else None
         if held is None:
             raise ValueError(f"nothing was submitted on slot {slot}")
-        n, want_dist, want_fpt = held[4:]
-        if self.refine is not None or self.model is not None:
-            return self._wait_all(slot, n, want_dist)
-        dist = np.empty((n, self.nY), dtype=np.float32) if want_dist else None
-        fpt = np.empty((n, self.K), dtype=np.float64) if want_fpt else None
-        call = np.empty(n, dtype=np.int32)
-        status = np.empty(n, dtype=np.int32)
-        rc = self.L.wdx_demux_wait(self.ctx.handle, int(slot), _lib.ptr(fpt), _lib.ptr(dist), _lib.ptr(call),
-                                   _lib.ptr(status))
+        _, n, want = held
+        o = _marshal.outputs(n, self.K, self.nY, self._n_classes, want)
+        if self._all:
+            out = _marshal.out_c(o)
+            rc = self.L.wdx_demux_wait_refine(self.ctx.handle, int(slot), C.byref(out), _lib.ptr(o["refine_idx"]))
+        else:
+            rc = self.L.wdx_demux_wait(self.ctx.handle, int(slot), _lib.ptr(o["fpt"]), _lib.ptr(o["dist"]), _lib.ptr(o["call"]),
+                                       _lib.ptr(o["status"]))
         # WDX_ERR_INVALID (an argument error, or another thread already waiting on this slot) leaves the minibatch IN
         # FLIGHT in the slot (wdx.h): the copy-in may still be reading the arrays, so they stay referenced and the
         # caller can wait again.  Success and a HIP error both free the slot on the C side.
         if rc != _lib.WDX_ERR_INVALID:
             self._held[slot] = None
         _lib.check(rc)
-        return DemuxBatch(status, call, dist, fpt)
-
-    def _wait_all(self, slot: int, n: int, want_dist: bool):
-        fb = FingerprintBatch(np.empty((n, self.K), dtype=np.float64), np.empty((n, self.K), dtype=np.int64),
-                              np.empty((n, 6), dtype=np.float64), np.empty(n, dtype=np.int32),
-                              np.empty((n, 3), dtype=np.int32) if self.refine is not None else None)
-        call = np.empty(n, dtype=np.int32)
-        dist = np.empty((n, self.nY), dtype=np.float32) if want_dist else None
-        prob = pred = conf = None
         if self.model is not None:
-            prob, pred, conf = np.empty((n, int(self.model.k))), np.empty(n, dtype=np.int32), np.empty(n)
-        out = _lib.MinibatchOutC(_lib.addr(fb.status), _lib.addr(call), _lib.addr(dist), _lib.addr(fb.fpt), _lib.addr(fb.dwell),
-                                 _lib.addr(fb.stats), _lib.addr(prob), _lib.addr(pred), _lib.addr(conf))
-        rc = self.L.wdx_demux_wait_refine(self.ctx.handle, int(slot), C.byref(out), _lib.ptr(fb.refine_idx))
-        if rc != _lib.WDX_ERR_INVALID:   # (as in `wait`: an argument error leaves the minibatch in flight)
-            self._held[slot] = None
-        _lib.check(rc)
-        if self.model is not None:
-            return BoostMinibatch(fb, call, dist, prob, pred.astype(np.int64), conf)
-        return RefineMinibatch(fb, call, dist)
+            return BoostMinibatch(fingerprints(o), o["call"], o["dist"], o["prob"], o["pred"].astype(np.int64), o["conf"])
+        if self.refine is not None:
+            return RefineMinibatch(fingerprints(o), o["call"], o["dist"])
+        return DemuxBatch(o["status"], o["call"], o["dist"], o["fpt"])
 
     def run(self, minibatches):
         """Drive an iterable of (signals, adapter_start, adapter_end[, success]) through both slots; yields one

@@ -18,7 +18,7 @@ from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _marshal
 
 MAX_ADAPTER_SAMPLES = 16384   # WDX_MAX_ADAPTER_SAMPLES (include/wdx.h)
 
@@ -218,33 +218,24 @@ class FingerprintBatch:
         return self.status == 0
 
 
+_FPT_WANT = _lib.WANT_FPT | _lib.WANT_DWELL | _lib.WANT_STATS    # the ReadResult arrays of a minibatch
+
+
+def fingerprints(o: dict) -> FingerprintBatch:
+    """`FingerprintBatch` of a minibatch's result arrays (`_marshal.outputs`)"""
+    return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
+
+
 def fingerprint_batch(signals, adapter_start, adapter_end, params: SegParams, success=None, device=None) -> FingerprintBatch:
     """Fingerprint a (n_reads, stride) float32 minibatch (file_proc.py:244-260 layout, NaN tail)."""
-    sig = np.asarray(signals)
-    if sig.ndim != 2:
-        raise ValueError("signals must be a 2-D (n_reads, stride) array")
-    sig = np.ascontiguousarray(sig, dtype=np.float32)
-    n, stride = sig.shape
-    a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-    a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-    if a_s.shape != (n,) or a_e.shape != (n,):
-        raise ValueError("adapter_start/adapter_end must have one entry per read")
-    ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
+    sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
     pc = params.to_c()
-    K = params.barcode_num_events
-    fpt = np.empty((n, K), dtype=np.float64)
-    dwell = np.empty((n, K), dtype=np.int64)
-    stats = np.empty((n, 6), dtype=np.float64)
-    status = np.empty(n, dtype=np.int32)
+    o = _marshal.outputs(n, params.barcode_num_events, 0, 0, _FPT_WANT)
     ctx = _lib.default_context(device)
-    L = _lib.load()
-    _lib.check(
-        L.wdx_fingerprint_batch(
-            ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok),
-            C.byref(pc), _lib.ptr(fpt), _lib.ptr(dwell), _lib.ptr(stats), _lib.ptr(status),
-        )
-    )
-    return FingerprintBatch(fpt, dwell, stats, status)
+    _lib.check(_lib.load().wdx_fingerprint_batch(
+        ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc), _lib.ptr(o["fpt"]),
+        _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["status"])))
+    return fingerprints(o)
 
 
 def calibrate_adc(adc, row_len, offset, scale, stride=None) -> np.ndarray:
@@ -286,39 +277,9 @@ def adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, succe
     ``row_off`` (int64[n + 1], multiples of 8): `adc` is 1-D and holds packed rows, row r = its ``row_len[r]`` samples at
     ``adc[row_off[r]:]``, adapter bounds relative to the row; ``row_win`` (optional) = samples of the float32 row it
     stands for, the surplus over ``row_len`` being NaN tail."""
-    a = adc if isinstance(adc, np.ndarray) else np.asarray(adc)
-    if a.dtype != np.int16 or not a.flags.c_contiguous:
-        raise ValueError("adc must be a C-contiguous int16 array (it is passed by address, never converted)")
-    r_len = np.ascontiguousarray(row_len, dtype=np.int32)
-    n = int(r_len.shape[0]) if r_len.ndim == 1 else -1
-    if row_off is None:
-        if a.ndim != 2 or a.shape[0] != n:
-            raise ValueError("adc must be a 2-D (n_reads, stride) array with one row_len per row")
-        stride = int(a.shape[1])
-        if row_win is not None:
-            raise ValueError("row_win belongs to packed rows (row_off)")
-        r_off = r_win = None
-    else:
-        r_off = np.ascontiguousarray(row_off, dtype=np.int64)
-        if a.ndim != 1 or n < 0 or r_off.shape != (n + 1,):
-            raise ValueError("packed rows: adc must be 1-D, row_off int64[n_reads + 1]")
-        if n and (r_off[0] < 0 or r_off[-1] > a.shape[0] or (np.diff(r_off) < 0).any()):
-            raise ValueError("packed rows: row_off must ascend within adc")
-        stride = 0
-        r_win = None if row_win is None else np.ascontiguousarray(row_win, dtype=np.int32)
-        if r_win is not None and r_win.shape != (n,):
-            raise ValueError("row_win must have one entry per read")
-    off = np.ascontiguousarray(offset, dtype=np.float32)
-    sc = np.ascontiguousarray(scale, dtype=np.float32)
-    a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-    a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-    ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
-    for name, v in (("offset", off), ("scale", sc), ("adapter_start", a_s), ("adapter_end", a_e), ("success", ok)):
-        if v is not None and v.shape != (n,):
-            raise ValueError(f"{name} must have one entry per read")
-    kept = (a, r_len, off, sc, r_off, r_win, a_s, a_e, ok)
-    desc = _lib.MinibatchAdcInC(_lib.addr(a), n, stride, _lib.addr(r_len), _lib.addr(off), _lib.addr(sc), _lib.addr(r_off),
-                                _lib.addr(r_win), _lib.addr(a_s), _lib.addr(a_e), _lib.addr(ok))
+    a, n, stride, *rest = _marshal.adc_rows(adc, row_len, offset, scale, adapter_start, adapter_end, success, row_off, row_win)
+    kept = (a, *rest)     # adc, row_len, offset, scale, row_off, row_win, a_start, a_end, ok: the descriptor's pointers, in order
+    desc = _lib.MinibatchAdcInC(_lib.addr(a), n, stride, *[_lib.addr(v) for v in rest])
     return desc, n, kept
 
 
@@ -328,43 +289,25 @@ def fingerprint_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_en
     device.  Bit-identical to ``fingerprint_batch(calibrate_adc(adc, row_len, offset, scale), ...)``."""
     desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success)
     pc = params.to_c()
-    K = params.barcode_num_events
-    fpt = np.empty((n, K), dtype=np.float64)
-    dwell = np.empty((n, K), dtype=np.int64)
-    stats = np.empty((n, 6), dtype=np.float64)
-    status = np.empty(n, dtype=np.int32)
+    o = _marshal.outputs(n, params.barcode_num_events, 0, 0, _FPT_WANT)
     ctx = _lib.default_context(device)
-    _lib.check(_lib.load().wdx_fingerprint_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), _lib.ptr(fpt), _lib.ptr(dwell),
-                                                     _lib.ptr(stats), _lib.ptr(status)))
+    _lib.check(_lib.load().wdx_fingerprint_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), _lib.ptr(o["fpt"]),
+                                                     _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["status"])))
     del kept
-    return FingerprintBatch(fpt, dwell, stats, status)
+    return fingerprints(o)
 
 
 def fingerprint_refine_batch(signals, adapter_start, adapter_end, params: SegParams, refine: RefineParams, success=None,
                              device=None) -> FingerprintBatch:
     """Consensus-refinement branch on a (n_reads, stride) float32 minibatch; K = refine.barcode_keep_events."""
-    sig = np.asarray(signals)
-    if sig.ndim != 2:
-        raise ValueError("signals must be a 2-D (n_reads, stride) array")
-    sig = np.ascontiguousarray(sig, dtype=np.float32)
-    n, stride = sig.shape
-    a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-    a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-    if a_s.shape != (n,) or a_e.shape != (n,):
-        raise ValueError("adapter_start/adapter_end must have one entry per read")
-    ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
+    sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
     pc, rc = params.to_c(), refine.to_c()
-    K = refine.barcode_keep_events
-    fpt = np.empty((n, K), dtype=np.float64)
-    dwell = np.empty((n, K), dtype=np.int64)
-    stats = np.empty((n, 6), dtype=np.float64)
-    idx = np.empty((n, 3), dtype=np.int32)
-    status = np.empty(n, dtype=np.int32)
+    o = _marshal.outputs(n, refine.barcode_keep_events, 0, 0, _FPT_WANT | _lib.WANT_REFINE_IDX)
     ctx = _lib.default_context(device)
     _lib.check(_lib.load().wdx_fingerprint_refine_batch(
         ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc), C.byref(rc),
-        _lib.ptr(fpt), _lib.ptr(dwell), _lib.ptr(stats), _lib.ptr(idx), _lib.ptr(status)))
-    return FingerprintBatch(fpt, dwell, stats, status, idx)
+        _lib.ptr(o["fpt"]), _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["refine_idx"]), _lib.ptr(o["status"])))
+    return fingerprints(o)
 
 
 @dataclass
@@ -389,64 +332,47 @@ def set_references(refs, window=None, penalty=None, device=None):
 
 
 def _submit_references(ctx, refs, window, penalty):
-    import ctypes as C
-
-    L = _lib.load()
-    _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(refs), refs.shape[0], refs.shape[1],
-                              int(window) if window else 0, float(penalty) if penalty else 0.0))
+    _marshal.set_refs(ctx, refs, window, penalty)
     gen = C.c_int64(0)
-    _lib.check(L.wdx_refs_generation(ctx.handle, C.byref(gen)))
+    _lib.check(_lib.load().wdx_refs_generation(ctx.handle, C.byref(gen)))
     ctx._demux_refs_gen = gen.value
 
 
-def _ensure_references(ctx):
-    """The context holds one reference set; distance_matrix_to / a DTW_SVM model may have replaced the one
-    `set_references` installed.  One counter read per call tells (wdx_refs_generation)."""
-    import ctypes as C
-
+def _held_references(ctx, who: str, n_refs=None) -> int:
+    """How many references `set_references` installed in this context, after making sure they are still the resident set:
+    distance_matrix_to / a DTW_SVM model may have replaced it, and one counter read per call tells (wdx_refs_generation).  The
+    distance matrix is sized from this number, never from the caller (the C ABI checks it against the resident set once
+    more)."""
     held = getattr(ctx, "_demux_refs", None)
     if held is None:
-        return
+        raise _lib.WdxError(f"{who}: no reference set -- call set_references() first")
+    n_held = int(held[0].shape[0])
+    if n_refs is not None and int(n_refs) != n_held:
+        raise ValueError(f"n_refs={n_refs} but set_references() installed {n_held} references")
     gen = C.c_int64(0)
     _lib.check(_lib.load().wdx_refs_generation(ctx.handle, C.byref(gen)))
     if gen.value != ctx._demux_refs_gen:
         _submit_references(ctx, *held)
+    return n_held
+
+
+def _demux_want(want_dist, want_fpt) -> int:
+    return (_lib.WANT_DIST if want_dist else 0) | (_lib.WANT_FPT if want_fpt else 0)
 
 
 def demux_batch(signals, adapter_start, adapter_end, params: SegParams, success=None, want_dist=True,
                 want_fpt=False, n_refs=None, device=None) -> DemuxBatch:
     """One call per minibatch / live tick: fingerprints, distances to the resident references
     (`set_references`) and the nearest-reference call, with a single device synchronisation."""
-    sig = np.asarray(signals)
-    if sig.ndim != 2:
-        raise ValueError("signals must be a 2-D (n_reads, stride) array")
-    sig = np.ascontiguousarray(sig, dtype=np.float32)
-    n, stride = sig.shape
-    a_s = np.ascontiguousarray(adapter_start, dtype=np.int32)
-    a_e = np.ascontiguousarray(adapter_end, dtype=np.int32)
-    if a_s.shape != (n,) or a_e.shape != (n,):
-        raise ValueError("adapter_start/adapter_end must have one entry per read")
-    ok = None if success is None else np.ascontiguousarray(success, dtype=np.uint8)
+    sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
     pc = params.to_c()
-    K = params.barcode_num_events
     ctx = _lib.default_context(device)
-    held = getattr(ctx, "_demux_refs", None)
-    if held is None:
-        raise _lib.WdxError("demux_batch: no reference set -- call set_references() first")
-    # the distance matrix is sized from the set this context holds, never from the caller (the C ABI checks
-    # it against the resident set once more)
-    n_held = int(held[0].shape[0])
-    if n_refs is not None and int(n_refs) != n_held:
-        raise ValueError(f"n_refs={n_refs} but set_references() installed {n_held} references")
-    dist = np.empty((n, n_held), dtype=np.float32) if want_dist else None
-    fpt = np.empty((n, K), dtype=np.float64) if want_fpt else None
-    call = np.empty(n, dtype=np.int32)
-    status = np.empty(n, dtype=np.int32)
-    _ensure_references(ctx)
+    n_held = _held_references(ctx, "demux_batch", n_refs)
+    o = _marshal.outputs(n, params.barcode_num_events, n_held, 0, _demux_want(want_dist, want_fpt))
     _lib.check(_lib.load().wdx_demux_batch(
         ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc),
-        n_held, _lib.ptr(fpt), _lib.ptr(dist), _lib.ptr(call), _lib.ptr(status)))
-    return DemuxBatch(status, call, dist, fpt)
+        n_held, _lib.ptr(o["fpt"]), _lib.ptr(o["dist"]), _lib.ptr(o["call"]), _lib.ptr(o["status"])))
+    return DemuxBatch(o["status"], o["call"], o["dist"], o["fpt"])
 
 
 def demux_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, params: SegParams, success=None, want_dist=True,
@@ -456,19 +382,12 @@ def demux_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, par
     desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success)
     pc = params.to_c()
     ctx = _lib.default_context(device)
-    held = getattr(ctx, "_demux_refs", None)
-    if held is None:
-        raise _lib.WdxError("demux_batch_adc: no reference set -- call set_references() first")
-    n_held = int(held[0].shape[0])
-    dist = np.empty((n, n_held), dtype=np.float32) if want_dist else None
-    fpt = np.empty((n, params.barcode_num_events), dtype=np.float64) if want_fpt else None
-    call = np.empty(n, dtype=np.int32)
-    status = np.empty(n, dtype=np.int32)
-    _ensure_references(ctx)
-    _lib.check(_lib.load().wdx_demux_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), n_held, _lib.ptr(fpt), _lib.ptr(dist),
-                                               _lib.ptr(call), _lib.ptr(status)))
+    n_held = _held_references(ctx, "demux_batch_adc")
+    o = _marshal.outputs(n, params.barcode_num_events, n_held, 0, _demux_want(want_dist, want_fpt))
+    _lib.check(_lib.load().wdx_demux_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), n_held, _lib.ptr(o["fpt"]),
+                                               _lib.ptr(o["dist"]), _lib.ptr(o["call"]), _lib.ptr(o["status"])))
     del kept
-    return DemuxBatch(status, call, dist, fpt)
+    return DemuxBatch(o["status"], o["call"], o["dist"], o["fpt"])
 
 
 def detect_results_to_fpt_batch(calibrated_signals, spc, detect_results: Sequence, read_ids: Optional[Sequence[str]] = None,
