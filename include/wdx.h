@@ -72,7 +72,9 @@ extern "C" {
  *                                               WDX_READ_FAIL_UNKNOWN, as in the reference)
  *   padding             >= 0       negative  -> WDX_ERR_INVALID
  *   min_obs_per_base    any        below 1 every read fails with WDX_READ_FAIL_UNKNOWN (scipy refuses distance 0)
- * Adapter windows (padding included) longer than WDX_MAX_ADAPTER_SAMPLES come back WDX_READ_FAIL_UNKNOWN. */
+ * Adapter windows (padding included) longer than WDX_MAX_ADAPTER_SAMPLES come back WDX_READ_FAIL_UNKNOWN -- on a context
+ * with WDX_OPT_LONG_WINDOWS = 1, longer than WDX_MAX_LONG_ADAPTER_SAMPLES (plain branch; the refinement branch keeps the
+ * smaller limit). */
 typedef struct wdx_seg_params {
     int32_t padding;            /* sig_extract.padding                                          */
     int32_t sig_norm;           /* sig_extract.normalization   (WDX_NORM_*)                     */
@@ -137,6 +139,18 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
 #define WDX_OPT_BOOST_KERNEL 19         /* boost tail: 0 (default) the kernel is chosen by batch size (WDX_BOOST_SMALL_MAX_READS) |
                                          * 1 the lane-per-read kernel only | 2 the tree-parallel kernel only (A/B, tests); both
                                          * give the same bits */
+/* A product option, not a diagnostic one.  0 (default): adapter windows beyond WDX_MAX_ADAPTER_SAMPLES are reported
+ * WDX_READ_FAIL_UNKNOWN.  1: windows up to WDX_MAX_LONG_ADAPTER_SAMPLES are fingerprinted (the reference has no limit:
+ * `--export core.max_obs_trace=...`), bit for bit like the shorter ones, by one more storage form of the exact kernel
+ * (samples and score curve in HBM: a rare-read path); longer ones are reported WDX_READ_FAIL_UNKNOWN.  Any other value:
+ * WDX_ERR_INVALID.  Every entry that fingerprints on this context honours it -- wdx_fingerprint_batch[_adc],
+ * wdx_fingerprint_dev, wdx_demux_batch[_adc], wdx_demux_dev, wdx_demux_svm_dev / _mlp_dev / _boost_dev,
+ * wdx_demux_submit[_ex|_adc] (a pipeline slot copies the options at every submit), a feeder served by this
+ * context, wdx_live_tick[_ex] -- with two exceptions: the consensus-refinement branch (wdx_*_refine*, rp != NULL) and
+ * wdx_fingerprint_profile_dev keep the limit of WDX_MAX_ADAPTER_SAMPLES.  Cost: 12 MiB of device memory per context
+ * (16 slots of 768 KiB), allocated by the first call that meets such a window with the option on (a synchronising
+ * hipMalloc on that one call) and never otherwise; each pipeline slot that meets one owns its own (96 MiB for 8). */
+#define WDX_OPT_LONG_WINDOWS 20
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -185,7 +199,8 @@ int wdx_fingerprint_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64
  *   d_row_len == NULL  -> row_len[r] = d_row_off ? d_row_off[r+1]-d_row_off[r] : stride
  * (so a packed batch passes int64 offsets[n_reads+1] and NULL lengths).  max_len bounds the
  * adapter window of every read (it sizes the LDS carve-up); windows longer than max_len or than
- * WDX_MAX_ADAPTER_SAMPLES are reported WDX_READ_FAIL_UNKNOWN.  (The largest window the reference admits is
+ * WDX_MAX_ADAPTER_SAMPLES (WDX_OPT_LONG_WINDOWS = 1: than WDX_MAX_LONG_ADAPTER_SAMPLES, see there) are reported
+ * WDX_READ_FAIL_UNKNOWN.  (The largest window the reference admits is
  * max_obs_trace + 2*padding = 15 200 samples, DEPRECATED/config_files/rna002_70bps@v0.4.4.toml:2; up to 11 200
  * samples a read's score curve lives in LDS, beyond that in a context-owned HBM block of 32 MiB that is
  * allocated on first need -- a synchronising hipMalloc on that one call.)
@@ -197,6 +212,7 @@ int wdx_fingerprint_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
                         int64_t *d_dwell, double *d_stats, int32_t *d_status, void *stream);
 
 #define WDX_MAX_ADAPTER_SAMPLES 16384
+#define WDX_MAX_LONG_ADAPTER_SAMPLES 65536 /* with WDX_OPT_LONG_WINDOWS = 1 */
 
 /* ---- N3: consensus-guided barcode refinement (tRNA models) -- detect_results_to_fpt with
  *      segmentation.consensus_refinement = True (sig_proc.py:257-378, 452-521): segment the adapter, find the

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Fingerprint-stage throughput by adapter-window length (device-resident minibatch layout), for one parameter triple:
-which kernel a window reaches and what it costs there.   python tools/long_window_bench.py [E d W] [n_reads]"""
+which kernel a window reaches and what it costs there.   python tools/long_window_bench.py [E d W] [n_reads]
+
+    python tools/long_window_bench.py --long [n_reads]
+
+the long form of the exact kernel (``long_windows=True``: windows beyond 16 384 samples, fingerprint_long_kernel) at 20 000 and
+65 536 samples for the three shipped triples, beside the CPU oracle on one core of this machine; one JSON line per row."""
 import os
 import sys
 import time
@@ -14,6 +19,45 @@ import torch  # noqa: E402
 from warpdemux_amd import sig_proc  # noqa: E402
 from warpdemux_amd.engine import DemuxEngine  # noqa: E402
 
+
+
+def long_mode(n):
+    import json
+
+    from oracle import wdx_oracle as orc
+
+    rng = np.random.default_rng(1)
+    for name, (E, d, W) in (("rna004", (110, 6, 12)), ("rna002", (110, 15, 30)), ("trna", (120, 9, 18))):
+        kw = dict(padding=0, num_events=E, min_obs_per_base=d, running_stat_width=W, barcode_num_events=25)
+        eng = DemuxEngine(np.zeros((4, 25)), 15, 0.1, sig_proc.SegParams(**kw), long_windows=True)
+        for ln in (20000, 65536):
+            dw = max(12, ln // 135)
+            base = (np.repeat(rng.normal(80, 15, (16, ln // dw + 1)), dw, axis=1)[:, :ln] + rng.normal(0, 2, (16, ln))).astype(np.float32)
+            mb = torch.from_numpy(np.tile(base, (n // 16, 1))).cuda()
+            a_s = torch.zeros(n, dtype=torch.int32, device="cuda")
+            a_e = torch.full((n,), ln, dtype=torch.int32, device="cuda")
+            for _ in range(2):
+                out = eng.fingerprint(mb, a_s, a_e, stride=ln, max_len=ln)
+            torch.cuda.synchronize()
+            reps = 3
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                out = eng.fingerprint(mb, a_s, a_e, stride=ln, max_len=ln)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / reps
+            t0 = time.perf_counter()
+            ref = orc.fingerprint_batch(base, np.zeros(16, np.int32), np.full(16, ln, np.int32), orc.SegParams(**kw))
+            dt_cpu = (time.perf_counter() - t0) / 16
+            same = bool(np.array_equal(out[0][:16].cpu().numpy(), ref[0], equal_nan=True))
+            print(json.dumps(dict(triple=name, window=ln, n_reads=n, gpu_reads_per_s=round(n / dt, 1), gpu_ms_per_call=round(dt * 1e3, 3),
+                                  ok=int((out[3] == 0).sum().item()), oracle_reads_per_s_one_core=round(1.0 / dt_cpu, 1),
+                                  bit_identical_to_oracle=same)), flush=True)
+        eng.ctx.close()
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--long":
+    long_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 256)
+    sys.exit(0)
 E, d, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) > 3 else (110, 15, 30)
 n = int(sys.argv[4]) if len(sys.argv) > 4 else 8192
 rng = np.random.default_rng(1)

@@ -6,6 +6,7 @@ point raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -42,6 +43,7 @@ OPT_DTW_UNFUSED = 16
 OPT_MLP_CHUNK_ROWS = 17
 OPT_BOOST_CHUNK_ROWS = 18
 OPT_BOOST_KERNEL = 19   # 0 by batch size | 1 lane-per-read | 2 tree-parallel
+OPT_LONG_WINDOWS = 20   # product option: 1 = adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (0 / 1, else ValueError)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -534,6 +536,7 @@ class Context:
         self._L = L
         self.device = int(device)
         self.pid = os.getpid()
+        self.long_windows = False
 
     @property
     def handle(self):
@@ -544,8 +547,24 @@ class Context:
         return self._h
 
     def set_option(self, option: int, value: int = 1):
-        """Diagnostic switch (wdx_ctx_set_option); tests and profiling tools only."""
+        """Diagnostic switch (wdx_ctx_set_option); tests and profiling tools only -- and OPT_LONG_WINDOWS, which the
+        ``long_windows=`` keyword of the classes and module-level calls sets."""
         check(self._L.wdx_ctx_set_option(self.handle, int(option), int(value)))
+        if int(option) == OPT_LONG_WINDOWS:
+            self.long_windows = bool(value)
+
+    @contextlib.contextmanager
+    def long_windows_for_call(self, on: bool):
+        """OPT_LONG_WINDOWS = ``on`` for the duration of one call on a shared context, then what it was before -- also when
+        the call raises."""
+        before = getattr(self, "long_windows", False)
+        if bool(on) != before:
+            self.set_option(OPT_LONG_WINDOWS, int(bool(on)))
+        try:
+            yield self
+        finally:
+            if bool(on) != before:
+                self.set_option(OPT_LONG_WINDOWS, int(before))
 
     def synchronize(self, stream=None):
         check(self._L.wdx_ctx_synchronize(self.handle, stream))

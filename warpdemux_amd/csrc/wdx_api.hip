@@ -188,9 +188,12 @@ int use_stream(wdx_ctx *ctx, hipStream_t s) {
 int fingerprint_stage(wdx_ctx *B, const FpReads &in, const wdx_seg_params &p, const FpOut &out, void *d_ws,
                       hipStream_t s, const RefineDev *rf, bool main_events) {
     if (int rc = B->fp_big.ensure((size_t)fingerprint_big_bytes(in.max_len))) return rc;
+    const bool with_long = B->knobs.long_windows && !rf && fingerprint_long_bytes(in.max_len) > 0;
+    if (with_long)
+        if (int rc = B->fp_long.ensure((size_t)fingerprint_long_bytes(in.max_len))) return rc;
     Timed t(B, WDX_K_FINGERPRINT, s);
     return launch_fingerprint(in, p, out, s, d_ws, B->knobs, &t.n_launches, nullptr, 0, 0, rf,
-                              main_events ? &t.main : nullptr, (double *)B->fp_big.p);
+                              main_events ? &t.main : nullptr, (double *)B->fp_big.p, with_long ? B->fp_long.p : nullptr);
 }
 
 int check_ref_length(const DtwRefs &R, const wdx_seg_params &p) {
@@ -477,7 +480,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     comm_destroy(ctx);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf, &ctx->mb_ridx})
         b->release();
     ctx->pin_in.release();
@@ -519,6 +522,13 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
         case WDX_OPT_MLP_CHUNK_ROWS: ctx->knobs.mlp_chunk_rows = value > 0 ? value : 0; break;
         case WDX_OPT_BOOST_CHUNK_ROWS: ctx->knobs.boost_chunk_rows = value > 0 ? value : 0; break;
         case WDX_OPT_BOOST_KERNEL: ctx->knobs.boost_kernel = (value >= 0 && value <= 2) ? (int)value : 0; break;
+        case WDX_OPT_LONG_WINDOWS:
+            if (value != 0 && value != 1) {
+                set_error("WDX_OPT_LONG_WINDOWS is 0 or 1, not %lld", (long long)value);
+                return WDX_ERR_INVALID;
+            }
+            ctx->knobs.long_windows = value == 1;
+            break;
         default:
             set_error("unknown option %d", (int)option);
             return WDX_ERR_INVALID;

@@ -44,6 +44,9 @@ struct Knobs {
     int64_t mlp_chunk_rows = 0;      // WDX_OPT_MLP_CHUNK_ROWS: rows per pass of wdx_dtw_mlp_predict (0 = built-in)
     int64_t boost_chunk_rows = 0;    // WDX_OPT_BOOST_CHUNK_ROWS: rows per pass of wdx_boost_predict (0 = built-in)
     int boost_kernel = 0;            // WDX_OPT_BOOST_KERNEL: 0 by batch size | 1 lane-per-read | 2 tree-parallel
+    bool long_windows = false;       // WDX_OPT_LONG_WINDOWS: adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (product option)
+    // the longest adapter window this context fingerprints (the host loops cut one sample beyond it: that reports it)
+    int64_t max_window() const { return long_windows ? WDX_MAX_LONG_ADAPTER_SAMPLES : WDX_MAX_ADAPTER_SAMPLES; }
 };
 
 // A launch over more workgroups than grid.x admits is cut into slices (block_base != 0 from the second on).  The built-in
@@ -173,13 +176,17 @@ int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &
                        void *d_ws /* fingerprint_workspace_bytes(n) or null */, const Knobs &knobs,
                        int64_t *n_launches = nullptr, long long *d_prof = nullptr, int64_t prof_reads = 0,
                        int stop_phase = 0, const struct RefineDev *rf = nullptr, MainEvents *main_ev = nullptr,
-                       double *d_big = nullptr /* fingerprint_big_bytes(max_len) bytes, or null */);
+                       double *d_big = nullptr /* fingerprint_big_bytes(max_len) bytes, or null */,
+                       void *d_long = nullptr /* fingerprint_long_bytes(max_len) bytes, or null: WDX_OPT_LONG_WINDOWS */);
 int64_t fingerprint_workspace_bytes(int64_t n_reads);
 // device bytes of the fast kernels' hand-over records for the refinement branch (RefineDev::ws), zero-initialised
 int64_t fingerprint_refine_ws_bytes(int64_t n_reads);
 void set_refine_ws(struct RefineDev *rf, void *d_ws);
 // device bytes the exact kernel needs for the score curves of windows beyond its LDS capacity (0 when max_len fits)
 int64_t fingerprint_big_bytes(int64_t max_len);
+// ... and, with WDX_OPT_LONG_WINDOWS, for the score curves and samples of windows beyond WDX_MAX_ADAPTER_SAMPLES: 16 slots
+// of 768 KB = 12 MB (0 when max_len <= WDX_MAX_ADAPTER_SAMPLES)
+int64_t fingerprint_long_bytes(int64_t max_len);
 int launch_clip_bounds_selftest(const float *d_sig, const int64_t *d_row_off, int64_t stride, int64_t n_reads,
                                 const int32_t *d_a_start, const int32_t *d_a_end, const wdx_seg_params &p, int cap,
                                 void *d_rec, hipStream_t stream);

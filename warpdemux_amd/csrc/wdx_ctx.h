@@ -58,6 +58,9 @@ struct wdx_ctx {
     wdx::Buffer in0, in1, in2, in3, out0, out1, out2, out3, tmp0, tmp1, tmp2, scratch, fp_ws, svm_buf, ref_buf;
     wdx::Buffer ref_ws;  // refinement branch: the fast kernels' hand-over records (fingerprint_refine_ws_bytes)
     wdx::Buffer fp_big;  // score curves of adapter windows beyond the exact kernel's LDS capacity (fingerprint_big_bytes)
+    // WDX_OPT_LONG_WINDOWS: slots of the long form (fingerprint_long_bytes: 12 MB), allocated by the first call that meets a
+    // window beyond WDX_MAX_ADAPTER_SAMPLES with the option on -- never otherwise.  A pipeline slot owns its own: 96 MB for 8
+    wdx::Buffer fp_long;
     wdx::PinnedBuffer pin_in, pin_out;  // staging of small (live-tick sized) host-buffer calls
     std::vector<double> ref_query_host;  // the consensus query resident in ref_buf (refine_prepare uploads on change)
     wdx::Buffer pk_idx;       // packed staging of a page-locked minibatch: window offsets / first columns / shifted bounds
@@ -139,7 +142,7 @@ WDX_INTERNAL int dtw_settle_inf(const DtwRefs &R, const double *dX, int64_t nX, 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // (wdx_api.hip) The fingerprint stage as every entry point but the profiling one runs it: `B` (the context, or the
-// pipeline slot that owns the stream) supplies fp_big for max_len, the knobs and the WDX_K_FINGERPRINT event scope.
+// pipeline slot that owns the stream) supplies fp_big (and fp_long) for max_len, the knobs and the WDX_K_FINGERPRINT event scope.
 // main_events = false leaves the main / clip / tail kernel pairs unrecorded (they go back to the pool):
 // wdx_fingerprint_refine_dev, the host-batch call (wdx_minibatch.hip: fingerprint_batch_impl) and wdx_live_tick have never
 // recorded them.  Kept as found: neither DESIGN.md nor DESIGN_HISTORY.md gives a reason.

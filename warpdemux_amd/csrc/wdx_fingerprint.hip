@@ -29,6 +29,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace wdx {
@@ -45,6 +46,16 @@ constexpr int kExactLdsCap = 11200;
 constexpr int kBigCap = WDX_MAX_ADAPTER_SAMPLES;
 constexpr int kBigSlots = 256;  // one workgroup per CU (97 KB of LDS each)
 static_assert(kBigCap % 64 == 0 && kBigCap >= 15200, "the exact path must take every window the reference accepts");
+// WDX_OPT_LONG_WINDOWS: windows of kBigCap+1 .. kLongCap samples run the SAME code once more with the clipped float32
+// samples in the workgroup's HBM slot too (fingerprint_long_kernel): beside the fixed tables LDS holds the peak-state
+// bytes only (64 KB of the 160 KB).  A slot is 65 536 x (8 + 4) B = 768 KB; kLongSlots of them are 12 MB per context,
+// allocated at the first call that sees such a window with the option on (fingerprint_long_bytes).
+constexpr int kLongCap = WDX_MAX_LONG_ADAPTER_SAMPLES;
+constexpr int kLongSlots = 16;
+constexpr size_t kLongSlotBytes = (size_t)kLongCap * (8 + 4);
+// positions fit 16 bits (the peak list's uint16 entries hold positions < ns < kLongCap); one thread's chunk of the state
+// bytes fits a 64-bit mask at 1024 threads
+static_assert(kLongCap % 64 == 0 && kLongCap <= 65536 && kLongCap > kBigCap && kLongCap <= 64 * 1024, "long form of the exact kernel");
 
 enum : unsigned char { ST_NONE = 0, ST_UNDECIDED = 1, ST_KEPT = 2, ST_DROPPED = 3, ST_SELECTED = 4 };
 
@@ -445,7 +456,8 @@ __device__ __forceinline__ int block_excl_scan(int v, FpShared &sh, int &total) 
     return base + incl - v;
 }
 
-template <int BLOCK>
+// WIDE (the long form, ns up to kLongCap): a thread's chunk of the state bytes is up to 64 positions -- a 64-bit mask
+template <int BLOCK, bool WIDE = false>
 __device__ int fp_segment(const double *scores, unsigned char *state, const int ns, const int d_eff, const int W,
                           const int E, const bool accept_less, const float *sig, const int n_end, int *cpts, double *ev,
                           unsigned *hist, FpShared &sh, int &nseg, int &nms_iters, const bool no_list = false,
@@ -472,23 +484,30 @@ __device__ int fp_segment(const double *scores, unsigned char *state, const int 
     int nsel;
     bool use_list;
     int np = 0, lbase = 0;
-    unsigned lbits = 0;
-    const int lchunk = (ns + BLOCK - 1) / BLOCK;  // <= 32: cap <= 16 384, BLOCK >= 512
+    using LBits = typename std::conditional<WIDE, unsigned long long, unsigned>::type;
+    constexpr int kLBits = WIDE ? 64 : 32;
+    LBits lbits = 0;
+    const int lchunk = (ns + BLOCK - 1) / BLOCK;  // <= 32: cap <= 16 384, BLOCK >= 512 (WIDE: <= 64, cap <= 65 536, BLOCK = 1024)
     const int lc0 = tid * lchunk;
     {
         const int lc1 = min(ns, lc0 + lchunk);
-        for (int i = lc0; i < lc1; ++i) lbits |= (state[i] == ST_UNDECIDED ? 1u : 0u) << (i - lc0);
-        lbase = block_excl_scan<BLOCK>(__popc(lbits), sh, np);  // (its barriers: every state byte has been read)
-        use_list = !no_list && lchunk <= 32 && 3 * np + 8 <= ns;
+        for (int i = lc0; i < lc1; ++i) lbits |= (LBits)(state[i] == ST_UNDECIDED ? 1u : 0u) << (i - lc0);
+        int lcount;
+        if constexpr (WIDE) lcount = __popcll(lbits);
+        else lcount = __popc(lbits);
+        lbase = block_excl_scan<BLOCK>(lcount, sh, np);  // (its barriers: every state byte has been read)
+        use_list = !no_list && lchunk <= kLBits && 3 * np + 8 <= ns;
     }
     if (use_list) {
         unsigned short *lpos = reinterpret_cast<unsigned short *>(state);
         unsigned char *lst = state + ((2 * np + 3) & ~3);
         {
             int o = lbase;
-            unsigned b = lbits;
+            LBits b = lbits;
             while (b) {
-                const int j = __ffs((int)b) - 1;
+                int j;
+                if constexpr (WIDE) j = __ffsll((unsigned long long)b) - 1;
+                else j = __ffs((int)b) - 1;
                 b &= b - 1;
                 lpos[o] = (unsigned short)(lc0 + j);
                 lst[o] = ST_UNDECIDED;
@@ -1102,8 +1121,9 @@ __device__ void fp_refine_tail(const FpArgs &A, const int64_t r, unsigned char *
         }                                                                                   \
     } while (0)
 
-template <int BLOCK, bool PROF, bool BIG = false>
+template <int BLOCK, bool PROF, bool BIG = false, bool LONG = false>
 __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char *smem) {
+    static_assert(!LONG || (BIG && !PROF), "the long form is the big form with the samples in the slot as well");
     const int tid = threadIdx.x;
     const wdx_seg_params &P = A.p;
     const int K = P.barcode_num_events;
@@ -1111,16 +1131,18 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
 
     // LDS carve-up (every region starts 8-byte aligned; cap is a multiple of 64).  BIG: the score curve lives in
     // this workgroup's HBM slot instead (same code, global loads/stores: the address space follows the
-    // instantiation), everything else stays in LDS.
-    double *scores = BIG ? A.big_scores + (size_t)blockIdx.x * kBigCap : reinterpret_cast<double *>(smem);  // cap
+    // instantiation), everything else stays in LDS.  LONG: the slot (A.big_scores: kLongSlotBytes each) holds the score
+    // curve and, behind it, the clipped samples; LDS keeps the fixed tables and the dedicated peak-state bytes.
+    double *scores = LONG ? A.big_scores + (size_t)blockIdx.x * (kLongSlotBytes / 8)
+                          : (BIG ? A.big_scores + (size_t)blockIdx.x * kBigCap : reinterpret_cast<double *>(smem));  // cap
     double *Mt = BIG ? reinterpret_cast<double *>(smem) : scores + A.cap;  // kTile + kMaxW
     double *Vt = Mt + (kTile + kMaxW);                                    // kTile + kMaxW
     double *ev = Vt + (kTile + kMaxW);                                    // kSegCap
     double *zz = ev + kSegCap;                                            // kSegCap
     double *tmp = zz + kSegCap;                                           // kSegCap
     FpShared &sh = *reinterpret_cast<FpShared *>(tmp + kSegCap);
-    float *sig = reinterpret_cast<float *>(&sh + 1);                      // cap
-    unsigned *hist = reinterpret_cast<unsigned *>(sig + A.cap);           // 256
+    float *sig = LONG ? reinterpret_cast<float *>(scores + kLongCap) : reinterpret_cast<float *>(&sh + 1);   // cap
+    unsigned *hist = LONG ? reinterpret_cast<unsigned *>(&sh + 1) : reinterpret_cast<unsigned *>(sig + A.cap);   // 256
     int *cpts = reinterpret_cast<int *>(hist + 256);                      // kSegCap + 1
     // the peak-state bytes are live only after the last t-score tile: they reuse the tile buffers
     // whenever they fit, else a dedicated tail region
@@ -1159,7 +1181,7 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
     int64_t n64 = stop - start;
     if (n64 < 0) n64 = 0;
     if (n64 > A.cap) {
-        if (!BIG && A.defer_big && n64 <= kBigCap) return;  // fingerprint_big_kernel takes it
+        if (!BIG && n64 <= A.defer_big) return;  // fingerprint_big_kernel (fingerprint_long_kernel) takes it
         finish(WDX_READ_FAIL_UNKNOWN);
         return;
     }
@@ -1180,7 +1202,7 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
         float lo, hi;
         // behind the launch chain the bounds exist already (clip_bounds_kernel: the same float32 numbers; CLIP_OK also
         // says that the window holds no NaN and lo <= hi) -- the two workgroup-wide selects are a quarter of this kernel
-        const ClipRec *crp = A.clip;
+        const ClipRec *crp = LONG ? nullptr : A.clip;   // (no clip kernel takes a long window: its own two medians)
         int cflag = CLIP_NONE;
         if (crp) {
             const ClipRec cr = crp[r];   // (block-uniform)
@@ -1228,9 +1250,12 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
         // mean_normalize on the float32 signal (sig_proc.py:99-111, accept_nan=True): np.mean / np.std, or
         // np.nanmean / np.nanstd when the window holds a NaN -- float32 sums in NumPy's association
         // (oracle: mean_normalize_f32).  LDS scratch: the score curve and the event arrays are still unused.
+        // LONG: up to 7 x 64 + 130 leaves (seven full 8192-element chunks and a partial one) -- more than hist and ev
+        // hold: the leaf tables take the tile buffers instead (2 x 4 KB of their 9 KB, the stack behind them)
         float *sq = reinterpret_cast<float *>(scores);   // n floats
-        float *lsum = reinterpret_cast<float *>(ev);       // leaf sums
-        int *stk = reinterpret_cast<int *>(zz);            // traversal stack
+        unsigned *lstart = LONG ? reinterpret_cast<unsigned *>(Mt) : hist;                         // leaf starts
+        float *lsum = LONG ? reinterpret_cast<float *>(Mt) + 1024 : reinterpret_cast<float *>(ev); // leaf sums
+        int *stk = LONG ? reinterpret_cast<int *>(Mt) + 2048 : reinterpret_cast<int *>(zz);        // traversal stack
         unsigned vcnt = 0;
         for (int i = tid; i < n; i += BLOCK) vcnt += (sig[i] == sig[i]);
         unsigned gmin_, gmax_, cnt;
@@ -1238,23 +1263,23 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
         const bool has_nan = cnt != (unsigned)n;
         float shift, scale;
         if (!has_nan) {
-            shift = block_np_add_reduce_f32<BLOCK>([&](int i) { return sig[i]; }, n, hist, lsum, stk, sh) / (float)n;
+            shift = block_np_add_reduce_f32<BLOCK>([&](int i) { return sig[i]; }, n, lstart, lsum, stk, sh) / (float)n;
             for (int i = tid; i < n; i += BLOCK) {
                 const float d = sig[i] - shift;
                 sq[i] = d * d;
             }
-            scale = sqrtf(block_np_add_reduce_f32<BLOCK>([&](int i) { return sq[i]; }, n, hist, lsum, stk, sh) / (float)n);
+            scale = sqrtf(block_np_add_reduce_f32<BLOCK>([&](int i) { return sq[i]; }, n, lstart, lsum, stk, sh) / (float)n);
         } else {
             // _replace_nan(a, 0); sums in float32; _divide_by_count forms the quotient in float64 (float32 / intp)
             const float tot = block_np_add_reduce_f32<BLOCK>(
-                [&](int i) { const float v = sig[i]; return v == v ? v : 0.0f; }, n, hist, lsum, stk, sh);
+                [&](int i) { const float v = sig[i]; return v == v ? v : 0.0f; }, n, lstart, lsum, stk, sh);
             shift = (float)((double)tot / (double)cnt);
             for (int i = tid; i < n; i += BLOCK) {
                 const float v = sig[i];
                 const float d = (v == v) ? v - shift : 0.0f;
                 sq[i] = d * d;
             }
-            const float var = (float)((double)block_np_add_reduce_f32<BLOCK>([&](int i) { return sq[i]; }, n, hist,
+            const float var = (float)((double)block_np_add_reduce_f32<BLOCK>([&](int i) { return sq[i]; }, n, lstart,
                                                                              lsum, stk, sh) / (double)cnt);
             scale = sqrtf(var);
         }
@@ -1315,7 +1340,7 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
     // ---- P3-P6: find_peaks + top-E + boundaries + event means (fp_segment) ----------------------------
     int nms_iters = 0, nseg = 0;
     {
-        const int st = fp_segment<BLOCK>(scores, state, ns, d_eff, W, E, P.accept_less_cpts != 0, sig, n, cpts, ev,
+        const int st = fp_segment<BLOCK, LONG>(scores, state, ns, d_eff, W, E, P.accept_less_cpts != 0, sig, n, cpts, ev,
                                          hist, sh, nseg, nms_iters, A.no_list != 0);
         if (st != WDX_READ_OK) {
             finish(st);
@@ -1323,6 +1348,7 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
         }
     }
     WDX_STAMP(7);
+    if constexpr (!LONG)   // (the refinement branch does not take long windows: launch_fingerprint never sends it one)
     if (A.rf.query) {
         // The refinement kernels behind the fast kernels (one wave per three reads for the match, a quarter of this
         // workgroup for the barcode's segmentation) take this read too when they can reproduce its clipped samples from
@@ -1467,6 +1493,27 @@ __global__ __launch_bounds__(BLOCK) void fingerprint_big_kernel(FpArgs A, const 
         if (stop - start <= small_cap || stop - start > kBigCap) continue;
         __syncthreads();
         fp_process_read<BLOCK, false, true>(A, r, smem);
+    }
+}
+
+// WDX_OPT_LONG_WINDOWS: windows of kBigCap+1 .. kLongCap samples, left alone by every launch before this one: a fixed grid
+// of <= kLongSlots workgroups strides over the slow list (or over all reads) and takes only those
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void fingerprint_long_kernel(FpArgs A, const unsigned *count, const int32_t *list) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int64_t n = count ? (int64_t)*count : A.n_reads;
+    for (int64_t k = blockIdx.x; k < n; k += gridDim.x) {
+        const int64_t r = list ? (int64_t)list[k] : k;
+        if (A.ok && !A.ok[r]) continue;  // the regular kernel reported it
+        const int64_t row_len = A.row_len ? (int64_t)A.row_len[r]
+                                          : (A.row_off ? A.row_off[r + 1] - A.row_off[r] : A.stride);
+        int64_t start = (int64_t)A.a_start[r] - A.p.padding;
+        if (start < 0) start = 0;
+        int64_t stop = (int64_t)A.a_end[r] + A.p.padding;
+        if (stop > row_len) stop = row_len;
+        if (stop - start <= kBigCap || stop - start > kLongCap) continue;
+        __syncthreads();
+        fp_process_read<BLOCK, false, true, true>(A, r, smem);
     }
 }
 
@@ -1618,6 +1665,26 @@ static size_t fp_lds_bytes_big(int cap) { return fp_lds_bytes(cap) - (size_t)cap
 
 int64_t fingerprint_big_bytes(int64_t max_len) {
     return max_len > kExactLdsCap ? (int64_t)kBigSlots * kBigCap * 8 : 0;
+}
+
+// the long form keeps no samples and no score curve in LDS, and always the dedicated state bytes
+static size_t fp_lds_bytes_long() { return fp_lds_bytes(kLongCap) - (size_t)kLongCap * (8 + 4); }
+static_assert(kLongCap > (kTile + kMaxW) * 16, "fp_lds_bytes counts the dedicated state bytes");
+
+int64_t fingerprint_long_bytes(int64_t max_len) { return max_len > kBigCap ? (int64_t)(kLongSlots * kLongSlotBytes) : 0; }
+
+static int launch_fp_long(FpArgs A, void *d_long, const unsigned *count, const int32_t *list, hipStream_t stream) {
+    static LdsAttr attr;
+    const size_t lds = fp_lds_bytes_long();
+    if (int rc = attr.ensure(fingerprint_long_kernel<1024>, lds)) return rc;
+    A.cap = kLongCap;
+    A.defer_big = 0;
+    A.big_scores = reinterpret_cast<double *>(d_long);
+    A.clip = nullptr;
+    const int64_t grid = A.n_reads < kLongSlots ? A.n_reads : kLongSlots;
+    hipLaunchKernelGGL((fingerprint_long_kernel<1024>), dim3((unsigned)grid), dim3(1024), lds, stream, A, count, list);
+    WDX_HIP_TRY(hipGetLastError());
+    return WDX_SUCCESS;
 }
 
 static int launch_fp_big(FpArgs A, int small_cap, const unsigned *count, const int32_t *list, hipStream_t stream) {

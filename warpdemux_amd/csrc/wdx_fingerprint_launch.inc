@@ -172,6 +172,7 @@ struct PlanFlags {
     bool prof;        // diagnostic build (d_prof)
     int stop_phase;
     bool has_big;     // the caller gave the buffer of fingerprint_big_bytes
+    bool has_long;    // ... and the one of fingerprint_long_bytes
     bool refine;      // consensus-refinement branch
     bool refine_ws;   // ... with the fast kernels' hand-over records (RefineDev::ws)
 };
@@ -182,6 +183,7 @@ struct FastPlan {
     size_t lds;
     bool small;       // 512 threads (else 1024)
     bool with_huge;   // fingerprint_big_kernel behind it
+    bool with_long;   // fingerprint_long_kernel behind that (WDX_OPT_LONG_WINDOWS)
     int exact_clip_cap;   // kExact: clip_bounds_kernel ahead of it for windows up to this many samples (0 = none)
     // the chain
     int combo, nbt;
@@ -223,6 +225,10 @@ static FastPlan plan_fast_chain(const wdx_seg_params &p, int64_t max_len, int64_
     // fingerprint_big_kernel at the end (needs the caller's fingerprint_big_bytes(max_len) buffer; without it they
     // are reported WDX_READ_FAIL_UNKNOWN as windows beyond WDX_MAX_ADAPTER_SAMPLES always are)
     pl.with_huge = max_len > kExactLdsCap && f.has_big && !f.prof;
+    // WDX_OPT_LONG_WINDOWS: windows of kBigCap+1 .. kLongCap samples are left alone in the same way and taken by
+    // fingerprint_long_kernel behind that (the caller's fingerprint_long_bytes(max_len) buffer).  Not the refinement branch:
+    // the exact kernel's in-place refine code reads the samples and the score curve where the other forms keep them
+    pl.with_long = knobs.long_windows && max_len > kBigCap && f.has_long && pl.with_huge && !f.refine;
     if (f.prof && !f.has_ws) {
         pl.path = FastPlan::kProfExact;
         return pl;
@@ -383,6 +389,7 @@ struct FpRun {
     hipStream_t stream;
     int64_t *n_launches;   // nullable
     MainEvents *ev;        // nullable
+    void *d_long;          // fingerprint_long_kernel's slots (pl.with_long)
     // a fast kernel's arguments: the exact kernel's list, everything else null or zero
     FastArgs fast_args(int capF, int capP) const {
         FastArgs F{};
@@ -590,6 +597,8 @@ static int stage_exact(FpRun &R) {
     }
     if (R.pl.with_huge)
         if (int rc = launch_fp_big(A, R.pl.cap, R.ws.count + kCntSlow, R.ws.slow, R.stream)) return rc;
+    if (R.pl.with_long)
+        if (int rc = launch_fp_long(A, R.d_long, R.ws.count + kCntSlow, R.ws.slow, R.stream)) return rc;
     return WDX_SUCCESS;
 }
 // WDX_OPT_DEBUG_OCCUPANCY: where the reads went (synchronises)
@@ -705,11 +714,11 @@ static int validate_fingerprint_call(int64_t n_reads, int64_t max_len, const wdx
 
 int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &out, hipStream_t stream, void *d_ws,
                        const Knobs &knobs, int64_t *n_launches, long long *d_prof, int64_t prof_reads, int stop_phase,
-                       const RefineDev *rf, MainEvents *main_ev, double *d_big) {
+                       const RefineDev *rf, MainEvents *main_ev, double *d_big, void *d_long) {
     if (in.n_reads == 0) return WDX_SUCCESS;
     if (int rc = validate_fingerprint_call(in.n_reads, in.max_len, p, rf)) return rc;
     LaunchSliceScope slice_scope(knobs.max_launch_slice);
-    const PlanFlags flags{d_ws != nullptr, d_prof != nullptr, stop_phase, d_big != nullptr, rf != nullptr, rf && rf->ws};
+    const PlanFlags flags{d_ws != nullptr, d_prof != nullptr, stop_phase, d_big != nullptr, d_long != nullptr, rf != nullptr, rf && rf->ws};
     const FastPlan pl = plan_fast_chain(p, in.max_len, in.n_reads, knobs, flags);
     if (pl.lds > 160 * 1024) {
         set_error("fingerprint LDS carve-up (%zu B) exceeds 160 KiB", pl.lds);
@@ -721,9 +730,9 @@ int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &
     }
     (void)hipGetLastError();  // do not inherit a stale error from an earlier failed call
     FpRun R{FpArgs{in.sig, in.row_off, in.row_len, in.stride, in.n_reads, in.a_start, in.a_end, in.ok, p, out.fpt, out.dwell, out.stats,
-                   out.status, pl.cap, 0, d_prof, prof_reads, stop_phase, 1, rf ? *rf : RefineDev{}, d_big, pl.with_huge ? 1 : 0,
-                   knobs.exact_no_list ? 1 : 0},
-            pl, FpWorkspace(d_ws, in.n_reads), stream, n_launches, main_ev};
+                   out.status, pl.cap, 0, d_prof, prof_reads, stop_phase, 1, rf ? *rf : RefineDev{}, d_big,
+                   pl.with_long ? kLongCap : (pl.with_huge ? kBigCap : 0), knobs.exact_no_list ? 1 : 0},
+            pl, FpWorkspace(d_ws, in.n_reads), stream, n_launches, main_ev, d_long};
     const uint64_t e1 = (uint64_t)(p.num_events > 0 ? p.num_events : 1);
     R.A.e_magic1 = (unsigned)std::min<uint64_t>(((1ull << 32) + e1 - 1) / e1, 0xffffffffull);   // (E = 1: 2^32 - 1 -> q = n - 1, rounded up to n)
     R.A.e_magic2 = (unsigned)(((1ull << 32) + 2 * e1 - 1) / (2 * e1));
@@ -743,6 +752,8 @@ int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &
     if (int rc = pl.small ? launch_fp_chunks<512, false>(R.A, pl.lds, stream, n_launches)
                           : launch_fp_chunks<1024, false>(R.A, pl.lds, stream, n_launches))
         return rc;
-    if (pl.with_huge) return launch_fp_big(R.A, pl.cap, nullptr, nullptr, stream);
+    if (pl.with_huge)
+        if (int rc = launch_fp_big(R.A, pl.cap, nullptr, nullptr, stream)) return rc;
+    if (pl.with_long) return launch_fp_long(R.A, d_long, nullptr, nullptr, stream);
     return WDX_SUCCESS;
 }

@@ -64,8 +64,10 @@ struct FpArgs {
     int stop_phase;      // diagnostic build only: leave the fast kernel after this phase (0 = run all)
     int exact_scores;    // fast kernel: exact t-scores from the first attempt (WDX_OPT_FAST_EXACT_SCORES)
     RefineDev rf;        // rf.query != nullptr: consensus-refinement branch (exact kernel only)
-    double *big_scores;  // kBigSlots x kBigCap doubles: score curves of windows beyond the LDS capacity (nullable)
-    int defer_big;       // 1: a window beyond `cap` is left to fingerprint_big_kernel (no status written here)
+    double *big_scores;  // kBigSlots x kBigCap doubles: score curves of windows beyond the LDS capacity (nullable);
+                         // fingerprint_long_kernel: its kLongSlots slots (score curve + samples) instead
+    int defer_big;       // > 0: a window beyond `cap` of up to this many samples is left to fingerprint_big_kernel /
+                         // fingerprint_long_kernel (no status written here): 0, kBigCap or kLongCap
     int no_list;         // WDX_OPT_EXACT_NO_PEAK_LIST: fp_segment in position space only (diagnostic)
     int refine_record;   // exact kernel, refinement branch: 1 = leave a RefineRec for the refinement kernels where the read
                          // allows it (no NaN in the window, configured window width) instead of refining in place
@@ -76,10 +78,10 @@ struct FpArgs {
 };
 
 // (int)rint((double)n / (double)den) -- the reference's `round(n / den)` (sig_proc.py:526-533; banker's rounding) -- in integer
-// arithmetic: magic = ceil(2^32 / den) gives the exact quotient for n * den < 2^32 (n <= 16 384 samples, den <= 2 * 253), and the
+// arithmetic: magic = ceil(2^32 / den) gives the exact quotient for n * den < 2^32 (n <= 65 536 samples, den <= 2 * 253: 3.3e7), and the
 // double quotient can only differ from the rational one's rounding within 2^-53 of a tie, which is exact or >= 1 / (2 den) away.
 // n is uniform: scalar instructions (s_mul_hi_u32) instead of a float64 division expanded on the vector ALU by every lane
-// (checked against the float form for every den <= 506, n < 20 000).
+// (checked against the float form for every den <= 506, n <= 65 536).
 __device__ __forceinline__ int rdiv_half_even(unsigned n, unsigned den, unsigned magic) {
     unsigned q = __umulhi(n, magic);
     const unsigned rem2 = 2u * (n - q * den);

@@ -41,7 +41,7 @@ class DemuxEngine:
     (model._X in the reference, models/dtw_base.py:20)."""
 
     def __init__(self, refs: np.ndarray, window: Optional[int] = 15, penalty: Optional[float] = 0.1,
-                 params: Optional[SegParams] = None, device: int = 0):
+                 params: Optional[SegParams] = None, device: int = 0, long_windows: bool = False):
         torch = _torch()
         if not torch.cuda.is_available():
             raise _lib.WdxError("DemuxEngine needs a visible MI355X (torch.cuda.is_available() is False)")
@@ -49,6 +49,8 @@ class DemuxEngine:
         self.device = int(device)
         self.tdev = torch.device("cuda", self.device)
         self.ctx = _lib.Context(self.device)
+        if long_windows:   # adapter windows of up to 65 536 samples on the plain entries (WDX_OPT_LONG_WINDOWS)
+            self.ctx.set_option(_lib.OPT_LONG_WINDOWS, 1)
         self.L = _lib.load()
         self.params = params or SegParams(barcode_num_events=int(np.asarray(refs).shape[1]))
         self.set_refs(refs, window, penalty)

@@ -68,11 +68,14 @@ class LiveDemux:
     ``adc``: :meth:`tick_adc` works on ANY LiveDemux; ``adc=True`` only makes the constructor's warm-up tick an int16 one,
     so that the int16 staging buffers too are allocated before the run starts.
 
+    ``long_windows``: plain ticks fingerprint adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS), int16 ones
+    included; refined ticks keep the limit of 16 384.
+
     Every check of the arguments happens before a context is created and raises ``ValueError``."""
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, *, model=None,
                  refine: Optional[RefineParams] = None, adc: bool = False, device: int = 0, max_reads: int = 512,
-                 max_samples: int = 10000):
+                 max_samples: int = 10000, long_windows: bool = False):
         d = _marshal.deployment(
             refs, window, penalty, params, model, refine, who="LiveDemux", models=("DTW_SVM", "DTW_MLP", "Fpt_Boost"),
             bare_refine=False, refine_dtw=False,
@@ -84,6 +87,8 @@ class LiveDemux:
 
         self.L = _lib.load()
         self.ctx = _lib.Context(device)      # this object's own context = own stream + staging buffers
+        if long_windows:
+            self.ctx.set_option(_lib.OPT_LONG_WINDOWS, 1)
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:

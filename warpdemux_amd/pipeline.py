@@ -111,12 +111,13 @@ class MinibatchPipeline:
     MAX_SLOTS for a feeder process that serves many producers.  ``refine``: every minibatch takes the
     consensus-refinement branch (K = ``refine.barcode_keep_events``); then ``refs`` may be None (fingerprints only).
     ``model``: a `models.Fpt_Boost` kept resident on the device; every minibatch brings its prediction back
-    (`BoostMinibatch`), ``refs`` may be None, and K must equal ``model.n_features``."""
+    (`BoostMinibatch`), ``refs`` may be None, and K must equal ``model.n_features``.
+    ``long_windows``: plain minibatches fingerprint adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS)."""
 
     N_SLOTS = 2
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, device: int = 0,
-                 n_slots: int = 2, refine: Optional[RefineParams] = None, model=None):
+                 n_slots: int = 2, refine: Optional[RefineParams] = None, model=None, long_windows: bool = False):
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
         self.N_SLOTS = int(n_slots)
@@ -127,6 +128,8 @@ class MinibatchPipeline:
         self.refine, self.model, self.params, self.nY, self.K, self._n_classes = refine, model, d.params, d.nY, d.K, d.n_classes
         self.L = _lib.load()
         self.ctx = _lib.Context(device)
+        if long_windows:   # (every slot copies the context's options at its submit; 12 MB per slot that meets a long window)
+            self.ctx.set_option(_lib.OPT_LONG_WINDOWS, 1)
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:

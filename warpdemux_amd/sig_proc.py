@@ -21,6 +21,7 @@ import numpy as np
 from . import _lib, _marshal
 
 MAX_ADAPTER_SAMPLES = 16384   # WDX_MAX_ADAPTER_SAMPLES (include/wdx.h)
+MAX_LONG_ADAPTER_SAMPLES = 65536   # WDX_MAX_LONG_ADAPTER_SAMPLES: with ``long_windows=True`` (WDX_OPT_LONG_WINDOWS)
 
 # status code -> ReadResult.fail_reason (reference strings: sig_proc.py:400-407, 440-446, 538-544,
 # 554-560; file_proc.py:224).  Codes 2 and 4 carry the exception text in the reference; the only
@@ -57,8 +58,10 @@ class SegParams:
     clip_bounds: str = "auto"
 
     @classmethod
-    def from_spc(cls, spc) -> "SegParams":
-        """From a reference-style SigProcConfig (attribute access as in sig_proc.py:414-534)."""
+    def from_spc(cls, spc, long_windows: bool = False) -> "SegParams":
+        """From a reference-style SigProcConfig (attribute access as in sig_proc.py:414-534).  ``long_windows``: the
+        configuration is meant for objects and calls with ``long_windows=True``, which take adapter windows of up to
+        WDX_MAX_LONG_ADAPTER_SAMPLES = 65 536 samples (plain branch only)."""
         seg = spc.segmentation
         k = seg.barcode_num_events
         if getattr(seg, "consensus_refinement", False):
@@ -71,13 +74,16 @@ class SegParams:
         # The engine takes adapter windows of at most WDX_MAX_ADAPTER_SAMPLES = 16 384 samples (the shipped configs admit
         # max_obs_trace + 2 * padding = 10 200 / 15 200); the reference has no such limit (sig_proc.py:382-391).  A
         # configuration that admits longer windows (`--export core.max_obs_trace=...`) is refused HERE, once, instead of
-        # every such read coming back "unknown" from the kernels.
+        # every such read coming back "unknown" from the kernels.  With ``long_windows`` the limit is
+        # WDX_MAX_LONG_ADAPTER_SAMPLES = 65 536.
         mot = getattr(getattr(spc, "core", None), "max_obs_trace", None)
-        if isinstance(mot, (int, np.integer)) and int(mot) + 2 * int(spc.sig_extract.padding) > MAX_ADAPTER_SAMPLES:
+        limit, limit_name = ((MAX_LONG_ADAPTER_SAMPLES, "WDX_MAX_LONG_ADAPTER_SAMPLES") if long_windows else
+                             (MAX_ADAPTER_SAMPLES, "WDX_MAX_ADAPTER_SAMPLES"))
+        if isinstance(mot, (int, np.integer)) and int(mot) + 2 * int(spc.sig_extract.padding) > limit:
             raise NotImplementedError(
                 f"core.max_obs_trace = {int(mot)} with padding {int(spc.sig_extract.padding)} admits adapter windows of "
-                f"{int(mot) + 2 * int(spc.sig_extract.padding)} samples; the HIP engine takes at most {MAX_ADAPTER_SAMPLES} "
-                "(WDX_MAX_ADAPTER_SAMPLES)")
+                f"{int(mot) + 2 * int(spc.sig_extract.padding)} samples; the HIP engine takes at most {limit} "
+                f"({limit_name})")
         return cls(
             padding=int(spc.sig_extract.padding),
             sig_norm=str(spc.sig_extract.normalization),
@@ -226,15 +232,18 @@ def fingerprints(o: dict) -> FingerprintBatch:
     return FingerprintBatch(o["fpt"], o["dwell"], o["stats"], o["status"], o["refine_idx"])
 
 
-def fingerprint_batch(signals, adapter_start, adapter_end, params: SegParams, success=None, device=None) -> FingerprintBatch:
-    """Fingerprint a (n_reads, stride) float32 minibatch (file_proc.py:244-260 layout, NaN tail)."""
+def fingerprint_batch(signals, adapter_start, adapter_end, params: SegParams, success=None, device=None,
+                      long_windows: bool = False) -> FingerprintBatch:
+    """Fingerprint a (n_reads, stride) float32 minibatch (file_proc.py:244-260 layout, NaN tail).  ``long_windows``:
+    adapter windows of up to MAX_LONG_ADAPTER_SAMPLES samples for this call (WDX_OPT_LONG_WINDOWS on the default context,
+    put back afterwards); the default reports windows beyond MAX_ADAPTER_SAMPLES as failed ("unknown")."""
     sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
     pc = params.to_c()
     o = _marshal.outputs(n, params.barcode_num_events, 0, 0, _FPT_WANT)
-    ctx = _lib.default_context(device)
-    _lib.check(_lib.load().wdx_fingerprint_batch(
-        ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc), _lib.ptr(o["fpt"]),
-        _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["status"])))
+    with _lib.default_context(device).long_windows_for_call(long_windows) as ctx:
+        _lib.check(_lib.load().wdx_fingerprint_batch(
+            ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc), _lib.ptr(o["fpt"]),
+            _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["status"])))
     return fingerprints(o)
 
 
@@ -284,15 +293,15 @@ def adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, succe
 
 
 def fingerprint_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, params: SegParams, success=None,
-                          device=None) -> FingerprintBatch:
+                          device=None, long_windows: bool = False) -> FingerprintBatch:
     """`fingerprint_batch` for a (n_reads, stride) int16 ADC minibatch: 2 bytes per sample over the bus, calibrated on the
     device.  Bit-identical to ``fingerprint_batch(calibrate_adc(adc, row_len, offset, scale), ...)``."""
     desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success)
     pc = params.to_c()
     o = _marshal.outputs(n, params.barcode_num_events, 0, 0, _FPT_WANT)
-    ctx = _lib.default_context(device)
-    _lib.check(_lib.load().wdx_fingerprint_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), _lib.ptr(o["fpt"]),
-                                                     _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["status"])))
+    with _lib.default_context(device).long_windows_for_call(long_windows) as ctx:
+        _lib.check(_lib.load().wdx_fingerprint_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), _lib.ptr(o["fpt"]),
+                                                         _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["status"])))
     del kept
     return fingerprints(o)
 
@@ -361,7 +370,7 @@ def _demux_want(want_dist, want_fpt) -> int:
 
 
 def demux_batch(signals, adapter_start, adapter_end, params: SegParams, success=None, want_dist=True,
-                want_fpt=False, n_refs=None, device=None) -> DemuxBatch:
+                want_fpt=False, n_refs=None, device=None, long_windows: bool = False) -> DemuxBatch:
     """One call per minibatch / live tick: fingerprints, distances to the resident references
     (`set_references`) and the nearest-reference call, with a single device synchronisation."""
     sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
@@ -369,14 +378,15 @@ def demux_batch(signals, adapter_start, adapter_end, params: SegParams, success=
     ctx = _lib.default_context(device)
     n_held = _held_references(ctx, "demux_batch", n_refs)
     o = _marshal.outputs(n, params.barcode_num_events, n_held, 0, _demux_want(want_dist, want_fpt))
-    _lib.check(_lib.load().wdx_demux_batch(
-        ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc),
-        n_held, _lib.ptr(o["fpt"]), _lib.ptr(o["dist"]), _lib.ptr(o["call"]), _lib.ptr(o["status"])))
+    with ctx.long_windows_for_call(long_windows):
+        _lib.check(_lib.load().wdx_demux_batch(
+            ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc),
+            n_held, _lib.ptr(o["fpt"]), _lib.ptr(o["dist"]), _lib.ptr(o["call"]), _lib.ptr(o["status"])))
     return DemuxBatch(o["status"], o["call"], o["dist"], o["fpt"])
 
 
 def demux_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, params: SegParams, success=None, want_dist=True,
-                    want_fpt=False, device=None) -> DemuxBatch:
+                    want_fpt=False, device=None, long_windows: bool = False) -> DemuxBatch:
     """`demux_batch` for a (n_reads, stride) int16 ADC minibatch (wdx_demux_batch_adc); bit-identical to `demux_batch` on
     ``calibrate_adc(adc, row_len, offset, scale)``."""
     desc, n, kept = adc_minibatch(adc, row_len, offset, scale, adapter_start, adapter_end, success)
@@ -384,18 +394,21 @@ def demux_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, par
     ctx = _lib.default_context(device)
     n_held = _held_references(ctx, "demux_batch_adc")
     o = _marshal.outputs(n, params.barcode_num_events, n_held, 0, _demux_want(want_dist, want_fpt))
-    _lib.check(_lib.load().wdx_demux_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), n_held, _lib.ptr(o["fpt"]),
-                                               _lib.ptr(o["dist"]), _lib.ptr(o["call"]), _lib.ptr(o["status"])))
+    with ctx.long_windows_for_call(long_windows):
+        _lib.check(_lib.load().wdx_demux_batch_adc(ctx.handle, C.byref(desc), C.byref(pc), n_held, _lib.ptr(o["fpt"]),
+                                                   _lib.ptr(o["dist"]), _lib.ptr(o["call"]), _lib.ptr(o["status"])))
     del kept
     return DemuxBatch(o["status"], o["call"], o["dist"], o["fpt"])
 
 
 def detect_results_to_fpt_batch(calibrated_signals, spc, detect_results: Sequence, read_ids: Optional[Sequence[str]] = None,
-                                device=None, consensus_query=None) -> List[ReadResult]:
+                                device=None, consensus_query=None, long_windows: bool = False) -> List[ReadResult]:
     """Batched `detect_results_to_fpt`: one ReadResult per row, identical fields to the reference's
     per-read call (sig_proc.py:590-605) plus the `barcode_fpt_wrapper` read-id (file_proc.py:216).  With
-    ``spc.segmentation.consensus_refinement`` the caller passes the consensus signal like the reference does."""
-    params = SegParams.from_spc(spc)
+    ``spc.segmentation.consensus_refinement`` the caller passes the consensus signal like the reference does.
+    ``long_windows``: a configuration with ``core.max_obs_trace`` + 2 x padding up to MAX_LONG_ADAPTER_SAMPLES is accepted and
+    its long windows are fingerprinted (plain branch; the refinement branch keeps MAX_ADAPTER_SAMPLES)."""
+    params = SegParams.from_spc(spc, long_windows=long_windows)
     refine = None
     if getattr(spc.segmentation, "consensus_refinement", False):
         if consensus_query is None or np.asarray(consensus_query).size == 0:
@@ -406,7 +419,7 @@ def detect_results_to_fpt_batch(calibrated_signals, spc, detect_results: Sequenc
     a_s = np.array([d.adapter_start if (d.success and d.adapter_start is not None) else 0 for d in detect_results], dtype=np.int32)
     a_e = np.array([d.adapter_end if (d.success and d.adapter_end is not None) else 0 for d in detect_results], dtype=np.int32)
     if refine is None:
-        fb = fingerprint_batch(calibrated_signals, a_s, a_e, params, success=ok, device=device)
+        fb = fingerprint_batch(calibrated_signals, a_s, a_e, params, success=ok, device=device, long_windows=long_windows)
     else:
         fb = fingerprint_refine_batch(calibrated_signals, a_s, a_e, params, refine, success=ok, device=device)
     return read_results_from_batch(fb, detect_results, read_ids, refined=refine is not None)
