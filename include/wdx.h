@@ -73,8 +73,8 @@ extern "C" {
  *   padding             >= 0       negative  -> WDX_ERR_INVALID
  *   min_obs_per_base    any        below 1 every read fails with WDX_READ_FAIL_UNKNOWN (scipy refuses distance 0)
  * Adapter windows (padding included) longer than WDX_MAX_ADAPTER_SAMPLES come back WDX_READ_FAIL_UNKNOWN -- on a context
- * with WDX_OPT_LONG_WINDOWS = 1, longer than WDX_MAX_LONG_ADAPTER_SAMPLES (plain branch; the refinement branch keeps the
- * smaller limit). */
+ * with WDX_OPT_LONG_WINDOWS = 1 (plain branch) / WDX_OPT_LONG_REFINE_WINDOWS = 1 (consensus-refinement branch), longer
+ * than WDX_MAX_LONG_ADAPTER_SAMPLES. */
 typedef struct wdx_seg_params {
     int32_t padding;            /* sig_extract.padding                                          */
     int32_t sig_norm;           /* sig_extract.normalization   (WDX_NORM_*)                     */
@@ -146,11 +146,24 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
  * WDX_ERR_INVALID.  Every entry that fingerprints on this context honours it -- wdx_fingerprint_batch[_adc],
  * wdx_fingerprint_dev, wdx_demux_batch[_adc], wdx_demux_dev, wdx_demux_svm_dev / _mlp_dev / _boost_dev,
  * wdx_demux_submit[_ex|_adc] (a pipeline slot copies the options at every submit), a feeder served by this
- * context, wdx_live_tick[_ex] -- with two exceptions: the consensus-refinement branch (wdx_*_refine*, rp != NULL) and
- * wdx_fingerprint_profile_dev keep the limit of WDX_MAX_ADAPTER_SAMPLES.  Cost: 12 MiB of device memory per context
+ * context, wdx_live_tick[_ex] -- with two exceptions: the consensus-refinement branch (wdx_*_refine*, rp != NULL) does not
+ * look at this option but at WDX_OPT_LONG_REFINE_WINDOWS, and wdx_fingerprint_profile_dev keeps the limit of
+ * WDX_MAX_ADAPTER_SAMPLES.  Cost: 12 MiB of device memory per context
  * (16 slots of 768 KiB), allocated by the first call that meets such a window with the option on (a synchronising
  * hipMalloc on that one call) and never otherwise; each pipeline slot that meets one owns its own (96 MiB for 8). */
 #define WDX_OPT_LONG_WINDOWS 20
+/* The same product option for the consensus-refinement branch (the flow of the tRNA models), independent of the one above:
+ * a call with rp != NULL looks at this option only, a plain call at WDX_OPT_LONG_WINDOWS only.  0 (default): a refined
+ * adapter window beyond WDX_MAX_ADAPTER_SAMPLES is reported WDX_READ_FAIL_UNKNOWN.  1: windows up to
+ * WDX_MAX_LONG_ADAPTER_SAMPLES are segmented, matched against the consensus and their barcode tail -- of any length inside
+ * the window -- segmented again, in place, by the long form of the exact kernel, bit for bit like the shorter ones; longer
+ * ones are reported WDX_READ_FAIL_UNKNOWN.  Any other value: WDX_ERR_INVALID.  Honoured by wdx_fingerprint_refine_batch,
+ * wdx_fingerprint_refine_dev, wdx_demux_refine_dev, wdx_demux_boost_dev with rp, wdx_demux_submit_refine (float32 and int16
+ * descriptors; a pipeline slot copies the options at every submit), a refine feeder ring served by this context and
+ * wdx_live_tick_ex with rp (an int16 tick's staging cuts at the cap of the branch the tick runs, plus one).  The slots are
+ * the ones of WDX_OPT_LONG_WINDOWS (12 MiB per context or pipeline slot, allocated by the first call that meets such a
+ * window with the option of its branch on, never otherwise). */
+#define WDX_OPT_LONG_REFINE_WINDOWS 21
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -199,7 +212,7 @@ int wdx_fingerprint_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64
  *   d_row_len == NULL  -> row_len[r] = d_row_off ? d_row_off[r+1]-d_row_off[r] : stride
  * (so a packed batch passes int64 offsets[n_reads+1] and NULL lengths).  max_len bounds the
  * adapter window of every read (it sizes the LDS carve-up); windows longer than max_len or than
- * WDX_MAX_ADAPTER_SAMPLES (WDX_OPT_LONG_WINDOWS = 1: than WDX_MAX_LONG_ADAPTER_SAMPLES, see there) are reported
+ * WDX_MAX_ADAPTER_SAMPLES (WDX_OPT_LONG_WINDOWS / WDX_OPT_LONG_REFINE_WINDOWS = 1: than WDX_MAX_LONG_ADAPTER_SAMPLES, see there) are reported
  * WDX_READ_FAIL_UNKNOWN.  (The largest window the reference admits is
  * max_obs_trace + 2*padding = 15 200 samples, DEPRECATED/config_files/rna002_70bps@v0.4.4.toml:2; up to 11 200
  * samples a read's score curve lives in LDS, beyond that in a context-owned HBM block of 32 MiB that is
@@ -212,7 +225,7 @@ int wdx_fingerprint_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
                         int64_t *d_dwell, double *d_stats, int32_t *d_status, void *stream);
 
 #define WDX_MAX_ADAPTER_SAMPLES 16384
-#define WDX_MAX_LONG_ADAPTER_SAMPLES 65536 /* with WDX_OPT_LONG_WINDOWS = 1 */
+#define WDX_MAX_LONG_ADAPTER_SAMPLES 65536 /* with WDX_OPT_LONG_WINDOWS = 1 (refinement: WDX_OPT_LONG_REFINE_WINDOWS = 1) */
 
 /* ---- N3: consensus-guided barcode refinement (tRNA models) -- detect_results_to_fpt with
  *      segmentation.consensus_refinement = True (sig_proc.py:257-378, 452-521): segment the adapter, find the

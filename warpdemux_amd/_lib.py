@@ -44,6 +44,7 @@ OPT_MLP_CHUNK_ROWS = 17
 OPT_BOOST_CHUNK_ROWS = 18
 OPT_BOOST_KERNEL = 19   # 0 by batch size | 1 lane-per-read | 2 tree-parallel
 OPT_LONG_WINDOWS = 20   # product option: 1 = adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (0 / 1, else ValueError)
+OPT_LONG_REFINE_WINDOWS = 21   # ... the same for the consensus-refinement branch, which looks at this option only
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -537,6 +538,7 @@ class Context:
         self.device = int(device)
         self.pid = os.getpid()
         self.long_windows = False
+        self.long_refine_windows = False
 
     @property
     def handle(self):
@@ -547,11 +549,19 @@ class Context:
         return self._h
 
     def set_option(self, option: int, value: int = 1):
-        """Diagnostic switch (wdx_ctx_set_option); tests and profiling tools only -- and OPT_LONG_WINDOWS, which the
-        ``long_windows=`` keyword of the classes and module-level calls sets."""
+        """Diagnostic switch (wdx_ctx_set_option); tests and profiling tools only -- and OPT_LONG_WINDOWS /
+        OPT_LONG_REFINE_WINDOWS, which the ``long_windows=`` keyword of the classes and module-level calls sets."""
         check(self._L.wdx_ctx_set_option(self.handle, int(option), int(value)))
         if int(option) == OPT_LONG_WINDOWS:
             self.long_windows = bool(value)
+        elif int(option) == OPT_LONG_REFINE_WINDOWS:
+            self.long_refine_windows = bool(value)
+
+    def set_long_windows(self):
+        """Both product options on: what an object that owns its context does for ``long_windows=True`` -- its plain calls
+        look at OPT_LONG_WINDOWS, its refining ones at OPT_LONG_REFINE_WINDOWS."""
+        self.set_option(OPT_LONG_WINDOWS, 1)
+        self.set_option(OPT_LONG_REFINE_WINDOWS, 1)
 
     @contextlib.contextmanager
     def long_windows_for_call(self, on: bool):
@@ -565,6 +575,19 @@ class Context:
         finally:
             if bool(on) != before:
                 self.set_option(OPT_LONG_WINDOWS, int(before))
+
+    @contextlib.contextmanager
+    def long_refine_windows_for_call(self, on: bool):
+        """`long_windows_for_call` for a call of the consensus-refinement branch: OPT_LONG_REFINE_WINDOWS = ``on`` for its
+        duration, then what it was before -- also when the call raises."""
+        before = getattr(self, "long_refine_windows", False)
+        if bool(on) != before:
+            self.set_option(OPT_LONG_REFINE_WINDOWS, int(bool(on)))
+        try:
+            yield self
+        finally:
+            if bool(on) != before:
+                self.set_option(OPT_LONG_REFINE_WINDOWS, int(before))
 
     def synchronize(self, stream=None):
         check(self._L.wdx_ctx_synchronize(self.handle, stream))

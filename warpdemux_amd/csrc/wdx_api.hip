@@ -188,7 +188,7 @@ int use_stream(wdx_ctx *ctx, hipStream_t s) {
 int fingerprint_stage(wdx_ctx *B, const FpReads &in, const wdx_seg_params &p, const FpOut &out, void *d_ws,
                       hipStream_t s, const RefineDev *rf, bool main_events) {
     if (int rc = B->fp_big.ensure((size_t)fingerprint_big_bytes(in.max_len))) return rc;
-    const bool with_long = B->knobs.long_windows && !rf && fingerprint_long_bytes(in.max_len) > 0;
+    const bool with_long = B->knobs.long_form(rf != nullptr) && fingerprint_long_bytes(in.max_len) > 0;
     if (with_long)
         if (int rc = B->fp_long.ensure((size_t)fingerprint_long_bytes(in.max_len))) return rc;
     Timed t(B, WDX_K_FINGERPRINT, s);
@@ -528,6 +528,13 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
                 return WDX_ERR_INVALID;
             }
             ctx->knobs.long_windows = value == 1;
+            break;
+        case WDX_OPT_LONG_REFINE_WINDOWS:
+            if (value != 0 && value != 1) {
+                set_error("WDX_OPT_LONG_REFINE_WINDOWS is 0 or 1, not %lld", (long long)value);
+                return WDX_ERR_INVALID;
+            }
+            ctx->knobs.long_refine_windows = value == 1;
             break;
         default:
             set_error("unknown option %d", (int)option);

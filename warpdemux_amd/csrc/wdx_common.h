@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/wdx.h"
+#include "wdx_window.h"
 
 namespace wdx {
 
@@ -45,8 +46,11 @@ struct Knobs {
     int64_t boost_chunk_rows = 0;    // WDX_OPT_BOOST_CHUNK_ROWS: rows per pass of wdx_boost_predict (0 = built-in)
     int boost_kernel = 0;            // WDX_OPT_BOOST_KERNEL: 0 by batch size | 1 lane-per-read | 2 tree-parallel
     bool long_windows = false;       // WDX_OPT_LONG_WINDOWS: adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (product option)
-    // the longest adapter window this context fingerprints (the host loops cut one sample beyond it: that reports it)
-    int64_t max_window() const { return long_windows ? WDX_MAX_LONG_ADAPTER_SAMPLES : WDX_MAX_ADAPTER_SAMPLES; }
+    bool long_refine_windows = false;   // WDX_OPT_LONG_REFINE_WINDOWS: the same for the consensus-refinement branch (product option)
+    // the long form of the exact kernel serves this call (wdx_window.h: the refinement branch has its own option)
+    bool long_form(bool refine) const { return long_form_on(refine, long_windows, long_refine_windows); }
+    // the longest adapter window a call of this branch fingerprints (the host loops cut one sample beyond it: that reports it)
+    int64_t max_window(bool refine) const { return max_adapter_window(refine, long_windows, long_refine_windows); }
 };
 
 // A launch over more workgroups than grid.x admits is cut into slices (block_base != 0 from the second on).  The built-in

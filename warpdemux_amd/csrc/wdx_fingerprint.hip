@@ -484,16 +484,19 @@ __device__ int fp_segment(const double *scores, unsigned char *state, const int 
     int nsel;
     bool use_list;
     int np = 0, lbase = 0;
-    using LBits = typename std::conditional<WIDE, unsigned long long, unsigned>::type;
-    constexpr int kLBits = WIDE ? 64 : 32;
+    // (WIDE at 512 threads -- the refining long kernel -- : up to 128 positions, two 64-bit words)
+    constexpr int kLBits = WIDE ? (BLOCK >= 1024 ? 64 : 128) : 32;
+    using LBits = typename std::conditional<!WIDE, unsigned,
+                                            typename std::conditional<kLBits == 64, unsigned long long, unsigned __int128>::type>::type;
     LBits lbits = 0;
-    const int lchunk = (ns + BLOCK - 1) / BLOCK;  // <= 32: cap <= 16 384, BLOCK >= 512 (WIDE: <= 64, cap <= 65 536, BLOCK = 1024)
+    const int lchunk = (ns + BLOCK - 1) / BLOCK;  // <= 32: cap <= 16 384, BLOCK >= 512 (WIDE: <= 64 at 1024 threads, <= 128 at 512; cap <= 65 536)
     const int lc0 = tid * lchunk;
     {
         const int lc1 = min(ns, lc0 + lchunk);
         for (int i = lc0; i < lc1; ++i) lbits |= (LBits)(state[i] == ST_UNDECIDED ? 1u : 0u) << (i - lc0);
         int lcount;
-        if constexpr (WIDE) lcount = __popcll(lbits);
+        if constexpr (kLBits == 128) lcount = __popcll((unsigned long long)lbits) + __popcll((unsigned long long)(lbits >> 64));
+        else if constexpr (WIDE) lcount = __popcll(lbits);
         else lcount = __popc(lbits);
         lbase = block_excl_scan<BLOCK>(lcount, sh, np);  // (its barriers: every state byte has been read)
         use_list = !no_list && lchunk <= kLBits && 3 * np + 8 <= ns;
@@ -506,7 +509,10 @@ __device__ int fp_segment(const double *scores, unsigned char *state, const int 
             LBits b = lbits;
             while (b) {
                 int j;
-                if constexpr (WIDE) j = __ffsll((unsigned long long)b) - 1;
+                if constexpr (kLBits == 128) {
+                    const unsigned long long b_lo = (unsigned long long)b;
+                    j = b_lo ? __ffsll(b_lo) - 1 : 63 + __ffsll((unsigned long long)(b >> 64));
+                } else if constexpr (WIDE) j = __ffsll((unsigned long long)b) - 1;
                 else j = __ffs((int)b) - 1;
                 b &= b - 1;
                 lpos[o] = (unsigned short)(lc0 + j);
@@ -1010,7 +1016,8 @@ __device__ bool fp_refine_match(const FpArgs &A, const int64_t r, const int *cpt
     return true;
 }
 
-template <int BLOCK, class Prep>
+// WIDE: the long form -- the barcode tail can exceed 16 384 positions, so fp_segment takes its 64-bit chunk masks
+template <int BLOCK, bool WIDE = false, class Prep>
 __device__ void fp_refine_finish(const FpArgs &A, const int64_t r, const RefineMatch &M, unsigned char *state, const int ns,
                                  const int n, int *cpts, double *zz, unsigned *hist, FpShared &sh, Prep prep,
                                  const bool exact_sums = false) {
@@ -1050,12 +1057,12 @@ __device__ void fp_refine_finish(const FpArgs &A, const int64_t r, const RefineM
         // compute_base_means indexes out of bounds -> exception -> "unknown"; checked BEFORE the means are summed
         if (n_end2 != n - sbs) {
             // still "event segmentation failed" when the tail has too few peaks (that return comes first)
-            const int st0 = fp_segment<BLOCK>(sc_t, state, ns2, P.min_obs_per_base, P.running_stat_width, R.E2,
+            const int st0 = fp_segment<BLOCK, WIDE>(sc_t, state, ns2, P.min_obs_per_base, P.running_stat_width, R.E2,
                                               false, sg_t, min(n_end2, n - sbs), cpts, zz, hist, sh, nseg2, it2, A.no_list != 0);
             finish(st0 == WDX_READ_FAIL_SEGMENT ? WDX_READ_FAIL_SEGMENT : WDX_READ_FAIL_UNKNOWN, false);
             return;
         }
-        const int st = fp_segment<BLOCK>(sc_t, state, ns2, P.min_obs_per_base, P.running_stat_width, R.E2, false,
+        const int st = fp_segment<BLOCK, WIDE>(sc_t, state, ns2, P.min_obs_per_base, P.running_stat_width, R.E2, false,
                                          sg_t, n_end2, cpts, zz, hist, sh, nseg2, it2, A.no_list != 0, exact_sums);
         if (st != WDX_READ_OK) {
             finish(st, false);
@@ -1097,7 +1104,7 @@ __device__ void fp_refine_finish(const FpArgs &A, const int64_t r, const RefineM
 }
 
 
-template <int BLOCK, class Prep>
+template <int BLOCK, bool WIDE = false, class Prep>
 __device__ void fp_refine_tail(const FpArgs &A, const int64_t r, unsigned char *state,
                                const int ns, const int W, const int n, int *cpts, double *ev,
                                double *zz, double *tmp, unsigned char *scratch, unsigned *hist, FpShared &sh,
@@ -1105,7 +1112,7 @@ __device__ void fp_refine_tail(const FpArgs &A, const int64_t r, unsigned char *
     (void)W;
     RefineMatch M;
     if (!fp_refine_match<BLOCK>(A, r, cpts, ev, zz, tmp, scratch, sh, nseg, M)) return;
-    fp_refine_finish<BLOCK>(A, r, M, state, ns, n, cpts, zz, hist, sh, prep);
+    fp_refine_finish<BLOCK, WIDE>(A, r, M, state, ns, n, cpts, zz, hist, sh, prep);
 }
 
 // ---- the kernel -----------------------------------------------------------------------------------
@@ -1121,9 +1128,12 @@ __device__ void fp_refine_tail(const FpArgs &A, const int64_t r, unsigned char *
         }                                                                                   \
     } while (0)
 
-template <int BLOCK, bool PROF, bool BIG = false, bool LONG = false>
+// LONG_REFINE: the long form that also refines in place (fingerprint_long_refine_kernel; the plain long kernel is never
+// sent a refining call and is compiled without that code: its registers are the plain branch's)
+template <int BLOCK, bool PROF, bool BIG = false, bool LONG = false, bool LONG_REFINE = false>
 __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char *smem) {
     static_assert(!LONG || (BIG && !PROF), "the long form is the big form with the samples in the slot as well");
+    static_assert(!LONG_REFINE || LONG, "the refining long form is a long form");
     const int tid = threadIdx.x;
     const wdx_seg_params &P = A.p;
     const int K = P.barcode_num_events;
@@ -1348,12 +1358,16 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
         }
     }
     WDX_STAMP(7);
-    if constexpr (!LONG)   // (the refinement branch does not take long windows: launch_fingerprint never sends it one)
+    if constexpr (!LONG || LONG_REFINE)
     if (A.rf.query) {
         // The refinement kernels behind the fast kernels (one wave per three reads for the match, a quarter of this
         // workgroup for the barcode's segmentation) take this read too when they can reproduce its clipped samples from
         // the recorded bounds: no NaN in the window, samples as loaded, the configured window width.
-        if (A.refine_record && A.rf.ws && P.sig_norm == WDX_NORM_NONE && W == P.running_stat_width && nseg <= 128 &&
+        // (LONG never hands over: no clip record exists for its windows and the tail kernels hold kTailCap samples.  It
+        // refines in place like the BIG form, the tail's score curve and samples at `sbs` inside the slot.  The match's
+        // scratch and ev / zz / tmp / hist / cpts depend on num_events and the query alone; the tail's state bytes and the
+        // peak list's uint16 positions, relative to sbs, are bounded by ns2 <= ns < kLongCap like the adapter pass's.)
+        if (!LONG && A.refine_record && A.rf.ws && P.sig_norm == WDX_NORM_NONE && W == P.running_stat_width && nseg <= 128 &&
             !__syncthreads_or(any_nan)) {
             RefineRec *rec = reinterpret_cast<RefineRec *>(A.rf.ws) + r;
             for (int s = tid; s < nseg; s += BLOCK) rec->ev[s] = ev[s];
@@ -1366,7 +1380,7 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
             }
             return;
         }
-        fp_refine_tail<BLOCK>(A, r, state, ns, W, n, cpts, ev, zz, tmp, reinterpret_cast<unsigned char *>(Mt), hist, sh, nseg,
+        fp_refine_tail<BLOCK, LONG>(A, r, state, ns, W, n, cpts, ev, zz, tmp, reinterpret_cast<unsigned char *>(Mt), hist, sh, nseg,
                               [&](int sbs, int, const double *&sc_t, const float *&sg_t) {
                                   sc_t = scores + sbs;   // the adapter pass's score curve and clipped samples are still here
                                   sg_t = sig + sbs;
@@ -1514,6 +1528,32 @@ __global__ __launch_bounds__(BLOCK) void fingerprint_long_kernel(FpArgs A, const
         if (stop - start <= kBigCap || stop - start > kLongCap) continue;
         __syncthreads();
         fp_process_read<BLOCK, false, true, true>(A, r, smem);
+    }
+}
+
+// WDX_OPT_LONG_REFINE_WINDOWS: the same windows on the consensus-refinement branch -- the long form with fp_refine_tail in
+// place, the barcode tail's score curve and samples at sig_barcode_start inside the slot.  A kernel of its own, of
+// kLongRefineBlock = 512 threads, in a translation unit of its own (wdx_fingerprint_long.hip: built with every call
+// inlined): adapter pass and refinement in one function need 169 VGPRs, and as calls they take FpArgs and the lambdas by
+// address, which puts them into scratch memory -- at 1024 threads (128 VGPRs) it spills; the plain long kernel above keeps
+// its registers and its code.
+[[maybe_unused]] constexpr int kLongRefineBlock = 512;
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void fingerprint_long_refine_kernel(FpArgs A, const unsigned *count, const int32_t *list) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int64_t n = count ? (int64_t)*count : A.n_reads;
+    for (int64_t k = blockIdx.x; k < n; k += gridDim.x) {
+        const int64_t r = list ? (int64_t)list[k] : k;
+        if (A.ok && !A.ok[r]) continue;  // the regular kernel reported it
+        const int64_t row_len = A.row_len ? (int64_t)A.row_len[r]
+                                          : (A.row_off ? A.row_off[r + 1] - A.row_off[r] : A.stride);
+        int64_t start = (int64_t)A.a_start[r] - A.p.padding;
+        if (start < 0) start = 0;
+        int64_t stop = (int64_t)A.a_end[r] + A.p.padding;
+        if (stop > row_len) stop = row_len;
+        if (stop - start <= kBigCap || stop - start > kLongCap) continue;
+        __syncthreads();
+        fp_process_read<BLOCK, false, true, true, true>(A, r, smem);
     }
 }
 
@@ -1676,12 +1716,15 @@ int64_t fingerprint_long_bytes(int64_t max_len) { return max_len > kBigCap ? (in
 static int launch_fp_long(FpArgs A, void *d_long, const unsigned *count, const int32_t *list, hipStream_t stream) {
     static LdsAttr attr;
     const size_t lds = fp_lds_bytes_long();
-    if (int rc = attr.ensure(fingerprint_long_kernel<1024>, lds)) return rc;
+    if (!A.rf.query)
+        if (int rc = attr.ensure(fingerprint_long_kernel<1024>, lds)) return rc;
     A.cap = kLongCap;
     A.defer_big = 0;
     A.big_scores = reinterpret_cast<double *>(d_long);
     A.clip = nullptr;
+    A.refine_record = 0;
     const int64_t grid = A.n_reads < kLongSlots ? A.n_reads : kLongSlots;
+    if (A.rf.query) return launch_fp_long_refine(A, count, list, grid, lds, stream);   // (wdx_fingerprint_long.hip)
     hipLaunchKernelGGL((fingerprint_long_kernel<1024>), dim3((unsigned)grid), dim3(1024), lds, stream, A, count, list);
     WDX_HIP_TRY(hipGetLastError());
     return WDX_SUCCESS;

@@ -225,10 +225,10 @@ static FastPlan plan_fast_chain(const wdx_seg_params &p, int64_t max_len, int64_
     // fingerprint_big_kernel at the end (needs the caller's fingerprint_big_bytes(max_len) buffer; without it they
     // are reported WDX_READ_FAIL_UNKNOWN as windows beyond WDX_MAX_ADAPTER_SAMPLES always are)
     pl.with_huge = max_len > kExactLdsCap && f.has_big && !f.prof;
-    // WDX_OPT_LONG_WINDOWS: windows of kBigCap+1 .. kLongCap samples are left alone in the same way and taken by
-    // fingerprint_long_kernel behind that (the caller's fingerprint_long_bytes(max_len) buffer).  Not the refinement branch:
-    // the exact kernel's in-place refine code reads the samples and the score curve where the other forms keep them
-    pl.with_long = knobs.long_windows && max_len > kBigCap && f.has_long && pl.with_huge && !f.refine;
+    // WDX_OPT_LONG_WINDOWS (the refinement branch: WDX_OPT_LONG_REFINE_WINDOWS): windows of kBigCap+1 .. kLongCap samples are
+    // left alone in the same way and taken by fingerprint_long_kernel behind that (the caller's
+    // fingerprint_long_bytes(max_len) buffer), which refines in place where the call refines
+    pl.with_long = knobs.long_form(f.refine) && max_len > kBigCap && f.has_long && pl.with_huge;
     if (f.prof && !f.has_ws) {
         pl.path = FastPlan::kProfExact;
         return pl;

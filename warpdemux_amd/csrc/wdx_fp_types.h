@@ -123,6 +123,9 @@ __device__ __forceinline__ float key_f32(unsigned k) {
     return __uint_as_float(u);
 }
 
+// (wdx_fingerprint_long.hip) fingerprint_long_refine_kernel over `grid` slots of A.big_scores: launch_fp_long's other half
+int launch_fp_long_refine(const FpArgs &A, const unsigned *count, const int32_t *list, int64_t grid, size_t lds_bytes, hipStream_t stream);
+
 // A1 for a whole batch ahead of the fast kernels' launch chain (wdx_clip.hip): one ClipRec per read of A; windows of
 // 256 .. cap samples (cap = 4096, 5120 or 6144: the main fast instantiation's) are taken, the others are flagged CLIP_NONE.
 int launch_clip_bounds(const FpArgs &A, ClipRec *d_rec, int cap, hipStream_t stream);

@@ -157,8 +157,9 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
     //          rows start on 32-byte boundaries of the float32 buffer (in1), as fingerprint_adc_rows lays them out
     // float32: the window inside the read, taken from its very first sample.  int16: a ragged row has no limit -- a window that
     // runs past the read's end keeps its NaN tail -- and a window beyond the kernels' limit keeps one sample more than the
-    // limit (the context's: WDX_OPT_LONG_WINDOWS raises it), which is what reports it.
-    const WindowOpts wo{p->padding, 1, adc ? ctx->knobs.max_window() + 1 : 0};
+    // limit (the context's, for the branch this tick runs: WDX_OPT_LONG_WINDOWS raises it for a plain tick,
+    // WDX_OPT_LONG_REFINE_WINDOWS for one with refine parameters), which is what reports it.
+    const WindowOpts wo{p->padding, 1, adc ? ctx->knobs.max_window(rp != nullptr) + 1 : 0};
     auto window = [&](int64_t r) {
         return adapter_window(a_start[r], a_end[r], adc ? kNoRowLimit : (int64_t)row_len[r], ok && !ok[r], wo, adc ? (int64_t)row_len[r] : -1);
     };

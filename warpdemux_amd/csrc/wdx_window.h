@@ -10,7 +10,20 @@
 
 #include <algorithm>
 
+#include "../../include/wdx.h"
+
 namespace wdx {
+
+// The longest adapter window a call fingerprints -- the one statement of which product option raises it: a call of the
+// consensus-refinement branch (rp != NULL) looks at WDX_OPT_LONG_REFINE_WINDOWS only, a plain call at WDX_OPT_LONG_WINDOWS
+// only (tests/host/long_cap_check.cpp).
+inline bool long_form_on(bool refine, bool long_windows, bool long_refine_windows) {
+    return refine ? long_refine_windows : long_windows;
+}
+inline int64_t max_adapter_window(bool refine, bool long_windows, bool long_refine_windows) {
+    return long_form_on(refine, long_windows, long_refine_windows) ? (int64_t)WDX_MAX_LONG_ADAPTER_SAMPLES
+                                                                   : (int64_t)WDX_MAX_ADAPTER_SAMPLES;
+}
 
 constexpr int64_t kNoRowLimit = INT64_MAX;   // ragged rows whose window may run past the read's end (live int16 chunks)
 

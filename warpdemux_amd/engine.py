@@ -49,8 +49,8 @@ class DemuxEngine:
         self.device = int(device)
         self.tdev = torch.device("cuda", self.device)
         self.ctx = _lib.Context(self.device)
-        if long_windows:   # adapter windows of up to 65 536 samples on the plain entries (WDX_OPT_LONG_WINDOWS)
-            self.ctx.set_option(_lib.OPT_LONG_WINDOWS, 1)
+        if long_windows:   # adapter windows of up to 65 536 samples: WDX_OPT_LONG_WINDOWS (the plain entries) and
+            self.ctx.set_long_windows()   # WDX_OPT_LONG_REFINE_WINDOWS (the refining ones)
         self.L = _lib.load()
         self.params = params or SegParams(barcode_num_events=int(np.asarray(refs).shape[1]))
         self.set_refs(refs, window, penalty)

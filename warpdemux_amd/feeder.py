@@ -58,7 +58,7 @@ def _serve(shm_name: str, refs, window, penalty, model, device: int, ready, long
         L = _lib.load()
         ctx = _lib.Context(device)
         if long_windows:
-            ctx.set_option(_lib.OPT_LONG_WINDOWS, 1)
+            ctx.set_long_windows()   # (OPT_LONG_WINDOWS and OPT_LONG_REFINE_WINDOWS: a refine ring looks at the second)
         if refs.shape[0]:   # (a fingerprint-only refine ring has none)
             _marshal.set_refs(ctx, refs, window, penalty)
         if model is not None:
@@ -106,8 +106,8 @@ class Feeder:
     ``refs`` may be None with or without ``refine`` (`demux_batch` is then refused) or given beside it; K must equal
     ``model.n_features``.
 
-    ``long_windows``: the serving context fingerprints adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS; plain
-    minibatches -- `stride` must hold such rows)."""
+    ``long_windows``: the serving context fingerprints adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS, and
+    WDX_OPT_LONG_REFINE_WINDOWS for a ``refine`` ring -- `stride` must hold such rows)."""
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, max_reads: int = 1000,
                  stride: int = 10000, n_slots: int = 16, device: int = 0, start_timeout: float = 120.0, model=None,

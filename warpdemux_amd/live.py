@@ -68,8 +68,8 @@ class LiveDemux:
     ``adc``: :meth:`tick_adc` works on ANY LiveDemux; ``adc=True`` only makes the constructor's warm-up tick an int16 one,
     so that the int16 staging buffers too are allocated before the run starts.
 
-    ``long_windows``: plain ticks fingerprint adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS), int16 ones
-    included; refined ticks keep the limit of 16 384.
+    ``long_windows``: ticks fingerprint adapter windows of up to 65 536 samples, int16 ones included (WDX_OPT_LONG_WINDOWS;
+    refined ticks: WDX_OPT_LONG_REFINE_WINDOWS).
 
     Every check of the arguments happens before a context is created and raises ``ValueError``."""
 
@@ -88,7 +88,7 @@ class LiveDemux:
         self.L = _lib.load()
         self.ctx = _lib.Context(device)      # this object's own context = own stream + staging buffers
         if long_windows:
-            self.ctx.set_option(_lib.OPT_LONG_WINDOWS, 1)
+            self.ctx.set_long_windows()
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:

@@ -112,7 +112,8 @@ class MinibatchPipeline:
     consensus-refinement branch (K = ``refine.barcode_keep_events``); then ``refs`` may be None (fingerprints only).
     ``model``: a `models.Fpt_Boost` kept resident on the device; every minibatch brings its prediction back
     (`BoostMinibatch`), ``refs`` may be None, and K must equal ``model.n_features``.
-    ``long_windows``: plain minibatches fingerprint adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS)."""
+    ``long_windows``: minibatches fingerprint adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS; with ``refine``:
+    WDX_OPT_LONG_REFINE_WINDOWS)."""
 
     N_SLOTS = 2
 
@@ -129,7 +130,7 @@ class MinibatchPipeline:
         self.L = _lib.load()
         self.ctx = _lib.Context(device)
         if long_windows:   # (every slot copies the context's options at its submit; 12 MB per slot that meets a long window)
-            self.ctx.set_option(_lib.OPT_LONG_WINDOWS, 1)
+            self.ctx.set_long_windows()
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:

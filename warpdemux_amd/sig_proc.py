@@ -61,7 +61,7 @@ class SegParams:
     def from_spc(cls, spc, long_windows: bool = False) -> "SegParams":
         """From a reference-style SigProcConfig (attribute access as in sig_proc.py:414-534).  ``long_windows``: the
         configuration is meant for objects and calls with ``long_windows=True``, which take adapter windows of up to
-        WDX_MAX_LONG_ADAPTER_SAMPLES = 65 536 samples (plain branch only)."""
+        WDX_MAX_LONG_ADAPTER_SAMPLES = 65 536 samples (plain and consensus-refinement branch)."""
         seg = spc.segmentation
         k = seg.barcode_num_events
         if getattr(seg, "consensus_refinement", False):
@@ -307,15 +307,17 @@ def fingerprint_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_en
 
 
 def fingerprint_refine_batch(signals, adapter_start, adapter_end, params: SegParams, refine: RefineParams, success=None,
-                             device=None) -> FingerprintBatch:
-    """Consensus-refinement branch on a (n_reads, stride) float32 minibatch; K = refine.barcode_keep_events."""
+                             device=None, long_windows: bool = False) -> FingerprintBatch:
+    """Consensus-refinement branch on a (n_reads, stride) float32 minibatch; K = refine.barcode_keep_events.
+    ``long_windows``: adapter windows of up to MAX_LONG_ADAPTER_SAMPLES samples for this call (WDX_OPT_LONG_REFINE_WINDOWS on
+    the default context, put back afterwards); the default reports windows beyond MAX_ADAPTER_SAMPLES as failed ("unknown")."""
     sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
     pc, rc = params.to_c(), refine.to_c()
     o = _marshal.outputs(n, refine.barcode_keep_events, 0, 0, _FPT_WANT | _lib.WANT_REFINE_IDX)
-    ctx = _lib.default_context(device)
-    _lib.check(_lib.load().wdx_fingerprint_refine_batch(
-        ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc), C.byref(rc),
-        _lib.ptr(o["fpt"]), _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["refine_idx"]), _lib.ptr(o["status"])))
+    with _lib.default_context(device).long_refine_windows_for_call(long_windows) as ctx:
+        _lib.check(_lib.load().wdx_fingerprint_refine_batch(
+            ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc), C.byref(rc),
+            _lib.ptr(o["fpt"]), _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["refine_idx"]), _lib.ptr(o["status"])))
     return fingerprints(o)
 
 
@@ -407,7 +409,7 @@ def detect_results_to_fpt_batch(calibrated_signals, spc, detect_results: Sequenc
     per-read call (sig_proc.py:590-605) plus the `barcode_fpt_wrapper` read-id (file_proc.py:216).  With
     ``spc.segmentation.consensus_refinement`` the caller passes the consensus signal like the reference does.
     ``long_windows``: a configuration with ``core.max_obs_trace`` + 2 x padding up to MAX_LONG_ADAPTER_SAMPLES is accepted and
-    its long windows are fingerprinted (plain branch; the refinement branch keeps MAX_ADAPTER_SAMPLES)."""
+    its long windows are fingerprinted, on the plain and on the consensus-refinement branch."""
     params = SegParams.from_spc(spc, long_windows=long_windows)
     refine = None
     if getattr(spc.segmentation, "consensus_refinement", False):
@@ -421,7 +423,8 @@ def detect_results_to_fpt_batch(calibrated_signals, spc, detect_results: Sequenc
     if refine is None:
         fb = fingerprint_batch(calibrated_signals, a_s, a_e, params, success=ok, device=device, long_windows=long_windows)
     else:
-        fb = fingerprint_refine_batch(calibrated_signals, a_s, a_e, params, refine, success=ok, device=device)
+        kw = dict(long_windows=True) if long_windows else {}     # (the default call is what it has always been)
+        fb = fingerprint_refine_batch(calibrated_signals, a_s, a_e, params, refine, success=ok, device=device, **kw)
     return read_results_from_batch(fb, detect_results, read_ids, refined=refine is not None)
 
 
