@@ -164,6 +164,10 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
  * the ones of WDX_OPT_LONG_WINDOWS (12 MiB per context or pipeline slot, allocated by the first call that meets such a
  * window with the option of its branch on, never otherwise). */
 #define WDX_OPT_LONG_REFINE_WINDOWS 21
+/* Reads per slice of the *_adc_dev entries (int16 device shards, below): 0 (default) = as many as the 1 GiB staging budget
+ * holds; a positive value is used as given wherever it stays inside that budget (tests walk several slices at small n);
+ * negative: WDX_ERR_INVALID.  It changes which reads share a launch, never a result. */
+#define WDX_OPT_ADC_DEV_SLICE_READS 22
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -405,6 +409,78 @@ int wdx_demux_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, const wdx_
 int wdx_calibrate_adc_dev(wdx_ctx *ctx, const int16_t *d_adc, const int64_t *d_row_off, const int32_t *d_row_len,
                           int64_t stride, int64_t n_reads, const float *d_offset, const float *d_scale, float *d_out,
                           void *stream);
+/* ---- int16 ADC shards that STAY on the device: the *_adc_dev twins of the device-resident entries ------------------
+ * A caller who holds what a pod5 file holds keeps its shard int16 in HBM -- 2 bytes per sample instead of the 4 of a float32
+ * copy -- and float32 exists only for the reads in flight.  An int16 device shard (all pointers DEVICE memory):
+ *   adc                      the samples, in one of two layouts:
+ *                              strided   row_off == NULL: (n_reads, stride) int16 rows
+ *                              packed    row_off int64[n_reads + 1], every entry a multiple of 8 (A PRECONDITION: these are
+ *                                        device arrays, nothing is checked synchronously; as for wdx_calibrate_adc_dev);
+ *                                        read r holds its samples at adc[row_off[r] ..)
+ *   row_len  int32[n_reads]  REQUIRED: ADC samples of read r; clamped to the row (0 .. stride; packed: 0 .. row_off[r+1] -
+ *                            row_off[r]), as wdx_calibrate_adc_dev clamps it
+ *   offset, scale            REQUIRED: float32[n_reads]
+ *   row_win  int32[n_reads]  nullable, packed only: as wdx_minibatch_adc_in.row_win -- samples of the float32 row read r
+ *                            stands for, row_win[r] - row_len[r] of them the NaN tail; NULL (or less than row_len) = row_len
+ * THE CONTRACT is the one above: read r stands for the float32 row pa[i] = scale[r] * ((float)adc[i] + offset[r]) for
+ * i < row_len[r] (float32 add, THEN float32 multiply: two roundings, never fused), NaN from there to `stride` (strided) or
+ * row_win[r] (packed); a_start / a_end are relative to the row.  Every *_adc_dev entry returns, bit for bit, what its
+ * float32 twin returns on those rows -- status, fpt, dwell, stats, refine_idx, dist, call, the INCREMENTED counts, prob /
+ * pred / conf / n_nonfinite; failed detections, empty and inverted windows, windows that run into the NaN tail and whatever
+ * WDX_OPT_LONG_WINDOWS / WDX_OPT_LONG_REFINE_WINDOWS select on the context included.  A caller whose reader calibrates by
+ * another formula must not use this path.
+ * How: the reads are walked in slices.  adc_dev_windows_kernel (wdx_adc.hip) decodes the adapter window of every read of a
+ * slice -- the window rule of the host ways in, start rounded down to a multiple of 8 samples -- into a context-owned
+ * float32 staging block of at most 1 GiB, the float32 twin's own body runs on that block and writes its outputs at the
+ * slice's read offset, the next slice reuses the block in stream order: no host synchronisation, and the staging never
+ * depends on the size of the shard.  Arguments other than `in` are those of the float32 twin (max_len bounds the adapter
+ * windows as there; a window beyond it is reported WDX_READ_FAIL_UNKNOWN as there).  d_work: the *_adc_workspace_bytes of
+ * the same context, n_reads, max_len and K (they depend on the context's WDX_OPT_ADC_DEV_SLICE_READS and long-window options:
+ * ask after setting those).  n_reads == 0 returns what the twin returns. */
+typedef struct wdx_adc_dev_in {
+    const int16_t *adc;
+    const int64_t *row_off;      /* packed: int64[n_reads + 1], multiples of 8; NULL = strided              */
+    int64_t stride;              /* strided: samples of a row (= of the float32 row); ignored when packed   */
+    const int32_t *row_len;      /* REQUIRED                                                                */
+    const float *offset, *scale; /* REQUIRED                                                                */
+    const int32_t *row_win;      /* packed only, nullable                                                   */
+} wdx_adc_dev_in;
+int wdx_fingerprint_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                            const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                            double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_status, void *stream);
+int wdx_fingerprint_refine_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                                   const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
+                                   const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell,
+                                   double *d_stats, int32_t *d_refine_idx, int32_t *d_status, void *stream);
+/* d_work of wdx_demux_adc_dev / _svm_adc_dev / _mlp_adc_dev and of wdx_demux_boost_adc_dev without rp: the float32 twin's
+ * workspace for the largest slice; ..._refine_...: of wdx_demux_refine_adc_dev and wdx_demux_boost_adc_dev with rp.  0 on
+ * bad arguments.  Neither holds the staging block: the context owns it. */
+int64_t wdx_demux_adc_workspace_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t barcode_num_events);
+int64_t wdx_demux_refine_adc_workspace_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t barcode_keep_events);
+/* Device bytes of the staging block a call with these arguments needs (the context keeps the largest so far; at most
+ * 1 GiB); refine != 0: for the consensus-refinement entries. */
+int64_t wdx_adc_dev_staging_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t refine);
+int wdx_demux_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                      const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell,
+                      double *d_stats, int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts, void *d_work,
+                      void *stream);
+int wdx_demux_refine_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                             const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                             const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell, double *d_stats,
+                             int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts,
+                             void *d_work, void *stream);
+int wdx_demux_svm_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                          const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt,
+                          int32_t *d_status, float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf, void *d_work,
+                          int64_t block_rows, void *stream);
+int wdx_demux_mlp_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                          const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt,
+                          int32_t *d_status, float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf,
+                          int64_t *d_n_nonfinite, void *d_work, int64_t block_rows, void *stream);
+int wdx_demux_boost_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                            const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                            const wdx_refine_params *rp, double *d_fpt, int32_t *d_refine_idx, int32_t *d_status,
+                            double *d_raw, double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, void *stream);
 /* ---- consensus refinement (wdx_refine_params) through the pipelined minibatches ----------------------------------
  * The tRNA models' branch on the same slots, for float32 rows (`in`) or int16 ADC rows (`in_adc`): exactly one of the
  * two is non-NULL, and all three ways in of either format work as above.  K = rp->barcode_keep_events for fpt, dwell and
@@ -844,6 +920,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_MLP 9              /* the MLP tail kernel (wdx_mlp_predict_dev, wdx_dtw_mlp_predict, wdx_demux_mlp_dev) */
 #define WDX_K_BOOST 10           /* the boost tail, whichever of its two kernels ran (wdx_boost_predict_dev, wdx_boost_predict,
                                     wdx_demux_boost_dev, WDX_WANT_BOOST minibatches) */
+#define WDX_K_ADC_DEV_WINDOWS 11 /* adc_dev_windows_kernel: the window decode ahead of every slice of an *_adc_dev call */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

@@ -27,6 +27,7 @@ WDX_ERR_NO_REFS = -5
 K_FINGERPRINT, K_DTW, K_TRANSPOSE, K_COUNT, K_SVM, K_REDUCE, K_FINGERPRINT_MAIN, K_FINGERPRINT_CLIP, K_FINGERPRINT_TAIL = 0, 1, 2, 3, 4, 5, 6, 7, 8
 K_MLP = 9
 K_BOOST = 10
+K_ADC_DEV_WINDOWS = 11   # the window decode ahead of every slice of an *_adc_dev call (int16 device shards)
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -45,6 +46,7 @@ OPT_BOOST_CHUNK_ROWS = 18
 OPT_BOOST_KERNEL = 19   # 0 by batch size | 1 lane-per-read | 2 tree-parallel
 OPT_LONG_WINDOWS = 20   # product option: 1 = adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (0 / 1, else ValueError)
 OPT_LONG_REFINE_WINDOWS = 21   # ... the same for the consensus-refinement branch, which looks at this option only
+OPT_ADC_DEV_SLICE_READS = 22   # reads per slice of the *_adc_dev entries (0 = as many as the staging budget holds)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -68,6 +70,9 @@ EXPORTS = [
     "wdx_feeder_ring_bytes_refine", "wdx_feeder_ring_init_refine", "wdx_feeder_run_refine",
     "wdx_boost_set_model", "wdx_boost_predict_dev", "wdx_boost_predict", "wdx_demux_boost_dev", "wdx_feeder_predict_boost",
     "wdx_live_tick_ex",
+    "wdx_fingerprint_adc_dev", "wdx_fingerprint_refine_adc_dev", "wdx_demux_adc_workspace_bytes",
+    "wdx_demux_refine_adc_workspace_bytes", "wdx_adc_dev_staging_bytes", "wdx_demux_adc_dev", "wdx_demux_refine_adc_dev",
+    "wdx_demux_svm_adc_dev", "wdx_demux_mlp_adc_dev", "wdx_demux_boost_adc_dev",
 ]
 
 
@@ -206,6 +211,15 @@ class MinibatchAdcInC(C.Structure):
         ("adc", C.c_void_p), ("n_reads", C.c_int64), ("stride", C.c_int64), ("row_len", C.c_void_p), ("offset", C.c_void_p),
         ("scale", C.c_void_p), ("row_off", C.c_void_p), ("row_win", C.c_void_p), ("a_start", C.c_void_p), ("a_end", C.c_void_p),
         ("ok", C.c_void_p),
+    ]
+
+
+class AdcDevInC(C.Structure):
+    """wdx_adc_dev_in (include/wdx.h): an int16 shard in device memory"""
+
+    _fields_ = [
+        ("adc", C.c_void_p), ("row_off", C.c_void_p), ("stride", C.c_int64), ("row_len", C.c_void_p), ("offset", C.c_void_p),
+        ("scale", C.c_void_p), ("row_win", C.c_void_p),
     ]
 
 
@@ -500,6 +514,30 @@ def load():
         L.wdx_live_tick_ex.restype = C.c_int
         L.wdx_live_tick_ex.argtypes = [vp, P(LiveInC), P(SegParamsC), P(RefineParamsC), i64, C.c_uint32, P(MinibatchOutC), vp,
                                        P(i64)]
+        A = P(AdcDevInC)
+        L.wdx_fingerprint_adc_dev.restype = C.c_int
+        L.wdx_fingerprint_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp]
+        L.wdx_fingerprint_refine_adc_dev.restype = C.c_int
+        L.wdx_fingerprint_refine_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), P(RefineParamsC), vp, vp, vp,
+                                                     vp, vp, vp]
+        L.wdx_demux_adc_workspace_bytes.restype = i64
+        L.wdx_demux_adc_workspace_bytes.argtypes = [vp, i64, i64, i32]
+        L.wdx_demux_refine_adc_workspace_bytes.restype = i64
+        L.wdx_demux_refine_adc_workspace_bytes.argtypes = [vp, i64, i64, i32]
+        L.wdx_adc_dev_staging_bytes.restype = i64
+        L.wdx_adc_dev_staging_bytes.argtypes = [vp, i64, i64, i32]
+        L.wdx_demux_adc_dev.restype = C.c_int
+        L.wdx_demux_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_demux_refine_adc_dev.restype = C.c_int
+        L.wdx_demux_refine_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), P(RefineParamsC), vp, vp, vp, vp, vp,
+                                               vp, vp, vp, vp, vp]
+        L.wdx_demux_svm_adc_dev.restype = C.c_int
+        L.wdx_demux_svm_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        L.wdx_demux_mlp_adc_dev.restype = C.c_int
+        L.wdx_demux_mlp_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        L.wdx_demux_boost_adc_dev.restype = C.c_int
+        L.wdx_demux_boost_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), P(RefineParamsC), vp, vp, vp, vp, vp,
+                                              vp, vp, vp, vp]
         _lib = L
         return L
 

@@ -42,14 +42,14 @@ static uint64_t fnv1a(const void *data, size_t n, uint64_t h = 0xcbf29ce48422232
     return h;
 }
 
-int Buffer::ensure(size_t need) {
+int Buffer::ensure(size_t need, bool exact) {
     if (need <= bytes) return WDX_SUCCESS;
     if (p) (void)hipFree(p);
     p = nullptr;
     bytes = 0;
-    size_t want = need + need / 4;
+    size_t want = exact ? need : need + need / 4;
     hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) {
+    if (e != hipSuccess && !exact) {
         e = hipMalloc(&p, need);
         want = need;
     }
@@ -411,6 +411,87 @@ static int dtw_dev_route(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_ou
 
 }  // namespace wdx
 
+namespace wdx {
+
+AdcDevPlan adc_dev_plan_for(const wdx_ctx *ctx, int64_t n_reads, int64_t max_len, bool refine) {
+    return adc_dev_plan(n_reads, adc_dev_max_len(max_len, ctx->knobs.max_window(refine)), ctx->knobs.adc_dev_slice_reads);
+}
+
+int adc_dev_stage(wdx_ctx *B, const DevRows &rows, const AdcDevPlan &plan, bool refine, int64_t padding, int64_t r0, int64_t m,
+                  hipStream_t s, FpReads *rd) {
+    const wdx_adc_dev_in &A = *rows.adc;
+    float *stage = (float *)B->adc_stage.p;
+    // the three int32 arrays behind the rows of the LARGEST slice the block was planned for: every slice finds them there
+    int32_t *idx = (int32_t *)(stage + std::min(rows.f32.n_reads, plan.slice_reads) * plan.pitch);
+    AdcDevWindows W{};
+    W.adc = A.adc, W.row_off = A.row_off, W.stride = A.stride, W.row_len = A.row_len, W.row_win = A.row_off ? A.row_win : nullptr;
+    W.offset = A.offset, W.scale = A.scale, W.a_start = rows.f32.a_start, W.a_end = rows.f32.a_end, W.ok = rows.f32.ok;
+    W.padding = padding, W.max_len = adc_dev_max_len(rows.f32.max_len, B->knobs.max_window(refine));
+    W.r0 = r0, W.n = m, W.dst = stage, W.pitch = plan.pitch;
+    W.a_start_out = idx, W.a_end_out = idx + m, W.row_len_out = idx + 2 * m;
+    {
+        Timed t(B, WDX_K_ADC_DEV_WINDOWS, s);
+        if (int rc = launch_adc_dev_windows(W, s)) return rc;
+    }
+    *rd = FpReads{stage, nullptr, W.row_len_out, plan.pitch, rows.f32.max_len, m, W.a_start_out, W.a_end_out,
+                  from_read(rows.f32.ok, r0)};
+    return WDX_SUCCESS;
+}
+
+// the shard descriptor itself (a HOST struct of device pointers); its arrays are looked at by DevRows::missing when there
+// are reads
+int adc_dev_in_ok(const char *who, const wdx_adc_dev_in *in) {
+    if (in && (in->row_off || (in->stride >= 0 && in->stride <= INT32_MAX))) return WDX_SUCCESS;
+    set_error("%s: bad arguments", who);
+    return WDX_ERR_INVALID;
+}
+
+int fingerprint_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell,
+                         double *d_stats, int32_t *d_status, void *stream) {
+    WDX_ENTER(ctx);
+    const int64_t n_reads = rows.f32.n_reads;
+    if (n_reads < 0 || !p || (n_reads > 0 && (rows.missing() || !rows.f32.a_start || !rows.f32.a_end || !d_status))) {
+        set_error("fingerprint_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int64_t K = p->barcode_num_events;
+    return for_each_slice(ctx, rows, false, p->padding, s, [&](const FpReads &in, int64_t r0) {
+        if (int e = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(in.n_reads))) return e;
+        return fingerprint_stage(ctx, in, *p, FpOut{from_read(d_fpt, r0, K), from_read(d_dwell, r0, K), from_read(d_stats, r0, 6),
+                                                   from_read(d_status, r0)}, ctx->fp_ws.p, s);
+    });
+}
+
+int fingerprint_refine_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p_in, const wdx_refine_params *rp,
+                                double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_refine_idx, int32_t *d_status,
+                                void *stream) {
+    WDX_ENTER(ctx);
+    const int64_t n_reads = rows.f32.n_reads;
+    if (n_reads < 0 || !rp ||
+        (n_reads > 0 && (rows.missing() || !rows.f32.a_start || !rows.f32.a_end || !d_status || !d_refine_idx))) {
+        set_error("fingerprint_refine_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    wdx_seg_params pv;
+    if ((rc = refine_seg_params("fingerprint_refine_dev", p_in, rp, &pv))) return rc;
+    if (n_reads == 0) return WDX_SUCCESS;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int64_t K = pv.barcode_num_events;
+    return for_each_slice(ctx, rows, true, pv.padding, s, [&](const FpReads &in, int64_t r0) {
+        if (int e = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(in.n_reads))) return e;
+        return demux_chain(ctx, DtwRefs{}, in, pv, rp, from_read(d_refine_idx, r0, 3), nullptr, ctx->fp_ws.p, false, ChainTail{},
+                           ChainOut{FpOut{from_read(d_fpt, r0, K), from_read(d_dwell, r0, K), from_read(d_stats, r0, 6),
+                                          from_read(d_status, r0)}}, s);
+    });
+}
+
+}  // namespace wdx
+
 extern "C" {
 
 int wdx_abi_version(void) { return WDX_ABI_VERSION; }
@@ -480,7 +561,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     comm_destroy(ctx);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->adc_stage, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf, &ctx->mb_ridx})
         b->release();
     ctx->pin_in.release();
@@ -535,6 +616,13 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
                 return WDX_ERR_INVALID;
             }
             ctx->knobs.long_refine_windows = value == 1;
+            break;
+        case WDX_OPT_ADC_DEV_SLICE_READS:
+            if (value < 0) {
+                set_error("WDX_OPT_ADC_DEV_SLICE_READS is 0 (built-in) or a number of reads, not %lld", (long long)value);
+                return WDX_ERR_INVALID;
+            }
+            ctx->knobs.adc_dev_slice_reads = value;
             break;
         default:
             set_error("unknown option %d", (int)option);
@@ -641,16 +729,16 @@ int wdx_fingerprint_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
                         const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
                         const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell, double *d_stats,
                         int32_t *d_status, void *stream) {
-    WDX_ENTER(ctx);
-    if (n_reads < 0 || !p || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status))) {
-        set_error("fingerprint_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
-    if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    return fingerprint_stage(ctx, in, *p, FpOut{d_fpt, d_dwell, d_stats, d_status}, ctx->fp_ws.p, (hipStream_t)stream);
+    return fingerprint_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok), p,
+                                d_fpt, d_dwell, d_stats, d_status, stream);
+}
+
+int wdx_fingerprint_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                            const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                            double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_status, void *stream) {
+    if (int e = adc_dev_in_ok("fingerprint_adc_dev", in)) return e;
+    return fingerprint_dev_rows(ctx, DevRows(in, max_len, n_reads, d_a_start, d_a_end, d_ok), p, d_fpt, d_dwell, d_stats,
+                                d_status, stream);
 }
 
 int wdx_fingerprint_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
@@ -659,21 +747,17 @@ int wdx_fingerprint_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *
                                const wdx_seg_params *p_in, const wdx_refine_params *rp, double *d_fpt,
                                int64_t *d_dwell, double *d_stats, int32_t *d_refine_idx, int32_t *d_status,
                                void *stream) {
-    WDX_ENTER(ctx);
-    if (n_reads < 0 || !rp || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_refine_idx))) {
-        set_error("fingerprint_refine_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    wdx_seg_params pv;
-    if ((rc = refine_seg_params("fingerprint_refine_dev", p_in, rp, &pv))) return rc;
-    if (n_reads == 0) return WDX_SUCCESS;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    return demux_chain(ctx, DtwRefs{}, in, pv, rp, d_refine_idx, nullptr, ctx->fp_ws.p, false, ChainTail{},
-                       ChainOut{FpOut{d_fpt, d_dwell, d_stats, d_status}}, s);
+    return fingerprint_refine_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok),
+                                       p_in, rp, d_fpt, d_dwell, d_stats, d_refine_idx, d_status, stream);
+}
+
+int wdx_fingerprint_refine_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                                   const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
+                                   const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell,
+                                   double *d_stats, int32_t *d_refine_idx, int32_t *d_status, void *stream) {
+    if (int e = adc_dev_in_ok("fingerprint_refine_adc_dev", in)) return e;
+    return fingerprint_refine_dev_rows(ctx, DevRows(in, max_len, n_reads, d_a_start, d_a_end, d_ok), p, rp, d_fpt, d_dwell,
+                                       d_stats, d_refine_idx, d_status, stream);
 }
 
 int wdx_fingerprint_profile_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
@@ -729,17 +813,38 @@ int64_t wdx_demux_refine_workspace_bytes(int64_t n_reads, int32_t K) {
     return base ? round_up(base, 256) + fingerprint_refine_ws_bytes(n_reads) : 0;
 }
 
+// the largest d_work any slice of an int16 shard asks its float32 twin's layout for: a full slice, or the last, shorter one
+// (which may be the one below kRowMajorMinReads that holds the read-minor copy)
+static int64_t adc_workspace_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t K, bool refine) {
+    if (!ctx || n_reads < 0 || K < 1) return 0;
+    const AdcDevPlan P = adc_dev_plan_for(ctx, n_reads, max_len, refine);
+    int64_t (*bytes)(int64_t, int32_t) = refine ? wdx_demux_refine_workspace_bytes : wdx_demux_workspace_bytes;
+    return std::max(bytes(std::min(std::max<int64_t>(n_reads, 1), P.slice_reads), K), bytes(std::max<int64_t>(P.last_reads, 1), K));
+}
+
+int64_t wdx_demux_adc_workspace_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t K) {
+    return adc_workspace_bytes(ctx, n_reads, max_len, K, false);
+}
+
+int64_t wdx_demux_refine_adc_workspace_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t K) {
+    return adc_workspace_bytes(ctx, n_reads, max_len, K, true);
+}
+
+int64_t wdx_adc_dev_staging_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t refine) {
+    return ctx ? adc_dev_plan_for(ctx, n_reads, max_len, refine != 0).staging_bytes : 0;
+}
+
+}  // extern "C"
+
 // wdx_demux_dev; with rp the fingerprint stage takes the refinement branch (wdx_demux_refine_dev: `p` carries
 // K = rp->barcode_keep_events already, the hand-over records live behind the plain call's pieces of d_work)
-static int demux_dev_body(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
-                          const int32_t *d_row_len, int64_t stride, int64_t max_len, int64_t n_reads,
-                          const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
-                          const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell,
-                          double *d_stats, int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call,
-                          int64_t *d_counts, void *d_work, void *stream) {
+int wdx::demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt,
+                        int64_t *d_dwell, double *d_stats, int32_t *d_refine_idx, int32_t *d_status, float *d_dist,
+                        int32_t *d_call, int64_t *d_counts, void *d_work, void *stream) {
     WDX_ENTER(ctx);
-    if (n_reads < 0 || !p ||
-        (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_dist || !d_call || !d_work))) {
+    if (rows.f32.n_reads < 0 || !p ||
+        (rows.f32.n_reads > 0 &&
+         (rows.missing() || !rows.f32.a_start || !rows.f32.a_end || !d_status || !d_dist || !d_call || !d_work))) {
         set_error("demux_dev: bad arguments");
         return WDX_ERR_INVALID;
     }
@@ -755,42 +860,51 @@ static int demux_dev_body(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row
         set_error("demux_dev needs window <= %d", kMaxRegWindow);
         return WDX_ERR_UNSUPPORTED;
     }
-    if (n_reads == 0) return WDX_SUCCESS;
+    if (rows.f32.n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
     unsigned char *w = (unsigned char *)d_work;
-    double *fpt = d_fpt ? d_fpt : (double *)w;
-    const bool rowmajor = n_reads >= kRowMajorMinReads;
-    const DemuxWork W = demux_work_layout(n_reads, K, !rowmajor);
-    const int64_t ld = W.ld;
-    double *fptT = (double *)(w + W.fptT);
-    uint8_t *flags = w + W.flags;
-    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    RefineDev *rf = nullptr;
-    RefineDevGuard rf_guard{rf};
-    if (rp && (rc = refine_prepare(ctx, *rp, n_reads, d_refine_idx, w + round_up(W.bytes, 256), s, &rf))) return rc;
-    if ((rc = fingerprint_stage(ctx, in, *p, FpOut{fpt, d_dwell, d_stats, d_status}, w + W.fp_ws, s, rf, rf == nullptr)))
-        return rc;
-    if (rowmajor) {
-        // failed reads carry NaN fingerprints; the DTW kernel reads the row-major rows in place and flags them
-        Timed t(ctx, WDX_K_DTW, s);
-        if ((rc = launch_dtw(fpt, 1, n_reads, nullptr, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
-                             R.window, R.penalty, d_dist, R.nY, 1, d_call, nullptr, 0, s, ctx->knobs, true, &ctx->dtw_last)))
+    return for_each_slice(ctx, rows, rp != nullptr, p->padding, s, [&](const FpReads &in, int64_t r0) {
+        int rc = WDX_SUCCESS;
+        const int64_t n_reads = in.n_reads;
+        double *fpt = d_fpt ? d_fpt + r0 * K : (double *)w;
+        int32_t *status = d_status + r0, *call = d_call + r0;
+        float *dist = d_dist + r0 * R.nY;
+        const bool rowmajor = n_reads >= kRowMajorMinReads;
+        const DemuxWork W = demux_work_layout(n_reads, K, !rowmajor);
+        const int64_t ld = W.ld;
+        double *fptT = (double *)(w + W.fptT);
+        uint8_t *flags = w + W.flags;
+        RefineDev *rf = nullptr;
+        RefineDevGuard rf_guard{rf};
+        if (rp && (rc = refine_prepare(ctx, *rp, n_reads, from_read(d_refine_idx, r0, 3), w + round_up(W.bytes, 256), s, &rf)))
             return rc;
-    } else {
-        {
-            Timed t(ctx, WDX_K_TRANSPOSE, s);
-            if ((rc = launch_transpose(fpt, n_reads, K, fptT, ld, flags, s))) return rc;
+        if ((rc = fingerprint_stage(ctx, in, *p, FpOut{fpt, from_read(d_dwell, r0, K), from_read(d_stats, r0, 6), status},
+                                    w + W.fp_ws, s, rf, rf == nullptr)))
+            return rc;
+        if (rowmajor) {
+            // failed reads carry NaN fingerprints; the DTW kernel reads the row-major rows in place and flags them
+            Timed t(ctx, WDX_K_DTW, s);
+            if ((rc = launch_dtw(fpt, 1, n_reads, nullptr, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
+                                 R.window, R.penalty, dist, R.nY, 1, call, nullptr, 0, s, ctx->knobs, true, &ctx->dtw_last)))
+                return rc;
+        } else {
+            {
+                Timed t(ctx, WDX_K_TRANSPOSE, s);
+                if ((rc = launch_transpose(fpt, n_reads, K, fptT, ld, flags, s))) return rc;
+            }
+            Timed t(ctx, WDX_K_DTW, s);
+            if ((rc = launch_dtw(fptT, ld, n_reads, flags, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
+                                 R.window, R.penalty, dist, R.nY, 1, call, nullptr, 0, s, ctx->knobs, false, &ctx->dtw_last)))
+                return rc;
         }
-        Timed t(ctx, WDX_K_DTW, s);
-        if ((rc = launch_dtw(fptT, ld, n_reads, flags, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
-                             R.window, R.penalty, d_dist, R.nY, 1, d_call, nullptr, 0, s, ctx->knobs, false, &ctx->dtw_last)))
-            return rc;
-    }
-    if ((rc = dtw_settle_inf(R, fpt, n_reads, d_dist, d_call, s))) return rc;
-    Timed t(ctx, WDX_K_COUNT, s);
-    return launch_count_calls(d_call, d_status, n_reads, R.nY, d_counts, s);
+        if ((rc = dtw_settle_inf(R, fpt, n_reads, dist, call, s))) return rc;
+        Timed t(ctx, WDX_K_COUNT, s);
+        return launch_count_calls(call, status, n_reads, R.nY, d_counts, s);
+    });
 }
+
+extern "C" {
 
 int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
                   const int32_t *d_row_len, int64_t stride, int64_t max_len, int64_t n_reads,
@@ -798,8 +912,17 @@ int wdx_demux_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off,
                   const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell, double *d_stats,
                   int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts, void *d_work,
                   void *stream) {
-    return demux_dev_body(ctx, d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, p, nullptr,
-                          d_fpt, d_dwell, d_stats, nullptr, d_status, d_dist, d_call, d_counts, d_work, stream);
+    return demux_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok), p,
+                          nullptr, d_fpt, d_dwell, d_stats, nullptr, d_status, d_dist, d_call, d_counts, d_work, stream);
+}
+
+int wdx_demux_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                      const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell,
+                      double *d_stats, int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts, void *d_work,
+                      void *stream) {
+    if (int e = adc_dev_in_ok("demux_adc_dev", in)) return e;
+    return demux_dev_rows(ctx, DevRows(in, max_len, n_reads, d_a_start, d_a_end, d_ok), p, nullptr, d_fpt, d_dwell, d_stats,
+                          nullptr, d_status, d_dist, d_call, d_counts, d_work, stream);
 }
 
 int wdx_demux_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len,
@@ -814,8 +937,24 @@ int wdx_demux_refine_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_
     }
     wdx_seg_params pv;
     if (int e = refine_seg_params("demux_refine_dev", p, rp, &pv)) return e;
-    return demux_dev_body(ctx, d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok, &pv, rp, d_fpt,
-                          d_dwell, d_stats, d_refine_idx, d_status, d_dist, d_call, d_counts, d_work, stream);
+    return demux_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok), &pv, rp,
+                          d_fpt, d_dwell, d_stats, d_refine_idx, d_status, d_dist, d_call, d_counts, d_work, stream);
+}
+
+int wdx_demux_refine_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                             const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                             const wdx_refine_params *rp, double *d_fpt, int64_t *d_dwell, double *d_stats,
+                             int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call, int64_t *d_counts,
+                             void *d_work, void *stream) {
+    if (!rp) {
+        set_error("demux_refine_adc_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (int e = adc_dev_in_ok("demux_refine_adc_dev", in)) return e;
+    wdx_seg_params pv;
+    if (int e = refine_seg_params("demux_refine_adc_dev", p, rp, &pv)) return e;
+    return demux_dev_rows(ctx, DevRows(in, max_len, n_reads, d_a_start, d_a_end, d_ok), &pv, rp, d_fpt, d_dwell, d_stats,
+                          d_refine_idx, d_status, d_dist, d_call, d_counts, d_work, stream);
 }
 
 int wdx_calibrate_adc_dev(wdx_ctx *ctx, const int16_t *d_adc, const int64_t *d_row_off, const int32_t *d_row_len,

@@ -129,6 +129,119 @@ static int svm_fused_route(wdx_ctx *ctx, const double *fpt, int64_t n_reads, dou
     return WDX_SUCCESS;
 }
 
+// ---- wdx_demux_{svm,mlp,boost}_dev and their *_adc_dev twins (int16 device shards): one body each, on the entry's DevRows ----
+
+int wdx::demux_svm_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_params *p, double *d_fpt, int32_t *d_status,
+                            float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, int64_t block_rows,
+                            void *stream) {
+    WDX_ENTER(ctx);
+    if (rd.f32.n_reads < 0 || !p || block_rows < 0 ||
+        (rd.f32.n_reads > 0 && (rd.missing() || !rd.f32.a_start || !rd.f32.a_end || !d_status || !d_work))) {
+        set_error("demux_svm_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_SVM, R.nY, 0, false, "demux_svm_dev"))) return rc;
+    if ((rc = check_ref_length(R, *p))) return rc;
+    if (rd.f32.n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int k = ctx->svm.k;
+    // (R.any_inf: the fused form has no distance matrix for launch_dtw_equal_inf to settle -- the row blocks do)
+    const bool fused = !d_dist && R.L == 25 && R.window == 15 && !ctx->knobs.no_short_dtw && !ctx->knobs.svm_scalar && k >= 2 &&
+                       k <= 16 && ctx->svm_chunks > 0 && !R.any_inf;
+    return for_each_slice(ctx, rd, false, p->padding, s, [&](const FpReads &in, int64_t r0) {
+        int rc = WDX_SUCCESS;
+        const int64_t n_reads = in.n_reads;
+        // ASYMMETRY, kept: an explicit block_rows below 2048 is raised to 2048 here; wdx_demux_mlp_dev honours it
+        const int64_t rows = std::min(n_reads, block_rows > 0 ? std::max<int64_t>(block_rows, 2048) : default_block_rows(R.nY));
+        if (!d_dist && !fused && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
+        double *prob = from_read(d_prob, r0, k), *conf = from_read(d_conf, r0);
+        int32_t *pred = from_read(d_pred, r0), *status = d_status + r0;
+        const double *fpt = nullptr;
+        if ((rc = demux_fingerprints(ctx, in, *p, from_read(d_fpt, r0, R.L), status, d_work, s, &fpt))) return rc;
+        if (fused)
+            rc = svm_fused_route(ctx, fpt, n_reads, prob, pred, conf, s);
+        else
+            rc = dtw_row_blocks(ctx, fpt, n_reads, rows, from_read(d_dist, r0, R.nY), s, [&](const float *dblk, int64_t b0, int64_t m) {
+                return svm_tail(ctx, ctx->svm, dblk, m, nullptr, from_read(prob, b0, k), from_read(pred, b0), from_read(conf, b0), s);
+            });
+        if (rc) return rc;
+        // failed reads are masked ONCE over all reads (of an int16 shard: of the slice), behind the last block
+        return launch_svm_mask_failed(status, n_reads, k, prob, pred, conf, s);
+    });
+}
+
+int wdx::demux_mlp_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_params *p, double *d_fpt, int32_t *d_status,
+                            float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite,
+                            void *d_work, int64_t block_rows, void *stream) {
+    WDX_ENTER(ctx);
+    if (rd.f32.n_reads < 0 || !p || block_rows < 0 ||
+        (rd.f32.n_reads > 0 && (rd.missing() || !rd.f32.a_start || !rd.f32.a_end || !d_status || !d_work))) {
+        set_error("demux_mlp_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_MLP, R.nY, 0, false, "demux_mlp_dev"))) return rc;
+    if ((rc = check_ref_length(R, *p))) return rc;
+    if (rd.f32.n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const int k = ctx->mlp.k;
+    return for_each_slice(ctx, rd, false, p->padding, s, [&](const FpReads &in, int64_t r0) {
+        int rc = WDX_SUCCESS;
+        const int64_t n_reads = in.n_reads;
+        // ASYMMETRY, kept: an explicit block_rows is honoured as given; wdx_demux_svm_dev raises it to 2048
+        const int64_t rows = std::min(n_reads, block_rows > 0 ? block_rows : default_block_rows(R.nY));
+        if (!d_dist && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
+        const double *fpt = nullptr;
+        if ((rc = demux_fingerprints(ctx, in, *p, from_read(d_fpt, r0, R.L), d_status + r0, d_work, s, &fpt))) return rc;
+        // (failed reads are masked by the kernel itself, block by block: its d_status argument)
+        return dtw_row_blocks(ctx, fpt, n_reads, rows, from_read(d_dist, r0, R.nY), s, [&](const float *dblk, int64_t b0, int64_t m) {
+            Timed t(ctx, WDX_K_MLP, s);
+            return launch_mlp_predict(ctx->mlp, dblk, m, d_status + r0 + b0, from_read(d_prob, r0 + b0, k),
+                                      from_read(d_pred, r0 + b0), from_read(d_conf, r0 + b0), d_n_nonfinite, s);
+        });
+    });
+}
+
+int wdx::demux_boost_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_params *p, const wdx_refine_params *rp,
+                              double *d_fpt, int32_t *d_refine_idx, int32_t *d_status, double *d_raw, double *d_prob,
+                              int32_t *d_pred, double *d_conf, void *d_work, void *stream) {
+    WDX_ENTER(ctx);
+    if (rd.f32.n_reads < 0 ||
+        (rd.f32.n_reads > 0 && (rd.missing() || !rd.f32.a_start || !rd.f32.a_end || !d_status || !d_work))) {
+        set_error("demux_boost_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    wdx_seg_params pv;
+    if ((rc = refine_seg_params("demux_boost_dev", p, rp, &pv))) return rc;
+    const int64_t K = pv.barcode_num_events;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_BOOST, 0, K, rp != nullptr, "demux_boost_dev"))) return rc;
+    if (rd.f32.n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    // d_work as wdx_demux_refine_dev lays it out: [fpt][fingerprint workspace] | the refinement kernels' hand-over records
+    unsigned char *w = (unsigned char *)d_work;
+    const BoostDev &M = ctx->boost;
+    return for_each_slice(ctx, rd, rp != nullptr, pv.padding, s, [&](const FpReads &in, int64_t r0) {
+        const DemuxWork W = demux_work_layout(in.n_reads, K, false);
+        double *fpt = d_fpt ? d_fpt + r0 * K : (double *)w;
+        ChainTail tail;
+        tail.kind = WDX_LIVE_TAIL_BOOST;
+        tail.boost = &M;
+        ChainOut out{FpOut{fpt, nullptr, nullptr, d_status + r0}};
+        out.raw = from_read(d_raw, r0, M.dim), out.prob = from_read(d_prob, r0, M.k);
+        out.pred = from_read(d_pred, r0), out.conf = from_read(d_conf, r0);
+        // (no DTW here, whatever is resident: an empty reference set)
+        return demux_chain(ctx, DtwRefs{}, in, pv, rp, from_read(d_refine_idx, r0, 3), w + round_up(W.bytes, 256), w + W.fp_ws, !rp,
+                           tail, out, s);
+    });
+}
+
 extern "C" {
 
 int wdx_svm_set_model(wdx_ctx *ctx, const wdx_svm_model *m) {
@@ -247,38 +360,17 @@ int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
                       int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
                       const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
                       double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, int64_t block_rows, void *stream) {
-    WDX_ENTER(ctx);
-    if (n_reads < 0 || !p || block_rows < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
-        set_error("demux_svm_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    DtwRefs &R = ctx->refs;
-    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_SVM, R.nY, 0, false, "demux_svm_dev"))) return rc;
-    if ((rc = check_ref_length(R, *p))) return rc;
-    if (n_reads == 0) return WDX_SUCCESS;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->svm.k;
-    // ASYMMETRY, kept: an explicit block_rows below 2048 is raised to 2048 here; wdx_demux_mlp_dev honours it
-    const int64_t rows = std::min(n_reads, block_rows > 0 ? std::max<int64_t>(block_rows, 2048) : default_block_rows(R.nY));
-    // (R.any_inf: the fused form has no distance matrix for launch_dtw_equal_inf to settle -- the row blocks do)
-    const bool fused = !d_dist && R.L == 25 && R.window == 15 && !ctx->knobs.no_short_dtw && !ctx->knobs.svm_scalar && k >= 2 &&
-                       k <= 16 && ctx->svm_chunks > 0 && !R.any_inf;
-    if (!d_dist && !fused && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
-    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    const double *fpt = nullptr;
-    if ((rc = demux_fingerprints(ctx, in, *p, d_fpt, d_status, d_work, s, &fpt))) return rc;
-    if (fused)
-        rc = svm_fused_route(ctx, fpt, n_reads, d_prob, d_pred, d_conf, s);
-    else
-        rc = dtw_row_blocks(ctx, fpt, n_reads, rows, d_dist, s, [&](const float *dblk, int64_t r0, int64_t m) {
-            return svm_tail(ctx, ctx->svm, dblk, m, nullptr, d_prob ? d_prob + r0 * k : nullptr, d_pred ? d_pred + r0 : nullptr,
-                            d_conf ? d_conf + r0 : nullptr, s);
-        });
-    if (rc) return rc;
-    // failed reads are masked ONCE over all reads, behind the last block
-    return launch_svm_mask_failed(d_status, n_reads, k, d_prob, d_pred, d_conf, s);
+    return demux_svm_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok), p,
+                              d_fpt, d_status, d_dist, d_prob, d_pred, d_conf, d_work, block_rows, stream);
+}
+
+int wdx_demux_svm_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                          const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt,
+                          int32_t *d_status, float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf, void *d_work,
+                          int64_t block_rows, void *stream) {
+    if (int e = adc_dev_in_ok("demux_svm_adc_dev", in)) return e;
+    return demux_svm_dev_rows(ctx, DevRows(in, max_len, n_reads, d_a_start, d_a_end, d_ok), p, d_fpt, d_status, d_dist, d_prob,
+                              d_pred, d_conf, d_work, block_rows, stream);
 }
 
 int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf) {
@@ -467,31 +559,17 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
                       const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt, int32_t *d_status, float *d_dist,
                       double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
                       int64_t block_rows, void *stream) {
-    WDX_ENTER(ctx);
-    if (n_reads < 0 || !p || block_rows < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
-        set_error("demux_mlp_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    DtwRefs &R = ctx->refs;
-    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_MLP, R.nY, 0, false, "demux_mlp_dev"))) return rc;
-    if ((rc = check_ref_length(R, *p))) return rc;
-    if (n_reads == 0) return WDX_SUCCESS;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->mlp.k;
-    // ASYMMETRY, kept: an explicit block_rows is honoured as given; wdx_demux_svm_dev raises it to 2048
-    const int64_t rows = std::min(n_reads, block_rows > 0 ? block_rows : default_block_rows(R.nY));
-    if (!d_dist && (rc = ctx->out0.ensure((size_t)(rows * R.nY) * 4))) return rc;
-    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    const double *fpt = nullptr;
-    if ((rc = demux_fingerprints(ctx, in, *p, d_fpt, d_status, d_work, s, &fpt))) return rc;
-    // (failed reads are masked by the kernel itself, block by block: its d_status argument)
-    return dtw_row_blocks(ctx, fpt, n_reads, rows, d_dist, s, [&](const float *dblk, int64_t r0, int64_t m) {
-        Timed t(ctx, WDX_K_MLP, s);
-        return launch_mlp_predict(ctx->mlp, dblk, m, d_status + r0, d_prob ? d_prob + r0 * k : nullptr,
-                                  d_pred ? d_pred + r0 : nullptr, d_conf ? d_conf + r0 : nullptr, d_n_nonfinite, s);
-    });
+    return demux_mlp_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok), p,
+                              d_fpt, d_status, d_dist, d_prob, d_pred, d_conf, d_n_nonfinite, d_work, block_rows, stream);
+}
+
+int wdx_demux_mlp_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads, const int32_t *d_a_start,
+                          const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p, double *d_fpt,
+                          int32_t *d_status, float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf,
+                          int64_t *d_n_nonfinite, void *d_work, int64_t block_rows, void *stream) {
+    if (int e = adc_dev_in_ok("demux_mlp_adc_dev", in)) return e;
+    return demux_mlp_dev_rows(ctx, DevRows(in, max_len, n_reads, d_a_start, d_a_end, d_ok), p, d_fpt, d_status, d_dist, d_prob,
+                              d_pred, d_conf, d_n_nonfinite, d_work, block_rows, stream);
 }
 
 // ---- Fpt_Boost: oblivious trees on the fingerprint rows (wdx_boost.hip) ----------------------------------
@@ -669,31 +747,17 @@ int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
                         const uint8_t *d_ok, const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt,
                         int32_t *d_refine_idx, int32_t *d_status, double *d_raw, double *d_prob, int32_t *d_pred,
                         double *d_conf, void *d_work, void *stream) {
-    WDX_ENTER(ctx);
-    if (n_reads < 0 || (n_reads > 0 && (!d_sig || !d_a_start || !d_a_end || !d_status || !d_work))) {
-        set_error("demux_boost_dev: bad arguments");
-        return WDX_ERR_INVALID;
-    }
-    wdx_seg_params pv;
-    if ((rc = refine_seg_params("demux_boost_dev", p, rp, &pv))) return rc;
-    const int64_t K = pv.barcode_num_events;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = tail_ready(ctx, WDX_LIVE_TAIL_BOOST, 0, K, rp != nullptr, "demux_boost_dev"))) return rc;
-    if (n_reads == 0) return WDX_SUCCESS;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    // d_work as wdx_demux_refine_dev lays it out: [fpt][fingerprint workspace] | the refinement kernels' hand-over records
-    unsigned char *w = (unsigned char *)d_work;
-    const DemuxWork W = demux_work_layout(n_reads, K, false);
-    double *fpt = d_fpt ? d_fpt : (double *)w;
-    const FpReads in{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok};
-    ChainTail tail;
-    tail.kind = WDX_LIVE_TAIL_BOOST;
-    tail.boost = &ctx->boost;
-    ChainOut out{FpOut{fpt, nullptr, nullptr, d_status}};
-    out.raw = d_raw, out.prob = d_prob, out.pred = d_pred, out.conf = d_conf;
-    // (no DTW here, whatever is resident: an empty reference set)
-    return demux_chain(ctx, DtwRefs{}, in, pv, rp, d_refine_idx, w + round_up(W.bytes, 256), w + W.fp_ws, !rp, tail, out, s);
+    return demux_boost_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok), p,
+                                rp, d_fpt, d_refine_idx, d_status, d_raw, d_prob, d_pred, d_conf, d_work, stream);
+}
+
+int wdx_demux_boost_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads,
+                            const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok, const wdx_seg_params *p,
+                            const wdx_refine_params *rp, double *d_fpt, int32_t *d_refine_idx, int32_t *d_status,
+                            double *d_raw, double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, void *stream) {
+    if (int e = adc_dev_in_ok("demux_boost_adc_dev", in)) return e;
+    return demux_boost_dev_rows(ctx, DevRows(in, max_len, n_reads, d_a_start, d_a_end, d_ok), p, rp, d_fpt, d_refine_idx,
+                                d_status, d_raw, d_prob, d_pred, d_conf, d_work, stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include "../../include/wdx.h"
 #include "wdx_window.h"
+#include "wdx_adc_dev.h"
 
 namespace wdx {
 
@@ -47,6 +48,7 @@ struct Knobs {
     int boost_kernel = 0;            // WDX_OPT_BOOST_KERNEL: 0 by batch size | 1 lane-per-read | 2 tree-parallel
     bool long_windows = false;       // WDX_OPT_LONG_WINDOWS: adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (product option)
     bool long_refine_windows = false;   // WDX_OPT_LONG_REFINE_WINDOWS: the same for the consensus-refinement branch (product option)
+    int64_t adc_dev_slice_reads = 0;    // WDX_OPT_ADC_DEV_SLICE_READS: reads per slice of an int16 device shard (0 = built-in)
     // the long form of the exact kernel serves this call (wdx_window.h: the refinement branch has its own option)
     bool long_form(bool refine) const { return long_form_on(refine, long_windows, long_refine_windows); }
     // the longest adapter window a call of this branch fingerprints (the host loops cut one sample beyond it: that reports it)
@@ -283,5 +285,24 @@ struct AdcRows {
 };
 // over_the_bus: pack_windows_adc_kernel (src = a page-locked host minibatch), else decode_adc_kernel
 int launch_adc_rows(const AdcRows &A, int64_t n_reads, bool over_the_bus, hipStream_t stream);
+
+// One slice of an int16 DEVICE shard (wdx_adc_dev_in; wdx_adc_dev.h) -> the staged float32 windows of reads r0 .. r0 + n - 1
+// and what the chain needs to read them: staged read i = dst + i * pitch, a_start_out / a_end_out / row_len_out int32[n].
+// The shard's arrays are indexed by the read's number in the shard (r0 + i), the outputs by i.
+struct AdcDevWindows {
+    const int16_t *adc;
+    const int64_t *row_off;   // packed: int64[n_reads + 1], multiples of 8; null = (n_reads, stride) rows
+    int64_t stride;
+    const int32_t *row_len, *row_win;   // row_win nullable (packed only)
+    const float *offset, *scale;
+    const int32_t *a_start, *a_end;
+    const uint8_t *ok;        // nullable
+    int64_t padding, max_len; // wdx_seg_params.padding; adc_dev_max_len's answer
+    int64_t r0, n;
+    float *dst;
+    int64_t pitch;
+    int32_t *a_start_out, *a_end_out, *row_len_out;
+};
+int launch_adc_dev_windows(const AdcDevWindows &A, hipStream_t stream);
 
 }  // namespace wdx

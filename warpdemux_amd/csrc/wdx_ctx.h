@@ -16,7 +16,8 @@ namespace wdx {
 struct Buffer {  // grow-only device workspace
     void *p = nullptr;
     size_t bytes = 0;
-    int ensure(size_t need);
+    // exact: allocate `need` bytes and no head-room (a block whose size is a stated bound: the int16 shards' staging)
+    int ensure(size_t need, bool exact = false);
     void release();
 };
 
@@ -27,7 +28,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 11;
+constexpr int kNumTimed = 12;
 
 // RAII: make the context's device current for the duration of one entry point and put the caller's
 // device back afterwards (a host thread that also drives torch must not find its device switched).
@@ -66,6 +67,9 @@ struct wdx_ctx {
     wdx::Buffer pk_idx;       // packed staging of a page-locked minibatch: window offsets / first columns / shifted bounds
     wdx::PinnedBuffer pk_host;  // ... and their host images (kept until the slot's copy has run)
     wdx::Buffer in_adc;       // int16 ADC rows as they arrived by DMA copy, ahead of decode_adc_kernel (wdx_adc.hip)
+    // float32 staging of an int16 DEVICE shard, one slice at a time (wdx_adc_dev.h: rows, then the slice's shifted bounds and
+    // packed lengths); reused in stream order by every slice and every *_adc_dev call
+    wdx::Buffer adc_stage;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     wdx::SvmDev svm{};
     bool svm_set = false;
@@ -199,6 +203,68 @@ struct ChainOut {
 WDX_INTERNAL int demux_chain(wdx_ctx *B, const DtwRefs &R, const FpReads &rd, const wdx_seg_params &p, const wdx_refine_params *rp,
                 int32_t *d_refine_idx, void *d_refine_ws, void *d_fp_ws, bool main_events, const ChainTail &tail,
                 const ChainOut &out, hipStream_t s);
+
+// The rows of a device-resident entry as it got them -- what the float32 entries and their *_adc_dev twins hand to ONE body:
+// float32 rows (`f32` whole), or an int16 shard (`adc` non-null; of f32 only max_len, n_reads, a_start, a_end and ok are
+// read).  for_each_slice gives the body the reads as the chain takes them and the number of the first one: the float32
+// rows in one piece, the shard slice by slice from the context's staging block (wdx_adc_dev.h).
+struct DevRows {
+    FpReads f32;
+    const wdx_adc_dev_in *adc = nullptr;
+    DevRows(const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride, int64_t max_len,
+            int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok)
+        : f32{d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok} {}
+    DevRows(const wdx_adc_dev_in *in, int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end,
+            const uint8_t *d_ok)
+        : f32{nullptr, nullptr, nullptr, 0, max_len, n_reads, d_a_start, d_a_end, d_ok}, adc(in) {}
+    // n_reads > 0 and no samples to read: the entry's "bad arguments"
+    bool missing() const { return adc ? !adc->adc || !adc->row_len || !adc->offset || !adc->scale : !f32.sig; }
+};
+// (wdx_api.hip) the shard descriptor of an *_adc_dev entry is there and names a layout ("<who>: bad arguments" otherwise)
+int adc_dev_in_ok(const char *who, const wdx_adc_dev_in *in);
+// (wdx_api.hip) the slices of a call on this context (its slice option, the longest window of its branch) ...
+AdcDevPlan adc_dev_plan_for(const wdx_ctx *ctx, int64_t n_reads, int64_t max_len, bool refine);
+// ... and reads r0 .. r0 + m - 1 of the shard decoded into B->adc_stage (already sized) on s; *rd = the slice for the chain
+int adc_dev_stage(wdx_ctx *B, const DevRows &rows, const AdcDevPlan &plan, bool refine, int64_t padding, int64_t r0, int64_t m,
+                  hipStream_t s, FpReads *rd);
+// With the context's mutex held, after use_stream(B, s).  body(const FpReads &, int64_t r0) -> int.
+template <class Body>
+int for_each_slice(wdx_ctx *B, const DevRows &rows, bool refine, int64_t padding, hipStream_t s, Body body) {
+    if (!rows.adc) return body(rows.f32, (int64_t)0);
+    const AdcDevPlan plan = adc_dev_plan_for(B, rows.f32.n_reads, rows.f32.max_len, refine);
+    if (plan.n_slices == 0) return WDX_SUCCESS;
+    if (int rc = B->adc_stage.ensure((size_t)plan.staging_bytes, true)) return rc;   // never beyond the budget
+    for (int64_t k = 0; k < plan.n_slices; ++k) {
+        FpReads rd;
+        const int64_t r0 = k * plan.slice_reads, m = k + 1 < plan.n_slices ? plan.slice_reads : plan.last_reads;
+        if (int rc = adc_dev_stage(B, rows, plan, refine, padding, r0, m, s, &rd)) return rc;
+        if (int rc = body(rd, r0)) return rc;
+    }
+    return WDX_SUCCESS;
+}
+// an output of `cols` values per read, from read r0 on (null stays null)
+template <class T>
+inline T *from_read(T *p, int64_t r0, int64_t cols = 1) { return p ? p + r0 * cols : nullptr; }
+
+// (wdx_api.hip / wdx_classify.hip) The device-resident entries behind their argument lists: the float32 entry and its
+// *_adc_dev twin call the same function with their DevRows.
+int fingerprint_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell,
+                         double *d_stats, int32_t *d_status, void *stream);
+int fingerprint_refine_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p_in, const wdx_refine_params *rp,
+                                double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_refine_idx, int32_t *d_status,
+                                void *stream);
+int demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt,
+                   int64_t *d_dwell, double *d_stats, int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call,
+                   int64_t *d_counts, void *d_work, void *stream);
+int demux_svm_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, double *d_fpt, int32_t *d_status,
+                       float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, int64_t block_rows,
+                       void *stream);
+int demux_mlp_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, double *d_fpt, int32_t *d_status,
+                       float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
+                       int64_t block_rows, void *stream);
+int demux_boost_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, const wdx_refine_params *rp,
+                         double *d_fpt, int32_t *d_refine_idx, int32_t *d_status, double *d_raw, double *d_prob,
+                         int32_t *d_pred, double *d_conf, void *d_work, void *stream);
 
 }  // namespace wdx
 

@@ -12,6 +12,14 @@
 
 #include "../../include/wdx.h"
 
+// The rule is also evaluated per read ON the device (wdx_adc.hip: the int16 device shards), from this very text: hipcc
+// compiles the functions below for both sides, the system compiler sees plain inline functions.
+#ifdef __HIPCC__
+#define WDX_HD __attribute__((host)) __attribute__((device))
+#else
+#define WDX_HD
+#endif
+
 namespace wdx {
 
 // The longest adapter window a call fingerprints -- the one statement of which product option raises it: a call of the
@@ -45,7 +53,7 @@ struct Window {
 // row_len >= 0: the read's own samples, which `valid` is counted against (int16 rows have no NaN tail to end them).
 // The start is clamped to the row BEFORE it is aligned: a start beyond the row (a failed detection's garbage) takes
 // nothing instead of samples of the next row.  A dead read or an empty window: row = valid = win = 0, bounds unshifted.
-inline Window adapter_window(int32_t a_start, int32_t a_end, int64_t limit, bool dead, const WindowOpts &o,
+WDX_HD inline Window adapter_window(int32_t a_start, int32_t a_end, int64_t limit, bool dead, const WindowOpts &o,
                              int64_t row_len = -1) {
     Window w;
     w.a_start = a_start;

@@ -28,6 +28,75 @@ def _dp(t):
 
 
 @dataclass
+class AdcShard:
+    """Raw int16 ADC reads that stay int16 in HBM (wdx_adc_dev_in, include/wdx.h), accepted wherever a `DemuxEngine` method
+    takes ``sig``: read r stands for the float32 row ``scale[r] * (float32(adc) + offset[r])`` -- float32 add, then float32
+    multiply, `sig_proc.calibrate_adc` -- with a NaN tail behind its ``row_len[r]`` samples, and every method returns, bit
+    for bit, what it returns on those float32 rows.  Only that formula: a reader that calibrates otherwise must not use it.
+
+    ``adc``: int16 device tensor -- (n, stride) rows (``stride`` defaults to its second dimension), or packed reads with
+    int64 ``offsets`` of n + 1 entries, each a multiple of 8; ``row_len`` int32 (n,), ``offset`` / ``scale`` float32 (n,);
+    ``row_win`` (packed only, optional) int32 (n,): samples of the float32 row read r stands for, the NaN tail included.
+    ``a_start`` / ``a_end`` of the call are relative to the row.  The method's own ``offsets=`` / ``stride=`` are not used."""
+    adc: "object"
+    row_len: "object"
+    offset: "object"
+    scale: "object"
+    offsets: Optional["object"] = None
+    stride: int = 0
+    row_win: Optional["object"] = None
+
+    def __post_init__(self):
+        torch = _torch()
+        want = [("adc", self.adc, torch.int16), ("row_len", self.row_len, torch.int32), ("offset", self.offset, torch.float32),
+                ("scale", self.scale, torch.float32), ("offsets", self.offsets, torch.int64), ("row_win", self.row_win, torch.int32)]
+        for name, t, dt in want:
+            if t is None:
+                continue
+            if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"AdcShard.{name} must be a contiguous {dt} device tensor")
+        n = int(self.row_len.shape[0])
+        if tuple(self.offset.shape) != (n,) or tuple(self.scale.shape) != (n,):
+            raise ValueError("AdcShard: row_len, offset and scale hold one entry per read")
+        if self.offsets is not None:
+            if tuple(self.offsets.shape) != (n + 1,):
+                raise ValueError("AdcShard.offsets holds n + 1 entries")
+        else:
+            if self.row_win is not None:
+                raise ValueError("AdcShard.row_win describes packed reads: give `offsets`")
+            if not self.stride:
+                if self.adc.dim() != 2:
+                    raise ValueError("packed reads need `offsets`, strided ones a 2-D `adc` or `stride`")
+                self.stride = int(self.adc.shape[1])
+        if self.row_win is not None and tuple(self.row_win.shape) != (n,):
+            raise ValueError("AdcShard.row_win holds one entry per read")
+        # the kernel reads adc through these numbers: what the shapes can show is checked here, on the host
+        if self.offsets is None:
+            if self.stride < 0 or (self.adc.dim() == 2 and (int(self.adc.shape[0]) != n or int(self.adc.shape[1]) != self.stride)):
+                raise ValueError(f"AdcShard: a 2-D adc holds one row of `stride` samples per read ({n} x {self.stride}), "
+                                 f"not {tuple(self.adc.shape)}")
+            if int(self.adc.numel()) < n * int(self.stride):
+                raise ValueError(f"AdcShard.adc holds {int(self.adc.numel())} samples, {n} rows of {self.stride} need more")
+        elif n and int(self.adc.numel()) < int(self.offsets[-1].item()):
+            raise ValueError(f"AdcShard.adc holds {int(self.adc.numel())} samples, its last offset is "
+                             f"{int(self.offsets[-1].item())}")
+
+    @property
+    def n_reads(self):
+        return int(self.row_len.shape[0])
+
+    def to_c(self):
+        return _lib.AdcDevInC(adc=self.adc.data_ptr(), row_off=None if self.offsets is None else self.offsets.data_ptr(),
+                              stride=int(self.stride), row_len=self.row_len.data_ptr(), offset=self.offset.data_ptr(),
+                              scale=self.scale.data_ptr(), row_win=None if self.row_win is None else self.row_win.data_ptr())
+
+    def nbytes(self):
+        """device bytes the shard's tensors hold"""
+        ts = [self.adc, self.row_len, self.offset, self.scale, self.offsets, self.row_win]
+        return sum(int(t.numel()) * t.element_size() for t in ts if t is not None)
+
+
+@dataclass
 class DemuxResult:
     dist: "object"      # torch float32 (n, nY)
     call: "object"      # torch int32 (n,)  argmin column, -1 for failed reads
@@ -72,11 +141,43 @@ class DemuxEngine:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
 
+    # -- the rows of a call: float32 `sig`, or an AdcShard ------------------------------------------------
+    def _rows(self, name, sig, offsets, stride, max_len, n):
+        """(entry, the arguments between the context and a_start) of device entry ``name`` for these rows: the float32 entry
+        itself, or its ``_adc_dev`` twin for an `AdcShard` (whose descriptor stays alive in the returned tuple)."""
+        if not isinstance(sig, AdcShard):
+            return getattr(self.L, name), (_dp(sig), _dp(offsets), None, int(stride), int(max_len), n)
+        if offsets is not None or stride:
+            raise ValueError("an AdcShard carries its own offsets / stride")
+        if sig.n_reads != n:
+            raise ValueError(f"the AdcShard holds {sig.n_reads} reads, a_start {n}")
+        desc = sig.to_c()
+        return getattr(self.L, name[:-len("_dev")] + "_adc_dev"), (C.byref(desc), int(max_len), n)
+
+    def _work_for(self, sig, n, max_len, K, refine):
+        """the d_work tensor of a call with these rows (grown on demand): the float32 entries size it by n, the int16 twins by
+        their largest slice (wdx_demux[_refine]_adc_workspace_bytes)"""
+        if isinstance(sig, AdcShard):
+            f = self.L.wdx_demux_refine_adc_workspace_bytes if refine else self.L.wdx_demux_adc_workspace_bytes
+            need = int(f(self.ctx.handle, n, int(max_len), K))
+        else:
+            need = int((self.L.wdx_demux_refine_workspace_bytes if refine else self.L.wdx_demux_workspace_bytes)(n, K))
+        attr = "_refine_work" if refine else "_work"
+        w = getattr(self, attr)
+        if w is None or w.numel() < need:
+            w = self.torch.empty(need, dtype=self.torch.uint8, device=self.tdev)
+            setattr(self, attr, w)
+        return w
+
+    def adc_staging_bytes(self, n, max_len, refine=False):
+        """device bytes of the float32 staging block an `AdcShard` call of n reads needs on this engine's context"""
+        return int(self.L.wdx_adc_dev_staging_bytes(self.ctx.handle, int(n), int(max_len), int(bool(refine))))
+
     # -- fused path --------------------------------------------------------------------------------
     def demux(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None,
               counts=None, want_fpt=False, out: Optional[DemuxResult] = None) -> DemuxResult:
         """sig: float32 device tensor, packed (with int64 ``offsets`` of n+1) or a (n, stride)
-        minibatch; a_start/a_end: int32 device tensors.  Enqueues on the current stream."""
+        minibatch -- or an `AdcShard`; a_start/a_end: int32 device tensors.  Enqueues on the current stream."""
         torch = self.torch
         n = int(a_start.shape[0])
         if out is None:
@@ -88,10 +189,11 @@ class DemuxEngine:
                 fpt=torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None,
             )
         pc = self.params.to_c()
-        _lib.check(self.L.wdx_demux_dev(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n,
+        entry, rows = self._rows("wdx_demux_dev", sig, offsets, stride, max_len, n)
+        _lib.check(entry(
+            self.ctx.handle, *rows,
             _dp(a_start), _dp(a_end), _dp(ok), C.byref(pc), _dp(out.fpt), None, None,
-            _dp(out.status), _dp(out.dist), _dp(out.call), _dp(out.counts), _dp(self._ensure_work(n)),
+            _dp(out.status), _dp(out.dist), _dp(out.call), _dp(out.counts), _dp(self._work_for(sig, n, max_len, self.K, False)),
             self._stream()))
         return out
 
@@ -104,8 +206,9 @@ class DemuxEngine:
         stats = torch.empty((n, 6), dtype=torch.float64, device=self.tdev) if want_stats else None
         status = torch.empty(n, dtype=torch.int32, device=self.tdev)
         pc = self.params.to_c()
-        _lib.check(self.L.wdx_fingerprint_dev(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start),
+        entry, rows = self._rows("wdx_fingerprint_dev", sig, offsets, stride, max_len, n)
+        _lib.check(entry(
+            self.ctx.handle, *rows, _dp(a_start),
             _dp(a_end), _dp(ok), C.byref(pc), _dp(fpt), _dp(dwell), _dp(stats), _dp(status),
             self._stream()))
         return fpt, dwell, stats, status
@@ -115,7 +218,7 @@ class DemuxEngine:
         (fpt f64 (n,K), dwell i64 (n,K), stats f64 (n,6), refine_idx i32 (n,3), status i32), K = refine.barcode_keep_events."""
         torch = self.torch
         n = int(a_start.shape[0])
-        if offsets is None and not stride:
+        if not isinstance(sig, AdcShard) and offsets is None and not stride:
             if sig.dim() != 2:
                 raise ValueError("packed reads need `offsets`, a minibatch needs 2-D `sig` or `stride`")
             stride = int(sig.shape[1])     # (stride 0 would make every row alias row 0; ADVICE r3)
@@ -127,8 +230,9 @@ class DemuxEngine:
         status = torch.empty(n, dtype=torch.int32, device=self.tdev)
         pc = self.params.to_c()
         rc = refine.to_c()
-        _lib.check(self.L.wdx_fingerprint_refine_dev(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+        entry, rows = self._rows("wdx_fingerprint_refine_dev", sig, offsets, stride, max_len, n)
+        _lib.check(entry(
+            self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
             C.byref(pc), C.byref(rc), _dp(fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(status), self._stream()))
         return fpt, dwell, stats, idx, status
 
@@ -138,7 +242,7 @@ class DemuxEngine:
         (DemuxResult with fpt, dwell i64 (n,K), stats f64 (n,6), refine_idx i32 (n,3))."""
         torch = self.torch
         n = int(a_start.shape[0])
-        if offsets is None and not stride:
+        if not isinstance(sig, AdcShard) and offsets is None and not stride:
             if sig.dim() != 2:
                 raise ValueError("packed reads need `offsets`, a minibatch needs 2-D `sig` or `stride`")
             stride = int(sig.shape[1])
@@ -152,14 +256,13 @@ class DemuxEngine:
         dwell = torch.empty((n, K), dtype=torch.int64, device=self.tdev)
         stats = torch.empty((n, 6), dtype=torch.float64, device=self.tdev)
         idx = torch.empty((n, 3), dtype=torch.int32, device=self.tdev)
-        need = int(self.L.wdx_demux_refine_workspace_bytes(n, K))
-        if self._refine_work is None or self._refine_work.numel() < need:
-            self._refine_work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
+        work = self._work_for(sig, n, max_len, K, True)
         pc, rc = self.params.to_c(), refine.to_c()
-        _lib.check(self.L.wdx_demux_refine_dev(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+        entry, rows = self._rows("wdx_demux_refine_dev", sig, offsets, stride, max_len, n)
+        _lib.check(entry(
+            self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
             C.byref(pc), C.byref(rc), _dp(out.fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(out.status), _dp(out.dist),
-            _dp(out.call), _dp(out.counts), _dp(self._refine_work), self._stream()))
+            _dp(out.call), _dp(out.counts), _dp(work), self._stream()))
         return out, dwell, stats, idx
 
     def dtw(self, X, want_argmin=True, out=None):
@@ -180,12 +283,6 @@ class DemuxEngine:
         return dist, am
 
     # -- classifier tails: SVM, MLP (DTW_MLP), boosted trees (Fpt_Boost; 4.8) --------
-    def _ensure_work(self, n):
-        need = int(self.L.wdx_demux_workspace_bytes(n, self.K))
-        if self._work is None or self._work.numel() < need:
-            self._work = self.torch.empty(need, dtype=self.torch.uint8, device=self.tdev)
-        return self._work
-
     def _set_model(self, model, kind):
         """Upload ``model`` and record it as the owner of the context's ``kind`` slot."""
         if kind != "boost" and model._X.shape != (self.nY, self.K):
@@ -207,7 +304,7 @@ class DemuxEngine:
 
     def _demux_tail(self, entry, k, sig, a_start, a_end, offsets, stride, max_len, ok, want_dist, want_fpt, block_rows, out,
                     *extra):
-        """``entry`` (wdx_demux_{svm,mlp}_dev) on raw rows; ``extra``: arguments between conf and the workspace."""
+        """``entry`` (the name of wdx_demux_{svm,mlp}_dev) on raw rows; ``extra``: arguments between conf and the workspace."""
         torch = self.torch
         n = int(a_start.shape[0])
         if out is None:
@@ -219,10 +316,11 @@ class DemuxEngine:
                    torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None)
         prob, pred, conf, status, dist, fpt = out
         pc = self.params.to_c()
+        entry, rows = self._rows(entry, sig, offsets, stride, max_len, n)
         _lib.check(entry(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+            self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
             C.byref(pc), _dp(fpt), _dp(status), _dp(dist), _dp(prob), _dp(pred), _dp(conf), *extra,
-            _dp(self._ensure_work(n)), int(block_rows), self._stream()))
+            _dp(self._work_for(sig, n, max_len, self.K, False)), int(block_rows), self._stream()))
         return out
 
     def set_svm(self, model):
@@ -240,7 +338,7 @@ class DemuxEngine:
         """The shipped models' whole path, device-resident (wdx_demux_svm_dev): raw rows -> fingerprint -> DTW against
         the resident training set -> SVM tail.  Returns (prob f64 (n,k), pred i32 (n,), conf f64 (n,), status i32 (n,),
         dist f32 (n,nY) or None, fpt f64 (n,K) or None); ``out`` = such a tuple from an earlier call is reused."""
-        return self._demux_tail(self.L.wdx_demux_svm_dev, self.n_classes, sig, a_start, a_end, offsets, stride, max_len, ok,
+        return self._demux_tail("wdx_demux_svm_dev", self.n_classes, sig, a_start, a_end, offsets, stride, max_len, ok,
                                 want_dist, want_fpt, block_rows, out)
 
     def set_mlp(self, model):
@@ -257,7 +355,7 @@ class DemuxEngine:
                   want_fpt=False, block_rows: int = 0, n_nonfinite=None, out=None):
         """demux_svm with the MLP tail (wdx_demux_mlp_dev): raw rows -> fingerprint -> DTW row blocks -> MLP tail.  Returns
         (prob f64 (n,k), pred i32 (n,), conf f64 (n,), status i32 (n,), dist f32 (n,nY) or None, fpt f64 (n,K) or None)."""
-        return self._demux_tail(self.L.wdx_demux_mlp_dev, self.mlp_classes, sig, a_start, a_end, offsets, stride, max_len, ok,
+        return self._demux_tail("wdx_demux_mlp_dev", self.mlp_classes, sig, a_start, a_end, offsets, stride, max_len, ok,
                                 want_dist, want_fpt, block_rows, out, _dp(n_nonfinite))
 
     def set_boost(self, model):
@@ -289,7 +387,7 @@ class DemuxEngine:
         None, fpt f64 (n,K) or None, raw f64 (n,dim) or None)."""
         torch = self.torch
         n = int(a_start.shape[0])
-        if offsets is None and not stride:
+        if not isinstance(sig, AdcShard) and offsets is None and not stride:
             if sig.dim() != 2:
                 raise ValueError("packed reads need `offsets`, a minibatch needs 2-D `sig` or `stride`")
             stride = int(sig.shape[1])
@@ -301,15 +399,15 @@ class DemuxEngine:
         idx = torch.empty((n, 3), dtype=torch.int32, device=self.tdev) if refine is not None else None
         fpt = torch.empty((n, K), dtype=torch.float64, device=self.tdev) if want_fpt else None
         raw = torch.empty((n, self.boost_dim), dtype=torch.float64, device=self.tdev) if want_raw else None
-        need = int(self.L.wdx_demux_refine_workspace_bytes(n, K))
-        if self._refine_work is None or self._refine_work.numel() < need:
-            self._refine_work = torch.empty(need, dtype=torch.uint8, device=self.tdev)
+        # (float32 rows: the refine size, as always; a shard: the size of the branch the call takes, whose slices it is planned by)
+        work = self._work_for(sig, n, max_len, K, refine is not None or not isinstance(sig, AdcShard))
         pc = self.params.to_c()
         rc = refine.to_c() if refine is not None else None
-        _lib.check(self.L.wdx_demux_boost_dev(
-            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+        entry, rows = self._rows("wdx_demux_boost_dev", sig, offsets, stride, max_len, n)
+        _lib.check(entry(
+            self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
             C.byref(pc), C.byref(rc) if rc is not None else None, _dp(fpt), _dp(idx), _dp(status), _dp(raw), _dp(prob),
-            _dp(pred), _dp(conf), _dp(self._refine_work), self._stream()))
+            _dp(pred), _dp(conf), _dp(work), self._stream()))
         return prob, pred, conf, status, idx, fpt, raw
 
     # -- synthetic inputs, generated in HBM ----------------------------------------------------------

@@ -254,7 +254,11 @@ def calibrate_adc(adc, row_len, offset, scale, stride=None) -> np.ndarray:
     multiply: two roundings, never one fused operation -- and NaN from there to ``stride`` (the NaN tail of
     file_proc.py:255-260).  Every ``*_adc`` call returns, bit for bit, what its float32 counterpart returns on this array.
     A reader that calibrates by another formula (another order of operations, float64 arithmetic) is not served by the
-    int16 path: compare its rows with this function's first."""
+    int16 path: compare its rows with this function's first.
+
+    The same array is what an int16 shard that stays in device memory stands for: ``engine.AdcShard`` (the ``*_adc_dev``
+    entry points), accepted by every ``DemuxEngine`` method that takes ``sig`` -- a packed shard's row ends at ``row_win``
+    instead of ``stride``.  The same caveat applies there."""
     adc = np.asarray(adc)
     if adc.ndim != 2 or adc.dtype != np.int16:
         raise ValueError("adc must be a 2-D (n_reads, stride) int16 array")
