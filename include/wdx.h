@@ -168,6 +168,35 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
  * holds; a positive value is used as given wherever it stays inside that budget (tests walk several slices at small n);
  * negative: WDX_ERR_INVALID.  It changes which reads share a launch, never a result. */
 #define WDX_OPT_ADC_DEV_SLICE_READS 22
+/* A product option of the consensus-refinement branch: segmentation.refinement_optimal_cpts (sig_proc.py:348-354).  0 (default): the
+ * barcode tail of the score curve is cut at its strongest peaks.  1: it is cut at the least-squares OPTIMAL change-points, what the
+ * reference asks ruptures.KernelCPD(kernel="linear", min_size=min_obs_per_base).predict(n_bkps=barcode_num_events[0]) for; everything up
+ * to and including the subsequence match (stats, refine_idx, the outlier filter) is unchanged.  Any other value: WDX_ERR_INVALID.
+ * THE RULE, in float64 with no operation fused -- parity with ruptures' own bits is NOT pinned (the library is absent where this was
+ * built):
+ *   x = adapter_scores[sig_barcode_start:], the adapter's t-scores with the ADAPTED window width w_eff: N = max(0, n - 2 w_eff -
+ *   sig_barcode_start) samples; m = min_obs_per_base as configured; B = barcode_segm_events
+ *   P[0] = Q[0] = 0, P[t] = P[t-1] + x[t-1], Q[t] = Q[t-1] + x[t-1] * x[t-1]               (sequential)
+ *   cost(s, t) = (Q[t] - Q[s]) - ((P[t] - P[s]) * (P[t] - P[s])) / (double)(t - s)
+ *   V_0[t] = cost(0, t) for t >= m;  V_k[t] = min over s in [k m, t - m] of V_{k-1}[s] + cost(s, t), ties to the smallest s
+ *   valid_cpts = [0, b_1 .. b_B, N] by the back-trace from t = N, k = B; like the reference this branch adds no
+ *   running_stat_width to the boundaries and ends at N, not at the signal's end.  Dwell times = diff(valid_cpts): B + 1 of them.
+ *   Event means = the reference's compute_base_means(adapter_sig[sig_barcode_start:], valid_cpts), which closes the slice with one
+ *   more event when the last boundary is not its end: B + 2 means, the last over the 2 w_eff samples behind the score curve.  fpt =
+ *   the last barcode_keep_events of the normalize_wrt'ed means, dwell = the last barcode_keep_events dwell times -- as the
+ *   reference returns them, one event apart.  barcode_keep_events > B + 1 (the reference would return fewer dwell times than
+ *   fingerprint entries, or raise): WDX_READ_FAIL_UNKNOWN.
+ * Deviation: an infeasible tail ((B + 1) m > N) or a non-finite score in it is WDX_READ_FAIL_SEGMENT with NaN stats and refine_idx
+ * -1 (ruptures raises there and the reference's call dies).
+ * Honoured by every entry that takes rp: wdx_fingerprint_refine_batch, wdx_fingerprint_refine_dev / _adc_dev, wdx_demux_refine_dev /
+ * _adc_dev, wdx_demux_boost_dev / _adc_dev with rp, wdx_demux_submit_refine (a pipeline slot copies the options at every submit), a
+ * refine feeder ring served by this context, wdx_live_tick_ex with rp.  With the option on a call with rp returns
+ * WDX_ERR_UNSUPPORTED when WDX_OPT_LONG_REFINE_WINDOWS is 1 as well, when min_obs_per_base < 1, or when sig_extract.normalization is
+ * not WDX_NORM_NONE (no shipped configuration normalises the signal on this branch).  Cost: a per-read dynamic programme of B N^2 / 2
+ * candidates (fingerprint_refine_optimal_kernel, WDX_K_REFINE_OPTIMAL) and a context-owned scratch buffer of at most 256 MiB for the
+ * path tables of the reads in flight, allocated by the first refining call with the option on and never otherwise (each pipeline
+ * slot that meets one owns its own); workspaces and every allocation of the default path are unchanged. */
+#define WDX_OPT_REFINE_OPTIMAL_CPTS 23
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -251,7 +280,8 @@ typedef struct wdx_refine_params {
 /* As wdx_fingerprint_batch; K = rp->barcode_keep_events (p->barcode_num_events is ignored); stats are the ADAPTER's;
  * refine_idx (n_reads, 3) int32 = {seg_cons_query_start, seg_cons_query_end, sig_barcode_start} (-1 when the read
  * failed earlier).  Status WDX_READ_FAIL_CONSENSUS still reports stats and refine_idx, like the reference's
- * ReadResult.  Limits: num_events <= 127, refinement_optimal_cpts (ruptures KernelCPD) -> not offered. */
+ * ReadResult.  Limits: num_events <= 127; refinement_optimal_cpts (ruptures KernelCPD): WDX_OPT_REFINE_OPTIMAL_CPTS = 1 on the
+ * context (off by default; the rule and its limits are stated there). */
 int wdx_fingerprint_refine_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64_t stride,
                                  const int32_t *a_start, const int32_t *a_end, const uint8_t *ok,
                                  const wdx_seg_params *p, const wdx_refine_params *rp, double *fpt, int64_t *dwell,
@@ -921,6 +951,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_BOOST 10           /* the boost tail, whichever of its two kernels ran (wdx_boost_predict_dev, wdx_boost_predict,
                                     wdx_demux_boost_dev, WDX_WANT_BOOST minibatches) */
 #define WDX_K_ADC_DEV_WINDOWS 11 /* adc_dev_windows_kernel: the window decode ahead of every slice of an *_adc_dev call */
+#define WDX_K_REFINE_OPTIMAL 12   /* fingerprint_refine_optimal_kernel alone (WDX_OPT_REFINE_OPTIMAL_CPTS; part of WDX_K_FINGERPRINT) */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);
@@ -972,6 +1003,15 @@ int wdx_fingerprint_profile_dev(wdx_ctx *ctx, const float *d_sig, const int64_t 
  * on the kernel's value range (variance sums in [2^-402, 2^261], mean differences in {0} U [2^-201, 2^129]). */
 int wdx_selftest_score_dev(wdx_ctx *ctx, const double *d_dm, const double *d_vs, int64_t n, double *d_fast,
                            double *d_ref, void *stream);
+
+/* Self-test: the dynamic programme of WDX_OPT_REFINE_OPTIMAL_CPTS alone.  Series i = d_x[d_off[i] .. d_off[i + 1]) (float64, DEVICE;
+ * d_off int64[n_series + 1]), at most max_len <= WDX_MAX_ADAPTER_SAMPLES samples each; n_bkps (1..253) change-points, pieces of at
+ * least min_size samples (< 1: WDX_ERR_UNSUPPORTED).  d_cpts (n_series, n_bkps + 2) int32 = [0, b_1 .. b_B, N]; d_status[i] =
+ * WDX_READ_OK, or WDX_READ_FAIL_SEGMENT (infeasible, or a non-finite sample) / WDX_READ_FAIL_UNKNOWN (longer than max_len) with a
+ * row of -1.  max_slots > 0 bounds the workgroups (= slices of the context's scratch buffer) the series are walked by. */
+int wdx_selftest_optimal_cpts_dev(wdx_ctx *ctx, const double *d_x, const int64_t *d_off, int64_t n_series, int32_t n_bkps,
+                                  int32_t min_size, int64_t max_len, int32_t max_slots, int32_t *d_cpts, int32_t *d_status,
+                                  void *stream);
 
 /* Self-test of clip_bounds_kernel (A1 ahead of the fast fingerprint kernels: one wave per read): packed
  * reads (d_row_off int64[n_reads+1]) or rows of `stride` samples; cap = 4096, 5120 or 6144 selects the instantiation

@@ -28,6 +28,7 @@ K_FINGERPRINT, K_DTW, K_TRANSPOSE, K_COUNT, K_SVM, K_REDUCE, K_FINGERPRINT_MAIN,
 K_MLP = 9
 K_BOOST = 10
 K_ADC_DEV_WINDOWS = 11   # the window decode ahead of every slice of an *_adc_dev call (int16 device shards)
+K_REFINE_OPTIMAL = 12     # fingerprint_refine_optimal_kernel alone (OPT_REFINE_OPTIMAL_CPTS)
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -47,6 +48,8 @@ OPT_BOOST_KERNEL = 19   # 0 by batch size | 1 lane-per-read | 2 tree-parallel
 OPT_LONG_WINDOWS = 20   # product option: 1 = adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (0 / 1, else ValueError)
 OPT_LONG_REFINE_WINDOWS = 21   # ... the same for the consensus-refinement branch, which looks at this option only
 OPT_ADC_DEV_SLICE_READS = 22   # reads per slice of the *_adc_dev entries (0 = as many as the staging budget holds)
+OPT_REFINE_OPTIMAL_CPTS = 23   # product option of the refinement branch: barcode tails cut at their optimal change-points
+                               # (segmentation.refinement_optimal_cpts; ``RefineParams.optimal_cpts`` sets it)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -61,7 +64,7 @@ EXPORTS = [
     "wdx_host_alloc", "wdx_host_alloc_on", "wdx_host_free", "wdx_host_register", "wdx_host_unregister", "wdx_live_tick", "wdx_svm_set_model",
     "wdx_svm_predict_dev", "wdx_dtw_svm_predict", "wdx_demux_svm_dev", "wdx_demux_workspace_bytes", "wdx_demux_dev",
     "wdx_kernel_timing", "wdx_kernel_time", "wdx_kernel_time_reset", "wdx_dtw_last_launch", "wdx_synth_lengths_dev",
-    "wdx_synth_fill_dev", "wdx_fingerprint_profile_dev", "wdx_calib_read_dev", "wdx_selftest_score_dev", "wdx_selftest_clip_dev",
+    "wdx_synth_fill_dev", "wdx_fingerprint_profile_dev", "wdx_calib_read_dev", "wdx_selftest_score_dev", "wdx_selftest_clip_dev", "wdx_selftest_optimal_cpts_dev",
     "wdx_feeder_ring_bytes", "wdx_feeder_ring_init", "wdx_feeder_serve", "wdx_feeder_run", "wdx_feeder_demux", "wdx_feeder_predict", "wdx_feeder_stop",
     "wdx_feeder_served", "wdx_feeder_stats", "wdx_feeder_alive", "wdx_feeder_selftest",
     "wdx_mlp_set_model", "wdx_mlp_predict_dev", "wdx_dtw_mlp_predict", "wdx_demux_mlp_dev",
@@ -429,6 +432,8 @@ def load():
         L.wdx_kernel_time_reset.argtypes = [vp]
         L.wdx_fingerprint_profile_dev.restype = C.c_int
         L.wdx_fingerprint_profile_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, P(SegParamsC), vp, vp, i64, i32, i32, vp]
+        L.wdx_selftest_optimal_cpts_dev.restype = C.c_int
+        L.wdx_selftest_optimal_cpts_dev.argtypes = [vp, vp, vp, i64, i32, i32, i64, i32, vp, vp, vp]
         L.wdx_selftest_score_dev.restype = C.c_int
         L.wdx_selftest_score_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
         L.wdx_selftest_clip_dev.restype = C.c_int
@@ -577,6 +582,7 @@ class Context:
         self.pid = os.getpid()
         self.long_windows = False
         self.long_refine_windows = False
+        self.refine_optimal = False
 
     @property
     def handle(self):
@@ -594,6 +600,8 @@ class Context:
             self.long_windows = bool(value)
         elif int(option) == OPT_LONG_REFINE_WINDOWS:
             self.long_refine_windows = bool(value)
+        elif int(option) == OPT_REFINE_OPTIMAL_CPTS:
+            self.refine_optimal = bool(value)
 
     def set_long_windows(self):
         """Both product options on: what an object that owns its context does for ``long_windows=True`` -- its plain calls
@@ -626,6 +634,28 @@ class Context:
         finally:
             if bool(on) != before:
                 self.set_option(OPT_LONG_REFINE_WINDOWS, int(before))
+
+    @contextlib.contextmanager
+    def refine_options_for_call(self, refine, long_windows=None):
+        """The options of one call of the consensus-refinement branch on this context: OPT_REFINE_OPTIMAL_CPTS from
+        ``refine.optimal_cpts`` (None: a plain call, nothing changes) and, unless ``long_windows`` is None,
+        OPT_LONG_REFINE_WINDOWS -- for the call's duration, then what they were before, also when the call raises."""
+        on = bool(getattr(refine, "optimal_cpts", False))
+        before = getattr(self, "refine_optimal", False)
+        if on and (long_windows or (long_windows is None and getattr(self, "long_refine_windows", False))):
+            raise ValueError("optimal_cpts and long_windows do not go together (WDX_OPT_REFINE_OPTIMAL_CPTS serves adapter "
+                             "windows of up to MAX_ADAPTER_SAMPLES samples)")
+        if refine is not None and on != before:
+            self.set_option(OPT_REFINE_OPTIMAL_CPTS, int(on))
+        try:
+            if long_windows is None:
+                yield self
+            else:
+                with self.long_refine_windows_for_call(long_windows):
+                    yield self
+        finally:
+            if refine is not None and on != before:
+                self.set_option(OPT_REFINE_OPTIMAL_CPTS, int(before))
 
     def synchronize(self, stream=None):
         check(self._L.wdx_ctx_synchronize(self.handle, stream))

@@ -140,6 +140,15 @@ class Deployment(NamedTuple):
     n_classes: int              # columns of the tail's prob (0 without a model)
 
 
+def refine_options(refine, long_windows: bool, who: str) -> bool:
+    """``refine.optimal_cpts`` of an object that owns its context, checked against ``long_windows`` before the context exists."""
+    on = bool(getattr(refine, "optimal_cpts", False))
+    if on and long_windows:
+        raise ValueError(f"{who}: optimal_cpts and long_windows do not go together (WDX_OPT_REFINE_OPTIMAL_CPTS serves adapter "
+                         "windows of up to MAX_ADAPTER_SAMPLES samples)")
+    return on
+
+
 def deployment(refs, window, penalty, params, model, refine, *, who: str, models: tuple, nothing_to_serve: str,
                bare_refine: bool, refine_dtw: bool) -> Deployment:
     """THE rule of what a `MinibatchPipeline`, `Feeder` or `LiveDemux` serves, checked before any context exists

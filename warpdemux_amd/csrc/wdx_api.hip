@@ -160,6 +160,10 @@ Timed::~Timed() {
         c->pending[WDX_K_FINGERPRINT_TAIL].push_back(tp);
         c->pending_launches[WDX_K_FINGERPRINT_TAIL].push_back(1);
     }
+    for (const auto &tp : main.optimal) {
+        c->pending[WDX_K_REFINE_OPTIMAL].push_back(tp);
+        c->pending_launches[WDX_K_REFINE_OPTIMAL].push_back(1);
+    }
     if (main.c_first) {
         if (main.c_recorded) {
             c->pending[WDX_K_FINGERPRINT_CLIP].push_back({main.c_first, main.c_second});
@@ -191,9 +195,23 @@ int fingerprint_stage(wdx_ctx *B, const FpReads &in, const wdx_seg_params &p, co
     const bool with_long = B->knobs.long_form(rf != nullptr) && fingerprint_long_bytes(in.max_len) > 0;
     if (with_long)
         if (int rc = B->fp_long.ensure((size_t)fingerprint_long_bytes(in.max_len))) return rc;
+    // WDX_OPT_REFINE_OPTIMAL_CPTS: the scratch of the optimal change-points (path tables of the reads in flight), allocated by
+    // the first refining call with the option on and never otherwise
+    const bool optimal = rf != nullptr && B->knobs.refine_optimal;
+    if (optimal)
+        if (int rc = B->fp_opt.ensure((size_t)fingerprint_optimal_bytes(in.n_reads, in.max_len, refine_segm_events(rf)))) return rc;
     Timed t(B, WDX_K_FINGERPRINT, s);
-    return launch_fingerprint(in, p, out, s, d_ws, B->knobs, &t.n_launches, nullptr, 0, 0, rf,
-                              main_events ? &t.main : nullptr, (double *)B->fp_big.p, with_long ? B->fp_long.p : nullptr);
+    MainEvents only_optimal;   // (a caller that asked for no main-kernel events still gets the optimal kernel's pair)
+    MainEvents *ev = main_events ? &t.main : nullptr;
+    if (!ev && optimal && t.main.take) {
+        only_optimal.take = t.main.take;
+        only_optimal.take_arg = t.main.take_arg;
+        ev = &only_optimal;
+    }
+    const int rc = launch_fingerprint(in, p, out, s, d_ws, B->knobs, &t.n_launches, nullptr, 0, 0, rf, ev, (double *)B->fp_big.p,
+                                      with_long ? B->fp_long.p : nullptr, optimal ? B->fp_opt.p : nullptr);
+    for (const auto &tp : only_optimal.optimal) t.main.optimal.push_back(tp);
+    return rc;
 }
 
 int check_ref_length(const DtwRefs &R, const wdx_seg_params &p) {
@@ -561,7 +579,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     comm_destroy(ctx);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->adc_stage, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->fp_opt, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->adc_stage, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf, &ctx->mb_ridx})
         b->release();
     ctx->pin_in.release();
@@ -616,6 +634,13 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
                 return WDX_ERR_INVALID;
             }
             ctx->knobs.long_refine_windows = value == 1;
+            break;
+        case WDX_OPT_REFINE_OPTIMAL_CPTS:
+            if (value != 0 && value != 1) {
+                set_error("WDX_OPT_REFINE_OPTIMAL_CPTS is 0 or 1, not %lld", (long long)value);
+                return WDX_ERR_INVALID;
+            }
+            ctx->knobs.refine_optimal = value == 1;
             break;
         case WDX_OPT_ADC_DEV_SLICE_READS:
             if (value < 0) {
@@ -1101,6 +1126,28 @@ int wdx_selftest_score_dev(wdx_ctx *ctx, const double *d_dm, const double *d_vs,
         return WDX_ERR_INVALID;
     }
     return launch_score_selftest(d_dm, d_vs, n, d_fast, d_ref, (hipStream_t)stream);
+}
+
+int wdx_selftest_optimal_cpts_dev(wdx_ctx *ctx, const double *d_x, const int64_t *d_off, int64_t n_series, int32_t n_bkps,
+                                  int32_t min_size, int64_t max_len, int32_t max_slots, int32_t *d_cpts, int32_t *d_status,
+                                  void *stream) {
+    WDX_ENTER(ctx);
+    if (n_series < 0 || n_bkps < 1 || n_bkps > 253 || max_len < 0 || max_len > WDX_MAX_ADAPTER_SAMPLES || max_slots < 0 ||
+        (n_series > 0 && (!d_x || !d_off || !d_cpts || !d_status))) {
+        set_error("selftest_optimal_cpts_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    if (min_size < 1) {
+        set_error("optimal change-points: min_size must be >= 1");
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (n_series == 0) return WDX_SUCCESS;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = use_stream(ctx, (hipStream_t)stream)) return rc;
+    const OptimalPlan pl = plan_refine_optimal(n_series, max_len, n_bkps, max_slots);
+    if (int rc = ctx->fp_opt.ensure(pl.bytes)) return rc;
+    return launch_optimal_cpts_selftest(d_x, d_off, n_series, n_bkps, min_size, d_cpts, d_status, pl, ctx->fp_opt.p,
+                                        (hipStream_t)stream);
 }
 
 int wdx_selftest_clip_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, int64_t stride, int64_t n_reads,

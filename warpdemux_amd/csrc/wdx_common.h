@@ -48,6 +48,7 @@ struct Knobs {
     int boost_kernel = 0;            // WDX_OPT_BOOST_KERNEL: 0 by batch size | 1 lane-per-read | 2 tree-parallel
     bool long_windows = false;       // WDX_OPT_LONG_WINDOWS: adapter windows up to WDX_MAX_LONG_ADAPTER_SAMPLES (product option)
     bool long_refine_windows = false;   // WDX_OPT_LONG_REFINE_WINDOWS: the same for the consensus-refinement branch (product option)
+    bool refine_optimal = false;        // WDX_OPT_REFINE_OPTIMAL_CPTS: barcode tails cut at their optimal change-points (product option)
     int64_t adc_dev_slice_reads = 0;    // WDX_OPT_ADC_DEV_SLICE_READS: reads per slice of an int16 device shard (0 = built-in)
     // the long form of the exact kernel serves this call (wdx_window.h: the refinement branch has its own option)
     bool long_form(bool refine) const { return long_form_on(refine, long_windows, long_refine_windows); }
@@ -146,6 +147,7 @@ int launch_count_calls(int32_t *call, const int32_t *status /*nullable*/, int64_
 struct RefineDev;  // wdx_fingerprint.hip: device-side view of wdx_refine_params
 int fill_refine_dev(const wdx_refine_params &rp, const double *d_query, int32_t *d_idx, struct RefineDev **out);
 void free_refine_dev(struct RefineDev *rf);
+int refine_segm_events(const struct RefineDev *rf);   // barcode_num_events[0]
 
 // ---- fingerprint (wdx_fingerprint.hip) ---------------------------------------------------------
 // Optional event pair recorded around the launches of the MAIN fast kernel only (WDX_K_FINGERPRINT_MAIN): the
@@ -156,6 +158,8 @@ struct MainEvents {
     // a third pair around clip_bounds_kernel (WDX_K_FINGERPRINT_CLIP): the launch ahead of the main kernel
     hipEvent_t c_first = nullptr, c_second = nullptr;
     bool c_recorded = false;
+    // ... and one around fingerprint_refine_optimal_kernel (WDX_K_REFINE_OPTIMAL), from the pool through `take`
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> optimal;
     // SPLIT main kernel: first / second bracket the whole sequence of (tile kernel, tail kernel) launch pairs; one more
     // pair per slice around the tail kernel alone (WDX_K_FINGERPRINT_TAIL), taken from the context's pool through `take`
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tail;
@@ -183,7 +187,10 @@ int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &
                        int64_t *n_launches = nullptr, long long *d_prof = nullptr, int64_t prof_reads = 0,
                        int stop_phase = 0, const struct RefineDev *rf = nullptr, MainEvents *main_ev = nullptr,
                        double *d_big = nullptr /* fingerprint_big_bytes(max_len) bytes, or null */,
-                       void *d_long = nullptr /* fingerprint_long_bytes(max_len) bytes, or null: WDX_OPT_LONG_WINDOWS */);
+                       void *d_long = nullptr /* fingerprint_long_bytes(max_len) bytes, or null: WDX_OPT_LONG_WINDOWS */,
+                       void *d_opt = nullptr /* fingerprint_optimal_bytes(n_reads, max_len, E2) bytes: WDX_OPT_REFINE_OPTIMAL_CPTS */);
+// device bytes of the optimal change-points' scratch for a refining call (at most 256 MiB: the reads are taken in slices)
+int64_t fingerprint_optimal_bytes(int64_t n_reads, int64_t max_len, int32_t barcode_segm_events);
 int64_t fingerprint_workspace_bytes(int64_t n_reads);
 // device bytes of the fast kernels' hand-over records for the refinement branch (RefineDev::ws), zero-initialised
 int64_t fingerprint_refine_ws_bytes(int64_t n_reads);
@@ -193,6 +200,22 @@ int64_t fingerprint_big_bytes(int64_t max_len);
 // ... and, with WDX_OPT_LONG_WINDOWS, for the score curves and samples of windows beyond WDX_MAX_ADAPTER_SAMPLES: 16 slots
 // of 768 KB = 12 MB (0 when max_len <= WDX_MAX_ADAPTER_SAMPLES)
 int64_t fingerprint_long_bytes(int64_t max_len);
+// WDX_OPT_REFINE_OPTIMAL_CPTS: the optimal change-points of the barcode tail for the matched reads (RefineRec::state == 3) of
+// A, whichever kernel segmented the adapter (wdx_refine_optimal.hip).  A grid of `slots` workgroups strides over the reads;
+// each owns `slot_bytes` of the context's scratch buffer (the path table of the read in flight and, for tails beyond
+// kOptLdsCap samples, its prefix sums and two rows of the value table).
+constexpr int kOptLdsCap = 2047;                    // tails whose prefix sums and value rows live in LDS
+constexpr size_t kOptScratchMax = (size_t)256 << 20;   // upper bound of the scratch buffer
+constexpr int64_t kOptMaxSlots = 2048;
+struct OptimalPlan {
+    int64_t cap;         // longest tail a slot holds
+    size_t slot_bytes;
+    int64_t slots;
+    size_t bytes;        // slots * slot_bytes <= kOptScratchMax
+};
+OptimalPlan plan_refine_optimal(int64_t n_reads, int64_t max_len, int B, int64_t max_slots = 0);
+int launch_optimal_cpts_selftest(const double *d_x, const int64_t *d_off, int64_t n_series, int B, int m, int32_t *d_cpts,
+                                 int32_t *d_status, const OptimalPlan &pl, void *d_scratch, hipStream_t stream);
 int launch_clip_bounds_selftest(const float *d_sig, const int64_t *d_row_off, int64_t stride, int64_t n_reads,
                                 const int32_t *d_a_start, const int32_t *d_a_end, const wdx_seg_params &p, int cap,
                                 void *d_rec, hipStream_t stream);

@@ -28,7 +28,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 12;
+constexpr int kNumTimed = 13;
 
 // RAII: make the context's device current for the duration of one entry point and put the caller's
 // device back afterwards (a host thread that also drives torch must not find its device switched).
@@ -62,6 +62,9 @@ struct wdx_ctx {
     // WDX_OPT_LONG_WINDOWS: slots of the long form (fingerprint_long_bytes: 12 MB), allocated by the first call that meets a
     // window beyond WDX_MAX_ADAPTER_SAMPLES with the option on -- never otherwise.  A pipeline slot owns its own: 96 MB for 8
     wdx::Buffer fp_long;
+    // WDX_OPT_REFINE_OPTIMAL_CPTS: scratch of fingerprint_refine_optimal_kernel (fingerprint_optimal_bytes: at most 256 MiB),
+    // allocated by the first refining call with the option on -- never otherwise
+    wdx::Buffer fp_opt;
     wdx::PinnedBuffer pin_in, pin_out;  // staging of small (live-tick sized) host-buffer calls
     std::vector<double> ref_query_host;  // the consensus query resident in ref_buf (refine_prepare uploads on change)
     wdx::Buffer pk_idx;       // packed staging of a page-locked minibatch: window offsets / first columns / shifted bounds

@@ -1367,8 +1367,9 @@ __device__ void fp_process_read(const FpArgs &A, const int64_t r, unsigned char 
         // refines in place like the BIG form, the tail's score curve and samples at `sbs` inside the slot.  The match's
         // scratch and ev / zz / tmp / hist / cpts depend on num_events and the query alone; the tail's state bytes and the
         // peak list's uint16 positions, relative to sbs, are bounded by ns2 <= ns < kLongCap like the adapter pass's.)
-        if (!LONG && A.refine_record && A.rf.ws && P.sig_norm == WDX_NORM_NONE && W == P.running_stat_width && nseg <= 128 &&
-            !__syncthreads_or(any_nan)) {
+        // (WDX_OPT_REFINE_OPTIMAL_CPTS: its kernel re-creates the adapted width and the exact clip itself -- every read)
+        if (!LONG && A.refine_record && A.rf.ws && P.sig_norm == WDX_NORM_NONE && nseg <= 128 &&
+            (A.refine_optimal || (W == P.running_stat_width && !__syncthreads_or(any_nan)))) {
             RefineRec *rec = reinterpret_cast<RefineRec *>(A.rf.ws) + r;
             for (int s = tid; s < nseg; s += BLOCK) rec->ev[s] = ev[s];
             for (int s = tid; s <= nseg; s += BLOCK) rec->cpts[s] = cpts[s];
@@ -1785,6 +1786,7 @@ int fill_refine_dev(const wdx_refine_params &rp, const double *d_query, int32_t 
     return WDX_SUCCESS;
 }
 void free_refine_dev(RefineDev *rf) { delete rf; }
+int refine_segm_events(const RefineDev *rf) { return rf->E2; }
 void set_refine_ws(RefineDev *rf, void *d_ws) { rf->ws = reinterpret_cast<unsigned char *>(d_ws); }
 
 // Self-test of the t-score's unscaled sqrt / quotient sequences (fast_sqrt_mid, fast_div_mid) against the

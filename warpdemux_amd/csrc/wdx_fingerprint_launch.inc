@@ -390,6 +390,8 @@ struct FpRun {
     int64_t *n_launches;   // nullable
     MainEvents *ev;        // nullable
     void *d_long;          // fingerprint_long_kernel's slots (pl.with_long)
+    void *d_opt;           // WDX_OPT_REFINE_OPTIMAL_CPTS: the scratch of plan_refine_optimal(n_reads, max_len, E2)
+    int64_t max_len;
     // a fast kernel's arguments: the exact kernel's list, everything else null or zero
     FastArgs fast_args(int capF, int capP) const {
         FastArgs F{};
@@ -577,10 +579,38 @@ static void stage_retry(const FpRun &R) {
         hipLaunchKernelGGL(pl.k.ls, dim3((unsigned)pl.grid), dim3(FB), pl.flds2, R.stream, F3b);
     }
 }
+// WDX_OPT_REFINE_OPTIMAL_CPTS: every read of the call has left a record by now (the fast kernels, the exact kernel and its big
+// form alike); the subsequence match for all of them, then the optimal change-points of their barcode tails -- one launch
+// whose workgroups stride over the reads, each with its slot of the context's scratch buffer (WDX_K_REFINE_OPTIMAL)
+static int stage_refine_optimal(FpArgs A, int64_t max_len, void *d_opt, hipStream_t stream, MainEvents *ev) {
+    A.refine_record = 0;
+    if (int rc = for_each_slice(A.n_reads, 1 << 22, [&](int64_t base, int64_t n) {
+            A.block_base = base;
+            return launch_refine_match_wave(A, n, stream);
+        }))
+        return rc;
+    std::pair<hipEvent_t, hipEvent_t> tp{nullptr, nullptr};
+    if (ev && ev->take) tp = ev->take(ev->take_arg);   // (take is set whenever the context times its kernels)
+    if (tp.first) (void)hipEventRecord(tp.first, stream);
+    const int rc = launch_refine_optimal(A, plan_refine_optimal(A.n_reads, max_len, A.rf.E2), d_opt, stream);
+    if (tp.first) {
+        (void)hipEventRecord(tp.second, stream);
+        ev->optimal.push_back(tp);
+    }
+    return rc;
+}
 // the exact general kernel for the slow list (and, refinement branch, the refinement kernels behind it)
 static int stage_exact(FpRun &R) {
     FpArgs &A = R.A;
     if (R.pl.clip_reuse) A.clip = R.ws.clip;
+    if (R.pl.refine && A.refine_optimal) {
+        // the exact kernel and its big form leave a record for every read they segment; nothing comes back
+        A.refine_record = 1;
+        if (int rc = launch_exact_list(R, A, kCntSlow)) return rc;
+        if (R.pl.with_huge)
+            if (int rc = launch_fp_big(A, R.pl.cap, R.ws.count + kCntSlow, R.ws.slow, R.stream)) return rc;
+        return stage_refine_optimal(A, R.max_len, R.d_opt, R.stream, R.ev);
+    }
     if (R.pl.refine) {
         // refinement branch: the exact kernel segments the adapters of the slow list's reads and leaves them, like the
         // fast kernels theirs, to the refinement kernels (reads it cannot hand over it refines in place); barcode
@@ -677,7 +707,8 @@ static int run_fast_chain(FpRun &R, const Knobs &knobs) {
 }
 
 // ---- entry ----------------------------------------------------------------------------------------------------------
-static int validate_fingerprint_call(int64_t n_reads, int64_t max_len, const wdx_seg_params &p, const RefineDev *rf) {
+static int validate_fingerprint_call(int64_t n_reads, int64_t max_len, const wdx_seg_params &p, const RefineDev *rf,
+                                     const Knobs &knobs) {
     if (n_reads > 0x7fffffffLL) {
         set_error("at most 2^31-1 reads per call");
         return WDX_ERR_INVALID;
@@ -708,15 +739,29 @@ static int validate_fingerprint_call(int64_t n_reads, int64_t max_len, const wdx
             set_error("consensus refinement: barcode_num_events[0] must be in [1, %d], psi >= 0", kMaxEvents);
             return WDX_ERR_INVALID;
         }
+        if (knobs.refine_optimal) {
+            if (knobs.long_refine_windows) {
+                set_error("WDX_OPT_REFINE_OPTIMAL_CPTS and WDX_OPT_LONG_REFINE_WINDOWS do not go together");
+                return WDX_ERR_UNSUPPORTED;
+            }
+            if (p.min_obs_per_base < 1) {
+                set_error("optimal change-points: min_obs_per_base must be >= 1");
+                return WDX_ERR_UNSUPPORTED;
+            }
+            if (p.sig_norm != WDX_NORM_NONE || !rf->ws) {   // (what the record path does not serve: wdx.h)
+                set_error("optimal change-points: sig_extract.normalization must be \"none\"");
+                return WDX_ERR_UNSUPPORTED;
+            }
+        }
     }
     return WDX_SUCCESS;
 }
 
 int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &out, hipStream_t stream, void *d_ws,
                        const Knobs &knobs, int64_t *n_launches, long long *d_prof, int64_t prof_reads, int stop_phase,
-                       const RefineDev *rf, MainEvents *main_ev, double *d_big, void *d_long) {
+                       const RefineDev *rf, MainEvents *main_ev, double *d_big, void *d_long, void *d_opt) {
     if (in.n_reads == 0) return WDX_SUCCESS;
-    if (int rc = validate_fingerprint_call(in.n_reads, in.max_len, p, rf)) return rc;
+    if (int rc = validate_fingerprint_call(in.n_reads, in.max_len, p, rf, knobs)) return rc;
     LaunchSliceScope slice_scope(knobs.max_launch_slice);
     const PlanFlags flags{d_ws != nullptr, d_prof != nullptr, stop_phase, d_big != nullptr, d_long != nullptr, rf != nullptr, rf && rf->ws};
     const FastPlan pl = plan_fast_chain(p, in.max_len, in.n_reads, knobs, flags);
@@ -732,7 +777,9 @@ int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &
     FpRun R{FpArgs{in.sig, in.row_off, in.row_len, in.stride, in.n_reads, in.a_start, in.a_end, in.ok, p, out.fpt, out.dwell, out.stats,
                    out.status, pl.cap, 0, d_prof, prof_reads, stop_phase, 1, rf ? *rf : RefineDev{}, d_big,
                    pl.with_long ? kLongCap : (pl.with_huge ? kBigCap : 0), knobs.exact_no_list ? 1 : 0},
-            pl, FpWorkspace(d_ws, in.n_reads), stream, n_launches, main_ev, d_long};
+            pl, FpWorkspace(d_ws, in.n_reads), stream, n_launches, main_ev, d_long, d_opt, in.max_len};
+    const bool optimal = rf && knobs.refine_optimal;
+    R.A.refine_optimal = optimal ? 1 : 0;
     const uint64_t e1 = (uint64_t)(p.num_events > 0 ? p.num_events : 1);
     R.A.e_magic1 = (unsigned)std::min<uint64_t>(((1ull << 32) + e1 - 1) / e1, 0xffffffffull);   // (E = 1: 2^32 - 1 -> q = n - 1, rounded up to n)
     R.A.e_magic2 = (unsigned)(((1ull << 32) + 2 * e1 - 1) / (2 * e1));
@@ -749,11 +796,13 @@ int launch_fingerprint(const FpReads &in, const wdx_seg_params &p, const FpOut &
         if (int rc = launch_clip_bounds(R.A, R.ws.clip, pl.exact_clip_cap, stream)) return rc;
         R.A.clip = R.ws.clip;
     }
+    if (optimal) R.A.refine_record = 1;   // every read leaves a record: stage_refine_optimal does the rest
     if (int rc = pl.small ? launch_fp_chunks<512, false>(R.A, pl.lds, stream, n_launches)
                           : launch_fp_chunks<1024, false>(R.A, pl.lds, stream, n_launches))
         return rc;
     if (pl.with_huge)
         if (int rc = launch_fp_big(R.A, pl.cap, nullptr, nullptr, stream)) return rc;
+    if (optimal) return stage_refine_optimal(R.A, in.max_len, d_opt, stream, main_ev);
     if (pl.with_long) return launch_fp_long(R.A, d_long, nullptr, nullptr, stream);
     return WDX_SUCCESS;
 }

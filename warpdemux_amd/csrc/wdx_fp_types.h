@@ -74,6 +74,8 @@ struct FpArgs {
     int peak_filter;     // fast kernels on approximate keys: 1 = drop peaks below kPeakTau at the append (WDX_OPT_NO_PEAK_FILTER)
     unsigned *dbg_reasons;  // WDX_OPT_DEBUG_OCCUPANCY: 16 counters, why the fast kernels handed reads to the exact kernel (else null)
     const ClipRec *clip; // exact kernel behind the launch chain: the reads' clip records (CLIP_OK -> the two medians are not redone); nullable
+    int refine_optimal;  // WDX_OPT_REFINE_OPTIMAL_CPTS: the exact kernel leaves a record for EVERY read of the refinement branch (shrunk
+                         // window width, NaN samples included) -- fingerprint_refine_optimal_kernel finishes them all
     unsigned e_magic1, e_magic2;   // ceil(2^32 / E), ceil(2^32 / 2E) (launch_fingerprint): the fast kernels' window parameters without a division
 };
 
@@ -214,5 +216,8 @@ int launch_refine_match_wave(FpArgs A, int64_t n, hipStream_t stream);
 // false: the parameters are outside what it takes (the workgroup-per-read kernel in wdx_fingerprint.hip serves those)
 bool refine_tail_wave_takes(const FpArgs &A);
 int launch_refine_tail_wave(FpArgs A, int64_t n, unsigned *back_count, int32_t *back_list, hipStream_t stream);
+
+// (wdx_refine_optimal.hip; OptimalPlan: wdx_common.h)
+int launch_refine_optimal(FpArgs A, const OptimalPlan &pl, void *d_scratch, hipStream_t stream);
 
 }  // namespace wdx

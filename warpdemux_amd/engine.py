@@ -231,9 +231,10 @@ class DemuxEngine:
         pc = self.params.to_c()
         rc = refine.to_c()
         entry, rows = self._rows("wdx_fingerprint_refine_dev", sig, offsets, stride, max_len, n)
-        _lib.check(entry(
-            self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
-            C.byref(pc), C.byref(rc), _dp(fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(status), self._stream()))
+        with self.ctx.refine_options_for_call(refine):   # (refine.optimal_cpts -> WDX_OPT_REFINE_OPTIMAL_CPTS for this call)
+            _lib.check(entry(
+                self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
+                C.byref(pc), C.byref(rc), _dp(fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(status), self._stream()))
         return fpt, dwell, stats, idx, status
 
     def demux_refine(self, sig, a_start, a_end, refine, *, offsets=None, stride=0, max_len: int, ok=None, counts=None):
@@ -259,10 +260,11 @@ class DemuxEngine:
         work = self._work_for(sig, n, max_len, K, True)
         pc, rc = self.params.to_c(), refine.to_c()
         entry, rows = self._rows("wdx_demux_refine_dev", sig, offsets, stride, max_len, n)
-        _lib.check(entry(
-            self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
-            C.byref(pc), C.byref(rc), _dp(out.fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(out.status), _dp(out.dist),
-            _dp(out.call), _dp(out.counts), _dp(work), self._stream()))
+        with self.ctx.refine_options_for_call(refine):
+            _lib.check(entry(
+                self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
+                C.byref(pc), C.byref(rc), _dp(out.fpt), _dp(dwell), _dp(stats), _dp(idx), _dp(out.status), _dp(out.dist),
+                _dp(out.call), _dp(out.counts), _dp(work), self._stream()))
         return out, dwell, stats, idx
 
     def dtw(self, X, want_argmin=True, out=None):
@@ -404,10 +406,11 @@ class DemuxEngine:
         pc = self.params.to_c()
         rc = refine.to_c() if refine is not None else None
         entry, rows = self._rows("wdx_demux_boost_dev", sig, offsets, stride, max_len, n)
-        _lib.check(entry(
-            self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
-            C.byref(pc), C.byref(rc) if rc is not None else None, _dp(fpt), _dp(idx), _dp(status), _dp(raw), _dp(prob),
-            _dp(pred), _dp(conf), _dp(work), self._stream()))
+        with self.ctx.refine_options_for_call(refine):
+            _lib.check(entry(
+                self.ctx.handle, *rows, _dp(a_start), _dp(a_end), _dp(ok),
+                C.byref(pc), C.byref(rc) if rc is not None else None, _dp(fpt), _dp(idx), _dp(status), _dp(raw), _dp(prob),
+                _dp(pred), _dp(conf), _dp(work), self._stream()))
         return prob, pred, conf, status, idx, fpt, raw
 
     # -- synthetic inputs, generated in HBM ----------------------------------------------------------

@@ -76,6 +76,7 @@ class LiveDemux:
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, *, model=None,
                  refine: Optional[RefineParams] = None, adc: bool = False, device: int = 0, max_reads: int = 512,
                  max_samples: int = 10000, long_windows: bool = False):
+        optimal = _marshal.refine_options(refine, long_windows, "LiveDemux")
         d = _marshal.deployment(
             refs, window, penalty, params, model, refine, who="LiveDemux", models=("DTW_SVM", "DTW_MLP", "Fpt_Boost"),
             bare_refine=False, refine_dtw=False,
@@ -89,6 +90,8 @@ class LiveDemux:
         self.ctx = _lib.Context(device)      # this object's own context = own stream + staging buffers
         if long_windows:
             self.ctx.set_long_windows()
+        if optimal:   # refine.optimal_cpts: refined ticks cut the barcode tail at its optimal change-points
+            self.ctx.set_option(_lib.OPT_REFINE_OPTIMAL_CPTS, 1)
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:

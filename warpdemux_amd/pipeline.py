@@ -122,6 +122,7 @@ class MinibatchPipeline:
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
         self.N_SLOTS = int(n_slots)
+        optimal = _marshal.refine_options(refine, long_windows, "MinibatchPipeline")
         d = _marshal.deployment(
             refs, window, penalty, params, model, refine, who="MinibatchPipeline", models=("Fpt_Boost",), bare_refine=True,
             refine_dtw=True,
@@ -131,6 +132,8 @@ class MinibatchPipeline:
         self.ctx = _lib.Context(device)
         if long_windows:   # (every slot copies the context's options at its submit; 12 MB per slot that meets a long window)
             self.ctx.set_long_windows()
+        if optimal:   # refine.optimal_cpts: WDX_OPT_REFINE_OPTIMAL_CPTS (the slots copy it like every option)
+            self.ctx.set_option(_lib.OPT_REFINE_OPTIMAL_CPTS, 1)
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:

@@ -8,7 +8,8 @@ reference's field names and fail-reason strings so the callers' savers see the s
 Both branches of the reference are covered: the plain one (``segmentation.consensus_refinement = false``, the
 shipped RNA004 config) and the consensus-guided barcode refinement of the tRNA models (sig_proc.py:257-378,
 452-521; `RefineParams`, `fingerprint_refine_batch`).  ``refinement_optimal_cpts`` (ruptures KernelCPD, false
-in every shipped config) is not offered.
+in every shipped config) is served behind an option of its own: ``RefineParams.optimal_cpts`` / ``from_spc(...,
+optimal_cpts=True)`` -- the stated float64 rule of include/wdx.h; parity with ruptures itself is unpinned.
 """
 from __future__ import annotations
 
@@ -129,11 +130,16 @@ class RefineParams:
     ub_end: int = 97
     barcode_segm_events: int = 25
     barcode_keep_events: int = 25
+    # segmentation.refinement_optimal_cpts: the barcode tail is cut at its least-squares optimal change-points instead of its
+    # strongest peaks (WDX_OPT_REFINE_OPTIMAL_CPTS on the context of the call; not a field of wdx_refine_params)
+    optimal_cpts: bool = False
 
     @classmethod
-    def from_spc(cls, spc, consensus_query) -> "RefineParams":
+    def from_spc(cls, spc, consensus_query, optimal_cpts: bool = False) -> "RefineParams":
+        """``optimal_cpts=True`` accepts a configuration with ``refinement_optimal_cpts`` (the field is then set from the
+        configuration); without the keyword such a configuration is refused, as it always was."""
         seg = spc.segmentation
-        if getattr(seg, "refinement_optimal_cpts", False):
+        if getattr(seg, "refinement_optimal_cpts", False) and not optimal_cpts:
             raise NotImplementedError("refinement_optimal_cpts (ruptures KernelCPD) is not offered by the HIP engine")
         k = seg.barcode_num_events
         if isinstance(k, (int, np.integer)):
@@ -148,7 +154,8 @@ class RefineParams:
                    psi=tuple(int(v) for v in seg.consensus_subseq_match_psi),
                    ub_start=int(seg.consensus_subseq_match_ub_start), lb_end=int(seg.consensus_subseq_match_lb_end),
                    ub_end=int(seg.consensus_subseq_match_ub_end), barcode_segm_events=int(k[0]),
-                   barcode_keep_events=int(k[1]))
+                   barcode_keep_events=int(k[1]),
+                   optimal_cpts=bool(optimal_cpts and getattr(seg, "refinement_optimal_cpts", False)))
 
     def to_c(self) -> "_lib.RefineParamsC":
         if self.subseq_norm not in _lib.NORM_CODES:
@@ -314,11 +321,13 @@ def fingerprint_refine_batch(signals, adapter_start, adapter_end, params: SegPar
                              device=None, long_windows: bool = False) -> FingerprintBatch:
     """Consensus-refinement branch on a (n_reads, stride) float32 minibatch; K = refine.barcode_keep_events.
     ``long_windows``: adapter windows of up to MAX_LONG_ADAPTER_SAMPLES samples for this call (WDX_OPT_LONG_REFINE_WINDOWS on
-    the default context, put back afterwards); the default reports windows beyond MAX_ADAPTER_SAMPLES as failed ("unknown")."""
+    the default context, put back afterwards); the default reports windows beyond MAX_ADAPTER_SAMPLES as failed ("unknown").
+    ``refine.optimal_cpts``: WDX_OPT_REFINE_OPTIMAL_CPTS for this call, in the same way; not together with ``long_windows``."""
+    _marshal.refine_options(refine, long_windows, "fingerprint_refine_batch")
     sig, a_s, a_e, ok, n, stride = _marshal.minibatch(signals, adapter_start, adapter_end, success)
     pc, rc = params.to_c(), refine.to_c()
     o = _marshal.outputs(n, refine.barcode_keep_events, 0, 0, _FPT_WANT | _lib.WANT_REFINE_IDX)
-    with _lib.default_context(device).long_refine_windows_for_call(long_windows) as ctx:
+    with _lib.default_context(device).refine_options_for_call(refine, long_windows) as ctx:
         _lib.check(_lib.load().wdx_fingerprint_refine_batch(
             ctx.handle, _lib.ptr(sig), n, stride, _lib.ptr(a_s), _lib.ptr(a_e), _lib.ptr(ok), C.byref(pc), C.byref(rc),
             _lib.ptr(o["fpt"]), _lib.ptr(o["dwell"]), _lib.ptr(o["stats"]), _lib.ptr(o["refine_idx"]), _lib.ptr(o["status"])))
@@ -408,18 +417,20 @@ def demux_batch_adc(adc, row_len, offset, scale, adapter_start, adapter_end, par
 
 
 def detect_results_to_fpt_batch(calibrated_signals, spc, detect_results: Sequence, read_ids: Optional[Sequence[str]] = None,
-                                device=None, consensus_query=None, long_windows: bool = False) -> List[ReadResult]:
+                                device=None, consensus_query=None, long_windows: bool = False,
+                                optimal_cpts: bool = False) -> List[ReadResult]:
     """Batched `detect_results_to_fpt`: one ReadResult per row, identical fields to the reference's
     per-read call (sig_proc.py:590-605) plus the `barcode_fpt_wrapper` read-id (file_proc.py:216).  With
     ``spc.segmentation.consensus_refinement`` the caller passes the consensus signal like the reference does.
     ``long_windows``: a configuration with ``core.max_obs_trace`` + 2 x padding up to MAX_LONG_ADAPTER_SAMPLES is accepted and
-    its long windows are fingerprinted, on the plain and on the consensus-refinement branch."""
+    its long windows are fingerprinted, on the plain and on the consensus-refinement branch.  ``optimal_cpts``: a configuration
+    with ``segmentation.refinement_optimal_cpts`` is accepted and served (`RefineParams.from_spc`); refused without it."""
     params = SegParams.from_spc(spc, long_windows=long_windows)
     refine = None
     if getattr(spc.segmentation, "consensus_refinement", False):
         if consensus_query is None or np.asarray(consensus_query).size == 0:
             raise ValueError("consensus_model must be specified when consensus_refinement is True")
-        refine = RefineParams.from_spc(spc, consensus_query)
+        refine = RefineParams.from_spc(spc, consensus_query, **(dict(optimal_cpts=True) if optimal_cpts else {}))
     n = len(detect_results)
     ok = np.array([bool(d.success) for d in detect_results], dtype=np.uint8)
     a_s = np.array([d.adapter_start if (d.success and d.adapter_start is not None) else 0 for d in detect_results], dtype=np.int32)
@@ -466,7 +477,8 @@ def read_results_from_batch(fb: FingerprintBatch, detect_results: Sequence, read
     return out
 
 
-def detect_results_to_fpt(calibrated_signal, spc, detect_results, consensus_query=np.array([])) -> ReadResult:
+def detect_results_to_fpt(calibrated_signal, spc, detect_results, consensus_query=np.array([]), optimal_cpts: bool = False) -> ReadResult:
     """Per-read signature of the reference (sig_proc.py:394-399); a batch of one."""
     sig = np.asarray(calibrated_signal, dtype=np.float32).reshape(1, -1)
-    return detect_results_to_fpt_batch(sig, spc, [detect_results], consensus_query=consensus_query)[0]
+    kw = dict(optimal_cpts=True) if optimal_cpts else {}
+    return detect_results_to_fpt_batch(sig, spc, [detect_results], consensus_query=consensus_query, **kw)[0]
