@@ -197,6 +197,24 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
  * path tables of the reads in flight, allocated by the first refining call with the option on and never otherwise (each pipeline
  * slot that meets one owns its own); workspaces and every allocation of the default path are unchanged. */
 #define WDX_OPT_REFINE_OPTIMAL_CPTS 23
+/* A product option of the DTW seam, not a diagnostic one.  0 (default): effective windows beyond 32 -- the reference's default
+ * window=None (unbanded) on series longer than 32 points included -- run on the scratch-row kernel (WDX_DTW_SCRATCH: two DP rows per
+ * lane in a context-owned global block, one launch per 65 536 lanes), and the fused device-resident entries (wdx_demux_dev,
+ * wdx_demux_refine_dev and their _adc_dev twins) return WDX_ERR_UNSUPPORTED for such a reference set.  1: effective windows
+ * 33 .. L at series lengths L <= WDX_DTW_WIDE_MAX_L run on the wide-window kernel (WDX_DTW_WIDE) wherever a DTW is dispatched on this
+ * context: wdx_dtw_matrix[_dev], wdx_demux_batch[_adc], wdx_demux_dev / _refine_dev / _adc_dev / _refine_adc_dev (which then accept
+ * such a set), wdx_demux_submit* (a pipeline slot copies the options at every submit), a feeder served by this context,
+ * wdx_live_tick[_ex], wdx_dtw_svm_predict, wdx_dtw_mlp_predict, wdx_demux_svm_dev, wdx_demux_mlp_dev.  Any other value:
+ * WDX_ERR_INVALID.  Same float32 distances and argmin as the scratch rows, bit for bit (the reference's six float64 operations per
+ * cell; WDX_OPT_DTW_UNFUSED changes nothing here); all three operand layouts, the reference split over grid.y and the fused
+ * argmin follow the rules of the register-band kernels; one launch per dispatch.  Cost: none in memory -- no scratch block, nothing
+ * added to wdx_demux_workspace_bytes; the DP state is 32 float64 registers per lane plus 512 L bytes of LDS per wave (so 2 waves
+ * per CU at L = 110, 1 from L = 161 on).
+ * Limits: L > WDX_DTW_WIDE_MAX_L stays on the scratch rows with the option on, and the fused device-resident entries still return
+ * WDX_ERR_UNSUPPORTED ("demux_dev needs window <= 32") there, as they do for every window beyond 32 with the option off.
+ * Measured against the scratch rows (profiles/wide_dtw.json): see there for the figures of every shape class. */
+#define WDX_OPT_WIDE_DTW 24
+#define WDX_DTW_WIDE_MAX_L 256 /* longest series of the wide-window kernel: every fingerprint length (K <= 254) fits */
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -968,6 +986,7 @@ int wdx_kernel_time_reset(wdx_ctx *ctx);
 #define WDX_DTW_BAND 3      /* rolling register band: band_w = 8, 15, 16 or 32                                */
 #define WDX_DTW_SCRATCH 4   /* two DP rows per lane in global scratch (windows beyond 32)                     */
 #define WDX_DTW_SHORT_SVM 5 /* the 25-point kernel with the SVM decision sums in its epilogue                 */
+#define WDX_DTW_WIDE 6      /* strips of 32 columns in registers, edge column in LDS (WDX_OPT_WIDE_DTW: windows 33 .. L)  */
 #define WDX_DTW_LAYOUT_ROW_MAJOR 0     /* lanes = reads, each lane reads its own (n, L) row in place                      */
 #define WDX_DTW_LAYOUT_READ_MINOR 1    /* lanes = reads, transposed copy (L, ld): one coalesced load per sample           */
 #define WDX_DTW_LAYOUT_REFS_AS_LANES 2 /* lanes = references (resident transposed set), the reads are the uniform operand */

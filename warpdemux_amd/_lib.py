@@ -50,6 +50,9 @@ OPT_LONG_REFINE_WINDOWS = 21   # ... the same for the consensus-refinement branc
 OPT_ADC_DEV_SLICE_READS = 22   # reads per slice of the *_adc_dev entries (0 = as many as the staging budget holds)
 OPT_REFINE_OPTIMAL_CPTS = 23   # product option of the refinement branch: barcode tails cut at their optimal change-points
                                # (segmentation.refinement_optimal_cpts; ``RefineParams.optimal_cpts`` sets it)
+OPT_WIDE_DTW = 24   # product option of the DTW seam: 1 = effective windows 33 .. L at L <= DTW_WIDE_MAX_L (``window=None`` included) on the
+                    # wide-window kernel instead of the scratch rows; the fused device entries then accept such references (0 / 1)
+DTW_WIDE_MAX_L = 256   # WDX_DTW_WIDE_MAX_L
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -115,8 +118,8 @@ class RefineParamsC(C.Structure):
 
 
 # wdx_dtw_launch_info.family / .layout (include/wdx.h)
-DTW_NONE, DTW_WAVEFRONT, DTW_SHORT, DTW_BAND, DTW_SCRATCH, DTW_SHORT_SVM = range(6)
-DTW_FAMILY_NAMES = ("none", "wavefront", "short", "band", "scratch", "short+svm")
+DTW_NONE, DTW_WAVEFRONT, DTW_SHORT, DTW_BAND, DTW_SCRATCH, DTW_SHORT_SVM, DTW_WIDE = range(7)
+DTW_FAMILY_NAMES = ("none", "wavefront", "short", "band", "scratch", "short+svm", "wide")
 DTW_LAYOUT_ROW_MAJOR, DTW_LAYOUT_READ_MINOR, DTW_LAYOUT_REFS_AS_LANES = range(3)
 DTW_LAYOUT_NAMES = ("row-major", "read-minor", "refs-as-lanes")
 
@@ -583,6 +586,7 @@ class Context:
         self.long_windows = False
         self.long_refine_windows = False
         self.refine_optimal = False
+        self.wide_dtw = False
 
     @property
     def handle(self):
@@ -594,7 +598,9 @@ class Context:
 
     def set_option(self, option: int, value: int = 1):
         """Diagnostic switch (wdx_ctx_set_option); tests and profiling tools only -- and OPT_LONG_WINDOWS /
-        OPT_LONG_REFINE_WINDOWS, which the ``long_windows=`` keyword of the classes and module-level calls sets."""
+        OPT_LONG_REFINE_WINDOWS, which the ``long_windows=`` keyword of the classes and module-level calls sets, and
+        OPT_WIDE_DTW, which their ``wide_dtw=`` keyword sets (users of the reference-named functions of
+        `parallel_distances` set it here, on `default_context()`)."""
         check(self._L.wdx_ctx_set_option(self.handle, int(option), int(value)))
         if int(option) == OPT_LONG_WINDOWS:
             self.long_windows = bool(value)
@@ -602,6 +608,8 @@ class Context:
             self.long_refine_windows = bool(value)
         elif int(option) == OPT_REFINE_OPTIMAL_CPTS:
             self.refine_optimal = bool(value)
+        elif int(option) == OPT_WIDE_DTW:
+            self.wide_dtw = bool(value)
 
     def set_long_windows(self):
         """Both product options on: what an object that owns its context does for ``long_windows=True`` -- its plain calls
@@ -621,6 +629,19 @@ class Context:
         finally:
             if bool(on) != before:
                 self.set_option(OPT_LONG_WINDOWS, int(before))
+
+    @contextlib.contextmanager
+    def wide_dtw_for_call(self, on: bool):
+        """OPT_WIDE_DTW = ``on`` for the duration of one call on a shared context, then what it was before -- also when the
+        call raises."""
+        before = self.wide_dtw
+        if bool(on) != before:
+            self.set_option(OPT_WIDE_DTW, int(bool(on)))
+        try:
+            yield self
+        finally:
+            if bool(on) != before:
+                self.set_option(OPT_WIDE_DTW, int(before))
 
     @contextlib.contextmanager
     def long_refine_windows_for_call(self, on: bool):

@@ -149,6 +149,14 @@ def refine_options(refine, long_windows: bool, who: str) -> bool:
     return on
 
 
+def wide_dtw_option(wide_dtw, who: str) -> bool:
+    """The ``wide_dtw=`` keyword of an object that owns its context (WDX_OPT_WIDE_DTW), checked before the context exists: a
+    bool and nothing else -- an integer window handed to the wrong keyword must not switch a kernel."""
+    if not isinstance(wide_dtw, (bool, np.bool_)):
+        raise ValueError(f"{who}: wide_dtw is True or False, not {wide_dtw!r}")
+    return bool(wide_dtw)
+
+
 def deployment(refs, window, penalty, params, model, refine, *, who: str, models: tuple, nothing_to_serve: str,
                bare_refine: bool, refine_dtw: bool) -> Deployment:
     """THE rule of what a `MinibatchPipeline`, `Feeder` or `LiveDemux` serves, checked before any context exists

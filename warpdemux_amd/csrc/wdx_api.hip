@@ -358,7 +358,7 @@ static int dtw_dev_route(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_ou
     if (nX == 0 || R.nY == 0) return WDX_SUCCESS;
     int rc;
     const int64_t L = R.L;
-    const int64_t sb = dtw_scratch_bytes(L, R.window);
+    const int64_t sb = dtw_wide_eligible(L, R.window, ctx->knobs) ? 0 : dtw_scratch_bytes(L, R.window);   // (WDX_OPT_WIDE_DTW: no scratch rows)
     if (sb && (rc = ctx->scratch.ensure((size_t)sb))) return rc;
     // small problems: one launch of the anti-diagonal wavefront kernel straight from the row-major
     // inputs (no transpose), then the argmin
@@ -642,6 +642,13 @@ int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value) {
             }
             ctx->knobs.refine_optimal = value == 1;
             break;
+        case WDX_OPT_WIDE_DTW:
+            if (value != 0 && value != 1) {
+                set_error("WDX_OPT_WIDE_DTW is 0 or 1, not %lld", (long long)value);
+                return WDX_ERR_INVALID;
+            }
+            ctx->knobs.wide_dtw = value == 1;
+            break;
         case WDX_OPT_ADC_DEV_SLICE_READS:
             if (value < 0) {
                 set_error("WDX_OPT_ADC_DEV_SLICE_READS is 0 (built-in) or a number of reads, not %lld", (long long)value);
@@ -881,7 +888,7 @@ int wdx::demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params 
     }
     const int64_t K = p->barcode_num_events;
     if ((rc = check_ref_length(R, *p))) return rc;
-    if (dtw_scratch_bytes(R.L, R.window)) {
+    if (dtw_scratch_bytes(R.L, R.window) && !dtw_wide_eligible(R.L, R.window, ctx->knobs)) {
         set_error("demux_dev needs window <= %d", kMaxRegWindow);
         return WDX_ERR_UNSUPPORTED;
     }

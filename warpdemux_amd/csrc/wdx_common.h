@@ -50,6 +50,7 @@ struct Knobs {
     bool long_refine_windows = false;   // WDX_OPT_LONG_REFINE_WINDOWS: the same for the consensus-refinement branch (product option)
     bool refine_optimal = false;        // WDX_OPT_REFINE_OPTIMAL_CPTS: barcode tails cut at their optimal change-points (product option)
     int64_t adc_dev_slice_reads = 0;    // WDX_OPT_ADC_DEV_SLICE_READS: reads per slice of an int16 device shard (0 = built-in)
+    bool wide_dtw = false;              // WDX_OPT_WIDE_DTW: effective windows 33 .. L at L <= WDX_DTW_WIDE_MAX_L on dtw_wide_kernel (product option)
     // the long form of the exact kernel serves this call (wdx_window.h: the refinement branch has its own option)
     bool long_form(bool refine) const { return long_form_on(refine, long_windows, long_refine_windows); }
     // the longest adapter window a call of this branch fingerprints (the host loops cut one sample beyond it: that reports it)
@@ -109,6 +110,9 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan /
                int32_t *d_argmin, void *d_scratch, int64_t scratch_bytes, hipStream_t stream,
                const Knobs &knobs, bool a_rowmajor = false, wdx_dtw_launch_info *info = nullptr);
 int64_t dtw_scratch_bytes(int64_t L, int window);
+// WDX_OPT_WIDE_DTW is on and the shape is the wide kernel's (wdx_dtw_wide.h): launch_dtw takes it instead of the scratch rows --
+// no scratch block, row-major rows and a fused argmin are legal
+bool dtw_wide_eligible(int64_t L, int window, const Knobs &knobs);
 // The shipped models' DTW (25 points, window 15) over references in support-vector order with the SVM decision sums in
 // its epilogue: P[slot][q][read] (wdx_dtw.hip: dtw_short_svm_kernel); gather of the resident references into that order.
 int launch_dtw_svm_partial(const double *X, int64_t nA, const double *Ypad_sv, int64_t Lpad, int halo, const uint8_t *y_nan_sv,

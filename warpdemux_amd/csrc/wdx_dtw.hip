@@ -14,6 +14,7 @@
 // oracle's order, except min(up+p2, left+p2) == min(up,left)+p2, which is exact because rounding
 // is monotone.  No MFMA: this is a min-plus recurrence.
 #include "wdx_common.h"
+#include "wdx_dtw_wide.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -433,6 +434,120 @@ __global__ __launch_bounds__(64) void dtw_scratch_kernel(
     }
 }
 
+// ---- wide windows: effective window 33 .. L at L <= WDX_DTW_WIDE_MAX_L (WDX_OPT_WIDE_DTW; wdx_dtw_wide.h) ----------
+// Lane = pair like the band kernels (same operands, layouts, grid and argmin), but the band no longer fits the registers, so
+// the DP matrix is walked in vertical strips of S = 32 columns [j0, j0 + S).  A strip keeps its segment of the previous DP
+// row in S float64 registers and updates it in place, row by row; what the next strip needs of it -- its right-edge column
+// D[i][j0 + S - 1] -- goes through LDS, edge[i * 64 + lane] (conflict-free b64 accesses), overwritten in place: a row reads
+// the old value (the cell to its left) before it writes its own, and keeps the one it read as the next row's diagonal.  Per
+// row and strip: one LDS read, one LDS write, one load of x, S cells; the reference's samples of a strip are uniform and the
+// same for all its rows.  No global scratch.  The cell is dtw_scratch_kernel's, operation for operation (the reference's
+// six, un-fused): the two kernels give the same bits, non-finite samples included.
+// The band |i - j| <= w - 1 limits a strip to rows [j0 - (w-1), j0 + S-1 + (w-1)]; inside them the rows [j0 + S-1 - (w-1),
+// j0 + (w-1)] see the whole strip inside the band and run without masks (every row when w = L), the up to S-1 rows above
+// and below mask the cells outside it to +inf.  Columns >= L of the last strip are computed on the references' zero halo
+// (kWideDtwHalo = S - 1 samples, within the halo launch_dtw demands) and never read: values only travel right and down.
+constexpr int kWideS = kWideDtwStrip;
+// (launch_dtw checks halo >= kMaxRegWindow - 1 for every kernel: that is the halo the last strip reads)
+static_assert(kWideDtwHalo <= kMaxRegWindow - 1, "the last strip of dtw_wide_kernel reads beyond the references' halo");
+static_assert(kWideDtwMinWindow == kMaxRegWindow + 1, "the wide kernel starts where the register-band kernels end");
+
+template <bool MASKED>
+__device__ __forceinline__ void dtw_wide_row(double (&r)[kWideS], const double x, const double *__restrict__ ys, const double p2,
+                                             double left, double diag, const int clo, const int chi) {
+#pragma unroll
+    for (int c = 0; c < kWideS; ++c) {
+        double d = x - ys[c];
+        d = d * d;
+        const double up = r[c];
+        double t = min_f64(up, left) + p2;
+        t = min_f64(t, diag);
+        double v = d + t;
+        if (MASKED) v = (c < clo || c > chi) ? WDX_INF : v;
+        r[c] = v;
+        left = v;
+        diag = up;
+    }
+}
+
+// rows [i, iend) of the strip at j0; xn = x[i] on entry and x[iend] on return (when iend <= ihi)
+template <bool MASKED>
+__device__ __forceinline__ void dtw_wide_rows(double (&r)[kWideS], int &i, const int iend, const int ihi, double &xn,
+                                              const double *__restrict__ xp, const int64_t ldA, const double *__restrict__ ys,
+                                              const double p2, double *__restrict__ edge, double &diag, const bool first,
+                                              const bool last, const int j0, const int w) {
+    for (; i < iend; ++i) {
+        const double x = xn;
+        if (i < ihi) xn = xp[(int64_t)(i + 1) * ldA];   // (uniform)
+        const double left = first ? WDX_INF : edge[i * 64];
+        dtw_wide_row<MASKED>(r, x, ys, p2, left, diag, i - (w - 1) - j0, i + (w - 1) - j0);
+        diag = left;
+        if (!last) edge[i * 64] = r[kWideS - 1];
+    }
+}
+
+template <bool ROWMAJOR>
+__global__ __launch_bounds__(64) void dtw_wide_kernel(
+    const double *__restrict__ AT, int64_t ldA, int64_t nA, const uint8_t *__restrict__ a_nan,
+    const double *__restrict__ Bpad, int64_t Lpad, int halo, int nB,
+    const uint8_t *__restrict__ b_nan, int L, int w, double p2, float *__restrict__ out,
+    int64_t sA, int64_t sB, int32_t *__restrict__ argmin, int refs_per_block) {
+    extern __shared__ double wide_lds[];   // L rows x 64 lanes
+    constexpr int S = kWideS;
+    double *__restrict__ edge = wide_lds + threadIdx.x;
+    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = a < nA;
+    const int64_t al = active ? a : nA - 1;
+    const int b0 = blockIdx.y * refs_per_block;
+    const int b1 = min(nB, b0 + refs_per_block);
+    if (ROWMAJOR) ldA = 1;
+    const double *__restrict__ xp = ROWMAJOR ? AT + al * (int64_t)L : AT + al;
+    // (ROWMAJOR without flags: the lazy NaN sweep of dtw_band_kernel -- a finite result proves a NaN-free row)
+    bool anan = a_nan ? (a_nan[al] != 0) : false;
+    bool swept = a_nan != nullptr || !ROWMAJOR;   // (uniform)
+    ArgminAcc acc;
+
+    for (int b = b0; b < b1; ++b) {
+        const double *__restrict__ y = Bpad + (int64_t)b * Lpad + halo;
+        double r[S];
+        for (int j0 = 0; j0 < L; j0 += S) {
+            const bool first = j0 == 0, last = j0 + S >= L;
+            const int ilo = max(0, j0 - (w - 1)), ihi = min(L - 1, j0 + S - 1 + (w - 1));
+            // (the strip's last column INSIDE the matrix decides where the unmasked rows begin: w = L masks nothing)
+            const int m0 = max(ilo, min(j0 + S - 1, L - 1) - (w - 1)), m1 = min(ihi, j0 + (w - 1));   // ilo <= m0 <= j0 <= m1 <= ihi
+#pragma unroll
+            for (int c = 0; c < S; ++c) r[c] = WDX_INF;   // row ilo - 1 of the strip: outside the band, or row -1
+            // D[ilo - 1][j0 - 1]: the virtual D[-1][-1] = 0 of the first strip, the band's lower edge of a later one
+            double diag = first ? 0.0 : (ilo > 0 ? edge[(ilo - 1) * 64] : WDX_INF);
+            double xn = xp[(int64_t)ilo * ldA];
+            int i = ilo;
+            dtw_wide_rows<true>(r, i, m0, ihi, xn, xp, ldA, y + j0, p2, edge, diag, first, last, j0, w);
+            dtw_wide_rows<false>(r, i, m1 + 1, ihi, xn, xp, ldA, y + j0, p2, edge, diag, first, last, j0, w);
+            dtw_wide_rows<true>(r, i, ihi + 1, ihi, xn, xp, ldA, y + j0, p2, edge, diag, first, last, j0, w);
+            if (!last) {
+                // rows of the next strip below this one's: the cell to their left is outside the band
+                const int ihn = min(L - 1, j0 + 2 * S - 1 + (w - 1));
+                for (; i <= ihn; ++i) edge[i * 64] = WDX_INF;
+            }
+        }
+        // D[L-1][L-1] sits in the last strip at column (L - 1) mod S
+        const int cl = (L - 1) & (S - 1);
+        double Dv = r[0];
+#pragma unroll
+        for (int c = 1; c < S; ++c) Dv = (c == cl) ? r[c] : Dv;
+        double res = sqrt(Dv);
+        if (!swept && __ballot(!(res < WDX_INF)) != 0ull) {   // (rare)
+            anan = row_has_nan(xp, L);
+            swept = true;
+        }
+        if (anan || (b_nan && b_nan[b])) res = __builtin_nan("");
+        const float f = (float)res;
+        if (active) out[a * sA + (int64_t)b * sB] = f;
+        acc.push(f, b);
+    }
+    if (argmin && active) argmin[a] = acc.idx;
+}
+
 // ---- anti-diagonal wavefront kernel (latency path: few pairs, e.g. the live 100 ms ticks) ----------
 // One 16-lane DPP row per (read, reference) pair, four pairs per wave.  Front k = i + j is evaluated
 // by all lanes at once: lane l holds band offset o = j - i = 2l - 14 on even fronts and 2l - 15 on odd
@@ -545,6 +660,8 @@ int64_t dtw_scratch_bytes(int64_t L, int window) {
     return 2 * (L + 1) * 65536 * (int64_t)sizeof(double);
 }
 
+bool dtw_wide_eligible(int64_t L, int window, const Knobs &knobs) { return wide_dtw_plan(L, window, knobs.wide_dtw).eligible; }
+
 // Row-major X (nX, L) against padded refs; out (nX, nY) row-major.  Caller checked eligibility.
 int launch_dtw_wavefront(const double *X, int64_t nX, const double *Ypad, int64_t Lpad, int halo,
                          int64_t nY, int64_t L, int window, double penalty, float *out,
@@ -579,7 +696,8 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan, 
     }
     int w = (window <= 0 || window > L) ? (int)L : window;  // |i-j| <= w-1 is vacuous beyond L
     const double p2 = penalty * penalty;
-    if (w > kMaxRegWindow) {
+    const WideDtwPlan wide = wide_dtw_plan(L, w, knobs.wide_dtw);   // (WDX_OPT_WIDE_DTW: the grid and argmin rules below are its too)
+    if (w > kMaxRegWindow && !wide.eligible) {
         if (a_rowmajor) {
             set_error("the scratch-row DTW path takes the read-minor layout");
             return WDX_ERR_INVALID;
@@ -642,6 +760,18 @@ int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan, 
     dim3 grid((unsigned)gx, (unsigned)((nB + rpb - 1) / rpb));
     const int32_t layout = a_rowmajor ? WDX_DTW_LAYOUT_ROW_MAJOR : WDX_DTW_LAYOUT_READ_MINOR;
     if (info) *info = {WDX_DTW_BAND, 0, 0, layout, fused_argmin != nullptr, 1, rpb, w, grid.x, grid.y};
+    if (wide.eligible) {
+        if (info) info->family = WDX_DTW_WIDE;
+        void (*kern)(const double *, int64_t, int64_t, const uint8_t *, const double *, int64_t, int, int, const uint8_t *, int, int,
+                     double, float *, int64_t, int64_t, int32_t *, int) = a_rowmajor ? dtw_wide_kernel<true> : dtw_wide_kernel<false>;
+        static LdsAttr attr[2];   // (more than 64 KiB of dynamic LDS from L = 129 on)
+        if (int rc = attr[a_rowmajor].ensure(kern, (size_t)wide.lds_bytes)) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(64), (size_t)wide.lds_bytes, stream, AT, ldA, nA, a_nan, Bpad, Lpad, halo, (int)nB, b_nan,
+                           (int)L, w, p2, out, sA, sB, fused_argmin, rpb);
+        WDX_HIP_TRY(hipGetLastError());
+        if (d_argmin && !fused_argmin) return launch_argmin(out, nA, nB, d_argmin, stream);
+        return WDX_SUCCESS;
+    }
     if (L == 25 && w == 15 && !knobs.no_short_dtw) {
         if (info) info->family = WDX_DTW_SHORT, info->band_w = 15, info->exact_w = 1;
         if (a_rowmajor)

@@ -107,10 +107,14 @@ class DemuxResult:
 
 class DemuxEngine:
     """One engine per process per GPU.  ``refs``: (nY, L) float64 reference fingerprints
-    (model._X in the reference, models/dtw_base.py:20)."""
+    (model._X in the reference, models/dtw_base.py:20).  ``wide_dtw``: effective windows 33 .. L (``window=None`` on
+    fingerprints of 33 .. 256 events) run on the wide-window DTW kernel (WDX_OPT_WIDE_DTW); without it `demux` and its kin
+    refuse such references (``NotImplementedError``: the fused entries need window <= 32)."""
 
     def __init__(self, refs: np.ndarray, window: Optional[int] = 15, penalty: Optional[float] = 0.1,
-                 params: Optional[SegParams] = None, device: int = 0, long_windows: bool = False):
+                 params: Optional[SegParams] = None, device: int = 0, long_windows: bool = False,
+                 wide_dtw: bool = False):
+        wide_dtw = _marshal.wide_dtw_option(wide_dtw, "DemuxEngine")
         torch = _torch()
         if not torch.cuda.is_available():
             raise _lib.WdxError("DemuxEngine needs a visible MI355X (torch.cuda.is_available() is False)")
@@ -120,6 +124,8 @@ class DemuxEngine:
         self.ctx = _lib.Context(self.device)
         if long_windows:   # adapter windows of up to 65 536 samples: WDX_OPT_LONG_WINDOWS (the plain entries) and
             self.ctx.set_long_windows()   # WDX_OPT_LONG_REFINE_WINDOWS (the refining ones)
+        if wide_dtw:   # windows beyond 32 (``window=None`` on long fingerprints) on the wide-window kernel: WDX_OPT_WIDE_DTW
+            self.ctx.set_option(_lib.OPT_WIDE_DTW, 1)
         self.L = _lib.load()
         self.params = params or SegParams(barcode_num_events=int(np.asarray(refs).shape[1]))
         self.set_refs(refs, window, penalty)

@@ -50,7 +50,8 @@ from .sig_proc import DemuxBatch, FingerprintBatch, RefineParams, SegParams, fin
 MAX_SLOTS = 32      # ring slots (WDX_FEEDER_MAX_RING_SLOTS); the feeder keeps at most 8 of them in flight on the device
 
 
-def _serve(shm_name: str, refs, window, penalty, model, device: int, ready, long_windows: bool = False, optimal_cpts: bool = False):
+def _serve(shm_name: str, refs, window, penalty, model, device: int, ready, long_windows: bool = False, optimal_cpts: bool = False,
+           wide_dtw: bool = False):
     """The GPU-facing process (forked from a parent that never touched the GPU)."""
     shm = shared_memory.SharedMemory(name=shm_name)
     rc = 1
@@ -61,6 +62,8 @@ def _serve(shm_name: str, refs, window, penalty, model, device: int, ready, long
             ctx.set_long_windows()   # (OPT_LONG_WINDOWS and OPT_LONG_REFINE_WINDOWS: a refine ring looks at the second)
         if optimal_cpts:    # (refine.optimal_cpts: the ring's refine minibatches are cut at their optimal change-points)
             ctx.set_option(_lib.OPT_REFINE_OPTIMAL_CPTS, 1)
+        if wide_dtw:
+            ctx.set_option(_lib.OPT_WIDE_DTW, 1)
         if refs.shape[0]:   # (a fingerprint-only refine ring has none)
             _marshal.set_refs(ctx, refs, window, penalty)
         if model is not None:
@@ -109,11 +112,16 @@ class Feeder:
     ``model.n_features``.
 
     ``long_windows``: the serving context fingerprints adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS, and
-    WDX_OPT_LONG_REFINE_WINDOWS for a ``refine`` ring -- `stride` must hold such rows)."""
+    WDX_OPT_LONG_REFINE_WINDOWS for a ``refine`` ring -- `stride` must hold such rows).
+
+    ``wide_dtw``: the serving context runs effective windows 33 .. L (``window=None`` on fingerprints of 33 .. 256 events) on
+    the wide-window DTW kernel instead of the scratch rows (WDX_OPT_WIDE_DTW); same results."""
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, max_reads: int = 1000,
                  stride: int = 10000, n_slots: int = 16, device: int = 0, start_timeout: float = 120.0, model=None,
-                 adc: bool = False, refine: Optional[RefineParams] = None, long_windows: bool = False):
+                 adc: bool = False, refine: Optional[RefineParams] = None, long_windows: bool = False,
+                 wide_dtw: bool = False):
+        wide_dtw = _marshal.wide_dtw_option(wide_dtw, "Feeder")
         optimal = _marshal.refine_options(refine, long_windows, "Feeder")
         d = _marshal.deployment(refs, window, penalty, params, model, refine, who="Feeder", models=("DTW_SVM", "Fpt_Boost"),
                                 bare_refine=True, refine_dtw=True, nothing_to_serve="refs or model is required")
@@ -149,7 +157,7 @@ class Feeder:
         self._shm, self._owner, self._base = shm, os.getpid(), base
         ctx = mp.get_context("fork")
         ready = ctx.Event()
-        self._proc = ctx.Process(target=_serve, args=(self._shm.name, d.refs, d.window, d.penalty, model, int(device), ready, bool(long_windows), optimal),
+        self._proc = ctx.Process(target=_serve, args=(self._shm.name, d.refs, d.window, d.penalty, model, int(device), ready, bool(long_windows), optimal, wide_dtw),
                                  daemon=True)
         self._proc.start()
         import time

@@ -71,11 +71,15 @@ class LiveDemux:
     ``long_windows``: ticks fingerprint adapter windows of up to 65 536 samples, int16 ones included (WDX_OPT_LONG_WINDOWS;
     refined ticks: WDX_OPT_LONG_REFINE_WINDOWS).
 
+    ``wide_dtw``: effective windows 33 .. L (``window=None`` on fingerprints of 33 .. 256 events) run on the wide-window DTW
+    kernel instead of the scratch rows (WDX_OPT_WIDE_DTW); same results.
+
     Every check of the arguments happens before a context is created and raises ``ValueError``."""
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, *, model=None,
                  refine: Optional[RefineParams] = None, adc: bool = False, device: int = 0, max_reads: int = 512,
-                 max_samples: int = 10000, long_windows: bool = False):
+                 max_samples: int = 10000, long_windows: bool = False, wide_dtw: bool = False):
+        wide_dtw = _marshal.wide_dtw_option(wide_dtw, "LiveDemux")
         optimal = _marshal.refine_options(refine, long_windows, "LiveDemux")
         d = _marshal.deployment(
             refs, window, penalty, params, model, refine, who="LiveDemux", models=("DTW_SVM", "DTW_MLP", "Fpt_Boost"),
@@ -92,6 +96,8 @@ class LiveDemux:
             self.ctx.set_long_windows()
         if optimal:   # refine.optimal_cpts: refined ticks cut the barcode tail at its optimal change-points
             self.ctx.set_option(_lib.OPT_REFINE_OPTIMAL_CPTS, 1)
+        if wide_dtw:
+            self.ctx.set_option(_lib.OPT_WIDE_DTW, 1)
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:

@@ -149,6 +149,15 @@ def parallel_distance_matrix(
     return _dtw(A, B, window, penalty)
 
 
-def nearest_reference(X, Y, window=None, penalty=None):
-    """(float32 distances (nX,nY), int32 argmin per read) -- SURVEY.md §8 row B3."""
-    return _dtw(_as_f64_2d(X, "X"), _as_f64_2d(Y, "Y"), window, penalty, want_argmin=True)
+def nearest_reference(X, Y, window=None, penalty=None, wide_dtw=None):
+    """(float32 distances (nX,nY), int32 argmin per read) -- SURVEY.md §8 row B3.  ``wide_dtw``: True / False sets
+    WDX_OPT_WIDE_DTW on the default context for this call (effective windows 33 .. L on the wide-window kernel); None leaves
+    the context as its owner set it.  The reference-named functions above keep the reference's signatures: their users set
+    ``_lib.default_context().set_option(_lib.OPT_WIDE_DTW, 1)``."""
+    X, Y = _as_f64_2d(X, "X"), _as_f64_2d(Y, "Y")
+    if wide_dtw is None:
+        return _dtw(X, Y, window, penalty, want_argmin=True)
+    if not isinstance(wide_dtw, (bool, np.bool_)):
+        raise ValueError(f"nearest_reference: wide_dtw is True, False or None, not {wide_dtw!r}")
+    with _lib.default_context().wide_dtw_for_call(bool(wide_dtw)):
+        return _dtw(X, Y, window, penalty, want_argmin=True)

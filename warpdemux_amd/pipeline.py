@@ -113,12 +113,16 @@ class MinibatchPipeline:
     ``model``: a `models.Fpt_Boost` kept resident on the device; every minibatch brings its prediction back
     (`BoostMinibatch`), ``refs`` may be None, and K must equal ``model.n_features``.
     ``long_windows``: minibatches fingerprint adapter windows of up to 65 536 samples (WDX_OPT_LONG_WINDOWS; with ``refine``:
-    WDX_OPT_LONG_REFINE_WINDOWS)."""
+    WDX_OPT_LONG_REFINE_WINDOWS).
+    ``wide_dtw``: effective windows 33 .. L (``window=None`` on fingerprints of 33 .. 256 events) run on the wide-window DTW
+    kernel instead of the scratch rows (WDX_OPT_WIDE_DTW); same results."""
 
     N_SLOTS = 2
 
     def __init__(self, refs=None, window=None, penalty=None, params: Optional[SegParams] = None, device: int = 0,
-                 n_slots: int = 2, refine: Optional[RefineParams] = None, model=None, long_windows: bool = False):
+                 n_slots: int = 2, refine: Optional[RefineParams] = None, model=None, long_windows: bool = False,
+                 wide_dtw: bool = False):
+        wide_dtw = _marshal.wide_dtw_option(wide_dtw, "MinibatchPipeline")
         if not 1 <= int(n_slots) <= MAX_SLOTS:
             raise ValueError(f"n_slots must be in [1, {MAX_SLOTS}]")
         self.N_SLOTS = int(n_slots)
@@ -134,6 +138,8 @@ class MinibatchPipeline:
             self.ctx.set_long_windows()
         if optimal:   # refine.optimal_cpts: WDX_OPT_REFINE_OPTIMAL_CPTS (the slots copy it like every option)
             self.ctx.set_option(_lib.OPT_REFINE_OPTIMAL_CPTS, 1)
+        if wide_dtw:
+            self.ctx.set_option(_lib.OPT_WIDE_DTW, 1)
         if self.nY:
             _marshal.set_refs(self.ctx, d.refs, d.window, d.penalty)
         if model is not None:
