@@ -34,7 +34,7 @@ def effective_window(w, L):
 
 def instantiation(w, L, short=True):
     """(family, W, EXACT_W) that serves window w at length L once the wavefront kernel is out of the way: the kernels' own
-    domains (wdx_dtw.hip: launch_dtw), not a tuning threshold."""
+    domains (wdx_dtw_plan.h: dtw_plan), not a tuning threshold."""
     we = effective_window(w, L)
     if we > 32:
         return ("scratch", 0, False)
@@ -44,7 +44,7 @@ def instantiation(w, L, short=True):
 
 
 def fused_rule(nX, nY):
-    """launch_dtw folds the argmin into the DTW kernel when one block walks every reference anyway."""
+    """dtw_plan folds the argmin into the DTW kernel when one block walks every reference anyway."""
     gx = (nX + 63) // 64
     return gx >= 8 * 3072 or nY == 1 or (gx >= 2048 and nY < 32)
 

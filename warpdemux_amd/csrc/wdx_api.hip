@@ -271,7 +271,7 @@ int set_refs_locked(wdx_ctx *ctx, const double *Y, int64_t nY, int64_t L, int32_
         set_error("set_refs: penalty is NaN");
         return WDX_ERR_INVALID;
     }
-    const int w_eff = (window <= 0 || window > L) ? (int)L : window;
+    const int w_eff = (int)dtw_effective_window(L, window);
     uint64_t h = fnv1a(Y, (size_t)(nY * L) * sizeof(double));
     h = fnv1a(&nY, sizeof(nY), h);
     h = fnv1a(&L, sizeof(L), h);
@@ -290,8 +290,8 @@ int set_refs_locked(wdx_ctx *ctx, const double *Y, int64_t nY, int64_t L, int32_
     // freed or half-written buffers (a later call then reports WDX_ERR_NO_REFS instead of reading them)
     R.window = 0;
     R.content_hash = 0;
-    const int halo = kMaxRegWindow - 1;
-    const int64_t Lpad = L + 2 * halo;
+    const int halo = kDtwHalo;
+    const int64_t Lpad = dtw_padded_length(L);
     const int64_t ldT = round_up(nY > 0 ? nY : 1, 64);
     int rc;
     if ((rc = ctx->refs_pad.ensure((size_t)(nY > 0 ? nY : 1) * Lpad * sizeof(double)))) return rc;
@@ -326,103 +326,69 @@ int set_refs_locked(wdx_ctx *ctx, const double *Y, int64_t nY, int64_t L, int32_
     return WDX_SUCCESS;
 }
 
-// Batches from this size on go through the DTW kernel's row-major form (no transposed copy of the fingerprints:
-// at 10 M reads the copy is 17.6 GB of traffic and 6 ms); below it the launch is latency-bound and the
-// read-minor copy (a few MB, two tiny kernels) buys coalesced row loads: live ticks and minibatches measured
-// 0.1-0.3 ms faster that way.
-constexpr int64_t kRowMajorMinReads = 8192;
+// Where the copy a plan names lives (plan.copy_bytes, plan.flag_bytes), and the scratch rows' block (plan.scratch_bytes)
+struct DtwWork {
+    double *copy;
+    uint8_t *flags;
+    void *scratch;
+    int64_t scratch_bytes;
+};
 
-static int dtw_dev_route(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin, hipStream_t stream);
+// Device rows dX (nX, L) against the resident refs -> d_out (nX, nY) [+ argmin] as the plan (wdx_dtw_plan.h) says: the copy it
+// names into W (WDX_K_TRANSPOSE), then its launches (WDX_K_DTW).  dtw_settle_inf is the caller's.
+static int dtw_rows_vs_refs(wdx_ctx *ctx, const DtwPlan &P, const double *dX, const DtwWork &W, float *d_out, int32_t *d_argmin,
+                            hipStream_t stream) {
+    const DtwRefs &R = ctx->refs;
+    if (P.info.family == WDX_DTW_NONE) return WDX_SUCCESS;   // (no reads or no references)
+    const int64_t nX = P.prep == DtwPrep::kPaddedReads ? P.rows : P.lanes;
+    // lanes = reads, each reading its own row-major row in place, against the resident padded refs
+    DtwOperands op{dX, 1, P.lanes, nullptr, R.pad, R.Lpad, R.halo, P.rows, R.has_nan, R.penalty, d_out, R.nY, 1,
+                   d_argmin, W.scratch, W.scratch_bytes, ctx->knobs.dtw_unfused, stream};
+    if (P.prep == DtwPrep::kReadMinor) {
+        Timed t(ctx, WDX_K_TRANSPOSE, stream);
+        if (int rc = launch_transpose(dX, nX, P.L, W.copy, P.ld, W.flags, stream)) return rc;
+        op.A = W.copy, op.ldA = P.ld, op.a_nan = W.flags;
+    } else if (P.prep == DtwPrep::kPaddedReads) {
+        // lanes = refs (the resident transposed set), the padded reads are the uniform operand
+        Timed t(ctx, WDX_K_TRANSPOSE, stream);
+        if (int rc = launch_pad_rows(dX, nX, P.L, W.copy, P.ld, kDtwHalo, W.flags, stream)) return rc;
+        op.A = R.T, op.ldA = R.ldT, op.a_nan = R.has_nan;
+        op.Bpad = W.copy, op.Lpad = P.ld, op.halo = kDtwHalo, op.b_nan = W.flags;
+        op.sA = 1, op.sB = R.nY;
+    }
+    // the wavefront and the refs-as-lanes routes take their argmin behind the WDX_K_DTW scope, the others inside it
+    const bool late_argmin = P.info.family == WDX_DTW_WAVEFRONT || P.prep == DtwPrep::kPaddedReads;
+    if (late_argmin) op.argmin = nullptr;
+    {
+        Timed t(ctx, WDX_K_DTW, stream);
+        if (int rc = run_dtw_plan(P, op, &ctx->dtw_last)) return rc;
+    }
+    if (late_argmin && P.argmin_after && d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
+    return WDX_SUCCESS;
+}
 
 // DTW of device rows dX (nX, L) against the resident refs -> d_out (nX, nY) [+ argmin]
 int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin,
                    hipStream_t stream) {
-    if (int rc = dtw_dev_route(ctx, dX, nX, d_out, d_argmin, stream)) return rc;
-    return dtw_settle_inf(ctx->refs, dX, nX, d_out, d_argmin, stream);
+    const DtwRefs &R = ctx->refs;
+    if (R.window == 0) {
+        set_error("no reference set: call wdx_set_refs first");
+        return WDX_ERR_NO_REFS;
+    }
+    const DtwPlan P = dtw_plan(nX, R.nY, R.L, R.window, d_argmin != nullptr, DtwEntry::kMatrix, ctx->knobs.dtw_switches());
+    int rc;
+    if (P.scratch_bytes && (rc = ctx->scratch.ensure((size_t)P.scratch_bytes))) return rc;
+    if (P.copy_bytes && (rc = ctx->tmp1.ensure((size_t)P.copy_bytes))) return rc;
+    if (P.flag_bytes && (rc = ctx->tmp2.ensure((size_t)P.flag_bytes))) return rc;
+    const DtwWork W{(double *)ctx->tmp1.p, (uint8_t *)ctx->tmp2.p, ctx->scratch.p, (int64_t)ctx->scratch.bytes};
+    if ((rc = dtw_rows_vs_refs(ctx, P, dX, W, d_out, d_argmin, stream))) return rc;
+    return dtw_settle_inf(R, dX, nX, d_out, d_argmin, stream);
 }
 
 // a reference with an infinite sample (never a fingerprint)
 int dtw_settle_inf(const DtwRefs &R, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin, hipStream_t stream) {
     if (!R.any_inf || nX == 0 || R.nY == 0) return WDX_SUCCESS;
     if (int rc = launch_dtw_equal_inf(dX, nX, R.pad, R.Lpad, R.halo, R.nY, R.L, d_out, stream)) return rc;
-    if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
-    return WDX_SUCCESS;
-}
-
-static int dtw_dev_route(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin, hipStream_t stream) {
-    DtwRefs &R = ctx->refs;
-    if (R.window == 0) {
-        set_error("no reference set: call wdx_set_refs first");
-        return WDX_ERR_NO_REFS;
-    }
-    if (nX == 0 || R.nY == 0) return WDX_SUCCESS;
-    int rc;
-    const int64_t L = R.L;
-    const int64_t sb = dtw_wide_eligible(L, R.window, ctx->knobs) ? 0 : dtw_scratch_bytes(L, R.window);   // (WDX_OPT_WIDE_DTW: no scratch rows)
-    if (sb && (rc = ctx->scratch.ensure((size_t)sb))) return rc;
-    // small problems: one launch of the anti-diagonal wavefront kernel straight from the row-major
-    // inputs (no transpose), then the argmin
-    if (dtw_wavefront_eligible(nX, R.nY, L, R.window, ctx->knobs)) {
-        {
-            Timed t(ctx, WDX_K_DTW, stream);
-            if ((rc = launch_dtw_wavefront(dX, nX, R.pad, R.Lpad, R.halo, R.nY, L, R.window, R.penalty,
-                                           d_out, stream, &ctx->dtw_last)))
-                return rc;
-        }
-        if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
-        return WDX_SUCCESS;
-    }
-    // lanes = reads unless there are too few of them to fill a wave and there are more refs
-    const bool lanes_are_reads = nX >= 64 || nX >= R.nY;
-    if (lanes_are_reads && !sb && nX >= kRowMajorMinReads) {
-        // the kernel reads the row-major fingerprints as they are (a lane owns a row): no transposed copy
-        Timed t(ctx, WDX_K_DTW, stream);
-        return launch_dtw(dX, 1, nX, nullptr, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, L, R.window, R.penalty, d_out,
-                          R.nY, 1, d_argmin, nullptr, 0, stream, ctx->knobs, true, &ctx->dtw_last);
-    }
-    if (lanes_are_reads) {
-        const int64_t ld = round_up(nX, 64);
-        if ((rc = ctx->tmp1.ensure((size_t)L * ld * sizeof(double)))) return rc;
-        if ((rc = ctx->tmp2.ensure((size_t)ld))) return rc;
-        {
-            Timed t(ctx, WDX_K_TRANSPOSE, stream);
-            if ((rc = launch_transpose(dX, nX, L, (double *)ctx->tmp1.p, ld, (uint8_t *)ctx->tmp2.p,
-                                       stream)))
-                return rc;
-        }
-        Timed t(ctx, WDX_K_DTW, stream);
-        if (sb && d_argmin) {
-            if ((rc = launch_dtw((const double *)ctx->tmp1.p, ld, nX, (const uint8_t *)ctx->tmp2.p,
-                                 R.pad, R.Lpad, R.halo, R.nY, R.has_nan, L, R.window, R.penalty,
-                                 d_out, R.nY, 1, nullptr, ctx->scratch.p, (int64_t)ctx->scratch.bytes,
-                                 stream, ctx->knobs, false, &ctx->dtw_last)))
-                return rc;
-            return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
-        }
-        return launch_dtw((const double *)ctx->tmp1.p, ld, nX, (const uint8_t *)ctx->tmp2.p, R.pad,
-                          R.Lpad, R.halo, R.nY, R.has_nan, L, R.window, R.penalty, d_out, R.nY, 1,
-                          d_argmin, ctx->scratch.p, (int64_t)ctx->scratch.bytes, stream, ctx->knobs, false, &ctx->dtw_last);
-    }
-    // few reads, many refs (live / per-read calls): lanes = refs, the read is the uniform operand
-    const int halo = kMaxRegWindow - 1;
-    const int64_t Lpad = L + 2 * halo;
-    if ((rc = ctx->tmp1.ensure((size_t)nX * Lpad * sizeof(double)))) return rc;
-    if ((rc = ctx->tmp2.ensure((size_t)round_up(nX, 64)))) return rc;
-    {
-        Timed t(ctx, WDX_K_TRANSPOSE, stream);
-        if ((rc = launch_pad_rows(dX, nX, L, (double *)ctx->tmp1.p, Lpad, halo,
-                                  (uint8_t *)ctx->tmp2.p, stream)))
-            return rc;
-    }
-    {
-        Timed t(ctx, WDX_K_DTW, stream);
-        if ((rc = launch_dtw(R.T, R.ldT, R.nY, R.has_nan, (const double *)ctx->tmp1.p, Lpad, halo,
-                             nX, (const uint8_t *)ctx->tmp2.p, L, R.window, R.penalty, d_out, 1,
-                             R.nY, nullptr, ctx->scratch.p, (int64_t)ctx->scratch.bytes, stream, ctx->knobs, false,
-                             &ctx->dtw_last)))
-            return rc;
-        ctx->dtw_last.layout = WDX_DTW_LAYOUT_REFS_AS_LANES;
-    }
     if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
     return WDX_SUCCESS;
 }
@@ -888,7 +854,8 @@ int wdx::demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params 
     }
     const int64_t K = p->barcode_num_events;
     if ((rc = check_ref_length(R, *p))) return rc;
-    if (dtw_scratch_bytes(R.L, R.window) && !dtw_wide_eligible(R.L, R.window, ctx->knobs)) {
+    const DtwSwitches sw = ctx->knobs.dtw_switches();
+    if (dtw_plan(rows.f32.n_reads, R.nY, R.L, R.window, true, DtwEntry::kFused, sw).unsupported) {
         set_error("demux_dev needs window <= %d", kMaxRegWindow);
         return WDX_ERR_UNSUPPORTED;
     }
@@ -902,11 +869,9 @@ int wdx::demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params 
         double *fpt = d_fpt ? d_fpt + r0 * K : (double *)w;
         int32_t *status = d_status + r0, *call = d_call + r0;
         float *dist = d_dist + r0 * R.nY;
-        const bool rowmajor = n_reads >= kRowMajorMinReads;
-        const DemuxWork W = demux_work_layout(n_reads, K, !rowmajor);
-        const int64_t ld = W.ld;
-        double *fptT = (double *)(w + W.fptT);
-        uint8_t *flags = w + W.flags;
+        // (failed reads carry NaN fingerprints: the row-major kernels flag them themselves, the read-minor copy has flags)
+        const DtwPlan P = dtw_plan(n_reads, R.nY, R.L, R.window, true, DtwEntry::kFused, sw);
+        const DemuxWork W = demux_work_layout(n_reads, K, P.prep == DtwPrep::kReadMinor);
         RefineDev *rf = nullptr;
         RefineDevGuard rf_guard{rf};
         if (rp && (rc = refine_prepare(ctx, *rp, n_reads, from_read(d_refine_idx, r0, 3), w + round_up(W.bytes, 256), s, &rf)))
@@ -914,22 +879,7 @@ int wdx::demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params 
         if ((rc = fingerprint_stage(ctx, in, *p, FpOut{fpt, from_read(d_dwell, r0, K), from_read(d_stats, r0, 6), status},
                                     w + W.fp_ws, s, rf, rf == nullptr)))
             return rc;
-        if (rowmajor) {
-            // failed reads carry NaN fingerprints; the DTW kernel reads the row-major rows in place and flags them
-            Timed t(ctx, WDX_K_DTW, s);
-            if ((rc = launch_dtw(fpt, 1, n_reads, nullptr, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
-                                 R.window, R.penalty, dist, R.nY, 1, call, nullptr, 0, s, ctx->knobs, true, &ctx->dtw_last)))
-                return rc;
-        } else {
-            {
-                Timed t(ctx, WDX_K_TRANSPOSE, s);
-                if ((rc = launch_transpose(fpt, n_reads, K, fptT, ld, flags, s))) return rc;
-            }
-            Timed t(ctx, WDX_K_DTW, s);
-            if ((rc = launch_dtw(fptT, ld, n_reads, flags, R.pad, R.Lpad, R.halo, R.nY, R.has_nan, R.L,
-                                 R.window, R.penalty, dist, R.nY, 1, call, nullptr, 0, s, ctx->knobs, false, &ctx->dtw_last)))
-                return rc;
-        }
+        if ((rc = dtw_rows_vs_refs(ctx, P, fpt, DtwWork{(double *)(w + W.fptT), w + W.flags, nullptr, 0}, dist, call, s))) return rc;
         if ((rc = dtw_settle_inf(R, fpt, n_reads, dist, call, s))) return rc;
         Timed t(ctx, WDX_K_COUNT, s);
         return launch_count_calls(call, status, n_reads, R.nY, d_counts, s);

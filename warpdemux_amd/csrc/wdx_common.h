@@ -8,6 +8,7 @@
 #include "../../include/wdx.h"
 #include "wdx_window.h"
 #include "wdx_adc_dev.h"
+#include "wdx_dtw_plan.h"
 
 namespace wdx {
 
@@ -55,6 +56,8 @@ struct Knobs {
     bool long_form(bool refine) const { return long_form_on(refine, long_windows, long_refine_windows); }
     // the longest adapter window a call of this branch fingerprints (the host loops cut one sample beyond it: that reports it)
     int64_t max_window(bool refine) const { return max_adapter_window(refine, long_windows, long_refine_windows); }
+    // what the DTW dispatch rule reads of them (wdx_dtw_plan.h)
+    DtwSwitches dtw_switches() const { return {no_wavefront, no_short_dtw, wide_dtw}; }
 };
 
 // A launch over more workgroups than grid.x admits is cut into slices (block_base != 0 from the second on).  The built-in
@@ -83,10 +86,6 @@ struct LdsAttr {
 };
 
 // ---- DTW (wdx_dtw.hip) -----------------------------------------------------------------------
-// Largest Sakoe-Chiba window handled by the register-band kernel; wider / unbanded problems with
-// L > this go to the scratch-row kernel.
-constexpr int kMaxRegWindow = 32;
-
 struct DtwRefs {  // resident reference set, both layouts (see DESIGN.md "DTW data layout")
     double *pad = nullptr;   // (nY, Lpad) row-major, Lpad = L + 2*halo, series starts at +halo
     double *T = nullptr;     // (L, ldT) read-minor (series along columns)
@@ -99,20 +98,31 @@ struct DtwRefs {  // resident reference set, both layouts (see DESIGN.md "DTW da
     bool any_inf = false;  // a reference holds an infinite sample: dtw_dev_locked runs launch_dtw_equal_inf behind the DTW kernel
 };
 
-// lanes run over the columns of AT (L, ldA) [nA series] -- or, with a_rowmajor, over the rows of an (nA, L)
-// row-major array (ldA ignored; a_nan may be null: the kernel flags NaN series itself); the uniform operand is
-// Bpad (nB rows).
-// out[a*sA + b*sB] = (float)dtw(a, b).  d_argmin (nullable) is only legal when the lanes are the
-// reads (sA == nB, sB == 1): int32[nA].
-int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan /*nullable*/,
-               const double *Bpad, int64_t Lpad, int halo, int64_t nB, const uint8_t *b_nan,
-               int64_t L, int window, double penalty, float *out, int64_t sA, int64_t sB,
-               int32_t *d_argmin, void *d_scratch, int64_t scratch_bytes, hipStream_t stream,
-               const Knobs &knobs, bool a_rowmajor = false, wdx_dtw_launch_info *info = nullptr);
-int64_t dtw_scratch_bytes(int64_t L, int window);
-// WDX_OPT_WIDE_DTW is on and the shape is the wide kernel's (wdx_dtw_wide.h): launch_dtw takes it instead of the scratch rows --
-// no scratch block, row-major rows and a fused argmin are legal
-bool dtw_wide_eligible(int64_t L, int window, const Knobs &knobs);
+// The operands of one DTW dispatch (run_dtw_plan).  Lanes run over the columns of A (L, ldA) [nA series] -- or, in the plan's
+// row-major layout, over the rows of an (nA, L) row-major array (ldA ignored; a_nan may be null: the kernel flags NaN series
+// itself; the wavefront kernel reads such rows too); the uniform operand is Bpad (nB rows of Lpad samples, each series at +halo).
+// out[a*sA + b*sB] = (float)dtw(a, b).  argmin (nullable) is only legal when the lanes are the reads (sA == nB, sB == 1): int32[nA].
+struct DtwOperands {
+    const double *A;
+    int64_t ldA, nA;
+    const uint8_t *a_nan;  // nullable
+    const double *Bpad;
+    int64_t Lpad;
+    int halo;
+    int64_t nB;
+    const uint8_t *b_nan;
+    double penalty;
+    float *out;
+    int64_t sA, sB;
+    int32_t *argmin;
+    void *scratch;  // the scratch rows' block (plan.scratch_bytes bytes at least), else unused
+    int64_t scratch_bytes;
+    int unfused;  // Knobs::dtw_unfused
+    hipStream_t stream;
+};
+// Launches what the plan names -- one kernel family, the scratch rows' launch loop included -- then launch_argmin where the plan
+// asks for one and `argmin` is given, and stores plan.info as the record of the dispatch (wdx_dtw_last_launch).
+int run_dtw_plan(const DtwPlan &plan, const DtwOperands &op, wdx_dtw_launch_info *record);
 // The shipped models' DTW (25 points, window 15) over references in support-vector order with the SVM decision sums in
 // its epilogue: P[slot][q][read] (wdx_dtw.hip: dtw_short_svm_kernel); gather of the resident references into that order.
 int launch_dtw_svm_partial(const double *X, int64_t nA, const double *Ypad_sv, int64_t Lpad, int halo, const uint8_t *y_nan_sv,
@@ -121,12 +131,6 @@ int launch_dtw_svm_partial(const double *X, int64_t nA, const double *Ypad_sv, i
                            hipStream_t stream, int unfused, wdx_dtw_launch_info *info = nullptr);
 int launch_gather_rows(const double *src, const uint8_t *sflag, const int32_t *d_idx, int64_t n, int64_t ld, double *dst,
                        uint8_t *dflag, hipStream_t stream);
-// anti-diagonal wavefront kernel for small problems (latency path)
-bool dtw_wavefront_eligible(int64_t nX, int64_t nY, int64_t L, int window, const Knobs &knobs);
-int launch_dtw_wavefront(const double *X, int64_t nX, const double *Ypad, int64_t Lpad, int halo,
-                         int64_t nY, int64_t L, int window, double penalty, float *out,
-                         hipStream_t stream, wdx_dtw_launch_info *info = nullptr);
-
 // Equal infinities in a read and a reference at ONE index k: x[k] - y[k] is NaN without a NaN sample.  The reference's
 // `if (t < minv)` keeps a NaN diagonal predecessor, so cell (k, k) poisons the main diagonal and the distance is NaN; v_min_f64
 // drops the NaN and the DTW kernels return +inf (row k holds nothing finite).  This pass turns exactly those +inf entries of

@@ -14,7 +14,7 @@
 // oracle's order, except min(up+p2, left+p2) == min(up,left)+p2, which is exact because rounding
 // is monotone.  No MFMA: this is a min-plus recurrence.
 #include "wdx_common.h"
-#include "wdx_dtw_wide.h"
+#include "wdx_dtw_plan.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -446,9 +446,9 @@ __global__ __launch_bounds__(64) void dtw_scratch_kernel(
 // The band |i - j| <= w - 1 limits a strip to rows [j0 - (w-1), j0 + S-1 + (w-1)]; inside them the rows [j0 + S-1 - (w-1),
 // j0 + (w-1)] see the whole strip inside the band and run without masks (every row when w = L), the up to S-1 rows above
 // and below mask the cells outside it to +inf.  Columns >= L of the last strip are computed on the references' zero halo
-// (kWideDtwHalo = S - 1 samples, within the halo launch_dtw demands) and never read: values only travel right and down.
+// (kWideDtwHalo = S - 1 samples, within the halo run_dtw_plan demands) and never read: values only travel right and down.
 constexpr int kWideS = kWideDtwStrip;
-// (launch_dtw checks halo >= kMaxRegWindow - 1 for every kernel: that is the halo the last strip reads)
+// (run_dtw_plan checks halo >= kMaxRegWindow - 1 for every kernel: that is the halo the last strip reads)
 static_assert(kWideDtwHalo <= kMaxRegWindow - 1, "the last strip of dtw_wide_kernel reads beyond the references' halo");
 static_assert(kWideDtwMinWindow == kMaxRegWindow + 1, "the wide kernel starts where the register-band kernels end");
 
@@ -558,8 +558,6 @@ __global__ __launch_bounds__(64) void dtw_wide_kernel(
 // of a pair are staged in LDS once.  2L-1 dependent fronts instead of L*(2w-1) dependent cells: ~15x
 // shorter critical path than the lane-per-pair kernel, at ~1.6x its instruction count per pair, hence
 // only used when the whole problem fits the machine at once.  Same float64 operations per cell.
-constexpr int kWfPairsPerBlock = 16;  // 256 threads
-
 __device__ __forceinline__ double dpp_row_shift(double v, double fill, bool left) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     const int flo = __double2loint(fill), fhi = __double2hiint(fill);
@@ -655,159 +653,71 @@ int launch_dtw_equal_inf(const double *X, int64_t nX, const double *Ypad, int64_
     return WDX_SUCCESS;
 }
 
-int64_t dtw_scratch_bytes(int64_t L, int window) {
-    if (window <= kMaxRegWindow) return 0;
-    return 2 * (L + 1) * 65536 * (int64_t)sizeof(double);
+// The band ladder's instantiations (plan.info.band_w: 8 / 16 / 32 masked per cell, 15 exact) in both lane layouts
+using BandKernel = decltype(&dtw_band_kernel<8, false, false>);
+static BandKernel band_kernel(int band_w, bool rowmajor) {
+    if (band_w == 8) return rowmajor ? dtw_band_kernel<8, false, true> : dtw_band_kernel<8, false, false>;
+    if (band_w == 15) return rowmajor ? dtw_band_kernel<15, true, true> : dtw_band_kernel<15, true, false>;
+    if (band_w == 16) return rowmajor ? dtw_band_kernel<16, false, true> : dtw_band_kernel<16, false, false>;
+    return rowmajor ? dtw_band_kernel<32, false, true> : dtw_band_kernel<32, false, false>;
 }
 
-bool dtw_wide_eligible(int64_t L, int window, const Knobs &knobs) { return wide_dtw_plan(L, window, knobs.wide_dtw).eligible; }
-
-// Row-major X (nX, L) against padded refs; out (nX, nY) row-major.  Caller checked eligibility.
-int launch_dtw_wavefront(const double *X, int64_t nX, const double *Ypad, int64_t Lpad, int halo,
-                         int64_t nY, int64_t L, int window, double penalty, float *out,
-                         hipStream_t stream, wdx_dtw_launch_info *info) {
-    const int w = (window <= 0 || window > L) ? (int)L : window;
-    const int64_t npairs = nX * nY;
-    if (npairs == 0) return WDX_SUCCESS;
-    const size_t lds = (size_t)kWfPairsPerBlock * 2 * (size_t)L * sizeof(double);
-    if (info)
-        *info = {WDX_DTW_WAVEFRONT, 0, 0, WDX_DTW_LAYOUT_ROW_MAJOR, 0, 1, 1, w, (npairs + kWfPairsPerBlock - 1) / kWfPairsPerBlock, 1};
-    hipLaunchKernelGGL(dtw_wavefront_kernel, dim3((unsigned)((npairs + kWfPairsPerBlock - 1) / kWfPairsPerBlock)),
-                       dim3(256), lds, stream, X, nX, Ypad, Lpad, halo, (int)nY, (int)L, w,
-                       penalty * penalty, out);
-    WDX_HIP_TRY(hipGetLastError());
-    return WDX_SUCCESS;
-}
-
-bool dtw_wavefront_eligible(int64_t nX, int64_t nY, int64_t L, int window, const Knobs &knobs) {
-    const int64_t w = (window <= 0 || window > L) ? L : window;
-    return w <= 16 && L >= 1 && L <= 256 && nX * nY <= 16384 && !knobs.no_wavefront;
-}
-
-int launch_dtw(const double *AT, int64_t ldA, int64_t nA, const uint8_t *a_nan, const double *Bpad,
-               int64_t Lpad, int halo, int64_t nB, const uint8_t *b_nan, int64_t L, int window,
-               double penalty, float *out, int64_t sA, int64_t sB, int32_t *d_argmin,
-               void *d_scratch, int64_t scratch_bytes, hipStream_t stream, const Knobs &knobs,
-               bool a_rowmajor, wdx_dtw_launch_info *info) {
-    if (nA == 0 || nB == 0) return WDX_SUCCESS;
-    if (L <= 0) {
-        set_error("DTW series length must be positive");
+// see wdx_common.h.  Every decision is the plan's (wdx_dtw_plan.h); here are the launches and what guards them against a
+// caller whose operands are not the plan's.
+int run_dtw_plan(const DtwPlan &P, const DtwOperands &op, wdx_dtw_launch_info *record) {
+    const wdx_dtw_launch_info &I = P.info;
+    if (I.family == WDX_DTW_NONE) return WDX_SUCCESS;
+    if (op.halo < kDtwHalo) {
+        set_error("reference rows need a halo of %d samples", kDtwHalo);
         return WDX_ERR_INVALID;
     }
-    int w = (window <= 0 || window > L) ? (int)L : window;  // |i-j| <= w-1 is vacuous beyond L
-    const double p2 = penalty * penalty;
-    const WideDtwPlan wide = wide_dtw_plan(L, w, knobs.wide_dtw);   // (WDX_OPT_WIDE_DTW: the grid and argmin rules below are its too)
-    if (w > kMaxRegWindow && !wide.eligible) {
-        if (a_rowmajor) {
-            set_error("the scratch-row DTW path takes the read-minor layout");
-            return WDX_ERR_INVALID;
-        }
-        const int64_t nT = 65536;
-        if (scratch_bytes < dtw_scratch_bytes(L, w) || !d_scratch) {
-            set_error("DTW scratch too small for window %d", w);
-            return WDX_ERR_INVALID;
-        }
-        if (d_argmin) {
-            set_error("fused argmin is not available on the scratch-row DTW path");
-            return WDX_ERR_INVALID;
-        }
-        if (info) *info = {WDX_DTW_SCRATCH, 0, 0, WDX_DTW_LAYOUT_READ_MINOR, 0, 0, (int32_t)nB, w, 0, 1};
-        for (int64_t a_base = 0; a_base < nA; a_base += nT) {
-            int64_t n = nA - a_base < nT ? nA - a_base : nT;
-            dim3 grid((unsigned)((n + 63) / 64));
-            if (info) {
-                ++info->launches;
-                info->grid_x = grid.x;
-            }
-            hipLaunchKernelGGL(dtw_scratch_kernel, grid, dim3(64), 0, stream, AT, ldA, a_base, nA,
-                               a_nan, Bpad, Lpad, halo, (int)nB, b_nan, (int)L, w, p2, out, sA, sB,
-                               (double *)d_scratch, nT);
-        }
-        WDX_HIP_TRY(hipGetLastError());
-        return WDX_SUCCESS;
-    }
-    if (halo < kMaxRegWindow - 1) {
-        set_error("reference rows need a halo of %d samples", kMaxRegWindow - 1);
-        return WDX_ERR_INVALID;
-    }
-    const int64_t gx = (nA + 63) / 64;
-    // one block walks `rpb` refs.  With enough a-series to fill 256 CUs x 8 waves a single block
-    // walks them all and (if asked) folds the argmin in; otherwise the refs are split over grid.y
-    // and the argmin is a second, tiny kernel.
-    int32_t *fused_argmin = nullptr;
-    int rpb = (int)nB;
-    if (gx >= 8 * 3072 || nB == 1 || (gx >= 2048 && nB < 32)) {
-        fused_argmin = d_argmin;
-    } else {
-        // A wave lives for the whole launch (one block = one wave walking its refs): with about as many waves as
-        // the chip has slots (256 CUs x 4 SIMDs x 3 waves of this kernel = 3072) a few stragglers double the
-        // launch time -- 1563 x 2 blocks ran at 67 % of the rate of the same kernel on a long grid.  Aim for
-        // >= 8 waves per slot (dynamic balancing by the dispatcher), at least 16 refs per block.
-        int64_t max_y = (nB + 15) / 16;
-        int64_t want_y = (8 * 3072 + gx - 1) / gx;
-        if (gx * max_y <= 3072) {  // fits the chip at once anyway: latency-bound -- as many short blocks as it takes
-            want_y = (2048 + gx - 1) / gx;
-            max_y = nB;
-        }
-        if (want_y > max_y) want_y = max_y;
-        if (want_y < 1) want_y = 1;
-        rpb = (int)((nB + want_y - 1) / want_y);
-    }
-    if (d_argmin && (sA != nB || sB != 1)) {
+    if (op.argmin && (op.sA != op.nB || op.sB != 1)) {
         set_error("argmin needs the row-major (nA, nB) output layout");
         return WDX_ERR_INVALID;
     }
-    dim3 grid((unsigned)gx, (unsigned)((nB + rpb - 1) / rpb));
-    const int32_t layout = a_rowmajor ? WDX_DTW_LAYOUT_ROW_MAJOR : WDX_DTW_LAYOUT_READ_MINOR;
-    if (info) *info = {WDX_DTW_BAND, 0, 0, layout, fused_argmin != nullptr, 1, rpb, w, grid.x, grid.y};
-    if (wide.eligible) {
-        if (info) info->family = WDX_DTW_WIDE;
-        void (*kern)(const double *, int64_t, int64_t, const uint8_t *, const double *, int64_t, int, int, const uint8_t *, int, int,
-                     double, float *, int64_t, int64_t, int32_t *, int) = a_rowmajor ? dtw_wide_kernel<true> : dtw_wide_kernel<false>;
+    if (P.scratch_bytes && (op.scratch_bytes < P.scratch_bytes || !op.scratch)) {
+        set_error("DTW scratch too small for window %d", I.window);
+        return WDX_ERR_INVALID;
+    }
+    if (record) *record = I;
+    const bool rowmajor = I.layout == WDX_DTW_LAYOUT_ROW_MAJOR;
+    const int L = (int)P.L, w = I.window, nB = (int)op.nB, rpb = I.refs_per_block;
+    const double p2 = op.penalty * op.penalty;
+    int32_t *const fused_argmin = I.fused_argmin ? op.argmin : nullptr;
+    const dim3 grid((unsigned)I.grid_x, (unsigned)I.grid_y);
+    switch (I.family) {
+    case WDX_DTW_WAVEFRONT:  // row-major reads against padded refs; out (nA, nB) row-major
+        hipLaunchKernelGGL(dtw_wavefront_kernel, grid, dim3(256), (size_t)P.lds_bytes, op.stream, op.A, op.nA, op.Bpad, op.Lpad, op.halo,
+                           nB, L, w, p2, op.out);
+        break;
+    case WDX_DTW_SCRATCH:
+        for (int64_t a_base = 0; a_base < op.nA; a_base += kScratchLanes) {
+            const int64_t n = op.nA - a_base < kScratchLanes ? op.nA - a_base : kScratchLanes;
+            hipLaunchKernelGGL(dtw_scratch_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, op.stream, op.A, op.ldA, a_base, op.nA,
+                               op.a_nan, op.Bpad, op.Lpad, op.halo, nB, op.b_nan, L, w, p2, op.out, op.sA, op.sB,
+                               (double *)op.scratch, kScratchLanes);
+        }
+        break;
+    case WDX_DTW_WIDE: {
+        const auto kern = rowmajor ? dtw_wide_kernel<true> : dtw_wide_kernel<false>;
         static LdsAttr attr[2];   // (more than 64 KiB of dynamic LDS from L = 129 on)
-        if (int rc = attr[a_rowmajor].ensure(kern, (size_t)wide.lds_bytes)) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(64), (size_t)wide.lds_bytes, stream, AT, ldA, nA, a_nan, Bpad, Lpad, halo, (int)nB, b_nan,
-                           (int)L, w, p2, out, sA, sB, fused_argmin, rpb);
-        WDX_HIP_TRY(hipGetLastError());
-        if (d_argmin && !fused_argmin) return launch_argmin(out, nA, nB, d_argmin, stream);
-        return WDX_SUCCESS;
+        if (int rc = attr[rowmajor].ensure(kern, (size_t)P.lds_bytes)) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(64), (size_t)P.lds_bytes, op.stream, op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad, op.halo,
+                           nB, op.b_nan, L, w, p2, op.out, op.sA, op.sB, fused_argmin, rpb);
+        break;
     }
-    if (L == 25 && w == 15 && !knobs.no_short_dtw) {
-        if (info) info->family = WDX_DTW_SHORT, info->band_w = 15, info->exact_w = 1;
-        if (a_rowmajor)
-            hipLaunchKernelGGL((dtw_short_kernel<25, 15, true>), grid, dim3(64), 0, stream, AT, ldA, nA, a_nan, Bpad,
-                               Lpad, halo, (int)nB, b_nan, p2, out, sA, sB, fused_argmin, rpb, knobs.dtw_unfused);
-        else
-            hipLaunchKernelGGL((dtw_short_kernel<25, 15, false>), grid, dim3(64), 0, stream, AT, ldA, nA, a_nan, Bpad,
-                               Lpad, halo, (int)nB, b_nan, p2, out, sA, sB, fused_argmin, rpb, knobs.dtw_unfused);
-        WDX_HIP_TRY(hipGetLastError());
-        if (d_argmin && !fused_argmin) return launch_argmin(out, nA, nB, d_argmin, stream);
-        return WDX_SUCCESS;
+    case WDX_DTW_SHORT:
+        hipLaunchKernelGGL((rowmajor ? dtw_short_kernel<25, 15, true> : dtw_short_kernel<25, 15, false>), grid, dim3(64), 0, op.stream,
+                           op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad, op.halo, nB, op.b_nan, p2, op.out, op.sA, op.sB,
+                           fused_argmin, rpb, op.unfused);
+        break;
+    case WDX_DTW_BAND:
+        hipLaunchKernelGGL(band_kernel(I.band_w, rowmajor), grid, dim3(64), 0, op.stream, op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad,
+                           op.halo, nB, op.b_nan, L, w, p2, op.out, op.sA, op.sB, fused_argmin, rpb, op.unfused);
+        break;
     }
-#define WDX_LAUNCH_BAND(WW, EX)                                                                          \
-    do {                                                                                                 \
-        if (info) info->band_w = WW, info->exact_w = EX;                                                 \
-        if (a_rowmajor)                                                                                  \
-            hipLaunchKernelGGL((dtw_band_kernel<WW, EX, true>), grid, dim3(64), 0, stream, AT, ldA, nA,  \
-                               a_nan, Bpad, Lpad, halo, (int)nB, b_nan, (int)L, w, p2, out, sA, sB,      \
-                               fused_argmin, rpb, knobs.dtw_unfused);                                    \
-        else                                                                                             \
-            hipLaunchKernelGGL((dtw_band_kernel<WW, EX, false>), grid, dim3(64), 0, stream, AT, ldA, nA, \
-                               a_nan, Bpad, Lpad, halo, (int)nB, b_nan, (int)L, w, p2, out, sA, sB,      \
-                               fused_argmin, rpb, knobs.dtw_unfused);                                    \
-    } while (0)
-    if (w == 15) {
-        WDX_LAUNCH_BAND(15, true);
-    } else if (w <= 8) {
-        WDX_LAUNCH_BAND(8, false);
-    } else if (w <= 16) {
-        WDX_LAUNCH_BAND(16, false);
-    } else {
-        WDX_LAUNCH_BAND(32, false);
-    }
-#undef WDX_LAUNCH_BAND
     WDX_HIP_TRY(hipGetLastError());
-    if (d_argmin && !fused_argmin) return launch_argmin(out, nA, nB, d_argmin, stream);
+    if (P.argmin_after && op.argmin) return launch_argmin(op.out, op.nA, op.nB, op.argmin, op.stream);
     return WDX_SUCCESS;
 }
 
