@@ -438,6 +438,73 @@ void wdx_oracle_new_means(const double *x, const int64_t *segs, int64_t n_segs, 
     }
 }
 
+/* The optimal change-points of the consensus refinement (sig_proc.py:348-354 asks ruptures.KernelCPD(kernel="linear",
+ * min_size=m).predict(n_bkps=B) for them; parity with ruptures' own bits is UNPINNED).  The stated float64 rule of
+ * include/wdx.h, operation for operation -- the fast twin of tests/helpers/optimal_cpts.py:optimal_cpts, which stays the
+ * readable statement:
+ *   P[t] = P[t-1] + x[t-1], Q[t] = Q[t-1] + x[t-1] * x[t-1]                               sequential
+ *   cost(s, t) = (Q[t] - Q[s]) - ((P[t] - P[s]) * (P[t] - P[s])) / (double)(t - s)
+ *   V_0[t] = cost(0, t), V_k[t] = min over s in [k m, t - m] of V_{k-1}[s] + cost(s, t), strict `<` while s ascends
+ *   cpts = 0, b_1 .. b_B, N by the back-trace from (B, N)
+ * Only the states that can lie on a path to (B, N) are filled, t in [(k + 1) m, N - (B - k) m]: every s a filled state
+ * looks at is a filled state of the row before, so the answer is that of the full table.
+ * Returns 0 and cpts[0 .. n_bkps + 1]; 1 infeasible ((B + 1) m > N), 2 min_size < 1 or n_bkps < 1, 3 a non-finite
+ * sample, 4 out of memory. */
+int wdx_oracle_optimal_cpts(const double *x, int64_t n, int32_t n_bkps, int32_t min_size, int64_t *cpts) {
+    const int64_t N = n, B = n_bkps, m = min_size;
+    if (m < 1 || B < 1) return 2;
+    if (N < 0 || (B + 1) * m > N) return 1;
+    for (int64_t i = 0; i < N; i++)
+        if (!(x[i] - x[i] == 0.0)) return 3;
+    double *P = (double *)malloc(sizeof(double) * (size_t)(N + 1) * 4);
+    int32_t *path = (int32_t *)malloc(sizeof(int32_t) * (size_t)B * (size_t)(N + 1));
+    if (!P || !path) {
+        free(P);
+        free(path);
+        return 4;
+    }
+    double *Q = P + (N + 1), *Vp = Q + (N + 1), *Vn = Vp + (N + 1);
+    P[0] = 0.0;
+    Q[0] = 0.0;
+    for (int64_t t = 0; t < N; t++) {
+        P[t + 1] = P[t] + x[t];
+        Q[t + 1] = Q[t] + x[t] * x[t];
+    }
+    for (int64_t t = m; t <= N - B * m; t++) Vp[t] = (Q[t] - Q[0]) - ((P[t] - P[0]) * (P[t] - P[0])) / (double)t;
+    for (int64_t k = 1; k <= B; k++) {
+        const int64_t s_lo = k * m, t_hi = N - (B - k) * m;
+        int32_t *row = path + (size_t)(k - 1) * (size_t)(N + 1);
+        for (int64_t t = s_lo + m; t <= t_hi; t++) {
+            const double Pt = P[t], Qt = Q[t];
+            double best = HUGE_VAL;
+            int64_t bs = s_lo;
+            for (int64_t s = s_lo; s <= t - m; s++) {
+                const double dP = Pt - P[s];
+                const double c = Vp[s] + ((Qt - Q[s]) - (dP * dP) / (double)(t - s));
+                if (c < best) {
+                    best = c;
+                    bs = s;
+                }
+            }
+            Vn[t] = best;
+            row[t] = (int32_t)bs;
+        }
+        double *sw = Vp;
+        Vp = Vn;
+        Vn = sw;
+    }
+    int64_t t = N;
+    cpts[B + 1] = N;
+    for (int64_t k = B; k >= 1; k--) {
+        t = path[(size_t)(k - 1) * (size_t)(N + 1) + (size_t)t];
+        cpts[k] = t;
+    }
+    cpts[0] = 0;
+    free(P);
+    free(path);
+    return 0;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* A0-A7: detect_results_to_fpt, non-refinement branch (sig_proc.py:394-605)                   */
 /* ------------------------------------------------------------------------------------------ */

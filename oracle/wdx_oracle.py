@@ -126,6 +126,8 @@ def lib():
         L.wdx_oracle_scores_to_cpts.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
         L.wdx_oracle_new_means.restype = None
         L.wdx_oracle_new_means.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.wdx_oracle_optimal_cpts.restype = C.c_int
+        L.wdx_oracle_optimal_cpts.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
         L.wdx_oracle_fingerprint_one.restype = C.c_int
         L.wdx_oracle_fingerprint_one.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int, P(SegParamsC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wdx_oracle_normalize_f64.restype = C.c_int
@@ -189,6 +191,20 @@ def new_means(x, segs) -> np.ndarray:
     out = np.empty(segs.size - 1, dtype=np.float64)
     lib().wdx_oracle_new_means(_p(x), _p(segs), segs.size - 1, _p(out))
     return out
+
+
+def optimal_cpts(x, n_bkps, min_size):
+    """[0, b_1 .. b_B, N] (int64) by the stated float64 rule of include/wdx.h, or None: infeasible, n_bkps < 1,
+    min_size < 1 or a non-finite sample.  The fast twin of tests/helpers/optimal_cpts.py:optimal_cpts."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    n_bkps, min_size = int(n_bkps), int(min_size)
+    if n_bkps < 1 or min_size < 1 or n_bkps >= 2 ** 31 or min_size >= 2 ** 31:
+        return None
+    out = np.empty(n_bkps + 2, dtype=np.int64)
+    rc = lib().wdx_oracle_optimal_cpts(_p(x), x.size, n_bkps, min_size, _p(out))
+    if rc == 4:
+        raise MemoryError("wdx_oracle_optimal_cpts")
+    return None if rc else out
 
 
 def normalize(x, method="mean"):

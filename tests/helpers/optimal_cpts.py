@@ -80,9 +80,12 @@ def _py_round(v):
     return int(round(v))   # Python's round: half to even, as the reference's int(round(...))
 
 
-def refine_one(row, a_start, a_end, seg, ref, query, optimal, ok=True):
+def refine_one(row, a_start, a_end, seg, ref, query, optimal, ok=True, rule="numpy"):
     """One read of the refinement branch -> (status, fpt (K,), dwell (K,), stats (6,), idx (3,)).  seg / ref: the keyword
-    dicts of SegParams / RefineParams (sig_extract.normalization "none" only); ``optimal``: the rule of the barcode tail."""
+    dicts of SegParams / RefineParams (sig_extract.normalization "none" only); ``optimal``: the rule of the barcode tail;
+    ``rule``: which statement of the optimal rule evaluates it, "numpy" (`optimal_cpts` above) or "c" (the oracle's
+    wdx_oracle_optimal_cpts: the same answers, some fifteen times sooner)."""
+    cpts_fn = {"numpy": optimal_cpts, "c": orc.optimal_cpts}[rule]
     p = orc.SegParams(**seg)
     r = orc.RefineParams(query=query, **ref)
     assert p.sig_norm == "none"
@@ -139,7 +142,7 @@ def refine_one(row, a_start, a_end, seg, ref, query, optimal, ok=True):
     sbs = int(cpts[qe])
     tail = scores[sbs:]
     if optimal:
-        cp2 = optimal_cpts(tail, r.barcode_segm_events, p.min_obs_per_base)
+        cp2 = cpts_fn(tail, r.barcode_segm_events, p.min_obs_per_base)
         if cp2 is None:
             return out(3)
     else:
@@ -182,9 +185,9 @@ def refine_one(row, a_start, a_end, seg, ref, query, optimal, ok=True):
     return out(0)
 
 
-def refine_batch(sig, a_start, a_end, seg, ref, query, optimal, ok=None):
+def refine_batch(sig, a_start, a_end, seg, ref, query, optimal, ok=None, rule="numpy"):
     """`refine_one` over a minibatch -> (fpt, dwell, stats, idx, status), the layout of oracle.fingerprint_refine_batch"""
-    res = [refine_one(sig[i], a_start[i], a_end[i], seg, ref, query, optimal, True if ok is None else bool(ok[i]))
+    res = [refine_one(sig[i], a_start[i], a_end[i], seg, ref, query, optimal, True if ok is None else bool(ok[i]), rule)
            for i in range(len(a_start))]
     return (np.stack([r[1] for r in res]), np.stack([r[2] for r in res]), np.stack([r[3] for r in res]),
             np.stack([r[4] for r in res]), np.array([r[0] for r in res], dtype=np.int32))

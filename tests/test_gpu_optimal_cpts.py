@@ -19,7 +19,7 @@ from warpdemux_amd import _lib, models, pipeline, sig_proc
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LDS_CAP = 2047          # kOptLdsCap (wdx_common.h): tails whose prefix sums and value rows live in LDS
+LDS_CAP = 2047          # kOptLdsCap (wdx_refine_optimal_plan.h): tails whose prefix sums and value rows live in LDS
 MAX_BKPS = 253          # the cap of barcode_segm_events
 OK, SEGMENT = 0, 3
 same = oi.same

@@ -1,7 +1,8 @@
 """Optimal change-points of the consensus refinement (WDX_OPT_REFINE_OPTIMAL_CPTS), the parts that need no GPU: the NumPy
-restatement of the rule (tests/helpers/optimal_cpts.py) against brute force in exact arithmetic, its ties, the refinement
-branch composed of the oracle's primitives against the oracle (peak rule) and against fixture g14 (optimal rule), and the
-constructor rules of the Python layer."""
+restatement of the rule (tests/helpers/optimal_cpts.py) against brute force in exact arithmetic, its ties, the oracle's C
+statement of the same rule (wdx_oracle_optimal_cpts, the fast reference of tests/test_gpu_optimal_batch.py) against the NumPy
+one with no tolerance, the refinement branch composed of the oracle's primitives against the oracle (peak rule) and against
+fixture g14 (optimal rule, through either statement), and the constructor rules of the Python layer."""
 import os
 import re
 from types import SimpleNamespace as NS
@@ -58,6 +59,83 @@ def test_failures_of_the_rule():
         assert oc.optimal_cpts(y, 2, 3) is None
 
 
+def _both(x, B, m):
+    """the two statements of the rule on one series: identical arrays or both None; -> the answer"""
+    a, c = oc.optimal_cpts(x, B, m), orc.optimal_cpts(x, B, m)
+    assert (a is None) == (c is None), (len(x), B, m, a, c)
+    if a is not None:
+        assert c.dtype == np.int64 and c.shape == (B + 2,) and a.tolist() == c.tolist(), (len(x), B, m, a.tolist(), c.tolist())
+    return c
+
+
+def _series(rng, N, grid):
+    """noisy steps; ``grid``: levels and noise on the integers, so that costs tie exactly"""
+    n_steps = int(rng.integers(1, 12))
+    lv = np.repeat(rng.normal(0, 4, n_steps), -(-N // n_steps))[:N]
+    if grid:
+        return np.round(lv) + rng.integers(-1, 2, N).astype(np.float64)
+    return lv + rng.normal(0, 1, N)
+
+
+def test_c_statement_equals_the_numpy_statement_on_seeded_series():
+    """330 series, N in 4 .. 600 (small N favoured: the NumPy statement costs B N Python steps), B in 1 .. 40, m in 1 .. 12,
+    every third series on an integer grid; about one in eight infeasible.  No tolerance: the same arrays."""
+    rng = np.random.default_rng(20260114)
+    n_ok = n_none = 0
+    seen_N, seen_B, seen_m = set(), set(), set()
+    for i in range(330):
+        N = (4, 600)[i] if i < 2 else int(4 + 596 * rng.random() ** 3)
+        m = (1, 12)[i] if i < 2 else int(rng.integers(1, min(12, max(1, N // 3)) + 1))
+        fit = N // m - 1                                  # the largest feasible B
+        if i < 2:
+            B = (1, 40)[i]
+        elif i % 8 == 5 or fit < 1:
+            B = int(min(40, max(1, fit + int(rng.integers(1, 4)))))
+        else:
+            B = int(rng.integers(1, min(40, fit) + 1))
+        got = _both(_series(rng, N, i % 3 == 0), B, m)
+        assert (got is not None) == ((B + 1) * m <= N)
+        if got is None:
+            n_none += 1
+        else:
+            n_ok += 1
+            assert got[0] == 0 and got[-1] == N and np.diff(got).min() >= m
+        seen_N.add(N), seen_B.add(B), seen_m.add(m)
+    assert n_ok >= 250 and n_none >= 20, (n_ok, n_none)
+    assert {4, 600} <= seen_N and {1, 40} <= seen_B and seen_m == set(range(1, 13))
+
+
+def test_c_statement_at_the_cap_of_the_change_points_and_at_every_feasibility_edge():
+    rng = np.random.default_rng(7)
+    for N, m in ((253, 1), (254, 1), (255, 1), (600, 1), (600, 2), (507, 2), (508, 2)):      # B = 253, barcode_segm_events' cap
+        assert (_both(_series(rng, N, N % 2 == 0), 253, m) is not None) == (254 * m <= N)
+    for B, m in ((1, 1), (1, 12), (3, 9), (7, 5), (25, 9), (40, 1), (40, 12)):
+        for N in ((B + 1) * m - 1, (B + 1) * m, (B + 1) * m + 1):
+            for grid in (False, True):
+                got = _both(_series(rng, N, grid), B, m)
+                assert (got is not None) == (N >= (B + 1) * m)
+                if N == (B + 1) * m:
+                    assert got.tolist() == list(range(0, N + 1, m)), "one feasible segmentation"
+
+
+def test_c_statement_ties_constants_and_failures():
+    assert _both(np.zeros(40), 3, 9).tolist() == [0, 9, 18, 27, 40]
+    assert _both(np.repeat([1.0, 5.0, 2.0, 7.0], 10), 3, 9).tolist() == [0, 10, 20, 30, 40]
+    for x in (np.full(77, 2.5), np.full(300, -1e6), np.zeros(210), np.full(5, 1e-300)):
+        for B, m in ((1, 1), (4, 1), (5, 5), (3, 2)):
+            _both(x, B, m)
+    x = np.arange(20.0)
+    assert orc.optimal_cpts(x, 1, 11) is None and orc.optimal_cpts(x, 1, 10).tolist() == [0, 10, 20]
+    assert orc.optimal_cpts(x, 1, 0) is None and orc.optimal_cpts(x, 1, -3) is None
+    assert orc.optimal_cpts(x, 0, 3) is None and orc.optimal_cpts(x, -1, 3) is None
+    assert orc.optimal_cpts(np.zeros(0), 1, 1) is None and orc.optimal_cpts(np.zeros(1), 1, 1) is None
+    for bad in (np.nan, np.inf, -np.inf):
+        for at in (0, 7, 19):
+            y = x.copy()
+            y[at] = bad
+            assert _both(y, 2, 3) is None
+
+
 def _reads(consensus, n, seed):
     rng = np.random.default_rng(seed)
     rows = []
@@ -105,7 +183,7 @@ def test_composition_with_the_peak_rule_is_the_oracle(golden_dir):
     assert (o[4] == 0).sum() >= 8 and _same(h[2][rep], o[2][rep]) and _same(h[3][rep], o[3][rep])
 
 
-def test_composition_with_the_optimal_rule_is_fixture_g14(golden_dir):
+def test_composition_with_the_optimal_rule_is_fixture_g14(golden_dir, rule="numpy"):
     """option on: the same composition with `optimal_cpts` for the barcode tail == the reference's own code around a stand-in
     for ruptures.KernelCPD (tests/golden/make_golden_optimal.py)"""
     g = np.load(os.path.join(golden_dir, "g14_refine_optimal.npz"))
@@ -114,7 +192,7 @@ def test_composition_with_the_optimal_rule_is_fixture_g14(golden_dir):
     for k in range(int(g["n"])):
         seg, ref = params_from(g, k)
         a_s, a_e = (int(v) for v in g[f"args_{k}"])
-        st, fpt, dwell, stats, idx = oc.refine_one(g[f"row_{k}"], a_s, a_e, seg, ref, g["consensus"], optimal=True)
+        st, fpt, dwell, stats, idx = oc.refine_one(g[f"row_{k}"], a_s, a_e, seg, ref, g["consensus"], optimal=True, rule=rule)
         tag = str(g[f"tag_{k}"])
         assert st == int(g[f"status_{k}"]), (k, tag, st)
         assert _same(fpt, g[f"fpt_{k}"]) and _same(dwell, g[f"dwell_{k}"]), (k, tag)
@@ -123,6 +201,11 @@ def test_composition_with_the_optimal_rule_is_fixture_g14(golden_dir):
         tags.append(tag)
     assert sts[tags.index("infeasible_tail")] == 3 and sts[tags.index("late_consensus")] == 6
     assert sts[tags.index("shrunk_width")] == 0 and sts.count(0) >= 8
+
+
+def test_composition_through_the_c_statement_is_fixture_g14(golden_dir):
+    """the same twelve cases, every array, with the oracle's wdx_oracle_optimal_cpts evaluating the tail"""
+    test_composition_with_the_optimal_rule_is_fixture_g14(golden_dir, rule="c")
 
 
 def _spc(optimal):

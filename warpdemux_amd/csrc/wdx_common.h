@@ -9,6 +9,7 @@
 #include "wdx_window.h"
 #include "wdx_adc_dev.h"
 #include "wdx_dtw_plan.h"
+#include "wdx_refine_optimal_plan.h"
 
 namespace wdx {
 
@@ -211,17 +212,8 @@ int64_t fingerprint_long_bytes(int64_t max_len);
 // WDX_OPT_REFINE_OPTIMAL_CPTS: the optimal change-points of the barcode tail for the matched reads (RefineRec::state == 3) of
 // A, whichever kernel segmented the adapter (wdx_refine_optimal.hip).  A grid of `slots` workgroups strides over the reads;
 // each owns `slot_bytes` of the context's scratch buffer (the path table of the read in flight and, for tails beyond
-// kOptLdsCap samples, its prefix sums and two rows of the value table).
-constexpr int kOptLdsCap = 2047;                    // tails whose prefix sums and value rows live in LDS
-constexpr size_t kOptScratchMax = (size_t)256 << 20;   // upper bound of the scratch buffer
-constexpr int64_t kOptMaxSlots = 2048;
-struct OptimalPlan {
-    int64_t cap;         // longest tail a slot holds
-    size_t slot_bytes;
-    int64_t slots;
-    size_t bytes;        // slots * slot_bytes <= kOptScratchMax
-};
-OptimalPlan plan_refine_optimal(int64_t n_reads, int64_t max_len, int B, int64_t max_slots = 0);
+// kOptLdsCap samples, its prefix sums and two rows of the value table).  OptimalPlan, plan_refine_optimal and their constants:
+// wdx_refine_optimal_plan.h.
 int launch_optimal_cpts_selftest(const double *d_x, const int64_t *d_off, int64_t n_series, int B, int m, int32_t *d_cpts,
                                  int32_t *d_status, const OptimalPlan &pl, void *d_scratch, hipStream_t stream);
 int launch_clip_bounds_selftest(const float *d_sig, const int64_t *d_row_off, int64_t stride, int64_t n_reads,

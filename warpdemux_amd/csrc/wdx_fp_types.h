@@ -217,7 +217,7 @@ int launch_refine_match_wave(FpArgs A, int64_t n, hipStream_t stream);
 bool refine_tail_wave_takes(const FpArgs &A);
 int launch_refine_tail_wave(FpArgs A, int64_t n, unsigned *back_count, int32_t *back_list, hipStream_t stream);
 
-// (wdx_refine_optimal.hip; OptimalPlan: wdx_common.h)
+// (wdx_refine_optimal.hip; OptimalPlan: wdx_refine_optimal_plan.h)
 int launch_refine_optimal(FpArgs A, const OptimalPlan &pl, void *d_scratch, hipStream_t stream);
 
 }  // namespace wdx

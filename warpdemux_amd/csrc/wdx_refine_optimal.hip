@@ -27,7 +27,6 @@
 // fewer tails from LDS and add nothing.  What would: cost(s, t) does not depend on k, so a pass over the (s, t) pairs that
 // carries several rows of V at once would pay the division once per pair instead of once per row -- not done here.
 #include "wdx_fp_types.h"
-#include <algorithm>
 
 namespace wdx {
 
@@ -35,7 +34,6 @@ namespace {
 
 constexpr int kOB = 256;            // threads of a workgroup
 constexpr int kOptSegMax = 254;     // events of the barcode: barcode_num_events[0] + 1 <= kMaxEvents + 1
-constexpr int kOptMaxTail = WDX_MAX_ADAPTER_SAMPLES;
 
 struct OptLds {
     double dp[4][kOptLdsCap + 1];   // P, Q, V (two rows)
@@ -304,30 +302,7 @@ __global__ __launch_bounds__(kOB) void optimal_cpts_selftest_kernel(const double
 
 }  // namespace
 
-// bytes of one workgroup's slot for tails of up to `cap` samples and B change-points
-static size_t optimal_slot_bytes(int64_t cap, int B) {
-    size_t b = ((size_t)B * (size_t)(cap + 1) * 2 + 15) & ~(size_t)15;
-    if (cap > kOptLdsCap) b += (size_t)4 * (size_t)(cap + 1) * 8;
-    return (b + 255) & ~(size_t)255;
-}
-static int64_t optimal_tail_cap(int64_t max_len) {
-    // (the exact kernel's LDS carve-up rounds max_len up to a multiple of 64 samples: so does this bound)
-    return std::min<int64_t>((std::max<int64_t>(max_len, 64) + 63) / 64 * 64, kOptMaxTail);
-}
-
-OptimalPlan plan_refine_optimal(int64_t n_reads, int64_t max_len, int B, int64_t max_slots) {
-    OptimalPlan pl{};
-    pl.cap = optimal_tail_cap(max_len);
-    pl.slot_bytes = optimal_slot_bytes(pl.cap, B < 1 ? 1 : B);
-    int64_t slots = (int64_t)(kOptScratchMax / pl.slot_bytes);   // (the largest slot, B = 253 at 16 384 samples, is 8.5 MiB)
-    slots = std::min<int64_t>(slots, kOptMaxSlots);
-    if (max_slots > 0) slots = std::min(slots, max_slots);
-    slots = std::min(slots, n_reads);
-    pl.slots = std::max<int64_t>(slots, 1);
-    pl.bytes = (size_t)pl.slots * pl.slot_bytes;
-    return pl;
-}
-
+// (the slot plan -- optimal_slot_bytes, optimal_tail_cap, plan_refine_optimal -- is wdx_refine_optimal_plan.h)
 int64_t fingerprint_optimal_bytes(int64_t n_reads, int64_t max_len, int32_t barcode_segm_events) {
     return n_reads > 0 ? (int64_t)plan_refine_optimal(n_reads, max_len, barcode_segm_events).bytes : 0;
 }
