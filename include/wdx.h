@@ -343,6 +343,51 @@ int wdx_demux_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64_t str
                     const wdx_seg_params *p, int64_t n_refs, double *fpt, float *dist, int32_t *call,
                     int32_t *status);
 
+/* ---- nearest-reference calls with reference labels, margin and rejection ------------------------------------------
+ * The `process_probs` of the distance path (models/utils.py:45-61 ends every classifier of the reference that way: argmax,
+ * label map, top1 - top2 margin, per-class thresholds -> -1), computed where the distances are produced.  The reference has
+ * no such function for distances: the rule below is this engine's own, on the float32 distances wdx_dtw_matrix[_dev] returns.
+ * Reference c of the resident set carries the label ref_label[c] in 0 .. n_labels-1 (several references may share one: a
+ * few consensus signals per barcode, a model's training rows as a 1-nearest-neighbour classifier); a NULL label array is
+ * the identity and n_labels must then be nY.  For the distance row d of a read (float32 throughout):
+ *   c1 = np.argmin(d) (first minimum; a first NaN wins outright), lab = ref_label[c1], d1 = d[c1]
+ *   d2 = min(d[c] for c with ref_label[c] != lab): +inf when no reference has another label, NaN when the row holds a NaN
+ *   margin = d2 - d1 (inf - inf is NaN)
+ *   call = lab, but -1 when d1 is NaN, when min_margin is given and !(margin >= min_margin[lab]), or when max_dist is given
+ *          and !(d1 <= max_dist[lab]) -- a NaN rejects
+ *   a read whose status (nullable) is not 0: call = -1, d1 = d2 = NaN
+ *   counts int64[n_labels + 1] (nullable) is INCREMENTED: bin lab by the accepted reads, bin n_labels by every call of -1.
+ * With identity labels and no thresholds, call is the argmin wdx_dtw_matrix_dev / wdx_demux_dev return wherever the row has
+ * no NaN.  Outputs: call int32[n]; best (n, 2) float32 = {d1, d2} (NaN as 0x7fc00000); dist (n, nY) float32, NULLABLE --
+ * without it the (n, nY) matrix is never written where one lane of the DTW kernel walks all references of a read
+ * (wdx_dtw_last_launch: fused_argmin = 1 reports that the rule ran in the kernel's epilogue), and goes through a
+ * context-owned block of at most 96 MiB, row block by row block, on every other route (fused_argmin = 0: the rule ran on the
+ * block's matrix, nearest_rows_kernel).  Every DTW option (WDX_OPT_WIDE_DTW included) applies as in wdx_dtw_matrix_dev /
+ * wdx_demux_dev.  Label and threshold arrays are read during the call only: no context state, no lifetime rule.
+ * WDX_ERR_NO_REFS without a resident reference set; WDX_ERR_INVALID: n_labels < 1, a NULL label array with n_labels != nY, an
+ * empty reference set.  The context stays usable after a refusal.
+ *
+ * wdx_nearest_dev: dX (nX, L) float64 DEVICE fingerprints against the resident set; every array DEVICE memory; d_status,
+ * d_ref_label, d_min_margin, d_max_dist, d_dist, d_best, d_counts nullable.  Enqueued on `stream`; no synchronisation.
+ * PRECONDITION: device labels lie in 0 .. n_labels-1.  One that does not is read as a group of its own whose reads get call
+ * -1 (bin n_labels); it indexes nothing. */
+int wdx_nearest_dev(wdx_ctx *ctx, const double *dX, int64_t nX, const int32_t *d_status, const int32_t *d_ref_label,
+                    int64_t n_labels, const float *d_min_margin, const float *d_max_dist, float *d_dist, int32_t *d_call,
+                    float *d_best, int64_t *d_counts, void *stream);
+/* wdx_demux_dev (same inputs, same d_work of wdx_demux_workspace_bytes(n_reads, K) bytes, float32 rows) with the rule in the
+ * argmin's place: d_call, d_best and d_counts int64[n_labels + 1] follow it, with the reads' own d_status; d_dist is
+ * nullable. */
+int wdx_demux_nearest_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                          int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
+                          const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_status,
+                          const int32_t *d_ref_label, int64_t n_labels, const float *d_min_margin, const float *d_max_dist,
+                          float *d_dist, int32_t *d_call, float *d_best, int64_t *d_counts, void *d_work, void *stream);
+/* Host form: X (nX, L) float64, the label and threshold arrays, dist (nullable), call and best are HOST memory; runs against
+ * the RESIDENT set (wdx_set_refs), so that the labels' length is the resident nY.  A label outside 0 .. n_labels-1 is
+ * WDX_ERR_INVALID.  One synchronisation. */
+int wdx_dtw_nearest(wdx_ctx *ctx, const double *X, int64_t nX, const int32_t *ref_label, int64_t n_labels, const float *min_margin,
+                    const float *max_dist, float *dist, int32_t *call, float *best);
+
 /* Pipelined form of wdx_demux_batch for the reference's worker loop (file_proc.py:380-454: fill minibatch k+1
  * while minibatch k is processed; 1197-1243: several such workers share one GPU).  A context has WDX_MAX_SLOTS slots (the
  * worker loop uses two; a feeder that serves many producers keeps more minibatches in flight), each with its own stream
@@ -975,7 +1020,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);
 int wdx_kernel_time(wdx_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
 int wdx_kernel_time_reset(wdx_ctx *ctx);
-/* Which DTW kernel the latest dispatch through this context took (wdx_dtw_matrix[_dev], wdx_demux_*, wdx_live_tick,
+/* Which DTW kernel the latest dispatch through this context took (wdx_dtw_matrix[_dev], wdx_demux_*, wdx_nearest_dev, wdx_dtw_nearest, wdx_live_tick,
  * wdx_dtw_svm_predict, wdx_demux_svm_dev; a pipelined minibatch reports at its wdx_demux_submit[_ex]).  Host-side
  * bookkeeping of the launcher: nothing on the device changes.  The thresholds between the paths are tuning constants;
  * tests that mean "band<8>, row-major" ask here instead of restating them.  A call that dispatched nothing (no reads, no
@@ -995,7 +1040,8 @@ typedef struct wdx_dtw_launch_info {
     int32_t band_w;         /* template window of the instantiation (band: 8 / 15 / 16 / 32, short: 15), else 0      */
     int32_t exact_w;        /* 1: the instantiation serves exactly window band_w (no per-cell window mask)           */
     int32_t layout;         /* WDX_DTW_LAYOUT_* (wavefront and short+svm read row-major rows)                        */
-    int32_t fused_argmin;   /* 1: the DTW kernel wrote the argmin itself, 0: separate kernel or none asked for       */
+    int32_t fused_argmin;   /* 1: the DTW kernel wrote the argmin itself, 0: separate kernel or none asked for; after a
+                               nearest-reference call: 1 the rule ran in the DTW kernel's epilogue, 0 behind it on the matrix */
     int32_t launches;       /* DTW kernel launches of the dispatch (the scratch-row loop: one per 65 536 lanes)      */
     int32_t refs_per_block; /* uniform-operand series one block walks (wavefront: 1)                                 */
     int32_t window;         /* effective window, 1..L                                                                */

@@ -79,6 +79,7 @@ EXPORTS = [
     "wdx_fingerprint_adc_dev", "wdx_fingerprint_refine_adc_dev", "wdx_demux_adc_workspace_bytes",
     "wdx_demux_refine_adc_workspace_bytes", "wdx_adc_dev_staging_bytes", "wdx_demux_adc_dev", "wdx_demux_refine_adc_dev",
     "wdx_demux_svm_adc_dev", "wdx_demux_mlp_adc_dev", "wdx_demux_boost_adc_dev",
+    "wdx_nearest_dev", "wdx_demux_nearest_dev", "wdx_dtw_nearest",
 ]
 
 
@@ -546,6 +547,13 @@ def load():
         L.wdx_demux_boost_adc_dev.restype = C.c_int
         L.wdx_demux_boost_adc_dev.argtypes = [vp, A, i64, i64, vp, vp, vp, P(SegParamsC), P(RefineParamsC), vp, vp, vp, vp, vp,
                                               vp, vp, vp, vp]
+        L.wdx_nearest_dev.restype = C.c_int
+        L.wdx_nearest_dev.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_demux_nearest_dev.restype = C.c_int
+        L.wdx_demux_nearest_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, P(SegParamsC), vp, vp, vp, vp, vp, i64, vp,
+                                            vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_dtw_nearest.restype = C.c_int
+        L.wdx_dtw_nearest.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
         _lib = L
         return L
 

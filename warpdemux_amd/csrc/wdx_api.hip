@@ -337,13 +337,14 @@ struct DtwWork {
 // Device rows dX (nX, L) against the resident refs -> d_out (nX, nY) [+ argmin] as the plan (wdx_dtw_plan.h) says: the copy it
 // names into W (WDX_K_TRANSPOSE), then its launches (WDX_K_DTW).  dtw_settle_inf is the caller's.
 static int dtw_rows_vs_refs(wdx_ctx *ctx, const DtwPlan &P, const double *dX, const DtwWork &W, float *d_out, int32_t *d_argmin,
-                            hipStream_t stream) {
+                            hipStream_t stream, const NearestArgs *nearest = nullptr) {
     const DtwRefs &R = ctx->refs;
     if (P.info.family == WDX_DTW_NONE) return WDX_SUCCESS;   // (no reads or no references)
     const int64_t nX = P.prep == DtwPrep::kPaddedReads ? P.rows : P.lanes;
     // lanes = reads, each reading its own row-major row in place, against the resident padded refs
     DtwOperands op{dX, 1, P.lanes, nullptr, R.pad, R.Lpad, R.halo, P.rows, R.has_nan, R.penalty, d_out, R.nY, 1,
                    d_argmin, W.scratch, W.scratch_bytes, ctx->knobs.dtw_unfused, stream};
+    op.nearest = nearest;   // (the rule in the kernel's epilogue: plans of nearest_plan with rule kFused)
     if (P.prep == DtwPrep::kReadMinor) {
         Timed t(ctx, WDX_K_TRANSPOSE, stream);
         if (int rc = launch_transpose(dX, nX, P.L, W.copy, P.ld, W.flags, stream)) return rc;
@@ -391,6 +392,64 @@ int dtw_settle_inf(const DtwRefs &R, const double *dX, int64_t nX, float *d_out,
     if (int rc = launch_dtw_equal_inf(dX, nX, R.pad, R.Lpad, R.halo, R.nY, R.L, d_out, stream)) return rc;
     if (d_argmin) return launch_argmin(d_out, nX, R.nY, d_argmin, stream);
     return WDX_SUCCESS;
+}
+
+// What every nearest-reference entry refuses before it looks at its reads (include/wdx.h: wdx_nearest_dev)
+static int nearest_args_ok(const char *who, const DtwRefs &R, bool have_labels, int64_t n_labels) {
+    if (R.window == 0) {
+        set_error("no reference set: call wdx_set_refs first");
+        return WDX_ERR_NO_REFS;
+    }
+    if (n_labels < 1 || n_labels > INT32_MAX) {
+        set_error("%s: n_labels must be at least 1, not %lld", who, (long long)n_labels);
+        return WDX_ERR_INVALID;
+    }
+    if (R.nY < 1 || R.nY > INT32_MAX) {
+        set_error("%s: the resident reference set holds %lld references", who, (long long)R.nY);
+        return WDX_ERR_INVALID;
+    }
+    if (!have_labels && n_labels != R.nY) {
+        set_error("%s: without reference labels n_labels (%lld) must be the number of resident references (%lld)", who,
+                  (long long)n_labels, (long long)R.nY);
+        return WDX_ERR_INVALID;
+    }
+    return WDX_SUCCESS;
+}
+
+// Device rows dX (nX, L) against the resident refs, then the nearest-reference rule, as nearest_plan says: row block by row
+// block, each with the rule in its DTW kernel's epilogue or behind it on the block's matrix (d_dist, or the context's block
+// buffer when the caller wants no distances).  The copies a plan names live in the context's tmp1 / tmp2, the scratch rows in
+// its scratch block.  d_counts (nullable) is incremented by the calls.  With the mutex held, after use_stream.
+static int nearest_rows_vs_refs(wdx_ctx *ctx, const double *dX, int64_t nX, DtwEntry entry, const NearestArgs &N, float *d_dist,
+                                int64_t *d_counts, hipStream_t stream) {
+    const DtwRefs &R = ctx->refs;
+    const DtwSwitches sw = ctx->knobs.dtw_switches();
+    const int64_t step = nearest_plan(nX, R.nY, R.L, R.window, d_dist != nullptr, R.any_inf, entry, sw).block_rows;
+    for (int64_t r0 = 0; r0 < nX && step > 0; r0 += step) {
+        const int64_t m = std::min(step, nX - r0);
+        const NearestPlan NP = nearest_plan(m, R.nY, R.L, R.window, d_dist != nullptr, R.any_inf, entry, sw);
+        const DtwPlan &P = NP.dtw;
+        int rc;
+        if (P.scratch_bytes && (rc = ctx->scratch.ensure((size_t)P.scratch_bytes))) return rc;
+        if (P.copy_bytes && (rc = ctx->tmp1.ensure((size_t)P.copy_bytes))) return rc;
+        if (P.flag_bytes && (rc = ctx->tmp2.ensure((size_t)P.flag_bytes))) return rc;
+        if (NP.buffer && (rc = ctx->nearest_buf.ensure((size_t)NP.buffer_bytes))) return rc;
+        const DtwWork W{(double *)ctx->tmp1.p, (uint8_t *)ctx->tmp2.p, ctx->scratch.p, (int64_t)ctx->scratch.bytes};
+        const double *X = dX + r0 * R.L;
+        float *out = d_dist ? d_dist + r0 * R.nY : (NP.buffer ? (float *)ctx->nearest_buf.p : nullptr);
+        const NearestArgs Nb = N.from(r0);
+        if (NP.rule == NearestRule::kFused) {
+            if ((rc = dtw_rows_vs_refs(ctx, P, X, W, out, nullptr, stream, &Nb))) return rc;
+        } else {
+            if ((rc = dtw_rows_vs_refs(ctx, P, X, W, out, nullptr, stream))) return rc;
+            if ((rc = dtw_settle_inf(R, X, m, out, nullptr, stream))) return rc;
+            Timed t(ctx, WDX_K_COUNT, stream);
+            if ((rc = launch_nearest_rows(out, m, R.nY, Nb, stream))) return rc;
+        }
+    }
+    if (!d_counts) return WDX_SUCCESS;
+    Timed t(ctx, WDX_K_COUNT, stream);
+    return launch_count_calls(N.call, nullptr, nX, N.n_labels, d_counts, stream);
 }
 
 }  // namespace wdx
@@ -545,7 +604,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     comm_destroy(ctx);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->fp_opt, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->adc_stage, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm_buf, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->fp_opt, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->adc_stage, &ctx->nearest_buf, &ctx->svm_fused, &ctx->svm_refs, &ctx->mlp_buf, &ctx->boost_buf,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf, &ctx->mb_ridx})
         b->release();
     ctx->pin_in.release();
@@ -1142,6 +1201,124 @@ int wdx_synth_fill_dev(wdx_ctx *ctx, uint64_t seed, int64_t first_read, int64_t 
     return launch_synth_fill(seed, first_read, n_reads, n_barcodes, n_bc_events, noise_scale, spikes,
                              d_dwell_table, d_lead, d_bc, d_off, d_sig, d_barcode,
                              (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- nearest-reference calls with reference labels, margin and rejection (include/wdx.h) ------------------------------
+
+int wdx::demux_nearest_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell,
+                                double *d_stats, int32_t *d_status, const NearestArgs &N, float *d_dist, int64_t *d_counts,
+                                void *d_work, void *stream) {
+    WDX_ENTER(ctx);
+    if (rows.f32.n_reads < 0 || !p ||
+        (rows.f32.n_reads > 0 && (rows.missing() || !rows.f32.a_start || !rows.f32.a_end || !d_status || !N.call || !d_work))) {
+        set_error("demux_nearest_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    DtwRefs &R = ctx->refs;
+    if ((rc = nearest_args_ok("demux_nearest_dev", R, N.label != nullptr, N.n_labels))) return rc;
+    const int64_t K = p->barcode_num_events;
+    if ((rc = check_ref_length(R, *p))) return rc;
+    if (dtw_plan(rows.f32.n_reads, R.nY, R.L, R.window, true, DtwEntry::kFused, ctx->knobs.dtw_switches()).unsupported) {
+        set_error("demux_nearest_dev needs window <= %d", kMaxRegWindow);
+        return WDX_ERR_UNSUPPORTED;
+    }
+    if (rows.f32.n_reads == 0) return WDX_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    unsigned char *w = (unsigned char *)d_work;
+    return for_each_slice(ctx, rows, false, p->padding, s, [&](const FpReads &in, int64_t r0) {
+        const int64_t n_reads = in.n_reads;
+        double *fpt = d_fpt ? d_fpt + r0 * K : (double *)w;
+        // (the read-minor copy of a small slice lives in the context's own blocks here: d_work holds the fingerprints and the
+        // fingerprint workspace, which wdx_demux_workspace_bytes covers for every n_reads)
+        const DemuxWork W = demux_work_layout(n_reads, K, false);
+        if (int e = fingerprint_stage(ctx, in, *p, FpOut{fpt, from_read(d_dwell, r0, K), from_read(d_stats, r0, 6), d_status + r0},
+                                      w + W.fp_ws, s))
+            return e;
+        NearestArgs Ns = N.from(r0);
+        Ns.status = d_status + r0;
+        return nearest_rows_vs_refs(ctx, fpt, n_reads, DtwEntry::kFused, Ns, from_read(d_dist, r0, R.nY), d_counts, s);
+    });
+}
+
+extern "C" {
+
+int wdx_nearest_dev(wdx_ctx *ctx, const double *dX, int64_t nX, const int32_t *d_status, const int32_t *d_ref_label,
+                    int64_t n_labels, const float *d_min_margin, const float *d_max_dist, float *d_dist, int32_t *d_call,
+                    float *d_best, int64_t *d_counts, void *stream) {
+    WDX_ENTER(ctx);
+    if (nX < 0 || (nX > 0 && (!dX || !d_call))) {
+        set_error("nearest_dev: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((rc = nearest_args_ok("nearest_dev", ctx->refs, d_ref_label != nullptr, n_labels))) return rc;
+    if (nX == 0) return WDX_SUCCESS;
+    if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
+    const NearestArgs N{d_ref_label, (int32_t)n_labels, d_min_margin, d_max_dist, d_status, d_call, d_best};
+    return nearest_rows_vs_refs(ctx, dX, nX, DtwEntry::kMatrix, N, d_dist, d_counts, (hipStream_t)stream);
+}
+
+int wdx_demux_nearest_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                          int64_t max_len, int64_t n_reads, const int32_t *d_a_start, const int32_t *d_a_end, const uint8_t *d_ok,
+                          const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell, double *d_stats, int32_t *d_status,
+                          const int32_t *d_ref_label, int64_t n_labels, const float *d_min_margin, const float *d_max_dist,
+                          float *d_dist, int32_t *d_call, float *d_best, int64_t *d_counts, void *d_work, void *stream) {
+    const NearestArgs N{d_ref_label, (int32_t)(n_labels >= 1 && n_labels <= INT32_MAX ? n_labels : 0), d_min_margin, d_max_dist, nullptr,
+                        d_call, d_best};
+    return demux_nearest_dev_rows(ctx, DevRows(d_sig, d_row_off, d_row_len, stride, max_len, n_reads, d_a_start, d_a_end, d_ok), p,
+                                  d_fpt, d_dwell, d_stats, d_status, N, d_dist, d_counts, d_work, stream);
+}
+
+int wdx_dtw_nearest(wdx_ctx *ctx, const double *X, int64_t nX, const int32_t *ref_label, int64_t n_labels, const float *min_margin,
+                    const float *max_dist, float *dist, int32_t *call, float *best) {
+    WDX_ENTER(ctx);
+    if (nX < 0 || (nX > 0 && (!X || !call || !best))) {
+        set_error("dtw_nearest: bad arguments");
+        return WDX_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    const DtwRefs &R = ctx->refs;
+    if ((rc = nearest_args_ok("dtw_nearest", R, ref_label != nullptr, n_labels))) return rc;
+    if (ref_label)
+        for (int64_t c = 0; c < R.nY; ++c)
+            if (ref_label[c] < 0 || ref_label[c] >= n_labels) {
+                set_error("dtw_nearest: the label of reference %lld is %d, outside 0 .. %lld", (long long)c, (int)ref_label[c],
+                          (long long)n_labels - 1);
+                return WDX_ERR_INVALID;
+            }
+    if (nX == 0) return WDX_SUCCESS;
+    hipStream_t s = ctx->stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    const size_t xb = (size_t)(nX * R.L) * sizeof(double), ob = (size_t)(nX * R.nY) * sizeof(float);
+    const size_t lb = (size_t)R.nY * sizeof(int32_t), tb = (size_t)n_labels * sizeof(float);
+    if ((rc = ctx->in0.ensure(xb))) return rc;
+    if (ref_label && (rc = ctx->in1.ensure(lb))) return rc;
+    if (min_margin && (rc = ctx->in2.ensure(tb))) return rc;
+    if (max_dist && (rc = ctx->in3.ensure(tb))) return rc;
+    if (dist && (rc = ctx->out0.ensure(ob))) return rc;
+    if ((rc = ctx->out1.ensure((size_t)nX * sizeof(int32_t)))) return rc;
+    if ((rc = ctx->out2.ensure((size_t)nX * 2 * sizeof(float)))) return rc;
+    StreamDrain drain(s);
+    WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X, xb, hipMemcpyHostToDevice, s));
+    if (ref_label) WDX_HIP_TRY(hipMemcpyAsync(ctx->in1.p, ref_label, lb, hipMemcpyHostToDevice, s));
+    if (min_margin) WDX_HIP_TRY(hipMemcpyAsync(ctx->in2.p, min_margin, tb, hipMemcpyHostToDevice, s));
+    if (max_dist) WDX_HIP_TRY(hipMemcpyAsync(ctx->in3.p, max_dist, tb, hipMemcpyHostToDevice, s));
+    const NearestArgs N{ref_label ? (const int32_t *)ctx->in1.p : nullptr, (int32_t)n_labels,
+                        min_margin ? (const float *)ctx->in2.p : nullptr, max_dist ? (const float *)ctx->in3.p : nullptr, nullptr,
+                        (int32_t *)ctx->out1.p, (float *)ctx->out2.p};
+    if ((rc = nearest_rows_vs_refs(ctx, (const double *)ctx->in0.p, nX, DtwEntry::kMatrix, N, dist ? (float *)ctx->out0.p : nullptr,
+                                   nullptr, s)))
+        return rc;
+    if (dist) WDX_HIP_TRY(hipMemcpyAsync(dist, ctx->out0.p, ob, hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipMemcpyAsync(call, ctx->out1.p, (size_t)nX * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipMemcpyAsync(best, ctx->out2.p, (size_t)nX * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipStreamSynchronize(s));
+    drain.done();
+    return WDX_SUCCESS;
 }
 
 }  // extern "C"

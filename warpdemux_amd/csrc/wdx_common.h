@@ -103,6 +103,22 @@ struct DtwRefs {  // resident reference set, both layouts (see DESIGN.md "DTW da
 // row-major layout, over the rows of an (nA, L) row-major array (ldA ignored; a_nan may be null: the kernel flags NaN series
 // itself; the wavefront kernel reads such rows too); the uniform operand is Bpad (nB rows of Lpad samples, each series at +halo).
 // out[a*sA + b*sB] = (float)dtw(a, b).  argmin (nullable) is only legal when the lanes are the reads (sA == nB, sB == 1): int32[nA].
+// The nearest-reference rule of one dispatch (include/wdx.h: wdx_nearest_dev), every pointer DEVICE memory and already at the
+// dispatch's first read.  label[c] in 0 .. n_labels-1 is the label of reference c (null: the identity); a label outside that
+// range is read as n_labels, a group of its own whose call is -1 -- it never indexes a threshold or a histogram bin.
+struct NearestArgs {
+    const int32_t *label;     // [nY], nullable
+    int32_t n_labels;
+    const float *min_margin;  // [n_labels], nullable
+    const float *max_dist;    // [n_labels], nullable
+    const int32_t *status;    // [n], nullable: a read whose status is not 0 gets call -1 and best NaN
+    int32_t *call;            // [n]
+    float *best;              // (n, 2): d1, d2; nullable
+    NearestArgs from(int64_t r0) const {
+        return {label, n_labels, min_margin, max_dist, status ? status + r0 : nullptr, call + r0, best ? best + 2 * r0 : nullptr};
+    }
+};
+
 struct DtwOperands {
     const double *A;
     int64_t ldA, nA;
@@ -120,6 +136,9 @@ struct DtwOperands {
     int64_t scratch_bytes;
     int unfused;  // Knobs::dtw_unfused
     hipStream_t stream;
+    // The nearest-reference rule in the kernel's epilogue (a plan of nearest_plan with rule kFused only: the lanes are the reads
+    // and one lane walks every reference).  `out` may then be null: no distance is written.  `argmin` is not used.
+    const NearestArgs *nearest = nullptr;
 };
 // Launches what the plan names -- one kernel family, the scratch rows' launch loop included -- then launch_argmin where the plan
 // asks for one and `argmin` is given, and stores plan.info as the record of the dispatch (wdx_dtw_last_launch).
@@ -149,6 +168,8 @@ int launch_pad_rows(const double *src, int64_t n, int64_t L, double *dst, int64_
                     uint8_t *has_nan, hipStream_t stream);
 // per-row argmin of a float32 (n, m) matrix with np.argmin semantics
 int launch_argmin(const float *D, int64_t n, int64_t m, int32_t *out, hipStream_t stream);
+// The nearest-reference rule on the rows of a float32 (n, m) matrix (one wave per row): call, best as NearestArgs says
+int launch_nearest_rows(const float *D, int64_t n, int64_t m, const NearestArgs &N, hipStream_t stream);
 // call[r] = status[r] ? -1 : call[r]; counts[call or m] += 1
 int launch_count_calls(int32_t *call, const int32_t *status /*nullable*/, int64_t n, int64_t m,
                        int64_t *counts /*nullable*/, hipStream_t stream);

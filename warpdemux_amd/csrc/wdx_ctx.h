@@ -73,6 +73,9 @@ struct wdx_ctx {
     // float32 staging of an int16 DEVICE shard, one slice at a time (wdx_adc_dev.h: rows, then the slice's shifted bounds and
     // packed lengths); reused in stream order by every slice and every *_adc_dev call
     wdx::Buffer adc_stage;
+    // distances of one row block of a nearest-reference call that asked for no `dist` and whose rule runs behind the DTW
+    // kernels (wdx_dtw_plan.h: nearest_plan, at most kNearestBlockBytes); allocated by the first such call
+    wdx::Buffer nearest_buf;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     wdx::SvmDev svm{};
     bool svm_set = false;
@@ -259,6 +262,10 @@ int fingerprint_refine_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg
 int demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, const wdx_refine_params *rp, double *d_fpt,
                    int64_t *d_dwell, double *d_stats, int32_t *d_refine_idx, int32_t *d_status, float *d_dist, int32_t *d_call,
                    int64_t *d_counts, void *d_work, void *stream);
+// (wdx_api.hip) wdx_demux_nearest_dev: demux_dev_rows without the refinement branch, the nearest-reference rule in the argmin's place
+int demux_nearest_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, double *d_fpt, int64_t *d_dwell,
+                           double *d_stats, int32_t *d_status, const NearestArgs &N, float *d_dist, int64_t *d_counts, void *d_work,
+                           void *stream);
 int demux_svm_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params *p, double *d_fpt, int32_t *d_status,
                        float *d_dist, double *d_prob, int32_t *d_pred, double *d_conf, void *d_work, int64_t block_rows,
                        void *stream);

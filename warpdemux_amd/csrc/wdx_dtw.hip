@@ -18,6 +18,7 @@
 
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 #include <utility>
 
 namespace wdx {
@@ -143,6 +144,93 @@ struct ArgminAcc {
     }
 };
 
+// ---- the nearest-reference rule (include/wdx.h: wdx_nearest_dev) -----------------------------------------------------
+// Running state over the columns a lane has seen, in rising column order: b1 = their minimum, at column idx (np.argmin's first
+// index; ArgminAcc's NaN latch), l1 = that column's label, b2 = the minimum over the columns of every OTHER label.  Update
+// on (v, l):  l == l1: b1 = min(b1, v);  v < b1: the old b1 becomes b2 (everything of a label other than l that was seen is
+// >= b1, and b1 itself is of another label) and (v, l) the new minimum;  else b2 = min(b2, v).  b1 <= b2 throughout, so the
+// label of the second-best group never has to be kept.  l1 = -1 until a value below +inf arrives: a row of +inf alone ends
+// with idx 0 and b1 = b2 = +inf, which is what the rule says of it.
+struct NearestAcc {
+    float b1 = __builtin_huge_valf(), b2 = __builtin_huge_valf();
+    int l1 = -1, idx = 0;
+    bool nan = false;
+    __device__ __forceinline__ void push(float v, int i, int l) {
+        if (nan) return;
+        if (v != v) {
+            nan = true;
+            idx = i;
+        } else if (l == l1) {
+            if (v < b1) {
+                b1 = v;
+                idx = i;
+            }
+        } else if (v < b1) {
+            b2 = b1;
+            b1 = v;
+            l1 = l;
+            idx = i;
+        } else {
+            b2 = v < b2 ? v : b2;
+        }
+    }
+};
+// label of reference c: the caller's, the identity without labels; anything outside 0 .. G-1 is group G
+__device__ __forceinline__ int nearest_label(const NearestArgs &N, int c) {
+    if (!N.label) return c;
+    const int l = N.label[c];
+    return (unsigned)l < (unsigned)N.n_labels ? l : N.n_labels;
+}
+// read a's outputs from the finished state: first-minimum column idx, d1, d2, the NaN latch
+__device__ __forceinline__ void nearest_emit(const NearestArgs &N, int64_t a, int idx, float d1, float d2, bool nan) {
+    const int lab = nearest_label(N, idx);
+    int call = lab < N.n_labels ? lab : -1;
+    if (nan) {
+        d1 = d2 = __builtin_nanf("");
+        call = -1;
+    } else if (call >= 0) {
+        const float margin = d2 - d1;   // (inf - inf: NaN, and the negated comparisons reject it)
+        if (N.min_margin && !(margin >= N.min_margin[lab])) call = -1;
+        if (N.max_dist && !(d1 <= N.max_dist[lab])) call = -1;
+    }
+    if (N.status && N.status[a] != 0) {
+        d1 = d2 = __builtin_nanf("");
+        call = -1;
+    }
+    N.call[a] = call;
+    if (N.best) {
+        N.best[2 * a] = d1;
+        N.best[2 * a + 1] = d2;
+    }
+}
+// What stands in the argmin's place of a lane-per-pair kernel's argument list and epilogue: the int32 argmin array (nullable)
+// of the existing instantiations, or the rule's arguments of the NEAREST ones -- separate instantiations, so that the
+// existing ones keep their arguments, registers and code.
+template <bool NEAREST>
+using DtwEpilogue = std::conditional_t<NEAREST, NearestArgs, int32_t *>;
+template <bool NEAREST>
+using DtwAcc = std::conditional_t<NEAREST, NearestAcc, ArgminAcc>;
+// one finished pair: the distance (NEAREST: only when there is a matrix to write) and the running update
+template <bool NEAREST>
+__device__ __forceinline__ void dtw_pair_out(DtwAcc<NEAREST> &acc, const DtwEpilogue<NEAREST> &epi, float *__restrict__ out,
+                                             int64_t off, bool active, float f, int b) {
+    if constexpr (NEAREST) {
+        if (active && out) out[off] = f;
+        acc.push(f, b, nearest_label(epi, b));
+    } else {
+        if (active) out[off] = f;
+        acc.push(f, b);
+    }
+}
+template <bool NEAREST>
+__device__ __forceinline__ void dtw_lane_out(const DtwAcc<NEAREST> &acc, const DtwEpilogue<NEAREST> &epi, int64_t a, bool active) {
+    if constexpr (NEAREST) {
+        if (active) nearest_emit(epi, a, acc.idx, acc.b1, acc.b2, acc.nan);
+    } else {
+        if (epi && active) epi[a] = acc.idx;
+    }
+}
+
 // true when the float64 row holds a NaN: lane-private sweep of a row-major series (16-byte loads)
 __device__ __forceinline__ bool row_has_nan(const double *__restrict__ row, int L) {
     bool f = false;
@@ -169,12 +257,14 @@ __device__ __forceinline__ bool row_has_nan(const double *__restrict__ row, int 
 // loads (one 64-byte sector per lane and chunk instead of one per row) one chunk ahead of the recurrence,
 // and the NaN flag of the series is computed here when the caller has none: no transposed copy of the
 // fingerprints, no separate flag kernel.
-template <int W, bool EXACT_W, bool ROWMAJOR>
-__global__ __launch_bounds__(64) void dtw_band_kernel(
+// (NEAREST, W = 15: the rule's state would cost the read-minor form its third wave per SIMD -- 170 VGPRs -- so these two are held to
+// the 168 three waves allow; a bound of 0 is no bound, and the existing instantiations are compiled as before)
+template <int W, bool EXACT_W, bool ROWMAJOR, bool NEAREST = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NEAREST && W == 15 ? 3 : 0))) void dtw_band_kernel(
     const double *__restrict__ AT, int64_t ldA, int64_t nA, const uint8_t *__restrict__ a_nan,
     const double *__restrict__ Bpad, int64_t Lpad, int halo, int nB,
     const uint8_t *__restrict__ b_nan, int L, int w, double p2, float *__restrict__ out,
-    int64_t sA, int64_t sB, int32_t *__restrict__ argmin, int refs_per_block, int unfused) {
+    int64_t sA, int64_t sB, DtwEpilogue<NEAREST> epi, int refs_per_block, int unfused) {
     constexpr int B = 2 * W - 1;
     const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = a < nA;
@@ -191,7 +281,7 @@ __global__ __launch_bounds__(64) void dtw_band_kernel(
     bool anan = a_nan ? (a_nan[al] != 0) : false;
     bool swept = a_nan != nullptr || !ROWMAJOR;   // (uniform)
     const double delta = dtw_delta(L);
-    ArgminAcc acc;
+    DtwAcc<NEAREST> acc;
 
     for (int b = b0; b < b1; ++b) {
         const double *__restrict__ y = Bpad + (int64_t)b * Lpad + (halo - (W - 1));
@@ -291,10 +381,9 @@ __global__ __launch_bounds__(64) void dtw_band_kernel(
         const bool pnan = anan || bnan;
         if (pnan) res = __builtin_nan("");
         float f = (float)res;
-        if (active) out[a * sA + (int64_t)b * sB] = f;
-        acc.push(f, b);
+        dtw_pair_out<NEAREST>(acc, epi, out, a * sA + (int64_t)b * sB, active, f, b);
     }
-    if (argmin && active) argmin[a] = acc.idx;
+    dtw_lane_out<NEAREST>(acc, epi, a, active);
 }
 
 // Short series, fully unrolled (the shipped DTW_SVM models: 25-point fingerprints, window 15, penalty 0.1
@@ -354,12 +443,13 @@ __device__ __forceinline__ double dtw_short_pair(const double (&x)[L], const dou
     return pnan ? __builtin_nan("") : res;
 }
 
-template <int L, int W, bool ROWMAJOR>
-__global__ __launch_bounds__(64) void dtw_short_kernel(
+// (NEAREST: held to three waves per SIMD like dtw_short_svm_kernel -- left alone the rule's state takes 175 VGPRs, two waves)
+template <int L, int W, bool ROWMAJOR, bool NEAREST = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NEAREST ? 3 : 0))) void dtw_short_kernel(
     const double *__restrict__ AT, int64_t ldA, int64_t nA, const uint8_t *__restrict__ a_nan,
     const double *__restrict__ Bpad, int64_t Lpad, int halo, int nB,
     const uint8_t *__restrict__ b_nan, double p2, float *__restrict__ out, int64_t sA, int64_t sB,
-    int32_t *__restrict__ argmin, int refs_per_block, int unfused) {
+    DtwEpilogue<NEAREST> epi, int refs_per_block, int unfused) {
     const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = a < nA;
     const int64_t al = active ? a : nA - 1;
@@ -374,15 +464,14 @@ __global__ __launch_bounds__(64) void dtw_short_kernel(
 #pragma unroll
         for (int i = 0; i < L; ++i) anan |= x[i] != x[i];
     }
-    ArgminAcc acc;
+    DtwAcc<NEAREST> acc;
     for (int b = b0; b < b1; ++b) {
         const double *__restrict__ y = Bpad + (int64_t)b * Lpad + halo;
         const double res = dtw_short_pair<L, W>(x, y, p2, anan || (b_nan && b_nan[b]), delta, unfused);
         const float f = (float)res;
-        if (active) out[a * sA + (int64_t)b * sB] = f;
-        acc.push(f, b);
+        dtw_pair_out<NEAREST>(acc, epi, out, a * sA + (int64_t)b * sB, active, f, b);
     }
-    if (argmin && active) argmin[a] = acc.idx;
+    dtw_lane_out<NEAREST>(acc, epi, a, active);
 }
 
 // Any window / any length: two rolling DP rows per lane in global scratch, element (row, j) of lane
@@ -486,12 +575,12 @@ __device__ __forceinline__ void dtw_wide_rows(double (&r)[kWideS], int &i, const
     }
 }
 
-template <bool ROWMAJOR>
+template <bool ROWMAJOR, bool NEAREST = false>
 __global__ __launch_bounds__(64) void dtw_wide_kernel(
     const double *__restrict__ AT, int64_t ldA, int64_t nA, const uint8_t *__restrict__ a_nan,
     const double *__restrict__ Bpad, int64_t Lpad, int halo, int nB,
     const uint8_t *__restrict__ b_nan, int L, int w, double p2, float *__restrict__ out,
-    int64_t sA, int64_t sB, int32_t *__restrict__ argmin, int refs_per_block) {
+    int64_t sA, int64_t sB, DtwEpilogue<NEAREST> epi, int refs_per_block) {
     extern __shared__ double wide_lds[];   // L rows x 64 lanes
     constexpr int S = kWideS;
     double *__restrict__ edge = wide_lds + threadIdx.x;
@@ -505,7 +594,7 @@ __global__ __launch_bounds__(64) void dtw_wide_kernel(
     // (ROWMAJOR without flags: the lazy NaN sweep of dtw_band_kernel -- a finite result proves a NaN-free row)
     bool anan = a_nan ? (a_nan[al] != 0) : false;
     bool swept = a_nan != nullptr || !ROWMAJOR;   // (uniform)
-    ArgminAcc acc;
+    DtwAcc<NEAREST> acc;
 
     for (int b = b0; b < b1; ++b) {
         const double *__restrict__ y = Bpad + (int64_t)b * Lpad + halo;
@@ -542,10 +631,9 @@ __global__ __launch_bounds__(64) void dtw_wide_kernel(
         }
         if (anan || (b_nan && b_nan[b])) res = __builtin_nan("");
         const float f = (float)res;
-        if (active) out[a * sA + (int64_t)b * sB] = f;
-        acc.push(f, b);
+        dtw_pair_out<NEAREST>(acc, epi, out, a * sA + (int64_t)b * sB, active, f, b);
     }
-    if (argmin && active) argmin[a] = acc.idx;
+    dtw_lane_out<NEAREST>(acc, epi, a, active);
 }
 
 // ---- anti-diagonal wavefront kernel (latency path: few pairs, e.g. the live 100 ms ticks) ----------
@@ -661,6 +749,14 @@ static BandKernel band_kernel(int band_w, bool rowmajor) {
     if (band_w == 16) return rowmajor ? dtw_band_kernel<16, false, true> : dtw_band_kernel<16, false, false>;
     return rowmajor ? dtw_band_kernel<32, false, true> : dtw_band_kernel<32, false, false>;
 }
+// ... and their twins with the nearest-reference rule in the epilogue
+using BandNearestKernel = decltype(&dtw_band_kernel<8, false, false, true>);
+static BandNearestKernel band_nearest_kernel(int band_w, bool rowmajor) {
+    if (band_w == 8) return rowmajor ? dtw_band_kernel<8, false, true, true> : dtw_band_kernel<8, false, false, true>;
+    if (band_w == 15) return rowmajor ? dtw_band_kernel<15, true, true, true> : dtw_band_kernel<15, true, false, true>;
+    if (band_w == 16) return rowmajor ? dtw_band_kernel<16, false, true, true> : dtw_band_kernel<16, false, false, true>;
+    return rowmajor ? dtw_band_kernel<32, false, true, true> : dtw_band_kernel<32, false, false, true>;
+}
 
 // see wdx_common.h.  Every decision is the plan's (wdx_dtw_plan.h); here are the launches and what guards them against a
 // caller whose operands are not the plan's.
@@ -677,6 +773,12 @@ int run_dtw_plan(const DtwPlan &P, const DtwOperands &op, wdx_dtw_launch_info *r
     }
     if (P.scratch_bytes && (op.scratch_bytes < P.scratch_bytes || !op.scratch)) {
         set_error("DTW scratch too small for window %d", I.window);
+        return WDX_ERR_INVALID;
+    }
+    const NearestArgs *const nz = op.nearest;
+    if (nz && (!I.fused_argmin || (I.family != WDX_DTW_WIDE && I.family != WDX_DTW_SHORT && I.family != WDX_DTW_BAND) ||
+               I.layout == WDX_DTW_LAYOUT_REFS_AS_LANES || op.sA != op.nB || op.sB != 1 || I.grid_y != 1 || I.refs_per_block < op.nB)) {
+        set_error("the nearest-reference rule is fused only where one lane walks every reference of a read");
         return WDX_ERR_INVALID;
     }
     if (record) *record = I;
@@ -700,18 +802,36 @@ int run_dtw_plan(const DtwPlan &P, const DtwOperands &op, wdx_dtw_launch_info *r
         break;
     case WDX_DTW_WIDE: {
         const auto kern = rowmajor ? dtw_wide_kernel<true> : dtw_wide_kernel<false>;
-        static LdsAttr attr[2];   // (more than 64 KiB of dynamic LDS from L = 129 on)
+        static LdsAttr attr[4];   // (more than 64 KiB of dynamic LDS from L = 129 on)
+        if (nz) {
+            const auto kern_nz = rowmajor ? dtw_wide_kernel<true, true> : dtw_wide_kernel<false, true>;
+            if (int rc = attr[2 + rowmajor].ensure(kern_nz, (size_t)P.lds_bytes)) return rc;
+            hipLaunchKernelGGL(kern_nz, grid, dim3(64), (size_t)P.lds_bytes, op.stream, op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad,
+                               op.halo, nB, op.b_nan, L, w, p2, op.out, op.sA, op.sB, *nz, rpb);
+            break;
+        }
         if (int rc = attr[rowmajor].ensure(kern, (size_t)P.lds_bytes)) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(64), (size_t)P.lds_bytes, op.stream, op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad, op.halo,
                            nB, op.b_nan, L, w, p2, op.out, op.sA, op.sB, fused_argmin, rpb);
         break;
     }
     case WDX_DTW_SHORT:
+        if (nz) {
+            hipLaunchKernelGGL((rowmajor ? dtw_short_kernel<25, 15, true, true> : dtw_short_kernel<25, 15, false, true>), grid, dim3(64), 0,
+                               op.stream, op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad, op.halo, nB, op.b_nan, p2, op.out, op.sA, op.sB,
+                               *nz, rpb, op.unfused);
+            break;
+        }
         hipLaunchKernelGGL((rowmajor ? dtw_short_kernel<25, 15, true> : dtw_short_kernel<25, 15, false>), grid, dim3(64), 0, op.stream,
                            op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad, op.halo, nB, op.b_nan, p2, op.out, op.sA, op.sB,
                            fused_argmin, rpb, op.unfused);
         break;
     case WDX_DTW_BAND:
+        if (nz) {
+            hipLaunchKernelGGL(band_nearest_kernel(I.band_w, rowmajor), grid, dim3(64), 0, op.stream, op.A, op.ldA, op.nA, op.a_nan, op.Bpad,
+                               op.Lpad, op.halo, nB, op.b_nan, L, w, p2, op.out, op.sA, op.sB, *nz, rpb, op.unfused);
+            break;
+        }
         hipLaunchKernelGGL(band_kernel(I.band_w, rowmajor), grid, dim3(64), 0, op.stream, op.A, op.ldA, op.nA, op.a_nan, op.Bpad, op.Lpad,
                            op.halo, nB, op.b_nan, L, w, p2, op.out, op.sA, op.sB, fused_argmin, rpb, op.unfused);
         break;
@@ -935,6 +1055,47 @@ int launch_argmin(const float *D, int64_t n, int64_t m, int32_t *out, hipStream_
     if (n == 0) return WDX_SUCCESS;
     hipLaunchKernelGGL(argmin_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, D,
                        n, m, out);
+    WDX_HIP_TRY(hipGetLastError());
+    return WDX_SUCCESS;
+}
+
+// The nearest-reference rule on a finished matrix: one wave per row, a lane keeps NearestAcc over its columns lane, lane + 64,
+// ..., then the lanes' states are merged.  Merge of two states over disjoint column sets: the smaller b1 wins, on equal values
+// the smaller column (so ties between labels resolve to the first column, as the sequential rule does); the merged b2 is the
+// winner's b2 against what the loser holds of another label -- its b1 when its label differs from the winner's, else its b2.
+// A lane without a finite value (l1 = -1) carries b1 = b2 = +inf and column INT_MAX: it never wins against one that has.  The
+// first NaN column of the row is the minimum of the lanes' NaN columns (a lane stops at its first).
+__global__ __launch_bounds__(256) void nearest_rows_kernel(const float *__restrict__ D, int64_t n, int64_t m, NearestArgs N) {
+    const int64_t r = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    const int lane = threadIdx.x & 63;
+    if (r >= n) return;
+    NearestAcc acc;
+    for (int64_t c = lane; c < m; c += 64) acc.push(D[r * m + c], (int)c, nearest_label(N, (int)c));
+    int nan_col = acc.nan ? acc.idx : 0x7fffffff;
+    float b1 = acc.b1, b2 = acc.b2;
+    int l1 = acc.l1, idx = (acc.nan || acc.l1 < 0) ? 0x7fffffff : acc.idx;
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob1 = __shfl_xor(b1, off), ob2 = __shfl_xor(b2, off);
+        const int ol1 = __shfl_xor(l1, off), oidx = __shfl_xor(idx, off), onan = __shfl_xor(nan_col, off);
+        nan_col = onan < nan_col ? onan : nan_col;
+        const bool take = ob1 < b1 || (ob1 == b1 && oidx < idx);
+        const float wb2 = take ? ob2 : b2;                                // the winner's second value
+        const float lo = take ? (l1 != ol1 ? b1 : b2) : (ol1 != l1 ? ob1 : ob2);   // the loser's best of another label
+        b2 = lo < wb2 ? lo : wb2;
+        if (take) {
+            b1 = ob1;
+            l1 = ol1;
+            idx = oidx;
+        }
+    }
+    if (lane != 0) return;
+    const bool nan = nan_col != 0x7fffffff;
+    nearest_emit(N, r, nan ? nan_col : (l1 < 0 ? 0 : idx), b1, b2, nan);
+}
+
+int launch_nearest_rows(const float *D, int64_t n, int64_t m, const NearestArgs &N, hipStream_t stream) {
+    if (n == 0) return WDX_SUCCESS;
+    hipLaunchKernelGGL(nearest_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, D, n, m, N);
     WDX_HIP_TRY(hipGetLastError());
     return WDX_SUCCESS;
 }

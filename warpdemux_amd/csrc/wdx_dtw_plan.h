@@ -142,4 +142,51 @@ inline DtwPlan dtw_plan(int64_t nX, int64_t nY, int64_t L, int64_t window, bool 
     return P;
 }
 
+// ---- the nearest-reference rule behind a dispatch (wdx_nearest_dev, wdx_demux_nearest_dev, wdx_dtw_nearest) ---------------
+// Where the rule (label of the nearest reference, margin to the nearest reference of another label, thresholds) is computed:
+//   kFused  in the DTW kernel's epilogue, beside what would be its argmin: the plan lets one lane walk all references of a read
+//           (today's fused-argmin condition).  Without a `dist` output these launches write no distances at all.
+//   kAfter  by nearest_rows_kernel on the (rows, nY) float32 matrix the dispatch wrote: references split over grid.y,
+//           references as lanes, the wavefront kernel, the scratch rows -- and every route when a resident reference holds an
+//           infinite sample (dtw_settle_inf rewrites entries of the matrix behind the kernels, so the matrix has to exist).
+// kAfter without a `dist` output sends the distances through a context-owned block buffer of at most kNearestBlockBytes: the
+// call is cut into row blocks of block_rows reads, each dispatched by its own plan.  plan.dtw is the dispatch of one such
+// block (of the whole call when block_rows >= nX), and dtw.info.fused_argmin reports the decision: 1 = kFused.
+enum class NearestRule { kNone, kFused, kAfter };
+constexpr int64_t kNearestBlockBytes = 96ll << 20;
+struct NearestPlan {
+    DtwPlan dtw;
+    NearestRule rule = NearestRule::kNone;  // kNone: nothing to dispatch (no reads, no references) or dtw.unsupported
+    bool buffer = false;        // the distances go through the block buffer
+    int64_t block_rows = 0;     // reads per dispatch
+    int64_t buffer_bytes = 0;   // block_rows * nY * 4 when `buffer`
+};
+
+inline NearestPlan nearest_plan(int64_t nX, int64_t nY, int64_t L, int64_t window, bool have_dist, bool refs_any_inf, DtwEntry entry,
+                                const DtwSwitches &sw) {
+    NearestPlan N;
+    N.dtw = dtw_plan(nX, nY, L, window, true, entry, sw);
+    if (N.dtw.unsupported || N.dtw.info.family == WDX_DTW_NONE) return N;
+    N.block_rows = nX;
+    N.dtw.argmin_after = false;   // (the rule's own first-minimum column takes the argmin's place)
+    if (N.dtw.info.fused_argmin && !refs_any_inf) {
+        N.rule = NearestRule::kFused;
+        return N;
+    }
+    N.rule = NearestRule::kAfter;
+    N.dtw.info.fused_argmin = 0;
+    if (have_dist) return N;
+    N.buffer = true;
+    int64_t rows = kNearestBlockBytes / (nY * (int64_t)sizeof(float));
+    if (rows >= 64) rows -= rows % 64;
+    if (rows < 1) rows = 1;
+    if (rows < nX) {   // the plan of a full block; the caller plans the last, shorter one by its own size
+        const NearestPlan B = nearest_plan(rows, nY, L, window, false, refs_any_inf, entry, sw);
+        if (B.rule != NearestRule::kAfter) return B;   // (a block never fuses where the whole call did not; kept general)
+        N = B;
+    }
+    N.buffer_bytes = N.block_rows * nY * (int64_t)sizeof(float);
+    return N;
+}
+
 }  // namespace wdx

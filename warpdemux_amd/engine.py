@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib, _marshal, synth
+from . import _lib, _marshal, _nearest, synth
 from .sig_proc import SegParams
 
 
@@ -103,6 +103,16 @@ class DemuxResult:
     status: "object"    # torch int32 (n,)  WDX_READ_*
     counts: "object"    # torch int64 (nY+1,) accumulated call histogram (slot nY = failed)
     fpt: Optional["object"] = None   # torch float64 (n, K) when requested
+
+
+@dataclass
+class NearestResult:
+    call: "object"      # torch int32 (n,)   label of the nearest reference, -1 when rejected or failed
+    best: "object"      # torch float32 (n, 2)  d1 = distance to the nearest reference, d2 = to the nearest of another label
+    status: "object"    # torch int32 (n,)  WDX_READ_* (`nearest`: the caller's tensor, or None)
+    counts: "object"    # torch int64 (G+1,) accumulated per-label histogram (slot G = every call of -1)
+    dist: Optional["object"] = None   # torch float32 (n, nY) when requested
+    fpt: Optional["object"] = None    # torch float64 (n, K) when requested (`demux_nearest`)
 
 
 class DemuxEngine:
@@ -289,6 +299,83 @@ class DemuxEngine:
             am = torch.empty(n, dtype=torch.int32, device=self.tdev) if want_argmin else None
         _lib.check(self.L.wdx_dtw_matrix_dev(self.ctx.handle, _dp(X), n, _dp(dist), _dp(am), self._stream()))
         return dist, am
+
+    # -- nearest-reference calls with reference labels, margin and rejection (wdx_nearest_dev; include/wdx.h states the rule) ---
+    def _rule_args(self, labels, n_labels, min_margin, max_dist):
+        """(labels int32 device tensor or None, G, min_margin / max_dist float32 device tensors or None).  Host arrays are
+        checked in full and uploaded; device tensors are checked for dtype and length (labels in 0 .. G-1 is then the
+        caller's precondition, and ``n_labels`` must be given)."""
+        torch = self.torch
+        if torch.is_tensor(labels):
+            if labels.dtype != torch.int32 or tuple(labels.shape) != (self.nY,) or not labels.is_contiguous():
+                raise ValueError(f"labels must be a contiguous int32 ({self.nY},) tensor")
+            if n_labels is None:
+                raise ValueError("device labels need n_labels")
+            G = _nearest.n_labels_of(self.nY, None, n_labels)
+            if G < 1:
+                raise ValueError(f"n_labels must be at least 1, not {G}")
+            lab = labels.to(self.tdev)
+        else:
+            lab, G = _nearest.host_labels(self.nY, labels, n_labels)
+            lab = None if lab is None else torch.from_numpy(lab).to(self.tdev)
+        thr = []
+        for name, t in (("min_margin", min_margin), ("max_dist", max_dist)):
+            if torch.is_tensor(t):
+                if t.dtype != torch.float32 or tuple(t.shape) != (G,) or not t.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous float32 ({G},) tensor")
+                thr.append(t.to(self.tdev))
+            else:
+                t = _nearest.host_threshold(name, t, G)
+                thr.append(None if t is None else torch.from_numpy(t).to(self.tdev))
+        return lab, G, thr[0], thr[1]
+
+    def _rule_counts(self, counts, G):
+        torch = self.torch
+        if counts is None:
+            return torch.zeros(G + 1, dtype=torch.int64, device=self.tdev)
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (G + 1,) or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int64 ({G + 1},) device tensor")
+        return counts
+
+    def nearest(self, X, labels=None, n_labels=None, min_margin=None, max_dist=None, want_dist=False, counts=None, status=None):
+        """The nearest-reference rule on device fingerprints X (n, L) float64 against the resident refs (wdx_nearest_dev):
+        ``labels`` one label per reference (None: the identity), ``min_margin`` / ``max_dist`` a scalar or one threshold per
+        label, ``status`` an optional int32 (n,) device tensor (a read whose status is not 0 is called -1).  Returns a
+        `NearestResult`; without ``want_dist`` no (n, nY) matrix is allocated.  Enqueues on the current stream."""
+        torch = self.torch
+        if X.dtype != torch.float64 or X.dim() != 2 or int(X.shape[1]) != self.K or not X.is_contiguous():
+            raise ValueError(f"X must be a contiguous float64 (n, {self.K}) device tensor")
+        n = int(X.shape[0])
+        lab, G, mm, md = self._rule_args(labels, n_labels, min_margin, max_dist)
+        out = NearestResult(call=torch.empty(n, dtype=torch.int32, device=self.tdev),
+                            best=torch.empty((n, 2), dtype=torch.float32, device=self.tdev), status=status,
+                            counts=self._rule_counts(counts, G),
+                            dist=torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev) if want_dist else None)
+        _lib.check(self.L.wdx_nearest_dev(self.ctx.handle, _dp(X), n, _dp(status), _dp(lab), G, _dp(mm), _dp(md), _dp(out.dist),
+                                          _dp(out.call), _dp(out.best), _dp(out.counts), self._stream()))
+        return out
+
+    def demux_nearest(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, labels=None, n_labels=None,
+                      min_margin=None, max_dist=None, want_dist=False, want_fpt=False, counts=None):
+        """`demux` with the nearest-reference rule in the argmin's place (wdx_demux_nearest_dev): raw float32 rows ->
+        fingerprint -> DTW -> label of the nearest reference, margin, rejection, per-label histogram.  Returns a
+        `NearestResult` (``status`` the reads' own).  An `AdcShard` is not accepted here."""
+        torch = self.torch
+        if isinstance(sig, AdcShard):
+            raise NotImplementedError("demux_nearest takes float32 rows (no int16 twin of wdx_demux_nearest_dev exists)")
+        n = int(a_start.shape[0])
+        lab, G, mm, md = self._rule_args(labels, n_labels, min_margin, max_dist)
+        out = NearestResult(call=torch.empty(n, dtype=torch.int32, device=self.tdev),
+                            best=torch.empty((n, 2), dtype=torch.float32, device=self.tdev),
+                            status=torch.empty(n, dtype=torch.int32, device=self.tdev), counts=self._rule_counts(counts, G),
+                            dist=torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev) if want_dist else None,
+                            fpt=torch.empty((n, self.K), dtype=torch.float64, device=self.tdev) if want_fpt else None)
+        pc = self.params.to_c()
+        _lib.check(self.L.wdx_demux_nearest_dev(
+            self.ctx.handle, _dp(sig), _dp(offsets), None, int(stride), int(max_len), n, _dp(a_start), _dp(a_end), _dp(ok),
+            C.byref(pc), _dp(out.fpt), None, None, _dp(out.status), _dp(lab), G, _dp(mm), _dp(md), _dp(out.dist), _dp(out.call),
+            _dp(out.best), _dp(out.counts), _dp(self._work_for(sig, n, max_len, self.K, False)), self._stream()))
+        return out
 
     # -- classifier tails: SVM (SURVEY.md 8(f) N1), MLP (DTW_MLP; DESIGN.md 4.7), boosted trees (Fpt_Boost; 4.8) --------
     def _set_model(self, model, kind):

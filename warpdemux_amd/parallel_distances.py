@@ -161,3 +161,32 @@ def nearest_reference(X, Y, window=None, penalty=None, wide_dtw=None):
         raise ValueError(f"nearest_reference: wide_dtw is True, False or None, not {wide_dtw!r}")
     with _lib.default_context().wide_dtw_for_call(bool(wide_dtw)):
         return _dtw(X, Y, window, penalty, want_argmin=True)
+
+
+def nearest_label(X, Y, labels=None, window=None, penalty=None, min_margin=None, max_dist=None, want_dist=False, n_labels=None):
+    """(call int32 (nX,), best float32 (nX, 2) = d1, d2[, float32 distances (nX, nY)]): the nearest reference's label, the
+    distance to it and to the nearest reference of another label, and the per-label rejection thresholds -- the rule of
+    include/wdx.h (wdx_nearest_dev), the engine's own: the reference ends its classifiers in ``process_probs`` and has no
+    function for distances.  ``labels``: one integer label per row of ``Y`` (several references may share one), None for
+    the identity; ``min_margin`` / ``max_dist``: a scalar or one float32 threshold per label -- a read is called -1 unless
+    ``d2 - d1 >= min_margin[label]`` and ``d1 <= max_dist[label]``.  Without ``want_dist`` the (nX, nY) matrix is not
+    returned and, on large batches, never written.  Goes through wdx_set_refs + wdx_dtw_nearest."""
+    from . import _nearest
+
+    X, Y = _as_f64_2d(X, "X"), _as_f64_2d(Y, "Y")
+    if X.shape[1] != Y.shape[1]:
+        raise ValueError(f"X and Y must have the same number of columns, got {X.shape[1]} and {Y.shape[1]}")
+    lab, G = _nearest.host_labels(Y.shape[0], labels, n_labels)
+    mm = _nearest.host_threshold("min_margin", min_margin, G)
+    md = _nearest.host_threshold("max_dist", max_dist, G)
+    ctx = _lib.default_context()
+    L = _lib.load()
+    _lib.check(L.wdx_set_refs(ctx.handle, _lib.ptr(Y), Y.shape[0], Y.shape[1], int(window) if window else 0,
+                              float(penalty) if penalty else 0.0))
+    n = X.shape[0]
+    call = np.empty(n, dtype=np.int32)
+    best = np.empty((n, 2), dtype=np.float32)
+    dist = np.empty((n, Y.shape[0]), dtype=np.float32) if want_dist else None
+    _lib.check(L.wdx_dtw_nearest(ctx.handle, _lib.ptr(X), n, _lib.ptr(lab), G, _lib.ptr(mm), _lib.ptr(md), _lib.ptr(dist),
+                                 _lib.ptr(call), _lib.ptr(best)))
+    return (call, best, dist) if want_dist else (call, best)
