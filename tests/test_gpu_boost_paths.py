@@ -327,3 +327,18 @@ def test_feeder_with_a_boost_model_forked_workers():
         assert rec[run] and all(rec[run].values()), (run, rec[run])
     assert rec["mismatch"] == {"first": "INVALID", "second": "INVALID", "predict": "INVALID", "still_serving": True}
     assert rec["refused"] == {"demux_without_references": True}
+
+
+def test_feeder_refuses_an_svm_of_another_class_count():
+    """The same mismatch on the SVM side: a ring laid out for 3 classes, a resident DTW_SVM with 4.  WDX_WANT_SVM through
+    wdx_feeder_run and wdx_feeder_predict is answered WDX_ERR_INVALID naming both counts, minibatch by minibatch; the feeder
+    keeps serving what needs no tail and ends with every slot free (tests/helpers/feeder_svm_mismatch_check.py)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "feeder_svm_mismatch_check.py")],
+                       capture_output=True, text=True, cwd=ROOT, timeout=120)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    rec = json.loads(p.stdout.strip().splitlines()[-1])
+    assert rec["model_classes"] == 4
+    for call in ("run", "predict", "run_again"):
+        assert "the SVM model has 4 classes" in rec[call] and "laid out for 3 and 25" in rec[call], (call, rec[call])
+    assert rec["served_without_the_tail"] is True and rec["alive"] is True
+    assert rec["stats"]["free_slots"] == rec["stats"]["n_slots"] == 2 and rec["stats"]["served"] == 5
