@@ -23,7 +23,18 @@
  * every context owns a non-blocking HIP stream on which all of its host-buffer calls run, so calls
  * through different contexts overlap on the device.  The workspaces of a context are ordered by stream
  * order; when consecutive calls on one context name different streams the library waits for the earlier
- * stream first.  HIP is initialised lazily inside wdx_ctx_create, so a process may fork
+ * stream first.  Streams, as tests/test_gpu_streams.py holds them:
+ *   - A context may be used from any stream of its device -- the NULL stream, the context's own, a caller's non-blocking
+ *     ones -- one call at a time; a *_dev call reads its inputs and writes its outputs in the order of the stream it was
+ *     given and returns without waiting for it (test_late_inputs_on_one_side_stream).
+ *   - When a call names another stream than the call before it on the same context, everything enqueued on the earlier
+ *     stream has finished before the new call's work touches the context's workspaces
+ *     (test_two_streams_share_one_context).
+ *   - A setter (wdx_set_refs, wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model) may be called with work pending,
+ *     on a caller's stream or in a minibatch slot: that work finishes with the state it was enqueued with, later calls
+ *     see the new one (test_resident_state_replaced_behind_pending_work,
+ *     test_minibatch_in_flight_keeps_what_it_was_submitted_with).
+ * HIP is initialised lazily inside wdx_ctx_create, so a process may fork
  * (file_proc.py:1197-1243, ProcessPoolExecutor workers) before creating its context; a context must not
  * be used in a child forked after its creation.  The caller's current HIP device is left unchanged by
  * every entry point.  Nothing in the library reads the environment.
@@ -827,6 +838,11 @@ typedef struct wdx_svm_model {
     const int32_t *label_map;  /* [k] class index -> barcode label (model.label_mapper); nullable     */
     const double *thresholds;  /* [k] model.thresholds; nullable = no thresholding                    */
 } wdx_svm_model;
+/* Copies every array at set time.  The model is replaced in place, so the call first waits for the stream of the latest
+ * call on this context and for every pipelined minibatch in flight (as wdx_set_refs does for the reference set): a minibatch
+ * submitted with WDX_WANT_SVM hands over the answers of the model it was submitted with, every later submit reads the new
+ * one (tests/test_gpu_streams.py: test_minibatch_in_flight_keeps_what_it_was_submitted_with).  The class count a slot's prob
+ * is sized by is fixed at its submit. */
 int wdx_svm_set_model(wdx_ctx *ctx, const wdx_svm_model *m);
 /* d_dist: (n, n_train) float32 DEVICE distances (wdx_dtw_matrix_dev output); outputs DEVICE, nullable:
  * d_prob (n,k) float64 = y_prob, d_pred int32[n] = predicted barcode or -1, d_conf float64[n] = margin. */

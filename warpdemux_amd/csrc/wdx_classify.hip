@@ -274,6 +274,10 @@ int wdx_svm_set_model(wdx_ctx *ctx, const wdx_svm_model *m) {
     std::lock_guard<std::mutex> g(ctx->mu);
     if ((rc = use_stream(ctx, ctx->stream))) return rc;
     WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
+    // a pipelined minibatch (WDX_WANT_SVM) may still be reading it too: its tail's arguments point into svm_buf, which is
+    // rewritten in place below, and a slot's stream is non-blocking (as wdx_set_refs drains the slots for the reference set)
+    for (wdx_ctx *S : ctx->slots)
+        if (S) WDX_HIP_TRY(hipStreamSynchronize(S->stream));
     // one device block: [doubles: dual_coef | rho | probA | probB | thresholds][int32: n_support | start | support | label_map]
     const size_t nd = (size_t)(k - 1) * nsv + 3 * (size_t)np + (size_t)k;
     const size_t ni = 3 * (size_t)k + (size_t)nsv;
@@ -453,8 +457,7 @@ int wdx_mlp_set_model(wdx_ctx *ctx, const wdx_mlp_model *m) {
     std::lock_guard<std::mutex> g(ctx->mu);
     if ((rc = use_stream(ctx, ctx->stream))) return rc;
     WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
-    // ASYMMETRY, kept: wdx_svm_set_model has no device-wide synchronisation
-    WDX_HIP_TRY(hipDeviceSynchronize());  // (nor one on a caller's stream: the model is replaced in place)
+    WDX_HIP_TRY(hipDeviceSynchronize());  // nor one on any other stream: the model is replaced in place
     std::vector<unsigned char> h(bytes);
     ctx->mlp_set = false;  // not set until the upload below has succeeded
     if ((rc = ctx->mlp_buf.ensure(bytes))) return rc;
