@@ -847,27 +847,14 @@ int wdx_fingerprint_profile_dev(wdx_ctx *ctx, const float *d_sig, const int64_t 
 
 }  // extern "C"
 
-DemuxWork wdx::demux_work_layout(int64_t n_reads, int64_t K, bool with_T) {
-    DemuxWork W;
-    W.ld = round_up(n_reads > 0 ? n_reads : 1, 64);
-    W.fptT = round_up(n_reads * K * 8, 256);
-    W.flags = W.fptT + (with_T ? K * W.ld * 8 : 0);
-    W.fp_ws = W.flags + (with_T ? round_up(W.ld, 256) : 0);
-    // (the unrounded pieces plus 512 for the two roundings: what callers have always been told to allocate)
-    W.bytes = n_reads * K * 8 + (with_T ? K * W.ld * 8 + W.ld : 0) + 512 + fingerprint_workspace_bytes(n_reads);
-    return W;
-}
-
 extern "C" {
 
 int64_t wdx_demux_workspace_bytes(int64_t n_reads, int32_t K) {
-    if (n_reads < 0 || K < 1) return 0;
-    return demux_work_layout(n_reads, K, n_reads < kRowMajorMinReads).bytes;   // (small batches: wdx_demux_dev transposes)
+    return demux_workspace_size(n_reads, K);   // (wdx_work_layout.h)
 }
 
 int64_t wdx_demux_refine_workspace_bytes(int64_t n_reads, int32_t K) {
-    const int64_t base = wdx_demux_workspace_bytes(n_reads, K);
-    return base ? round_up(base, 256) + fingerprint_refine_ws_bytes(n_reads) : 0;
+    return demux_refine_workspace_size(n_reads, K);
 }
 
 // the largest d_work any slice of an int16 shard asks its float32 twin's layout for: a full slice, or the last, shorter one
@@ -875,8 +862,7 @@ int64_t wdx_demux_refine_workspace_bytes(int64_t n_reads, int32_t K) {
 static int64_t adc_workspace_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t K, bool refine) {
     if (!ctx || n_reads < 0 || K < 1) return 0;
     const AdcDevPlan P = adc_dev_plan_for(ctx, n_reads, max_len, refine);
-    int64_t (*bytes)(int64_t, int32_t) = refine ? wdx_demux_refine_workspace_bytes : wdx_demux_workspace_bytes;
-    return std::max(bytes(std::min(std::max<int64_t>(n_reads, 1), P.slice_reads), K), bytes(std::max<int64_t>(P.last_reads, 1), K));
+    return demux_shard_workspace_size(n_reads, P.slice_reads, P.last_reads, K, refine);
 }
 
 int64_t wdx_demux_adc_workspace_bytes(wdx_ctx *ctx, int64_t n_reads, int64_t max_len, int32_t K) {
@@ -933,7 +919,7 @@ int wdx::demux_dev_rows(wdx_ctx *ctx, const DevRows &rows, const wdx_seg_params 
         const DemuxWork W = demux_work_layout(n_reads, K, P.prep == DtwPrep::kReadMinor);
         RefineDev *rf = nullptr;
         RefineDevGuard rf_guard{rf};
-        if (rp && (rc = refine_prepare(ctx, *rp, n_reads, from_read(d_refine_idx, r0, 3), w + round_up(W.bytes, 256), s, &rf)))
+        if (rp && (rc = refine_prepare(ctx, *rp, n_reads, from_read(d_refine_idx, r0, 3), w + demux_refine_records_offset(W), s, &rf)))
             return rc;
         if ((rc = fingerprint_stage(ctx, in, *p, FpOut{fpt, from_read(d_dwell, r0, K), from_read(d_stats, r0, 6), status},
                                     w + W.fp_ws, s, rf, rf == nullptr)))

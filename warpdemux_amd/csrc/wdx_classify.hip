@@ -237,7 +237,7 @@ int wdx::demux_boost_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_par
         out.raw = from_read(d_raw, r0, M.dim), out.prob = from_read(d_prob, r0, M.k);
         out.pred = from_read(d_pred, r0), out.conf = from_read(d_conf, r0);
         // (no DTW here, whatever is resident: an empty reference set)
-        return demux_chain(ctx, DtwRefs{}, in, pv, rp, from_read(d_refine_idx, r0, 3), w + round_up(W.bytes, 256), w + W.fp_ws, !rp,
+        return demux_chain(ctx, DtwRefs{}, in, pv, rp, from_read(d_refine_idx, r0, 3), w + demux_refine_records_offset(W), w + W.fp_ws, !rp,
                            tail, out, s);
     });
 }

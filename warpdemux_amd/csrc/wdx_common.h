@@ -10,6 +10,7 @@
 #include "wdx_adc_dev.h"
 #include "wdx_dtw_plan.h"
 #include "wdx_refine_optimal_plan.h"
+#include "wdx_work_layout.h"
 
 namespace wdx {
 

@@ -149,8 +149,6 @@ int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int
 WDX_INTERNAL int dtw_settle_inf(const DtwRefs &R, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin,
                                 hipStream_t stream);
 
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
 // (wdx_api.hip) The fingerprint stage as every entry point but the profiling one runs it: `B` (the context, or the
 // pipeline slot that owns the stream) supplies fp_big (and fp_long) for max_len, the knobs and the WDX_K_FINGERPRINT event scope.
 // main_events = false leaves the main / clip / tail kernel pairs unrecorded (they go back to the pool):
@@ -168,13 +166,7 @@ int refine_prepare(wdx_ctx *B, const wdx_refine_params &rp, int64_t n_reads, int
                    RefineDev **rf);
 // (wdx_api.hip) "barcode_num_events != reference length" check of every entry that fingerprints and then runs the DTW
 int check_ref_length(const DtwRefs &R, const wdx_seg_params &p);
-// (wdx_api.hip) Byte offsets of the pieces of a caller's d_work, and its size (wdx_demux_workspace_bytes):
-// [fpt (n,K) f64][with_T only: fptT (K,ld) f64 | nan flags ld][fingerprint workspace], pieces on 256-byte boundaries.
-// with_T: the read-minor copy wdx_demux_dev makes of a small batch; the classifier entries pass false.
-struct DemuxWork {
-    int64_t ld, fptT, flags, fp_ws, bytes;
-};
-DemuxWork demux_work_layout(int64_t n_reads, int64_t K, bool with_T);
+// (wdx_work_layout.h) demux_work_layout: byte offsets of the pieces of a caller's d_work, and its size
 // (wdx_classify.hip) SVM tail on a device distance block (n, n_train) under WDX_K_SVM; with d_status (nullable) the
 // failed reads are masked right behind it: pred -1, NaN probabilities (the reference never shows them to the model)
 int svm_tail(wdx_ctx *B, const SvmDev &M, const float *d_dist, int64_t n, const int32_t *d_status, double *d_prob,

@@ -21,7 +21,9 @@ enum FpCounter : int {
     kCntBackList,   // (diagnostic, back + 2: beyond the tail kernel's peak list)
     kFpCounters
 };
-static_assert(kFpCounters == 8 && sizeof(ClipRec) == 16, "workspace layout");
+static_assert(kFpCounters == kWorkCounters && sizeof(ClipRec) == kWorkClipRecBytes && kSplitRecBytes == kWorkSplitRecBytes &&
+                  kSplitSlice == kWorkSplitSlice && kCntBack + 1 == kWorkLists,
+              "workspace layout: wdx_work_layout.h");
 constexpr int kNoList = -1;
 struct FpWorkspace {
     unsigned *count;        // kFpCounters
@@ -30,32 +32,23 @@ struct FpWorkspace {
     unsigned char *split;   // kSplitRecBytes x min(n_reads, kSplitSlice)
     unsigned *dbg;          // 16
     int64_t bytes;
-    FpWorkspace(void *d_ws, int64_t n_reads) {
-        const int64_t n = n_reads > 0 ? n_reads : 0;
+    FpWorkspace(void *d_ws, int64_t n_reads) {   // pointers on the pieces of fp_work_layout (wdx_work_layout.h)
+        const FpWorkLayout W = fp_work_layout(n_reads);
         const uintptr_t b = reinterpret_cast<uintptr_t>(d_ws);
-        int64_t off = 0;
-        auto carve = [&](int64_t size) {
-            const uintptr_t at = b + (uintptr_t)off;
-            off += size;
-            return at;
-        };
-        count = reinterpret_cast<unsigned *>(carve(kFpCounters * 4));
-        clip = reinterpret_cast<ClipRec *>(carve((int64_t)sizeof(ClipRec) * n));
-        int32_t **const lists[6] = {&slow, &big0, &big1, &retry, &big2, &back};
-        for (int32_t **l : lists) *l = reinterpret_cast<int32_t *>(carve(4 * n));
-        off = (off + 15) / 16 * 16;
-        // (the lists of one slice for every batch size: 4.6 KB per read -- the launch chain is for batches of 2048 reads and
-        // more by default, but WDX_OPT_FAST_CHAIN_MIN_READS sends smaller ones through it: the randomised parameter tests)
-        split = reinterpret_cast<unsigned char *>(carve((int64_t)kSplitRecBytes * std::min<int64_t>(n, kSplitSlice)));
-        dbg = reinterpret_cast<unsigned *>(carve(64));
-        bytes = off;
+        count = reinterpret_cast<unsigned *>(b + (uintptr_t)W.count);
+        clip = reinterpret_cast<ClipRec *>(b + (uintptr_t)W.clip);
+        int32_t **const lists[kWorkLists] = {&slow, &big0, &big1, &retry, &big2, &back};
+        for (int i = 0; i < kWorkLists; ++i) *lists[i] = reinterpret_cast<int32_t *>(b + (uintptr_t)W.list[i]);
+        split = reinterpret_cast<unsigned char *>(b + (uintptr_t)W.split);
+        dbg = reinterpret_cast<unsigned *>(b + (uintptr_t)W.dbg);
+        bytes = W.bytes;
     }
     int32_t *list(int c) const {
         int32_t *const l[6] = {slow, big0, big1, retry, big2, back};
         return l[c];
     }
 };
-int64_t fingerprint_workspace_bytes(int64_t n_reads) { return FpWorkspace(nullptr, n_reads).bytes; }
+int64_t fingerprint_workspace_bytes(int64_t n_reads) { return fingerprint_workspace_size(n_reads); }
 
 // ---- kernels --------------------------------------------------------------------------------------------------------
 // The fast kernels exist for three (window width, suppression reach) combinations -- the shipped parameter triples:

@@ -31,7 +31,7 @@ struct RefineRec {
     double ev[128];        // nseg event means
     double m[8];           // RefineMatch of the match kernel (bit copy)
 };
-static_assert(sizeof(RefineRec) == 1632, "fingerprint_refine_ws_bytes");
+static_assert(sizeof(RefineRec) == kWorkRefineRecBytes, "fingerprint_refine_ws_bytes: wdx_work_layout.h");
 // what the subsequence match leaves for the barcode's segmentation (RefineRec::m, bit copy)
 struct RefineMatch {
     double mean, sd, ev_med, ev_mad, dt_med, dt_mad;
