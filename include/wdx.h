@@ -34,6 +34,14 @@
  *     on a caller's stream or in a minibatch slot: that work finishes with the state it was enqueued with, later calls
  *     see the new one (test_resident_state_replaced_behind_pending_work,
  *     test_minibatch_in_flight_keeps_what_it_was_submitted_with).
+ * Resident models -- the ONE rule of wdx_svm_set_model, wdx_mlp_set_model and wdx_boost_set_model:
+ *   - The setter copies every array of the model at set time, and may be called with work pending on any stream of the
+ *     device.  It waits for the device.
+ *   - A refused model (WDX_ERR_INVALID, WDX_ERR_UNSUPPORTED), or a host or device allocation or a copy that fails, keeps
+ *     the previous model resident and usable.
+ *   - A minibatch in flight (WDX_WANT_SVM, WDX_WANT_BOOST) hands over the answers of the model it was submitted with; every
+ *     later submit reads the new one.  The class count a slot's prob is sized by is fixed at its submit.
+ *   Each model lives in its own slot of the context: setting one kind leaves the other two untouched.
  * HIP is initialised lazily inside wdx_ctx_create, so a process may fork
  * (file_proc.py:1197-1243, ProcessPoolExecutor workers) before creating its context; a context must not
  * be used in a child forked after its creation.  The caller's current HIP device is left unchanged by
@@ -841,11 +849,7 @@ typedef struct wdx_svm_model {
     const int32_t *label_map;  /* [k] class index -> barcode label (model.label_mapper); nullable     */
     const double *thresholds;  /* [k] model.thresholds; nullable = no thresholding                    */
 } wdx_svm_model;
-/* Copies every array at set time.  The model is replaced in place, so the call first waits for the stream of the latest
- * call on this context and for every pipelined minibatch in flight (as wdx_set_refs does for the reference set): a minibatch
- * submitted with WDX_WANT_SVM hands over the answers of the model it was submitted with, every later submit reads the new
- * one (tests/test_gpu_streams.py: test_minibatch_in_flight_keeps_what_it_was_submitted_with).  The class count a slot's prob
- * is sized by is fixed at its submit. */
+/* The rule of every model setter: "Resident models" at the top of this file. */
 int wdx_svm_set_model(wdx_ctx *ctx, const wdx_svm_model *m);
 /* d_dist: (n, n_train) float32 DEVICE distances (wdx_dtw_matrix_dev output); outputs DEVICE, nullable:
  * d_prob (n,k) float64 = y_prob, d_pred int32[n] = predicted barcode or -1, d_conf float64[n] = margin. */
@@ -878,7 +882,7 @@ int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
  *      the ABI as float64; for a float32 model each is the float32 result widened exactly.
  *      Limits: 1..WDX_MLP_MAX_LAYERS-1 hidden layers of 1..WDX_MLP_MAX_WIDTH units, k = 2..16 classes (softmax over k
  *      output units, or one logistic output unit for k = 2), at most WDX_MLP_MAX_SCALERS scaler steps; beyond them
- *      WDX_ERR_UNSUPPORTED, a malformed model WDX_ERR_INVALID.  A refused model leaves the previous one resident.
+ *      WDX_ERR_UNSUPPORTED, a malformed model WDX_ERR_INVALID.
  *      A row whose (scaled) input holds a NaN or an infinity -- scikit-learn refuses the whole call -- gets pred -1 and
  *      NaN probabilities / margin and is counted. */
 #define WDX_MLP_MAX_LAYERS 5   /* weight matrices: hidden layers + the output layer */
@@ -903,7 +907,7 @@ typedef struct wdx_mlp_model {
     const int32_t *label_map;  /* [k] class index -> barcode label (model.label_mapper); nullable                     */
     const double *thresholds;  /* [k] model.thresholds; nullable = no thresholding                                    */
 } wdx_mlp_model;
-/* Copies every array at set time (synchronises the context's stream first). */
+/* The rule of every model setter: "Resident models" at the top of this file. */
 int wdx_mlp_set_model(wdx_ctx *ctx, const wdx_mlp_model *m);
 /* d_dist: (n, n_in) float32 DEVICE rows; outputs DEVICE, nullable: d_prob (n,k) float64, d_pred int32[n], d_conf
  * float64[n]; d_n_nonfinite: nullable DEVICE int64, INCREMENTED by the rows with a non-finite input.  Enqueued on
@@ -936,8 +940,7 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
  *        leaf_values[leaf_base(t) + leaf * dim + c].
  *      raw_c = scale * (sum over trees, tree 0 first, one float64 add per tree) + bias[c]: float64 multiply, then add.
  *      Limits: 1..254 features, depth 0..16, dim 1..16, k 2..16, >= 1 tree; beyond them WDX_ERR_UNSUPPORTED, a malformed
- *      model WDX_ERR_INVALID.  A model that is refused, or whose staging copy or upload fails, leaves the previous one
- *      resident. */
+ *      model WDX_ERR_INVALID. */
 #define WDX_BOOST_MAX_FEATURES 254
 #define WDX_BOOST_MAX_DEPTH 16
 /* Two kernels serve the tail (wdx_boost.hip), with the same bits in every output: one lane per read (large batches), and
@@ -964,10 +967,7 @@ typedef struct wdx_boost_model {
     const int32_t *label_map;      /* [k] class index -> barcode label; nullable                                       */
     const double *thresholds;      /* [k]; nullable = no thresholding                                                  */
 } wdx_boost_model;
-/* Copies every array at set time.  It waits for the device first, so the boost tails of minibatches already submitted
- * (WDX_WANT_BOOST) have finished with the previous model: they hand over its answers, and every later submit reads the new
- * one (wdx_svm_set_model's rule: a slot in flight keeps what it was submitted with).  The class count a slot's prob is
- * sized by is fixed at its submit. */
+/* The rule of every model setter: "Resident models" at the top of this file. */
 int wdx_boost_set_model(wdx_ctx *ctx, const wdx_boost_model *m);
 /* d_fpt: (n, n_features) float64 DEVICE rows; d_status: nullable DEVICE int32[n], rows with status != WDX_READ_OK get
  * pred -1 and NaN raw / probabilities / margin.  Outputs DEVICE, nullable: d_raw (n, dim) float64, d_prob (n, k) float64,

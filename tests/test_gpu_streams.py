@@ -14,7 +14,9 @@ stream computes the decoy's results -- wrong values, never a fault.
       equal their serial results, and work enqueued behind call 2 sees what the delayed stream wrote (the library did wait)
   (C) the resident reference set / model replaced behind pending work: call 1 keeps the old state, call 2 gets the new one
   (D) wdx_ctx_synchronize(ctx, A): a copy made on B afterwards sees finished results
-  (E) a minibatch in flight (wdx_demux_submit_ex) keeps the reference set and the models it was submitted with
+  (E) a minibatch in flight (wdx_demux_submit_ex) keeps the reference set and the models it was submitted with (the SVM and the
+      boost model: the minibatch path has no WDX_WANT bit for the MLP tail, so no slot ever reads that model, and
+      wdx_mlp_set_model is held by (C) alone; the three model setters wait in one shared function, wdx_classify.hip: install)
 
 The reference of every comparison is the same call made serially on a SECOND context on the default stream, bit for bit; the
 plain fingerprint + DTW case of (A) is compared with the CPU oracle as well.  Each test body runs in a fresh child process

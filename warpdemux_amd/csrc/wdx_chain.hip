@@ -9,24 +9,24 @@ int tail_ready(const wdx_ctx *ctx, int tail, int64_t nY, int64_t K, bool refined
         set_error("no reference set: call wdx_set_refs first");
         return WDX_ERR_NO_REFS;
     }
-    const bool set = tail == WDX_LIVE_TAIL_SVM ? ctx->svm_set : tail == WDX_LIVE_TAIL_MLP ? ctx->mlp_set
-                   : tail == WDX_LIVE_TAIL_BOOST ? ctx->boost_set : true;
+    const bool set = tail == WDX_LIVE_TAIL_SVM ? ctx->svm.set : tail == WDX_LIVE_TAIL_MLP ? ctx->mlp.set
+                   : tail == WDX_LIVE_TAIL_BOOST ? ctx->boost.set : true;
     if (!set) {
         set_error("%s needs wdx_%s_set_model first", who,
                   tail == WDX_LIVE_TAIL_SVM ? "svm" : tail == WDX_LIVE_TAIL_MLP ? "mlp" : "boost");
         return WDX_ERR_NO_REFS;
     }
-    if (tail == WDX_LIVE_TAIL_SVM && nY != ctx->svm.n_train) {
-        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)nY, ctx->svm.n_train);
+    if (tail == WDX_LIVE_TAIL_SVM && nY != ctx->svm.dev.n_train) {
+        set_error("reference set has %lld rows but the SVM was trained on %d", (long long)nY, ctx->svm.dev.n_train);
         return WDX_ERR_INVALID;
     }
-    if (tail == WDX_LIVE_TAIL_MLP && nY != ctx->mlp.sizes[0]) {
-        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)nY, ctx->mlp.sizes[0]);
+    if (tail == WDX_LIVE_TAIL_MLP && nY != ctx->mlp.dev.sizes[0]) {
+        set_error("reference set has %lld rows but the MLP takes %d inputs", (long long)nY, ctx->mlp.dev.sizes[0]);
         return WDX_ERR_INVALID;
     }
-    if (tail == WDX_LIVE_TAIL_BOOST && K != ctx->boost.n_features) {
+    if (tail == WDX_LIVE_TAIL_BOOST && K != ctx->boost.dev.n_features) {
         set_error("%s (%lld) != the boost model's features (%d)", refined ? "barcode_keep_events" : "barcode_num_events",
-                  (long long)K, ctx->boost.n_features);
+                  (long long)K, ctx->boost.dev.n_features);
         return WDX_ERR_INVALID;
     }
     return WDX_SUCCESS;

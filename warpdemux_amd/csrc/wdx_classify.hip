@@ -5,10 +5,7 @@
 // what differs between them -- the SVM's fused route, the MLP's counter -- is in the entry points (model checks: tail_ready).
 #include "wdx_ctx.h"
 
-#include <string.h>
-
 #include <algorithm>
-#include <new>
 
 using namespace wdx;
 
@@ -99,31 +96,32 @@ static int dtw_predict_chunks(wdx_ctx *ctx, const double *X, int64_t n, int64_t 
 static int svm_fused_route(wdx_ctx *ctx, const double *fpt, int64_t n_reads, double *d_prob, int32_t *d_pred, double *d_conf,
                            hipStream_t s) {
     const DtwRefs &R = ctx->refs;
-    const SvmDev &M = ctx->svm;
+    const SvmDev &M = ctx->svm.dev;
+    const SvmFused &F = ctx->svm.fused;
     const int k = M.k;
     int rc;
-    if (ctx->svm_refs_gen != ctx->refs_gen || ctx->svm_refs_model_gen != ctx->svm_model_gen) {
+    if (ctx->svm_refs_gen != ctx->refs_gen || ctx->svm_refs_model_gen != ctx->svm.gen) {
         const size_t rb = (size_t)M.n_sv * R.Lpad * 8;
         if ((rc = ctx->svm_refs.ensure(rb + (size_t)M.n_sv))) return rc;
         if ((rc = launch_gather_rows(R.pad, R.has_nan, M.support, M.n_sv, R.Lpad, (double *)ctx->svm_refs.p,
                                      (uint8_t *)ctx->svm_refs.p + rb, s)))
             return rc;
         ctx->svm_refs_gen = ctx->refs_gen;
-        ctx->svm_refs_model_gen = ctx->svm_model_gen;
+        ctx->svm_refs_model_gen = ctx->svm.gen;
     }
     const size_t rb = (size_t)M.n_sv * R.Lpad * 8;
-    if ((rc = ctx->out0.ensure((size_t)ctx->svm_chunks * (k - 1) * (size_t)n_reads * 8))) return rc;
+    if ((rc = ctx->out0.ensure((size_t)F.chunks * (k - 1) * (size_t)n_reads * 8))) return rc;
     {
         Timed t(ctx, WDX_K_DTW, s);
         if ((rc = launch_dtw_svm_partial(fpt, n_reads, (const double *)ctx->svm_refs.p, R.Lpad, R.halo,
-                                         (const uint8_t *)ctx->svm_refs.p + rb, R.L, R.window, R.penalty, ctx->svm_coefT,
-                                         ctx->svm_chunk_ref0, ctx->svm_chunk_slot, ctx->svm_chunks, k - 1, M.pwr, M.ngamma,
+                                         (const uint8_t *)ctx->svm_refs.p + rb, R.L, R.window, R.penalty, F.coefT,
+                                         F.chunk_ref0, F.chunk_slot, F.chunks, k - 1, M.pwr, M.ngamma,
                                          (double *)ctx->out0.p, s, ctx->knobs.dtw_unfused, &ctx->dtw_last)))
             return rc;
     }
     {
         Timed t(ctx, WDX_K_SVM, s);
-        if ((rc = launch_svm_finish(M, (const double *)ctx->out0.p, ctx->svm_halves, n_reads, d_prob, d_pred, d_conf, s)))
+        if ((rc = launch_svm_finish(M, (const double *)ctx->out0.p, F.halves, n_reads, d_prob, d_pred, d_conf, s)))
             return rc;
     }
     return WDX_SUCCESS;
@@ -147,10 +145,10 @@ int wdx::demux_svm_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_param
     if (rd.f32.n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->svm.k;
+    const int k = ctx->svm.dev.k;
     // (R.any_inf: the fused form has no distance matrix for launch_dtw_equal_inf to settle -- the row blocks do)
     const bool fused = !d_dist && R.L == 25 && R.window == 15 && !ctx->knobs.no_short_dtw && !ctx->knobs.svm_scalar && k >= 2 &&
-                       k <= 16 && ctx->svm_chunks > 0 && !R.any_inf;
+                       k <= 16 && ctx->svm.fused.chunks > 0 && !R.any_inf;
     return for_each_slice(ctx, rd, false, p->padding, s, [&](const FpReads &in, int64_t r0) {
         int rc = WDX_SUCCESS;
         const int64_t n_reads = in.n_reads;
@@ -165,7 +163,7 @@ int wdx::demux_svm_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_param
             rc = svm_fused_route(ctx, fpt, n_reads, prob, pred, conf, s);
         else
             rc = dtw_row_blocks(ctx, fpt, n_reads, rows, from_read(d_dist, r0, R.nY), s, [&](const float *dblk, int64_t b0, int64_t m) {
-                return svm_tail(ctx, ctx->svm, dblk, m, nullptr, from_read(prob, b0, k), from_read(pred, b0), from_read(conf, b0), s);
+                return svm_tail(ctx, ctx->svm.dev, dblk, m, nullptr, from_read(prob, b0, k), from_read(pred, b0), from_read(conf, b0), s);
             });
         if (rc) return rc;
         // failed reads are masked ONCE over all reads (of an int16 shard: of the slice), behind the last block
@@ -189,7 +187,7 @@ int wdx::demux_mlp_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_param
     if (rd.f32.n_reads == 0) return WDX_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->mlp.k;
+    const int k = ctx->mlp.dev.k;
     return for_each_slice(ctx, rd, false, p->padding, s, [&](const FpReads &in, int64_t r0) {
         int rc = WDX_SUCCESS;
         const int64_t n_reads = in.n_reads;
@@ -201,7 +199,7 @@ int wdx::demux_mlp_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_param
         // (failed reads are masked by the kernel itself, block by block: its d_status argument)
         return dtw_row_blocks(ctx, fpt, n_reads, rows, from_read(d_dist, r0, R.nY), s, [&](const float *dblk, int64_t b0, int64_t m) {
             Timed t(ctx, WDX_K_MLP, s);
-            return launch_mlp_predict(ctx->mlp, dblk, m, d_status + r0 + b0, from_read(d_prob, r0 + b0, k),
+            return launch_mlp_predict(ctx->mlp.dev, dblk, m, d_status + r0 + b0, from_read(d_prob, r0 + b0, k),
                                       from_read(d_pred, r0 + b0), from_read(d_conf, r0 + b0), d_n_nonfinite, s);
         });
     });
@@ -226,7 +224,7 @@ int wdx::demux_boost_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_par
     if ((rc = use_stream(ctx, s))) return rc;
     // d_work as wdx_demux_refine_dev lays it out: [fpt][fingerprint workspace] | the refinement kernels' hand-over records
     unsigned char *w = (unsigned char *)d_work;
-    const BoostDev &M = ctx->boost;
+    const BoostDev &M = ctx->boost.dev;
     return for_each_slice(ctx, rd, rp != nullptr, pv.padding, s, [&](const FpReads &in, int64_t r0) {
         const DemuxWork W = demux_work_layout(in.n_reads, K, false);
         double *fpt = d_fpt ? d_fpt + r0 * K : (double *)w;
@@ -242,113 +240,58 @@ int wdx::demux_boost_dev_rows(wdx_ctx *ctx, const DevRows &rd, const wdx_seg_par
     });
 }
 
+// ---- the three setters: check, pack (wdx_model_image.h), install ------------------------------------------------------------
+
+static int refused(const ModelCheck &c) {
+    set_error("%s", c.msg);
+    return c.code;
+}
+
+// The one way a model becomes resident (include/wdx.h, "Resident models").  The caller may have work pending on any stream of
+// the device -- its own, a minibatch slot's -- that reads the previous model through pointers it took at its enqueue: the
+// device is idle before anything of that model goes away.  The image goes into a block of its own, and block, record and
+// flag are swapped only after the copy has succeeded: a failed allocation or copy keeps the previous model, still set.
+// bind(res): res.dev (and what lies beside it) on res.block.p.
+template <class R, class Image, class Bind>
+static int install(wdx_ctx *ctx, R &res, const Image &img, const char *who, Bind bind) {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (int rc = use_stream(ctx, ctx->stream)) return rc;
+    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    WDX_HIP_TRY(hipDeviceSynchronize());
+    const size_t bytes = img.bytes.size();
+    Buffer nb;
+    if (int rc = nb.ensure(bytes)) return rc;
+    if (hipError_t e = hipMemcpy(nb.p, img.bytes.data(), bytes, hipMemcpyHostToDevice); e != hipSuccess) {
+        set_error("%s: hipMemcpy of %zu bytes failed: %s", who, bytes, hipGetErrorString(e));
+        nb.release();
+        return WDX_ERR_HIP;
+    }
+    res.block.release();
+    res.block = nb;
+    bind(res);  // (every pointer of the previous model is replaced here, in one step with its block above)
+    res.set = true;
+    ++res.gen;
+    return WDX_SUCCESS;
+}
+
 extern "C" {
 
 int wdx_svm_set_model(wdx_ctx *ctx, const wdx_svm_model *m) {
     WDX_ENTER(ctx);
-    if (!m || m->n_classes < 2 || m->n_classes > 16 || m->n_sv < 1 || m->n_train < 1 || !m->n_support ||
-        !m->support || !m->dual_coef || !m->rho || !m->probA || !m->probB || m->pwr_dist < 1) {
-        set_error("svm_set_model: need 2..16 classes, support vectors, coefficients and Platt parameters");
-        return WDX_ERR_INVALID;
-    }
-    const int k = m->n_classes, nsv = m->n_sv, np = k * (k - 1) / 2;
-    int64_t tot = 0;
-    std::vector<int32_t> start(k);
-    for (int c = 0; c < k; ++c) {
-        if (m->n_support[c] < 0) {
-            set_error("svm_set_model: negative n_support");
-            return WDX_ERR_INVALID;
-        }
-        start[c] = (int32_t)tot;
-        tot += m->n_support[c];
-    }
-    if (tot != nsv) {
-        set_error("svm_set_model: sum(n_support) != n_sv");
-        return WDX_ERR_INVALID;
-    }
-    for (int s_ = 0; s_ < nsv; ++s_)
-        if (m->support[s_] < 0 || m->support[s_] >= m->n_train) {
-            set_error("svm_set_model: support index out of range");
-            return WDX_ERR_INVALID;
-        }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = use_stream(ctx, ctx->stream))) return rc;
-    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
-    // a pipelined minibatch (WDX_WANT_SVM) may still be reading it too: its tail's arguments point into svm_buf, which is
-    // rewritten in place below, and a slot's stream is non-blocking (as wdx_set_refs drains the slots for the reference set)
-    for (wdx_ctx *S : ctx->slots)
-        if (S) WDX_HIP_TRY(hipStreamSynchronize(S->stream));
-    // one device block: [doubles: dual_coef | rho | probA | probB | thresholds][int32: n_support | start | support | label_map]
-    const size_t nd = (size_t)(k - 1) * nsv + 3 * (size_t)np + (size_t)k;
-    const size_t ni = 3 * (size_t)k + (size_t)nsv;
-    ctx->svm_set = false;  // not set until the upload below has succeeded
-    if ((rc = ctx->svm_buf.ensure(nd * 8 + ni * 4))) return rc;
-    std::vector<unsigned char> h(nd * 8 + ni * 4);
-    double *hd = reinterpret_cast<double *>(h.data());
-    int32_t *hi = reinterpret_cast<int32_t *>(h.data() + nd * 8);
-    size_t o = 0;
-    memcpy(hd + o, m->dual_coef, (size_t)(k - 1) * nsv * 8); o += (size_t)(k - 1) * nsv;
-    memcpy(hd + o, m->rho, (size_t)np * 8); o += np;
-    memcpy(hd + o, m->probA, (size_t)np * 8); o += np;
-    memcpy(hd + o, m->probB, (size_t)np * 8); o += np;
-    if (m->thresholds) memcpy(hd + o, m->thresholds, (size_t)k * 8);
-    memcpy(hi, m->n_support, (size_t)k * 4);
-    memcpy(hi + k, start.data(), (size_t)k * 4);
-    memcpy(hi + 2 * k, m->support, (size_t)nsv * 4);
-    if (m->label_map) memcpy(hi + 2 * k + nsv, m->label_map, (size_t)k * 4);
-    WDX_HIP_TRY(hipMemcpy(ctx->svm_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
-    const double *dd = reinterpret_cast<const double *>(ctx->svm_buf.p);
-    const int32_t *di = reinterpret_cast<const int32_t *>(reinterpret_cast<const unsigned char *>(ctx->svm_buf.p) + nd * 8);
-    SvmDev &S = ctx->svm;
-    S.dual_coef = dd;
-    S.rho = dd + (size_t)(k - 1) * nsv;
-    S.probA = S.rho + np;
-    S.probB = S.probA + np;
-    S.thresholds = m->thresholds ? S.probB + np : nullptr;
-    S.n_support = di;
-    S.start = di + k;
-    S.support = di + 2 * k;
-    S.label_map = m->label_map ? di + 2 * k + nsv : nullptr;
-    S.k = k;
-    S.n_sv = nsv;
-    S.n_train = m->n_train;
-    S.pwr = m->pwr_dist;
-    S.ngamma = (float)(-m->gamma);
-    // for the fused DTW + SVM path (wdx_demux_svm_dev): coefficients vector-major, two chunks per class
-    {
-        const int H = 2, nch = k * H;
-        const size_t cb = (size_t)nsv * (k - 1) * 8, ib = (size_t)(2 * nch + 1) * 4;
-        if ((rc = ctx->svm_fused.ensure(cb + ib))) return rc;
-        std::vector<unsigned char> hf(cb + ib);
-        double *ct = reinterpret_cast<double *>(hf.data());
-        for (int s_ = 0; s_ < nsv; ++s_)
-            for (int q = 0; q < k - 1; ++q) ct[(size_t)s_ * (k - 1) + q] = m->dual_coef[(size_t)q * nsv + s_];
-        int32_t *ref0 = reinterpret_cast<int32_t *>(hf.data() + cb), *slot = ref0 + nch + 1;
-        for (int c = 0; c < k; ++c) {
-            const int half = (m->n_support[c] + 1) / 2;
-            ref0[2 * c] = start[c];
-            ref0[2 * c + 1] = start[c] + half;
-            slot[2 * c] = 2 * c;
-            slot[2 * c + 1] = 2 * c + 1;
-        }
-        ref0[nch] = nsv;
-        WDX_HIP_TRY(hipMemcpy(ctx->svm_fused.p, hf.data(), hf.size(), hipMemcpyHostToDevice));
-        ctx->svm_coefT = reinterpret_cast<const double *>(ctx->svm_fused.p);
-        ctx->svm_chunk_ref0 = reinterpret_cast<const int32_t *>(reinterpret_cast<const unsigned char *>(ctx->svm_fused.p) + cb);
-        ctx->svm_chunk_slot = ctx->svm_chunk_ref0 + nch + 1;
-        ctx->svm_chunks = nch;
-        ctx->svm_halves = H;
-        ++ctx->svm_model_gen;
-    }
-    ctx->svm_set = true;
-    return WDX_SUCCESS;
+    SvmImage img;
+    if (ModelCheck c = check_svm(m); c || (c = pack_svm(m, &img))) return refused(c);
+    return install(ctx, ctx->svm, img, "svm_set_model", [&](ResidentSvm &R) {
+        const SvmBound B = bind_svm(img, R.block.p);
+        R.dev = B.dev;
+        R.fused = B.fused;
+    });
 }
 
 int wdx_svm_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred,
                         double *d_conf, void *stream) {
     WDX_ENTER(ctx);
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->svm_set) {
+    if (!ctx->svm.set) {
         set_error("no SVM model: call wdx_svm_set_model first");
         return WDX_ERR_NO_REFS;
     }
@@ -357,7 +300,7 @@ int wdx_svm_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_
         return WDX_ERR_INVALID;
     }
     if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
-    return svm_tail(ctx, ctx->svm, d_dist, n, nullptr, d_prob, d_pred, d_conf, (hipStream_t)stream);
+    return svm_tail(ctx, ctx->svm.dev, d_dist, n, nullptr, d_prob, d_pred, d_conf, (hipStream_t)stream);
 }
 
 int wdx_demux_svm_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
@@ -389,12 +332,12 @@ int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
     if (n == 0) return WDX_SUCCESS;
     hipStream_t s = ctx->stream;
     if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->svm.k;
+    const int k = ctx->svm.dev.k;
     const int64_t chunk = host_chunk_rows(n, R.nY);
     if ((rc = ensure_chunk_buffers(ctx, chunk, k, 0))) return rc;
     StreamDrain drain(s);
     if ((rc = dtw_predict_chunks(ctx, X, n, chunk, k, prob, pred, conf, s, [&](const float *d, int64_t, int64_t m) {
-            return svm_tail(ctx, ctx->svm, d, m, nullptr, (double *)ctx->out1.p, (int32_t *)ctx->out2.p, (double *)ctx->out3.p, s);
+            return svm_tail(ctx, ctx->svm.dev, d, m, nullptr, (double *)ctx->out1.p, (int32_t *)ctx->out2.p, (double *)ctx->out3.p, s);
         })))
         return rc;
     WDX_HIP_TRY(hipStreamSynchronize(s));
@@ -404,112 +347,16 @@ int wdx_dtw_svm_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
 
 int wdx_mlp_set_model(wdx_ctx *ctx, const wdx_mlp_model *m) {
     WDX_ENTER(ctx);
-    // every check before anything of the resident model is touched: a refused model keeps the previous one
-    if (!m || (m->dtype_bytes != 4 && m->dtype_bytes != 8) || m->n_classes < 2 || m->n_layers < 1 || m->n_scalers < 0 ||
-        m->hidden_activation < WDX_MLP_ACT_IDENTITY || m->hidden_activation > WDX_MLP_ACT_RELU) {
-        set_error("mlp_set_model: need a float32 / float64 model with >= 2 classes, layers and a known activation");
-        return WDX_ERR_INVALID;
-    }
-    const int nl = m->n_layers, k = m->n_classes;
-    if (nl < 2 || nl > WDX_MLP_MAX_LAYERS) {
-        set_error("mlp_set_model: %d hidden layers (1..%d supported)", nl - 1, WDX_MLP_MAX_LAYERS - 1);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (k > 16) {
-        set_error("mlp_set_model: %d classes (2..16 supported)", k);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (m->n_scalers > WDX_MLP_MAX_SCALERS) {
-        set_error("mlp_set_model: %d scaler steps (at most %d supported)", m->n_scalers, WDX_MLP_MAX_SCALERS);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    for (int i = 0; i <= nl; ++i)
-        if (m->sizes[i] < 1) {
-            set_error("mlp_set_model: layer size %d of entry %d", m->sizes[i], i);
-            return WDX_ERR_INVALID;
-        }
-    for (int i = 0; i < nl; ++i)
-        if (!m->coefs[i] || !m->intercepts[i]) {
-            set_error("mlp_set_model: layer %d has no coefficients / intercepts", i);
-            return WDX_ERR_INVALID;
-        }
-    const int nout = m->sizes[nl];
-    if (nout != k && !(nout == 1 && k == 2)) {
-        set_error("mlp_set_model: %d output units for %d classes", nout, k);
-        return WDX_ERR_INVALID;
-    }
-    int widest = 16;
-    for (int i = 1; i < nl; ++i) {
-        if (m->sizes[i] > WDX_MLP_MAX_WIDTH) {
-            set_error("mlp_set_model: hidden layer of %d units (at most %d supported)", m->sizes[i], WDX_MLP_MAX_WIDTH);
-            return WDX_ERR_UNSUPPORTED;
-        }
-        widest = std::max(widest, m->sizes[i]);
-    }
-    const int64_t n_in = m->sizes[0];
-    const size_t T = (size_t)m->dtype_bytes;
-    // one device block: [doubles: scaler mean / scale steps | thresholds][working dtype: W_i | b_i ...][int32: label map]
-    size_t nd = (m->thresholds ? (size_t)k : 0);
-    for (int s_ = 0; s_ < m->n_scalers; ++s_) nd += (m->scaler_mean[s_] ? n_in : 0) + (m->scaler_scale[s_] ? n_in : 0);
-    size_t nw = 0;
-    for (int i = 0; i < nl; ++i) nw += (size_t)m->sizes[i] * m->sizes[i + 1] + (size_t)m->sizes[i + 1];
-    const size_t bytes = nd * 8 + round_up((int64_t)(nw * T), 8) + (m->label_map ? (size_t)k * 4 : 0);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = use_stream(ctx, ctx->stream))) return rc;
-    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));  // no kernel may still be reading the previous model
-    WDX_HIP_TRY(hipDeviceSynchronize());  // nor one on any other stream: the model is replaced in place
-    std::vector<unsigned char> h(bytes);
-    ctx->mlp_set = false;  // not set until the upload below has succeeded
-    if ((rc = ctx->mlp_buf.ensure(bytes))) return rc;
-    MlpDev M{};
-    unsigned char *dev = (unsigned char *)ctx->mlp_buf.p;
-    size_t o = 0;
-    for (int s_ = 0; s_ < m->n_scalers; ++s_) {
-        for (int which = 0; which < 2; ++which) {
-            const double *src = which ? m->scaler_scale[s_] : m->scaler_mean[s_];
-            if (!src) continue;
-            memcpy(h.data() + o, src, (size_t)n_in * 8);
-            (which ? M.scale[s_] : M.mean[s_]) = (const double *)(dev + o);
-            o += (size_t)n_in * 8;
-        }
-    }
-    if (m->thresholds) {
-        memcpy(h.data() + o, m->thresholds, (size_t)k * 8);
-        M.thresholds = (const double *)(dev + o);
-        o += (size_t)k * 8;
-    }
-    for (int i = 0; i < nl; ++i) {
-        const size_t wb = (size_t)m->sizes[i] * m->sizes[i + 1] * T, bb = (size_t)m->sizes[i + 1] * T;
-        memcpy(h.data() + o, m->coefs[i], wb);
-        M.coef[i] = dev + o;
-        o += wb;
-        memcpy(h.data() + o, m->intercepts[i], bb);
-        M.bias[i] = dev + o;
-        o += bb;
-    }
-    o = (size_t)round_up((int64_t)o, 8);
-    if (m->label_map) {
-        memcpy(h.data() + o, m->label_map, (size_t)k * 4);
-        M.label_map = (const int32_t *)(dev + o);
-    }
-    WDX_HIP_TRY(hipMemcpy(ctx->mlp_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
-    for (int i = 0; i <= nl; ++i) M.sizes[i] = m->sizes[i];
-    M.n_layers = nl;
-    M.n_scalers = m->n_scalers;
-    M.dtype_bytes = m->dtype_bytes;
-    M.hidden_act = m->hidden_activation;
-    M.k = k;
-    M.ld = (int)round_up(widest, 16) + 1;
-    ctx->mlp = M;
-    ctx->mlp_set = true;
-    return WDX_SUCCESS;
+    MlpImage img;
+    if (ModelCheck c = check_mlp(m); c || (c = pack_mlp(m, &img))) return refused(c);
+    return install(ctx, ctx->mlp, img, "mlp_set_model", [&](Resident<MlpDev> &R) { R.dev = bind_mlp(img, R.block.p); });
 }
 
 int wdx_mlp_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred, double *d_conf,
                         int64_t *d_n_nonfinite, void *stream) {
     WDX_ENTER(ctx);
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->mlp_set) {
+    if (!ctx->mlp.set) {
         set_error("no MLP model: call wdx_mlp_set_model first");
         return WDX_ERR_NO_REFS;
     }
@@ -519,7 +366,7 @@ int wdx_mlp_predict_dev(wdx_ctx *ctx, const float *d_dist, int64_t n, double *d_
     }
     if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
     Timed t(ctx, WDX_K_MLP, (hipStream_t)stream);
-    return launch_mlp_predict(ctx->mlp, d_dist, n, nullptr, d_prob, d_pred, d_conf, d_n_nonfinite, (hipStream_t)stream);
+    return launch_mlp_predict(ctx->mlp.dev, d_dist, n, nullptr, d_prob, d_pred, d_conf, d_n_nonfinite, (hipStream_t)stream);
 }
 
 int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, int32_t *pred, double *conf,
@@ -536,7 +383,7 @@ int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
     if (n == 0) return WDX_SUCCESS;
     hipStream_t s = ctx->stream;
     if ((rc = use_stream(ctx, s))) return rc;
-    const int k = ctx->mlp.k;
+    const int k = ctx->mlp.dev.k;
     int64_t chunk = host_chunk_rows(n, R.nY);
     if (ctx->knobs.mlp_chunk_rows > 0) chunk = std::min<int64_t>(chunk, ctx->knobs.mlp_chunk_rows);
     if ((rc = ensure_chunk_buffers(ctx, chunk, k, 8))) return rc;   // (+ 8: the non-finite counter behind conf)
@@ -546,7 +393,7 @@ int wdx_dtw_mlp_predict(wdx_ctx *ctx, const double *X, int64_t n, double *prob, 
     WDX_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
     if ((rc = dtw_predict_chunks(ctx, X, n, chunk, k, prob, pred, conf, s, [&](const float *d, int64_t, int64_t m) {
             Timed t(ctx, WDX_K_MLP, s);
-            return launch_mlp_predict(ctx->mlp, d, m, nullptr, (double *)ctx->out1.p, (int32_t *)ctx->out2.p,
+            return launch_mlp_predict(ctx->mlp.dev, d, m, nullptr, (double *)ctx->out1.p, (int32_t *)ctx->out2.p,
                                       (double *)ctx->out3.p, d_cnt, s);
         })))
         return rc;
@@ -577,122 +424,18 @@ int wdx_demux_mlp_adc_dev(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t max_le
 
 // ---- Fpt_Boost: oblivious trees on the fingerprint rows (wdx_boost.hip) ----------------------------------
 
-
 int wdx_boost_set_model(wdx_ctx *ctx, const wdx_boost_model *m) {
     WDX_ENTER(ctx);
-    // every check before anything of the resident model is touched: a refused model keeps the previous one
-    if (!m || m->n_trees < 1 || m->n_features < 1 || m->dim < 1 || m->n_classes < 2 || !m->depth || !m->leaf_values ||
-        !m->bias) {
-        set_error("boost_set_model: need >= 1 tree, >= 1 feature, >= 2 classes, depths, leaf values and a bias");
-        return WDX_ERR_INVALID;
-    }
-    const int nt = m->n_trees, F = m->n_features, dim = m->dim, k = m->n_classes;
-    if (F > WDX_BOOST_MAX_FEATURES) {
-        set_error("boost_set_model: %d features (1..%d supported)", F, WDX_BOOST_MAX_FEATURES);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (dim > 16 || k > 16) {
-        set_error("boost_set_model: %d values per leaf for %d classes (1..16 and 2..16 supported)", dim, k);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (dim != k && !(dim == 1 && k == 2)) {
-        set_error("boost_set_model: %d values per leaf for %d classes", dim, k);
-        return WDX_ERR_INVALID;
-    }
-    size_t n_splits = 0, n_leaves = 0;
-    for (int t = 0; t < nt; ++t) {
-        const int d = m->depth[t];
-        if (d < 0) {
-            set_error("boost_set_model: tree %d has depth %d", t, d);
-            return WDX_ERR_INVALID;
-        }
-        if (d > WDX_BOOST_MAX_DEPTH) {
-            set_error("boost_set_model: tree %d has depth %d (0..%d supported)", t, d, WDX_BOOST_MAX_DEPTH);
-            return WDX_ERR_UNSUPPORTED;
-        }
-        n_splits += (size_t)d;
-        n_leaves += (size_t)1 << d;
-    }
-    if (n_splits > 0x7fffffff) {
-        set_error("boost_set_model: too many splits");
-        return WDX_ERR_UNSUPPORTED;
-    }
-    if (n_splits && (!m->split_feature || !m->split_border)) {
-        set_error("boost_set_model: splits without features / borders");
-        return WDX_ERR_INVALID;
-    }
-    for (size_t i = 0; i < n_splits; ++i)
-        if (m->split_feature[i] < 0 || m->split_feature[i] >= F) {
-            set_error("boost_set_model: split %lld tests feature %d of %d", (long long)i, m->split_feature[i], F);
-            return WDX_ERR_INVALID;
-        }
-    // one device block: [doubles: leaves | bias | thresholds][trees][splits][int32: label map]
-    const size_t nd = n_leaves * dim + (size_t)dim + (m->thresholds ? (size_t)k : 0);
-    const size_t o_trees = nd * 8, o_splits = o_trees + (size_t)nt * sizeof(BoostTree);
-    const size_t o_labels = o_splits + n_splits * sizeof(BoostSplit);
-    const size_t bytes = o_labels + (m->label_map ? (size_t)k * 4 : 0);
-    std::vector<unsigned char> h;
-    try {
-        h.resize(bytes);
-    } catch (const std::bad_alloc &) {  // any number of trees is accepted: the staging copy can be refused by the host
-        set_error("boost_set_model: no host memory for a staging copy of %zu bytes", bytes);
-        return WDX_ERR_UNSUPPORTED;
-    }
-    double *hd = reinterpret_cast<double *>(h.data());
-    memcpy(hd, m->leaf_values, n_leaves * dim * 8);
-    memcpy(hd + n_leaves * dim, m->bias, (size_t)dim * 8);
-    if (m->thresholds) memcpy(hd + n_leaves * dim + dim, m->thresholds, (size_t)k * 8);
-    BoostTree *ht = reinterpret_cast<BoostTree *>(h.data() + o_trees);
-    BoostSplit *hs = reinterpret_cast<BoostSplit *>(h.data() + o_splits);
-    {
-        size_t s0 = 0, l0 = 0;
-        for (int t = 0; t < nt; ++t) {
-            ht[t] = BoostTree{(int32_t)s0, m->depth[t], (int64_t)l0};
-            s0 += (size_t)m->depth[t];
-            l0 += ((size_t)1 << m->depth[t]) * dim;
-        }
-    }
-    for (size_t i = 0; i < n_splits; ++i)
-        hs[i] = BoostSplit{(uint32_t)m->split_feature[i] | ((m->split_nan_true && m->split_nan_true[i]) ? 0x100u : 0u),
-                           m->split_border[i]};
-    if (m->label_map) memcpy(h.data() + o_labels, m->label_map, (size_t)k * 4);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((rc = use_stream(ctx, ctx->stream))) return rc;
-    WDX_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    WDX_HIP_TRY(hipDeviceSynchronize());  // no kernel on any stream may still be reading the previous model (as the MLP's)
-    // upload into a block of its own and swap only after it has succeeded: a failed allocation or copy keeps the previous model
-    Buffer nb;
-    if ((rc = nb.ensure(bytes))) return rc;
-    if (hipError_t e = hipMemcpy(nb.p, h.data(), bytes, hipMemcpyHostToDevice); e != hipSuccess) {
-        set_error("boost_set_model: hipMemcpy of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-        nb.release();
-        return WDX_ERR_HIP;
-    }
-    ctx->boost_buf.release();
-    ctx->boost_buf = nb;
-    const unsigned char *dev = (const unsigned char *)ctx->boost_buf.p;
-    BoostDev M{};
-    M.leaves = (const double *)dev;
-    M.bias = M.leaves + n_leaves * dim;
-    M.thresholds = m->thresholds ? M.bias + dim : nullptr;
-    M.trees = (const BoostTree *)(dev + o_trees);
-    M.splits = (const BoostSplit *)(dev + o_splits);
-    M.label_map = m->label_map ? (const int32_t *)(dev + o_labels) : nullptr;
-    M.scale = m->scale;
-    M.n_trees = nt;
-    M.n_features = F;
-    M.dim = dim;
-    M.k = k;
-    ctx->boost = M;  // (every pointer of the previous model is replaced here, in one step with its block above)
-    ctx->boost_set = true;
-    return WDX_SUCCESS;
+    BoostImage img;
+    if (ModelCheck c = check_boost(m); c || (c = pack_boost(m, &img))) return refused(c);
+    return install(ctx, ctx->boost, img, "boost_set_model", [&](Resident<BoostDev> &R) { R.dev = bind_boost(img, R.block.p); });
 }
 
 int wdx_boost_predict_dev(wdx_ctx *ctx, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
                           double *d_prob, int32_t *d_pred, double *d_conf, void *stream) {
     WDX_ENTER(ctx);
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->boost_set) {
+    if (!ctx->boost.set) {
         set_error("no boost model: call wdx_boost_set_model first");
         return WDX_ERR_NO_REFS;
     }
@@ -701,13 +444,13 @@ int wdx_boost_predict_dev(wdx_ctx *ctx, const double *d_fpt, const int32_t *d_st
         return WDX_ERR_INVALID;
     }
     if ((rc = use_stream(ctx, (hipStream_t)stream))) return rc;
-    return boost_tail(ctx, ctx->boost, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, (hipStream_t)stream);
+    return boost_tail(ctx, ctx->boost.dev, d_fpt, d_status, n, d_raw, d_prob, d_pred, d_conf, (hipStream_t)stream);
 }
 
 int wdx_boost_predict(wdx_ctx *ctx, const double *X, int64_t n, double *raw, double *prob, int32_t *pred, double *conf) {
     WDX_ENTER(ctx);
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->boost_set) {
+    if (!ctx->boost.set) {
         set_error("no boost model: call wdx_boost_set_model first");
         return WDX_ERR_NO_REFS;
     }
@@ -718,7 +461,7 @@ int wdx_boost_predict(wdx_ctx *ctx, const double *X, int64_t n, double *raw, dou
     if (n == 0) return WDX_SUCCESS;
     hipStream_t s = ctx->stream;
     if ((rc = use_stream(ctx, s))) return rc;
-    const BoostDev &M = ctx->boost;
+    const BoostDev &M = ctx->boost.dev;
     const int F = M.n_features, dim = M.dim, k = M.k;
     // rows per pass: the float64 rows of a chunk stay <= 1 GiB.  Workspaces: in0 rows | out0 raw | out1 prob | out2 pred | out3 conf
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)1 << 30) / (8 * F)));
@@ -732,7 +475,7 @@ int wdx_boost_predict(wdx_ctx *ctx, const double *X, int64_t n, double *raw, dou
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t c = std::min(chunk, n - r0);
         WDX_HIP_TRY(hipMemcpyAsync(ctx->in0.p, X + r0 * F, (size_t)(c * F) * 8, hipMemcpyHostToDevice, s));
-        if ((rc = boost_tail(ctx, ctx->boost, (const double *)ctx->in0.p, nullptr, c, (double *)ctx->out0.p, (double *)ctx->out1.p,
+        if ((rc = boost_tail(ctx, ctx->boost.dev, (const double *)ctx->in0.p, nullptr, c, (double *)ctx->out0.p, (double *)ctx->out1.p,
                              (int32_t *)ctx->out2.p, (double *)ctx->out3.p, s)))
             return rc;
         if (raw) WDX_HIP_TRY(hipMemcpyAsync(raw + r0 * dim, ctx->out0.p, (size_t)(c * dim) * 8, hipMemcpyDeviceToHost, s));

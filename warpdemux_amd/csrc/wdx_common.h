@@ -11,6 +11,7 @@
 #include "wdx_dtw_plan.h"
 #include "wdx_refine_optimal_plan.h"
 #include "wdx_work_layout.h"
+#include "wdx_model_image.h"
 
 namespace wdx {
 
@@ -251,13 +252,7 @@ int launch_synth_fill(uint64_t seed, int64_t first_read, int64_t n, int32_t n_ba
                       const int32_t *dwell_table, const float *lead, const float *bc,
                       const int64_t *off, float *sig, int32_t *barcode, hipStream_t stream);
 
-// ---- SVM tail (wdx_svm.hip) -----------------------------------------------------------------------
-struct SvmDev {  // device-resident SVC(kernel="precomputed", probability=True) + label map / thresholds
-    const int32_t *n_support, *support, *start, *label_map;
-    const double *dual_coef, *rho, *probA, *probB, *thresholds;  // label_map / thresholds nullable
-    int k, n_sv, n_train, pwr;
-    float ngamma;  // -gamma rounded to float32 (NumPy: python float * float32 array -> float32)
-};
+// ---- SVM tail (wdx_svm.hip; SvmDev, MlpDev, BoostDev and what they point to: wdx_model_image.h) ---
 int launch_svm_predict(const SvmDev &M, const float *d_dist, int64_t n, double *d_prob, int32_t *d_pred,
                        double *d_conf, hipStream_t stream, const Knobs &knobs);
 
@@ -268,15 +263,6 @@ int launch_svm_mask_failed(const int32_t *d_status, int64_t n, int k, double *d_
 
 // ---- MLP tail (wdx_mlp.hip) -----------------------------------------------------------------------
 constexpr int kMaxMlpWidth = 512;  // widest hidden layer (WDX_MLP_MAX_WIDTH)
-struct MlpDev {  // device-resident [StandardScaler]* + MLPClassifier + label map / thresholds
-    const void *coef[WDX_MLP_MAX_LAYERS], *bias[WDX_MLP_MAX_LAYERS];  // working dtype
-    const double *mean[WDX_MLP_MAX_SCALERS], *scale[WDX_MLP_MAX_SCALERS];  // nullable per step
-    const int32_t *label_map;  // nullable
-    const double *thresholds;  // nullable
-    int sizes[WDX_MLP_MAX_LAYERS + 1];
-    int n_layers, n_scalers, dtype_bytes, hidden_act, k;
-    int ld;  // row stride (elements) of the two LDS activation buffers
-};
 // d_status (nullable): rows with status != WDX_READ_OK get pred -1 and NaN, uncounted; d_n_nonfinite (nullable) is
 // INCREMENTED by the rows whose (scaled) input holds a NaN or an infinity
 int launch_mlp_predict(const MlpDev &M, const float *d_dist, int64_t n, const int32_t *d_status, double *d_prob,
@@ -284,24 +270,6 @@ int launch_mlp_predict(const MlpDev &M, const float *d_dist, int64_t n, const in
 
 // ---- boost tail (wdx_boost.hip) --------------------------------------------------------------------
 constexpr int kMaxBoostFeatures = WDX_BOOST_MAX_FEATURES;  // (the widest fingerprint the kernels write: kSegCap)
-struct BoostTree {   // 16 bytes, read through wave-uniform loads
-    int32_t split0;  // first split of the tree in `splits`
-    int32_t depth;
-    int64_t leaf0;   // first leaf value of the tree in `leaves`
-};
-struct BoostSplit {  // 8 bytes
-    uint32_t feat;   // bits 0..7 the feature, bit 8 the NaN rule (1: a NaN feature sets the bit)
-    float border;
-};
-struct BoostDev {  // device-resident oblivious-tree ensemble + label map / thresholds
-    const BoostTree *trees;
-    const BoostSplit *splits;
-    const double *leaves, *bias;
-    const int32_t *label_map;  // nullable
-    const double *thresholds;  // nullable
-    double scale;
-    int n_trees, n_features, dim, k;
-};
 // d_status (nullable): rows with status != WDX_READ_OK get pred -1 and NaN raw / prob / conf
 int launch_boost_predict(const BoostDev &M, const double *d_fpt, const int32_t *d_status, int64_t n, double *d_raw,
                          double *d_prob, int32_t *d_pred, double *d_conf, hipStream_t stream, const Knobs &knobs);

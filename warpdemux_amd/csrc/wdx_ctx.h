@@ -21,6 +21,20 @@ struct Buffer {  // grow-only device workspace
     void release();
 };
 
+// A classifier model resident on the device (wdx_classify.hip: install): ONE block that holds its image
+// (wdx_model_image.h) and the kernels' record bound to that block.  Block, record and flag change together, with the device
+// idle; gen counts the changes.
+template <class Dev>
+struct Resident {
+    Buffer block;
+    Dev dev{};
+    bool set = false;
+    int64_t gen = 0;
+};
+struct ResidentSvm : Resident<SvmDev> {
+    SvmFused fused{};  // the fused route's tables, in the same block
+};
+
 struct PinnedBuffer {  // grow-only page-locked host staging area
     void *p = nullptr;
     size_t bytes = 0;
@@ -56,7 +70,7 @@ struct wdx_ctx {
     wdx_dtw_launch_info dtw_last{};  // what the latest DTW dispatch launched (wdx_dtw_last_launch)
     wdx::Buffer refs_pad, refs_T, refs_nan;
     // host-buffer call workspaces
-    wdx::Buffer in0, in1, in2, in3, out0, out1, out2, out3, tmp0, tmp1, tmp2, scratch, fp_ws, svm_buf, ref_buf;
+    wdx::Buffer in0, in1, in2, in3, out0, out1, out2, out3, tmp0, tmp1, tmp2, scratch, fp_ws, ref_buf;
     wdx::Buffer ref_ws;  // refinement branch: the fast kernels' hand-over records (fingerprint_refine_ws_bytes)
     wdx::Buffer fp_big;  // score curves of adapter windows beyond the exact kernel's LDS capacity (fingerprint_big_bytes)
     // WDX_OPT_LONG_WINDOWS: slots of the long form (fingerprint_long_bytes: 12 MB), allocated by the first call that meets a
@@ -77,23 +91,14 @@ struct wdx_ctx {
     // kernels (wdx_dtw_plan.h: nearest_plan, at most kNearestBlockBytes); allocated by the first such call
     wdx::Buffer nearest_buf;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
-    wdx::SvmDev svm{};
-    bool svm_set = false;
-    // fused DTW + SVM path of wdx_demux_svm_dev: vector-major coefficients and the chunk tables (built with the model),
-    // the resident references gathered into support-vector order (rebuilt when the reference set or the model changes)
-    wdx::Buffer svm_fused, svm_refs;
-    const double *svm_coefT = nullptr;
-    const int32_t *svm_chunk_ref0 = nullptr, *svm_chunk_slot = nullptr;
-    int svm_chunks = 0, svm_halves = 0;
-    int64_t svm_refs_gen = -1, svm_model_gen = 0, svm_refs_model_gen = -1;
-    // MLP tail (wdx_mlp_set_model): its own slot, independent of the SVM's
-    wdx::Buffer mlp_buf;
-    wdx::MlpDev mlp{};
-    bool mlp_set = false;
-    // boost tail (wdx_boost_set_model): its own slot, independent of the SVM's and the MLP's
-    wdx::Buffer boost_buf;
-    wdx::BoostDev boost{};
-    bool boost_set = false;
+    // the classifier tails (wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model): a slot each, independent of one another
+    wdx::ResidentSvm svm;
+    wdx::Resident<wdx::MlpDev> mlp;
+    wdx::Resident<wdx::BoostDev> boost;
+    // fused DTW + SVM path of wdx_demux_svm_dev: the resident references gathered into support-vector order (rebuilt when
+    // the reference set or the model changes: refs_gen, svm.gen)
+    wdx::Buffer svm_refs;
+    int64_t svm_refs_gen = -1, svm_refs_model_gen = -1;
     wdx::Comm *comm = nullptr;
     // pipelined minibatches (wdx_demux_submit / wdx_demux_wait): up to WDX_MAX_SLOTS child contexts, each with its own stream and
     // workspaces, sharing this context's resident reference set; the fields below describe a child's batch in flight

@@ -187,15 +187,15 @@ struct Server {
         if (!(want & (WDX_WANT_BOOST | WDX_WANT_SVM))) return true;
         const int kc = R->n_classes, K = R->n_events;
         std::lock_guard<std::mutex> g(ctx->mu);
-        if ((want & WDX_WANT_BOOST) && ctx->boost_set && (ctx->boost.k != kc || ctx->boost.n_features != K)) {
-            set_error("feeder: the boost model has %d classes and %d features, the ring was laid out for %d and %d", ctx->boost.k,
-                      ctx->boost.n_features, kc, K);
+        if ((want & WDX_WANT_BOOST) && ctx->boost.set && (ctx->boost.dev.k != kc || ctx->boost.dev.n_features != K)) {
+            set_error("feeder: the boost model has %d classes and %d features, the ring was laid out for %d and %d", ctx->boost.dev.k,
+                      ctx->boost.dev.n_features, kc, K);
             return false;
         }
         // (the SVM's fingerprints are as long as the resident references; a ring without fingerprint regions has no length)
-        if ((want & WDX_WANT_SVM) && ctx->svm_set && (ctx->svm.k != kc || (K && ctx->refs.L && ctx->refs.L != K))) {
+        if ((want & WDX_WANT_SVM) && ctx->svm.set && (ctx->svm.dev.k != kc || (K && ctx->refs.L && ctx->refs.L != K))) {
             set_error("feeder: the SVM model has %d classes and %d-event fingerprints, the ring was laid out for %d and %d",
-                      ctx->svm.k, (int)ctx->refs.L, kc, K);
+                      ctx->svm.dev.k, (int)ctx->refs.L, kc, K);
             return false;
         }
         return true;

@@ -123,7 +123,7 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
         }
     }
     const int64_t nY = resident ? R.nY : 0;
-    if (tail == WDX_LIVE_TAIL_SVM && (!ctx->svm_set || ctx->svm.n_train != nY)) {
+    if (tail == WDX_LIVE_TAIL_SVM && (!ctx->svm.set || ctx->svm.dev.n_train != nY)) {
         set_error("live_tick: use_svm needs wdx_svm_set_model with a model trained on the resident reference set");
         return WDX_ERR_NO_REFS;
     }
@@ -221,8 +221,8 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
     h_off[n_reads] = adc ? dpos.next : pos.next;
 
     // ---- the output block -------------------------------------------------------------------------------------------
-    const int k = tail == WDX_LIVE_TAIL_SVM ? ctx->svm.k : tail == WDX_LIVE_TAIL_MLP ? ctx->mlp.k
-                : tail == WDX_LIVE_TAIL_BOOST ? ctx->boost.k : 0;
+    const int k = tail == WDX_LIVE_TAIL_SVM ? ctx->svm.dev.k : tail == WDX_LIVE_TAIL_MLP ? ctx->mlp.dev.k
+                : tail == WDX_LIVE_TAIL_BOOST ? ctx->boost.dev.k : 0;
     const bool run_dtw = nY > 0;
     // (a DTW tail without a single reference has nothing to read: as before, its outputs are left alone)
     const bool run_tail = tail == WDX_LIVE_TAIL_BOOST || (tail != WDX_LIVE_TAIL_NONE && run_dtw);
@@ -267,7 +267,7 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
                      (const int32_t *)(din + o_zero), (const int32_t *)(din + o_len), (const uint8_t *)(din + o_ok)};
     ChainTail ct;
     ct.kind = tail;
-    ct.svm = &ctx->svm, ct.mlp = &ctx->mlp, ct.boost = &ctx->boost;
+    ct.svm = &ctx->svm.dev, ct.mlp = &ctx->mlp.dev, ct.boost = &ctx->boost.dev;
     ChainOut co{FpOut{d_fpt, need[P_DWELL] ? (int64_t *)(dout + B.off[P_DWELL]) : nullptr,
                       need[P_STATS] ? (double *)(dout + B.off[P_STATS]) : nullptr, d_status}};
     co.dist = d_dist, co.call = d_call, co.prob = d_prob, co.pred = d_pred, co.conf = d_conf, co.n_nonfinite = d_cnt;

@@ -625,10 +625,10 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
         set_error("demux_submit: WDX_WANT_SVM and WDX_WANT_BOOST share prob / pred / conf: ask for one of them");
         return WDX_ERR_INVALID;
     }
-    const BoostDev boost = ctx->boost;   // (by value: the kernel's arguments are this model, whatever is set later)
+    const BoostDev boost = ctx->boost.dev;   // (by value: the kernel's arguments are this model, whatever is set later)
     ChainTail tail;
     tail.kind = want_svm ? WDX_LIVE_TAIL_SVM : want_boost ? WDX_LIVE_TAIL_BOOST : WDX_LIVE_TAIL_NONE;
-    tail.svm = want_svm ? &ctx->svm : nullptr;
+    tail.svm = want_svm ? &ctx->svm.dev : nullptr;
     tail.boost = want_boost ? &boost : nullptr;
     if ((rc = tail_ready(ctx, tail.kind, ctx->refs.nY, p->barcode_num_events, rp != nullptr, "demux_submit"))) return rc;
     wdx_ctx *S = nullptr;
@@ -646,7 +646,7 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
     const DtwRefs &R = no_refs ? none : ctx->refs;
     S->refs = R;  // device pointers of the parent's resident set (read-only; wdx_set_refs drains the slots)
     const int64_t K = p->barcode_num_events;
-    const int64_t k = want_svm ? ctx->svm.k : (want_boost ? ctx->boost.k : 0);
+    const int64_t k = want_svm ? ctx->svm.dev.k : (want_boost ? ctx->boost.dev.k : 0);
     const bool want_tail = want_svm || want_boost;
     // page-locked output block of the slot, 8-byte aligned pieces:
     // [fpt f64 n*K][dwell i64 n*K][stats f64 n*6][prob f64 n*k][conf f64 n][dist f32 n*nY][call i32 n][status i32 n][pred i32 n]
