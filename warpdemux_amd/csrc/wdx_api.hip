@@ -21,7 +21,7 @@ void set_error(const char *fmt, ...) {
 
 static thread_local int64_t g_slice_cap = 0;   // WDX_OPT_MAX_LAUNCH_SLICE of the call running on this thread (0 = none)
 
-int64_t launch_slice_limit(int64_t builtin) { return g_slice_cap > 0 && g_slice_cap < builtin ? g_slice_cap : builtin; }
+int64_t launch_slice_limit(int64_t builtin) { return fp_slice_limit(builtin, g_slice_cap); }
 LaunchSliceScope::LaunchSliceScope(int64_t cap) : saved(g_slice_cap) { g_slice_cap = cap; }
 LaunchSliceScope::~LaunchSliceScope() { g_slice_cap = saved; }
 

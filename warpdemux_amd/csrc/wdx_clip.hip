@@ -34,7 +34,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 // (one read = one wave = one workgroup: with four reads per workgroup a finished wave's registers and LDS waited for the slowest
 // of the four -- reads differ by their > 64-member levels -- and the kernel ran 45.1 instead of 38.9 ms per 10 M reads)
-constexpr int kClipWaves = 1;                       // reads per workgroup
+static_assert(kClipWaves == 1, "reads per workgroup: wdx_fp_plan.h sizes the grids by it");
 constexpr int kClipWaveWords = kHB;                 // histogram; the member list lies over its first 64 words (8 192 B)
 
 struct ClipArgs {
@@ -591,52 +591,33 @@ __global__ __launch_bounds__(1024) void route_long_windows_kernel(FpArgs A, int 
     big_list[base + at] = (int32_t)r;
 }
 
-int launch_route_long_windows(const FpArgs &A, int cap, unsigned *d_count, int32_t *d_list, hipStream_t stream) {
-    FpArgs R = A;
-    const int64_t n_wg = (A.n_reads + 1023) / 1024, max_slice = launch_slice_limit(1ll << 21);
-    for (int64_t base = 0; base < n_wg; base += max_slice) {
-        R.block_base = base * 1024;
-        hipLaunchKernelGGL(route_long_windows_kernel, dim3((unsigned)std::min<int64_t>(max_slice, n_wg - base)), dim3(1024), 0, stream,
-                           R, cap, d_count, d_list);
-    }
-    WDX_HIP_TRY(hipGetLastError());
-    return WDX_SUCCESS;
+// One step of a plan (wdx_fp_plan.h): the instantiation is the key's, the grid and its slices are the step's.
+// clip: 4096 .. 6144 samples ahead of the main kernel (the two long instantiations are reachable for the kernel's own tests);
+// clip-list: cap 6144 (the hand-overs of the main kernel), or the long-window lists ahead of clip_bounds_block_kernel: 8192 samples
+// at 128 registers per lane (three workgroups per CU), 13 312 at 208 (two; the register file ends at 256 per lane)
+static void (*clip_kernel_of(const FpKernelKey &k))(ClipArgs) {
+    if (!fp_key_exists(k)) return nullptr;
+    if (k.family == kFamClipList) return k.npl == 96 ? clip_bounds_list_kernel<96> : (k.npl == 128 ? clip_bounds_list_kernel<128> : clip_bounds_list_kernel<kClipWaveLongCap / 64>);
+    if (k.family != kFamClip) return nullptr;
+    return k.npl == 64 ? clip_bounds_kernel<64> : (k.npl == 80 ? clip_bounds_kernel<80> : (k.npl == 96 ? clip_bounds_kernel<96>
+           : (k.npl == 128 ? clip_bounds_kernel<128> : clip_bounds_kernel<kClipWaveLongCap / 64>)));
 }
-
-// cap 6144 (the hand-overs of the main kernel), or the long-window lists ahead of clip_bounds_block_kernel: 8192 samples at 128
-// registers per lane (three workgroups per CU), 13 312 at 208 (two; the register file ends at 256 per lane)
-int launch_clip_bounds_list(const FpArgs &A, ClipRec *d_rec, const unsigned *d_count, const int32_t *d_list, int64_t n_entries,
-                            hipStream_t stream, int cap, bool defer) {
-    if (n_entries <= 0) return WDX_SUCCESS;
-    if (cap != 6144 && cap != 8192 && cap != kClipWaveLongCap) {
-        set_error("clip_bounds_list_kernel: capacities are 6144, 8192 and 13312 samples");
+int launch_clip_step(const FpStep &s, const FpArgs &A, ClipRec *d_rec, unsigned *d_count, int32_t *d_list, int64_t max_launch_slice,
+                     hipStream_t stream) {
+    void (*const kclip)(ClipArgs) = clip_kernel_of(s.key);
+    if (!kclip && s.key.family != kFamRoute) {
+        set_error("clip kernels: capacities are 4096, 5120, 6144, 8192 and 13312 samples (lists: 6144, 8192, 13312)");
         return WDX_ERR_INVALID;
     }
-    void (*kclip)(ClipArgs) = cap == 6144 ? clip_bounds_list_kernel<96> : (cap == 8192 ? clip_bounds_list_kernel<128> : clip_bounds_list_kernel<kClipWaveLongCap / 64>);
-    ClipArgs CA{A, d_rec, cap, d_count, d_list, defer ? 1 : 0};
-    const int64_t n_wg = (n_entries + kClipWaves - 1) / kClipWaves, max_slice = launch_slice_limit(1ll << 22);
-    for (int64_t base = 0; base < n_wg; base += max_slice) {
-        CA.a.block_base = base * kClipWaves;
-        hipLaunchKernelGGL(kclip, dim3((unsigned)std::min<int64_t>(max_slice, n_wg - base)), dim3(kClipWaves * 64), 0, stream, CA);
-    }
-    WDX_HIP_TRY(hipGetLastError());
-    return WDX_SUCCESS;
-}
-
-int launch_clip_bounds(const FpArgs &A, ClipRec *d_rec, int cap, hipStream_t stream) {
-    if (cap > kClipWaveLongCap) {
-        set_error("clip_bounds_kernel takes windows of at most 13312 samples");
-        return WDX_ERR_INVALID;
-    }
-    // (the chain launches this form up to 6144 samples; beyond, the long-window lists take the list form -- the two long
-    // instantiations are reachable here for the kernel's own tests)
-    void (*kclip)(ClipArgs) = cap <= 4096 ? clip_bounds_kernel<64> : (cap <= 5120 ? clip_bounds_kernel<80> : (cap <= 6144 ? clip_bounds_kernel<96>
-                              : (cap <= 8192 ? clip_bounds_kernel<128> : clip_bounds_kernel<kClipWaveLongCap / 64>)));
-    ClipArgs CA{A, d_rec, cap, nullptr, nullptr, 0};
-    const int64_t n_wg = (A.n_reads + kClipWaves - 1) / kClipWaves, max_slice = launch_slice_limit(1ll << 22);
-    for (int64_t base = 0; base < n_wg; base += max_slice) {
-        CA.a.block_base = base * kClipWaves;
-        hipLaunchKernelGGL(kclip, dim3((unsigned)std::min<int64_t>(max_slice, n_wg - base)), dim3(kClipWaves * 64), 0, stream, CA);
+    ClipArgs CA{A, d_rec, s.capF, d_count, d_list, s.defer ? 1 : 0};
+    if (s.key.family == kFamClip) CA.in_count = nullptr, CA.in_list = nullptr;
+    const FpSlices S = fp_slices(s.extent, s.rule, s.slice_limit, max_launch_slice);
+    for (int64_t i = 0; i < S.count; ++i) {
+        CA.a.block_base = S.base(i) * s.per_wg;
+        if (s.key.family == kFamRoute)
+            hipLaunchKernelGGL(route_long_windows_kernel, dim3((unsigned)S.n(i)), dim3(s.wg), 0, stream, CA.a, s.capF, d_count, d_list);
+        else
+            hipLaunchKernelGGL(kclip, dim3((unsigned)S.n(i)), dim3(s.wg), 0, stream, CA);
     }
     WDX_HIP_TRY(hipGetLastError());
     return WDX_SUCCESS;
@@ -653,7 +634,11 @@ int launch_clip_bounds_selftest(const float *d_sig, const int64_t *d_row_off, in
     A.a_start = d_a_start;
     A.a_end = d_a_end;
     A.p = p;
-    return launch_clip_bounds(A, reinterpret_cast<ClipRec *>(d_rec), cap, stream);
+    if (cap > kClipWaveLongCap) {
+        set_error("clip_bounds_kernel takes windows of at most 13312 samples");
+        return WDX_ERR_INVALID;
+    }
+    return launch_clip_step(fp_clip_step(cap, n_reads), A, reinterpret_cast<ClipRec *>(d_rec), nullptr, nullptr, 0, stream);
 }
 
 }  // namespace wdx

@@ -12,6 +12,7 @@
 #include "wdx_refine_optimal_plan.h"
 #include "wdx_work_layout.h"
 #include "wdx_model_image.h"
+#include "wdx_fp_plan.h"
 
 namespace wdx {
 
@@ -61,12 +62,21 @@ struct Knobs {
     int64_t max_window(bool refine) const { return max_adapter_window(refine, long_windows, long_refine_windows); }
     // what the DTW dispatch rule reads of them (wdx_dtw_plan.h)
     DtwSwitches dtw_switches() const { return {no_wavefront, no_short_dtw, wide_dtw}; }
+    // ... and the fingerprint plan (wdx_fp_plan.h)
+    FpSwitches fp_switches() const {
+        FpSwitches s;
+        s.exact_path = exact_path, s.fast_peak_cap = fast_peak_cap, s.fast_main_cap = fast_main_cap, s.fast_chain_min = fast_chain_min;
+        s.fast_exact_scores = fast_exact_scores, s.no_clip_reuse = no_clip_reuse, s.no_wave_clip_long = no_wave_clip_long;
+        s.no_peak_filter = no_peak_filter, s.no_split = no_split, s.max_launch_slice = max_launch_slice;
+        s.long_windows = long_windows, s.long_refine_windows = long_refine_windows, s.refine_optimal = refine_optimal;
+        return s;
+    }
 };
 
 // A launch over more workgroups than grid.x admits is cut into slices (block_base != 0 from the second on).  The built-in
 // slice sizes are millions of workgroups; WDX_OPT_MAX_LAUNCH_SLICE lowers them for the calling thread while one
 // launch_fingerprint runs, so that the tests walk the multi-slice paths on batches the oracle finishes in seconds.
-int64_t launch_slice_limit(int64_t builtin);
+int64_t launch_slice_limit(int64_t builtin);   // fp_slice_limit (wdx_fp_plan.h) of the calling thread's WDX_OPT_MAX_LAUNCH_SLICE
 struct LaunchSliceScope {
     explicit LaunchSliceScope(int64_t cap);
     ~LaunchSliceScope();
@@ -87,6 +97,11 @@ struct LdsAttr {
         return WDX_SUCCESS;
     }
 };
+template <auto K>   // the one LdsAttr of kernel K
+inline LdsAttr &lds_attr_of() {
+    static LdsAttr attr;
+    return attr;
+}
 
 // ---- DTW (wdx_dtw.hip) -----------------------------------------------------------------------
 struct DtwRefs {  // resident reference set, both layouts (see DESIGN.md "DTW data layout")

@@ -34,24 +34,10 @@
 
 namespace wdx {
 
-constexpr int kMaxW = 64;        // cap on running_stat_width
+// kMaxW, kMaxEvents, kSegCap, the exact kernel's capacities (kExactLdsCap, kBigCap, kLongCap), their slot counts and the LDS
+// formulae (fp_lds_bytes, ...): wdx_fp_plan.h, where the host's plan reads the same ones.
 constexpr int kTile = 512;       // t-score tile, positions
-constexpr int kMaxEvents = 253;  // cap on num_events (E + 2 boundaries <= 255)
-constexpr int kSegCap = kMaxEvents + 1;
-// Exact kernel: windows up to kExactLdsCap samples keep their float64 score curve in LDS (12-13 B per sample of the
-// 160 KB); longer ones (up to WDX_MAX_ADAPTER_SAMPLES = kBigCap; the reference's RNA002 config allows
-// max_obs_trace + 2*padding = 15 200, DEPRECATED/config_files/rna002_70bps@v0.4.4.toml:2) run the SAME code with
-// the score curve in a per-workgroup HBM slot (L2-resident: 128 KB per slot) -- fingerprint_big_kernel.
-constexpr int kExactLdsCap = 11200;
-constexpr int kBigCap = WDX_MAX_ADAPTER_SAMPLES;
-constexpr int kBigSlots = 256;  // one workgroup per CU (97 KB of LDS each)
-static_assert(kBigCap % 64 == 0 && kBigCap >= 15200, "the exact path must take every window the reference accepts");
-// WDX_OPT_LONG_WINDOWS: windows of kBigCap+1 .. kLongCap samples run the SAME code once more with the clipped float32
-// samples in the workgroup's HBM slot too (fingerprint_long_kernel): beside the fixed tables LDS holds the peak-state
-// bytes only (64 KB of the 160 KB).  A slot is 65 536 x (8 + 4) B = 768 KB; kLongSlots of them are 12 MB per context,
-// allocated at the first call that sees such a window with the option on (fingerprint_long_bytes).
-constexpr int kLongCap = WDX_MAX_LONG_ADAPTER_SAMPLES;
-constexpr int kLongSlots = 16;
+static_assert(kTile == kExactTile, "the LDS formulae: wdx_fp_plan.h");
 constexpr size_t kLongSlotBytes = (size_t)kLongCap * (8 + 4);
 // positions fit 16 bits (the peak list's uint16 entries hold positions < ns < kLongCap); one thread's chunk of the state
 // bytes fits a 64-bit mask at 1024 threads
@@ -70,6 +56,7 @@ struct alignas(8) FpShared {
     double mean, sd;
     double stat[6];
 };
+static_assert(sizeof(FpShared) == kFpSharedBytes, "the LDS formulae: wdx_fp_plan.h");
 
 // ---- block primitives ----------------------------------------------------------------------------
 
@@ -1656,8 +1643,8 @@ __global__ __launch_bounds__(BLOCK) void fingerprint_refine_tail_kernel(FpArgs A
 }
 
 #ifndef WDX_DEV_KERNELS_ONLY  // (development: a TU that instantiates single kernels includes this file with the macro set)
-// fn(base, n) over n_items in slices of at most launch_slice_limit(builtin): FULL slices and a remainder (the fast kernels'
-// launch_sliced cuts equal slices instead); stops at fn's first error
+// fn(base, n) over n_items in slices of at most launch_slice_limit(builtin), full slices and a remainder (fp_slices' kFullSlices:
+// wdx_fp_plan.h); stops at fn's first error
 template <class Fn>
 static int for_each_slice(int64_t n_items, int64_t builtin, Fn fn) {
     const int64_t slice = launch_slice_limit(builtin);
@@ -1689,86 +1676,46 @@ int64_t fingerprint_refine_ws_bytes(int64_t n_reads) { return (int64_t)sizeof(Re
 #include "wdx_fingerprint_split.inc"
 #ifndef WDX_DEV_KERNELS_ONLY
 
-static size_t fp_lds_bytes(int cap) {
-    size_t b = 0;
-    b += (size_t)cap * 8;                   // scores
-    b += (size_t)(kTile + kMaxW) * 8 * 2;   // Mt, Vt (+ state when it fits)
-    b += (size_t)kSegCap * 8 * 3;           // ev, zz, tmp
-    b += sizeof(FpShared);
-    b += (size_t)cap * 4;                   // sig
-    b += (size_t)256 * 4;                   // hist
-    b += (size_t)(kSegCap + 1) * 4;         // cpts
-    if (cap > (int)((kTile + kMaxW) * 16)) b += (size_t)cap;  // dedicated state
-    return (b + 15) & ~(size_t)15;
-}
-
-static size_t fp_lds_bytes_big(int cap) { return fp_lds_bytes(cap) - (size_t)cap * 8; }  // no score curve in LDS
-
 int64_t fingerprint_big_bytes(int64_t max_len) {
     return max_len > kExactLdsCap ? (int64_t)kBigSlots * kBigCap * 8 : 0;
 }
-
-// the long form keeps no samples and no score curve in LDS, and always the dedicated state bytes
-static size_t fp_lds_bytes_long() { return fp_lds_bytes(kLongCap) - (size_t)kLongCap * (8 + 4); }
-static_assert(kLongCap > (kTile + kMaxW) * 16, "fp_lds_bytes counts the dedicated state bytes");
-
 int64_t fingerprint_long_bytes(int64_t max_len) { return max_len > kBigCap ? (int64_t)(kLongSlots * kLongSlotBytes) : 0; }
 
-static int launch_fp_long(FpArgs A, void *d_long, const unsigned *count, const int32_t *list, hipStream_t stream) {
-    static LdsAttr attr;
-    const size_t lds = fp_lds_bytes_long();
-    if (!A.rf.query)
-        if (int rc = attr.ensure(fingerprint_long_kernel<1024>, lds)) return rc;
-    A.cap = kLongCap;
-    A.defer_big = 0;
-    A.big_scores = reinterpret_cast<double *>(d_long);
-    A.clip = nullptr;
-    A.refine_record = 0;
-    const int64_t grid = A.n_reads < kLongSlots ? A.n_reads : kLongSlots;
-    if (A.rf.query) return launch_fp_long_refine(A, count, list, grid, lds, stream);   // (wdx_fingerprint_long.hip)
-    hipLaunchKernelGGL((fingerprint_long_kernel<1024>), dim3((unsigned)grid), dim3(1024), lds, stream, A, count, list);
+// One step of the exact families (fingerprint_kernel, _list_kernel, _big_kernel, _long_kernel): the plan's grid, workgroup, LDS
+// bytes and slices; `extra` is what the kernel takes behind its FpArgs.
+template <auto K, class... Extra>
+static int launch_exact(const FpStep &s, FpArgs A, int64_t max_launch_slice, hipStream_t stream, int64_t *n_launches, Extra... extra) {
+    if (int rc = lds_attr_of<K>().ensure(K, s.lds)) return rc;
+    const FpSlices S = fp_slices(s.extent, s.rule, s.slice_limit, max_launch_slice);
+    for (int64_t i = 0; i < S.count; ++i) {
+        A.block_base = S.base(i);
+        hipLaunchKernelGGL(K, dim3((unsigned)S.n(i)), dim3(s.wg), s.lds, stream, A, extra...);
+        if (s.counted && n_launches) ++*n_launches;
+    }
     WDX_HIP_TRY(hipGetLastError());
     return WDX_SUCCESS;
 }
-
-static int launch_fp_big(FpArgs A, int small_cap, const unsigned *count, const int32_t *list, hipStream_t stream) {
-    static LdsAttr attr;
-    const size_t lds = fp_lds_bytes_big(kBigCap);
-    if (int rc = attr.ensure(fingerprint_big_kernel<1024>, lds)) return rc;
-    A.cap = kBigCap;
-    A.defer_big = 0;
-    const int64_t grid = A.n_reads < kBigSlots ? A.n_reads : kBigSlots;
-    hipLaunchKernelGGL((fingerprint_big_kernel<1024>), dim3((unsigned)grid), dim3(1024), lds, stream, A, count, list,
-                       small_cap);
-    WDX_HIP_TRY(hipGetLastError());
-    return WDX_SUCCESS;
-}
-
-template <int BLOCK, bool PROF>
-static int launch_fp_chunks(FpArgs A, size_t lds, hipStream_t stream, int64_t *n_launches) {
-    static LdsAttr attr;
-    if (int rc = attr.ensure(fingerprint_kernel<BLOCK, PROF>, lds)) return rc;
-    // HIP drops work when grid.x * block.x reaches 2^32: launch in slices of 2^21 reads
-    (void)for_each_slice(A.n_reads, 1 << 21, [&](int64_t base, int64_t n) {
-        A.block_base = base;
-        hipLaunchKernelGGL((fingerprint_kernel<BLOCK, PROF>), dim3((unsigned)n), dim3(BLOCK), lds, stream, A);
-        if (n_launches) ++*n_launches;
-        return (int)WDX_SUCCESS;
-    });
-    WDX_HIP_TRY(hipGetLastError());
-    return WDX_SUCCESS;
-}
-
-template <int BLOCK>
-static int launch_fp_list(const FpArgs &A, size_t lds, const unsigned *count, const int32_t *list,
-                          hipStream_t stream, int max_grid = 2048) {
-    static LdsAttr attr;
-    if (int rc = attr.ensure(fingerprint_list_kernel<BLOCK>, lds)) return rc;
-    const int64_t grid = A.n_reads < max_grid ? A.n_reads : max_grid;
-    hipLaunchKernelGGL((fingerprint_list_kernel<BLOCK>), dim3((unsigned)grid), dim3(BLOCK), lds, stream,
-                       A, count, list);
-    WDX_HIP_TRY(hipGetLastError());
-    return WDX_SUCCESS;
+// the big and long forms of the exact kernel: a fixed grid of slots strides over the list (or over all reads)
+static int launch_big_long_step(const FpStep &s, FpArgs A, const unsigned *count, const int32_t *list, void *d_long, hipStream_t stream) {
+    switch (s.key.family) {
+        case kFamLong:
+            A.cap = kLongCap;
+            A.defer_big = 0;
+            A.big_scores = reinterpret_cast<double *>(d_long);
+            A.clip = nullptr;
+            A.refine_record = 0;
+            if (A.rf.query) return launch_fp_long_refine(A, count, list, s.extent, s.lds, stream);   // (wdx_fingerprint_long.hip)
+            return launch_exact<fingerprint_long_kernel<1024>>(s, A, 0, stream, nullptr, count, list);
+        case kFamBig: {
+            const int small_cap = A.cap;   // (the windows the launches before this one took)
+            A.cap = kBigCap;
+            A.defer_big = 0;
+            return launch_exact<fingerprint_big_kernel<1024>>(s, A, 0, stream, nullptr, count, list, small_cap);
+        }
+        default:
+            set_error("launch_big_long_step: not the big or the long form");
+            return WDX_ERR_INVALID;
+    }
 }
 
 int fill_refine_dev(const wdx_refine_params &rp, const double *d_query, int32_t *d_idx, RefineDev **out) {

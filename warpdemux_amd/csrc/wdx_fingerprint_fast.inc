@@ -20,26 +20,20 @@
 //   * event means: when every partial sum of the float32 samples is exactly representable in float64
 //     (checked from the clip bounds) summation order is irrelevant -> chunked partial sums + LDS atomics
 
-// Workgroup shape.  Two equivalent configurations were measured in round 1 (DESIGN.md 4.1): 256 threads x 4 score
-// positions per lane and 512 threads x 2 -- the same VALU instruction count and the same throughput; 256 threads
-// keep one wave of a workgroup on each SIMD.
-constexpr int FB = 256;          // threads per workgroup
+// Workgroup shape, capacities and the LDS carve-up's formulae (FB, kFW, kFSeg, kNpt*, kCapPMax, fast_sh_offset, ...): wdx_fp_plan.h,
+// where the host's plan reads the same ones.
+constexpr int FB = kFastBlock;   // threads per workgroup
+#ifndef WDX_WIDE_WG
+#define WDX_WIDE_WG 5
+#endif
+static_assert(kWideWgPerCu == WDX_WIDE_WG, "the plan's capacities assume this budget: wdx_fp_plan.h");
 constexpr int kWaves = FB / 64;
-constexpr int kFW = 12;          // the default window width (RNA004); instantiations exist for 12, 18 and 30 (fast_body)
 constexpr int kR = 6;             // consecutive score positions per lane in the t-score tile
 constexpr int kMaxPk = kR / 2;   // strict local maxima a lane can hold (they are >= 2 apart)
 // (per instantiation, in fast_body: kShiftW = FW / kR lanes between a window and the one FW samples further, kOwnW =
 // 63 - 2 kShiftW owned lanes per wave, kTSW = kWaves * kOwnW * kR score positions per tile)
-constexpr int kFSeg = 128;       // max segments (num_events + 1)
-#ifndef WDX_WIDE_WG
-#define WDX_WIDE_WG 5
-#endif
-constexpr int kWideWgPerCu = WDX_WIDE_WG;   // EXT main kernels of the NBT = 2 widths (6144 samples): workgroups per CU the registers are budgeted for
-constexpr int kCapPMax = 2048;   // largest peak-list capacity
 constexpr int kRounds = kCapPMax / (4 * FB) > 0 ? kCapPMax / (4 * FB) : 1;  // 4-peak ownership rounds
 constexpr int kNB = 4;           // neighbours per side inspected by the suppression, per neighbour thread (x NBT)
-// samples per thread of the instantiations (4096 / 5120: five workgroups per CU, 6144: four, 8192: three)
-constexpr int kNptSmall = 4096 / FB, kNptMid = 5120 / FB, kNptLarge = 6144 / FB, kNptHuge = 8192 / FB;
 static_assert(kFW % kR == 0 && kR == 6, "tile geometry");
 
 constexpr int kReach = 2;        // lanes ahead whose scores a plateau walk holds in registers (further ones: by shuffle)
@@ -79,20 +73,6 @@ static_assert(2 * 12 + 12 / 3 + 25 == 53 && 2 * 18 + 18 / 3 + 25 == 67 && 2 * 30
 constexpr double kPeakTauLo = 2.5, kPeakTauHi = 6.0;
 constexpr int kTopBits = 9;       // radix digit of the top-E select over the kept peaks' float64 scores
 constexpr int kTopKHistBytes = ((1 << kTopBits) + 64) * 4;  // its histogram (+ one trash bin per lane)
-__host__ __device__ constexpr size_t fast_sh_offset(int capF, int capP, int nbt = 1) {
-    // sig | pad | pk_score capP | pad | pk_pos pad|capP|pad | pk_state pad|capP|pad, rounded up to 16; pad = 4 * nbt
-    // entries either side (nbt = neighbour THREADS per side the suppression looks at: 1 for d_eff <= 9, 2 up to 17)
-    return (((size_t)(capF + 32) * 4 + (size_t)(capP + 8 * nbt) * 8 + (size_t)(capP + 8 * nbt) * 2 +
-             (size_t)(capP + 8 * nbt)) + 15) & ~(size_t)15;
-}
-
-constexpr int kStreamBuf = 6 * FB;  // STREAM: samples per tile buffer (six per thread and tile)
-__host__ __device__ constexpr size_t fast_stream_sh_offset(int capP, int nbt = 1) {
-    // two tile buffers | pad | pk_score capP | pad | pk_pos | pk_state (as fast_sh_offset)
-    return (((size_t)2 * kStreamBuf * 4 + (size_t)(capP + 8 * nbt) * 8 + (size_t)(capP + 8 * nbt) * 2 + (size_t)(capP + 8 * nbt)) +
-            15) & ~(size_t)15;
-}
-
 struct FastArgs {
     FpArgs a;
     int capF;              // adapter samples the LDS carve-up holds (multiple of 64)
@@ -131,7 +111,6 @@ struct SplitHdr {
 constexpr int kSplitMax = 256;
 constexpr int kSplitCutHi = 1 << 16;   // the entries were cut at kPeakTauHi (else: the whole list, cut at kPeakTauLo)
 constexpr size_t kSplitRecBytes = 16 + (size_t)kSplitMax * 18;
-constexpr int64_t kSplitSlice = 524288;   // reads per tile-kernel / tail-kernel launch pair (2.4 GB of lists; a pair boundary costs ~25 us: 131 072 -> 100.4, 262 144 -> 99.1, 1 M -> 98.1 ms of main pair per 10 M reads)
 
 struct alignas(8) FastShared {
     // cross-wave exchange slots, double-buffered by call parity so that every block-wide
@@ -145,6 +124,7 @@ struct alignas(8) FastShared {
     double mean, sd;
     double stat[6];
 };
+static_assert(sizeof(FastShared) == kFastSharedBytes, "the LDS formulae: wdx_fp_plan.h");
 
 // Block-wide exchange with one barrier per call: calls alternate between two slot sets, so a wave
 // that races ahead into call k+2 cannot overwrite what a slower wave still reads in call k
@@ -2698,7 +2678,6 @@ __global__ __launch_bounds__(FB, (NPT <= kNptMid ? 5 : 4) * FB / 256) void finge
 // Windows of 8193 .. 16384 samples (the reference's RNA002 config admits 15 200): the streaming form of the body, one
 // workgroup per entry of a device-side list (entries beyond the list's end leave at once).  Ahead of it
 // clip_bounds_block_kernel (below) writes the list entries' clip records.
-constexpr int kNptStream = 16384 / FB;
 template <int FW = kFW, int NBT = 1>
 __global__ __launch_bounds__(FB, 4 * FB / 256) void fingerprint_fast_stream_kernel(FastArgs F) {
     const int64_t k = F.a.block_base + blockIdx.x;
@@ -2706,33 +2685,7 @@ __global__ __launch_bounds__(FB, 4 * FB / 256) void fingerprint_fast_stream_kern
     fast_body<kNptStream, false, FW, NBT, true, true>(F, (int64_t)F.in_list[k]);
 }
 
-// The kernels of one (width, NBT) combination (main, 6144-sample list, striding 8192-sample list, streaming, and the split
-// forms where they exist), as the launch chain uses them (wdx_fingerprint_launch.inc).  The widths on exact scores only are
-// instantiated in translation units of their own (wdx_fingerprint_w1.hip,
-// _w2.hip: the build compiles them side by side -- one unit with every width took seven minutes).
-struct FastKernelSet {
-    void (*main)(FastArgs);
-    void (*l1)(FastArgs);
-    void (*ls)(FastArgs);
-    void (*st)(FastArgs);
-    void (*tile)(FastArgs) = nullptr;   // the split pair of the main launch: tile kernel ...
-    void (*tail)(FastArgs) = nullptr;   // ... and tail kernel (one wave per read)
-    void (*l1s)(FastArgs) = nullptr;    // the tile kernel of the 6144-sample list launch (its tail kernel is `tail`)
-};
-// (exact-scores-only widths: no retry launch and capF = 6144, so the one-workgroup-per-entry list kernel is never launched
-// for them: l1 stays null; odd widths do without the streaming form too -- windows beyond 8192 samples take the exact kernel)
-template <int FWx, bool WITH_STREAM = true>
-inline void fill_wide_set(bool ext, FastKernelSet &k) {
-    k.main = ext ? fingerprint_fast_kernel<kNptLarge, false, FWx, 2, true> : fingerprint_fast_kernel<kNptLarge, false, FWx, 2, false>;
-    k.l1 = nullptr;
-    k.ls = fingerprint_fast_list_kernel<kNptHuge, FWx, 2>;
-    if constexpr (WITH_STREAM) k.st = fingerprint_fast_stream_kernel<FWx, 2>;
-    else k.st = nullptr;
-}
-bool exact_only_kernels_a(int fw, bool ext, FastKernelSet &k);   // widths 8, 10, 14, 16, 20      (wdx_fingerprint_w1.hip)
-bool exact_only_kernels_b(int fw, bool ext, FastKernelSet &k);   // widths 22, 26, 28, 32, 34     (wdx_fingerprint_w2.hip)
-bool exact_only_kernels_c(int fw, bool ext, FastKernelSet &k);   // odd widths 7 .. 19            (wdx_fingerprint_w3.hip)
-bool exact_only_kernels_d(int fw, bool ext, FastKernelSet &k);   // odd widths 21 .. 35           (wdx_fingerprint_w4.hip)
+// (from a kernel key to these instantiations: resolve_fast_width, behind the split tail kernel in wdx_fingerprint_split.inc)
 
 // A1 for long windows (up to 16384 samples), one WORKGROUP per list entry with the samples in LDS: the radix selects of
 // the non-EXT fast kernels (fast_median_lds) as a kernel of their own -- clip_bounds_kernel's one-wave form would need
@@ -2829,13 +2782,3 @@ __global__ __launch_bounds__(FB) void clip_bounds_block_kernel(ClipBlockArgs C) 
     if (tid == 0) C.rec[r] = out;
 }
 #endif  // WDX_EXTRA_TU
-static size_t clip_block_lds_bytes(int cap) {
-    return (((size_t)(cap + 32) * 4 + (size_t)(kHB + 64) * 4 + sizeof(FastShared)) + 15) & ~(size_t)15;
-}
-
-static size_t fast_stream_lds_bytes(int capP, int nbt = 1) {
-    return (fast_stream_sh_offset(capP, nbt) + sizeof(FastShared) + 15) & ~(size_t)15;
-}
-static size_t fast_lds_bytes(int capF, int capP, int nbt = 1) {
-    return (fast_sh_offset(capF, capP, nbt) + sizeof(FastShared) + 15) & ~(size_t)15;
-}

@@ -18,7 +18,7 @@
 //   list)
 // (one wave per workgroup: a finished wave's slot and LDS go to the next read at once -- with four reads per workgroup they
 // waited for the slowest of the four: main pair 96.2 -> 95.4 ms per 10 M reads)
-constexpr int kSplitWaves = 1;
+// (kSplitWaves = 1: wdx_fp_plan.h, where the plan sizes the tail kernel's grid by it)
 struct alignas(8) SplitWaveLds {
     int cpts[kFSeg + 4];
     double pb[kFSeg + 2];   // P at the boundaries
@@ -440,3 +440,66 @@ __global__ __launch_bounds__(kSplitWaves * 64) void fingerprint_split_tail_kerne
         pp[14] = 1;
     }
 }
+
+// ---- from a key to its kernel ------------------------------------------------------------------------------------------
+// A kernel of the fast families and the LdsAttr that belongs to it: one static per instantiation.
+using FastKernel = void (*)(FastArgs);
+struct FpKernel {
+    FastKernel fn = nullptr;   // null: not built (fp_key_exists says which are)
+    LdsAttr *attr = nullptr;
+};
+template <auto K>
+inline FpKernel fp_kernel() {
+    return {K, &lds_attr_of<K>()};
+}
+// The kernels of one (width, NBT) pair, as fp_key_exists (wdx_fp_plan.h) lists them: what a pair has follows from its class
+// there, and nothing is instantiated here that the table does not name.  The exact-scores-only widths (kWide, kWideOdd) are
+// resolved in translation units of their own (wdx_fingerprint_w1.hip .. _w4.hip: the build compiles them side by side -- one
+// unit with every width took seven minutes).
+template <int FW, int NBT>
+inline FpKernel resolve_fast_width(const FpKernelKey &k) {
+    constexpr FpWidthClass WC = fp_width_class(FW, NBT);
+    static_assert(WC != kNoWidth, "fp_width_class: wdx_fp_plan.h");
+    if (k.fw != FW || k.nbt != NBT || !fp_key_exists(k)) return {};
+    const bool main = k.family == kFamFastMain;
+    if constexpr (WC != kFull) {
+        // (exact-scores-only widths: no retry launch and capF = 6144, so the one-workgroup-per-entry list kernel is never launched
+        // for them; odd widths do without the streaming form too -- windows beyond 8192 samples take the exact kernel)
+        if (main) return k.ext ? fp_kernel<fingerprint_fast_kernel<kNptLarge, false, FW, 2, true>>() : fp_kernel<fingerprint_fast_kernel<kNptLarge, false, FW, 2, false>>();
+        if (k.family == kFamListStride) return fp_kernel<fingerprint_fast_list_kernel<kNptHuge, FW, 2>>();
+        if constexpr (WC == kWide) {
+            if (k.family == kFamStream) return fp_kernel<fingerprint_fast_stream_kernel<FW, 2>>();
+        }
+        return {};
+    } else {
+        if (k.family == kFamList1 && !k.split) return fp_kernel<fingerprint_fast_list1_kernel<kNptLarge, FW, NBT>>();   // 6144 samples, one workgroup per entry
+        if (k.family == kFamListStride) return fp_kernel<fingerprint_fast_list_kernel<kNptHuge, FW, NBT>>();       // 8192 samples, striding
+        if (k.family == kFamStream) return fp_kernel<fingerprint_fast_stream_kernel<FW, NBT>>();
+        if constexpr (NBT == 2) {
+            if (main && !k.split) return k.ext ? fp_kernel<fingerprint_fast_kernel<kNptLarge, false, FW, 2, true>>() : fp_kernel<fingerprint_fast_kernel<kNptLarge, false, FW, 2, false>>();
+            if constexpr (fp_has_split(FW, 2)) {
+                if (main) return fp_kernel<fingerprint_fast_kernel<kNptLarge, false, FW, 2, true, true>>();
+                if (k.family == kFamSplitTail) return fp_kernel<fingerprint_split_tail_kernel<FW, 2>>();
+            }
+        } else {
+            if (main && k.npt == kNptMid && !k.prof)   // (always EXT)
+                return !k.split ? fp_kernel<fingerprint_fast_kernel<kNptMid, false, FW, 1, true>>() : fp_kernel<fingerprint_fast_kernel<kNptMid, false, FW, 1, true, true>>();
+            if (k.family == kFamSplitTail) return fp_kernel<fingerprint_split_tail_kernel<FW, 1>>();
+            if (k.family == kFamList1) return fp_kernel<fingerprint_fast_list1_kernel<kNptLarge, FW, 1, true>>();
+            if constexpr (fp_has_prof(FW, 1)) {
+                if (main && k.npt == kNptMid)   // (the tile kernel's diagnostic build: wdx_fingerprint_profile_dev's fast_path = 2)
+                    return !k.split ? fp_kernel<fingerprint_fast_kernel<kNptMid, true, FW, 1, true>>() : fp_kernel<fingerprint_fast_kernel<kNptMid, true, FW, 1, true, true>>();
+                if (main && k.npt == kNptSmall)
+                    return k.ext ? (k.prof ? fp_kernel<fingerprint_fast_kernel<kNptSmall, true, FW, 1, true>>() : fp_kernel<fingerprint_fast_kernel<kNptSmall, false, FW, 1, true>>())
+                                 : (k.prof ? fp_kernel<fingerprint_fast_kernel<kNptSmall, true, FW, 1, false>>() : fp_kernel<fingerprint_fast_kernel<kNptSmall, false, FW, 1, false>>());
+                if (main && k.prof) return k.ext ? fp_kernel<fingerprint_fast_kernel<kNptLarge, true, FW, 1, true>>() : fp_kernel<fingerprint_fast_kernel<kNptLarge, true, FW, 1, false>>();
+            }
+            if (main) return k.ext ? fp_kernel<fingerprint_fast_kernel<kNptLarge, false, FW, 1, true>>() : fp_kernel<fingerprint_fast_kernel<kNptLarge, false, FW, 1, false>>();
+        }
+        return {};
+    }
+}
+FpKernel resolve_fast_w1(const FpKernelKey &k);   // widths 8, 10, 14, 16, 20      (wdx_fingerprint_w1.hip)
+FpKernel resolve_fast_w2(const FpKernelKey &k);   // widths 22, 26, 28, 32, 34     (wdx_fingerprint_w2.hip)
+FpKernel resolve_fast_w3(const FpKernelKey &k);   // odd widths 7 .. 19            (wdx_fingerprint_w3.hip)
+FpKernel resolve_fast_w4(const FpKernelKey &k);   // odd widths 21 .. 35           (wdx_fingerprint_w4.hip)

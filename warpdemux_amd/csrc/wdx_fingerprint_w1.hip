@@ -7,14 +7,14 @@
 
 namespace wdx {
 
-bool exact_only_kernels_a(int fw, bool ext, FastKernelSet &k) {
-    switch (fw) {
-        case 8: fill_wide_set<8>(ext, k); return true;
-        case 10: fill_wide_set<10>(ext, k); return true;
-        case 14: fill_wide_set<14>(ext, k); return true;
-        case 16: fill_wide_set<16>(ext, k); return true;
-        case 20: fill_wide_set<20>(ext, k); return true;
-        default: return false;
+FpKernel resolve_fast_w1(const FpKernelKey &k) {
+    switch (k.fw) {
+        case 8: return resolve_fast_width<8, 2>(k);
+        case 10: return resolve_fast_width<10, 2>(k);
+        case 14: return resolve_fast_width<14, 2>(k);
+        case 16: return resolve_fast_width<16, 2>(k);
+        case 20: return resolve_fast_width<20, 2>(k);
+        default: return {};
     }
 }
 

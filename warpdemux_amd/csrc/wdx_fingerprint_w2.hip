@@ -7,14 +7,14 @@
 
 namespace wdx {
 
-bool exact_only_kernels_b(int fw, bool ext, FastKernelSet &k) {
-    switch (fw) {
-        case 22: fill_wide_set<22>(ext, k); return true;
-        case 26: fill_wide_set<26>(ext, k); return true;
-        case 28: fill_wide_set<28>(ext, k); return true;
-        case 32: fill_wide_set<32>(ext, k); return true;
-        case 34: fill_wide_set<34>(ext, k); return true;
-        default: return false;
+FpKernel resolve_fast_w2(const FpKernelKey &k) {
+    switch (k.fw) {
+        case 22: return resolve_fast_width<22, 2>(k);
+        case 26: return resolve_fast_width<26, 2>(k);
+        case 28: return resolve_fast_width<28, 2>(k);
+        case 32: return resolve_fast_width<32, 2>(k);
+        case 34: return resolve_fast_width<34, 2>(k);
+        default: return {};
     }
 }
 

@@ -7,16 +7,16 @@
 
 namespace wdx {
 
-bool exact_only_kernels_c(int fw, bool ext, FastKernelSet &k) {
-    switch (fw) {
-        case 7: fill_wide_set<7, false>(ext, k); return true;
-        case 9: fill_wide_set<9, false>(ext, k); return true;
-        case 11: fill_wide_set<11, false>(ext, k); return true;
-        case 13: fill_wide_set<13, false>(ext, k); return true;
-        case 15: fill_wide_set<15, false>(ext, k); return true;
-        case 17: fill_wide_set<17, false>(ext, k); return true;
-        case 19: fill_wide_set<19, false>(ext, k); return true;
-        default: return false;
+FpKernel resolve_fast_w3(const FpKernelKey &k) {
+    switch (k.fw) {
+        case 7: return resolve_fast_width<7, 2>(k);
+        case 9: return resolve_fast_width<9, 2>(k);
+        case 11: return resolve_fast_width<11, 2>(k);
+        case 13: return resolve_fast_width<13, 2>(k);
+        case 15: return resolve_fast_width<15, 2>(k);
+        case 17: return resolve_fast_width<17, 2>(k);
+        case 19: return resolve_fast_width<19, 2>(k);
+        default: return {};
     }
 }
 

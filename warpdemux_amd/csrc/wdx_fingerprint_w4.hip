@@ -7,17 +7,17 @@
 
 namespace wdx {
 
-bool exact_only_kernels_d(int fw, bool ext, FastKernelSet &k) {
-    switch (fw) {
-        case 21: fill_wide_set<21, false>(ext, k); return true;
-        case 23: fill_wide_set<23, false>(ext, k); return true;
-        case 25: fill_wide_set<25, false>(ext, k); return true;
-        case 27: fill_wide_set<27, false>(ext, k); return true;
-        case 29: fill_wide_set<29, false>(ext, k); return true;
-        case 31: fill_wide_set<31, false>(ext, k); return true;
-        case 33: fill_wide_set<33, false>(ext, k); return true;
-        case 35: fill_wide_set<35, false>(ext, k); return true;
-        default: return false;
+FpKernel resolve_fast_w4(const FpKernelKey &k) {
+    switch (k.fw) {
+        case 21: return resolve_fast_width<21, 2>(k);
+        case 23: return resolve_fast_width<23, 2>(k);
+        case 25: return resolve_fast_width<25, 2>(k);
+        case 27: return resolve_fast_width<27, 2>(k);
+        case 29: return resolve_fast_width<29, 2>(k);
+        case 31: return resolve_fast_width<31, 2>(k);
+        case 33: return resolve_fast_width<33, 2>(k);
+        case 35: return resolve_fast_width<35, 2>(k);
+        default: return {};
     }
 }
 

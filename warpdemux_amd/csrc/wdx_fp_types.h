@@ -5,9 +5,6 @@
 
 namespace wdx {
 
-constexpr int kHBits = 11;       // radix digit of the float32 medians (2048-bin histogram)
-constexpr int kHB = 1 << kHBits; // histogram bins
-
 // consensus-guided refinement (sig_proc.py:257-378, 452-521); query == nullptr: plain branch
 struct RefineDev {
     const double *query;   // consensus signal, DEVICE pointer
@@ -39,8 +36,6 @@ struct RefineMatch {
 };
 static_assert(sizeof(RefineMatch) == 64, "RefineRec::m");
 constexpr int kTailCap = 2048;        // barcode tails up to this many samples are segmented by the refinement tail kernels
-constexpr int kRefineMaxQuery = 96;   // LDS budget of the subsequence DP (direction words + three fronts)
-constexpr int kRefineMaxSeries = 128;
 
 struct ClipRec;
 struct FpArgs {
@@ -128,15 +123,13 @@ __device__ __forceinline__ float key_f32(unsigned k) {
 // (wdx_fingerprint_long.hip) fingerprint_long_refine_kernel over `grid` slots of A.big_scores: launch_fp_long's other half
 int launch_fp_long_refine(const FpArgs &A, const unsigned *count, const int32_t *list, int64_t grid, size_t lds_bytes, hipStream_t stream);
 
-// A1 for a whole batch ahead of the fast kernels' launch chain (wdx_clip.hip): one ClipRec per read of A; windows of
-// 256 .. cap samples (cap = 4096, 5120 or 6144: the main fast instantiation's) are taken, the others are flagged CLIP_NONE.
-int launch_clip_bounds(const FpArgs &A, ClipRec *d_rec, int cap, hipStream_t stream);
-int launch_route_long_windows(const FpArgs &A, int cap, unsigned *d_count, int32_t *d_list, hipStream_t stream);
-// the same for the first n_entries entries of a device-side read list (windows up to 6144 samples; reads that already
-// have a record are skipped)
-constexpr int kClipWaveLongCap = 13312;  // the longest window of the one-wave clip kernel (208 samples per lane)
-int launch_clip_bounds_list(const FpArgs &A, ClipRec *d_rec, const unsigned *d_count, const int32_t *d_list, int64_t n_entries,
-                            hipStream_t stream, int cap = 6144, bool defer = false);
+// One step of the one-wave clip families of a plan (wdx_fp_plan.h; wdx_clip.hip): kFamClip -- A1 for a whole batch ahead of the
+// fast kernels' launch chain, one ClipRec per read of A; windows of 256 .. s.capF samples are taken, the others are flagged
+// CLIP_NONE; kFamClipList -- the same for the first entries of a device-side read list (reads that already have a record are
+// skipped); kFamRoute -- the reads whose window is longer than s.capF, listed on d_list.  d_count / d_list: the list the step
+// takes (clip-list) or hands over to (route).
+int launch_clip_step(const FpStep &s, const FpArgs &A, ClipRec *d_rec, unsigned *d_count, int32_t *d_list, int64_t max_launch_slice,
+                     hipStream_t stream);
 
 // sqrt and quotient of the t-score without the range scaling of the compiler's general float64
 // expansions.  The iterations are exactly the ones hipcc emits for sqrt() and '/' on gfx950
