@@ -3,6 +3,7 @@
 #pragma once
 #include "wdx_common.h"
 #include "wdx_refine_args.h"
+#include "wdx_stage_plan.h"
 
 #include <mutex>
 #include <utility>
@@ -104,15 +105,12 @@ struct wdx_ctx {
     // workspaces, sharing this context's resident reference set; the fields below describe a child's batch in flight
     wdx_ctx *slots[WDX_MAX_SLOTS] = {};
     bool slot_busy = false, slot_waiting = false;
-    uint32_t slot_want = 0;  // WDX_WANT_* of the batch in flight
-    int64_t slot_n = 0, slot_K = 0, slot_nY = 0, slot_k = 0;
-    size_t slot_off[9] = {};  // fpt, dwell, stats, prob, conf, dist, call, status, pred in the slot's page-locked block
+    uint32_t slot_want = 0;   // WDX_WANT_* of the batch in flight
+    wdx::OutPlan slot_plan;   // ... and what it hands back: the pieces of the slot's page-locked block (wdx_stage_plan.h)
     wdx::Buffer mb_dwell, mb_stats, mb_prob, mb_pred, mb_conf;  // device side of the optional minibatch outputs
-    // a refine minibatch (wdx_demux_submit_refine; wdx_fingerprint_refine_batch on the context itself): its refine_idx on the device
-    // and, for a slot, in the page-locked block; the consensus query lives in its own ref_buf / ref_query_host, the records in ref_ws
+    // a refine minibatch (wdx_demux_submit_refine; wdx_fingerprint_refine_batch on the context itself): its refine_idx on the
+    // device; the consensus query lives in its own ref_buf / ref_query_host, the records in ref_ws
     wdx::Buffer mb_ridx;
-    bool slot_want_ridx = false;
-    size_t slot_off_ridx = 0;
     // timing
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[wdx::kNumTimed];

@@ -6,7 +6,13 @@
 //
 // One tick body (live_tick) serves every combination wdx_live_tick_ex offers -- float32 or int16 rows, the plain or the
 // consensus-refinement fingerprint, no tail / SVM / MLP / boost -- and wdx_live_tick, which is the float32 + plain +
-// [SVM] corner of it with its own, older argument list.  What is enqueued, in stream order:
+// [SVM] corner of it with its own, older argument list.  The body in parts:
+//   live_check_args, live_check_resident   every refusal, in the order they have always been made; a refused tick writes nothing
+//   plan_tick_stage, out_plan              what is staged and what comes back (wdx_stage_plan.h: host arithmetic only)
+//   fill_tick_stage                        the staging block: index columns, ok, the adapter windows
+//   live_enqueue                           the copies and the kernel chain below, in stream order
+//   deliver                                the output block's front into the caller's arrays
+// What is enqueued:
 //   H2D   the staging block: per-read index arrays + the adapter windows (float32, or int16 at 2 bytes per sample)
 //   [decode_adc_kernel        int16 windows -> calibrated float32 windows, NaN tail where a window passes the read's end]
 //   [refine_prepare           refinement: refine_idx = -1, the hand-over records' state words = 0]
@@ -16,41 +22,16 @@
 //   D2H   the wanted pieces of the output block, which lie at its front back to back
 // No new kernel: every producer writes its piece of the output block in place, so nothing has to be gathered.
 #include "wdx_ctx.h"
-#include "wdx_window.h"
-
-#include <string.h>
-
-#include <algorithm>
+#include "wdx_stage_plan.h"
 
 using namespace wdx;
 
 namespace {
 
-// The device / page-locked output block: the pieces the caller asked for first, back to back (they are what the one
-// device->host copy moves), the pieces only the device needs (fingerprints and distances nobody asked for) behind them.
-enum Piece { P_FPT, P_DWELL, P_STATS, P_PROB, P_CONF, P_CNT, P_DIST, P_RIDX, P_STATUS, P_CALL, P_PRED, P_COUNT };
-struct OutBlock {
-    size_t off[P_COUNT] = {}, bytes[P_COUNT] = {};
-    bool want[P_COUNT] = {};
-    size_t copy_bytes = 0, total = 0;
-    // need: the piece exists on the device; wanted: it travels back.  8-byte pieces before 4-byte ones (enum order).
-    void lay_out(const bool (&need)[P_COUNT]) {
-        size_t o = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            for (int q = 0; q < P_COUNT; ++q) {
-                if (!need[q] || want[q] != (pass == 0)) continue;
-                off[q] = o;
-                o += (bytes[q] + 7) / 8 * 8;
-            }
-            if (pass == 0) copy_bytes = o;
-        }
-        total = o;
-    }
-};
-
-int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, const wdx_refine_params *rp, int64_t n_refs,
-              uint32_t want, const wdx_minibatch_out *out, int32_t *refine_idx, int64_t *n_nonfinite, bool legacy) {
-    WDX_ENTER(ctx);
+// The refusals that need nothing of the context.  *pv: the parameters the chain runs with (K of the outputs, of the DTW and
+// of the boost tail).  An empty tick (n_reads == 0) passes the first five and is not looked at further.
+int live_check_args(const wdx_live_in *in, const wdx_seg_params *p_in, const wdx_refine_params *rp, uint32_t want,
+                    const wdx_minibatch_out *out, const int32_t *refine_idx, wdx_seg_params *pv) {
     if (!in || !p_in || !out || in->n_reads < 0) {
         set_error("live_tick: bad arguments");
         return WDX_ERR_INVALID;
@@ -79,8 +60,7 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
         return WDX_ERR_INVALID;
     }
     if (n_reads == 0) return WDX_SUCCESS;   // (and nothing was touched, *n_nonfinite included)
-    wdx_seg_params pv;   // K of the outputs, of the DTW and of the boost tail
-    if ((rc = refine_seg_params("live_tick", p_in, rp, &pv))) return rc;
+    if (int rc = refine_seg_params("live_tick", p_in, rp, pv)) return rc;
     if (rp && (tail == WDX_LIVE_TAIL_SVM || tail == WDX_LIVE_TAIL_MLP)) {
         set_error("live_tick: consensus refinement is served with no tail or the boost tail (no DTW model is trained on "
                   "refined fingerprints)");
@@ -95,14 +75,20 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
         set_error("live_tick: an output `want` asks for has no array");
         return WDX_ERR_INVALID;
     }
-    const wdx_seg_params *p = &pv;
-    const int64_t K = p->barcode_num_events;
-    if (K < 1) {
+    if (pv->barcode_num_events < 1) {
         set_error("barcode_num_events must be >= 1");
         return WDX_ERR_INVALID;
     }
-    std::lock_guard<std::mutex> g(ctx->mu);
-    DtwRefs &R = ctx->refs;
+    return WDX_SUCCESS;
+}
+
+// The refusals that look at what is resident (the context's mutex is held), and the two of the arguments that have always
+// come behind them.  *nY: the references the chain runs against (0: none).
+int live_check_resident(const wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params &p, bool refine, int64_t n_refs,
+                        uint32_t want, bool legacy, int64_t *nY) {
+    int rc = WDX_SUCCESS;
+    const DtwRefs &R = ctx->refs;
+    const int tail = in->tail;
     const bool resident = R.window != 0;
     if (!resident) {
         // no reference set: fingerprints [+ boost tail] only
@@ -115,183 +101,104 @@ int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, c
             return WDX_ERR_INVALID;
         }
     } else {
-        if ((rc = check_ref_length(R, *p))) return rc;
+        if ((rc = check_ref_length(R, p))) return rc;
         if (n_refs != R.nY) {
             set_error("live_tick: the caller sized `dist` for %lld references but %lld are resident", (long long)n_refs,
                       (long long)R.nY);
             return WDX_ERR_INVALID;
         }
     }
-    const int64_t nY = resident ? R.nY : 0;
-    if (tail == WDX_LIVE_TAIL_SVM && (!ctx->svm.set || ctx->svm.dev.n_train != nY)) {
+    *nY = resident ? R.nY : 0;
+    if (tail == WDX_LIVE_TAIL_SVM && (!ctx->svm.set || ctx->svm.dev.n_train != *nY)) {
         set_error("live_tick: use_svm needs wdx_svm_set_model with a model trained on the resident reference set");
         return WDX_ERR_NO_REFS;
     }
     // (the SVM's two refusals above share one code here and nowhere else: kept as found)
-    if (tail != WDX_LIVE_TAIL_SVM && (rc = tail_ready(ctx, tail, nY, K, rp != nullptr, "live_tick"))) return rc;
-    if (p->padding < 0) {
+    if (tail != WDX_LIVE_TAIL_SVM && (rc = tail_ready(ctx, tail, *nY, p.barcode_num_events, refine, "live_tick"))) return rc;
+    if (p.padding < 0) {
         set_error("padding must be >= 0");
         return WDX_ERR_INVALID;
     }
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const void *row = adc ? (const void *)in->adc_rows[r] : (const void *)in->rows[r];
+    for (int64_t r = 0; r < in->n_reads; ++r) {
+        const void *row = in->adc_rows ? (const void *)in->adc_rows[r] : (const void *)in->rows[r];
         if (in->row_len[r] < 0 || (in->row_len[r] > 0 && !row)) {
             set_error("live_tick: row %lld is null or has a negative length", (long long)r);
             return WDX_ERR_INVALID;
         }
     }
-    if (n_nonfinite) *n_nonfinite = 0;   // (behind every refusal: a refused tick writes nothing)
-    hipStream_t s = ctx->stream;
-    if ((rc = use_stream(ctx, s))) return rc;
-    const int32_t *row_len = in->row_len, *a_start = in->a_start, *a_end = in->a_end;
-    const uint8_t *ok = in->ok;
-    const size_t n = (size_t)n_reads;
+    return WDX_SUCCESS;
+}
 
-    // ---- adapter windows (extract_adapter, sig_proc.py:382-391), packed into the page-locked staging block ---------
-    // float32: [int64 off[n+1]] [int32 zero[n]] [int32 len[n]] [uint8 ok[n] padded] [float samples, back to back]
-    //          the packed row IS the window: a_start' = 0, a_end' = len makes [max(0, 0-pad), min(len, len+pad)) = the row
-    // int16:   [int64 dst_off[n+1]] [int64 src_off[n]] [int32 zero[n]] [int32 win[n]] [int32 valid[n]] [float offset[n]]
-    //          [float scale[n]] [uint8 ok[n] padded] [int16 samples, every row on a 16-byte boundary]
-    //          row r stands for win[r] float32 samples, the first valid[r] of them the read's own, the rest the NaN tail
-    //          of the *_adc contract (a window that runs past the read's end: wdx_minibatch_adc_in.row_win); decoded
-    //          rows start on 32-byte boundaries of the float32 buffer (in1), as fingerprint_adc_rows lays them out
-    // float32: the window inside the read, taken from its very first sample.  int16: a ragged row has no limit -- a window that
-    // runs past the read's end keeps its NaN tail -- and a window beyond the kernels' limit keeps one sample more than the
-    // limit (the context's, for the branch this tick runs: WDX_OPT_LONG_WINDOWS raises it for a plain tick,
-    // WDX_OPT_LONG_REFINE_WINDOWS for one with refine parameters), which is what reports it.
-    const WindowOpts wo{p->padding, 1, adc ? ctx->knobs.max_window(rp != nullptr) + 1 : 0};
-    auto window = [&](int64_t r) {
-        return adapter_window(a_start[r], a_end[r], adc ? kNoRowLimit : (int64_t)row_len[r], ok && !ok[r], wo, adc ? (int64_t)row_len[r] : -1);
-    };
-    // staged samples back to back (int16: every row on a 16-byte boundary); decoded int16 rows on 32-byte boundaries
-    const int64_t src_round = adc ? 8 : 1, dst_round = 8;
-    int64_t max_len = 0;
-    PackedOffset fit(src_round), dfit(dst_round);   // (the sizing pass; the fill pass below counts again)
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const Window w = window(r);
-        max_len = std::max(max_len, w.win);
-        fit.take(w.valid);
-        dfit.take(w.row);
-    }
-    const int64_t total = fit.next, dst_total = dfit.next;
-    size_t o_off = 0, o_src = 0, o_zero, o_len, o_valid = 0, o_cal = 0, o_ok, o_sig, in_bytes;
-    if (adc) {
-        o_src = (n + 1) * 8;
-        o_zero = o_src + n * 8;
-        o_len = o_zero + n * 4;
-        o_valid = o_len + n * 4;
-        o_cal = o_valid + n * 4;
-        o_ok = o_cal + n * 8;
-        o_sig = (o_ok + n + 15) / 16 * 16;
-        in_bytes = o_sig + (size_t)total * 2;
-    } else {
-        o_zero = (n + 1) * 8;
-        o_len = o_zero + n * 4;
-        o_ok = o_len + n * 4;
-        o_sig = (o_ok + n + 15) / 16 * 16;
-        in_bytes = o_sig + (size_t)total * 4;
-    }
-    if ((rc = ctx->pin_in.ensure(in_bytes))) return rc;
-    if ((rc = ctx->in0.ensure(in_bytes))) return rc;
-    if (adc && (rc = ctx->in1.ensure((size_t)(dst_total ? dst_total : 1) * 4))) return rc;
-    unsigned char *hin = (unsigned char *)ctx->pin_in.p;
-    int64_t *h_off = (int64_t *)(hin + o_off), *h_src = (int64_t *)(hin + o_src);
-    int32_t *h_zero = (int32_t *)(hin + o_zero), *h_len = (int32_t *)(hin + o_len), *h_valid = (int32_t *)(hin + o_valid);
-    float *h_cal = (float *)(hin + o_cal);
-    uint8_t *h_ok = hin + o_ok;
-    PackedOffset pos(src_round), dpos(dst_round);
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const Window w = window(r);
-        const int64_t at = pos.take(w.valid);
-        h_zero[r] = 0;
-        h_len[r] = (int32_t)w.row;
-        h_ok[r] = (!ok || ok[r]) ? 1 : 0;
-        if (adc) {
-            h_off[r] = dpos.take(w.row);
-            h_src[r] = at;
-            h_valid[r] = (int32_t)w.valid;
-            h_cal[r] = in->offset[r];
-            h_cal[n + r] = in->scale[r];
-            if (w.valid > 0) memcpy((int16_t *)(hin + o_sig) + at, in->adc_rows[r] + w.first, (size_t)w.valid * 2);
-        } else {
-            h_off[r] = at;
-            if (w.valid > 0) memcpy((float *)(hin + o_sig) + at, in->rows[r] + w.first, (size_t)w.valid * 4);
-        }
-    }
-    h_off[n_reads] = adc ? dpos.next : pos.next;
-
-    // ---- the output block -------------------------------------------------------------------------------------------
-    const int k = tail == WDX_LIVE_TAIL_SVM ? ctx->svm.dev.k : tail == WDX_LIVE_TAIL_MLP ? ctx->mlp.dev.k
-                : tail == WDX_LIVE_TAIL_BOOST ? ctx->boost.dev.k : 0;
-    const bool run_dtw = nY > 0;
-    // (a DTW tail without a single reference has nothing to read: as before, its outputs are left alone)
-    const bool run_tail = tail == WDX_LIVE_TAIL_BOOST || (tail != WDX_LIVE_TAIL_NONE && run_dtw);
-    OutBlock B;
-    bool need[P_COUNT] = {};
-    B.bytes[P_FPT] = n * K * 8, need[P_FPT] = true, B.want[P_FPT] = (want & WDX_WANT_FPT) != 0;
-    B.bytes[P_DWELL] = n * K * 8, need[P_DWELL] = B.want[P_DWELL] = (want & WDX_WANT_DWELL) != 0;
-    B.bytes[P_STATS] = n * 48, need[P_STATS] = B.want[P_STATS] = (want & WDX_WANT_STATS) != 0;
-    B.bytes[P_PROB] = n * (size_t)k * 8, need[P_PROB] = run_tail, B.want[P_PROB] = run_tail && out->prob;
-    B.bytes[P_CONF] = n * 8, need[P_CONF] = run_tail, B.want[P_CONF] = run_tail && out->conf;
-    B.bytes[P_CNT] = 8, need[P_CNT] = B.want[P_CNT] = run_tail && tail == WDX_LIVE_TAIL_MLP;
-    B.bytes[P_DIST] = n * (size_t)nY * 4, need[P_DIST] = run_dtw, B.want[P_DIST] = run_dtw && (want & WDX_WANT_DIST);
-    B.bytes[P_RIDX] = n * 12, need[P_RIDX] = B.want[P_RIDX] = (want & WDX_WANT_REFINE_IDX) != 0;
-    B.bytes[P_STATUS] = n * 4, need[P_STATUS] = B.want[P_STATUS] = true;
-    B.bytes[P_CALL] = n * 4, need[P_CALL] = run_dtw, B.want[P_CALL] = run_dtw && out->call;
-    B.bytes[P_PRED] = n * 4, need[P_PRED] = run_tail, B.want[P_PRED] = run_tail && out->pred;
-    B.lay_out(need);
-    if ((rc = ctx->out0.ensure(B.total))) return rc;
-    if ((rc = ctx->pin_out.ensure(B.copy_bytes))) return rc;
-    if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
+// The staging block (filled, in ctx->pin_in) -> the device, the kernel chain, the front of the output block -> ctx->pin_out;
+// everything on s, the caller synchronises.  in0: the staging block; in1: the decoded rows of an int16 tick; out0: the block.
+int live_enqueue(wdx_ctx *ctx, const TickStage &T, const OutPlan &B, int64_t n_reads, const wdx_seg_params &p,
+                 const wdx_refine_params *rp, int tail, hipStream_t s) {
+    int rc = WDX_SUCCESS;
     unsigned char *din = (unsigned char *)ctx->in0.p, *dout = (unsigned char *)ctx->out0.p;
-    unsigned char *hout = (unsigned char *)ctx->pin_out.p;
-    double *d_fpt = (double *)(dout + B.off[P_FPT]), *d_prob = (double *)(dout + B.off[P_PROB]),
-           *d_conf = (double *)(dout + B.off[P_CONF]);
-    float *d_dist = (float *)(dout + B.off[P_DIST]);
-    int32_t *d_status = (int32_t *)(dout + B.off[P_STATUS]), *d_call = (int32_t *)(dout + B.off[P_CALL]),
-            *d_pred = (int32_t *)(dout + B.off[P_PRED]);
-    int64_t *d_cnt = (int64_t *)(dout + B.off[P_CNT]);
-
-    StreamDrain drain(s);
-    WDX_HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, s));
-    const float *d_sig = (const float *)(din + o_sig);
-    if (adc) {
+    auto at = [&](OutPiece q) { return (void *)(dout + B.off[q]); };
+    auto at_or_null = [&](OutPiece q) { return B.exists[q] ? at(q) : nullptr; };
+    WDX_HIP_TRY(hipMemcpyAsync(din, ctx->pin_in.p, T.L.bytes, hipMemcpyHostToDevice, s));
+    const uint8_t *d_ok = din + T.L.ok;
+    FpReads rd;
+    if (T.adc) {
         // decode_adc_kernel ahead of the unchanged chain: the windows, calibrated, and the NaN tail where one passes its read's end
-        const float *d_cal = (const float *)(din + o_cal);
-        const AdcRows rows{(const int16_t *)(din + o_sig), (const int64_t *)(din + o_src), 0, (const int32_t *)(din + o_valid),
-                           d_cal, d_cal + n, (float *)ctx->in1.p, (const int64_t *)(din + o_off), 0, (const int32_t *)(din + o_len)};
+        const AdcImage D(din, T.L);
+        float *d_rows = (float *)ctx->in1.p;
+        const AdcRows rows{(const int16_t *)(din + T.L.sig), D.src, 0, D.valid, D.offset, D.scale, d_rows, D.dst, 0, D.out};
         if ((rc = launch_adc_rows(rows, n_reads, false, s))) return rc;
-        d_sig = (const float *)ctx->in1.p;
+        rd = FpReads{d_rows, D.dst, D.out, 0, T.max_len, n_reads, D.a_start, D.a_end, d_ok};
+    } else {
+        const int32_t *d_len = image_col<int32_t>(din, T.L, FT_LEN);
+        rd = FpReads{(const float *)(din + T.L.sig), image_col<int64_t>(din, T.L, FT_OFF), nullptr, 0, T.max_len, n_reads,
+                     image_col<int32_t>(din, T.L, FT_ZERO), d_len, d_ok};
     }
-    const FpReads rd{d_sig, (const int64_t *)(din + o_off), adc ? (const int32_t *)(din + o_len) : nullptr, 0, max_len, n_reads,
-                     (const int32_t *)(din + o_zero), (const int32_t *)(din + o_len), (const uint8_t *)(din + o_ok)};
     ChainTail ct;
     ct.kind = tail;
     ct.svm = &ctx->svm.dev, ct.mlp = &ctx->mlp.dev, ct.boost = &ctx->boost.dev;
-    ChainOut co{FpOut{d_fpt, need[P_DWELL] ? (int64_t *)(dout + B.off[P_DWELL]) : nullptr,
-                      need[P_STATS] ? (double *)(dout + B.off[P_STATS]) : nullptr, d_status}};
-    co.dist = d_dist, co.call = d_call, co.prob = d_prob, co.pred = d_pred, co.conf = d_conf, co.n_nonfinite = d_cnt;
+    ChainOut co{FpOut{(double *)at(P_FPT), (int64_t *)at_or_null(P_DWELL), (double *)at_or_null(P_STATS), (int32_t *)at(P_STATUS)}};
+    co.dist = (float *)at(P_DIST), co.call = (int32_t *)at(P_CALL);
+    co.prob = (double *)at(P_PROB), co.pred = (int32_t *)at(P_PRED), co.conf = (double *)at(P_CONF);
+    co.n_nonfinite = (int64_t *)at(P_CNT);
     // main_events = false, with and without refinement: wdx_live_tick has never recorded them (wdx_ctx.h: fingerprint_stage)
-    int32_t *d_ridx = need[P_RIDX] ? (int32_t *)(dout + B.off[P_RIDX]) : nullptr;
-    if ((rc = demux_chain(ctx, resident ? R : DtwRefs{}, rd, *p, rp, d_ridx, nullptr, ctx->fp_ws.p, false, ct, co, s))) return rc;
+    const DtwRefs R = ctx->refs.window != 0 ? ctx->refs : DtwRefs{};
+    if ((rc = demux_chain(ctx, R, rd, p, rp, (int32_t *)at_or_null(P_RIDX), nullptr, ctx->fp_ws.p, false, ct, co, s))) return rc;
     // one device->host copy: the wanted pieces are the front of the block
-    WDX_HIP_TRY(hipMemcpyAsync(hout, dout, B.copy_bytes, hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipMemcpyAsync(ctx->pin_out.p, dout, B.copy_bytes, hipMemcpyDeviceToHost, s));
+    return WDX_SUCCESS;
+}
+
+int live_tick(wdx_ctx *ctx, const wdx_live_in *in, const wdx_seg_params *p_in, const wdx_refine_params *rp, int64_t n_refs,
+              uint32_t want, const wdx_minibatch_out *out, int32_t *refine_idx, int64_t *n_nonfinite, bool legacy) {
+    WDX_ENTER(ctx);
+    wdx_seg_params pv;
+    if ((rc = live_check_args(in, p_in, rp, want, out, refine_idx, &pv))) return rc;
+    const int64_t n_reads = in->n_reads;
+    if (n_reads == 0) return WDX_SUCCESS;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    int64_t nY = 0;
+    if ((rc = live_check_resident(ctx, in, pv, rp != nullptr, n_refs, want, legacy, &nY))) return rc;
+    if (n_nonfinite) *n_nonfinite = 0;   // (behind every refusal: a refused tick writes nothing)
+    hipStream_t s = ctx->stream;
+    if ((rc = use_stream(ctx, s))) return rc;
+    // the longest window of the branch this tick runs (the context's: WDX_OPT_LONG_WINDOWS raises it for a plain tick,
+    // WDX_OPT_LONG_REFINE_WINDOWS for one with refine parameters)
+    const TickStage T = plan_tick_stage(*in, pv.padding, ctx->knobs.max_window(rp != nullptr) + 1);
+    if ((rc = ctx->pin_in.ensure(T.L.bytes))) return rc;
+    if ((rc = ctx->in0.ensure(T.L.bytes))) return rc;
+    if (T.adc && (rc = ctx->in1.ensure((size_t)(T.dst_total ? T.dst_total : 1) * 4))) return rc;
+    fill_tick_stage(*in, T, (unsigned char *)ctx->pin_in.p);
+    const int tail = in->tail;
+    const int k = tail == WDX_LIVE_TAIL_SVM ? ctx->svm.dev.k : tail == WDX_LIVE_TAIL_MLP ? ctx->mlp.dev.k
+                : tail == WDX_LIVE_TAIL_BOOST ? ctx->boost.dev.k : 0;
+    const OutPlan B = out_plan(n_reads, pv.barcode_num_events, nY, k, want, tail, rp != nullptr, have_of(*out));
+    if ((rc = ctx->out0.ensure(B.total))) return rc;
+    if ((rc = ctx->pin_out.ensure(B.copy_bytes))) return rc;
+    if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
+    StreamDrain drain(s);
+    if ((rc = live_enqueue(ctx, T, B, n_reads, pv, rp, tail, s))) return rc;
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
-    memcpy(out->status, hout + B.off[P_STATUS], B.bytes[P_STATUS]);
-    if (out->call) {
-        if (run_dtw) memcpy(out->call, hout + B.off[P_CALL], B.bytes[P_CALL]);
-        else for (int64_t r = 0; r < n_reads; ++r) out->call[r] = -1;
-    }
-    if (B.want[P_DIST]) memcpy(out->dist, hout + B.off[P_DIST], B.bytes[P_DIST]);
-    if (B.want[P_FPT]) memcpy(out->fpt, hout + B.off[P_FPT], B.bytes[P_FPT]);
-    if (B.want[P_DWELL]) memcpy(out->dwell, hout + B.off[P_DWELL], B.bytes[P_DWELL]);
-    if (B.want[P_STATS]) memcpy(out->stats, hout + B.off[P_STATS], B.bytes[P_STATS]);
-    if (B.want[P_RIDX]) memcpy(refine_idx, hout + B.off[P_RIDX], B.bytes[P_RIDX]);
-    if (B.want[P_PROB]) memcpy(out->prob, hout + B.off[P_PROB], B.bytes[P_PROB]);
-    if (B.want[P_PRED]) memcpy(out->pred, hout + B.off[P_PRED], B.bytes[P_PRED]);
-    if (B.want[P_CONF]) memcpy(out->conf, hout + B.off[P_CONF], B.bytes[P_CONF]);
-    if (B.want[P_CNT] && n_nonfinite) memcpy(n_nonfinite, hout + B.off[P_CNT], 8);
+    deliver(B, (const unsigned char *)ctx->pin_out.p, *out, refine_idx, n_nonfinite);
     return WDX_SUCCESS;
 }
 

@@ -12,15 +12,27 @@ using namespace wdx;
 
 extern "C" {
 
-struct MbHostOut {  // host destinations of one minibatch; null = not wanted (status always)
-    int32_t *status = nullptr, *call = nullptr;
-    float *dist = nullptr;
-    double *fpt = nullptr;
-    int64_t *dwell = nullptr;
-    double *stats = nullptr, *prob = nullptr;
-    int32_t *pred = nullptr;
-    double *conf = nullptr;
+// Host destinations of one minibatch, piece by piece of its plan (wdx_stage_plan.h): the caller's arrays, or the pieces of a
+// slot's page-locked block; null = the piece stays on the device
+struct MbHost {
+    void *to[P_COUNT];
 };
+static MbHost host_arrays(const wdx_minibatch_out &out) {
+    MbHost H{};
+    for (int q = 0; q < P_COUNT; ++q) H.to[q] = destination(q, out, nullptr, nullptr);
+    return H;
+}
+static MbHost host_block(const OutPlan &pl, unsigned char *block) {
+    MbHost H{};
+    for (int q = 0; q < P_COUNT; ++q) H.to[q] = pl.travels[q] ? block + pl.off[q] : nullptr;
+    return H;
+}
+// Which device buffer of `B` backs which piece of a minibatch (the MLP tail's count is the live tick's alone)
+static Buffer *piece_buffer(wdx_ctx *B, int q) {
+    Buffer *const of[P_COUNT] = {&B->out0, &B->mb_dwell, &B->mb_stats, &B->mb_prob, &B->mb_conf, nullptr,
+                                 &B->out1, &B->mb_ridx, &B->out3,     &B->out2,    &B->mb_pred};
+    return of[q];
+}
 
 // Way (i) in of float32 rows of one stride, pageable or not: the 2-D DMA copy of the columns that hold every adapter window
 // of the batch into B->in0, a_start / a_end / ok into in1 / in2 / in3 (the caller sized all four); *rd = the reads as the
@@ -80,11 +92,12 @@ static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const 
             (void)hipGetLastError();
     }
     if (packed_in) {
-        // device images: off int64[n+1] | len int32[n] | a_start int32[n] | a_end int32[n], straight from the caller's arrays
-        const size_t ib = (size_t)(n_reads + 1) * 8 + (size_t)n_reads * 12;
-        if ((rc = B->pk_idx.ensure(ib))) return rc;
-        int64_t *d_off = (int64_t *)B->pk_idx.p;
-        int32_t *d_len = (int32_t *)(d_off + n_reads + 1), *d_as = d_len + n_reads, *d_ae = d_as + n_reads;
+        // the device image (kPackedRowsImage), column by column straight from the caller's arrays
+        const ImageLayout L = image_layout(kPackedRowsImage, (size_t)n_reads);
+        if ((rc = B->pk_idx.ensure(L.bytes))) return rc;
+        int64_t *d_off = image_col<int64_t>(B->pk_idx.p, L, PK_OFF);
+        int32_t *d_len = image_col<int32_t>(B->pk_idx.p, L, PK_LEN), *d_as = image_col<int32_t>(B->pk_idx.p, L, PK_A_START),
+                *d_ae = image_col<int32_t>(B->pk_idx.p, L, PK_A_END);
         if (sb) WDX_HIP_TRY(hipMemcpyAsync(B->in0.p, sig, sb, hipMemcpyHostToDevice, s));
         WDX_HIP_TRY(hipMemcpyAsync(d_off, in.row_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, s));
         WDX_HIP_TRY(hipMemcpyAsync(d_len, in.row_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
@@ -95,30 +108,19 @@ static int fingerprint_float_rows(wdx_ctx *B, const wdx_minibatch_in &in, const 
         return WDX_SUCCESS;
     }
     if (!sig_dev) return fingerprint_float_columns(B, in, wb, rd);
-    // host images (page-locked, owned by the slot until its copy has run): off int64[n+1] | st int32[n] | len
-    // int32[n] | a_start' int32[n] | a_end' int32[n]
-    const size_t ib = (size_t)(n_reads + 1) * 8 + (size_t)n_reads * 16;
-    if ((rc = B->pk_host.ensure(ib))) return rc;
-    if ((rc = B->pk_idx.ensure(ib))) return rc;
-    int64_t *h_off = (int64_t *)B->pk_host.p;
-    int32_t *h_st = (int32_t *)(h_off + n_reads + 1), *h_len = h_st + n_reads, *h_as = h_len + n_reads, *h_ae = h_as + n_reads;
-    const WindowOpts bus{p->padding, 4, 0};  // (up to three samples ahead of the window come along: 16-byte aligned bus reads)
-    PackedOffset pos(4);                     // (rows start on 16-byte boundaries)
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const Window w = adapter_window(a_start[r], a_end[r], stride, ok && !ok[r], bus);
-        h_off[r] = pos.take(w.row);
-        h_st[r] = (int32_t)w.first;
-        h_len[r] = (int32_t)w.row;
-        h_as[r] = w.a_start;
-        h_ae[r] = w.a_end;
-    }
-    h_off[n_reads] = pos.next;
-    if ((rc = B->in0.ensure((size_t)(pos.next ? pos.next : 1) * sizeof(float)))) return rc;
-    WDX_HIP_TRY(hipMemcpyAsync(B->pk_idx.p, B->pk_host.p, ib, hipMemcpyHostToDevice, s));
-    const int64_t *d_off = (const int64_t *)B->pk_idx.p;
-    const int32_t *d_st = (const int32_t *)(d_off + n_reads + 1), *d_len = d_st + n_reads, *d_as = d_len + n_reads,
-                  *d_ae = d_as + n_reads;
-    if ((rc = launch_pack_windows(sig_dev, stride, n_reads, d_off, d_st, d_len, (float *)B->in0.p, s))) return rc;
+    // the bus-pack image (kBusPackImage; page-locked, owned by the slot until its copy has run) and its device copy
+    const ImageLayout L = image_layout(kBusPackImage, (size_t)n_reads);
+    if ((rc = B->pk_host.ensure(L.bytes))) return rc;
+    if ((rc = B->pk_idx.ensure(L.bytes))) return rc;
+    const int64_t packed = fill_bus_pack_image((unsigned char *)B->pk_host.p, L, n_reads, stride, a_start, a_end, ok, p->padding);
+    if ((rc = B->in0.ensure((size_t)(packed ? packed : 1) * sizeof(float)))) return rc;
+    WDX_HIP_TRY(hipMemcpyAsync(B->pk_idx.p, B->pk_host.p, L.bytes, hipMemcpyHostToDevice, s));
+    const int64_t *d_off = image_col<int64_t>(B->pk_idx.p, L, BP_OFF);
+    const int32_t *d_len = image_col<int32_t>(B->pk_idx.p, L, BP_LEN), *d_as = image_col<int32_t>(B->pk_idx.p, L, BP_A_START),
+                  *d_ae = image_col<int32_t>(B->pk_idx.p, L, BP_A_END);
+    if ((rc = launch_pack_windows(sig_dev, stride, n_reads, d_off, image_col<int32_t>(B->pk_idx.p, L, BP_FIRST), d_len,
+                                  (float *)B->in0.p, s)))
+        return rc;
     if (ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, ok, (size_t)n_reads, hipMemcpyHostToDevice, s));
     *rd = FpReads{(const float *)B->in0.p, d_off, d_len, 0, wb.max_len, n_reads, d_as, d_ae, d_ok};
     return WDX_SUCCESS;
@@ -181,22 +183,19 @@ static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const
     hipStream_t s = B->stream;
     const int64_t n = A.n_reads, stride = A.stride;
     const bool packed_in = A.row_off != nullptr;
-    // host images (page-locked, owned by the slot until its copy has run):
-    // dst_off int64[n+1] | src_off int64[n] | n_out int32[n] | n_valid int32[n] | a_start' int32[n] | a_end' int32[n] |
-    // offset float[n] | scale float[n]
-    const size_t ib = (size_t)(n + 1) * 8 + (size_t)n * 8 + (size_t)n * 24;
-    if ((rc = B->pk_host.ensure(ib))) return rc;
-    if ((rc = B->pk_idx.ensure(ib))) return rc;
+    // the int16 image (kAdcImage; page-locked, owned by the slot until its copy has run) and its device copy
+    const ImageLayout L = image_layout(kAdcImage, (size_t)n);
+    if ((rc = B->pk_host.ensure(L.bytes))) return rc;
+    if ((rc = B->pk_idx.ensure(L.bytes))) return rc;
     if ((rc = B->in3.ensure((size_t)n))) return rc;
-    int64_t *h_dst = (int64_t *)B->pk_host.p, *h_src = h_dst + n + 1;
-    int32_t *h_out = (int32_t *)(h_src + n), *h_valid = h_out + n, *h_as = h_valid + n, *h_ae = h_as + n;
-    float *h_cal = (float *)(h_ae + n);
+    const AdcImage H(B->pk_host.p, L), D(B->pk_idx.p, L);
     WindowBatch wb(stride);
-    PackedOffset pos(8);   // (rows start on 32-byte boundaries)
+    PackedOffset pos(kDecodedRowRound);
     const WindowOpts exact{p->padding, 1, 0}, groups{p->padding, 8, 0};
     for (int64_t r = 0; r < n; ++r) {
         const bool dead = A.ok && !A.ok[r];
         Window w;
+        int64_t src;
         if (packed_in) {
             // the caller's row as it stands; its window only bounds max_len
             w.row = A.row_win ? (int64_t)A.row_win[r] : (int64_t)A.row_len[r];
@@ -204,28 +203,19 @@ static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const
             w.a_start = A.a_start[r];
             w.a_end = A.a_end[r];
             wb.max_len = std::max(wb.max_len, adapter_window(w.a_start, w.a_end, w.row, dead, exact).win);
-            h_src[r] = A.row_off[r];
+            src = A.row_off[r];
         } else {
             w = adapter_window(A.a_start[r], A.a_end[r], stride, dead, groups, A.row_len[r]);
             wb.add(w);
-            h_src[r] = r * stride + w.first;
+            src = r * stride + w.first;
         }
-        h_dst[r] = pos.take(w.row);
-        h_out[r] = (int32_t)w.row;
-        h_valid[r] = (int32_t)w.valid;
-        h_as[r] = w.a_start;
-        h_ae[r] = w.a_end;
-        h_cal[r] = A.offset[r];
-        h_cal[n + r] = A.scale[r];
+        adc_image_row(H, r, w, src, pos, A.offset[r], A.scale[r]);
     }
-    h_dst[n] = pos.next;
+    H.dst[n] = pos.next;
     const int64_t col0 = wb.col0, col1 = wb.col1;
     if ((rc = B->in0.ensure((size_t)(pos.next ? pos.next : 1) * sizeof(float)))) return rc;
-    WDX_HIP_TRY(hipMemcpyAsync(B->pk_idx.p, B->pk_host.p, ib, hipMemcpyHostToDevice, s));
-    const int64_t *d_dst = (const int64_t *)B->pk_idx.p, *d_src = d_dst + n + 1;
-    const int32_t *d_out = (const int32_t *)(d_src + n), *d_valid = d_out + n, *d_as = d_valid + n, *d_ae = d_as + n;
-    const float *d_cal = (const float *)(d_ae + n);
-    AdcRows rows{nullptr, d_src, 0, d_valid, d_cal, d_cal + n, (float *)B->in0.p, d_dst, 0, d_out};
+    WDX_HIP_TRY(hipMemcpyAsync(B->pk_idx.p, B->pk_host.p, L.bytes, hipMemcpyHostToDevice, s));
+    AdcRows rows{nullptr, D.src, 0, D.valid, D.offset, D.scale, (float *)B->in0.p, D.dst, 0, D.out};
     const int16_t *adc_dev = nullptr;  // the minibatch as the device sees it, when it is page-locked
     if (!packed_in && col1 > col0 && (double)wb.win_total < 0.85 * (double)((col1 - col0) * n)) {
         hipPointerAttribute_t at;
@@ -250,7 +240,7 @@ static int fingerprint_adc_rows(wdx_ctx *B, const wdx_minibatch_adc_in &A, const
     }
     if ((rc = launch_adc_rows(rows, n, adc_dev != nullptr, s))) return rc;
     if (A.ok) WDX_HIP_TRY(hipMemcpyAsync(B->in3.p, A.ok, (size_t)n, hipMemcpyHostToDevice, s));
-    *rd = FpReads{(const float *)B->in0.p, d_dst, d_out, 0, wb.max_len, n, d_as, d_ae, A.ok ? (const uint8_t *)B->in3.p : nullptr};
+    *rd = FpReads{(const float *)B->in0.p, D.dst, D.out, 0, wb.max_len, n, D.a_start, D.a_end, A.ok ? (const uint8_t *)B->in3.p : nullptr};
     return WDX_SUCCESS;
 }
 
@@ -285,12 +275,15 @@ static int fingerprint_batch_impl(wdx_ctx *ctx, const float *sig, int64_t n_read
     if ((rc = ctx->in1.ensure((size_t)n_reads * 4))) return rc;
     if ((rc = ctx->in2.ensure((size_t)n_reads * 4))) return rc;
     if ((rc = ctx->in3.ensure((size_t)n_reads))) return rc;
-    if ((rc = ctx->out0.ensure((size_t)(n_reads * K) * 8))) return rc;
-    if ((rc = ctx->out1.ensure((size_t)(n_reads * K) * 8))) return rc;
-    if ((rc = ctx->out2.ensure((size_t)n_reads * 6 * 8))) return rc;
-    if ((rc = ctx->out3.ensure((size_t)n_reads * 4))) return rc;
+    // every fingerprint output, each in a buffer of its own: fpt out0, dwell out1, stats out2, status out3, refine_idx mb_ridx
+    const OutPlan pl = out_plan(n_reads, K, 0, 0, WDX_WANT_FPT | WDX_WANT_DWELL | WDX_WANT_STATS | WDX_WANT_REFINE_IDX,
+                                WDX_LIVE_TAIL_NONE, rp != nullptr, 0);
+    if ((rc = ctx->out0.ensure(pl.bytes[P_FPT]))) return rc;
+    if ((rc = ctx->out1.ensure(pl.bytes[P_DWELL]))) return rc;
+    if ((rc = ctx->out2.ensure(pl.bytes[P_STATS]))) return rc;
+    if ((rc = ctx->out3.ensure(pl.bytes[P_STATUS]))) return rc;
     if ((rc = ctx->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    if (rp && (rc = ctx->mb_ridx.ensure((size_t)n_reads * 12))) return rc;
+    if (rp && (rc = ctx->mb_ridx.ensure(pl.bytes[P_RIDX]))) return rc;
     StreamDrain drain(s);
     const wdx_minibatch_in in{sig, n_reads, stride, nullptr, nullptr, a_start, a_end, ok};
     FpReads rd;
@@ -298,11 +291,11 @@ static int fingerprint_batch_impl(wdx_ctx *ctx, const float *sig, int64_t n_read
     const ChainOut out{FpOut{(double *)ctx->out0.p, (int64_t *)ctx->out1.p, (double *)ctx->out2.p, (int32_t *)ctx->out3.p}};
     int32_t *d_ridx = (int32_t *)ctx->mb_ridx.p;
     if ((rc = demux_chain(ctx, DtwRefs{}, rd, pv, rp, d_ridx, nullptr, ctx->fp_ws.p, false, ChainTail{}, out, s))) return rc;
-    WDX_HIP_TRY(hipMemcpyAsync(fpt, ctx->out0.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
-    WDX_HIP_TRY(hipMemcpyAsync(dwell, ctx->out1.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
-    WDX_HIP_TRY(hipMemcpyAsync(stats, ctx->out2.p, (size_t)n_reads * 48, hipMemcpyDeviceToHost, s));
-    WDX_HIP_TRY(hipMemcpyAsync(status, ctx->out3.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
-    if (rp) WDX_HIP_TRY(hipMemcpyAsync(refine_idx, ctx->mb_ridx.p, (size_t)n_reads * 12, hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipMemcpyAsync(fpt, ctx->out0.p, pl.bytes[P_FPT], hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipMemcpyAsync(dwell, ctx->out1.p, pl.bytes[P_DWELL], hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipMemcpyAsync(stats, ctx->out2.p, pl.bytes[P_STATS], hipMemcpyDeviceToHost, s));
+    WDX_HIP_TRY(hipMemcpyAsync(status, ctx->out3.p, pl.bytes[P_STATUS], hipMemcpyDeviceToHost, s));
+    if (rp) WDX_HIP_TRY(hipMemcpyAsync(refine_idx, ctx->mb_ridx.p, pl.bytes[P_RIDX], hipMemcpyDeviceToHost, s));
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
     return WDX_SUCCESS;
@@ -334,62 +327,33 @@ struct MbIn {
     const wdx_minibatch_adc_in *adc = nullptr;
     int64_t n_reads() const { return adc ? adc->n_reads : f->n_reads; }
 };
-// The refinement branch of one minibatch: p->barcode_num_events is rp->barcode_keep_events already; h_idx = the host
-// destination of refine_idx (null: not wanted)
-struct MbRefine {
-    const wdx_refine_params *rp = nullptr;
-    int32_t *h_idx = nullptr;
-};
-
 // Body of the fused host-buffer call.  `B` owns the stream and every workspace that is touched (the context itself
 // for wdx_demux_batch; one of its pipeline slots for wdx_demux_submit[_ex]), `R` is the resident reference set
-// (read-only device memory of the parent context), `svm` the parent's resident model when the SVM tail is asked for.
-// Everything is ENQUEUED on B->stream -- copies in, the kernel chain, copies out to the host destinations (caller arrays
-// or the slot's page-locked block); the caller synchronises.
-static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, const wdx_seg_params *p,
-                               const MbHostOut &H, const ChainTail &tail = ChainTail{}, const MbRefine *rfn = nullptr) {
+// (read-only device memory of the parent context), `tail` names the parent's resident model when a tail is asked for, `pl` is
+// the plan of what comes back (for n_reads, p->barcode_num_events, R.nY and the tail) and `H` where its pieces go.  rp: the
+// refinement branch (p->barcode_num_events is rp->barcode_keep_events already).
+// Everything is ENQUEUED on B->stream -- copies in, the kernel chain, one copy out per travelling piece to its host
+// destination (caller arrays or the slot's page-locked block); the caller synchronises.
+static int demux_batch_enqueue(wdx_ctx *B, const DtwRefs &R, const MbIn &in, const wdx_seg_params *p, const OutPlan &pl,
+                               const MbHost &H, const ChainTail &tail = ChainTail{}, const wdx_refine_params *rp = nullptr) {
     int rc = WDX_SUCCESS;
     hipStream_t s = B->stream;
-    const int64_t n_reads = in.n_reads();
-    const int64_t K = p->barcode_num_events;
-    const size_t db = (size_t)(n_reads * (R.nY > 0 ? R.nY : 1)) * sizeof(float);
-    if ((rc = B->out0.ensure((size_t)(n_reads * K) * 8))) return rc;
-    if ((rc = B->out1.ensure(db))) return rc;
-    if ((rc = B->out2.ensure((size_t)n_reads * 4))) return rc;
-    if ((rc = B->out3.ensure((size_t)n_reads * 4))) return rc;
-    if (H.dwell && (rc = B->mb_dwell.ensure((size_t)(n_reads * K) * 8))) return rc;
-    if (H.stats && (rc = B->mb_stats.ensure((size_t)n_reads * 48))) return rc;
-    const size_t pb = (size_t)n_reads * (tail.svm ? tail.svm->k : tail.boost ? tail.boost->k : 0) * 8;   // (never both)
-    if (pb) {
-        if ((rc = B->mb_prob.ensure(pb))) return rc;
-        if ((rc = B->mb_pred.ensure((size_t)n_reads * 4))) return rc;
-        if ((rc = B->mb_conf.ensure((size_t)n_reads * 8))) return rc;
-    }
-    if ((rc = B->fp_ws.ensure((size_t)fingerprint_workspace_bytes(n_reads)))) return rc;
-    int64_t *d_dwell = H.dwell ? (int64_t *)B->mb_dwell.p : nullptr;
-    double *d_stats = H.stats ? (double *)B->mb_stats.p : nullptr;
-    if (rfn && (rc = B->mb_ridx.ensure((size_t)n_reads * 12))) return rc;
+    // (a refine minibatch records refine_idx on the device whether or not it travels: kept as found)
+    for (int q = 0; q < P_COUNT; ++q)
+        if ((pl.exists[q] || (q == P_RIDX && rp)) && (rc = piece_buffer(B, q)->ensure(pl.bytes[q]))) return rc;
+    if ((rc = B->fp_ws.ensure((size_t)fingerprint_workspace_bytes(pl.n)))) return rc;
+    auto dev = [&](OutPiece q) { return pl.exists[q] ? piece_buffer(B, q)->p : nullptr; };
     FpReads rd;
     if ((rc = in.adc ? fingerprint_adc_rows(B, *in.adc, p, &rd) : fingerprint_float_rows(B, *in.f, p, &rd))) return rc;
-    ChainOut out{FpOut{(double *)B->out0.p, d_dwell, d_stats, (int32_t *)B->out3.p}};
-    out.dist = (float *)B->out1.p, out.call = (int32_t *)B->out2.p;
-    out.prob = (double *)B->mb_prob.p, out.pred = (int32_t *)B->mb_pred.p, out.conf = (double *)B->mb_conf.p;
-    const wdx_refine_params *rp = rfn ? rfn->rp : nullptr;
+    ChainOut out{FpOut{(double *)dev(P_FPT), (int64_t *)dev(P_DWELL), (double *)dev(P_STATS), (int32_t *)dev(P_STATUS)}};
+    out.dist = (float *)dev(P_DIST), out.call = (int32_t *)dev(P_CALL);
+    out.prob = (double *)dev(P_PROB), out.pred = (int32_t *)dev(P_PRED), out.conf = (double *)dev(P_CONF);
     if ((rc = demux_chain(B, R, rd, *p, rp, (int32_t *)B->mb_ridx.p, nullptr, B->fp_ws.p, !rp, tail, out, s))) return rc;
-    if (R.nY > 0) {
-        if (H.call) WDX_HIP_TRY(hipMemcpyAsync(H.call, B->out2.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
-        if (H.dist) WDX_HIP_TRY(hipMemcpyAsync(H.dist, B->out1.p, db, hipMemcpyDeviceToHost, s));
-    }
-    if (pb && (tail.boost || R.nY > 0)) {
-        if (H.prob) WDX_HIP_TRY(hipMemcpyAsync(H.prob, B->mb_prob.p, pb, hipMemcpyDeviceToHost, s));
-        if (H.pred) WDX_HIP_TRY(hipMemcpyAsync(H.pred, B->mb_pred.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
-        if (H.conf) WDX_HIP_TRY(hipMemcpyAsync(H.conf, B->mb_conf.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
-    }
-    WDX_HIP_TRY(hipMemcpyAsync(H.status, B->out3.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
-    if (H.fpt) WDX_HIP_TRY(hipMemcpyAsync(H.fpt, B->out0.p, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
-    if (H.dwell) WDX_HIP_TRY(hipMemcpyAsync(H.dwell, d_dwell, (size_t)(n_reads * K) * 8, hipMemcpyDeviceToHost, s));
-    if (H.stats) WDX_HIP_TRY(hipMemcpyAsync(H.stats, d_stats, (size_t)n_reads * 48, hipMemcpyDeviceToHost, s));
-    if (rfn && rfn->h_idx) WDX_HIP_TRY(hipMemcpyAsync(rfn->h_idx, B->mb_ridx.p, (size_t)n_reads * 12, hipMemcpyDeviceToHost, s));
+    // (the small pieces first, the order these copies have always been enqueued in)
+    constexpr OutPiece kCopyOrder[] = {P_CALL, P_DIST, P_PROB, P_PRED, P_CONF, P_STATUS, P_FPT, P_DWELL, P_STATS, P_RIDX};
+    for (OutPiece q : kCopyOrder)
+        if (pl.travels[q] && H.to[q])
+            WDX_HIP_TRY(hipMemcpyAsync(H.to[q], piece_buffer(B, q)->p, pl.bytes[q], hipMemcpyDeviceToHost, s));
     return WDX_SUCCESS;
 }
 
@@ -432,16 +396,14 @@ static int demux_batch_blocking(wdx_ctx *ctx, const char *who, const MbIn &in, c
     hipStream_t s = ctx->stream;
     if ((rc = use_stream(ctx, s))) return rc;
     StreamDrain drain(s);
-    MbHostOut H;
-    H.status = status;
-    H.call = call;
-    H.dist = dist;
-    H.fpt = fpt;
-    if ((rc = demux_batch_enqueue(ctx, ctx->refs, in, p, H))) return rc;
+    wdx_minibatch_out out{};   // (an output is wanted when its array is given)
+    out.status = status, out.call = call, out.dist = dist, out.fpt = fpt;
+    const OutPlan pl = out_plan(n_reads, p->barcode_num_events, ctx->refs.nY, 0, (fpt ? WDX_WANT_FPT : 0u) | (dist ? WDX_WANT_DIST : 0u),
+                                WDX_LIVE_TAIL_NONE, false, kHaveCall);
+    if ((rc = demux_batch_enqueue(ctx, ctx->refs, in, p, pl, host_arrays(out)))) return rc;
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
-    if (ctx->refs.nY == 0)
-        for (int64_t r = 0; r < n_reads; ++r) call[r] = -1;
+    fill_no_call(pl, call);
     return WDX_SUCCESS;
 }
 
@@ -486,12 +448,11 @@ int wdx_fingerprint_batch_adc(wdx_ctx *ctx, const wdx_minibatch_adc_in *in, cons
     StreamDrain drain(s);
     MbIn mb;
     mb.adc = in;
-    MbHostOut H;
-    H.status = status;
-    H.fpt = fpt;
-    H.dwell = dwell;
-    H.stats = stats;
-    if ((rc = demux_batch_enqueue(ctx, DtwRefs{}, mb, p, H))) return rc;
+    wdx_minibatch_out out{};
+    out.status = status, out.fpt = fpt, out.dwell = dwell, out.stats = stats;
+    const OutPlan pl = out_plan(n_reads, p->barcode_num_events, 0, 0, WDX_WANT_FPT | WDX_WANT_DWELL | WDX_WANT_STATS,
+                                WDX_LIVE_TAIL_NONE, false, 0);
+    if ((rc = demux_batch_enqueue(ctx, DtwRefs{}, mb, p, pl, host_arrays(out)))) return rc;
     WDX_HIP_TRY(hipStreamSynchronize(s));
     drain.done();
     return WDX_SUCCESS;
@@ -645,56 +606,20 @@ static int demux_submit_locked(wdx_ctx *ctx, int32_t slot, const MbIn &in, const
     const DtwRefs none{};
     const DtwRefs &R = no_refs ? none : ctx->refs;
     S->refs = R;  // device pointers of the parent's resident set (read-only; wdx_set_refs drains the slots)
-    const int64_t K = p->barcode_num_events;
     const int64_t k = want_svm ? ctx->svm.dev.k : (want_boost ? ctx->boost.dev.k : 0);
-    const bool want_tail = want_svm || want_boost;
-    // page-locked output block of the slot, 8-byte aligned pieces:
-    // [fpt f64 n*K][dwell i64 n*K][stats f64 n*6][prob f64 n*k][conf f64 n][dist f32 n*nY][call i32 n][status i32 n][pred i32 n]
-    const size_t n = (size_t)n_reads;
-    const size_t bytes[9] = {(want & WDX_WANT_FPT) ? n * K * 8 : 0,
-                             (want & WDX_WANT_DWELL) ? n * K * 8 : 0,
-                             (want & WDX_WANT_STATS) ? n * 48 : 0,
-                             want_tail ? n * (size_t)k * 8 : 0,
-                             want_tail ? n * 8 : 0,
-                             ((want & WDX_WANT_DIST) && R.nY > 0) ? n * (size_t)R.nY * 4 : 0,
-                             n * 4,
-                             n * 4,
-                             want_tail ? n * 4 : 0};
-    size_t off = 0;
-    for (int q = 0; q < 9; ++q) {
-        S->slot_off[q] = off;
-        off += (bytes[q] + 7) / 8 * 8;
-    }
-    S->slot_want_ridx = rp && (want & WDX_WANT_REFINE_IDX);
-    S->slot_off_ridx = off;   // [refine_idx i32 n*3] behind the nine
-    if (S->slot_want_ridx) off += (n * 12 + 7) / 8 * 8;
-    if ((rc = S->pin_out.ensure(off + 8))) return rc;
-    unsigned char *ho = (unsigned char *)S->pin_out.p;
-    S->slot_n = n_reads;
-    S->slot_K = K;
-    S->slot_nY = R.nY;
-    S->slot_k = k;
-    S->slot_want = want & ~(bytes[5] ? 0u : WDX_WANT_DIST);
+    // the slot's page-locked block holds every piece that travels (wdx_stage_plan.h); wdx_demux_wait delivers from it by the
+    // plan kept here
+    const OutPlan pl = out_plan(n_reads, p->barcode_num_events, R.nY, k, want, tail.kind, rp != nullptr, kHaveAll);
+    if ((rc = S->pin_out.ensure(pl.copy_bytes + 8))) return rc;
+    S->slot_plan = pl;
+    S->slot_want = want;
     if (n_reads == 0) {
         S->slot_busy = true;
         return WDX_SUCCESS;
     }
-    MbHostOut H;
-    H.fpt = bytes[0] ? (double *)(ho + S->slot_off[0]) : nullptr;
-    H.dwell = bytes[1] ? (int64_t *)(ho + S->slot_off[1]) : nullptr;
-    H.stats = bytes[2] ? (double *)(ho + S->slot_off[2]) : nullptr;
-    H.prob = bytes[3] ? (double *)(ho + S->slot_off[3]) : nullptr;
-    H.conf = bytes[4] ? (double *)(ho + S->slot_off[4]) : nullptr;
-    H.dist = bytes[5] ? (float *)(ho + S->slot_off[5]) : nullptr;
-    H.call = (int32_t *)(ho + S->slot_off[6]);
-    H.status = (int32_t *)(ho + S->slot_off[7]);
-    H.pred = bytes[8] ? (int32_t *)(ho + S->slot_off[8]) : nullptr;
     StreamDrain drain(S->stream);
     S->dtw_last.family = WDX_DTW_NONE;   // (a submit that dispatches no DTW leaves the parent's record as it was)
-    MbRefine rfn;
-    rfn.rp = rp;
-    rfn.h_idx = S->slot_want_ridx ? (int32_t *)(ho + S->slot_off_ridx) : nullptr;
-    if ((rc = demux_batch_enqueue(S, R, in, p, H, tail, rp ? &rfn : nullptr))) return rc;
+    if ((rc = demux_batch_enqueue(S, R, in, p, pl, host_block(pl, (unsigned char *)S->pin_out.p), tail, rp))) return rc;
     drain.done();  // in flight on purpose: wdx_demux_wait synchronises
     if (S->dtw_last.family != WDX_DTW_NONE) ctx->dtw_last = S->dtw_last;
     S->slot_busy = true;
@@ -729,29 +654,30 @@ static int demux_wait_body(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *
             set_error("demux_wait: another thread is waiting on slot %d", (int)slot);
             return WDX_ERR_INVALID;
         }
-        if (S->slot_n > 0 && (!out->call || !out->status)) {
+        const OutPlan &pl = S->slot_plan;
+        if (pl.n > 0 && (!out->call || !out->status)) {
             set_error("demux_wait: call and status are required");
             return WDX_ERR_INVALID;
         }
         const uint32_t w = S->slot_want;
-        if (S->slot_n > 0 && ((out->fpt && !(w & WDX_WANT_FPT)) || (out->dist && !(w & WDX_WANT_DIST) && S->slot_nY > 0) ||
-                              (out->dwell && !(w & WDX_WANT_DWELL)) || (out->stats && !(w & WDX_WANT_STATS)) ||
-                              ((out->prob || out->pred || out->conf) && !(w & (WDX_WANT_SVM | WDX_WANT_BOOST))))) {
+        if (pl.n > 0 && ((out->fpt && !(w & WDX_WANT_FPT)) || (out->dist && !(w & WDX_WANT_DIST) && pl.nY > 0) ||
+                         (out->dwell && !(w & WDX_WANT_DWELL)) || (out->stats && !(w & WDX_WANT_STATS)) ||
+                         ((out->prob || out->pred || out->conf) && !(w & (WDX_WANT_SVM | WDX_WANT_BOOST))))) {
             set_error("demux_wait: an output that was not requested at wdx_demux_submit");
             return WDX_ERR_INVALID;
         }
-        if (S->slot_n > 0 && refine_idx && !S->slot_want_ridx) {
+        if (pl.n > 0 && refine_idx && !pl.travels[P_RIDX]) {
             set_error("demux_wait: refine_idx was not requested at wdx_demux_submit_refine");
             return WDX_ERR_INVALID;
         }
-        if (S->slot_n > 0 && !refine_idx && S->slot_want_ridx) {
+        if (pl.n > 0 && !refine_idx && pl.travels[P_RIDX]) {
             set_error("demux_wait: the slot holds a refine_idx (WDX_WANT_REFINE_IDX): wdx_demux_wait_refine takes it");
             return WDX_ERR_INVALID;
         }
         S->slot_waiting = true;
     }
     // (the wait itself runs outside the parent's mutex: the other slots can be submitted meanwhile)
-    hipError_t e = S->slot_n > 0 ? hipStreamSynchronize(S->stream) : hipSuccess;
+    hipError_t e = S->slot_plan.n > 0 ? hipStreamSynchronize(S->stream) : hipSuccess;
     std::lock_guard<std::mutex> g(ctx->mu);
     S->slot_waiting = false;
     S->slot_busy = false;
@@ -759,21 +685,9 @@ static int demux_wait_body(wdx_ctx *ctx, int32_t slot, const wdx_minibatch_out *
         set_error("demux_wait: hipStreamSynchronize failed: %s", hipGetErrorString(e));
         return WDX_ERR_HIP;
     }
-    const int64_t n = S->slot_n;
-    if (n == 0) return WDX_SUCCESS;
-    const unsigned char *ho = (const unsigned char *)S->pin_out.p;
-    const size_t nn = (size_t)n;
-    memcpy(out->status, ho + S->slot_off[7], nn * 4);
-    if (S->slot_nY > 0) memcpy(out->call, ho + S->slot_off[6], nn * 4);
-    else for (int64_t r = 0; r < n; ++r) out->call[r] = -1;
-    if (out->fpt) memcpy(out->fpt, ho + S->slot_off[0], nn * S->slot_K * 8);
-    if (out->dwell) memcpy(out->dwell, ho + S->slot_off[1], nn * S->slot_K * 8);
-    if (out->stats) memcpy(out->stats, ho + S->slot_off[2], nn * 48);
-    if (out->prob) memcpy(out->prob, ho + S->slot_off[3], nn * (size_t)S->slot_k * 8);
-    if (out->conf) memcpy(out->conf, ho + S->slot_off[4], nn * 8);
-    if (out->dist && S->slot_nY > 0) memcpy(out->dist, ho + S->slot_off[5], nn * S->slot_nY * 4);
-    if (out->pred) memcpy(out->pred, ho + S->slot_off[8], nn * 4);
-    if (refine_idx) memcpy(refine_idx, ho + S->slot_off_ridx, nn * 12);
+    // the pieces the caller gave an array for (every one of them was asked for: the refusals above); an empty minibatch
+    // writes nothing
+    if (S->slot_plan.n > 0) deliver(S->slot_plan, (const unsigned char *)S->pin_out.p, *out, refine_idx, nullptr);
     return WDX_SUCCESS;
 }
 
