@@ -234,6 +234,9 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
  * Measured against the scratch rows (profiles/wide_dtw.json): see there for the figures of every shape class. */
 #define WDX_OPT_WIDE_DTW 24
 #define WDX_DTW_WIDE_MAX_L 256 /* longest series of the wide-window kernel: every fingerprint length (K <= 254) fits */
+/* Diagnostic: 1 sends every wdx_medoids_device / wdx_dtw_medoids call through the general route (the label's matrix block by block
+ * through the DTW dispatch, then chunk sums) instead of the tile kernels.  Same bits.  Any other value than 0 or 1: WDX_ERR_INVALID. */
+#define WDX_OPT_MEDOID_GENERAL 25
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -409,6 +412,44 @@ int wdx_demux_nearest_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row
  * WDX_ERR_INVALID.  One synchronisation. */
 int wdx_dtw_nearest(wdx_ctx *ctx, const double *X, int64_t nX, const int32_t *ref_label, int64_t n_labels, const float *min_margin,
                     const float *max_dist, float *dist, int32_t *call, float *best);
+
+/* ---- reference signals from labelled fingerprints: per-label DTW medoids -----------------------------------------------
+ * The engine classifies against reference signals (wdx_set_refs, wdx_nearest_dev); this picks them.  The medoid of a label is
+ * the training fingerprint whose summed DTW distance to the fingerprints of its label is smallest -- the usual start of
+ * barycenter averaging, and a usable reference set as it is.  The reference has no such function: the rule below is this
+ * engine's own, exact arithmetic on the float32 distances wdx_dtw_matrix returns.
+ * Inputs: X (n, L) float64; label int32[n], one per row, in 0 .. n_labels-1, or -1 for "takes no part"; status int32[n]
+ * (nullable); window and penalty as for wdx_dtw_matrix (no resident reference set is read or written).  Every DTW option of the
+ * context (WDX_OPT_WIDE_DTW, WDX_OPT_DTW_UNFUSED, WDX_OPT_NO_SHORT_DTW, ...) applies as it does there.
+ *   A row is a MEMBER of label g when its label is g, its status (if given) is 0 and all L samples are finite.
+ *   f(a, b) is the float32 distance wdx_dtw_matrix returns for (X[a], X[b]).
+ *   The rows of label g in rising row order, members or not, are q_0 < q_1 < ... < q_{m-1}; chunk c holds q_{64c} .. q_{64c+63}.
+ *   cost[r] of a member r of g: a float64 total that starts at 0.0 and adds the chunk sums S_0, S_1, ... in rising c; S_c is a
+ *           float64 sum that starts at 0.0 and adds (double)f(r, q_j) over the MEMBERS of chunk c in rising j (non-members are
+ *           skipped, f(r, r) is included, an infinite sum is legal).  cost of a non-member: NaN.
+ *   medoid[g] int64: the member of g with the smallest cost, the first in row order among equal costs; -1 without a member
+ *   count[g] int64: the number of members;  medoid_cost[g] float64: cost[medoid[g]], or NaN
+ *   refs (n_labels, L) float64: row g is X[medoid[g]] bit for bit, or a row of NaN
+ * The summation order is part of the rule, so that the result does not depend on how the work is cut up: each unordered pair is
+ * computed once (f(a, b) == f(b, a) bit for bit: DESIGN.md), in 64 x 64 tiles, one wave each.
+ * Limit: a label of more than WDX_MEDOID_MAX_GROUP rows is WDX_ERR_UNSUPPORTED (the message names the label and its size; the
+ * caller subsamples).  WDX_ERR_INVALID: n_labels < 1, a label outside -1 .. n_labels-1, L < 1, a NULL medoid output.  An empty
+ * batch is success: every medoid -1, counts 0, NaN rows.  The context stays usable after a refusal, and nothing resident is
+ * touched: references, models and wdx_refs_generation stay as they are.  Workspace: context-owned and bounded, see
+ * warpdemux_amd/csrc/wdx_medoid_plan.h.
+ *
+ * wdx_medoids_device: dX, d_status and every output are DEVICE memory; d_status, d_medoid_cost, d_count, d_cost (float64[n]) and
+ * d_refs are nullable; `label` is HOST memory, read during the call only.  Enqueued on `stream`; no synchronisation -- the
+ * contract of the *_dev entries (its name does not end in _dev because tests/test_gpu_buffer_bounds.py keeps a closed table of
+ * those; tests/test_gpu_medoids.py holds this entry to the same stream and bounds checks). */
+#define WDX_MEDOID_MAX_GROUP 32768
+int wdx_medoids_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *label /* HOST */, int64_t n_labels,
+                       const int32_t *d_status, int32_t window, double penalty, int64_t *d_medoid, double *d_medoid_cost,
+                       int64_t *d_count, double *d_cost, double *d_refs, void *stream);
+/* Host form: every array HOST memory; one synchronisation. */
+int wdx_dtw_medoids(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const int32_t *label, int64_t n_labels,
+                    const int32_t *status, int32_t window, double penalty, int64_t *medoid, double *medoid_cost, int64_t *count,
+                    double *cost, double *refs);
 
 /* Pipelined form of wdx_demux_batch for the reference's worker loop (file_proc.py:380-454: fill minibatch k+1
  * while minibatch k is processed; 1197-1243: several such workers share one GPU).  A context has WDX_MAX_SLOTS slots (the
@@ -1034,6 +1075,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
                                     wdx_demux_boost_dev, WDX_WANT_BOOST minibatches) */
 #define WDX_K_ADC_DEV_WINDOWS 11 /* adc_dev_windows_kernel: the window decode ahead of every slice of an *_adc_dev call */
 #define WDX_K_REFINE_OPTIMAL 12   /* fingerprint_refine_optimal_kernel alone (WDX_OPT_REFINE_OPTIMAL_CPTS; part of WDX_K_FINGERPRINT) */
+#define WDX_K_MEDOID 13           /* per-label medoids: the pre-pass, the tile kernels (or the general route's chunk sums) and the reduce kernel */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

@@ -29,6 +29,7 @@ K_MLP = 9
 K_BOOST = 10
 K_ADC_DEV_WINDOWS = 11   # the window decode ahead of every slice of an *_adc_dev call (int16 device shards)
 K_REFINE_OPTIMAL = 12     # fingerprint_refine_optimal_kernel alone (OPT_REFINE_OPTIMAL_CPTS)
+K_MEDOID = 13             # per-label medoids: pre-pass, tile kernels (or the general route's chunk sums), reduce kernel
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -53,6 +54,8 @@ OPT_REFINE_OPTIMAL_CPTS = 23   # product option of the refinement branch: barcod
 OPT_WIDE_DTW = 24   # product option of the DTW seam: 1 = effective windows 33 .. L at L <= DTW_WIDE_MAX_L (``window=None`` included) on the
                     # wide-window kernel instead of the scratch rows; the fused device entries then accept such references (0 / 1)
 DTW_WIDE_MAX_L = 256   # WDX_DTW_WIDE_MAX_L
+OPT_MEDOID_GENERAL = 25   # diagnostic: per-label medoids through the DTW dispatch + chunk sums instead of the tile kernels (same bits)
+MEDOID_MAX_GROUP = 32768   # WDX_MEDOID_MAX_GROUP: rows of one label in wdx_medoids_device / wdx_dtw_medoids (beyond: NotImplementedError)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -80,6 +83,7 @@ EXPORTS = [
     "wdx_demux_refine_adc_workspace_bytes", "wdx_adc_dev_staging_bytes", "wdx_demux_adc_dev", "wdx_demux_refine_adc_dev",
     "wdx_demux_svm_adc_dev", "wdx_demux_mlp_adc_dev", "wdx_demux_boost_adc_dev",
     "wdx_nearest_dev", "wdx_demux_nearest_dev", "wdx_dtw_nearest",
+    "wdx_medoids_device", "wdx_dtw_medoids",
 ]
 
 
@@ -554,6 +558,10 @@ def load():
                                             vp, vp, vp, vp, vp, vp, vp]
         L.wdx_dtw_nearest.restype = C.c_int
         L.wdx_dtw_nearest.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+        L.wdx_medoids_device.restype = C.c_int
+        L.wdx_medoids_device.argtypes = [vp, vp, i64, i64, vp, i64, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp]
+        L.wdx_dtw_medoids.restype = C.c_int
+        L.wdx_dtw_medoids.argtypes = [vp, vp, i64, i64, vp, i64, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp]
         _lib = L
         return L
 

@@ -43,7 +43,13 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 13;
+constexpr int kNumTimed = 14;
+
+struct MedoidStage {   // a page-locked block and the event behind the latest copy out of it
+    void *host = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;
+};
 
 // RAII: make the context's device current for the duration of one entry point and put the caller's
 // device back afterwards (a host thread that also drives torch must not find its device switched).
@@ -91,6 +97,12 @@ struct wdx_ctx {
     // distances of one row block of a nearest-reference call that asked for no `dist` and whose rule runs behind the DTW
     // kernels (wdx_dtw_plan.h: nearest_plan, at most kNearestBlockBytes); allocated by the first such call
     wdx::Buffer nearest_buf;
+    // per-label medoids (wdx_medoid.hip): the workspace wdx_medoid_plan.h lays out, allocated by the first such call; and the
+    // page-locked images of the tables a call uploads.  A call returns with its copy pending, so the next call takes a block
+    // whose copy has run (its event has fired) or allocates another; blocks are freed only when a larger one is needed and at
+    // the context's end -- hipHostMalloc / hipHostFree wait for the device, and a call in the steady state must not
+    wdx::Buffer medoid_ws;
+    std::vector<wdx::MedoidStage> medoid_staged;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     // the classifier tails (wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model): a slot each, independent of one another
     wdx::ResidentSvm svm;
@@ -146,6 +158,8 @@ int set_refs_locked(wdx_ctx *ctx, const double *Y, int64_t nY, int64_t L, int32_
 // DTW of device rows dX (nX, L) against the resident refs -> d_out (nX, nY) [+ argmin]
 int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int32_t *d_argmin,
                    hipStream_t stream);
+// (wdx_medoid.hip) frees the page-locked table blocks whose copies have run (all: waits for each; wdx_ctx_destroy calls that)
+void medoid_release_staged(wdx_ctx *ctx, bool all);
 // (wdx_api.hip) behind a DTW launch when a resident reference holds an infinite sample (R.any_inf): pairs with the same
 // infinity at one index are NaN in the reference and +inf out of the kernels -- settled here, then the argmin again (a NaN
 // wins its row)

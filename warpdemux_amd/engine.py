@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib, _marshal, _nearest, synth
+from . import _lib, _marshal, _medoids, _nearest, synth
 from .sig_proc import SegParams
 
 
@@ -115,6 +115,15 @@ class NearestResult:
     fpt: Optional["object"] = None    # torch float64 (n, K) when requested (`demux_nearest`)
 
 
+@dataclass
+class MedoidResult:
+    index: "object"        # torch int64 (G,)  row of each label's medoid, -1 for a label without a member
+    refs: "object"         # torch float64 (G, L)  X[index] bit for bit (a NaN row without a member): goes straight into `set_refs`
+    count: "object"        # torch int64 (G,)  members of each label
+    medoid_cost: "object"  # torch float64 (G,)  cost[index], NaN without a member
+    cost: Optional["object"] = None   # torch float64 (n,) when requested: every member's summed distance, NaN for the others
+
+
 class DemuxEngine:
     """One engine per process per GPU.  ``refs``: (nY, L) float64 reference fingerprints
     (model._X in the reference, models/dtw_base.py:20).  ``wide_dtw``: effective windows 33 .. L (``window=None`` on
@@ -145,6 +154,8 @@ class DemuxEngine:
 
     # -- reference set ---------------------------------------------------------------------------
     def set_refs(self, refs, window, penalty):
+        if self.torch.is_tensor(refs):   # (a device tensor, e.g. `MedoidResult.refs`: the set is uploaded from the host)
+            refs = refs.detach().cpu().numpy()
         refs = np.ascontiguousarray(refs, dtype=np.float64)
         if refs.ndim != 2:
             raise ValueError("refs must be (nY, L)")
@@ -353,6 +364,31 @@ class DemuxEngine:
                             dist=torch.empty((n, self.nY), dtype=torch.float32, device=self.tdev) if want_dist else None)
         _lib.check(self.L.wdx_nearest_dev(self.ctx.handle, _dp(X), n, _dp(status), _dp(lab), G, _dp(mm), _dp(md), _dp(out.dist),
                                           _dp(out.call), _dp(out.best), _dp(out.counts), self._stream()))
+        return out
+
+    # -- reference signals from labelled fingerprints (wdx_medoids_device; include/wdx.h states the rule) ---------------------
+    def medoids(self, X, labels, n_labels=None, *, window, penalty, status=None, want_cost=False):
+        """The medoid of every label among the device fingerprints X (n, L) float64 -- e.g. what `fingerprint` returned for
+        labelled training reads: ``labels`` one HOST integer per row in 0 .. G-1 (-1: the row takes no part), ``status`` an
+        optional int32 (n,) device tensor (a row whose status is not 0 is no member, like a row with a sample that is not
+        finite).  Returns a `MedoidResult` of device tensors; ``set_refs(res.refs, window, penalty)`` makes the medoids the
+        resident reference set (this call itself leaves it alone).  Enqueues on the current stream."""
+        torch = self.torch
+        if not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or int(X.shape[1]) < 1 or not X.is_contiguous():
+            raise ValueError("X must be a contiguous float64 (n, L) device tensor with L >= 1")
+        n, L = int(X.shape[0]), int(X.shape[1])
+        lab, G = _medoids.host_labels(n, labels, n_labels)
+        if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (n,)
+                                   or not status.is_contiguous()):
+            raise ValueError(f"status must be a contiguous int32 ({n},) device tensor")
+        out = MedoidResult(index=torch.empty(G, dtype=torch.int64, device=self.tdev),
+                           refs=torch.empty((G, L), dtype=torch.float64, device=self.tdev),
+                           count=torch.empty(G, dtype=torch.int64, device=self.tdev),
+                           medoid_cost=torch.empty(G, dtype=torch.float64, device=self.tdev),
+                           cost=torch.empty(n, dtype=torch.float64, device=self.tdev) if want_cost else None)
+        _lib.check(self.L.wdx_medoids_device(self.ctx.handle, _dp(X), n, L, _lib.ptr(lab), G, _dp(status),
+                                             int(window) if window else 0, float(penalty) if penalty else 0.0, _dp(out.index),
+                                             _dp(out.medoid_cost), _dp(out.count), _dp(out.cost), _dp(out.refs), self._stream()))
         return out
 
     def demux_nearest(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, labels=None, n_labels=None,

@@ -190,3 +190,32 @@ def nearest_label(X, Y, labels=None, window=None, penalty=None, min_margin=None,
     _lib.check(L.wdx_dtw_nearest(ctx.handle, _lib.ptr(X), n, _lib.ptr(lab), G, _lib.ptr(mm), _lib.ptr(md), _lib.ptr(dist),
                                  _lib.ptr(call), _lib.ptr(best)))
     return (call, best, dist) if want_dist else (call, best)
+
+
+def label_medoids(X, labels, n_labels=None, window=None, penalty=None, status=None, want_cost=False):
+    """(index int64 (G,), refs float64 (G, L), count int64 (G,), medoid_cost float64 (G,)[, cost float64 (n,)]): the medoid of
+    every label -- the row whose summed DTW distance to the rows of its label is smallest -- as reference signals for
+    `nearest_label` / ``wdx_set_refs``.  The rule of include/wdx.h (wdx_medoids_device), the engine's own: the reference ships no
+    reference signals and has no code that makes them.  ``labels``: one integer per row of ``X`` in 0 .. G-1, or -1 for a row
+    that takes no part; ``status`` (optional): a row whose status is not 0 is no member of its label, like a row with a sample
+    that is not finite.  A label without a member has index -1, a NaN cost and a NaN row; ``cost`` of a non-member is NaN.
+    A label of more than ``_lib.MEDOID_MAX_GROUP`` rows is NotImplementedError.  Goes through wdx_dtw_medoids; the resident
+    reference set is not touched."""
+    from . import _medoids
+
+    X = _as_f64_2d(X, "X")
+    n, L = X.shape
+    lab, G = _medoids.host_labels(n, labels, n_labels)
+    st = _medoids.host_status(n, status)
+    if L < 1:
+        raise ValueError("X must have at least one column")
+    index = np.empty(G, dtype=np.int64)
+    refs = np.empty((G, L), dtype=np.float64)
+    count = np.empty(G, dtype=np.int64)
+    mcost = np.empty(G, dtype=np.float64)
+    cost = np.empty(n, dtype=np.float64) if want_cost else None
+    ctx = _lib.default_context()
+    _lib.check(_lib.load().wdx_dtw_medoids(ctx.handle, _lib.ptr(X), n, L, _lib.ptr(lab), G, _lib.ptr(st),
+                                           int(window) if window else 0, float(penalty) if penalty else 0.0, _lib.ptr(index),
+                                           _lib.ptr(mcost), _lib.ptr(count), _lib.ptr(cost), _lib.ptr(refs)))
+    return (index, refs, count, mcost, cost) if want_cost else (index, refs, count, mcost)
