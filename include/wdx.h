@@ -237,6 +237,10 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
 /* Diagnostic: 1 sends every wdx_medoids_device / wdx_dtw_medoids call through the general route (the label's matrix block by block
  * through the DTW dispatch, then chunk sums) instead of the tile kernels.  Same bits.  Any other value than 0 or 1: WDX_ERR_INVALID. */
 #define WDX_OPT_MEDOID_GENERAL 25
+/* Diagnostic: 1 sends every wdx_self_matrix_device / wdx_dtw_self_matrix call through the general route (row blocks through the
+ * DTW dispatch straight into the matrix, then a mask kernel for the non-members) instead of the tile kernels.  Same bits.  Any
+ * other value than 0 or 1: WDX_ERR_INVALID. */
+#define WDX_OPT_SELF_MATRIX_GENERAL 26
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -450,6 +454,35 @@ int wdx_medoids_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, con
 int wdx_dtw_medoids(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const int32_t *label, int64_t n_labels,
                     const int32_t *status, int32_t window, double penalty, int64_t *medoid, double *medoid_cost, int64_t *count,
                     double *cost, double *refs);
+
+/* ---- training matrix of a DTW kernel machine: the symmetric DTW self-distance matrix --------------------------------------
+ * The (n, n) matrix of the rows of X against themselves, which a DTW_SVM is fitted on (the reference computes it with
+ * distance_matrix_to(X, X), every unordered pair twice).  Each unordered pair is computed once, in 64 x 64 tiles of one wave
+ * each, and written to both of its places: f(a, b) == f(b, a) bit for bit.
+ * Inputs are those of the medoid entries: X (n, L) float64; status int32[n] (nullable); window and penalty as for
+ * wdx_dtw_matrix.
+ *   A row is a MEMBER when its status (if given) is 0 and all L samples are finite.
+ *   out[a * ld + b] is float32, 0 <= a, b < n, ld >= n.
+ *   Where a and b are both members it is f(a, b), the float32 wdx_dtw_matrix returns for (X[a], X[b]).
+ *   Otherwise it is the quiet NaN 0x7fc00000.
+ *   Columns n .. ld-1 of every row are not written.
+ * Every DTW option of the context applies as it does to wdx_dtw_matrix (WDX_OPT_WIDE_DTW, WDX_OPT_DTW_UNFUSED,
+ * WDX_OPT_NO_SHORT_DTW).  No resident reference set, no model and no wdx_refs_generation is read or changed.
+ * Limit: n > WDX_SELF_MATRIX_MAX_ROWS (1 024 chunks of 64 rows, a 16 GiB matrix) is WDX_ERR_UNSUPPORTED (the message names n).
+ * WDX_ERR_INVALID: L < 1, n < 0, ld < n, a NULL out with n > 0.  n == 0 is success and writes nothing.  After a refusal the
+ * context stays usable and nothing has been written.  Workspace: context-owned, grow-only and bounded, see
+ * warpdemux_amd/csrc/wdx_self_plan.h.
+ *
+ * wdx_self_matrix_device: dX, d_status and d_out are DEVICE memory.  Enqueued on `stream`; no synchronisation -- the contract of
+ * the *_dev entries (its name does not end in _dev for the reason wdx_medoids_device gives; tests/test_gpu_self_matrix.py holds
+ * this entry to the same stream and bounds checks). */
+#define WDX_SELF_MATRIX_MAX_ROWS 65536
+int wdx_self_matrix_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *d_status, int32_t window,
+                           double penalty, float *d_out, int64_t ld, void *stream);
+/* Host form: every array HOST memory; one synchronisation.  The device matrix is allocated for the call and freed before it
+ * returns (a context never keeps 16 GiB). */
+int wdx_dtw_self_matrix(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const int32_t *status, int32_t window,
+                        double penalty, float *out, int64_t ld);
 
 /* Pipelined form of wdx_demux_batch for the reference's worker loop (file_proc.py:380-454: fill minibatch k+1
  * while minibatch k is processed; 1197-1243: several such workers share one GPU).  A context has WDX_MAX_SLOTS slots (the

@@ -56,6 +56,9 @@ OPT_WIDE_DTW = 24   # product option of the DTW seam: 1 = effective windows 33 .
 DTW_WIDE_MAX_L = 256   # WDX_DTW_WIDE_MAX_L
 OPT_MEDOID_GENERAL = 25   # diagnostic: per-label medoids through the DTW dispatch + chunk sums instead of the tile kernels (same bits)
 MEDOID_MAX_GROUP = 32768   # WDX_MEDOID_MAX_GROUP: rows of one label in wdx_medoids_device / wdx_dtw_medoids (beyond: NotImplementedError)
+SVM_MAX_CLASSES = 16   # classes of a resident DTW_SVM (wdx_svm_set_model refuses more)
+OPT_SELF_MATRIX_GENERAL = 26   # diagnostic: the self-distance matrix through the DTW dispatch + a mask kernel instead of the tile kernels (same bits)
+SELF_MATRIX_MAX_ROWS = 65536   # WDX_SELF_MATRIX_MAX_ROWS: rows of wdx_self_matrix_device / wdx_dtw_self_matrix (beyond: NotImplementedError)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -84,6 +87,7 @@ EXPORTS = [
     "wdx_demux_svm_adc_dev", "wdx_demux_mlp_adc_dev", "wdx_demux_boost_adc_dev",
     "wdx_nearest_dev", "wdx_demux_nearest_dev", "wdx_dtw_nearest",
     "wdx_medoids_device", "wdx_dtw_medoids",
+    "wdx_self_matrix_device", "wdx_dtw_self_matrix",
 ]
 
 
@@ -562,6 +566,10 @@ def load():
         L.wdx_medoids_device.argtypes = [vp, vp, i64, i64, vp, i64, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp]
         L.wdx_dtw_medoids.restype = C.c_int
         L.wdx_dtw_medoids.argtypes = [vp, vp, i64, i64, vp, i64, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp]
+        L.wdx_self_matrix_device.restype = C.c_int
+        L.wdx_self_matrix_device.argtypes = [vp, vp, i64, i64, vp, C.c_int32, C.c_double, vp, i64, vp]
+        L.wdx_dtw_self_matrix.restype = C.c_int
+        L.wdx_dtw_self_matrix.argtypes = [vp, vp, i64, i64, vp, C.c_int32, C.c_double, vp, i64]
         _lib = L
         return L
 

@@ -102,6 +102,8 @@ struct wdx_ctx {
     // whose copy has run (its event has fired) or allocates another; blocks are freed only when a larger one is needed and at
     // the context's end -- hipHostMalloc / hipHostFree wait for the device, and a call in the steady state must not
     wdx::Buffer medoid_ws;
+    // the self-distance matrix (wdx_dtw_self.hip): the workspace wdx_self_plan.h lays out, allocated by the first such call
+    wdx::Buffer self_ws;
     std::vector<wdx::MedoidStage> medoid_staged;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     // the classifier tails (wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model): a slot each, independent of one another

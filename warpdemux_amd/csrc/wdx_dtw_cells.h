@@ -1,6 +1,7 @@
 // The cell machinery of the lane-per-pair DTW kernels (wdx_dtw.hip: dtw_band_kernel, dtw_short_kernel, dtw_short_svm_kernel;
-// wdx_medoid.hip: medoid_tile_kernel): the band row, the unrolled short rows, the fused cell and the settle decision.  Device
-// code only; every unit that includes it is compiled with -ffp-contract=off.
+// wdx_dtw_tile.h for the one-wave-per-tile kernels of wdx_medoid.hip and wdx_dtw_self.hip): the band row, the unrolled short
+// rows, the fused cell and the settle decision.  Device code only; every unit that includes it is compiled with
+// -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

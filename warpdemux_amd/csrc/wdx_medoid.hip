@@ -14,7 +14,7 @@
 // General route: the label's matrix block by block through dtw_plan / run_dtw_plan, then chunk sums of each row's own entries.
 // Reduce: per label, the partial sums of a row in rising chunk order -> cost, the first minimum -> medoid, and the gathers.
 #include "wdx_ctx.h"
-#include "wdx_dtw_cells.h"
+#include "wdx_dtw_tile.h"
 #include "wdx_medoid_plan.h"
 
 #include <math.h>
@@ -23,32 +23,7 @@
 
 namespace wdx {
 
-// ---- pre-pass: gather into the padded layout, member flags ----------------------------------------------------------------
-// One wave per padded row p: X[order[p]] -> dense[p] (L samples) and padded[p] (Lpad samples, zero halo); a padding row
-// (order -1) is zeros.  member[p] = a caller's row, status 0 (if given), all L samples finite.
-__global__ __launch_bounds__(256) void medoid_gather_kernel(const double *__restrict__ X, const int32_t *__restrict__ status,
-                                                            const int32_t *__restrict__ order, int64_t rows, int L, int64_t Lpad,
-                                                            int halo, double *__restrict__ dense, double *__restrict__ padded,
-                                                            uint8_t *__restrict__ member) {
-    const int64_t p = (int64_t)blockIdx.x * 4 + threadIdx.x / 64;
-    const int lane = threadIdx.x & 63;
-    if (p >= rows) return;
-    const int64_t src = order[p];
-    bool bad = false;
-    for (int64_t c = lane; c < Lpad; c += 64) {
-        const int64_t s = c - halo;
-        const bool in = s >= 0 && s < L;
-        const double v = (in && src >= 0) ? X[src * L + s] : 0.0;
-        padded[p * Lpad + c] = v;
-        if (in) {
-            dense[p * L + s] = v;
-            bad |= !(v - v == 0.0);   // NaN or an infinity
-        }
-    }
-    const unsigned long long any_bad = __ballot(bad);
-    if (lane == 0) member[p] = (src >= 0 && !any_bad && (!status || status[src] == 0)) ? 1 : 0;
-}
-
+// (the pre-pass, tile_gather_kernel, and the pair on the register band live in wdx_dtw_tile.h: the self-matrix kernels share them)
 __global__ __launch_bounds__(256) void medoid_fill_nan_kernel(double *__restrict__ cost, int64_t n) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n) cost[r] = __builtin_nan("");
@@ -69,96 +44,6 @@ struct MedoidTileArgs {
     double p2;
     int unfused;             // Knobs::dtw_unfused
 };
-
-// dtw_band_kernel's pair (row-major lanes): the accumulated cost D[L][L] on fused or on the reference's cells
-template <int W, bool EXACT_W, bool FMA>
-__device__ __forceinline__ double medoid_band_cost(const double *__restrict__ xp, const double *__restrict__ y, const int L,
-                                                   const int w, const double p2) {
-    constexpr int B = 2 * W - 1;
-    double r[B];
-#pragma unroll
-    for (int c = 0; c < B; ++c) r[c] = WDX_INF;
-    r[W - 1] = 0.0;
-    double xn = xp[0];
-    int i = 0;
-    if (EXACT_W && L >= 2 * (W - 1)) {
-        dtw_head_rows<W, FMA>(r, xp, 1, y, p2, std::make_integer_sequence<int, W - 1>{});
-        i = W - 1;
-        constexpr int CH = 8;
-        const int body_end = L - W + 1;
-        if (i + CH <= body_end) {
-            double xc[CH];
-#pragma unroll
-            for (int k = 0; k < CH; ++k) xc[k] = xp[i + k];
-            for (; i + CH <= body_end; i += CH) {
-                double xq[CH];
-                const bool more = i + 2 * CH <= body_end;  // wave-uniform
-                if (more) {
-#pragma unroll
-                    for (int k = 0; k < CH; ++k) xq[k] = xp[i + CH + k];
-                }
-#pragma unroll
-                for (int k = 0; k < CH; ++k) dtw_row<W, false, FMA>(r, xc[k], y + i + k, p2, 0, 0, 0);
-                if (more) {
-#pragma unroll
-                    for (int k = 0; k < CH; ++k) xc[k] = xq[k];
-                }
-            }
-        }
-        if (i < body_end) xn = xp[i];
-        for (; i < body_end; ++i) {
-            const double x = xn;
-            xn = xp[i + 1];  // i + 1 <= L - W + 1 < L
-            dtw_row<W, false, FMA>(r, x, y + i, p2, 0, 0, 0);
-        }
-        dtw_tail_rows<W, FMA>(r, xp, 1, y, p2, L - W + 1, std::make_integer_sequence<int, W - 1>{});
-    } else if (EXACT_W) {
-        const int head_end = min(W - 1, L);
-        const int body_end = max(head_end, L - W + 1);
-        for (; i < head_end; ++i) {
-            const double x = xn;
-            if (i + 1 < L) xn = xp[i + 1];
-            dtw_row<W, true, FMA>(r, x, y + i, p2, i - (W - 1), 0, L - 1);
-        }
-        for (; i < body_end; ++i) {
-            const double x = xn;
-            if (i + 1 < L) xn = xp[i + 1];
-            dtw_row<W, false, FMA>(r, x, y + i, p2, 0, 0, 0);
-        }
-        for (; i < L; ++i) {
-            const double x = xn;
-            if (i + 1 < L) xn = xp[i + 1];
-            dtw_row<W, true, FMA>(r, x, y + i, p2, i - (W - 1), 0, L - 1);
-        }
-    } else {
-        for (; i < L; ++i) {
-            const double x = xn;
-            if (i + 1 < L) xn = xp[i + 1];
-            dtw_row<W, true, FMA>(r, x, y + i, p2, i - (W - 1), max(0, i - (w - 1)), min(L - 1, i + (w - 1)));
-        }
-    }
-    return r[W - 1];
-}
-
-// One pair as the band kernels settle it; `use`: the lane's value will be read (only those lanes ask for the second pass)
-template <int W, bool EXACT_W>
-__device__ __forceinline__ float medoid_band_pair(const double *__restrict__ xp, const double *__restrict__ y, const int L, const int w,
-                                                  const double p2, const bool use, const double delta, const int unfused) {
-    double res = 0.0;
-    bool redo = unfused == 1;   // (uniform)
-    if (!redo) {
-        const double Dv = medoid_band_cost<W, EXACT_W, true>(xp, y, L, w, p2);
-        res = sqrt(Dv);
-        redo = dtw_redo(unfused, use && dtw_unsettled(Dv, res, (float)res, delta));
-    }
-    if (redo) res = sqrt(medoid_band_cost<W, EXACT_W, false>(xp, y, L, w, p2));
-    return (float)res;
-}
-
-// The workgroup IS one wave: its LDS operations execute in program order, so a lane reads what another lane wrote by an earlier
-// instruction without a barrier.  What is needed is that the compiler keeps that order (it does: the addresses may alias) and
-// schedules nothing across.
-__device__ __forceinline__ void medoid_wave_sync() { __builtin_amdgcn_wave_barrier(); }
 
 // SHORT: the unrolled 25-point / window-15 shape (W, EXACT_W ignored); DIAG: tile (I, I), the whole 64 x 64 hand-over in LDS.
 // (held to the three waves per SIMD the band kernels run at, like their NEAREST twins)
@@ -432,7 +317,7 @@ static int medoids_locked(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, 
     const int w_eff = (int)dtw_effective_window(L, window);
     Timed t(ctx, WDX_K_MEDOID, s);
     if (P.rows_padded)
-        hipLaunchKernelGGL(medoid_gather_kernel, dim3((unsigned)((P.rows_padded + 3) / 4)), dim3(256), 0, s, dX, d_status, order,
+        hipLaunchKernelGGL(tile_gather_kernel<false>, dim3((unsigned)((P.rows_padded + 3) / 4)), dim3(256), 0, s, dX, d_status, order, n,
                            P.rows_padded, (int)L, P.Lpad, kDtwHalo, dense, padded, member);
     if (d_cost && n > 0) hipLaunchKernelGGL(medoid_fill_nan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_cost, n);
     WDX_HIP_TRY(hipGetLastError());

@@ -391,6 +391,35 @@ class DemuxEngine:
                                              _dp(out.medoid_cost), _dp(out.count), _dp(out.cost), _dp(out.refs), self._stream()))
         return out
 
+    # -- the training matrix of a DTW kernel machine (wdx_self_matrix_device; include/wdx.h states the rule) -------------------
+    def self_distances(self, X, window=None, penalty=None, status=None, out=None):
+        """float32 (n, n) device tensor: the DTW distances of the device fingerprints X (n, L) float64 against themselves, each
+        unordered pair computed once.  ``status``: an optional int32 (n,) device tensor; a row whose status is not 0, like a
+        row with a sample that is not finite, is no member, and its row and column are NaN.  ``out``: a float32 device tensor
+        of n rows and at least n columns whose columns are contiguous -- a wider tensor (or a view of one) keeps its columns
+        from n on, its row stride is the matrix's leading dimension.  ``window`` / ``penalty`` as for `distance_matrix_to`
+        (``None``: unbanded / no penalty); the resident reference set is neither read nor changed.  Enqueues on the current
+        stream."""
+        torch = self.torch
+        if not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or int(X.shape[1]) < 1 or not X.is_contiguous():
+            raise ValueError("X must be a contiguous float64 (n, L) device tensor with L >= 1")
+        n, L = int(X.shape[0]), int(X.shape[1])
+        if n > _lib.SELF_MATRIX_MAX_ROWS:
+            raise NotImplementedError(f"self matrix: n = {n} rows, more than WDX_SELF_MATRIX_MAX_ROWS = {_lib.SELF_MATRIX_MAX_ROWS}: "
+                                      "subsample them")
+        if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (n,)
+                                   or not status.is_contiguous()):
+            raise ValueError(f"status must be a contiguous int32 ({n},) device tensor")
+        if out is None:
+            out = torch.empty((n, n), dtype=torch.float32, device=self.tdev)
+        elif (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or int(out.shape[0]) != n or int(out.shape[1]) < n
+              or (n > 0 and int(out.shape[1]) > 1 and out.stride(1) != 1) or (n > 1 and out.stride(0) < int(out.shape[1]))):
+            raise ValueError(f"out must be a float32 device tensor of {n} rows and at least {n} contiguous columns")
+        ld = int(out.stride(0)) if n > 1 else max(n, int(out.shape[1]))
+        _lib.check(self.L.wdx_self_matrix_device(self.ctx.handle, _dp(X), n, L, _dp(status), int(window) if window else 0,
+                                                 float(penalty) if penalty else 0.0, _dp(out), ld, self._stream()))
+        return out[:, :n]
+
     def demux_nearest(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, labels=None, n_labels=None,
                       min_margin=None, max_dist=None, want_dist=False, want_fpt=False, counts=None):
         """`demux` with the nearest-reference rule in the argmin's place (wdx_demux_nearest_dev): raw float32 rows ->

@@ -110,18 +110,86 @@ class DTW_SVM(_ResidentDTWModel):
         self._label_arr = np.array([self.label_mapper[i] for i in range(self.n_classes)], dtype=np.int32)
 
     @classmethod
-    def from_reference(cls, model, device: Optional[int] = None) -> "DTW_SVM":
-        """From a reference ``DTW_SVM`` instance (a loaded model_files/*.joblib)."""
-        svc = model.model
+    def from_sklearn(cls, svc, _X, label_mapper, thresholds, window, penalty, gamma=1.0, pwr_dist=1,
+                     block_size: Optional[int] = None, device: Optional[int] = None) -> "DTW_SVM":
+        """From a fitted ``SVC(kernel="precomputed", probability=True)`` and the training fingerprints ``_X`` its kernel
+        matrix was computed on: the estimator is only read for libsvm's parameters (``_n_support``, ``support_``,
+        ``_dual_coef_``, ``-_intercept_``, ``_probA``, ``_probB``)."""
         if getattr(svc, "kernel", None) != "precomputed" or not getattr(svc, "probability", False):
             raise ValueError("expected SVC(kernel='precomputed', probability=True)")
         return cls(
-            _X=model._X, n_support=svc._n_support, support=svc.support_, dual_coef=svc._dual_coef_,
+            _X=_X, n_support=svc._n_support, support=svc.support_, dual_coef=svc._dual_coef_,
             rho=-np.asarray(svc._intercept_, dtype=np.float64), probA=svc._probA, probB=svc._probB,
-            label_mapper=model.label_mapper, thresholds=model.thresholds, window=model.window,
-            penalty=model.penalty, gamma=model.gamma, pwr_dist=model.pwr_dist, block_size=model.block_size,
-            device=device,
+            label_mapper=label_mapper, thresholds=thresholds, window=window, penalty=penalty, gamma=gamma,
+            pwr_dist=pwr_dist, block_size=block_size, device=device,
         )
+
+    @classmethod
+    def from_reference(cls, model, device: Optional[int] = None) -> "DTW_SVM":
+        """From a reference ``DTW_SVM`` instance (a loaded model_files/*.joblib)."""
+        return cls.from_sklearn(model.model, model._X, model.label_mapper, model.thresholds, model.window, model.penalty,
+                                gamma=model.gamma, pwr_dist=model.pwr_dist, block_size=model.block_size, device=device)
+
+    @classmethod
+    def fit(cls, X, y, window, penalty, gamma=1.0, pwr_dist=1, C=1.0, thresholds=None, status=None, distances=None,
+            random_state=0, block_size: Optional[int] = None, device: Optional[int] = None) -> "DTW_SVM":
+        """Train a model on labelled fingerprints ``X`` (n, L), ``y`` (n,) integer barcode labels -- what the reference's
+        training does (models/dtw_svm.py: ``pdist_kernel`` on the training set's own distance matrix, then a precomputed-kernel
+        ``SVC`` with probabilities), with the matrix from the engine's symmetric self-distance kernels.
+
+        1. members only: a row with a sample that is not finite, or whose ``status`` (optional, one integer per row) is not 0,
+           is dropped; their number is ``n_dropped_`` of the returned model;
+        2. ``D = parallel_distances.self_distance_matrix(members, window, penalty)``, unless ``distances`` -- that float32
+           (m, m) matrix of the m members -- is given (no device is touched then);
+        3. ``K = exp(-gamma * D ** pwr_dist)`` on the float32 matrix;
+        4. ``SVC(kernel="precomputed", probability=True, C=C, random_state=random_state).fit(K, y[members])``;
+        5. ``label_mapper = {i: classes_[i]}``, ``_X`` = the member rows.
+
+        ``ValueError`` before any device work: fewer than two classes among the members, more than 16 classes (the limit of
+        the resident SVM tail), a ``y``, ``status`` or ``distances`` of the wrong shape."""
+        from sklearn.svm import SVC
+
+        from . import _medoids
+
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] < 1:
+            raise ValueError(f"X must be (n, L) with L >= 1, got shape {X.shape}")
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = X.shape[0]
+        y = np.asarray(y)
+        if y.shape != (n,):
+            raise ValueError(f"y must hold one label per row: shape ({n},), not {y.shape}")
+        if y.dtype.kind not in "iu":
+            raise ValueError(f"y must have an integer dtype, not {y.dtype}")
+        st = _medoids.host_status(n, status)
+        member = np.isfinite(X).all(axis=1)
+        if st is not None:
+            member &= st == 0
+        Xm, ym = np.ascontiguousarray(X[member]), y[member]
+        m = int(member.sum())
+        if distances is not None:
+            distances = np.asarray(distances)
+            if distances.shape != (m, m):
+                raise ValueError(f"distances must be the ({m}, {m}) matrix of the {m} members, not {distances.shape}")
+        classes = np.unique(ym)
+        if classes.size < 2:
+            raise ValueError(f"fit needs at least two classes among the members, found {classes.size}")
+        if classes.size > _lib.SVM_MAX_CLASSES:
+            raise ValueError(f"{classes.size} classes: the resident SVM tail serves at most {_lib.SVM_MAX_CLASSES}")
+        if thresholds is not None and np.asarray(thresholds).shape != (classes.size,):
+            raise ValueError(f"thresholds must hold one value per class: shape ({classes.size},), not {np.asarray(thresholds).shape}")
+        if distances is None:
+            from .parallel_distances import self_distance_matrix
+
+            D = self_distance_matrix(Xm, window=window, penalty=penalty)
+        else:
+            D = np.ascontiguousarray(distances, dtype=np.float32)
+        K = np.exp(-gamma * np.power(D, pwr_dist))   # the reference's pdist_kernel on the float32 matrix
+        svc = SVC(kernel="precomputed", probability=True, C=C, random_state=random_state).fit(K, ym)
+        model = cls.from_sklearn(svc, Xm, {i: int(c) for i, c in enumerate(svc.classes_)}, thresholds, window, penalty, gamma=gamma,
+                                 pwr_dist=pwr_dist, block_size=block_size, device=device)
+        model.n_dropped_ = n - m
+        return model
 
     @property
     def num_bcs(self):

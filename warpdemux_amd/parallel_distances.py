@@ -219,3 +219,24 @@ def label_medoids(X, labels, n_labels=None, window=None, penalty=None, status=No
                                            int(window) if window else 0, float(penalty) if penalty else 0.0, _lib.ptr(index),
                                            _lib.ptr(mcost), _lib.ptr(count), _lib.ptr(cost), _lib.ptr(refs)))
     return (index, refs, count, mcost, cost) if want_cost else (index, refs, count, mcost)
+
+
+def self_distance_matrix(X, window=None, penalty=None, status=None):
+    """float32 (n, n): the banded DTW distances of the rows of ``X`` against themselves -- the training matrix of a DTW kernel
+    machine (`models.DTW_SVM.fit`) -- with each unordered pair computed once.  The rule of include/wdx.h
+    (wdx_self_matrix_device): an entry whose row and column are both members is the float32 `distance_matrix_to(X, X)` holds
+    there, bit for bit; a row with a sample that is not finite, or whose ``status`` (optional, one integer per row) is not 0, is
+    no member, and its row and column are NaN.  More than ``_lib.SELF_MATRIX_MAX_ROWS`` rows are NotImplementedError.  Goes
+    through wdx_dtw_self_matrix; the resident reference set is not touched."""
+    from . import _medoids
+
+    X = _as_f64_2d(X, "X")
+    n, L = X.shape
+    st = _medoids.host_status(n, status)
+    if L < 1:
+        raise ValueError("X must have at least one column")
+    out = np.empty((n, n), dtype=np.float32)
+    ctx = _lib.default_context()
+    _lib.check(_lib.load().wdx_dtw_self_matrix(ctx.handle, _lib.ptr(X), n, L, _lib.ptr(st), int(window) if window else 0,
+                                               float(penalty) if penalty else 0.0, _lib.ptr(out), n))
+    return out
