@@ -241,6 +241,9 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
  * DTW dispatch straight into the matrix, then a mask kernel for the non-members) instead of the tile kernels.  Same bits.  Any
  * other value than 0 or 1: WDX_ERR_INVALID. */
 #define WDX_OPT_SELF_MATRIX_GENERAL 26
+/* Diagnostic: 1 sends every wdx_dba_step_device / wdx_dtw_dba_step call through the general route (two rolling rows per lane in
+ * global memory) instead of the register band.  Same bits.  Any other value than 0 or 1: WDX_ERR_INVALID. */
+#define WDX_OPT_DBA_GENERAL 27
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -483,6 +486,55 @@ int wdx_self_matrix_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L,
  * returns (a context never keeps 16 GiB). */
 int wdx_dtw_self_matrix(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const int32_t *status, int32_t window,
                         double penalty, float *out, int64_t ld);
+
+/* ---- barycenter reference signals: one step of DTW alignment and averaging ------------------------------------------------
+ * The medoid of a label is one noisy read; a barycenter averages the noise of the whole label away.  One call aligns every
+ * member of a label to the label's current centre and returns, per centre point, the mean of the samples matched to it; the
+ * iteration is a short host loop over this step (parallel_distances.label_barycenters).  The rule below is this engine's own,
+ * stated bit for bit as the medoid rule is: parity with dtaidistance's dtw_barycenter is NOT claimed.
+ * Inputs: X (n, L) float64; label int32[n] on the HOST, -1 .. n_labels-1; status int32[n] (nullable); C (n_labels, L) float64,
+ * the current centres; window and penalty as for wdx_dtw_matrix, w the effective window, p2 = penalty * penalty.
+ *   MEMBERS are those of the medoid rule: label g, status 0 (if given), all L samples finite.  A label whose centre row holds a
+ *   sample that is not finite, or which has no member, is IDLE.
+ *   Cost matrix of member x (rows i) against its centre c (columns j), on the reference's six operations (never the fused cell):
+ *     D[0][0] = 0, +inf elsewhere; for the cells inside the band (|i - j| < w)
+ *     t = fl(min(D[i][j+1], D[i+1][j]) + p2);  D[i+1][j+1] = fl(fl(d*d) + min(t, D[i][j])),  d = fl(x[i] - c[j]);
+ *     cost = D[L][L], a float64 that is not rooted.
+ *   Direction of cell (i, j), with diag = D[i][j], up = D[i][j+1], left = D[i+1][j]:  diag if diag <= t;  otherwise up if
+ *     up <= left (the raw values);  otherwise left.  Whatever the values, at i == 0 the step is left and at j == 0 it is up.
+ *     (The recurrence's own argmin with ties in that order: in exact arithmetic a step cannot raise the summed cost.)
+ *   Path: from (L-1, L-1) by the directions to (0, 0).  The rows matched to column j form one run lo[j] .. hi[j];
+ *     lo[0] = 0, hi[L-1] = L-1, hi[j] <= lo[j+1] <= hi[j] + 1.
+ *   Sums (float64, strictly sequential, starting at 0.0):  s_r[j] = x[lo[j]] + ... + x[hi[j]] in rising i;
+ *     k_r[j] = hi[j] - lo[j] + 1.  The rows of label g in rising row order, members or not, form chunks of 64 as in the medoid
+ *     rule;  S_c[j] adds s_r[j] over the MEMBERS of chunk c in rising order;  T[j] adds S_0[j], S_1[j], ...;  K[j] is the int64
+ *     sum of k_r[j];  inertia[g] is the same two-level sum of cost.
+ * Outputs: new_centres (n_labels, L) float64 = T[j] / (double)K[j], an idle label's row the quiet NaN;  count int64[n_labels], the
+ *   members (idle: 0);  inertia float64[n_labels] (idle: NaN);  cost float64[n] (nullable; the quiet NaN for a non-member and for a
+ *   member of an idle label);  runs int32 (n, L, 2) = lo, hi (nullable; -1 for those rows).
+ *   (float)sqrt(cost[r]) is the float32 wdx_dtw_matrix returns for (X[r], C[label[r]]).
+ * Nothing resident is read or changed: references, models and wdx_refs_generation stay as they are.
+ * Routes: effective windows up to 32 run on the register band (dba_align_kernel), wider ones and window 0 (unbanded) on two
+ * rolling rows per lane in global memory (dba_align_general_kernel); same bits.  WDX_OPT_DBA_GENERAL = 1 sends every call the
+ * second way.
+ * WDX_ERR_INVALID: n_labels < 1, a label outside -1 .. n_labels-1, L < 1, n < 0, a NULL d_new or d_centres.
+ * WDX_ERR_UNSUPPORTED: L > WDX_DBA_MAX_L (the message names L).  A label may hold any number of rows (the medoids' cap does not
+ * apply: a step has no block that grows with the square of a label).  n == 0 is success
+ * with every label idle.  Refusals happen before anything is launched or written, and the context stays usable.  Workspace:
+ * context-owned, grow-only and bounded, see warpdemux_amd/csrc/wdx_dba_plan.h.
+ *
+ * wdx_dba_step_device: dX, d_status, d_centres and every output are DEVICE memory; d_status, d_count, d_inertia, d_cost and d_runs
+ * are nullable; d_new must not overlap d_centres; `label` is HOST memory, read during the call only.  Enqueued on `stream`; no
+ * synchronisation -- the contract of the *_dev entries (its name ends in _device for the reason wdx_medoids_device gives;
+ * tests/test_gpu_dba.py holds this entry to the same stream and bounds checks). */
+#define WDX_DBA_MAX_L 1024
+int wdx_dba_step_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *label /* HOST */, int64_t n_labels,
+                        const int32_t *d_status, const double *d_centres, int32_t window, double penalty, double *d_new,
+                        int64_t *d_count, double *d_inertia, double *d_cost, int32_t *d_runs, void *stream);
+/* Host form: every array HOST memory; one synchronisation. */
+int wdx_dtw_dba_step(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const int32_t *label, int64_t n_labels,
+                     const int32_t *status, const double *centres, int32_t window, double penalty, double *new_centres,
+                     int64_t *count, double *inertia, double *cost, int32_t *runs);
 
 /* Pipelined form of wdx_demux_batch for the reference's worker loop (file_proc.py:380-454: fill minibatch k+1
  * while minibatch k is processed; 1197-1243: several such workers share one GPU).  A context has WDX_MAX_SLOTS slots (the

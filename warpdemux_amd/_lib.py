@@ -59,6 +59,8 @@ MEDOID_MAX_GROUP = 32768   # WDX_MEDOID_MAX_GROUP: rows of one label in wdx_medo
 SVM_MAX_CLASSES = 16   # classes of a resident DTW_SVM (wdx_svm_set_model refuses more)
 OPT_SELF_MATRIX_GENERAL = 26   # diagnostic: the self-distance matrix through the DTW dispatch + a mask kernel instead of the tile kernels (same bits)
 SELF_MATRIX_MAX_ROWS = 65536   # WDX_SELF_MATRIX_MAX_ROWS: rows of wdx_self_matrix_device / wdx_dtw_self_matrix (beyond: NotImplementedError)
+OPT_DBA_GENERAL = 27   # diagnostic: barycenter steps on two rolling rows per lane in global memory instead of the register band (same bits)
+DBA_MAX_L = 1024   # WDX_DBA_MAX_L: longest series of wdx_dba_step_device / wdx_dtw_dba_step (beyond: NotImplementedError)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
 
@@ -88,6 +90,7 @@ EXPORTS = [
     "wdx_nearest_dev", "wdx_demux_nearest_dev", "wdx_dtw_nearest",
     "wdx_medoids_device", "wdx_dtw_medoids",
     "wdx_self_matrix_device", "wdx_dtw_self_matrix",
+    "wdx_dba_step_device", "wdx_dtw_dba_step",
 ]
 
 
@@ -570,6 +573,10 @@ def load():
         L.wdx_self_matrix_device.argtypes = [vp, vp, i64, i64, vp, C.c_int32, C.c_double, vp, i64, vp]
         L.wdx_dtw_self_matrix.restype = C.c_int
         L.wdx_dtw_self_matrix.argtypes = [vp, vp, i64, i64, vp, C.c_int32, C.c_double, vp, i64]
+        L.wdx_dba_step_device.restype = C.c_int
+        L.wdx_dba_step_device.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp]
+        L.wdx_dtw_dba_step.restype = C.c_int
+        L.wdx_dtw_dba_step.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp]
         _lib = L
         return L
 

@@ -7,10 +7,10 @@ import numpy as np
 from . import _lib
 
 
-def host_labels(n, labels, n_labels):
+def host_labels(n, labels, n_labels, max_group=True):
     """(int32 labels (n,), G): an integer dtype, one label per row, every label in -1 .. G-1 (-1: the row takes no part);
     ``n_labels`` None: the largest label + 1 (at least 1).  A label of more than `_lib.MEDOID_MAX_GROUP` rows is
-    NotImplementedError: the caller subsamples."""
+    NotImplementedError: the caller subsamples (``max_group`` False: no such cap -- a barycenter step has none)."""
     labels = np.asarray(labels)
     if labels.dtype.kind not in "iu":
         raise ValueError(f"labels must have an integer dtype, not {labels.dtype}")
@@ -27,13 +27,37 @@ def host_labels(n, labels, n_labels):
     if labels.size and (int(labels.min()) < -1 or int(labels.max()) >= G):
         raise ValueError(f"labels must lie in -1 .. {G - 1}")
     labels = np.ascontiguousarray(labels, dtype=np.int32)
-    if labels.size:
+    if labels.size and max_group:
         sizes = np.bincount(labels[labels >= 0], minlength=G)
         g = int(np.argmax(sizes))
         if sizes[g] > _lib.MEDOID_MAX_GROUP:
             raise NotImplementedError(f"medoids: label {g} has {int(sizes[g])} rows, more than WDX_MEDOID_MAX_GROUP = "
                                       f"{_lib.MEDOID_MAX_GROUP}: subsample it")
     return labels, G
+
+
+def dba_length(L):
+    """L of a barycenter step (include/wdx.h: wdx_dba_step_device): 1 .. `_lib.DBA_MAX_L`"""
+    if int(L) < 1:
+        raise ValueError("X must have at least one column")
+    if int(L) > _lib.DBA_MAX_L:
+        raise NotImplementedError(f"dba: L = {int(L)} is more than WDX_DBA_MAX_L = {_lib.DBA_MAX_L}")
+    return int(L)
+
+
+def host_centres(centres, G, L):
+    """float64 centres (G, L) of a barycenter step on the host: one row per label (a row with a sample that is not finite makes
+    its label idle)"""
+    centres = np.asarray(centres)
+    if centres.ndim != 2 or centres.shape != (int(G), int(L)):
+        raise ValueError(f"centres must hold one row per label: shape ({int(G)}, {int(L)}), not {centres.shape}")
+    return np.ascontiguousarray(centres, dtype=np.float64)
+
+
+def n_iterations(n_iter):
+    if isinstance(n_iter, (bool, np.bool_)) or not isinstance(n_iter, (int, np.integer)) or int(n_iter) < 1:
+        raise ValueError(f"n_iter must be an integer of at least 1, not {n_iter!r}")
+    return int(n_iter)
 
 
 def host_status(n, status):

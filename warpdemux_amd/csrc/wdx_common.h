@@ -58,6 +58,7 @@ struct Knobs {
     bool wide_dtw = false;              // WDX_OPT_WIDE_DTW: effective windows 33 .. L at L <= WDX_DTW_WIDE_MAX_L on dtw_wide_kernel (product option)
     bool medoid_general = false;        // WDX_OPT_MEDOID_GENERAL: per-label medoids through the DTW dispatch + chunk sums (diagnostic)
     bool self_matrix_general = false;   // WDX_OPT_SELF_MATRIX_GENERAL: the self-distance matrix through the DTW dispatch + mask kernel (diagnostic)
+    bool dba_general = false;           // WDX_OPT_DBA_GENERAL: barycenter steps on the rolling rows in global memory (diagnostic)
     // the long form of the exact kernel serves this call (wdx_window.h: the refinement branch has its own option)
     bool long_form(bool refine) const { return long_form_on(refine, long_windows, long_refine_windows); }
     // the longest adapter window a call of this branch fingerprints (the host loops cut one sample beyond it: that reports it)

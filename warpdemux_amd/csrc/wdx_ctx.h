@@ -104,6 +104,8 @@ struct wdx_ctx {
     wdx::Buffer medoid_ws;
     // the self-distance matrix (wdx_dtw_self.hip): the workspace wdx_self_plan.h lays out, allocated by the first such call
     wdx::Buffer self_ws;
+    // barycenter steps (wdx_dba.hip): the workspace wdx_dba_plan.h lays out (its tables go through the medoid calls' staged blocks)
+    wdx::Buffer dba_ws;
     std::vector<wdx::MedoidStage> medoid_staged;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     // the classifier tails (wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model): a slot each, independent of one another
@@ -162,6 +164,9 @@ int dtw_dev_locked(wdx_ctx *ctx, const double *dX, int64_t nX, float *d_out, int
                    hipStream_t stream);
 // (wdx_medoid.hip) frees the page-locked table blocks whose copies have run (all: waits for each; wdx_ctx_destroy calls that)
 void medoid_release_staged(wdx_ctx *ctx, bool all);
+// (wdx_medoid.hip) a page-locked block of `bytes` whose previous copy has run; the caller fills it, enqueues its copy and records
+// `copied` behind it (wdx_dba.hip uploads its tables the same way)
+int medoid_stage_block(wdx_ctx *ctx, size_t bytes, MedoidStage **out);
 // (wdx_api.hip) behind a DTW launch when a resident reference holds an infinite sample (R.any_inf): pairs with the same
 // infinity at one index are NaN in the reference and +inf out of the kernels -- settled here, then the argmin again (a NaN
 // wins its row)

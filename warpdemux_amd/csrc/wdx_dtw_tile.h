@@ -10,7 +10,8 @@ namespace wdx {
 // One wave per padded row p: X[order[p]] -> dense[p] (L samples) and padded[p] (Lpad samples, zero halo); a padding row
 // (order -1) is zeros.  member[p] = a caller's row, status 0 (if given), all L samples finite.
 // IDENTITY: no order array -- padded row p is the caller's row p while p < n, padding behind.
-template <bool IDENTITY>
+// PADDED false: the dense form alone (`padded` is not written: wdx_dba.hip, whose uniform operand is the centre, not a row).
+template <bool IDENTITY, bool PADDED = true>
 __global__ __launch_bounds__(256) void tile_gather_kernel(const double *__restrict__ X, const int32_t *__restrict__ status,
                                                           const int32_t *__restrict__ order, int64_t n, int64_t rows, int L,
                                                           int64_t Lpad, int halo, double *__restrict__ dense,
@@ -24,7 +25,7 @@ __global__ __launch_bounds__(256) void tile_gather_kernel(const double *__restri
         const int64_t s = c - halo;
         const bool in = s >= 0 && s < L;
         const double v = (in && src >= 0) ? X[src * L + s] : 0.0;
-        padded[p * Lpad + c] = v;
+        if (PADDED) padded[p * Lpad + c] = v;
         if (in) {
             dense[p * L + s] = v;
             bad |= !(v - v == 0.0);   // NaN or an infinity

@@ -234,7 +234,7 @@ void medoid_release_staged(wdx_ctx *ctx, bool all) {
 
 // A page-locked block of `bytes` whose previous copy has run: one of the context's, or a new one (then the idle ones, all too
 // small, are freed first).  The caller fills it, enqueues its copy and records `copied` behind it.
-static int medoid_stage_block(wdx_ctx *ctx, size_t bytes, MedoidStage **out) {
+int medoid_stage_block(wdx_ctx *ctx, size_t bytes, MedoidStage **out) {
     for (MedoidStage &S : ctx->medoid_staged)
         if (S.bytes >= bytes && hipEventQuery(S.copied) == hipSuccess) {
             *out = &S;

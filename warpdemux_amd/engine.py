@@ -124,6 +124,15 @@ class MedoidResult:
     cost: Optional["object"] = None   # torch float64 (n,) when requested: every member's summed distance, NaN for the others
 
 
+@dataclass
+class DbaResult:
+    centres: "object"      # torch float64 (G, L)  the new centres (a NaN row for an idle label): goes straight into `set_refs`
+    count: "object"        # torch int64 (G,)  members of each label (0 for an idle label)
+    inertia: "object"      # torch float64 (G,)  summed cost of the centres the step received, NaN for an idle label
+    cost: Optional["object"] = None   # torch float64 (n,) when requested: D[L][L] of every member, not rooted; NaN for the others
+    runs: Optional["object"] = None   # torch int32 (n, L, 2) when requested: rows lo .. hi matched to each centre point, -1 for the others
+
+
 class DemuxEngine:
     """One engine per process per GPU.  ``refs``: (nY, L) float64 reference fingerprints
     (model._X in the reference, models/dtw_base.py:20).  ``wide_dtw``: effective windows 33 .. L (``window=None`` on
@@ -390,6 +399,56 @@ class DemuxEngine:
                                              int(window) if window else 0, float(penalty) if penalty else 0.0, _dp(out.index),
                                              _dp(out.medoid_cost), _dp(out.count), _dp(out.cost), _dp(out.refs), self._stream()))
         return out
+
+    # -- barycenter reference signals (wdx_dba_step_device; include/wdx.h states the rule) -------------------------------------
+    def dba_step(self, X, labels, centres, n_labels=None, *, window, penalty, status=None, want_cost=False, want_runs=False):
+        """One step of DTW barycenter averaging on the device fingerprints X (n, L) float64: ``labels`` one HOST integer per row
+        (-1: the row takes no part), ``centres`` a float64 (G, L) device tensor, ``status`` an optional int32 (n,) device tensor.
+        Returns a `DbaResult` of device tensors: every centre point becomes the mean of the samples its label's members match
+        to it; ``inertia`` is the summed cost of the centres given.  The engine's own rule, bit for bit; parity with
+        dtaidistance's DBA unpinned.  Nothing resident is read or changed.  Enqueues on the current stream."""
+        torch = self.torch
+        if not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or int(X.shape[1]) < 1 or not X.is_contiguous():
+            raise ValueError("X must be a contiguous float64 (n, L) device tensor with L >= 1")
+        n, L = int(X.shape[0]), _medoids.dba_length(X.shape[1])
+        if n_labels is None and torch.is_tensor(centres) and centres.dim() == 2:
+            n_labels = int(centres.shape[0])
+        lab, G = _medoids.host_labels(n, labels, n_labels, max_group=False)
+        if (not torch.is_tensor(centres) or centres.dtype != torch.float64 or tuple(centres.shape) != (G, L)
+                or not centres.is_contiguous()):
+            raise ValueError(f"centres must be a contiguous float64 ({G}, {L}) device tensor")
+        if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (n,)
+                                   or not status.is_contiguous()):
+            raise ValueError(f"status must be a contiguous int32 ({n},) device tensor")
+        out = DbaResult(centres=torch.empty((G, L), dtype=torch.float64, device=self.tdev),
+                        count=torch.empty(G, dtype=torch.int64, device=self.tdev),
+                        inertia=torch.empty(G, dtype=torch.float64, device=self.tdev),
+                        cost=torch.empty(n, dtype=torch.float64, device=self.tdev) if want_cost else None,
+                        runs=torch.empty((n, L, 2), dtype=torch.int32, device=self.tdev) if want_runs else None)
+        _lib.check(self.L.wdx_dba_step_device(self.ctx.handle, _dp(X), n, L, _lib.ptr(lab), G, _dp(status), _dp(centres),
+                                              int(window) if window else 0, float(penalty) if penalty else 0.0, _dp(out.centres),
+                                              _dp(out.count), _dp(out.inertia), _dp(out.cost), _dp(out.runs), self._stream()))
+        return out
+
+    def barycenters(self, X, labels, n_labels=None, *, window, penalty, status=None, init=None, n_iter=10):
+        """(centres (G, L) float64, count (G,) int64, inertia (steps, G) float64, device tensors): at most ``n_iter`` steps of
+        `dba_step` from ``init`` (None: `medoids(...).refs`), stopping early when a step returns every centre bit-identical to
+        its input (one host read of a flag per step).  Row k of ``inertia`` belongs to the centres step k received.
+        ``set_refs(centres, window, penalty)`` makes them the resident reference set."""
+        torch = self.torch
+        steps = _medoids.n_iterations(n_iter)
+        if init is None:
+            init = self.medoids(X, labels, n_labels, window=window, penalty=penalty, status=status).refs
+        C0, hist, count = init, [], None
+        for _ in range(steps):
+            res = self.dba_step(X, labels, C0, n_labels, window=window, penalty=penalty, status=status)
+            hist.append(res.inertia)
+            count = res.count
+            same = bool(torch.equal(res.centres.view(torch.int64), C0.view(torch.int64)))
+            C0 = res.centres
+            if same:
+                break
+        return C0, count, torch.stack(hist)
 
     # -- the training matrix of a DTW kernel machine (wdx_self_matrix_device; include/wdx.h states the rule) -------------------
     def self_distances(self, X, window=None, penalty=None, status=None, out=None):

@@ -240,3 +240,63 @@ def self_distance_matrix(X, window=None, penalty=None, status=None):
     _lib.check(_lib.load().wdx_dtw_self_matrix(ctx.handle, _lib.ptr(X), n, L, _lib.ptr(st), int(window) if window else 0,
                                                float(penalty) if penalty else 0.0, _lib.ptr(out), n))
     return out
+
+
+def dba_step(X, labels, centres, n_labels=None, window=None, penalty=None, status=None, want_cost=False, want_runs=False):
+    """(new_centres float64 (G, L), count int64 (G,), inertia float64 (G,)[, cost float64 (n,)][, runs int32 (n, L, 2)]): one
+    step of DTW barycenter averaging -- every member of a label is aligned to the label's current centre, and each centre point
+    becomes the mean of the samples matched to it.  The rule of include/wdx.h (wdx_dba_step_device), the engine's own, bit for
+    bit; parity with dtaidistance's DBA unpinned.  ``labels`` and ``status`` as for `label_medoids`; ``centres``: one row per
+    label.  A label without a member, or whose centre holds a sample that is not finite, is idle: a NaN row, count 0, NaN
+    inertia.  ``inertia`` is the summed squared-cost of the centres GIVEN (``cost``: per row, not rooted; ``runs``: the rows
+    lo .. hi of each series matched to every centre point).  Goes through wdx_dtw_dba_step; nothing resident is touched."""
+    from . import _medoids
+
+    X = _as_f64_2d(X, "X")
+    n, L = X.shape
+    if n_labels is None and np.ndim(centres) == 2:   # (one centre per label)
+        n_labels = int(np.shape(centres)[0])
+    lab, G = _medoids.host_labels(n, labels, n_labels, max_group=False)
+    st = _medoids.host_status(n, status)
+    L = _medoids.dba_length(L)
+    C0 = _medoids.host_centres(centres, G, L)
+    new = np.empty((G, L), dtype=np.float64)
+    count = np.empty(G, dtype=np.int64)
+    inertia = np.empty(G, dtype=np.float64)
+    cost = np.empty(n, dtype=np.float64) if want_cost else None
+    runs = np.empty((n, L, 2), dtype=np.int32) if want_runs else None
+    ctx = _lib.default_context()
+    _lib.check(_lib.load().wdx_dtw_dba_step(ctx.handle, _lib.ptr(X), n, L, _lib.ptr(lab), G, _lib.ptr(st), _lib.ptr(C0),
+                                            int(window) if window else 0, float(penalty) if penalty else 0.0, _lib.ptr(new),
+                                            _lib.ptr(count), _lib.ptr(inertia), _lib.ptr(cost), _lib.ptr(runs)))
+    return (new, count, inertia) + ((cost,) if want_cost else ()) + ((runs,) if want_runs else ())
+
+
+def label_barycenters(X, labels, n_labels=None, window=None, penalty=None, status=None, init=None, n_iter=10):
+    """(centres float64 (G, L), count int64 (G,), inertia float64 (steps, G)): barycenter reference signals, one per label, by at
+    most ``n_iter`` steps of `dba_step` from ``init`` (None: the ``refs`` of `label_medoids`).  The loop stops early when a step
+    returns every centre bit-identical to its input; row k of ``inertia`` is the inertia of the centres step k received.  There
+    is no tolerance: the caller reads the history.  The centres go straight into ``wdx_set_refs`` / `nearest_label` /
+    ``RefineParams(query=...)`` (a label without a member has a NaN row, as with the medoids).  The engine's own rule; parity
+    with dtaidistance's DBA unpinned."""
+    from . import _medoids
+
+    X = _as_f64_2d(X, "X")
+    n, L = X.shape
+    lab, G = _medoids.host_labels(n, labels, n_labels, max_group=init is None)   # (the medoids' cap holds for their start only)
+    st = _medoids.host_status(n, status)
+    L = _medoids.dba_length(L)
+    steps = _medoids.n_iterations(n_iter)
+    if init is None:
+        C0 = label_medoids(X, lab, G, window, penalty, status=st)[1]
+    else:
+        C0 = _medoids.host_centres(init, G, L).copy()
+    hist, count = [], np.zeros(G, dtype=np.int64)
+    for _ in range(steps):
+        new, count, inertia = dba_step(X, lab, C0, G, window, penalty, status=st)
+        hist.append(inertia)
+        same = np.array_equal(new.view(np.uint64), C0.view(np.uint64))
+        C0 = new
+        if same:
+            break
+    return C0, count, np.array(hist, dtype=np.float64).reshape(len(hist), G)
