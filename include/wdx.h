@@ -244,6 +244,10 @@ int wdx_ctx_stream(wdx_ctx *ctx, void **stream);
 /* Diagnostic: 1 sends every wdx_dba_step_device / wdx_dtw_dba_step call through the general route (two rolling rows per lane in
  * global memory) instead of the register band.  Same bits.  Any other value than 0 or 1: WDX_ERR_INVALID. */
 #define WDX_OPT_DBA_GENERAL 27
+/* Diagnostic: 1 sends every wdx_self_nearest_device / wdx_dtw_self_nearest call through the general route (blocks of rows through
+ * the DTW dispatch into a float32 block, then a rows kernel) instead of the tile kernels.  Same bits.  Any other value than 0 or 1:
+ * WDX_ERR_INVALID. */
+#define WDX_OPT_SELF_NEAREST_GENERAL 28
 int wdx_ctx_set_option(wdx_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- seam 1: batched DTW  (replaces parallel_distances.py:48-67 `distance_matrix_to`,
@@ -486,6 +490,39 @@ int wdx_self_matrix_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L,
  * returns (a context never keeps 16 GiB). */
 int wdx_dtw_self_matrix(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const int32_t *status, int32_t window,
                         double penalty, float *out, int64_t ld);
+
+/* ---- is a labelled set any good: leave-one-out nearest neighbours ----------------------------------------------------------
+ * Per row of a labelled set, the nearest other row of its own label and the nearest row of any other label: what the choice of
+ * window and penalty, the screening of labels before a fit, and the leave-one-out 1-nearest-neighbour error all come from
+ * (parallel_distances.loo_summary, loo_grid).  The self matrix's tile walk with this reduction in the place of the matrix: each
+ * unordered pair is computed once, nothing of size n x n is written, the workspace is O(n x L).
+ * Inputs: X (n, L) float64; label int32[n]: -1 means "takes no part", any value >= 0 is a label, NULL means every row has label
+ * 0; status int32[n] (nullable); window and penalty as for wdx_dtw_matrix.  Every DTW option of the context applies as it does
+ * to wdx_self_matrix_device (WDX_OPT_WIDE_DTW, WDX_OPT_DTW_UNFUSED, WDX_OPT_NO_SHORT_DTW).  Only equality of labels is used.
+ *   A row is a MEMBER when its label is >= 0, its status (if given) is 0 and all L samples are finite.
+ *   f(a, b) is the float32 wdx_dtw_matrix returns for (X[a], X[b]).  Between members it is never NaN: finite or +inf (the medoid
+ *   rule's note); +inf is ordered after every finite value.
+ *   For a member a, the OWN candidates are the members b != a with label[b] == label[a], the OTHER candidates the members with
+ *   label[b] != label[a].  On each side nn is the candidate with the smallest f(a, b) and best is that f; among equal distances
+ *   the lowest row index wins (also when every candidate is at +inf).  A side without a candidate has nn = -1, best = +inf.
+ *   For a non-member both sides have nn = -1 and best = the quiet NaN 0x7fc00000.
+ * Outputs: nn int32 (n, 2) = {own, other}; best float32 (n, 2).
+ * Nothing resident is read or changed: references, models and wdx_refs_generation stay as they are.
+ * Limit: n > WDX_SELF_MATRIX_MAX_ROWS is WDX_ERR_UNSUPPORTED (the message names n).  WDX_ERR_INVALID: L < 1, n < 0, a NULL nn or
+ * best with n > 0.  n == 0 is success and writes nothing.  Refusals happen before anything is launched or written, and the context
+ * stays usable.  Routes: the cases the self matrix's tile kernels serve run on tiles whose partial results are merged as 64-bit
+ * keys (float32 bits << 32 | row) by an atomic minimum, so the result does not depend on the order the tiles finish in; wider
+ * windows, window 0 and WDX_OPT_SELF_NEAREST_GENERAL = 1 go through the DTW dispatch in row blocks of at most 96 MiB; same bits.
+ * Workspace: context-owned, grow-only and bounded, see warpdemux_amd/csrc/wdx_loo_plan.h.
+ *
+ * wdx_self_nearest_device: every array is DEVICE memory (d_label and d_status nullable).  Enqueued on `stream`; no
+ * synchronisation -- the contract of the *_dev entries (its name ends in _device for the reason wdx_medoids_device gives;
+ * tests/test_gpu_loo.py holds this entry to the same stream and bounds checks). */
+int wdx_self_nearest_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *d_label, const int32_t *d_status,
+                            int32_t window, double penalty, int32_t *d_nn, float *d_best, void *stream);
+/* Host form: every array HOST memory; one synchronisation. */
+int wdx_dtw_self_nearest(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const int32_t *label, const int32_t *status,
+                         int32_t window, double penalty, int32_t *nn, float *best);
 
 /* ---- barycenter reference signals: one step of DTW alignment and averaging ------------------------------------------------
  * The medoid of a label is one noisy read; a barycenter averages the noise of the whole label away.  One call aligns every
@@ -1161,6 +1198,8 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_ADC_DEV_WINDOWS 11 /* adc_dev_windows_kernel: the window decode ahead of every slice of an *_adc_dev call */
 #define WDX_K_REFINE_OPTIMAL 12   /* fingerprint_refine_optimal_kernel alone (WDX_OPT_REFINE_OPTIMAL_CPTS; part of WDX_K_FINGERPRINT) */
 #define WDX_K_MEDOID 13           /* per-label medoids: the pre-pass, the tile kernels (or the general route's chunk sums) and the reduce kernel */
+#define WDX_K_SELF_NEAREST 14     /* leave-one-out nearest neighbours: the pre-pass, the tile kernels and the finish kernel (or the general
+                                    route's dispatches and rows kernel) */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

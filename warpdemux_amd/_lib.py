@@ -30,6 +30,7 @@ K_BOOST = 10
 K_ADC_DEV_WINDOWS = 11   # the window decode ahead of every slice of an *_adc_dev call (int16 device shards)
 K_REFINE_OPTIMAL = 12     # fingerprint_refine_optimal_kernel alone (OPT_REFINE_OPTIMAL_CPTS)
 K_MEDOID = 13             # per-label medoids: pre-pass, tile kernels (or the general route's chunk sums), reduce kernel
+K_SELF_NEAREST = 14       # leave-one-out nearest neighbours: pre-pass, tile kernels and finish kernel (or the general route's dispatches + rows kernel)
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -60,6 +61,7 @@ SVM_MAX_CLASSES = 16   # classes of a resident DTW_SVM (wdx_svm_set_model refuse
 OPT_SELF_MATRIX_GENERAL = 26   # diagnostic: the self-distance matrix through the DTW dispatch + a mask kernel instead of the tile kernels (same bits)
 SELF_MATRIX_MAX_ROWS = 65536   # WDX_SELF_MATRIX_MAX_ROWS: rows of wdx_self_matrix_device / wdx_dtw_self_matrix (beyond: NotImplementedError)
 OPT_DBA_GENERAL = 27   # diagnostic: barycenter steps on two rolling rows per lane in global memory instead of the register band (same bits)
+OPT_SELF_NEAREST_GENERAL = 28   # diagnostic: leave-one-out neighbours through the DTW dispatch + a rows kernel instead of the tile kernels (same bits)
 DBA_MAX_L = 1024   # WDX_DBA_MAX_L: longest series of wdx_dba_step_device / wdx_dtw_dba_step (beyond: NotImplementedError)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
@@ -91,6 +93,7 @@ EXPORTS = [
     "wdx_medoids_device", "wdx_dtw_medoids",
     "wdx_self_matrix_device", "wdx_dtw_self_matrix",
     "wdx_dba_step_device", "wdx_dtw_dba_step",
+    "wdx_self_nearest_device", "wdx_dtw_self_nearest",
 ]
 
 
@@ -573,6 +576,10 @@ def load():
         L.wdx_self_matrix_device.argtypes = [vp, vp, i64, i64, vp, C.c_int32, C.c_double, vp, i64, vp]
         L.wdx_dtw_self_matrix.restype = C.c_int
         L.wdx_dtw_self_matrix.argtypes = [vp, vp, i64, i64, vp, C.c_int32, C.c_double, vp, i64]
+        L.wdx_self_nearest_device.restype = C.c_int
+        L.wdx_self_nearest_device.argtypes = [vp, vp, i64, i64, vp, vp, C.c_int32, C.c_double, vp, vp, vp]
+        L.wdx_dtw_self_nearest.restype = C.c_int
+        L.wdx_dtw_self_nearest.argtypes = [vp, vp, i64, i64, vp, vp, C.c_int32, C.c_double, vp, vp]
         L.wdx_dba_step_device.restype = C.c_int
         L.wdx_dba_step_device.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp]
         L.wdx_dtw_dba_step.restype = C.c_int

@@ -59,6 +59,7 @@ struct Knobs {
     bool medoid_general = false;        // WDX_OPT_MEDOID_GENERAL: per-label medoids through the DTW dispatch + chunk sums (diagnostic)
     bool self_matrix_general = false;   // WDX_OPT_SELF_MATRIX_GENERAL: the self-distance matrix through the DTW dispatch + mask kernel (diagnostic)
     bool dba_general = false;           // WDX_OPT_DBA_GENERAL: barycenter steps on the rolling rows in global memory (diagnostic)
+    bool self_nearest_general = false;  // WDX_OPT_SELF_NEAREST_GENERAL: leave-one-out neighbours through the DTW dispatch + rows kernel (diagnostic)
     // the long form of the exact kernel serves this call (wdx_window.h: the refinement branch has its own option)
     bool long_form(bool refine) const { return long_form_on(refine, long_windows, long_refine_windows); }
     // the longest adapter window a call of this branch fingerprints (the host loops cut one sample beyond it: that reports it)

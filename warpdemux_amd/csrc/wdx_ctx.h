@@ -43,7 +43,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 14;
+constexpr int kNumTimed = 15;
 
 struct MedoidStage {   // a page-locked block and the event behind the latest copy out of it
     void *host = nullptr;
@@ -104,6 +104,8 @@ struct wdx_ctx {
     wdx::Buffer medoid_ws;
     // the self-distance matrix (wdx_dtw_self.hip): the workspace wdx_self_plan.h lays out, allocated by the first such call
     wdx::Buffer self_ws;
+    // leave-one-out nearest neighbours (wdx_dtw_loo.hip): the workspace wdx_loo_plan.h lays out, allocated by the first such call
+    wdx::Buffer loo_ws;
     // barycenter steps (wdx_dba.hip): the workspace wdx_dba_plan.h lays out (its tables go through the medoid calls' staged blocks)
     wdx::Buffer dba_ws;
     std::vector<wdx::MedoidStage> medoid_staged;

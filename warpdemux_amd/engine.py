@@ -133,6 +133,12 @@ class DbaResult:
     runs: Optional["object"] = None   # torch int32 (n, L, 2) when requested: rows lo .. hi matched to each centre point, -1 for the others
 
 
+@dataclass
+class LooResult:
+    nn: "object"           # torch int32 (n, 2)  {own, other}: the nearest other row of the row's label, the nearest row of another label; -1 without one
+    best: "object"         # torch float32 (n, 2)  the distances to them (+inf without a candidate, NaN for a non-member)
+
+
 class DemuxEngine:
     """One engine per process per GPU.  ``refs``: (nY, L) float64 reference fingerprints
     (model._X in the reference, models/dtw_base.py:20).  ``wide_dtw``: effective windows 33 .. L (``window=None`` on
@@ -478,6 +484,30 @@ class DemuxEngine:
         _lib.check(self.L.wdx_self_matrix_device(self.ctx.handle, _dp(X), n, L, _dp(status), int(window) if window else 0,
                                                  float(penalty) if penalty else 0.0, _dp(out), ld, self._stream()))
         return out[:, :n]
+
+    # -- is a labelled set any good (wdx_self_nearest_device; include/wdx.h states the rule) -----------------------------------
+    def loo_nearest(self, X, labels=None, *, window, penalty, status=None):
+        """`LooResult` of device tensors: per row of the device fingerprints X (n, L) float64 the nearest other row of its own
+        label and the nearest row of any other label, with the distances -- the self matrix's tile walk without the (n, n)
+        matrix.  ``labels``: an optional int32 (n,) device tensor (-1: the row takes no part; None: every row has label 0);
+        ``status``: an optional int32 (n,) device tensor (a row whose status is not 0, like a row with a sample that is not
+        finite, is no member: nn -1, best NaN).  `parallel_distances.loo_summary` reads the result on the host.  Nothing
+        resident is read or changed.  Enqueues on the current stream; does not synchronise."""
+        torch = self.torch
+        if not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or int(X.shape[1]) < 1 or not X.is_contiguous():
+            raise ValueError("X must be a contiguous float64 (n, L) device tensor with L >= 1")
+        n, L = int(X.shape[0]), int(X.shape[1])
+        if n > _lib.SELF_MATRIX_MAX_ROWS:
+            raise NotImplementedError(f"self nearest: n = {n} rows, more than WDX_SELF_MATRIX_MAX_ROWS = {_lib.SELF_MATRIX_MAX_ROWS}: "
+                                      "subsample them")
+        for name, t in (("labels", labels), ("status", status)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 ({n},) device tensor")
+        out = LooResult(nn=torch.empty((n, 2), dtype=torch.int32, device=self.tdev),
+                        best=torch.empty((n, 2), dtype=torch.float32, device=self.tdev))
+        _lib.check(self.L.wdx_self_nearest_device(self.ctx.handle, _dp(X), n, L, _dp(labels), _dp(status), int(window) if window else 0,
+                                                  float(penalty) if penalty else 0.0, _dp(out.nn), _dp(out.best), self._stream()))
+        return out
 
     def demux_nearest(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, labels=None, n_labels=None,
                       min_margin=None, max_dist=None, want_dist=False, want_fpt=False, counts=None):

@@ -10,6 +10,7 @@ Install in a WarpDemuX process with ``warpdemux_amd.install()`` (see INTEGRATION
 from __future__ import annotations
 
 import logging
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -300,3 +301,111 @@ def label_barycenters(X, labels, n_labels=None, window=None, penalty=None, statu
         if same:
             break
     return C0, count, np.array(hist, dtype=np.float64).reshape(len(hist), G)
+
+
+def _loo_labels(n, labels):
+    """int32 labels (n,) or None: an integer dtype, one label per row, none below -1 (-1: the row takes no part)"""
+    if labels is None:
+        return None
+    labels = np.asarray(labels)
+    if labels.dtype.kind not in "iu":
+        raise ValueError(f"labels must have an integer dtype, not {labels.dtype}")
+    if labels.shape != (int(n),):
+        raise ValueError(f"labels must hold one label per row: shape ({int(n)},), not {labels.shape}")
+    if labels.size and int(labels.min()) < -1:
+        raise ValueError(f"labels must be -1 (the row takes no part) or a label >= 0, not {int(labels.min())}")
+    if labels.size and int(labels.max()) > np.iinfo(np.int32).max:
+        raise ValueError(f"labels must fit an int32, not {int(labels.max())}")
+    return np.ascontiguousarray(labels, dtype=np.int32)
+
+
+def loo_nearest(X, labels=None, window=None, penalty=None, status=None):
+    """(nn int32 (n, 2), best float32 (n, 2)): per row of ``X`` the nearest OTHER row of its own label (column 0) and the nearest
+    row of any other label (column 1), and the banded DTW distances to them -- what tells whether a labelled set is any good
+    before a model is fitted on it (`loo_summary`, `loo_grid`).  The rule of include/wdx.h (wdx_self_nearest_device), the
+    engine's own: ``labels`` one integer per row (-1: the row takes no part; None: every row has label 0); a row with a sample
+    that is not finite, or whose ``status`` (optional, one integer per row) is not 0, is no member: nn -1, best NaN.  Among
+    equal distances the lowest row index wins; a side without a candidate has nn -1 and best +inf.  The distances are those of
+    `self_distance_matrix`, bit for bit, but no (n, n) matrix is written: the device memory is O(n L).  More than
+    ``_lib.SELF_MATRIX_MAX_ROWS`` rows are NotImplementedError.  Goes through wdx_dtw_self_nearest; nothing resident is touched."""
+    from . import _medoids
+
+    X = _as_f64_2d(X, "X")
+    n, L = X.shape
+    if L < 1:
+        raise ValueError("X must have at least one column")
+    lab = _loo_labels(n, labels)
+    st = _medoids.host_status(n, status)
+    if n > _lib.SELF_MATRIX_MAX_ROWS:
+        raise NotImplementedError(f"self nearest: n = {n} rows, more than WDX_SELF_MATRIX_MAX_ROWS = {_lib.SELF_MATRIX_MAX_ROWS}: "
+                                  "subsample them")
+    nn = np.empty((n, 2), dtype=np.int32)
+    best = np.empty((n, 2), dtype=np.float32)
+    ctx = _lib.default_context()
+    _lib.check(_lib.load().wdx_dtw_self_nearest(ctx.handle, _lib.ptr(X), n, L, _lib.ptr(lab), _lib.ptr(st), int(window) if window else 0,
+                                                float(penalty) if penalty else 0.0, _lib.ptr(nn), _lib.ptr(best)))
+    return nn, best
+
+
+@dataclass
+class LooSummary:
+    call: np.ndarray        # int32 (n,)  label of the nearer of the two sides; -1 for a non-member and without any candidate
+    margin: np.ndarray      # float32 (n,)  best[:, 1] - best[:, 0]: negative where another label is nearer; NaN for inf - inf and non-members
+    confusion: np.ndarray   # int64 (G, G + 1)  members by true label and call; the last column counts call -1
+    error_rate: float       # members with a candidate whose call is not their label / members with a candidate (NaN without one)
+    n_members: int
+    suspects: np.ndarray    # int64: the member rows whose call differs from their label, rising
+
+
+def loo_summary(labels, nn, best, n_labels=None):
+    """`LooSummary` of a `loo_nearest` result, on the host: the leave-one-out 1-nearest-neighbour call of every member (the
+    label of the nearer side; on equal distances the lower row index decides), its margin, the confusion of true label by call,
+    the error rate and the rows to look at first -- members whose nearest neighbour has another label."""
+    nn, best = np.asarray(nn), np.asarray(best)
+    if nn.ndim != 2 or nn.shape[1] != 2 or nn.dtype.kind not in "iu":
+        raise ValueError(f"nn must be an integer (n, 2) array, not {nn.dtype} {nn.shape}")
+    n = nn.shape[0]
+    if best.shape != (n, 2) or best.dtype != np.float32:
+        raise ValueError(f"best must be a float32 ({n}, 2) array, not {best.dtype} {best.shape}")
+    lab = _loo_labels(n, np.zeros(n, dtype=np.int32) if labels is None else labels)
+    if n_labels is None:
+        G = max(1, int(lab.max()) + 1) if n else 1
+    elif isinstance(n_labels, (bool, np.bool_)) or not isinstance(n_labels, (int, np.integer)) or int(n_labels) < 1:
+        raise ValueError(f"n_labels must be an integer of at least 1, not {n_labels!r}")
+    else:
+        G = int(n_labels)
+    if n and int(lab.max()) >= G:
+        raise ValueError(f"labels must lie in -1 .. {G - 1}")
+    if n and (int(nn.min()) < -1 or int(nn.max()) >= n):
+        raise ValueError(f"nn must hold row numbers in -1 .. {n - 1}")
+    member = (lab >= 0) & ~np.isnan(best[:, 0])
+    own, other = nn[:, 0].astype(np.int64), nn[:, 1].astype(np.int64)
+    has_own, has_other = member & (own >= 0), member & (other >= 0)
+    d_own, d_other = best[:, 0], best[:, 1]
+    take_other = has_other & (~has_own | (d_other < d_own) | ((d_other == d_own) & (other < own)))
+    call = np.full(n, -1, dtype=np.int32)
+    call[has_own] = lab[has_own]
+    call[take_other] = lab[other[take_other]]
+    with np.errstate(invalid="ignore"):
+        margin = (d_other - d_own).astype(np.float32)
+    margin[~member] = np.nan
+    confusion = np.zeros((G, G + 1), dtype=np.int64)
+    np.add.at(confusion, (lab[member], np.where(call[member] < 0, G, call[member])), 1)
+    judged = has_own | has_other
+    wrong = judged & (call != lab)
+    return LooSummary(call=call, margin=margin, confusion=confusion,
+                      error_rate=float(wrong.sum()) / float(judged.sum()) if judged.any() else float("nan"),
+                      n_members=int(member.sum()), suspects=np.flatnonzero(member & (call != lab)).astype(np.int64))
+
+
+def loo_grid(X, labels, windows, penalties, status=None):
+    """float64 (len(windows), len(penalties)): the leave-one-out 1-nearest-neighbour error rate of the labelled set for every
+    window and penalty -- one `loo_nearest` and one `loo_summary` per cell.  The cell with the smallest error is the first
+    choice for a chemistry or barcode set the shipped 15 / 0.1 were not chosen for."""
+    windows, penalties = list(windows), list(penalties)
+    out = np.empty((len(windows), len(penalties)), dtype=np.float64)
+    for i, w in enumerate(windows):
+        for j, p in enumerate(penalties):
+            nn, best = loo_nearest(X, labels, w, p, status=status)
+            out[i, j] = loo_summary(labels, nn, best).error_rate
+    return out
