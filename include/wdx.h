@@ -573,6 +573,71 @@ int wdx_dtw_dba_step(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const 
                      const int32_t *status, const double *centres, int32_t window, double penalty, double *new_centres,
                      int64_t *count, double *inertia, double *cost, int32_t *runs);
 
+/* ---- fitting a DTW kernel machine: a batch of binary C-SVC duals by SMO ------------------------------------------------------
+ * What a fit does behind the self-distance matrix: the k (k - 1) / 2 one-vs-one problems of a precomputed-kernel SVC, and the
+ * five fold problems of each that libsvm's Platt scaling cross-validates, are independent -- one call solves all of them, one
+ * workgroup per problem (models.DTW_SVM.fit(solver="device")).  Each problem is
+ *     min 1/2 a'Qa - e'a,   0 <= a_s <= C_s,   y'a = 0,   Q_st = y_s y_t K_st
+ * on rows of ONE kernel matrix K (m, m) float32 with leading dimension ld, every entry read as float64 (exactly).
+ * A problem (wdx_svm_problem) names n_pos + n_neg entries of the row list from row0 on -- K-row indices; the first n_pos carry
+ * y = +1 and C = c_pos, the next n_neg y = -1 and C = c_neg; "row t" below is the t-th of them, K_st = K[rows[s] * ld + rows[t]]
+ * -- and n_eval entries of the evaluation list from eval0 on: K-row indices e whose decision value is wanted (a fold's held-out
+ * rows).  alpha[row0 + t] belongs to row t, dec[eval0 + e] to evaluation row e, rho / n_iter / state [q] to problem q.
+ *
+ * THE RULE is libsvm's second-order working-set selection (Fan, Chen, Lin 2005) without shrinking, restated so that the result
+ * is defined bit for bit.  All arithmetic is float64; every product, sum and quotient is rounded on its own (nothing is
+ * contracted into a fused multiply-add); a maximum or minimum over rows rounds nothing.  TAU = 1e-12.
+ *   1. a = 0, G = -1 for every row; it = 0.
+ *   2. If any G_t is not finite: state 2, stop.   v_t = -y_t G_t.
+ *   3. I_up = {t: (y_t = +1 and a_t < C_t) or (y_t = -1 and a_t > 0)};  I_low = {t: (y_t = +1 and a_t > 0) or (y_t = -1 and a_t < C_t)}.
+ *   4. gmax = max of v over I_up and i the lowest row that attains it (-inf and no row when I_up is empty); gmin = min of v over
+ *      I_low (+inf when empty).  If gmax - gmin < eps: state 0, stop.  Otherwise, if it == max_iter: state 1, stop.
+ *   5. For t in I_low with b = gmax - v_t > 0:  c = (K_ii + K_tt) - 2 K_it, replaced by TAU unless c > 0;  score_t = (b b) / c.
+ *      j = the lowest row that attains the largest score.  No such row (every score NaN): state 2, stop.
+ *   6. The pair, exactly as libsvm's Solver::Solve moves and clips it.  q = (K_ii + K_jj) - 2 K_ij, replaced by TAU unless q > 0.
+ *      y_i != y_j:  d = (-G_i - G_j) / q;  diff = a_i - a_j;  a_i += d;  a_j += d;
+ *                   diff > 0:  if a_j < 0 then a_j = 0, a_i = diff;          else:  if a_i < 0 then a_i = 0, a_j = -diff;
+ *                   diff > C_i - C_j:  if a_i > C_i then a_i = C_i, a_j = C_i - diff;
+ *                   else:              if a_j > C_j then a_j = C_j, a_i = C_j + diff.
+ *      y_i == y_j:  d = (G_i - G_j) / q;  sum = a_i + a_j;  a_i -= d;  a_j += d;
+ *                   sum > C_i:  if a_i > C_i then a_i = C_i, a_j = sum - C_i;   else:  if a_j < 0 then a_j = 0, a_i = sum;
+ *                   sum > C_j:  if a_j > C_j then a_j = C_j, a_i = sum - C_j;   else:  if a_i < 0 then a_i = 0, a_j = sum.
+ *   7. With da_i, da_j the changes of the two:  G_t = G_t + ((y_t y_i K_it) da_i + (y_t y_j K_jt) da_j) for every t (rows i and j
+ *      of K are the ones read);  it = it + 1;  back to 2.
+ *   8. n_iter = it.  State 0 or 1:  rho = -(the sum of v_t over the free rows, 0 < a_t < C_t, added one by one in rising t from
+ *      0.0) / their count, or -(gmax + gmin) / 2 of the last step 4 when no row is free;
+ *      dec_e = (the sum over the rows s with a_s > 0, in rising s from 0.0, of (a_s y_s) K[e * ld + rows[s]]) - rho.
+ *      State 2:  rho and every dec_e are the quiet NaN 0x7ff8000000000000; alpha is what the solve had reached.
+ * A NaN in K therefore ends a solve (its gradient stops being finite), and every loop is bounded by max_iter.
+ *
+ * Refused before anything is launched or written (WDX_ERR_INVALID; the context stays usable): m < 1, ld < m, a negative count,
+ * eps not positive and finite, max_iter < 0, a NULL K, table or output, a problem with an empty side, with more than
+ * WDX_SVM_FIT_MAX_ROWS rows (warpdemux_amd/csrc/wdx_svm_fit_plan.h derives the cap), with a c that is not positive and finite,
+ * with a list range outside its list, or with a row or evaluation row outside 0 .. m-1.  n_problems == 0 is success.
+ *
+ * wdx_svm_solve_device: d_K and the five outputs are DEVICE memory; the problem table and the two lists are HOST memory, read
+ * during the call only (a row index is checked before it can reach a kernel; the call uploads them through a page-locked block
+ * of the context, as wdx_medoids_device does its labels).  Enqueued on `stream`; no synchronisation -- the contract of the *_dev
+ * entries (tests/test_gpu_svm_fit.py holds this entry to the stream check).  Outputs of different problems must not overlap;
+ * d_alpha is the solve's working storage too (what it held before the call is ignored, and it must not be read before the call's
+ * work on the stream has run).  Timed as WDX_K_SVM_FIT. */
+#define WDX_SVM_FIT_MAX_ROWS 16384
+typedef struct wdx_svm_problem {
+    int64_t row0;    /* first of the problem's n_pos + n_neg entries of the row list, and of its alpha values */
+    int64_t eval0;   /* first of its n_eval entries of the evaluation list, and of its dec values              */
+    int32_t n_pos, n_neg, n_eval, reserved_;
+    double c_pos, c_neg;
+} wdx_svm_problem;
+int wdx_svm_solve_device(wdx_ctx *ctx, const float *d_K, int64_t m, int64_t ld, const wdx_svm_problem *problems /* HOST */,
+                         int64_t n_problems, const int32_t *rows /* HOST */, int64_t n_rows, const int32_t *eval_rows /* HOST */,
+                         int64_t n_eval, double eps, int64_t max_iter, double *d_alpha, double *d_rho, int64_t *d_n_iter,
+                         int32_t *d_state, double *d_dec, void *stream);
+/* Host form: every array HOST memory; one synchronisation.  A K with an entry (of its m x m part) that is not finite is
+ * WDX_ERR_INVALID.  The device copy of K lives for the call only. */
+int wdx_svm_solve(wdx_ctx *ctx, const float *K, int64_t m, int64_t ld, const wdx_svm_problem *problems, int64_t n_problems,
+                  const int32_t *rows, int64_t n_rows, const int32_t *eval_rows, int64_t n_eval, double eps, int64_t max_iter,
+                  double *alpha, double *rho, int64_t *n_iter, int32_t *state, double *dec);
+
 /* Pipelined form of wdx_demux_batch for the reference's worker loop (file_proc.py:380-454: fill minibatch k+1
  * while minibatch k is processed; 1197-1243: several such workers share one GPU).  A context has WDX_MAX_SLOTS slots (the
  * worker loop uses two; a feeder that serves many producers keeps more minibatches in flight), each with its own stream
@@ -1200,6 +1265,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_MEDOID 13           /* per-label medoids: the pre-pass, the tile kernels (or the general route's chunk sums) and the reduce kernel */
 #define WDX_K_SELF_NEAREST 14     /* leave-one-out nearest neighbours: the pre-pass, the tile kernels and the finish kernel (or the general
                                     route's dispatches and rows kernel) */
+#define WDX_K_SVM_FIT 15          /* the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

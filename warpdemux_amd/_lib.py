@@ -31,6 +31,7 @@ K_ADC_DEV_WINDOWS = 11   # the window decode ahead of every slice of an *_adc_de
 K_REFINE_OPTIMAL = 12     # fingerprint_refine_optimal_kernel alone (OPT_REFINE_OPTIMAL_CPTS)
 K_MEDOID = 13             # per-label medoids: pre-pass, tile kernels (or the general route's chunk sums), reduce kernel
 K_SELF_NEAREST = 14       # leave-one-out nearest neighbours: pre-pass, tile kernels and finish kernel (or the general route's dispatches + rows kernel)
+K_SVM_FIT = 15            # the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -62,6 +63,9 @@ OPT_SELF_MATRIX_GENERAL = 26   # diagnostic: the self-distance matrix through th
 SELF_MATRIX_MAX_ROWS = 65536   # WDX_SELF_MATRIX_MAX_ROWS: rows of wdx_self_matrix_device / wdx_dtw_self_matrix (beyond: NotImplementedError)
 OPT_DBA_GENERAL = 27   # diagnostic: barycenter steps on two rolling rows per lane in global memory instead of the register band (same bits)
 OPT_SELF_NEAREST_GENERAL = 28   # diagnostic: leave-one-out neighbours through the DTW dispatch + a rows kernel instead of the tile kernels (same bits)
+SVM_FIT_MAX_ROWS = 16384   # WDX_SVM_FIT_MAX_ROWS: rows of one problem of wdx_svm_solve_device / wdx_svm_solve (beyond: NotImplementedError in Python)
+# (threads, rows per thread) of the solver's instantiations (wdx_svm_fit_plan.h: kSvmFitKernels); a call runs the smallest that holds its largest problem
+SVM_FIT_KERNELS = ((64, 4), (256, 8), (1024, 16))
 DBA_MAX_L = 1024   # WDX_DBA_MAX_L: longest series of wdx_dba_step_device / wdx_dtw_dba_step (beyond: NotImplementedError)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
@@ -94,6 +98,7 @@ EXPORTS = [
     "wdx_self_matrix_device", "wdx_dtw_self_matrix",
     "wdx_dba_step_device", "wdx_dtw_dba_step",
     "wdx_self_nearest_device", "wdx_dtw_self_nearest",
+    "wdx_svm_solve_device", "wdx_svm_solve",
 ]
 
 
@@ -584,6 +589,10 @@ def load():
         L.wdx_dba_step_device.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp]
         L.wdx_dtw_dba_step.restype = C.c_int
         L.wdx_dtw_dba_step.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp]
+        L.wdx_svm_solve_device.restype = C.c_int
+        L.wdx_svm_solve_device.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, C.c_double, i64, vp, vp, vp, vp, vp, vp]
+        L.wdx_svm_solve.restype = C.c_int
+        L.wdx_svm_solve.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, C.c_double, i64, vp, vp, vp, vp, vp]
         _lib = L
         return L
 

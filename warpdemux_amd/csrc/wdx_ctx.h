@@ -43,7 +43,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 15;
+constexpr int kNumTimed = 16;
 
 struct MedoidStage {   // a page-locked block and the event behind the latest copy out of it
     void *host = nullptr;
@@ -108,6 +108,8 @@ struct wdx_ctx {
     wdx::Buffer loo_ws;
     // barycenter steps (wdx_dba.hip): the workspace wdx_dba_plan.h lays out (its tables go through the medoid calls' staged blocks)
     wdx::Buffer dba_ws;
+    // the batched SMO solve (wdx_svm_fit.hip): the tables wdx_svm_fit_plan.h lays out (uploaded through the medoid calls' staged blocks)
+    wdx::Buffer svm_fit_ws;
     std::vector<wdx::MedoidStage> medoid_staged;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     // the classifier tails (wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model): a slot each, independent of one another

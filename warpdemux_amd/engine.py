@@ -139,6 +139,15 @@ class LooResult:
     best: "object"         # torch float32 (n, 2)  the distances to them (+inf without a candidate, NaN for a non-member)
 
 
+@dataclass
+class SvmSolveResult:
+    alpha: "object"        # torch float64 (len(rows),)  alpha of every entry of the row list
+    rho: "object"          # torch float64 (n_problems,)
+    n_iter: "object"       # torch int64 (n_problems,)
+    state: "object"        # torch int32 (n_problems,)  0 converged, 1 iteration cap, 2 stopped (non-finite gradient / no second index)
+    dec: "object"          # torch float64 (len(eval_rows),)  decision values of the evaluation rows
+
+
 class DemuxEngine:
     """One engine per process per GPU.  ``refs``: (nY, L) float64 reference fingerprints
     (model._X in the reference, models/dtw_base.py:20).  ``wide_dtw``: effective windows 33 .. L (``window=None`` on
@@ -484,6 +493,41 @@ class DemuxEngine:
         _lib.check(self.L.wdx_self_matrix_device(self.ctx.handle, _dp(X), n, L, _dp(status), int(window) if window else 0,
                                                  float(penalty) if penalty else 0.0, _dp(out), ld, self._stream()))
         return out[:, :n]
+
+    # -- fitting a kernel machine on a resident kernel matrix (wdx_svm_solve_device; include/wdx.h states the rule) ------------
+    def svm_solve(self, K, problems, rows, eval_rows=None, eps=1e-3, max_iter=10_000_000):
+        """`SvmSolveResult` of device tensors: a batch of binary C-SVC duals on the float32 device kernel matrix ``K`` (m rows,
+        at least m contiguous columns; a view of a wider tensor keeps its row stride as the leading dimension), one workgroup
+        per problem -- for callers who sweep C or the class weights over one resident ``K``.  ``problems``: a NumPy array of
+        `_svm_fit.PROBLEM_DTYPE` (wdx_svm_problem); ``rows`` / ``eval_rows``: the int32 HOST lists it points into (K-row
+        indices: they are checked on the host before anything is launched).  A problem of more than
+        ``_lib.SVM_FIT_MAX_ROWS`` rows is NotImplementedError.  Enqueues on the current stream; does not synchronise."""
+        from . import _svm_fit
+
+        torch = self.torch
+        if (not torch.is_tensor(K) or K.dtype != torch.float32 or K.dim() != 2 or int(K.shape[0]) < 1 or int(K.shape[1]) < int(K.shape[0])
+                or (int(K.shape[1]) > 1 and K.stride(1) != 1) or (int(K.shape[0]) > 1 and K.stride(0) < int(K.shape[1]))):
+            raise ValueError("K must be a float32 device tensor of m >= 1 rows and at least m contiguous columns")
+        m = int(K.shape[0])
+        ld = int(K.stride(0)) if m > 1 else int(K.shape[1])
+        problems = np.ascontiguousarray(problems, dtype=_svm_fit.PROBLEM_DTYPE)
+        if problems.ndim != 1:
+            raise ValueError("problems must be a one-dimensional array of _svm_fit.PROBLEM_DTYPE")
+        rows = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+        eval_rows = np.zeros(0, np.int32) if eval_rows is None else np.ascontiguousarray(eval_rows, dtype=np.int32).ravel()
+        if len(problems) and (problems["n_pos"].astype(np.int64) + problems["n_neg"]).max() > _lib.SVM_FIT_MAX_ROWS:
+            raise NotImplementedError(f"svm solve: a problem of {int((problems['n_pos'].astype(np.int64) + problems['n_neg']).max())} rows, "
+                                      f"more than WDX_SVM_FIT_MAX_ROWS = {_lib.SVM_FIT_MAX_ROWS}")
+        Q = len(problems)
+        out = SvmSolveResult(alpha=torch.zeros(len(rows), dtype=torch.float64, device=self.tdev),
+                             rho=torch.empty(Q, dtype=torch.float64, device=self.tdev),
+                             n_iter=torch.empty(Q, dtype=torch.int64, device=self.tdev),
+                             state=torch.empty(Q, dtype=torch.int32, device=self.tdev),
+                             dec=torch.zeros(len(eval_rows), dtype=torch.float64, device=self.tdev))
+        _lib.check(self.L.wdx_svm_solve_device(self.ctx.handle, _dp(K), m, ld, _lib.ptr(problems), Q, _lib.ptr(rows), len(rows),
+                                               _lib.ptr(eval_rows), len(eval_rows), float(eps), int(max_iter), _dp(out.alpha), _dp(out.rho),
+                                               _dp(out.n_iter), _dp(out.state), _dp(out.dec), self._stream()))
+        return out
 
     # -- is a labelled set any good (wdx_self_nearest_device; include/wdx.h states the rule) -----------------------------------
     def loo_nearest(self, X, labels=None, *, window, penalty, status=None):

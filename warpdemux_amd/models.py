@@ -132,7 +132,8 @@ class DTW_SVM(_ResidentDTWModel):
 
     @classmethod
     def fit(cls, X, y, window, penalty, gamma=1.0, pwr_dist=1, C=1.0, thresholds=None, status=None, distances=None,
-            random_state=0, block_size: Optional[int] = None, device: Optional[int] = None) -> "DTW_SVM":
+            random_state=0, block_size: Optional[int] = None, device: Optional[int] = None, class_weight=None, solver="libsvm",
+            tol=1e-3, max_iter=-1) -> "DTW_SVM":
         """Train a model on labelled fingerprints ``X`` (n, L), ``y`` (n,) integer barcode labels -- what the reference's
         training does (models/dtw_svm.py: ``pdist_kernel`` on the training set's own distance matrix, then a precomputed-kernel
         ``SVC`` with probabilities), with the matrix from the engine's symmetric self-distance kernels.
@@ -145,8 +146,23 @@ class DTW_SVM(_ResidentDTWModel):
         4. ``SVC(kernel="precomputed", probability=True, C=C, random_state=random_state).fit(K, y[members])``;
         5. ``label_mapper = {i: classes_[i]}``, ``_X`` = the member rows.
 
+        ``class_weight`` (``None``, ``"balanced"`` = n_members / (k * count), or a dict by label), ``tol`` and ``max_iter``
+        (-1: libsvm's own cap, max(10 000 000, 100 * rows)) are the ``SVC``'s; the shipped reference models are
+        ``C=1, class_weight="balanced", tol=1e-3``.
+
+        ``solver="device"`` replaces step 4 by one batched launch of the engine's SMO solver (include/wdx.h:
+        wdx_svm_solve_device states its rule; `_svm_fit` the host code around it): the same optimisation problems on the same
+        ``K``, per pair ``c_pos = C * w_i``, ``c_neg = C * w_j``, stopped at the same gap ``tol`` -- so every pair's solution
+        meets the KKT conditions to ``tol`` as libsvm's does, without being the same numbers.  ``probA`` / ``probB`` come from
+        libsvm's ``sigmoid_train`` on five folds per pair which are THIS ENGINE'S OWN (scikit-learn's random generator cannot
+        be reproduced; `_svm_fit` states the fold rule, seeded by ``random_state``, a non-negative integer): they differ from a
+        libsvm fit's.  A pair of more than ``_lib.SVM_FIT_MAX_ROWS`` rows is ``NotImplementedError``.  The model carries
+        ``fit_info_`` (per problem: pair, fold, rows, iterations, state), and a ``RuntimeWarning`` is raised when a problem's
+        state is not 0.
+
         ``ValueError`` before any device work: fewer than two classes among the members, more than 16 classes (the limit of
-        the resident SVM tail), a ``y``, ``status`` or ``distances`` of the wrong shape."""
+        the resident SVM tail), a ``y``, ``status`` or ``distances`` of the wrong shape, an unknown ``solver`` or
+        ``class_weight``, a ``tol`` that is not positive, a bad ``max_iter``."""
         from sklearn.svm import SVC
 
         from . import _medoids
@@ -178,6 +194,25 @@ class DTW_SVM(_ResidentDTWModel):
             raise ValueError(f"{classes.size} classes: the resident SVM tail serves at most {_lib.SVM_MAX_CLASSES}")
         if thresholds is not None and np.asarray(thresholds).shape != (classes.size,):
             raise ValueError(f"thresholds must hold one value per class: shape ({classes.size},), not {np.asarray(thresholds).shape}")
+        if solver not in ("libsvm", "device"):
+            raise ValueError(f'solver must be "libsvm" or "device", not {solver!r}')
+        if solver == "device":
+            from . import _svm_fit
+
+            for name, v in (("tol", tol), ("C", C)):
+                if not (np.isscalar(v) and np.isreal(v) and np.isfinite(v) and v > 0):
+                    raise ValueError(f"{name} must be positive and finite, not {v!r}")
+            y_idx = np.searchsorted(classes, ym)
+            weights = _svm_fit.class_weights(class_weight, classes, y_idx)
+            _svm_fit.effective_max_iter(max_iter, 0)
+            if not isinstance(random_state, (int, np.integer)) or random_state < 0:
+                raise ValueError(f'solver="device" needs a non-negative integer random_state, not {random_state!r}')
+            counts = np.bincount(y_idx)
+            if np.sort(counts)[-2:].sum() > _lib.SVM_FIT_MAX_ROWS:
+                raise NotImplementedError(f"the two largest classes hold {int(np.sort(counts)[-2:].sum())} rows, more than "
+                                          f"WDX_SVM_FIT_MAX_ROWS = {_lib.SVM_FIT_MAX_ROWS}: subsample them, or fit with solver='libsvm'")
+        elif not (class_weight is None or class_weight == "balanced" or isinstance(class_weight, dict)):
+            raise ValueError(f'class_weight must be None, "balanced" or a dict, not {class_weight!r}')
         if distances is None:
             from .parallel_distances import self_distance_matrix
 
@@ -185,9 +220,23 @@ class DTW_SVM(_ResidentDTWModel):
         else:
             D = np.ascontiguousarray(distances, dtype=np.float32)
         K = np.exp(-gamma * np.power(D, pwr_dist))   # the reference's pdist_kernel on the float32 matrix
-        svc = SVC(kernel="precomputed", probability=True, C=C, random_state=random_state).fit(K, ym)
-        model = cls.from_sklearn(svc, Xm, {i: int(c) for i, c in enumerate(svc.classes_)}, thresholds, window, penalty, gamma=gamma,
-                                 pwr_dist=pwr_dist, block_size=block_size, device=device)
+        if solver == "device":
+            import warnings
+
+            n_support, support, dual, rho, probA, probB, info = _svm_fit.fit_arrays(
+                K, y_idx, classes.size, C * weights, tol, max_iter, random_state,
+                lambda K_, batch, eps, cap: _svm_fit.solve_host(K_, batch, eps, cap, device=device))
+            model = cls(Xm, n_support, support, dual, rho, probA, probB, {i: int(c) for i, c in enumerate(classes)}, thresholds, window,
+                        penalty, gamma=gamma, pwr_dist=pwr_dist, block_size=block_size, device=device)
+            model.fit_info_ = info
+            if (info["state"] != 0).any():
+                warnings.warn(f"DTW_SVM.fit: {int((info['state'] != 0).sum())} of {len(info['state'])} problems did not converge "
+                              f"(states {sorted(set(int(s) for s in info['state']))}: 1 = iteration cap, 2 = stopped)", RuntimeWarning)
+        else:
+            svc = SVC(kernel="precomputed", probability=True, C=C, random_state=random_state, class_weight=class_weight, tol=tol,
+                      max_iter=max_iter).fit(K, ym)
+            model = cls.from_sklearn(svc, Xm, {i: int(c) for i, c in enumerate(svc.classes_)}, thresholds, window, penalty, gamma=gamma,
+                                     pwr_dist=pwr_dist, block_size=block_size, device=device)
         model.n_dropped_ = n - m
         return model
 
