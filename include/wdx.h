@@ -1156,6 +1156,72 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
                       double *d_prob, int32_t *d_pred, double *d_conf, int64_t *d_n_nonfinite, void *d_work,
                       int64_t block_rows, void *stream);
 
+/* ---- training a DTW_MLP on the device: scikit-learn's MLPClassifier(solver="adam") on a float32 distance matrix, in float32, with the
+ *      random draws (initial weights, the epochs' row orders) made by the caller (warpdemux_amd/_mlp_fit.py makes scikit-learn's).
+ *      Layer l = 0 .. n_layers-1 maps sizes[l] -> sizes[l+1] units; sizes[n_layers] = n_classes, or 1 (one logistic unit) for two classes.
+ *
+ *      THE RULE, bit for bit.  Every operation is float32 and rounded on its own (nothing is fused) unless float64 is named.
+ *        input     xs[i][f] = x[i][f]; with mean: xs = (float)((double)xs - mean[f]); with scale: xs = (float)((double)xs / scale[f]).
+ *                  A value of xs that is not finite ends the fit before the first step: state WDX_MLP_FIT_NONFINITE_INPUT.
+ *        epoch e   takes the rows in the order order[e][0 .. m-1] (NULL: 0 .. m-1) in batches of B = min(batch_size, m) rows, the last
+ *                  one of m - (steps-1) B rows; nb = the rows of the batch, step t = 1, 2, ... counts the batches of the whole fit.
+ *        forward   z = sum over k = 0, 1, ... (rising, one chain: a fused multiply-add per term, starting at +0) of a[k] W[k][j]; then
+ *                  z + b[j]; hidden units: relu max(z, 0), tanh (float)tanh((double)z), logistic (float)(1 / (1 + exp(-(double)z))).
+ *        output    softmax: zmax over the columns; e_c = (float)exp((double)(z_c - zmax)); s = e_0 + e_1 + ... in column order;
+ *                  p_c = e_c / s.  One logistic unit: p = (float)(1 / (1 + exp(-(double)z))).
+ *        loss      pc = min(max(p, eps), 1 - eps) with eps = 2^-23 and 1 - eps in float32; a row's loss = (float)-log((double)pc[y]) (one
+ *                  unit: pc for class 1, 1 - pc for class 0).  A workgroup adds the losses of its 16 rows in row order in float64;
+ *                  the host adds the workgroups' sums in batch-row order in float64: ce.
+ *        L2        per step and 16 x 16 tile of every W, BEFORE the update: the float64 sum of w * w (float64 products; the lane sums
+ *                  over its 4 rows, then lanes are added by halving strides 32, 16, ..., 1); the host adds the tiles in layer, tile-row,
+ *                  tile-column order: values.  The step's loss is ce + 0.5 alpha values, the epoch's loss their float64 sum over the
+ *                  steps in order, divided by m.
+ *        delta     output: p_c - (c == y) (one unit: p - y).  Hidden layer l: d = sum over j rising (one chain) of delta_{l+1}[j] W_l[i][j],
+ *                  then relu: 0 where A_l[i] == 0; tanh: d * (1 - A_l[i] * A_l[i]); logistic: (d * A_l[i]) * (1 - A_l[i]).
+ *        gradient  g = sum over the batch rows in row order (one chain) of A_l[r][i] delta_{l+1}[r][j]; g = (g + (float)alpha * w) / (float)nb.
+ *                  Intercepts: g = (delta[0][j] + delta[1][j] + ... in row order) / (float)nb.
+ *        Adam      m = (float)beta1 * m + (float)(1 - beta1) * g;  v = (float)beta2 * v + (float)(1 - beta2) * (g * g);
+ *                  lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) in float64 on the host;
+ *                  w = (float)((double)w + (-lr_t * (double)m) / (double)(sqrtf(v) + (float)epsilon)).
+ *        stop      after each epoch, on the float64 loss: count = loss > best - tol ? count + 1 : 0; best = min(best, loss); the fit ends
+ *                  with state WDX_MLP_FIT_TOL when count > n_iter_no_change, with WDX_MLP_FIT_MAX_EPOCHS after max_epochs epochs, and
+ *                  with WDX_MLP_FIT_NONFINITE_LOSS (the weights of that epoch's end are returned) when the epoch's loss is not finite.
+ *      Two fits of the same inputs return the same bits: there is no atomic operation and no order that depends on timing.
+ *
+ *      Limits (WDX_ERR_UNSUPPORTED beyond them; warpdemux_amd/csrc/wdx_mlp_fit_plan.h states every refusal and lays out the workspace):
+ *      n_layers <= WDX_MLP_MAX_LAYERS, hidden widths <= WDX_MLP_MAX_WIDTH, 2 .. 16 classes, batch_size 1 .. WDX_MLP_FIT_MAX_BATCH, m and
+ *      the loss slots of one epoch within int32.  WDX_ERR_INVALID: a malformed argument, or a class index outside 0 .. n_classes-1
+ *      (found on the device before the first step).  After a refusal or a stated state the context stays usable.
+ *
+ *      wdx_mlp_fit_device BLOCKS: it enqueues 2 n_layers launches per step on `stream` and synchronises it once per epoch (the loss
+ *      slots come back, the stop rule runs, the next order goes up).  d_dist (m, ld) float32 and d_y int32[m] are DEVICE memory; all
+ *      else is HOST memory: mean / scale float64[sizes[0]] (nullable), coefs[l] (sizes[l], sizes[l+1]) and intercepts[l] float32 --
+ *      the initial values in, the trained ones out --, order (max_epochs, m) int32 (nullable; every entry within 0 .. m-1,
+ *      checked on the host before it is uploaded: WDX_ERR_INVALID), loss_curve float64[max_epochs], *n_epochs the epochs run, *state WDX_MLP_FIT_*.  Nothing reads the
+ *      environment.  Timed as WDX_K_MLP_FIT (one event pair per epoch).  wdx_mlp_fit: the same on a HOST matrix and HOST class indices,
+ *      uploaded for the call, on the context's own stream. */
+#define WDX_MLP_FIT_MAX_BATCH 1024
+#define WDX_MLP_FIT_MAX_EPOCHS 0
+#define WDX_MLP_FIT_TOL 1
+#define WDX_MLP_FIT_NONFINITE_INPUT 2
+#define WDX_MLP_FIT_NONFINITE_LOSS 3
+typedef struct wdx_mlp_fit_params {
+    int32_t n_layers;          /* weight matrices, 2..WDX_MLP_MAX_LAYERS                     */
+    int32_t hidden_activation; /* WDX_MLP_ACT_*                                              */
+    int32_t n_classes;         /* 2..16                                                      */
+    int32_t batch_size;        /* 1..WDX_MLP_FIT_MAX_BATCH; beyond m: m                      */
+    int32_t max_epochs;        /* >= 1                                                       */
+    int32_t n_iter_no_change;  /* >= 0                                                       */
+    int32_t sizes[WDX_MLP_MAX_LAYERS + 1];
+    double lr, alpha, beta1, beta2, epsilon, tol;
+} wdx_mlp_fit_params;
+int wdx_mlp_fit_device(wdx_ctx *ctx, const float *d_dist, int64_t m, int64_t ld, const int32_t *d_y, const wdx_mlp_fit_params *p,
+                       const double *mean, const double *scale, float *const *coefs, float *const *intercepts, const int32_t *order,
+                       double *loss_curve, int32_t *n_epochs, int32_t *state, void *stream);
+int wdx_mlp_fit(wdx_ctx *ctx, const float *dist, int64_t m, int64_t ld, const int32_t *y, const wdx_mlp_fit_params *p,
+                const double *mean, const double *scale, float *const *coefs, float *const *intercepts, const int32_t *order,
+                double *loss_curve, int32_t *n_epochs, int32_t *state);
+
 /* ---- classifier tail of Fpt_Boost.predict (models/fpt_boost.py + models/utils.py:45-61): the float64 fingerprint rows
  *      themselves (no DTW, no reference set) -> an ensemble of oblivious (symmetric) trees over float features ->
  *      scale * sum + bias -> softmax (dim == k) or sigmoid (dim == 1, k == 2) -> argmax, label map, top1-top2 margin,
@@ -1266,6 +1332,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_SELF_NEAREST 14     /* leave-one-out nearest neighbours: the pre-pass, the tile kernels and the finish kernel (or the general
                                     route's dispatches and rows kernel) */
 #define WDX_K_SVM_FIT 15          /* the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch */
+#define WDX_K_MLP_FIT 16          /* the trainer of wdx_mlp_fit_device / wdx_mlp_fit: one event pair per epoch around its 2 n_layers launches per step */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

@@ -32,6 +32,7 @@ K_REFINE_OPTIMAL = 12     # fingerprint_refine_optimal_kernel alone (OPT_REFINE_
 K_MEDOID = 13             # per-label medoids: pre-pass, tile kernels (or the general route's chunk sums), reduce kernel
 K_SELF_NEAREST = 14       # leave-one-out nearest neighbours: pre-pass, tile kernels and finish kernel (or the general route's dispatches + rows kernel)
 K_SVM_FIT = 15            # the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch
+K_MLP_FIT = 16            # the MLP trainer (wdx_mlp_fit_device, wdx_mlp_fit): one event pair per epoch, 2 n_layers launches per step
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -99,6 +100,7 @@ EXPORTS = [
     "wdx_dba_step_device", "wdx_dtw_dba_step",
     "wdx_self_nearest_device", "wdx_dtw_self_nearest",
     "wdx_svm_solve_device", "wdx_svm_solve",
+    "wdx_mlp_fit_device", "wdx_mlp_fit",
 ]
 
 
@@ -184,6 +186,22 @@ class SvmModelC(C.Structure):
 # wdx_mlp_model (include/wdx.h)
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_SCALERS = 5, 512, 4
 MLP_ACT = {"identity": 0, "logistic": 1, "tanh": 2, "relu": 3}   # WDX_MLP_ACT_*
+
+
+MLP_FIT_MAX_BATCH = 1024   # WDX_MLP_FIT_MAX_BATCH: rows of one minibatch of wdx_mlp_fit_device / wdx_mlp_fit (beyond: NotImplementedError)
+MLP_FIT_MAX_CLASSES = 16
+MLP_FIT_STATES = ("max_epochs", "tol", "nonfinite_input", "nonfinite_loss")   # WDX_MLP_FIT_*
+
+
+class MlpFitParamsC(C.Structure):
+    """wdx_mlp_fit_params (include/wdx.h)"""
+
+    _fields_ = [
+        ("n_layers", C.c_int32), ("hidden_activation", C.c_int32), ("n_classes", C.c_int32), ("batch_size", C.c_int32),
+        ("max_epochs", C.c_int32), ("n_iter_no_change", C.c_int32), ("sizes", C.c_int32 * (MLP_MAX_LAYERS + 1)),
+        ("lr", C.c_double), ("alpha", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("epsilon", C.c_double),
+        ("tol", C.c_double),
+    ]
 
 
 class MlpModelC(C.Structure):
@@ -591,6 +609,10 @@ def load():
         L.wdx_dtw_dba_step.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp]
         L.wdx_svm_solve_device.restype = C.c_int
         L.wdx_svm_solve_device.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, C.c_double, i64, vp, vp, vp, vp, vp, vp]
+        L.wdx_mlp_fit_device.restype = C.c_int
+        L.wdx_mlp_fit_device.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_mlp_fit.restype = C.c_int
+        L.wdx_mlp_fit.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.wdx_svm_solve.restype = C.c_int
         L.wdx_svm_solve.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, C.c_double, i64, vp, vp, vp, vp, vp]
         _lib = L

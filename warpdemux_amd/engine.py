@@ -529,6 +529,38 @@ class DemuxEngine:
                                                _dp(out.n_iter), _dp(out.state), _dp(out.dec), self._stream()))
         return out
 
+    # -- training the MLP tail on a resident distance matrix (wdx_mlp_fit_device; include/wdx.h states the rule) ---------------
+    def mlp_fit(self, dist, y_idx, coefs, intercepts, *, activation="relu", n_classes=None, mean=None, scale=None, order=None,
+                batch_size=200, max_epochs=200, n_iter_no_change=10, learning_rate_init=1e-3, alpha=1e-4, beta_1=0.9, beta_2=0.999,
+                epsilon=1e-8, tol=1e-4):
+        """`_mlp_fit.FitResult` (host arrays): scikit-learn's ``MLPClassifier(solver="adam")`` trained in float32 on the float32
+        device matrix ``dist`` (m rows, F contiguous columns; a view of a wider tensor keeps its row stride as the leading
+        dimension) and the int32 (m,) device class indices ``y_idx``.  ``coefs`` / ``intercepts``: the HOST initial weights per
+        layer (F -> hidden... -> n_classes, or one unit for two classes; `_mlp_fit.schedule` draws scikit-learn's); ``mean`` /
+        ``scale``: optional HOST float64 (F,) scaler; ``order``: the optional HOST (max_epochs, m) int32 table of the epochs' row
+        orders (None: unshuffled).  ``n_classes`` defaults to the output layer's width (2 for one unit).  The call blocks: it
+        synchronises the current stream once per epoch.  A limit exceeded is NotImplementedError, a malformed argument
+        ValueError, both before anything is launched."""
+        from . import _mlp_fit
+
+        torch = self.torch
+        if (not torch.is_tensor(dist) or dist.dtype != torch.float32 or dist.dim() != 2 or int(dist.shape[0]) < 1 or int(dist.shape[1]) < 1
+                or (int(dist.shape[1]) > 1 and dist.stride(1) != 1) or (int(dist.shape[0]) > 1 and dist.stride(0) < int(dist.shape[1]))):
+            raise ValueError("dist must be a float32 device tensor of m >= 1 rows and F >= 1 contiguous columns")
+        m, F = int(dist.shape[0]), int(dist.shape[1])
+        ld = int(dist.stride(0)) if m > 1 else F
+        if not torch.is_tensor(y_idx) or y_idx.dtype != torch.int32 or tuple(y_idx.shape) != (m,) or not y_idx.is_contiguous():
+            raise ValueError(f"y_idx must be a contiguous int32 ({m},) device tensor")
+        sizes = [F] + [int(np.shape(b)[0]) for b in intercepts]
+        if len(sizes) < 2:
+            raise ValueError("coefs and intercepts must hold at least one layer")
+        k = int(n_classes) if n_classes is not None else (2 if sizes[-1] == 1 else sizes[-1])
+        p = _mlp_fit.params_c(sizes, activation, k, batch_size, max_epochs, n_iter_no_change, learning_rate_init, alpha, beta_1, beta_2,
+                              epsilon, tol)
+        W, B, mean, scale, order = _mlp_fit.check_arrays(sizes, m, coefs, intercepts, mean, scale, order, int(max_epochs))
+        return _mlp_fit.call(self.L.wdx_mlp_fit_device, self.ctx.handle, _dp(dist), m, ld, _dp(y_idx), p, W, B, mean, scale, order,
+                             stream=self._stream())
+
     # -- is a labelled set any good (wdx_self_nearest_device; include/wdx.h states the rule) -----------------------------------
     def loo_nearest(self, X, labels=None, *, window, penalty, status=None):
         """`LooResult` of device tensors: per row of the device fingerprints X (n, L) float64 the nearest other row of its own

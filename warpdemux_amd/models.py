@@ -336,6 +336,139 @@ class DTW_MLP(_ResidentDTWModel):
             n_classes=getattr(model, "n_classes", None), noise_class=getattr(model, "noise_class", False), device=device,
         )
 
+    @classmethod
+    def fit(cls, X, y, window, penalty, refs=None, hidden_layer_sizes=(100,), activation="relu", alpha=1e-4, batch_size="auto",
+            learning_rate_init=1e-3, max_iter=200, tol=1e-4, n_iter_no_change=10, shuffle=True, random_state=0, beta_1=0.9,
+            beta_2=0.999, epsilon=1e-8, scale=True, thresholds=None, status=None, distances=None, solver="device",
+            block_size: Optional[int] = None, device: Optional[int] = None) -> "DTW_MLP":
+        """Train a model on labelled fingerprints ``X`` (n, L), ``y`` (n,) integer barcode labels: the reference's DTW_MLP -- DTW
+        distances to a reference set, a ``StandardScaler``, an ``MLPClassifier(solver="adam")`` -- fitted in float32.
+
+        1. members only: a row with a sample that is not finite, or whose ``status`` (optional, one integer per row) is not 0,
+           is dropped; their number is ``n_dropped_`` of the returned model;
+        2. ``_X`` = ``refs`` (nY, L), for example the barycenters of `parallel_distances.label_barycenters`; ``None``: the
+           members themselves;
+        3. ``D = distance_matrix_to(members, _X, window, penalty)``, unless ``distances`` -- that float32 (m, nY) matrix of the
+           m members -- is given;
+        4. with ``scale``: ``mean_`` / ``scale_`` of a host ``StandardScaler().fit(D)``;
+        5. ``solver="device"``: the initial weights and every epoch's row order are drawn from ``RandomState(random_state)``
+           exactly as scikit-learn draws them (`_mlp_fit.schedule`; a non-negative integer seed), and the engine's trainer
+           (include/wdx.h: wdx_mlp_fit_device states its rule) follows scikit-learn's float32 trajectory with rounding as the only
+           difference.  ``solver="sklearn"``: the ``StandardScaler`` + ``MLPClassifier`` pipeline itself on the host matrix;
+        6. ``label_mapper = {i: classes_[i]}``.
+
+        ``batch_size="auto"`` is scikit-learn's ``min(200, m)``.  The model carries ``loss_curve_`` and ``n_iter_``; a
+        ``RuntimeWarning`` is raised when ``max_iter`` ends the fit with ``tol > 0``.  ``ValueError`` before any device work:
+        bad shapes, fewer than two classes among the members, more than 16 classes, an unknown ``solver`` or ``activation``, a
+        ``tol`` or ``learning_rate_init`` that is not positive; a limit of the trainer exceeded is ``NotImplementedError``
+        (`_lib.MLP_FIT_MAX_BATCH`, the tail's layers and widths).  A distance or scaled input that is not finite is
+        ``ValueError`` once the device has found it."""
+        import warnings
+
+        from . import _medoids, _mlp_fit
+
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] < 1:
+            raise ValueError(f"X must be (n, L) with L >= 1, got shape {X.shape}")
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = X.shape[0]
+        y = np.asarray(y)
+        if y.shape != (n,):
+            raise ValueError(f"y must hold one label per row: shape ({n},), not {y.shape}")
+        if y.dtype.kind not in "iu":
+            raise ValueError(f"y must have an integer dtype, not {y.dtype}")
+        st = _medoids.host_status(n, status)
+        member = np.isfinite(X).all(axis=1)
+        if st is not None:
+            member &= st == 0
+        Xm, ym = np.ascontiguousarray(X[member]), y[member]
+        m = int(member.sum())
+        if refs is None:
+            R = Xm
+        else:
+            R = np.asarray(refs)
+            if R.ndim != 2 or R.shape[1] != X.shape[1] or R.shape[0] < 1:
+                raise ValueError(f"refs must be (nY, {X.shape[1]}) with nY >= 1, got shape {R.shape}")
+            R = np.ascontiguousarray(R, dtype=np.float64)
+        nY = R.shape[0]
+        if distances is not None:
+            distances = np.asarray(distances)
+            if distances.shape != (m, nY):
+                raise ValueError(f"distances must be the ({m}, {nY}) matrix of the {m} members, not {distances.shape}")
+        classes = np.unique(ym)
+        if classes.size < 2:
+            raise ValueError(f"fit needs at least two classes among the members, found {classes.size}")
+        if classes.size > _lib.MLP_FIT_MAX_CLASSES:
+            raise ValueError(f"{classes.size} classes: the resident MLP tail serves at most {_lib.MLP_FIT_MAX_CLASSES}")
+        if thresholds is not None and np.asarray(thresholds).shape != (classes.size,):
+            raise ValueError(f"thresholds must hold one value per class: shape ({classes.size},), not {np.asarray(thresholds).shape}")
+        if solver not in ("device", "sklearn"):
+            raise ValueError(f'solver must be "device" or "sklearn", not {solver!r}')
+        if activation not in _mlp_fit.ACTIVATIONS:
+            raise ValueError(f"unknown activation {activation!r}: one of {_mlp_fit.ACTIVATIONS}")
+        for name, v in (("tol", tol), ("learning_rate_init", learning_rate_init)):
+            if not (np.isscalar(v) and np.isreal(v) and np.isfinite(v) and v > 0):
+                raise ValueError(f"{name} must be positive and finite, not {v!r}")
+        if batch_size == "auto":
+            bs = min(200, m)
+        elif isinstance(batch_size, (int, np.integer)) and batch_size >= 1:
+            bs = int(batch_size)
+        else:
+            raise ValueError(f'batch_size must be "auto" or a positive integer, not {batch_size!r}')
+        y_idx = np.searchsorted(classes, ym).astype(np.int32)
+        mapper = {i: int(c) for i, c in enumerate(classes)}
+        if solver == "device":
+            sizes = _mlp_fit.layer_sizes(nY, hidden_layer_sizes, classes.size)
+            p = _mlp_fit.params_c(sizes, activation, classes.size, bs, max_iter, n_iter_no_change, learning_rate_init, alpha, beta_1,
+                                  beta_2, epsilon, tol)
+            _mlp_fit.check_seed(random_state)
+        if distances is None:
+            from .parallel_distances import distance_matrix_to
+
+            D = distance_matrix_to(Xm, R, window=window, penalty=penalty, n_jobs=1)
+        D = np.ascontiguousarray(D if distances is None else distances, dtype=np.float32)
+        if solver == "sklearn":
+            from sklearn.exceptions import ConvergenceWarning
+            from sklearn.neural_network import MLPClassifier
+            from sklearn.pipeline import make_pipeline
+            from sklearn.preprocessing import StandardScaler
+
+            mlp = MLPClassifier(hidden_layer_sizes=hidden_layer_sizes, activation=activation, solver="adam", alpha=alpha, batch_size=bs,
+                                learning_rate_init=learning_rate_init, max_iter=max_iter, tol=tol, n_iter_no_change=n_iter_no_change,
+                                shuffle=shuffle, random_state=random_state, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
+            est = make_pipeline(StandardScaler(), mlp) if scale else mlp
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", ConvergenceWarning)
+                est.fit(D, y_idx)
+            scalers, mlp = _sklearn_mlp_parts(est)
+            model = cls(R, mlp.coefs_, mlp.intercepts_, activation, mapper, thresholds, window, penalty, scalers=scalers,
+                        n_classes=classes.size, block_size=block_size, out_activation=mlp.out_activation_, device=device)
+            model.loss_curve_, model.n_iter_ = np.asarray(mlp.loss_curve_, dtype=np.float64), int(mlp.n_iter_)
+            hit_cap = model.n_iter_ == max_iter
+        else:
+            mean = scl = None
+            if scale:
+                from sklearn.preprocessing import StandardScaler
+
+                if not np.isfinite(D).all():
+                    raise ValueError("DTW_MLP.fit: a distance is not finite")
+                sc = StandardScaler().fit(D)
+                mean, scl = sc.mean_, sc.scale_
+            W0, B0, order = _mlp_fit.schedule(sizes, activation, random_state, m, int(max_iter), shuffle)
+            W0, B0, mean, scl, order = _mlp_fit.check_arrays(sizes, m, W0, B0, mean, scl, order, int(max_iter))
+            res = _mlp_fit.fit_host(D, y_idx, p, W0, B0, mean, scl, order, device=device)
+            if res.state in ("nonfinite_input", "nonfinite_loss"):
+                raise ValueError("DTW_MLP.fit: " + ("a scaled distance is not finite" if res.state == "nonfinite_input" else
+                                                    f"the loss of epoch {res.n_iter} is not finite"))
+            model = cls(R, res.coefs, res.intercepts, activation, mapper, thresholds, window, penalty,
+                        scalers=[(mean, scl)] if scale else (), n_classes=classes.size, block_size=block_size, device=device)
+            model.loss_curve_, model.n_iter_ = res.loss_curve, res.n_iter
+            hit_cap = res.state == "max_epochs"
+        if hit_cap and tol > 0:
+            warnings.warn(f"DTW_MLP.fit: max_iter = {max_iter} reached and the optimisation has not converged yet", RuntimeWarning)
+        model.n_dropped_ = n - m
+        return model
+
     def num_bcs(self) -> int:
         """dtw_mlp.py:95-100"""
         if self.n_classes is not None:
