@@ -1282,6 +1282,68 @@ int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
                         int32_t *d_refine_idx, int32_t *d_status, double *d_raw, double *d_prob, int32_t *d_pred,
                         double *d_conf, void *d_work, void *stream);
 
+/* ---- training an Fpt_Boost on the device: gradient boosting of oblivious trees on the raw fingerprint, MultiClass with dim == k
+ *      (also for k = 2), emitting exactly the arrays the tail above reads.  The rule is this engine's own (parity with CatBoost's
+ *      trainer is NOT a goal: no ordered boosting, random strength or bootstrap) and is written so that NumPy restates the whole fit
+ *      bit for bit (tests/helpers/boost_fit_rule.py): gradients are quantised to integers, histograms are integer sums (any arrival
+ *      order of the atomics gives the same bits), exp is the stated polynomial, every float64 expression has one operation order and
+ *      nothing is fused.
+ *
+ *      THE RULE.  x = (float)X[row][f], rounded once.  Borders come from the caller (warpdemux_amd/_boost_fit.py: borders makes them
+ *      from the data): per feature n_borders[f] ascending float32 values, 0 .. border_count of them.
+ *        bins      bin[f][row] = the number of the feature's borders with x > border (float32 compare; NaN: 0), uint8.
+ *        per tree, from the scores S (n, k) float64:
+ *        softmax   z_c = S_c - max_c S_c;  e_c = exp_rule(z_c);  sum = e_0 + e_1 + ... in class order;  p_c = e_c / sum.
+ *        exp_rule  (x <= 0)  0 for x < -700; else kk = rint(x * LOG2E), r = (x - kk * LN2_HI) - kk * LN2_LO with fdlibm's
+ *                  LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42feep-1, LN2_LO = 0x1.a39ef35793c76p-33;
+ *                  P = c_13; P = P * r + c_i for i = 12 .. 0 (a multiply, then an add), c_0 = 1, c_i = c_{i-1} / i;  ldexp(P, kk).
+ *        gradient  g_c = (y == c) - p_c;  q_c = (int32)rint(g_c * 2^20), ties to even.
+ *        levels    l = 0 .. depth-1, every row starting in leaf 0.  For every feature f with borders and every border index b, per
+ *                  current leaf: GL_c, NL = the sums of q_c and the row count over the rows with bin <= b, GR_c, NR over bin > b
+ *                  (int64).  score(f, b): acc = 0; for leaf ascending, for class ascending: acc += GL*GL / (NL + lambda), then
+ *                  acc += GR*GR / (NR + lambda), with G and N converted to float64.  The level's split is the first maximum in
+ *                  (f, b) order (ties: the lowest f, then the lowest b).  Then leaf |= (bin[f] > b) << l.
+ *        leaves    V[leaf][c] = lr * (((double)G_c * 2^-20) / ((double)N + lambda)) over the rows of the leaf; an empty leaf gives 0.
+ *        update    S[row][c] = S[row][c] + V[leaf(row)][c].
+ *      The model is scale = 1, bias = 0 and per tree (split_feature, the float32 border borders[f][split_border], nan_true = 0,
+ *      leaves): d_scores after the call is, bit for bit, what the tail's raw scores are on the training rows.
+ *
+ *      Limits (WDX_ERR_UNSUPPORTED beyond them; warpdemux_amd/csrc/wdx_boost_fit_plan.h states every refusal, the workspace and the
+ *      overflow bounds): 1 .. WDX_BOOST_MAX_FEATURES features, 2 .. 16 classes, depth 1 .. WDX_BOOST_FIT_MAX_DEPTH, border_count
+ *      1 .. 255, n 1 .. 2^24, n_trees 1 .. WDX_BOOST_FIT_MAX_TREES, a workspace of at most WDX_BOOST_FIT_MAX_WORKSPACE bytes.
+ *      WDX_ERR_INVALID: lambda <= 0 or not finite, lr not finite, ld < n_features, an n_borders[f] outside 0 .. border_count, no
+ *      feature with a border, a NULL argument, a class index outside 0 .. k-1 (found on the device before the first tree; nothing
+ *      is written then).  After a refusal the context and its resident models stay usable.
+ *
+ *      wdx_boost_fit_device BLOCKS, but synchronises `stream` only before the first tree (the class-index check) and after the last:
+ *      3 * depth + 4 launches per tree, splits and leaves staying on the device in between.  d_X (n, ld) float64, d_y int32[n] and
+ *      d_scores (n, k) float64 are DEVICE memory; d_scores is IN/OUT -- zero it for a fresh fit; a further call continues the fit
+ *      with n_trees more trees.  HOST memory: borders (the features' borders one after another), n_borders int32[n_features], and
+ *      the outputs split_feature / split_border int32[n_trees * depth] (split l of tree t at t * depth + l; split_border is the
+ *      INDEX into the feature's borders) and leaf_values float64[n_trees * 2^depth * k] (leaf-major, class fastest).  Timed as
+ *      WDX_K_BOOST_FIT.  wdx_boost_fit: the same on HOST X, y and scores, uploaded for the call, on the context's own stream. */
+#define WDX_BOOST_FIT_MAX_DEPTH 8
+#define WDX_BOOST_FIT_MAX_BORDERS 255
+#define WDX_BOOST_FIT_MAX_ROWS (1 << 24)
+#define WDX_BOOST_FIT_MAX_TREES (1 << 20)
+#define WDX_BOOST_FIT_MAX_WORKSPACE ((int64_t)4 << 30)
+#define WDX_BOOST_FIT_GRAD_BITS 20   /* q = rint(g * 2^20) */
+#define WDX_BOOST_FIT_ROWS 2047      /* rows per workgroup pass of the histogram kernel: 2047 * 2^20 < 2^31 (int32 LDS partials) */
+typedef struct wdx_boost_fit_params {
+    int32_t n_features;   /* columns of X read, 1..WDX_BOOST_MAX_FEATURES          */
+    int32_t n_classes;    /* k, 2..16                                              */
+    int32_t n_trees;      /* trees added by this call                              */
+    int32_t depth;        /* 1..WDX_BOOST_FIT_MAX_DEPTH                            */
+    int32_t border_count; /* 1..255: no feature has more borders                   */
+    int32_t reserved;     /* 0                                                     */
+    double learning_rate, l2_leaf_reg;
+} wdx_boost_fit_params;
+int wdx_boost_fit_device(wdx_ctx *ctx, const double *d_X, int64_t n, int64_t ld, const int32_t *d_y, const float *borders,
+                         const int32_t *n_borders, const wdx_boost_fit_params *p, double *d_scores, int32_t *split_feature,
+                         int32_t *split_border, double *leaf_values, void *stream);
+int wdx_boost_fit(wdx_ctx *ctx, const double *X, int64_t n, int64_t ld, const int32_t *y, const float *borders, const int32_t *n_borders,
+                  const wdx_boost_fit_params *p, double *scores, int32_t *split_feature, int32_t *split_border, double *leaf_values);
+
 /* ---- multi-GPU: the only exchange on the path ---------------------------------------
  * Reads shard over one process per GPU with no data-path collective; after the last batch the per-barcode
  * call histogram -- the engine's form of the reference's shared run counters `ridx_dict`
@@ -1333,6 +1395,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
                                     route's dispatches and rows kernel) */
 #define WDX_K_SVM_FIT 15          /* the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch */
 #define WDX_K_MLP_FIT 16          /* the trainer of wdx_mlp_fit_device / wdx_mlp_fit: one event pair per epoch around its 2 n_layers launches per step */
+#define WDX_K_BOOST_FIT 17        /* the trainer of wdx_boost_fit_device / wdx_boost_fit: one event pair per call around 1 + n_trees (3 depth + 4) launches, counted as issued (refused for a class index: 1) */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

@@ -33,6 +33,7 @@ K_MEDOID = 13             # per-label medoids: pre-pass, tile kernels (or the ge
 K_SELF_NEAREST = 14       # leave-one-out nearest neighbours: pre-pass, tile kernels and finish kernel (or the general route's dispatches + rows kernel)
 K_SVM_FIT = 15            # the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch
 K_MLP_FIT = 16            # the MLP trainer (wdx_mlp_fit_device, wdx_mlp_fit): one event pair per epoch, 2 n_layers launches per step
+K_BOOST_FIT = 17          # the Fpt_Boost trainer (wdx_boost_fit_device, wdx_boost_fit): one event pair per call, 1 + n_trees (3 depth + 4) launches
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -101,6 +102,7 @@ EXPORTS = [
     "wdx_self_nearest_device", "wdx_dtw_self_nearest",
     "wdx_svm_solve_device", "wdx_svm_solve",
     "wdx_mlp_fit_device", "wdx_mlp_fit",
+    "wdx_boost_fit_device", "wdx_boost_fit",
 ]
 
 
@@ -221,6 +223,22 @@ BOOST_MAX_FEATURES, BOOST_MAX_DEPTH, BOOST_MAX_DIM = 254, 16, 16
 # the tree-parallel kernel (wdx_boost.hip): reads per workgroup, trees per chunk, and the largest batch that takes it by
 # default (WDX_BOOST_SMALL_READS / _TREE_CHUNK / _SMALL_MAX_READS; 0 would mean through OPT_BOOST_KERNEL only)
 BOOST_SMALL_READS, BOOST_TREE_CHUNK, BOOST_SMALL_MAX_READS = 16, 1024, 65536
+
+
+# the Fpt_Boost trainer (WDX_BOOST_FIT_*: deepest tree, most borders per feature, most rows, most trees per call, the workspace
+# cap in bytes, the bits of a quantised gradient, the rows of one histogram workgroup; beyond the limits: NotImplementedError)
+BOOST_FIT_MAX_DEPTH, BOOST_FIT_MAX_BORDERS, BOOST_FIT_MAX_ROWS, BOOST_FIT_MAX_TREES = 8, 255, 1 << 24, 1 << 20
+BOOST_FIT_MAX_WORKSPACE, BOOST_FIT_GRAD_BITS, BOOST_FIT_ROWS = 4 << 30, 20, 2047
+BOOST_FIT_MAX_CLASSES = 16
+
+
+class BoostFitParamsC(C.Structure):
+    """wdx_boost_fit_params (include/wdx.h)"""
+
+    _fields_ = [
+        ("n_features", C.c_int32), ("n_classes", C.c_int32), ("n_trees", C.c_int32), ("depth", C.c_int32), ("border_count", C.c_int32),
+        ("reserved", C.c_int32), ("learning_rate", C.c_double), ("l2_leaf_reg", C.c_double),
+    ]
 
 
 class BoostModelC(C.Structure):
@@ -613,6 +631,10 @@ def load():
         L.wdx_mlp_fit_device.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.wdx_mlp_fit.restype = C.c_int
         L.wdx_mlp_fit.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_boost_fit_device.restype = C.c_int
+        L.wdx_boost_fit_device.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_boost_fit.restype = C.c_int
+        L.wdx_boost_fit.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         L.wdx_svm_solve.restype = C.c_int
         L.wdx_svm_solve.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, C.c_double, i64, vp, vp, vp, vp, vp]
         _lib = L

@@ -43,7 +43,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 17;
+constexpr int kNumTimed = 18;
 
 struct MedoidStage {   // a page-locked block and the event behind the latest copy out of it
     void *host = nullptr;
@@ -112,6 +112,8 @@ struct wdx_ctx {
     wdx::Buffer svm_fit_ws;
     // the MLP trainer (wdx_mlp_fit.hip): the workspace wdx_mlp_fit_plan.h lays out, allocated by the first fit
     wdx::Buffer mlp_fit_ws;
+    // the Fpt_Boost trainer (wdx_boost_fit.hip): the workspace wdx_boost_fit_plan.h lays out, allocated by the first fit
+    wdx::Buffer boost_fit_ws;
     std::vector<wdx::MedoidStage> medoid_staged;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     // the classifier tails (wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model): a slot each, independent of one another

@@ -561,6 +561,38 @@ class DemuxEngine:
         return _mlp_fit.call(self.L.wdx_mlp_fit_device, self.ctx.handle, _dp(dist), m, ld, _dp(y_idx), p, W, B, mean, scale, order,
                              stream=self._stream())
 
+    # -- training the boost tail on resident fingerprints (wdx_boost_fit_device; include/wdx.h states the rule) -------------------
+    def boost_fit(self, X, y_idx, borders, scores, *, n_trees, depth=6, learning_rate=0.1, l2_leaf_reg=3.0, border_count=None):
+        """`_boost_fit.FitTrees` (host arrays) of ``n_trees`` more oblivious trees on the float64 device fingerprints ``X`` (n rows,
+        F contiguous columns; a view of a wider tensor keeps its row stride as the leading dimension), the int32 (n,) device class
+        indices ``y_idx`` and the float64 (n, k) contiguous device ``scores``, which are IN/OUT: zeros for a fresh fit, and a
+        further call continues the fit -- that is how a caller looks at a validation set between blocks of trees.  ``borders``:
+        the HOST list of the features' ascending float32 borders (`_boost_fit.borders` makes them from the data);
+        ``border_count`` defaults to the longest of them.  `_boost_fit.trees_of` turns the result into `models.Fpt_Boost`'s
+        trees.  The call blocks: it synchronises the current stream before the first tree and after the last, never in between.
+        A limit exceeded is NotImplementedError, a malformed argument ValueError, both before any tree is built."""
+        from . import _boost_fit
+
+        torch = self.torch
+        if (not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or int(X.shape[0]) < 1 or int(X.shape[1]) < 1
+                or (int(X.shape[1]) > 1 and X.stride(1) != 1) or (int(X.shape[0]) > 1 and X.stride(0) < int(X.shape[1]))):
+            raise ValueError("X must be a float64 device tensor of n >= 1 rows and F >= 1 contiguous columns")
+        n, F = int(X.shape[0]), int(X.shape[1])
+        ld = int(X.stride(0)) if n > 1 else F
+        if not torch.is_tensor(y_idx) or y_idx.dtype != torch.int32 or tuple(y_idx.shape) != (n,) or not y_idx.is_contiguous():
+            raise ValueError(f"y_idx must be a contiguous int32 ({n},) device tensor")
+        if (not torch.is_tensor(scores) or scores.dtype != torch.float64 or scores.dim() != 2 or int(scores.shape[0]) != n
+                or not scores.is_contiguous()):
+            raise ValueError(f"scores must be a contiguous float64 ({n}, k) device tensor")
+        if len(borders) != F:
+            raise ValueError(f"borders must hold one array per feature: {F}, not {len(borders)}")
+        flat, nb = _boost_fit.pack_borders(borders)
+        if border_count is None:
+            border_count = max(1, int(nb.max()))
+        p = _boost_fit.params_c(F, int(scores.shape[1]), n_trees, depth, border_count, learning_rate, l2_leaf_reg)
+        return _boost_fit.call(self.L.wdx_boost_fit_device, self.ctx.handle, _dp(X), n, ld, _dp(y_idx), flat, nb, p, _dp(scores),
+                               stream=self._stream())
+
     # -- is a labelled set any good (wdx_self_nearest_device; include/wdx.h states the rule) -----------------------------------
     def loo_nearest(self, X, labels=None, *, window, penalty, status=None):
         """`LooResult` of device tensors: per row of the device fingerprints X (n, L) float64 the nearest other row of its own

@@ -692,6 +692,69 @@ class Fpt_Boost:
             return cls.from_json(path, model.label_mapper, model.thresholds, n_classes=getattr(model, "n_classes", None),
                                  noise_class=getattr(model, "noise_class", False), device=device)
 
+    @classmethod
+    def fit(cls, X, y, n_trees=1000, depth=6, learning_rate=0.1, l2_leaf_reg=3.0, border_count=128, label_mapper=None,
+            thresholds=None, status=None, device: Optional[int] = None) -> "Fpt_Boost":
+        """Train a model on labelled fingerprints ``X`` (n, F), ``y`` (n,) integer barcode labels, on the device: gradient
+        boosting of oblivious trees on the raw fingerprint, MultiClass with one value per class and leaf (also for two classes).
+        The rule is this engine's own (include/wdx.h: wdx_boost_fit_device states it bit for bit, tests/helpers/boost_fit_rule.py
+        restates it in NumPy; `_boost_fit` holds the borders rule); parity with CatBoost's trainer is not a goal -- no ordered
+        boosting, random strength or bootstrap, no sample or class weights, no early stopping.
+
+        1. members only: a row whose ``status`` (optional, one integer per row) is not 0 is dropped; their number is
+           ``n_dropped_`` of the returned model.  A NaN feature value is data: it falls into the feature's lowest bin;
+        2. ``borders = _boost_fit.borders(members, border_count)`` on the host;
+        3. ``n_trees`` trees of ``depth`` levels from zero scores through ``wdx_boost_fit``;
+        4. ``label_mapper`` defaults to ``{i: classes[i]}`` of the sorted labels; a given one must map 0 .. k-1 onto them.
+
+        The returned model is resident-ready (``scale = 1``, ``bias = 0``, ``nan_true = 0``) and carries ``train_scores`` (m, k):
+        the trainer's final scores of the members, which are bit for bit what ``predict_raw(members)[0]`` returns, and
+        ``borders_``.  ``ValueError`` / ``NotImplementedError`` before any device work for what `_boost_fit.params_c` names."""
+        from . import _boost_fit, _medoids
+
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] < 1:
+            raise ValueError(f"X must be (n, F) with F >= 1, got shape {X.shape}")
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = X.shape[0]
+        y = np.asarray(y)
+        if y.shape != (n,):
+            raise ValueError(f"y must hold one label per row: shape ({n},), not {y.shape}")
+        if y.dtype.kind not in "iu":
+            raise ValueError(f"y must have an integer dtype, not {y.dtype}")
+        st = _medoids.host_status(n, status)
+        member = np.ones(n, dtype=bool) if st is None else st == 0
+        Xm, ym = np.ascontiguousarray(X[member]), y[member]
+        m = int(member.sum())
+        classes = np.unique(ym)
+        k = int(classes.size)
+        if label_mapper is None:
+            label_mapper = {i: int(c) for i, c in enumerate(classes)}
+            y_idx = np.searchsorted(classes, ym)
+        else:
+            label_mapper = {int(i): int(c) for i, c in dict(label_mapper).items()}
+            if sorted(label_mapper) != list(range(k)) or sorted(label_mapper.values()) != [int(c) for c in classes]:
+                raise ValueError(f"label_mapper must map 0 .. {k - 1} onto the {k} labels among the members")
+            inverse = {c: i for i, c in label_mapper.items()}
+            y_idx = np.array([inverse[int(c)] for c in ym], dtype=np.int64)
+        if thresholds is not None and np.asarray(thresholds).shape != (k,):
+            raise ValueError(f"thresholds must hold one value per class: shape ({k},), not {np.asarray(thresholds).shape}")
+        p = _boost_fit.params_c(X.shape[1], k, n_trees, depth, border_count, learning_rate, l2_leaf_reg)
+        if m > _lib.BOOST_FIT_MAX_ROWS:
+            raise NotImplementedError(f"{m} rows (1..{_lib.BOOST_FIT_MAX_ROWS} supported)")
+        if m < 1:
+            raise ValueError("fit needs at least one member row")
+        border_list = _boost_fit.borders(Xm, border_count)
+        if not any(b.size for b in border_list):
+            raise ValueError("no feature has a border (every column is constant or NaN): nothing to split on")
+        scores = np.zeros((m, k), dtype=np.float64)
+        fit = _boost_fit.fit_host(Xm, y_idx, border_list, p, scores, device=device)
+        model = cls(_boost_fit.trees_of(fit, border_list), X.shape[1], 1.0, np.zeros(k), label_mapper, thresholds, device=device)
+        model.train_scores = scores
+        model.borders_ = border_list
+        model.n_dropped_ = n - m
+        return model
+
     @property
     def is_trained(self):
         return len(self._depth) > 0
