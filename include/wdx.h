@@ -638,6 +638,96 @@ int wdx_svm_solve(wdx_ctx *ctx, const float *K, int64_t m, int64_t ld, const wdx
                   const int32_t *rows, int64_t n_rows, const int32_t *eval_rows, int64_t n_eval, double eps, int64_t max_iter,
                   double *alpha, double *rho, int64_t *n_iter, int32_t *state, double *dec);
 
+/* ---- the kernel matrix of a DTW kernel machine, on the device ------------------------------------------------------------------
+ * K = exp(-gamma D^p) of the float32 self-distance matrix D (m, m) with leading dimension ld (wdx_self_matrix_device leaves it on
+ * the device), so that a fit, a cross-validation or a sweep over gamma never moves a matrix over the bus.
+ *
+ * THE RULE, per entry, in float64 with every operation rounded on its own (nothing is contracted into a fused multiply-add):
+ *     t = (double)D_ij;   w = t, then pwr_dist - 1 times w = w * t;   x = -(gamma * w);
+ *     K_ij = (float)exp_rule(x)   (round to nearest even);   x NaN: K_ij = (float)x, a NaN.
+ * exp_rule is the engine's stated exponential (the one wdx_boost_fit_device's softmax uses):  0 for x < -700;  otherwise
+ *     kk = rint(x * LOG2E);   r = (x - kk * LN2_HI) - kk * LN2_LO;   P = c_13, then for i = 12 .. 0: P = P * r, P = P + c_i;
+ *     exp_rule(x) = ldexp(P, (int)kk)
+ * with LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42feep-1, LN2_LO = 0x1.a39ef35793c76p-33, c_0 = 1 and c_i = c_{i-1} / i.
+ * A distance of +inf therefore gives 0 and a NaN (a row that is no member) gives NaN.  It is NOT numpy.exp: the host route of
+ * models.DTW_SVM.fit computes K with NumPy from a float32 product, and an entry of the two matrices may differ by a few float32
+ * ulps (profiles/svm_cv.json holds the measured distance).
+ *
+ * d_D and d_K are DEVICE memory.  d_K == d_D with ldk == ld is allowed (in place: 65 536 rows need one matrix, not two); any other
+ * overlap of the two is not.  Columns from m on of either matrix are neither read nor written.  Refused before anything is
+ * launched (the context stays usable): m < 1, ld < m, ldk < m, pwr_dist < 1, a gamma that is not positive and finite, a NULL
+ * matrix (WDX_ERR_INVALID); m > WDX_SVM_KERNEL_MAX_ROWS or pwr_dist > WDX_SVM_KERNEL_MAX_POWER (WDX_ERR_UNSUPPORTED).  Enqueued
+ * on `stream`; no synchronisation -- the contract of the *_dev entries (its name ends in _device for the reason wdx_medoids_device
+ * gives; tests/test_gpu_svm_kernel.py holds it to the stream check).  Rows are read and written with 16-byte accesses when
+ * both base pointers are 16-byte aligned and ld and ldk are multiples of four, entry by entry otherwise and at the ragged end of a
+ * row: the same bits either way.  Timed as WDX_K_SVM_KERNEL. */
+#define WDX_SVM_KERNEL_MAX_ROWS 1048576
+#define WDX_SVM_KERNEL_MAX_POWER 16
+int wdx_svm_kernel_device(wdx_ctx *ctx, const float *d_D, int64_t m, int64_t ld, double gamma, int32_t pwr_dist, float *d_K, int64_t ldk,
+                       void *stream);
+
+/* ---- cross-validated probabilities of a DTW kernel machine: behind the decision values ------------------------------------------
+ * A cross-validation on one resident kernel matrix is ONE wdx_svm_solve_device launch (warpdemux_amd/_svm_cv.py states the plan):
+ * every fold's one-vs-one problems and their Platt folds, each pair's full problem naming the fold's held-out rows H_f as its
+ * evaluation rows.  Behind it the host fits probA / probB per (fold, pair) and this entry does, per held-out row, what the resident
+ * tail (wdx_svm_predict_dev) does behind ITS decision values, with the same device code, so that equal decision values and equal
+ * probA / probB give equal bits:  libsvm's sigmoid_predict per pair, clamped to [1e-7, 1 - 1e-7];  libsvm's
+ * multiclass_probability;  pred_idx = np.argmax (the first maximum);  conf = top1 - top2.
+ *
+ * Row i of fold f (the i-th entry of its held-out list, held[held_off[f] + i]) takes pair p's decision value from
+ * d_dec[dec_off[f * pairs + p] + i], pairs = k (k - 1) / 2 in libsvm's order (0, 1), (0, 2), ..; probA / probB [f * pairs + p].
+ * Outputs in MEMBER-ROW order: d_prob (m, k) float64, d_pred_idx int32[m] (the class INDEX: no label map, no threshold),
+ * d_conf float64[m]; a row no fold holds out is not written, a row named twice gets one of its results.  A row with a NaN
+ * decision value (a problem that ended in state 2) gets NaN probabilities, pred_idx -1 and a NaN margin.
+ *
+ * d_dec and the outputs are DEVICE memory; the five tables are HOST memory, read during the call only (checked before anything is
+ * launched, uploaded through a page-locked block of the context).  Refused (WDX_ERR_INVALID; the context stays usable): k outside
+ * 2 .. WDX_SVM_CV_MAX_CLASSES, n_folds outside 1 .. WDX_SVM_CV_MAX_FOLDS, m < 1, a NULL table or output, held_off that does not
+ * start at 0 or decreases, a block outside the n_dec decision values, a held-out row outside 0 .. m-1.  No held-out rows: success.
+ * Enqueued on `stream`; no synchronisation -- the contract of the *_dev entries.  Timed as WDX_K_SVM_CV_COUPLE. */
+#define WDX_SVM_CV_MAX_CLASSES 16
+#define WDX_SVM_CV_MAX_FOLDS 16
+int wdx_svm_cv_couple_device(wdx_ctx *ctx, const double *d_dec, int64_t n_dec, int32_t k, int32_t n_folds, const int64_t *dec_off /* HOST */,
+                          const double *probA /* HOST */, const double *probB /* HOST */, const int32_t *held /* HOST */,
+                          const int64_t *held_off /* HOST */, int64_t m, double *d_prob, int32_t *d_pred_idx, double *d_conf, void *stream);
+
+/* ---- accuracy thresholds from probabilities and labels ---------------------------------------------------------------------------
+ * What a shipped model carries and a fitted one lacked: per predicted class the confidence margin below which a read is left
+ * uncalled (process_probs: `-1` when top1 - top2 < thresholds[pred_idx]), chosen so that the calls that remain reach a target
+ * accuracy on labelled probabilities -- held-out ones, or a whole labelled shard that wdx_demux_svm_dev / wdx_demux_mlp_dev /
+ * wdx_demux_boost_dev left in device memory.  The reference ships such tables (target_accuracy_thresholds/) but not the procedure
+ * that made them: THE RULE below is this engine's own, and it is integer and order-free.
+ *   Rows.        prob (n, k) float64, contiguous; y_idx int32[n].  A row is USED when y_idx >= 0 and each of its k probabilities is
+ *                finite; the others are counted in `skipped`.  (A y_idx >= k is used, and no prediction hits it.)
+ *   Prediction.  p = the first maximum of the row; conf = top1 - top2 in float64, top2 the largest of the other k - 1 entries.
+ *   Grid.        g_i = (double)i / (double)R for i = 0 .. R, one IEEE division each.  bin = the largest i with g_i <= conf (conf
+ *                >= 0 = g_0; a conf beyond 1 lands in bin R).
+ *   Histograms.  N[p][bin] += 1;  H[p][bin] += (p == y_idx).
+ *   Suffix sums. kept[c][j] = the sum of N[c][b] over b >= j;  hit[c][j] = the same of H: the rows called c whose margin is at
+ *                least g_j, and those of them that are right.
+ *   Threshold.   thr[t][c] = g_j for the SMALLEST j in 1 .. R with kept[c][j] > 0 and 1000 * hit[c][j] >= targets_pm[t] *
+ *                kept[c][j] (int64: exact); +inf when no j qualifies -- every read called c is then left uncalled.  j >= 1: the
+ *                reference's tables bottom out at 0.01.
+ * Limits (WDX_ERR_INVALID outside them, before anything is launched; the context stays usable): 0 <= n, 2 <= k <=
+ * WDX_THRESHOLDS_MAX_CLASSES, 1 <= resolution R <= WDX_THRESHOLDS_MAX_RESOLUTION, 1 <= n_targets <= WDX_THRESHOLDS_MAX_TARGETS,
+ * 0 <= targets_pm[t] <= 1000 (per mille); n > WDX_THRESHOLDS_MAX_ROWS is WDX_ERR_UNSUPPORTED.
+ *
+ * wdx_accuracy_thresholds_device: d_prob, d_y_idx and the outputs are DEVICE memory; targets_pm is HOST memory, read during the call
+ * only.  d_thr (n_targets, k) float64 is required; d_kept and d_hit, (k, R + 1) int64 each, and d_skipped, one int64, are
+ * nullable (the context keeps what the caller does not want).  Enqueued on `stream`; no synchronisation -- the contract of the
+ * *_dev entries.  All sums are integers added by integer atomics: two runs give the same bits.  Timed as WDX_K_THRESHOLDS. */
+#define WDX_THRESHOLDS_MAX_CLASSES 16
+#define WDX_THRESHOLDS_MAX_RESOLUTION 4096
+#define WDX_THRESHOLDS_MAX_TARGETS 16
+#define WDX_THRESHOLDS_MAX_ROWS 1099511627776
+int wdx_accuracy_thresholds_device(wdx_ctx *ctx, const double *d_prob, int64_t n, int32_t k, const int32_t *d_y_idx, int32_t resolution,
+                                const int32_t *targets_pm /* HOST */, int32_t n_targets, double *d_thr, int64_t *d_kept, int64_t *d_hit,
+                                int64_t *d_skipped, void *stream);
+/* Host form: every array HOST memory (kept, hit and skipped nullable); one synchronisation.  The device copies live for the call
+ * only. */
+int wdx_accuracy_thresholds(wdx_ctx *ctx, const double *prob, int64_t n, int32_t k, const int32_t *y_idx, int32_t resolution,
+                            const int32_t *targets_pm, int32_t n_targets, double *thr, int64_t *kept, int64_t *hit, int64_t *skipped);
+
 /* Pipelined form of wdx_demux_batch for the reference's worker loop (file_proc.py:380-454: fill minibatch k+1
  * while minibatch k is processed; 1197-1243: several such workers share one GPU).  A context has WDX_MAX_SLOTS slots (the
  * worker loop uses two; a feeder that serves many producers keeps more minibatches in flight), each with its own stream
@@ -1396,6 +1486,9 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_SVM_FIT 15          /* the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch */
 #define WDX_K_MLP_FIT 16          /* the trainer of wdx_mlp_fit_device / wdx_mlp_fit: one event pair per epoch around its 2 n_layers launches per step */
 #define WDX_K_BOOST_FIT 17        /* the trainer of wdx_boost_fit_device / wdx_boost_fit: one event pair per call around 1 + n_trees (3 depth + 4) launches, counted as issued (refused for a class index: 1) */
+#define WDX_K_SVM_KERNEL 18       /* the kernel matrix of wdx_svm_kernel_device: its one launch */
+#define WDX_K_SVM_CV_COUPLE 20    /* the out-of-fold probabilities of wdx_svm_cv_couple_device: its one launch */
+#define WDX_K_THRESHOLDS 19       /* wdx_accuracy_thresholds_device / wdx_accuracy_thresholds: one event pair around the histogram pass and the selection (n == 0: the selection alone) */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

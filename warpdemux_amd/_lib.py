@@ -34,6 +34,9 @@ K_SELF_NEAREST = 14       # leave-one-out nearest neighbours: pre-pass, tile ker
 K_SVM_FIT = 15            # the batched SMO solve (wdx_svm_solve_device, wdx_svm_solve): its one launch
 K_MLP_FIT = 16            # the MLP trainer (wdx_mlp_fit_device, wdx_mlp_fit): one event pair per epoch, 2 n_layers launches per step
 K_BOOST_FIT = 17          # the Fpt_Boost trainer (wdx_boost_fit_device, wdx_boost_fit): one event pair per call, 1 + n_trees (3 depth + 4) launches
+K_SVM_KERNEL = 18         # the kernel matrix of wdx_svm_kernel_device: its one launch
+K_SVM_CV_COUPLE = 20      # the out-of-fold probabilities of wdx_svm_cv_couple_device: its one launch
+K_THRESHOLDS = 19         # accuracy thresholds (wdx_accuracy_thresholds_device, wdx_accuracy_thresholds): the histogram pass and the selection
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -68,6 +71,10 @@ OPT_SELF_NEAREST_GENERAL = 28   # diagnostic: leave-one-out neighbours through t
 SVM_FIT_MAX_ROWS = 16384   # WDX_SVM_FIT_MAX_ROWS: rows of one problem of wdx_svm_solve_device / wdx_svm_solve (beyond: NotImplementedError in Python)
 # (threads, rows per thread) of the solver's instantiations (wdx_svm_fit_plan.h: kSvmFitKernels); a call runs the smallest that holds its largest problem
 SVM_FIT_KERNELS = ((64, 4), (256, 8), (1024, 16))
+SVM_KERNEL_MAX_ROWS = 1 << 20   # WDX_SVM_KERNEL_MAX_ROWS
+SVM_KERNEL_MAX_POWER = 16       # WDX_SVM_KERNEL_MAX_POWER: pwr_dist of wdx_svm_kernel_device (beyond: NotImplementedError)
+SVM_CV_MAX_FOLDS = 16   # WDX_SVM_CV_MAX_FOLDS
+THRESHOLDS_MAX_CLASSES, THRESHOLDS_MAX_RESOLUTION, THRESHOLDS_MAX_TARGETS = 16, 4096, 16   # WDX_THRESHOLDS_MAX_*
 DBA_MAX_L = 1024   # WDX_DBA_MAX_L: longest series of wdx_dba_step_device / wdx_dtw_dba_step (beyond: NotImplementedError)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
@@ -103,6 +110,8 @@ EXPORTS = [
     "wdx_svm_solve_device", "wdx_svm_solve",
     "wdx_mlp_fit_device", "wdx_mlp_fit",
     "wdx_boost_fit_device", "wdx_boost_fit",
+    "wdx_svm_kernel_device", "wdx_svm_cv_couple_device",
+    "wdx_accuracy_thresholds_device", "wdx_accuracy_thresholds",
 ]
 
 
@@ -637,6 +646,14 @@ def load():
         L.wdx_boost_fit.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         L.wdx_svm_solve.restype = C.c_int
         L.wdx_svm_solve.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, C.c_double, i64, vp, vp, vp, vp, vp]
+        L.wdx_svm_kernel_device.restype = C.c_int
+        L.wdx_svm_kernel_device.argtypes = [vp, vp, i64, i64, C.c_double, C.c_int32, vp, i64, vp]
+        L.wdx_svm_cv_couple_device.restype = C.c_int
+        L.wdx_svm_cv_couple_device.argtypes = [vp, vp, i64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+        L.wdx_accuracy_thresholds_device.restype = C.c_int
+        L.wdx_accuracy_thresholds_device.argtypes = [vp, vp, i64, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.wdx_accuracy_thresholds.restype = C.c_int
+        L.wdx_accuracy_thresholds.argtypes = [vp, vp, i64, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
         _lib = L
         return L
 

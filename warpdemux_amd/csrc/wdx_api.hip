@@ -605,7 +605,7 @@ void wdx_ctx_destroy(wdx_ctx *ctx) {
     medoid_release_staged(ctx, true);
     for (Buffer *b : {&ctx->refs_pad, &ctx->refs_T, &ctx->refs_nan, &ctx->in0, &ctx->in1, &ctx->in2,
                       &ctx->in3, &ctx->out0, &ctx->out1, &ctx->out2, &ctx->out3, &ctx->tmp0,
-                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm.block, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->fp_opt, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->adc_stage, &ctx->nearest_buf, &ctx->medoid_ws, &ctx->self_ws, &ctx->loo_ws, &ctx->dba_ws, &ctx->svm_fit_ws, &ctx->mlp_fit_ws, &ctx->boost_fit_ws, &ctx->svm_refs, &ctx->mlp.block, &ctx->boost.block,
+                      &ctx->tmp1, &ctx->tmp2, &ctx->scratch, &ctx->fp_ws, &ctx->svm.block, &ctx->ref_buf, &ctx->fp_big, &ctx->fp_long, &ctx->fp_opt, &ctx->ref_ws, &ctx->pk_idx, &ctx->in_adc, &ctx->adc_stage, &ctx->nearest_buf, &ctx->medoid_ws, &ctx->self_ws, &ctx->loo_ws, &ctx->dba_ws, &ctx->svm_fit_ws, &ctx->mlp_fit_ws, &ctx->boost_fit_ws, &ctx->thr_ws, &ctx->svm_cv_ws, &ctx->svm_refs, &ctx->mlp.block, &ctx->boost.block,
                       &ctx->mb_dwell, &ctx->mb_stats, &ctx->mb_prob, &ctx->mb_pred, &ctx->mb_conf, &ctx->mb_ridx})
         b->release();
     ctx->pin_in.release();

@@ -19,6 +19,7 @@
 //   boost_fit_score_kernel      S += V[leaf]; zeroes the leaf sums
 #include "wdx_ctx.h"
 #include "wdx_boost_fit_plan.h"
+#include "wdx_exp_rule.h"
 
 #include <math.h>
 
@@ -32,21 +33,6 @@ namespace {
 static_assert(kBoostFitThreads == 256 && WDX_BOOST_FIT_MAX_BORDERS + 1 <= kBoostFitThreads && WDX_BOOST_MAX_FEATURES <= kBoostFitThreads,
               "one thread per border, one per feature");
 constexpr int kCh = kBoostFitMaxClasses + 1;
-
-// exp(x) for x <= 0 by the stated rule: every multiply and add rounded on its own (the build has -ffp-contract=off)
-__device__ __forceinline__ double exp_rule(double x) {
-    if (x < -700.0) return 0.0;
-    constexpr BoostFitExpCoef C;
-    const double kk = rint(x * kBoostFitLog2e);
-    const double r = (x - kk * kBoostFitLn2Hi) - kk * kBoostFitLn2Lo;
-    double P = C.c[kBoostFitExpDegree];
-#pragma unroll
-    for (int i = kBoostFitExpDegree - 1; i >= 0; --i) {
-        P = P * r;
-        P = P + C.c[i];
-    }
-    return ldexp(P, (int)kk);
-}
 
 // grid (ceil(n / 256), F).  flags[1] |= 1 when a class index lies outside 0 .. k-1
 __global__ __launch_bounds__(kBoostFitThreads) void boost_fit_binarise_kernel(const double *X, int64_t n, int64_t ld, const float *borders,

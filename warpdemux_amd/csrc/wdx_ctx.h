@@ -43,7 +43,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 18;
+constexpr int kNumTimed = 21;
 
 struct MedoidStage {   // a page-locked block and the event behind the latest copy out of it
     void *host = nullptr;
@@ -114,6 +114,10 @@ struct wdx_ctx {
     wdx::Buffer mlp_fit_ws;
     // the Fpt_Boost trainer (wdx_boost_fit.hip): the workspace wdx_boost_fit_plan.h lays out, allocated by the first fit
     wdx::Buffer boost_fit_ws;
+    // accuracy thresholds (wdx_thresholds.hip): the histograms and the skipped count a caller did not ask for (wdx_thresholds_plan.h)
+    wdx::Buffer thr_ws;
+    // out-of-fold probabilities (wdx_svm_cv.hip): the tables of a call (uploaded through the medoid calls' staged blocks)
+    wdx::Buffer svm_cv_ws;
     std::vector<wdx::MedoidStage> medoid_staged;
     int64_t refs_gen = 0;  // bumped whenever the resident reference set (samples or window/penalty) changes
     // the classifier tails (wdx_svm_set_model, wdx_mlp_set_model, wdx_boost_set_model): a slot each, independent of one another

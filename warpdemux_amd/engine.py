@@ -148,6 +148,21 @@ class SvmSolveResult:
     dec: "object"          # torch float64 (len(eval_rows),)  decision values of the evaluation rows
 
 
+@dataclass
+class SvmCvResult:
+    prob: "object"         # torch float64 (m, k)  out-of-fold probabilities, member-row order (NaN: a problem of the row's fold stopped)
+    pred_idx: "object"     # torch int32 (m,)  np.argmax of them (the class INDEX; -1 with NaN probabilities)
+    conf: "object"         # torch float64 (m,)  top1 - top2
+    fold_of_row: "object"  # numpy int32 (m,)  the fold that holds the row out
+    folds: list            # per fold (n_support, support, dual_coef, rho, probA, probB); support numbers the rows of train[f]
+    train: list            # per fold T_f: the member rows it was fitted on, ascending
+    held: list             # per fold H_f
+    fit_info: dict         # per problem of the one launch: pair, fold (-1: a full problem), part (fold, or cv: the full data), rows, n_iter, state
+    full: "object"         # with_full: the full data's (n_support, support, dual_coef, rho, probA, probB), else None
+    plan: "object"         # the `_svm_cv.CvPlan`
+    solution: "object"     # the `_svm_fit.Solution` (host arrays) of the one launch
+
+
 class DemuxEngine:
     """One engine per process per GPU.  ``refs``: (nY, L) float64 reference fingerprints
     (model._X in the reference, models/dtw_base.py:20).  ``wide_dtw``: effective windows 33 .. L (``window=None`` on
@@ -528,6 +543,108 @@ class DemuxEngine:
                                                _lib.ptr(eval_rows), len(eval_rows), float(eps), int(max_iter), _dp(out.alpha), _dp(out.rho),
                                                _dp(out.n_iter), _dp(out.state), _dp(out.dec), self._stream()))
         return out
+
+    # -- the kernel matrix of a kernel machine from the resident self-distance matrix (wdx_svm_kernel_device; include/wdx.h states the rule)
+    def svm_kernel(self, D, gamma, pwr_dist=1, out=None):
+        """float32 (m, m) device tensor ``K = exp_rule(-(gamma * D ** pwr_dist))`` of the float32 device distances ``D`` (m rows, at
+        least m contiguous columns; a view of a wider tensor keeps its row stride as the leading dimension; `self_distances`
+        leaves such a matrix on the device).  ``out``: a float32 device tensor of the same kind; ``out=D`` works in place.  The
+        exponential is the engine's stated ``exp_rule`` (include/wdx.h) of a float64 product, not ``numpy.exp`` of a float32
+        one: an entry may differ from the host route's by a few float32 ulps.  A distance of +inf gives 0, a NaN gives NaN.  Enqueues on the current stream; does not
+        synchronise."""
+        torch = self.torch
+
+        def matrix(t, name):
+            if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or int(t.shape[0]) < 1 or int(t.shape[1]) < int(t.shape[0])
+                    or (int(t.shape[1]) > 1 and t.stride(1) != 1) or (int(t.shape[0]) > 1 and t.stride(0) < int(t.shape[1]))):
+                raise ValueError(f"{name} must be a float32 device tensor of m >= 1 rows and at least m contiguous columns")
+            return int(t.stride(0)) if int(t.shape[0]) > 1 else int(t.shape[1])
+
+        ld = matrix(D, "D")
+        m = int(D.shape[0])
+        if out is None:
+            out = torch.empty((m, m), dtype=torch.float32, device=self.tdev)
+        ldk = matrix(out, "out")
+        if int(out.shape[0]) != m:
+            raise ValueError(f"out must have {m} rows, not {int(out.shape[0])}")
+        if int(pwr_dist) != pwr_dist:
+            raise ValueError(f"pwr_dist must be an integer, not {pwr_dist!r}")
+        _lib.check(self.L.wdx_svm_kernel_device(self.ctx.handle, _dp(D), m, ld, float(gamma), int(pwr_dist), _dp(out), ldk, self._stream()))
+        return out[:, :m]
+
+    # -- cross-validated probabilities on a resident kernel matrix (_svm_cv states the plan; wdx_svm_cv_couple_device the tail) ------
+    def svm_cross_val(self, K, y_idx, k, C=1.0, class_weight=None, tol=1e-3, max_iter=-1, random_state=0, cv=5, with_full=False,
+                      classes=None):
+        """`SvmCvResult`: ``cv``-fold out-of-fold probabilities of a precomputed-kernel SVC on the float32 device kernel matrix
+        ``K`` (as for `svm_solve`) and the HOST class numbers ``y_idx`` (0 .. k-1, one per row of ``K``).  Every fold's
+        one-vs-one problems, their Platt folds and, with ``with_full``, the full data's own fit are ONE `svm_solve` launch
+        (`_svm_cv` states the folds and the plan); the host then fits ``probA`` / ``probB`` per fold (`_svm_fit.sigmoid_train`)
+        and wdx_svm_cv_couple_device turns the held-out decision values into probabilities with the resident tail's own code.
+        ``classes``: the k labels a ``class_weight`` dict names (default 0 .. k-1).  A class with fewer than ``cv`` members is
+        ValueError before any device work.  The call blocks: it synchronises the current stream once, behind the solve."""
+        from . import _svm_cv, _svm_fit
+
+        torch = self.torch
+        y_idx = np.asarray(y_idx)
+        k = int(k)
+        if y_idx.ndim != 1 or y_idx.dtype.kind not in "iu" or (len(y_idx) and (y_idx.min() < 0 or y_idx.max() >= k)):
+            raise ValueError(f"y_idx must hold one class number 0 .. {k - 1} per row")
+        if not 2 <= k <= _lib.SVM_MAX_CLASSES:
+            raise ValueError(f"k = {k} classes (2..{_lib.SVM_MAX_CLASSES})")
+        if not torch.is_tensor(K) or K.dim() != 2 or int(K.shape[0]) != len(y_idx):
+            raise ValueError(f"K must be a device matrix of {len(y_idx)} rows, one per entry of y_idx")
+        for name, v in (("tol", tol), ("C", C)):
+            if not (np.isscalar(v) and np.isreal(v) and np.isfinite(v) and v > 0):
+                raise ValueError(f"{name} must be positive and finite, not {v!r}")
+        if not isinstance(random_state, (int, np.integer)) or random_state < 0:
+            raise ValueError(f"random_state must be a non-negative integer, not {random_state!r}")
+        classes = np.arange(k) if classes is None else np.asarray(classes)
+        _svm_fit.effective_max_iter(max_iter, 0)
+        p = _svm_cv.plan(y_idx, k, float(C), class_weight, classes, int(random_state), cv, with_full)
+        _svm_fit.check_batch(p.batch)
+        dev = self.svm_solve(K, p.batch.problems, p.batch.rows, p.batch.eval_rows, eps=float(tol),
+                             max_iter=_svm_fit.effective_max_iter(max_iter, _svm_cv.largest_problem(p)))
+        sol = _svm_fit.Solution(*(t.cpu().numpy() for t in (dev.alpha, dev.rho, dev.n_iter, dev.state, dev.dec)))
+        parts = [_svm_cv.part_arrays(p, g, y_idx, sol) for g in range(len(p.sub))]
+        off, A, B, held, held_off = _svm_cv.couple_tables(p, [a[4] for a in parts[:p.cv]], [a[5] for a in parts[:p.cv]])
+        m = len(y_idx)
+        prob = torch.full((m, k), float("nan"), dtype=torch.float64, device=self.tdev)
+        pred = torch.full((m,), -1, dtype=torch.int32, device=self.tdev)
+        conf = torch.full((m,), float("nan"), dtype=torch.float64, device=self.tdev)
+        _lib.check(self.L.wdx_svm_cv_couple_device(self.ctx.handle, _dp(dev.dec), int(dev.dec.numel()), k, p.cv, _lib.ptr(off), _lib.ptr(A),
+                                                _lib.ptr(B), _lib.ptr(held), _lib.ptr(held_off), m, _dp(prob), _dp(pred), _dp(conf),
+                                                self._stream()))
+        return SvmCvResult(prob=prob, pred_idx=pred, conf=conf, fold_of_row=p.fold_of_row, folds=parts[:p.cv], train=p.train, held=p.held,
+                           fit_info=_svm_cv.fit_info(p, sol), full=parts[p.cv] if with_full else None, plan=p, solution=sol)
+
+    # -- per-class confidence thresholds from labelled probabilities (wdx_accuracy_thresholds_device; include/wdx.h states the rule) --
+    def accuracy_thresholds(self, prob, y_idx, targets=(0.99,), resolution=100):
+        """``(thr (T, k) float64, kept (k, R + 1) int64, hit (k, R + 1) int64, skipped int64 ())`` device tensors: per target
+        accuracy and predicted class the smallest margin ``j / R`` (j >= 1) at which the rows called that class with at least
+        that margin reach the target, ``+inf`` where none does -- a row of ``thr`` is a ``thresholds=`` vector of a model.
+        ``prob``: a contiguous float64 (n, k) device tensor -- what `demux_svm` / `demux_mlp` / `demux_boost` or `svm_predict`
+        left on the device, or held-out probabilities; ``y_idx``: the int32 (n,) device class indices (negative: the row is
+        skipped, like a row with a probability that is not finite).  ``targets``: fractions that are whole numbers of per
+        mille (ValueError otherwise).  ``kept`` / ``hit``: the suffix sums the rule selects from.  Enqueues on the current
+        stream; does not synchronise."""
+        from . import _thresholds
+
+        torch = self.torch
+        if not torch.is_tensor(prob) or prob.dtype != torch.float64 or prob.dim() != 2 or not prob.is_contiguous():
+            raise ValueError("prob must be a contiguous float64 (n, k) device tensor")
+        n, k = int(prob.shape[0]), int(prob.shape[1])
+        if not torch.is_tensor(y_idx) or y_idx.dtype != torch.int32 or tuple(y_idx.shape) != (n,) or not y_idx.is_contiguous():
+            raise ValueError(f"y_idx must be a contiguous int32 ({n},) device tensor")
+        R = int(resolution)
+        _thresholds.check_sizes(k, R)
+        pm = _thresholds.targets_per_mille(targets)
+        thr = torch.empty((len(pm), k), dtype=torch.float64, device=self.tdev)
+        kept = torch.empty((k, R + 1), dtype=torch.int64, device=self.tdev)
+        hit = torch.empty((k, R + 1), dtype=torch.int64, device=self.tdev)
+        skipped = torch.empty((), dtype=torch.int64, device=self.tdev)
+        _lib.check(self.L.wdx_accuracy_thresholds_device(self.ctx.handle, _dp(prob), n, k, _dp(y_idx), R, _lib.ptr(pm), len(pm), _dp(thr),
+                                                      _dp(kept), _dp(hit), _dp(skipped), self._stream()))
+        return thr, kept, hit, skipped
 
     # -- training the MLP tail on a resident distance matrix (wdx_mlp_fit_device; include/wdx.h states the rule) ---------------
     def mlp_fit(self, dist, y_idx, coefs, intercepts, *, activation="relu", n_classes=None, mean=None, scale=None, order=None,

@@ -75,3 +75,50 @@ def predictions_frame(read_ids, y_pred, y_prob, conf, label_mapper):
 def save_predictions(predictions, filename: str) -> None:
     """barcode_predictions_<batch>.csv.gz (file_proc.py:757-766): no index column, gzip."""
     predictions.to_csv(filename, index=False, compression="gzip")
+
+
+# ---- target_accuracy_thresholds/<model>.csv: per barcode, the confidence threshold that reaches each target accuracy ----------
+
+def _target_column(t) -> str:
+    """0.95 -> '95_0', 0.999 -> '99_9': per cent, an underscore, the tenth."""
+    pm = int(round(float(t) * 1000))
+    if abs(float(t) * 1000 - pm) > 1e-6 or not 0 <= pm <= 1000:
+        raise ValueError(f"a target accuracy must be a whole number of per mille in 0 .. 1, not {t!r}")
+    return f"{pm // 10}_{pm % 10}"
+
+
+def write_accuracy_thresholds(path: str, label_mapper, table, targets) -> None:
+    """The layout of the reference's ``target_accuracy_thresholds/*.csv``: header ``true_barcode,95_0,...,99_9`` (one column per
+    target), one row per barcode label in ``label_mapper``'s index order, values in their shortest round-trip form (``0.4``,
+    ``inf``).  ``table``: (T, k), a row per target -- what `models.accuracy_thresholds` and
+    `DemuxEngine.accuracy_thresholds` return."""
+    table = np.asarray(table, dtype=np.float64)
+    targets = list(np.atleast_1d(targets))
+    mapper = {int(i): int(c) for i, c in dict(label_mapper).items()}
+    if table.shape != (len(targets), len(mapper)) or sorted(mapper) != list(range(len(mapper))):
+        raise ValueError(f"table must be (targets, classes) = ({len(targets)}, {len(mapper)}), not {table.shape}")
+    lines = [",".join(["true_barcode"] + [_target_column(t) for t in targets])]
+    for i in range(len(mapper)):
+        lines.append(",".join([str(mapper[i])] + [repr(float(v)) for v in table[:, i]]))
+    with open(path, "w", newline="") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def read_accuracy_thresholds(path: str):
+    """(label_mapper {i: barcode}, table float64 (T, k), targets: list of T fractions) of such a file."""
+    with open(path, newline="") as f:
+        rows = [ln.rstrip("\r\n").split(",") for ln in f if ln.strip()]
+    if not rows or rows[0][0] != "true_barcode" or len(rows[0]) < 2:
+        raise ValueError(f"{path}: the header must be true_barcode,<target>,...")
+    targets = []
+    for name in rows[0][1:]:
+        whole, _, tenth = name.partition("_")
+        if not (whole.isdigit() and tenth.isdigit() and len(tenth) == 1):
+            raise ValueError(f"{path}: '{name}' is no target column (95_0 .. 99_9)")
+        targets.append((int(whole) * 10 + int(tenth)) / 1000)
+    body = rows[1:]
+    if any(len(r) != len(rows[0]) for r in body):
+        raise ValueError(f"{path}: every row must hold {len(rows[0])} fields")
+    mapper = {i: int(r[0]) for i, r in enumerate(body)}
+    table = np.array([[float(v) for v in r[1:]] for r in body], dtype=np.float64).reshape(len(body), len(targets)).T
+    return mapper, np.ascontiguousarray(table), targets

@@ -133,7 +133,7 @@ class DTW_SVM(_ResidentDTWModel):
     @classmethod
     def fit(cls, X, y, window, penalty, gamma=1.0, pwr_dist=1, C=1.0, thresholds=None, status=None, distances=None,
             random_state=0, block_size: Optional[int] = None, device: Optional[int] = None, class_weight=None, solver="libsvm",
-            tol=1e-3, max_iter=-1) -> "DTW_SVM":
+            tol=1e-3, max_iter=-1, target_accuracy=0.99, cv=5) -> "DTW_SVM":
         """Train a model on labelled fingerprints ``X`` (n, L), ``y`` (n,) integer barcode labels -- what the reference's
         training does (models/dtw_svm.py: ``pdist_kernel`` on the training set's own distance matrix, then a precomputed-kernel
         ``SVC`` with probabilities), with the matrix from the engine's symmetric self-distance kernels.
@@ -159,6 +159,19 @@ class DTW_SVM(_ResidentDTWModel):
         libsvm fit's.  A pair of more than ``_lib.SVM_FIT_MAX_ROWS`` rows is ``NotImplementedError``.  The model carries
         ``fit_info_`` (per problem: pair, fold, rows, iterations, state), and a ``RuntimeWarning`` is raised when a problem's
         state is not 0.
+
+        ``thresholds="cv"`` (``solver="device"`` only, ``ValueError`` otherwise) returns a DEPLOYABLE model, one with the
+        per-class confidence thresholds every shipped model carries: the self-distance matrix, the kernel matrix and the solve
+        stay on the device, the full data's problems and the ``cv`` outer folds' (`_svm_cv` states the folds) are one launch,
+        and ``thresholds`` are those that reach ``target_accuracy`` (a whole number of per mille) on the out-of-fold
+        probabilities -- the engine's own rule (include/wdx.h: wdx_accuracy_thresholds_device; the reference ships threshold tables
+        but not the procedure behind them).  The model keeps ``cv_``: ``prob`` / ``pred`` / ``conf`` / ``fold`` as
+        `cross_val_predict` returns them, the ``(1, k)`` table ``thresholds``, ``kept`` / ``hit`` / ``skipped`` and ``target``.
+        On this route ``K`` comes from the engine's stated ``exp_rule`` (include/wdx.h: wdx_svm_kernel_device), not from
+        ``numpy.exp``, and its argument is a float64 product: measured on a 16 384-row matrix (profiles/svm_cv.json), an entry lies
+        at most 3 float32 ulps from step 3's and the decision values of the two fits differ by at most 5.8e-4, inside the
+        stopping gap ``tol`` = 1e-3.  A class with
+        fewer than ``cv`` members is ``ValueError``.
 
         ``ValueError`` before any device work: fewer than two classes among the members, more than 16 classes (the limit of
         the resident SVM tail), a ``y``, ``status`` or ``distances`` of the wrong shape, an unknown ``solver`` or
@@ -192,10 +205,15 @@ class DTW_SVM(_ResidentDTWModel):
             raise ValueError(f"fit needs at least two classes among the members, found {classes.size}")
         if classes.size > _lib.SVM_MAX_CLASSES:
             raise ValueError(f"{classes.size} classes: the resident SVM tail serves at most {_lib.SVM_MAX_CLASSES}")
-        if thresholds is not None and np.asarray(thresholds).shape != (classes.size,):
+        want_cv = isinstance(thresholds, str)
+        if want_cv and thresholds != "cv":
+            raise ValueError(f'thresholds must be None, one value per class or "cv", not {thresholds!r}')
+        if not want_cv and thresholds is not None and np.asarray(thresholds).shape != (classes.size,):
             raise ValueError(f"thresholds must hold one value per class: shape ({classes.size},), not {np.asarray(thresholds).shape}")
         if solver not in ("libsvm", "device"):
             raise ValueError(f'solver must be "libsvm" or "device", not {solver!r}')
+        if want_cv and solver != "device":
+            raise ValueError('thresholds="cv" needs solver="device"')
         if solver == "device":
             from . import _svm_fit
 
@@ -213,6 +231,29 @@ class DTW_SVM(_ResidentDTWModel):
                                           f"WDX_SVM_FIT_MAX_ROWS = {_lib.SVM_FIT_MAX_ROWS}: subsample them, or fit with solver='libsvm'")
         elif not (class_weight is None or class_weight == "balanced" or isinstance(class_weight, dict)):
             raise ValueError(f'class_weight must be None, "balanced" or a dict, not {class_weight!r}')
+        if want_cv:
+            from . import _svm_cv, _thresholds
+
+            _svm_cv.check_cv(cv, counts)
+            target = _thresholds.targets_per_mille([target_accuracy])
+            res = _svm_cv_on_device(Xm, y_idx, classes, window, penalty, gamma, pwr_dist, C, class_weight, tol, max_iter, random_state, cv,
+                                    True, device, distances=distances, targets=[target_accuracy])
+            n_support, support, dual, rho, probA, probB = res["full"]
+            model = cls(Xm, n_support, support, dual, rho, probA, probB, {i: int(c) for i, c in enumerate(classes)}, res["thresholds"][0],
+                        window, penalty, gamma=gamma, pwr_dist=pwr_dist, block_size=block_size, device=device)
+            info = res["fit_info"]
+            full = info["part"] == cv
+            model.fit_info_ = {"pairs": info["pairs"], **{key: info[key][full] for key in ("pair", "fold", "rows", "n_iter", "state")}}
+            model.cv_ = {key: res[key] for key in ("prob", "pred", "conf", "fold", "thresholds", "kept", "hit", "skipped")}
+            model.cv_["target"] = int(target[0]) / 1000
+            model.cv_["fit_info"] = info
+            if (info["state"] != 0).any():
+                import warnings
+
+                warnings.warn(f"DTW_SVM.fit: {int((info['state'] != 0).sum())} of {len(info['state'])} problems did not converge "
+                              f"(states {sorted(set(int(s) for s in info['state']))}: 1 = iteration cap, 2 = stopped)", RuntimeWarning)
+            model.n_dropped_ = n - m
+            return model
         if distances is None:
             from .parallel_distances import self_distance_matrix
 
@@ -239,6 +280,40 @@ class DTW_SVM(_ResidentDTWModel):
                                      pwr_dist=pwr_dist, block_size=block_size, device=device)
         model.n_dropped_ = n - m
         return model
+
+    @classmethod
+    def cross_val_predict(cls, X, y, window, penalty, gamma=1.0, pwr_dist=1, C=1.0, class_weight=None, tol=1e-3, max_iter=-1,
+                          random_state=0, cv=5, status=None, device: Optional[int] = None):
+        """``(y_prob float64 (m, k), y_pred int64 (m,), conf float64 (m,), fold int32 (m,))`` on the m member rows (as `fit`
+        finds them): every row's probabilities from the model of the fold that holds it out -- what a threshold is calibrated
+        on.  The self-distance matrix, the kernel matrix (``exp_rule``: see `fit`) and the one batched solve of all ``cv`` folds
+        stay on the device; over the bus come the solve's results for `_svm_fit.sigmoid_train`, and these four arrays.
+        ``y_pred`` holds labels (columns of ``y_prob``: the sorted labels), -1 where a problem of the row's fold stopped (NaN
+        probabilities).  The folds are the engine's own (`_svm_cv`), seeded by ``random_state``.  A class with fewer than
+        ``cv`` members (2 <= cv <= 10) is ``ValueError`` before any device work."""
+        from . import _medoids, _svm_cv
+
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] < 1:
+            raise ValueError(f"X must be (n, L) with L >= 1, got shape {X.shape}")
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = X.shape[0]
+        y = np.asarray(y)
+        if y.shape != (n,) or y.dtype.kind not in "iu":
+            raise ValueError(f"y must hold one integer label per row: shape ({n},)")
+        st = _medoids.host_status(n, status)
+        member = np.isfinite(X).all(axis=1)
+        if st is not None:
+            member &= st == 0
+        Xm, ym = np.ascontiguousarray(X[member]), y[member]
+        classes = np.unique(ym)
+        if not 2 <= classes.size <= _lib.SVM_MAX_CLASSES:
+            raise ValueError(f"{classes.size} classes among the members (2..{_lib.SVM_MAX_CLASSES})")
+        y_idx = np.searchsorted(classes, ym)
+        _svm_cv.check_cv(cv, np.bincount(y_idx))
+        res = _svm_cv_on_device(Xm, y_idx, classes, window, penalty, gamma, pwr_dist, C, class_weight, tol, max_iter, random_state, cv, False,
+                                device)
+        return res["prob"], res["pred"], res["conf"], res["fold"]
 
     @property
     def num_bcs(self):
@@ -823,3 +898,63 @@ def from_reference(model, device: Optional[int] = None):
     if name == "Fpt_Boost":
         return Fpt_Boost.from_reference(model, device=device)
     raise NotImplementedError(f"no device model for {name} (DTW_SVM, DTW_MLP and Fpt_Boost are supported)")
+
+
+def _svm_cv_on_device(Xm, y_idx, classes, window, penalty, gamma, pwr_dist, C, class_weight, tol, max_iter, random_state, cv, with_full,
+                      device, distances=None, targets=None):
+    """What `DTW_SVM.cross_val_predict` and ``DTW_SVM.fit(thresholds="cv")`` share: D, K = exp_rule(-(gamma D^p)) in place, the one
+    solve and the coupling on the device -> host arrays (and, with ``targets``, the thresholds of the out-of-fold probabilities)."""
+    import torch
+
+    from .engine import DemuxEngine
+
+    eng = DemuxEngine(np.zeros((1, Xm.shape[1])), 15, 0.1, device=int(device) if device is not None else 0)
+    try:
+        with torch.cuda.device(eng.tdev):
+            if distances is None:
+                D = eng.self_distances(torch.tensor(Xm, device=eng.tdev), window, penalty)
+            else:
+                D = torch.tensor(np.ascontiguousarray(distances, dtype=np.float32), device=eng.tdev)
+            K = eng.svm_kernel(D, gamma, pwr_dist, out=D)
+            r = eng.svm_cross_val(K, y_idx, len(classes), C, class_weight, tol, max_iter, random_state, cv, with_full, classes=classes)
+            pred_idx = r.pred_idx.cpu().numpy()
+            out = {"prob": r.prob.cpu().numpy(), "conf": r.conf.cpu().numpy(), "fold": r.fold_of_row.copy(), "fit_info": r.fit_info,
+                   "full": r.full, "pred": np.where(pred_idx >= 0, np.asarray(classes)[np.maximum(pred_idx, 0)], -1).astype(np.int64)}
+            if targets is not None:
+                thr, kept, hit, skipped = eng.accuracy_thresholds(r.prob, torch.tensor(np.asarray(y_idx, dtype=np.int32), device=eng.tdev), targets)
+                out.update(thresholds=thr.cpu().numpy(), kept=kept.cpu().numpy(), hit=hit.cpu().numpy(), skipped=int(skipped))
+            return out
+    finally:
+        eng.close()
+
+
+def accuracy_thresholds(y_prob, y, label_mapper, targets=(0.99,), resolution=100, device: Optional[int] = None):
+    """Per-class confidence thresholds from labelled probabilities the caller holds -- held-out rows of a `DTW_MLP` or an
+    `Fpt_Boost`, say: float64 (k,) for one target, (T, k) for a sequence of them, usable as ``thresholds=`` of any of the three
+    classes.  ``y_prob``: (n, k) host probabilities, columns in ``label_mapper``'s order; ``y``: the rows' true labels (a label
+    ``label_mapper`` does not name, -1 for instance, leaves its row out, like a probability that is not finite);
+    ``targets``: accuracies as fractions that are whole numbers of per mille (0.95, 0.999; ValueError otherwise).
+
+    The rule is the engine's own (include/wdx.h: wdx_accuracy_thresholds_device; the reference ships threshold tables but not the
+    procedure behind them): with ``conf = top1 - top2`` binned on the grid ``j / resolution``, a class's threshold is the smallest
+    ``j / resolution``, j >= 1, at which the rows called that class with at least that margin are right in at least the target
+    share of cases, and ``+inf`` -- no read of that class is called -- where no margin reaches it.  Runs on the device."""
+    from . import _thresholds
+
+    y_prob = np.ascontiguousarray(y_prob, dtype=np.float64)
+    if y_prob.ndim != 2:
+        raise ValueError(f"y_prob must be (n, k), not {y_prob.shape}")
+    n, k = y_prob.shape
+    mapper = {int(i): int(c) for i, c in dict(label_mapper).items()}
+    if sorted(mapper) != list(range(k)):
+        raise ValueError(f"label_mapper must map 0 .. {k - 1}, one entry per column of y_prob")
+    y = np.asarray(y)
+    if y.shape != (n,):
+        raise ValueError(f"y must hold one label per row: shape ({n},), not {y.shape}")
+    y_idx = np.full(n, -1, dtype=np.int32)
+    for i, c in mapper.items():
+        y_idx[y == c] = i
+    single = np.ndim(targets) == 0
+    pm = _thresholds.targets_per_mille(targets)
+    thr, _, _, _ = _thresholds.host(y_prob, y_idx, pm, resolution, device=device)
+    return thr[0] if single else thr
