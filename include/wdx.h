@@ -451,8 +451,10 @@ int wdx_dtw_nearest(wdx_ctx *ctx, const double *X, int64_t nX, const int32_t *re
  *
  * wdx_medoids_device: dX, d_status and every output are DEVICE memory; d_status, d_medoid_cost, d_count, d_cost (float64[n]) and
  * d_refs are nullable; `label` is HOST memory, read during the call only.  Enqueued on `stream`; no synchronisation -- the
- * contract of the *_dev entries (its name does not end in _dev because tests/test_gpu_buffer_bounds.py keeps a closed table of
- * those; tests/test_gpu_medoids.py holds this entry to the same stream and bounds checks). */
+ * contract of the *_dev entries.  The entries whose names end in _device are the training entries; they have a closed table of
+ * their own (tests/helpers/device_entries.py: one row per entry with its arguments by role and their exact sizes), which
+ * tests/test_gpu_device_entries.py holds to exact buffers, workspace states and the stream contract, as
+ * tests/test_gpu_buffer_bounds.py and tests/test_gpu_streams.py hold the table of the *_dev names. */
 #define WDX_MEDOID_MAX_GROUP 32768
 int wdx_medoids_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *label /* HOST */, int64_t n_labels,
                        const int32_t *d_status, int32_t window, double penalty, int64_t *d_medoid, double *d_medoid_cost,
@@ -481,8 +483,7 @@ int wdx_dtw_medoids(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const i
  * warpdemux_amd/csrc/wdx_self_plan.h.
  *
  * wdx_self_matrix_device: dX, d_status and d_out are DEVICE memory.  Enqueued on `stream`; no synchronisation -- the contract of
- * the *_dev entries (its name does not end in _dev for the reason wdx_medoids_device gives; tests/test_gpu_self_matrix.py holds
- * this entry to the same stream and bounds checks). */
+ * the *_dev entries (a row of the table of the _device entries: wdx_medoids_device says where it is held). */
 #define WDX_SELF_MATRIX_MAX_ROWS 65536
 int wdx_self_matrix_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *d_status, int32_t window,
                            double penalty, float *d_out, int64_t ld, void *stream);
@@ -516,8 +517,8 @@ int wdx_dtw_self_matrix(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, con
  * Workspace: context-owned, grow-only and bounded, see warpdemux_amd/csrc/wdx_loo_plan.h.
  *
  * wdx_self_nearest_device: every array is DEVICE memory (d_label and d_status nullable).  Enqueued on `stream`; no
- * synchronisation -- the contract of the *_dev entries (its name ends in _device for the reason wdx_medoids_device gives;
- * tests/test_gpu_loo.py holds this entry to the same stream and bounds checks). */
+ * synchronisation -- the contract of the *_dev entries (a row of the table of the _device entries: wdx_medoids_device says where it
+ * is held). */
 int wdx_self_nearest_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *d_label, const int32_t *d_status,
                             int32_t window, double penalty, int32_t *d_nn, float *d_best, void *stream);
 /* Host form: every array HOST memory; one synchronisation. */
@@ -562,8 +563,8 @@ int wdx_dtw_self_nearest(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, co
  *
  * wdx_dba_step_device: dX, d_status, d_centres and every output are DEVICE memory; d_status, d_count, d_inertia, d_cost and d_runs
  * are nullable; d_new must not overlap d_centres; `label` is HOST memory, read during the call only.  Enqueued on `stream`; no
- * synchronisation -- the contract of the *_dev entries (its name ends in _device for the reason wdx_medoids_device gives;
- * tests/test_gpu_dba.py holds this entry to the same stream and bounds checks). */
+ * synchronisation -- the contract of the *_dev entries (a row of the table of the _device entries: wdx_medoids_device says where it
+ * is held). */
 #define WDX_DBA_MAX_L 1024
 int wdx_dba_step_device(wdx_ctx *ctx, const double *dX, int64_t n, int64_t L, const int32_t *label /* HOST */, int64_t n_labels,
                         const int32_t *d_status, const double *d_centres, int32_t window, double penalty, double *d_new,
@@ -618,7 +619,9 @@ int wdx_dtw_dba_step(wdx_ctx *ctx, const double *X, int64_t n, int64_t L, const 
  * wdx_svm_solve_device: d_K and the five outputs are DEVICE memory; the problem table and the two lists are HOST memory, read
  * during the call only (a row index is checked before it can reach a kernel; the call uploads them through a page-locked block
  * of the context, as wdx_medoids_device does its labels).  Enqueued on `stream`; no synchronisation -- the contract of the *_dev
- * entries (tests/test_gpu_svm_fit.py holds this entry to the stream check).  Outputs of different problems must not overlap;
+ * entries (a row of the table of the _device entries: wdx_medoids_device says where it is held).  Only K[r * ld + c] with r and c
+ * among the rows and evaluation rows named is read: columns m .. ld-1 of K are never read, and K ends on element (m-1) ld + m - 1.
+ * Outputs of different problems must not overlap;
  * d_alpha is the solve's working storage too (what it held before the call is ignored, and it must not be read before the call's
  * work on the stream has run).  Timed as WDX_K_SVM_FIT. */
 #define WDX_SVM_FIT_MAX_ROWS 16384
@@ -657,8 +660,8 @@ int wdx_svm_solve(wdx_ctx *ctx, const float *K, int64_t m, int64_t ld, const wdx
  * overlap of the two is not.  Columns from m on of either matrix are neither read nor written.  Refused before anything is
  * launched (the context stays usable): m < 1, ld < m, ldk < m, pwr_dist < 1, a gamma that is not positive and finite, a NULL
  * matrix (WDX_ERR_INVALID); m > WDX_SVM_KERNEL_MAX_ROWS or pwr_dist > WDX_SVM_KERNEL_MAX_POWER (WDX_ERR_UNSUPPORTED).  Enqueued
- * on `stream`; no synchronisation -- the contract of the *_dev entries (its name ends in _device for the reason wdx_medoids_device
- * gives; tests/test_gpu_svm_kernel.py holds it to the stream check).  Rows are read and written with 16-byte accesses when
+ * on `stream`; no synchronisation -- the contract of the *_dev entries (a row of the table of the _device entries: wdx_medoids_device
+ * says where it is held).  Rows are read and written with 16-byte accesses when
  * both base pointers are 16-byte aligned and ld and ldk are multiples of four, entry by entry otherwise and at the ragged end of a
  * row: the same bits either way.  Timed as WDX_K_SVM_KERNEL. */
 #define WDX_SVM_KERNEL_MAX_ROWS 1048576
@@ -1284,7 +1287,8 @@ int wdx_demux_mlp_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off
  *      (found on the device before the first step).  After a refusal or a stated state the context stays usable.
  *
  *      wdx_mlp_fit_device BLOCKS: it enqueues 2 n_layers launches per step on `stream` and synchronises it once per epoch (the loss
- *      slots come back, the stop rule runs, the next order goes up).  d_dist (m, ld) float32 and d_y int32[m] are DEVICE memory; all
+ *      slots come back, the stop rule runs, the next order goes up).  d_dist (m, ld) float32 and d_y int32[m] are DEVICE memory
+ *      (columns sizes[0] .. ld-1 of d_dist are never read: it ends on element (m-1) ld + sizes[0] - 1); all
  *      else is HOST memory: mean / scale float64[sizes[0]] (nullable), coefs[l] (sizes[l], sizes[l+1]) and intercepts[l] float32 --
  *      the initial values in, the trained ones out --, order (max_epochs, m) int32 (nullable; every entry within 0 .. m-1,
  *      checked on the host before it is uploaded: WDX_ERR_INVALID), loss_curve float64[max_epochs], *n_epochs the epochs run, *state WDX_MLP_FIT_*.  Nothing reads the
@@ -1406,7 +1410,8 @@ int wdx_demux_boost_dev(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_o
  *      is written then).  After a refusal the context and its resident models stay usable.
  *
  *      wdx_boost_fit_device BLOCKS, but synchronises `stream` only before the first tree (the class-index check) and after the last:
- *      3 * depth + 4 launches per tree, splits and leaves staying on the device in between.  d_X (n, ld) float64, d_y int32[n] and
+ *      3 * depth + 4 launches per tree, splits and leaves staying on the device in between.  Columns n_features .. ld-1 of d_X are
+ *      never read (it ends on element (n-1) ld + n_features - 1).  d_X (n, ld) float64, d_y int32[n] and
  *      d_scores (n, k) float64 are DEVICE memory; d_scores is IN/OUT -- zero it for a fresh fit; a further call continues the fit
  *      with n_trees more trees.  HOST memory: borders (the features' borders one after another), n_borders int32[n_features], and
  *      the outputs split_feature / split_border int32[n_trees * depth] (split l of tree t at t * depth + l; split_border is the

@@ -648,7 +648,8 @@ def test_the_lists_were_used():
 
 
 def test_the_table_names_every_device_entry():
-    """every wdx_*_dev of the library that computes for a caller has a row here; a new entry without one fails"""
+    """every wdx_*_dev of the library that computes for a caller has a row here; a new entry without one fails
+    (the wdx_*_device entries have the sibling table tests/helpers/device_entries.py)"""
     diagnostics = ("profile", "selftest_", "calib_read", "synth_")
     lib = {e for e in _lib.EXPORTS if e.endswith("_dev") and not any(d in e for d in diagnostics)}
     fused = {"wdx_%s_dev" % v[0] for v in FUSED.values()}
