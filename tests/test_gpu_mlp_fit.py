@@ -8,7 +8,11 @@ prints its figures before it asserts; `measure` returns them (tools/bench_mlp_fi
 
 The shapes are the smallest at which a kernel takes another path: a last batch of 11 rows (no multiple of 16 or 4); one logistic
 output unit behind two hidden layers; every dimension a whole tile; 16 classes with batch 1 and with a batch beyond m; a fan-in of
-2 601 (the long k chain); each of the four activations; no shuffling; no scaler; a leading dimension beyond F."""
+2 601 (the long k chain); each of the four activations; no shuffling; no scaler; a leading dimension beyond F.  Beyond these twelve,
+22 cases (34 in all) run the rest of the accepted domain: seven at its edges (five weight matrices, hidden widths 1, 3, 5 and 512,
+the step from four to five tiles, every dimension 1, a batch of WDX_MLP_FIT_MAX_BATCH rows), six with a hyper-parameter away from
+scikit-learn's default (HYPER), and nine that read the gradient out (RO: see there and tests/test_mlp_fit_readout_host.py).  A fit
+whose loss is not finite ends with its state."""
 import ctypes as C
 import functools
 import os
@@ -44,6 +48,54 @@ CASES = {
     "203x19-no-scaler": (203, 19, (17,), 5, "relu", 64, 6, True, False, 0),
     "203x19-ld-beyond-F": (203, 19, (17,), 5, "relu", 64, 6, True, True, 13),
 }
+# name: keyword arguments given both to MLPClassifier and to DemuxEngine.mlp_fit; a case without an entry runs scikit-learn's defaults
+HYPER = {}
+
+# The accepted domain beyond the shapes above (default hyper-parameters): five weight matrices with deltas for l = 1 .. 4 and widths
+# below four; a hidden layer of one unit; all eight accumulators of a wave and a forward LDS beyond 64 KB; the delta kernel and 1 024
+# Adam tiles at 512 x 512; the step from four to five tiles; every dimension 1; WDX_MLP_FIT_MAX_BATCH rows in one chain.
+CASES.update({
+    "max-depth-relu": (150, 9, (20, 3, 33, 5), 4, "relu", 64, 4, True, True, 0),
+    "max-depth-tanh-1unit": (150, 9, (17, 16, 15, 1), 2, "tanh", 64, 4, True, True, 0),
+    "width-512": (120, 7, (512,), 3, "relu", 50, 3, True, True, 0),
+    "width-512x512-logistic": (100, 5, (512, 512), 16, "logistic", 48, 2, True, True, 0),
+    "width-64x65": (90, 6, (64, 65), 3, "relu", 32, 4, True, True, 0),
+    "tiny-2x1-1": (2, 1, (1,), 2, "tanh", 1, 6, True, True, 0),
+    "batch-1024": (1030, 6, (8,), 3, "relu", 1024, 3, True, True, 0),
+})
+
+# Each hyper-parameter alone at a value of its own (two swapped fields cannot cancel), and all five together.
+_BASE = (203, 19, (17,), 5, None, 64, 6, True, True, 0)
+for _name, _act, _kw in [
+    ("alpha-0.5", "relu", dict(alpha=0.5)),
+    ("lr-0.02", "relu", dict(learning_rate_init=0.02)),
+    ("beta1-0", "tanh", dict(beta_1=0.0)),
+    ("beta2-0.9", "tanh", dict(beta_2=0.9)),
+    ("epsilon-1e-3", "tanh", dict(epsilon=1e-3)),
+    ("hyper-mixed-logistic", "logistic", dict(alpha=0.03, learning_rate_init=0.004, beta_1=0.7, beta_2=0.95, epsilon=1e-5)),
+]:
+    CASES[_name] = _BASE[:4] + (_act,) + _BASE[5:]
+    HYPER[_name] = _kw
+
+# Gradient read-out.  With epsilon = 1e-8 Adam's m / (sqrt(v) + epsilon) does not change when a gradient element is scaled, so the
+# cases above cannot see a wrong divisor, a mis-scaled alpha w or a moment carried with the wrong weight
+# (tests/test_mlp_fit_readout_host.py measures that blind spot).  Under RO the update is -g / (|g| + 1), monotone in g: the result
+# reads out every element of every gradient.  37 rows, 19 -> 17 -> 33: every dimension a ragged tile, nb no multiple of 4.
+RO = dict(alpha=0.0, learning_rate_init=1.0, beta_1=0.0, beta_2=0.0, epsilon=1.0)
+_RO_BASE = (37, 19, (17, 33), 5, "tanh", 200, 1, True, True, 0)
+for _act in ("relu", "tanh", "logistic", "identity"):
+    CASES["readout-" + _act] = _RO_BASE[:4] + (_act,) + _RO_BASE[5:]
+    HYPER["readout-" + _act] = RO
+_MOMENTS = dict(alpha=0.0, learning_rate_init=1.0, beta_1=0.5, beta_2=0.25, epsilon=1.0)
+for _name, _spec, _kw in [
+    ("readout-1unit-alpha", (37, 19, (17, 33), 2, "tanh", 200, 1, True, True, 0), dict(RO, alpha=0.5)),   # alpha w at full weight
+    ("readout-two-steps", (37, 19, (17, 33), 5, "tanh", 26, 1, True, True, 0), RO),   # 26 and 11 rows: the divisor is nb
+    ("readout-moments", (37, 19, (17, 33), 5, "tanh", 26, 2, True, True, 0), _MOMENTS),   # both moments at visible weight
+    ("readout-moments-alpha", (37, 19, (17, 33), 5, "logistic", 26, 2, True, True, 0), dict(_MOMENTS, alpha=0.5, learning_rate_init=0.25)),
+    ("readout-batch-1024", (1030, 6, (8,), 3, "tanh", 1024, 1, True, True, 0), RO),   # the 1 024-row chain
+]:
+    CASES[_name] = _spec
+    HYPER[_name] = _kw
 
 
 def _imports():
@@ -90,15 +142,20 @@ def _flat(coefs, intercepts):
     return np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in list(coefs) + list(intercepts)])
 
 
-@functools.lru_cache(maxsize=None)
 def reference(name):
     """The case's inputs and both scikit-learn runs, computed once and shared: the exact run (float64) and the float32 run."""
-    m, F, hidden, k, act, batch, epochs, shuffle, scaled, _ = CASES[name]
+    return reference_of(CASES[name], tuple(sorted(HYPER.get(name, {}).items())))
+
+
+@functools.lru_cache(maxsize=None)
+def reference_of(spec, hyper=()):
+    """`reference` of a case given as its tuple and its sorted hyper-parameter items"""
+    m, F, hidden, k, act, batch, epochs, shuffle, scaled, _ = spec
     D, y = distances(m, F, k)
     mean, scale = scaler_of(D) if scaled else (None, None)
     Xs = mlp_ref.scale([(mean, scale)], D)
-    sk64 = sklearn_fit(Xs.astype(np.float64), y, hidden, act, batch, epochs, shuffle)
-    sk32 = sklearn_fit(Xs, y, hidden, act, batch, epochs, shuffle)
+    sk64 = sklearn_fit(Xs.astype(np.float64), y, hidden, act, batch, epochs, shuffle, **dict(hyper))
+    sk32 = sklearn_fit(Xs, y, hidden, act, batch, epochs, shuffle, **dict(hyper))
     assert sk32.coefs_[0].dtype == np.float32 and sk64.coefs_[0].dtype == np.float64
     th64, th32 = _flat(sk64.coefs_, sk64.intercepts_), _flat(sk32.coefs_, sk32.intercepts_)
     l64, l32 = np.asarray(sk64.loss_curve_, np.float64), np.asarray(sk32.loss_curve_, np.float64)
@@ -117,6 +174,7 @@ def device_fit(eng, name, **over):
     wide = torch.full((m, F + ld_extra), float("nan"), dtype=torch.float32, device=eng.tdev)
     wide[:, :F] = torch.from_numpy(np.array(R["D"])).to(eng.tdev)
     kw = dict(activation=act, n_classes=k, mean=R["mean"], scale=R["scale"], order=order, batch_size=batch, max_epochs=epochs)
+    kw.update(HYPER.get(name, {}))
     kw.update(over)
     return eng.mlp_fit(wide[:, :F], torch.from_numpy(np.array(R["y"])).to(eng.tdev), W0, B0, **kw)
 
@@ -130,8 +188,9 @@ def measure(eng, name):
     ok_len = len(res.loss_curve) == len(R["l64"])
     err_loss = float(np.abs(res.loss_curve - R["l64"]).max()) if ok_len else float("nan")
     return dict(case=name, e_ref=R["e_ref"], max_abs_theta=float(np.abs(R["th64"]).max()), T=R["T"], device_err=err,
-                ratio_to_e_ref=err / R["e_ref"] if R["e_ref"] else float("nan"), e_ref_loss=R["e_loss"], T_loss=R["T_loss"],
-                device_err_loss=err_loss, ratio_loss=err_loss / R["e_loss"] if R["e_loss"] else float("nan"), n_iter=res.n_iter,
+                ratio_to_e_ref=err / R["e_ref"] if R["e_ref"] else float("nan"), ratio_to_T=err / R["T"], e_ref_loss=R["e_loss"],
+                T_loss=R["T_loss"], device_err_loss=err_loss, ratio_loss=err_loss / R["e_loss"] if R["e_loss"] else float("nan"),
+                ratio_loss_to_T=err_loss / R["T_loss"], hyper=dict(HYPER.get(name, {})), n_iter=res.n_iter,
                 state=res.state, finite=bool(np.isfinite(th).all()), float32=all(a.dtype == np.float32 for a in res.coefs + res.intercepts))
 
 
@@ -180,6 +239,20 @@ def test_kernel_time_counts_the_launches(eng):
         eng.kernel_timing(False)
     m, batch, epochs, nl = 530, 200, 6, 3
     assert launches == epochs * -(-m // batch) * 2 * nl and ms > 0, (ms, launches)
+
+
+def test_kernel_time_counts_the_launches_of_five_layers(eng):
+    name = "max-depth-relu"
+    eng.kernel_timing(True)
+    try:
+        eng.kernel_time_reset()
+        device_fit(eng, name)
+        ms, launches = eng.kernel_time(_lib.K_MLP_FIT)
+    finally:
+        eng.kernel_timing(False)
+    m, _, hidden, _, _, batch, epochs = CASES[name][:7]
+    nl = len(hidden) + 1
+    assert nl == _lib.MLP_MAX_LAYERS == 5 and launches == epochs * -(-m // batch) * 2 * nl == 120 and ms > 0, (ms, launches)
 
 
 # ---- a model served as fitted ---------------------------------------------------------------------------------------------------------
@@ -328,6 +401,37 @@ def test_a_nan_row_ends_the_fit_with_its_state_and_the_context_stays_usable(eng)
     # the context is usable: the case itself still meets its contract
     f = measure(eng, name)
     assert f["device_err"] <= f["T"], f
+
+
+def test_a_loss_that_is_not_finite_ends_the_fit_with_its_state_and_the_context_stays_usable(eng):
+    """learning_rate_init = 1e38: the first step moves every weight by about 1e38, the second step's products overflow and its loss
+    is NaN.  That is arithmetic, not a fault: the fit ends after epoch 1 with WDX_MLP_FIT_NONFINITE_LOSS."""
+    from helpers import mlp_fit_rule as rule
+
+    name, epochs, lr = "203x19-17-5-last-batch-11", 3, 1e38
+    m, F, hidden, k, act, batch, _, shuffle, _, _ = CASES[name]
+    R = reference(name)
+    sizes = _mlp_fit.layer_sizes(F, hidden, k)
+    W0, B0, order = _mlp_fit.schedule(sizes, act, SEED, m, epochs, shuffle)
+    # the float32 rule itself gives a loss that is not finite for epoch 1: otherwise the input is wrong, not the device
+    Xs = mlp_ref.scale([(R["mean"], R["scale"])], R["D"])
+    for ordered in (True, False):
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            curve = rule.fit(Xs, np.array(R["y"]), k, W0, B0, order, activation=act, batch_size=batch, lr=lr, max_epochs=epochs, ordered=ordered)[2]
+        print(f"float32 rule, ordered={ordered}: loss curve {curve}")
+        assert not np.isfinite(curve[0]), (ordered, curve)
+    res = device_fit(eng, name, max_epochs=epochs, order=order, learning_rate_init=lr)
+    print(f"device: state {res.state}, n_iter {res.n_iter}, loss curve {res.loss_curve}")
+    assert res.state == "nonfinite_loss" and res.n_iter == 1
+    assert res.loss_curve.shape == (1,) and not np.isfinite(res.loss_curve[0])
+    with pytest.raises(ValueError, match="the loss of epoch 1 is not finite"):
+        models.DTW_MLP.fit(np.random.default_rng(0).normal(size=(m, 8)), R["y"], 3, 0.1, refs=np.zeros((F, 8)), distances=np.array(R["D"]),
+                           hidden_layer_sizes=hidden, activation=act, batch_size=batch, max_iter=epochs, random_state=SEED, solver="device",
+                           learning_rate_init=lr)
+    # the context is usable: an ordinary case still meets its contract
+    f = measure(eng, name)
+    assert f["state"] == "max_epochs" and f["device_err"] <= f["T"] and f["device_err_loss"] <= f["T_loss"], f
 
 
 def test_every_refusal_comes_back_before_a_launch(eng):

@@ -70,7 +70,9 @@ def main():
         with open(args.accuracy, "w") as f:
             json.dump(dict(tool="tools/bench_mlp_fit.py --accuracy", device=torch.cuda.get_device_name(0),
                            contract="T = 4 max(E_ref, 2^-24 max|theta|); E_ref = max |scikit-learn float32 - scikit-learn float64|; "
-                                    "ratio_to_e_ref = max |device - scikit-learn float64| / E_ref (the contract allows 4)",
+                                    "ratio_to_e_ref = max |device - scikit-learn float64| / E_ref (the contract allows 4 where E_ref is the "
+                                    "larger term), ratio_to_T the same error / T (the contract allows 1); ratio_loss and ratio_loss_to_T: "
+                                    "the loss curve's; hyper: the case's hyper-parameters beyond scikit-learn's defaults",
                            cases=cases), f, indent=1)
             f.write("\n")
 
