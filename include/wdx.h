@@ -1439,6 +1439,89 @@ int wdx_boost_fit_device(wdx_ctx *ctx, const double *d_X, int64_t n, int64_t ld,
 int wdx_boost_fit(wdx_ctx *ctx, const double *X, int64_t n, int64_t ld, const int32_t *y, const float *borders, const int32_t *n_borders,
                   const wdx_boost_fit_params *p, double *scores, int32_t *split_feature, int32_t *split_border, double *leaf_values);
 
+/* ---- adapter boundary detection: a_start / a_end / ok of every entry above, found on the device --------------------------------
+ * In the reference these come from ADAPTed (combined_detect_llr2 / _cnn / _start_peak, file_proc.py:395-413; the live session's
+ * mean_var_shift_polyA_detect), whose source is not part of the reference tree.  THE RULE below is
+ * the engine's own rule; parity with ADAPTed unpinned; accuracy on real reads unmeasured.
+ * Every quantity is an exact integer except the one float64 expression of step 3, whose operations are single IEEE operations in a
+ * stated order: any summation order gives the same bits.  NumPy
+ * restatement: tests/helpers/detect_rule.py; the kernel (wdx_detect.hip) is held to it with array_equal.
+ *
+ * Thresholds, converted once on the host (float32 products, float32 clamps; a clamp never changes a comparison below, because
+ * q lies in -32768 .. 32767):
+ *   thr1    = (int32)fminf(fmaxf(rintf(open_pore_pa * quant_per_pa), -32768.f), 32768.f)
+ *   shift_q = (int32)fminf(fmaxf(rintf(min_shift_pa * quant_per_pa), -65536.f), 65536.f)
+ *   var_q   = (int64)fmin(fmax(floor(((double)max_polya_var * (double)quant_per_pa) * (double)quant_per_pa), -1.0), 2147483648.0)
+ * Trace of read r:
+ *   n     the number of leading non-NaN samples of the row, capped by the row's length and by max_obs_trace
+ *   v     = x[i] * quant_per_pa                       one float32 multiply
+ *   q[i]  = 32767 if v >= 32767, -32768 if v <= -32768, else (int)rintf(v)      (round half to even)
+ *   P[t]  = sum of q[i], i < t;  P2[t] = sum of q[i]^2, i < t                   (int64, exact)
+ * With sw = start_win, pw = polya_win, tw = step_win:
+ *   1  n < sw + min_obs_adapter + pw: WDX_DETECT_SHORT.
+ *   2  find_start == 0: s = 0.  Otherwise s = the smallest i in 0 .. min(max_start, n - sw) with q[i] < thr1 and
+ *      P[i + sw] - P[i] < thr1 * sw; none: WDX_DETECT_NO_START.
+ *   3  lo = s + min_obs_adapter, hi = min(n - pw, s + max_obs_adapter); lo > hi: WDX_DETECT_NO_ROOM.  For i in lo .. hi, in
+ *      float64 with nothing fused, L = P[i] - P[s], R = P[n] - P[i]:
+ *          g(i) = ((double)L * (double)L) / (double)(i - s) + ((double)R * (double)R) / (double)(n - i)
+ *      c = the i with the largest g, ties to the smallest i.
+ *   4  For j in max(lo, c - refine) .. min(hi, c + refine): S1 = P[j + pw] - P[j], S2 = P2[j + pw] - P2[j], A1 = P[j] - P[s],
+ *      la = j - s.  j qualifies when  pw * S2 - S1 * S1 <= var_q * pw * pw  and  S1 * la - A1 * pw >= shift_q * pw * la.
+ *      e = the qualifying j with the largest D(j) = (P[j + tw] - P[j]) - (P[j] - P[j - tw]), ties to the smallest j; none:
+ *      WDX_DETECT_NO_POLYA.
+ * Outputs per read (all nullable except code):
+ *   a_start int32  s once step 2 has it (NO_ROOM, NO_POLYA, OK), else -1   a_end int32  e on WDX_DETECT_OK, else -1
+ *   ok uint8       1 on WDX_DETECT_OK, else 0                             code int32   WDX_DETECT_*
+ *   info (n_reads, 4) int32 = {n, c, P[e] - P[s], P[e + pw] - P[e]}, -1 where a value is not reached
+ *   gain float64   g(c); where c is not reached the NaN with the bits 0x7FF8000000000000
+ * Domain (WDX_ERR_INVALID outside it, nothing launched or written): 1 <= max_obs_trace <= WDX_DETECT_MAX_TRACE; quant_per_pa > 0;
+ * find_start 0 or 1; 1 <= step_win <= polya_win <= 1024; step_win <= min_obs_adapter <= max_obs_adapter; 1 <= start_win <= 256;
+ * 0 <= refine <= 4096; max_start >= 0; every float finite. */
+#define WDX_DETECT_MAX_TRACE 16384
+#define WDX_DETECT_OK 0
+#define WDX_DETECT_SHORT 1
+#define WDX_DETECT_NO_START 2
+#define WDX_DETECT_NO_ROOM 3
+#define WDX_DETECT_NO_POLYA 4
+typedef struct wdx_detect_params {
+    int32_t max_obs_trace;    /* samples of a row the rule looks at, 1 .. WDX_DETECT_MAX_TRACE                            */
+    float quant_per_pa;       /* integer steps per pA (> 0; 8: steps of 0.125 pA, +-4 096 pA before the clamp)           */
+    int32_t find_start;       /* 0: s = 0; 1: step 2                                                                     */
+    float open_pore_pa;       /* step 2: the adapter starts where the signal has left the open-pore level                */
+    int32_t start_win;        /* step 2: samples of the mean that must lie below open_pore_pa too                        */
+    int32_t max_start;        /* step 2: the last sample the start is looked for at                                      */
+    int32_t min_obs_adapter;  /* step 3: the fewest and the most samples between the start and the adapter's end         */
+    int32_t max_obs_adapter;
+    int32_t polya_win;        /* steps 3 and 4: samples behind the adapter's end that must look like the polyA tail      */
+    int32_t step_win;         /* step 4: samples on either side of the step D(j)                                         */
+    int32_t refine;           /* step 4: candidates on either side of c                                                  */
+    float min_shift_pa;       /* step 4: mean of the polyA window minus mean of the adapter, at least                    */
+    float max_polya_var;      /* step 4: variance of the polyA window (pA^2), at most                                    */
+} wdx_detect_params;
+/* Device-resident float32 rows, in the layouts of wdx_fingerprint_dev (strided; strided with d_row_len, clamped to 0 .. stride;
+ * packed int64 d_row_off[n_reads + 1] with or without d_row_len, clamped to the row's slice).  Nothing beyond
+ * min(row length, max_obs_trace) samples of a row is read.  Outputs DEVICE arrays as stated above.  detect_kernel, one wave per
+ * read: the row quantised once into 2 * max_obs_trace bytes of LDS, every step on it.  Enqueued on `stream`; no synchronisation,
+ * no allocation.  n_reads == 0 is success and writes nothing.  Timed as WDX_K_DETECT. */
+int wdx_detect_rows(wdx_ctx *ctx, const float *d_sig, const int64_t *d_row_off, const int32_t *d_row_len, int64_t stride,
+                    int64_t n_reads, const wdx_detect_params *params, int32_t *d_a_start, int32_t *d_a_end, uint8_t *d_ok,
+                    int32_t *d_code, int32_t *d_info, double *d_gain, void *stream);
+/* The same on an int16 shard that stays in device memory (wdx_adc_dev_in and its contract, above; row_win plays no part: the rule
+ * ends at the first NaN).  Bit-identical to wdx_detect_rows on the calibrated rows.  There is no float32 staging block: the kernel
+ * calibrates and quantises as it loads. */
+int wdx_detect_rows_adc(wdx_ctx *ctx, const wdx_adc_dev_in *in, int64_t n_reads, const wdx_detect_params *params,
+                        int32_t *d_a_start, int32_t *d_a_end, uint8_t *d_ok, int32_t *d_code, int32_t *d_info, double *d_gain,
+                        void *stream);
+/* Blocking host-buffer forms on the context's own stream: sig (n_reads, stride) float32 with a NaN tail and row_len (nullable)
+ * int32[n_reads]; adc (n_reads, stride) int16 with row_len, offset, scale [n_reads] REQUIRED.  The rows are copied up, the call
+ * above is made, the outputs (HOST arrays, nullable as above) are copied down.  One synchronisation. */
+int wdx_detect_batch(wdx_ctx *ctx, const float *sig, int64_t n_reads, int64_t stride, const int32_t *row_len,
+                     const wdx_detect_params *params, int32_t *a_start, int32_t *a_end, uint8_t *ok, int32_t *code, int32_t *info,
+                     double *gain);
+int wdx_detect_batch_adc(wdx_ctx *ctx, const int16_t *adc, int64_t n_reads, int64_t stride, const int32_t *row_len,
+                         const float *offset, const float *scale, const wdx_detect_params *params, int32_t *a_start,
+                         int32_t *a_end, uint8_t *ok, int32_t *code, int32_t *info, double *gain);
+
 /* ---- multi-GPU: the only exchange on the path ---------------------------------------
  * Reads shard over one process per GPU with no data-path collective; after the last batch the per-barcode
  * call histogram -- the engine's form of the reference's shared run counters `ridx_dict`
@@ -1494,6 +1577,7 @@ int wdx_reduce_counts_host(wdx_ctx *ctx, int64_t *counts, int32_t n);
 #define WDX_K_SVM_KERNEL 18       /* the kernel matrix of wdx_svm_kernel_device: its one launch */
 #define WDX_K_SVM_CV_COUPLE 20    /* the out-of-fold probabilities of wdx_svm_cv_couple_device: its one launch */
 #define WDX_K_THRESHOLDS 19       /* wdx_accuracy_thresholds_device / wdx_accuracy_thresholds: one event pair around the histogram pass and the selection (n == 0: the selection alone) */
+#define WDX_K_DETECT 21           /* detect_kernel (wdx_detect_rows, wdx_detect_rows_adc and the host-buffer forms): its one launch */
 /* When enabled, every kernel launch through this context is bracketed by hipEvents on its
  * stream; wdx_kernel_time() synchronises them and returns accumulated ms and launch count. */
 int wdx_kernel_timing(wdx_ctx *ctx, int enable);

@@ -37,6 +37,7 @@ K_BOOST_FIT = 17          # the Fpt_Boost trainer (wdx_boost_fit_device, wdx_boo
 K_SVM_KERNEL = 18         # the kernel matrix of wdx_svm_kernel_device: its one launch
 K_SVM_CV_COUPLE = 20      # the out-of-fold probabilities of wdx_svm_cv_couple_device: its one launch
 K_THRESHOLDS = 19         # accuracy thresholds (wdx_accuracy_thresholds_device, wdx_accuracy_thresholds): the histogram pass and the selection
+K_DETECT = 21             # adapter boundary detection (wdx_detect_rows, wdx_detect_rows_adc and the host-buffer forms): its one launch
 
 # wdx_ctx_set_option selectors (diagnostics; the product path leaves all of them 0)
 OPT_EXACT_PATH, OPT_NO_WAVEFRONT_DTW, OPT_NO_SHORT_DTW, OPT_SVM_SCALAR, OPT_DEBUG_OCCUPANCY, OPT_FAST_PEAK_CAP = 1, 2, 3, 4, 5, 6
@@ -112,6 +113,7 @@ EXPORTS = [
     "wdx_boost_fit_device", "wdx_boost_fit",
     "wdx_svm_kernel_device", "wdx_svm_cv_couple_device",
     "wdx_accuracy_thresholds_device", "wdx_accuracy_thresholds",
+    "wdx_detect_rows", "wdx_detect_rows_adc", "wdx_detect_batch", "wdx_detect_batch_adc",
 ]
 
 
@@ -291,6 +293,21 @@ class AdcDevInC(C.Structure):
     _fields_ = [
         ("adc", C.c_void_p), ("row_off", C.c_void_p), ("stride", C.c_int64), ("row_len", C.c_void_p), ("offset", C.c_void_p),
         ("scale", C.c_void_p), ("row_win", C.c_void_p),
+    ]
+
+
+DETECT_MAX_TRACE = 16384   # WDX_DETECT_MAX_TRACE
+DETECT_OK, DETECT_SHORT, DETECT_NO_START, DETECT_NO_ROOM, DETECT_NO_POLYA = 0, 1, 2, 3, 4   # WDX_DETECT_*
+
+
+class DetectParamsC(C.Structure):
+    """wdx_detect_params (include/wdx.h)"""
+
+    _fields_ = [
+        ("max_obs_trace", C.c_int32), ("quant_per_pa", C.c_float), ("find_start", C.c_int32), ("open_pore_pa", C.c_float),
+        ("start_win", C.c_int32), ("max_start", C.c_int32), ("min_obs_adapter", C.c_int32), ("max_obs_adapter", C.c_int32),
+        ("polya_win", C.c_int32), ("step_win", C.c_int32), ("refine", C.c_int32), ("min_shift_pa", C.c_float),
+        ("max_polya_var", C.c_float),
     ]
 
 
@@ -654,6 +671,14 @@ def load():
         L.wdx_accuracy_thresholds_device.argtypes = [vp, vp, i64, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.wdx_accuracy_thresholds.restype = C.c_int
         L.wdx_accuracy_thresholds.argtypes = [vp, vp, i64, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
+        L.wdx_detect_rows.restype = C.c_int
+        L.wdx_detect_rows.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_detect_rows_adc.restype = C.c_int
+        L.wdx_detect_rows_adc.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_detect_batch.restype = C.c_int
+        L.wdx_detect_batch.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.wdx_detect_batch_adc.restype = C.c_int
+        L.wdx_detect_batch_adc.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
         return L
 

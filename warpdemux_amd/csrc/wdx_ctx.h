@@ -43,7 +43,7 @@ struct PinnedBuffer {  // grow-only page-locked host staging area
     void release();
 };
 
-constexpr int kNumTimed = 21;
+constexpr int kNumTimed = 22;
 
 struct MedoidStage {   // a page-locked block and the event behind the latest copy out of it
     void *host = nullptr;

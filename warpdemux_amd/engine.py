@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib, _marshal, _medoids, _nearest, synth
-from .sig_proc import SegParams
+from .sig_proc import DetectParams, SegParams
 
 
 def _torch():
@@ -103,6 +103,16 @@ class DemuxResult:
     status: "object"    # torch int32 (n,)  WDX_READ_*
     counts: "object"    # torch int64 (nY+1,) accumulated call histogram (slot nY = failed)
     fpt: Optional["object"] = None   # torch float64 (n, K) when requested
+
+
+@dataclass
+class DetectResult:
+    a_start: "object"   # torch int32 (n,)  adapter start, -1 where none was found
+    a_end: "object"     # torch int32 (n,)  adapter end, -1 unless the read succeeded
+    ok: "object"        # torch uint8 (n,)
+    code: "object"      # torch int32 (n,)  WDX_DETECT_*
+    info: Optional["object"] = None   # torch int32 (n, 4) when requested: {n, c, P[e] - P[s], P[e + polya_win] - P[e]}
+    gain: Optional["object"] = None   # torch float64 (n,) when requested: g(c)
 
 
 @dataclass
@@ -261,6 +271,52 @@ class DemuxEngine:
             _dp(a_start), _dp(a_end), _dp(ok), C.byref(pc), _dp(out.fpt), None, None,
             _dp(out.status), _dp(out.dist), _dp(out.call), _dp(out.counts), _dp(self._work_for(sig, n, max_len, self.K, False)),
             self._stream()))
+        return out
+
+    # -- boundary detection ahead of every entry ----------------------------------------------------
+    def detect(self, sig, *, offsets=None, stride=0, row_len=None, params: Optional[DetectParams] = None,
+               want_info: bool = False) -> DetectResult:
+        """Adapter boundaries of device-resident reads (wdx_detect_rows; an `AdcShard`: wdx_detect_rows_adc, bit-identical on
+        the calibrated rows): float32 ``sig`` as a (n, stride) minibatch with a NaN tail (``stride`` defaults to its second
+        dimension), with int32 ``row_len`` (n,), or packed with int64 ``offsets`` of n + 1 entries.  The result's tensors go
+        straight into `demux` and its kin: ``d = eng.detect(sig); eng.demux(sig, d.a_start, d.a_end, ok=d.ok, ...)``.
+        The engine's own rule; parity with ADAPTed unpinned; accuracy on real reads unmeasured.  Enqueues on the current stream."""
+        torch = self.torch
+        pc = (params or DetectParams()).to_c()
+        if isinstance(sig, AdcShard):
+            if offsets is not None or stride or row_len is not None:
+                raise ValueError("an AdcShard carries its own offsets / stride / row_len")
+            n = sig.n_reads
+        else:
+            if sig.dtype != torch.float32 or not sig.is_contiguous() or not sig.is_cuda:
+                raise ValueError("sig must be a contiguous float32 device tensor (or an AdcShard)")
+            if offsets is not None:
+                # (the kernel reads n + 1 int64 entries at this address)
+                if (offsets.dtype != torch.int64 or offsets.dim() != 1 or int(offsets.numel()) < 1 or not offsets.is_contiguous()
+                        or not offsets.is_cuda):
+                    raise ValueError("offsets must be a contiguous int64 device tensor of n + 1 entries")
+                n = int(offsets.shape[0]) - 1
+            else:
+                if not stride:
+                    if sig.dim() != 2:
+                        raise ValueError("packed reads need `offsets`, strided ones a 2-D `sig` or `stride`")
+                    stride = int(sig.shape[1])
+                n = int(sig.numel()) // int(stride) if sig.dim() != 2 else int(sig.shape[0])
+                if int(sig.numel()) < n * int(stride):
+                    raise ValueError(f"sig holds {int(sig.numel())} samples, {n} rows of {stride} need more")
+            if row_len is not None and (row_len.dtype != torch.int32 or tuple(row_len.shape) != (n,) or not row_len.is_cuda):
+                raise ValueError("row_len must be an int32 device tensor with one entry per read")
+        out = DetectResult(
+            a_start=torch.empty(n, dtype=torch.int32, device=self.tdev), a_end=torch.empty(n, dtype=torch.int32, device=self.tdev),
+            ok=torch.empty(n, dtype=torch.uint8, device=self.tdev), code=torch.empty(n, dtype=torch.int32, device=self.tdev),
+            info=torch.empty((n, 4), dtype=torch.int32, device=self.tdev) if want_info else None,
+            gain=torch.empty(n, dtype=torch.float64, device=self.tdev) if want_info else None)
+        outs = (_dp(out.a_start), _dp(out.a_end), _dp(out.ok), _dp(out.code), _dp(out.info), _dp(out.gain), self._stream())
+        if isinstance(sig, AdcShard):
+            desc = sig.to_c()
+            _lib.check(self.L.wdx_detect_rows_adc(self.ctx.handle, C.byref(desc), n, C.byref(pc), *outs))
+        else:
+            _lib.check(self.L.wdx_detect_rows(self.ctx.handle, _dp(sig), _dp(offsets), _dp(row_len), int(stride), n, C.byref(pc), *outs))
         return out
 
     def fingerprint(self, sig, a_start, a_end, *, offsets=None, stride=0, max_len: int, ok=None, want_stats: bool = True):

@@ -176,6 +176,144 @@ class DetectResults:
     adapter_end: Optional[int] = None
 
 
+# WDX_DETECT_* code -> DetectResults.fail_reason.  The strings are the engine's own, like the rule (include/wdx.h: the engine's
+# own rule; parity with ADAPTed unpinned; accuracy on real reads unmeasured).
+DETECT_FAIL_REASONS = {
+    0: "",
+    1: "trace too short for an adapter and a polyA window",
+    2: "no adapter start below the open-pore level",
+    3: "no room for an adapter end behind the start",
+    4: "no polyA-like window behind the adapter",
+}
+
+
+@dataclass
+class DetectParams:
+    """wdx_detect_params (include/wdx.h states the rule bit for bit and the domain): the engine's own boundary detection ahead of
+    every entry that takes ``a_start`` / ``a_end`` / ``ok``.  The defaults are the values the rule was prototyped with on
+    synthetic RNA004-like traces; accuracy on real reads is unmeasured."""
+
+    max_obs_trace: int = 10000
+    quant_per_pa: float = 8.0
+    find_start: bool = True
+    open_pore_pa: float = 150.0
+    start_win: int = 32
+    max_start: int = 2000
+    min_obs_adapter: int = 1000
+    max_obs_adapter: int = 8000
+    polya_win: int = 200
+    step_win: int = 8
+    refine: int = 300
+    min_shift_pa: float = 8.0
+    max_polya_var: float = 9.0
+
+    def to_c(self) -> "_lib.DetectParamsC":
+        """The C structure, after the domain check the library makes too (``ValueError``)."""
+        ints = ("max_obs_trace", "start_win", "max_start", "min_obs_adapter", "max_obs_adapter", "polya_win", "step_win", "refine")
+        for name in ints:
+            v = getattr(self, name)
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not -2**31 <= int(v) < 2**31:
+                raise ValueError(f"DetectParams.{name} must be an int32")
+        with np.errstate(over="ignore"):   # (a value beyond float32 becomes infinite and is refused below)
+            floats = [np.float32(getattr(self, name)) for name in ("quant_per_pa", "open_pore_pa", "min_shift_pa", "max_polya_var")]
+        if not all(np.isfinite(f) for f in floats):
+            raise ValueError("DetectParams: quant_per_pa, open_pore_pa, min_shift_pa and max_polya_var must be finite float32")
+        if not 1 <= self.max_obs_trace <= _lib.DETECT_MAX_TRACE:
+            raise ValueError(f"DetectParams.max_obs_trace = {self.max_obs_trace} (1..{_lib.DETECT_MAX_TRACE})")
+        if not floats[0] > 0:
+            raise ValueError(f"DetectParams.quant_per_pa = {self.quant_per_pa} must be positive")
+        if self.find_start not in (0, 1):
+            raise ValueError("DetectParams.find_start is 0 / 1")
+        if not 1 <= self.step_win <= self.polya_win <= 1024:
+            raise ValueError("DetectParams: 1 <= step_win <= polya_win <= 1024")
+        if not self.step_win <= self.min_obs_adapter <= self.max_obs_adapter:
+            raise ValueError("DetectParams: step_win <= min_obs_adapter <= max_obs_adapter")
+        if not 1 <= self.start_win <= 256:
+            raise ValueError("DetectParams: 1 <= start_win <= 256")
+        if not 0 <= self.refine <= 4096:
+            raise ValueError("DetectParams: 0 <= refine <= 4096")
+        if self.max_start < 0:
+            raise ValueError("DetectParams.max_start must not be negative")
+        return _lib.DetectParamsC(int(self.max_obs_trace), float(floats[0]), int(self.find_start), float(floats[1]),
+                                  int(self.start_win), int(self.max_start), int(self.min_obs_adapter), int(self.max_obs_adapter),
+                                  int(self.polya_win), int(self.step_win), int(self.refine), float(floats[2]), float(floats[3]))
+
+
+@dataclass
+class DetectBatch:
+    """Struct-of-arrays result of the boundary detection on one minibatch (include/wdx.h: the outputs per read)."""
+
+    a_start: np.ndarray   # (n,) int32, -1 where no start was found
+    a_end: np.ndarray     # (n,) int32, -1 unless the read succeeded
+    ok: np.ndarray        # (n,) uint8
+    code: np.ndarray      # (n,) int32 WDX_DETECT_*
+    info: np.ndarray      # (n, 4) int32 {n, c, P[e] - P[s], P[e + polya_win] - P[e]}
+    gain: np.ndarray      # (n,) float64 g(c)
+
+    def results(self) -> List["DetectResults"]:
+        """one `DetectResults` per read, as the fingerprint shims take them"""
+        return [DetectResults(success=bool(self.ok[i]), fail_reason=DETECT_FAIL_REASONS[int(self.code[i])],
+                              adapter_start=int(self.a_start[i]) if self.a_start[i] >= 0 else None,
+                              adapter_end=int(self.a_end[i]) if self.a_end[i] >= 0 else None) for i in range(len(self.code))]
+
+
+def _detect_outputs(n):
+    return DetectBatch(np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.uint8), np.empty(n, np.int32),
+                       np.empty((n, 4), np.int32), np.empty(n, np.float64))
+
+
+def _detect_row_len(row_len, n, stride, required):
+    if row_len is None:
+        if required:
+            raise ValueError("row_len is required for int16 rows (there is no NaN tail to find the end by)")
+        return None
+    row_len = np.ascontiguousarray(row_len, dtype=np.int32)
+    if row_len.shape != (n,):
+        raise ValueError("row_len must have one entry per read")
+    return row_len
+
+
+def detect_batch_arrays(signals, params: Optional[DetectParams] = None, row_len=None, device=None) -> DetectBatch:
+    """Boundary detection on a (n_reads, stride) float32 minibatch with a NaN tail (wdx_detect_batch): the arrays."""
+    sig = np.ascontiguousarray(signals, dtype=np.float32)
+    if sig.ndim != 2:
+        raise ValueError("signals must be a 2-D (n_reads, stride) array")
+    n, stride = sig.shape
+    pc = (params or DetectParams()).to_c()
+    row_len = _detect_row_len(row_len, n, stride, False)
+    o = _detect_outputs(n)
+    _lib.check(_lib.load().wdx_detect_batch(
+        _lib.default_context(device).handle, _lib.ptr(sig), n, stride, _lib.ptr(row_len), C.byref(pc), _lib.ptr(o.a_start),
+        _lib.ptr(o.a_end), _lib.ptr(o.ok), _lib.ptr(o.code), _lib.ptr(o.info), _lib.ptr(o.gain)))
+    return o
+
+
+def detect_batch(signals, params: Optional[DetectParams] = None, row_len=None, device=None) -> List[DetectResults]:
+    """The module-level, host-fed boundary detection: one `DetectResults` per row of a (n_reads, stride) float32 minibatch --
+    what `detect_results_to_fpt_batch` takes.  The engine's own rule; parity with ADAPTed unpinned; accuracy on real reads
+    unmeasured."""
+    return detect_batch_arrays(signals, params, row_len, device).results()
+
+
+def detect_batch_adc(adc, row_len, offset, scale, params: Optional[DetectParams] = None, device=None) -> DetectBatch:
+    """`detect_batch_arrays` for a (n_reads, stride) int16 ADC minibatch (wdx_detect_batch_adc); bit-identical to it on
+    ``calibrate_adc(adc, row_len, offset, scale)``."""
+    adc = np.asarray(adc)
+    if adc.ndim != 2 or adc.dtype != np.int16 or not adc.flags.c_contiguous:
+        raise ValueError("adc must be a C-contiguous 2-D (n_reads, stride) int16 array")
+    n, stride = adc.shape
+    row_len = _detect_row_len(row_len, n, stride, True)
+    off, sc = np.ascontiguousarray(offset, dtype=np.float32), np.ascontiguousarray(scale, dtype=np.float32)
+    if off.shape != (n,) or sc.shape != (n,):
+        raise ValueError("offset and scale must have one entry per read")
+    pc = (params or DetectParams()).to_c()
+    o = _detect_outputs(n)
+    _lib.check(_lib.load().wdx_detect_batch_adc(
+        _lib.default_context(device).handle, _lib.ptr(adc), n, stride, _lib.ptr(row_len), _lib.ptr(off), _lib.ptr(sc), C.byref(pc),
+        _lib.ptr(o.a_start), _lib.ptr(o.a_end), _lib.ptr(o.ok), _lib.ptr(o.code), _lib.ptr(o.info), _lib.ptr(o.gain)))
+    return o
+
+
 @dataclass
 class ReadResult:
     """Same fields as warpdemux.sig_proc.ReadResult (sig_proc.py:26-62)."""
